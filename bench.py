@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decode tok/s + %HBM-roofline, Llama-3.2-1B Q8_0 greedy decode on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one decode step (one token through the whole hot path: embedding row, 16 decoder layers,
@@ -11,12 +11,18 @@ quantiser), a 16-token synthetic prompt (= the W warm-up steps by default) and t
 Weights, KV cache and every activation are resident in HBM when the timed region starts; token ids never
 leave the device between steps.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run does only what the headline needs: build the image, warm up, time the K steps, print the line
+(`value` tok/s, `ms_per_step`).  --dump-outputs DIR also writes what the timed call returned, the K greedy
+token ids, as DIR/tokens.npy (float64; the inputs are seeded, so two builds can be compared id for id).
+Everything else - the objects below, `value_128_steps`, and at N > 1 the further shard configurations - is
+measured only with --full; without it those keys are null.
+
+Extra objects on that line (--full):
   roofline      the dominant kernel family (the fused Q8_0 dequant-GEMV, lmrs::gemv_static_kernel<...>): algorithmic
                 bytes (int8 weights + f32 group scales) of one decode step's 65 GEMV launches / their summed
                 durations AS THEY RUN INSIDE THE STEP: the real step (same launches as the captured graph, live
                 activations and positions) is replayed eagerly with a HIP event pair on every dispatch
-                (lmrs_bench_step), against the 8 TB/s HBM3E peak; `frac_vs_measured_copy` prices the same figure
+                (lmrs_bench_step; below the split-attention switch only: past it, from `in_step_from_pos`), against the 8 TB/s HBM3E peak; `frac_vs_measured_copy` prices the same figure
                 against the 6.29 TB/s the chip sustains on a device copy.  `in_step` lists every kernel of the step
                 (attention and argmax included).  `achieved` / `frac` are the WHOLE-STEP figure (SURVEY.md §8d bytes
                 per token / measured time per token, = `path`); the family's own figure on its event durations,
@@ -184,9 +190,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--model", default="llama-3.2-1b")
     ap.add_argument("--qtype", default="q8_0", choices=["q8_0", "q4_0"], help="weight quantisation of the synthetic image (config 3: gemma-2-2b q4_0)")
-    ap.add_argument("--cpu-steps", type=int, default=-1, help="oracle steps for cpu_baseline (-1: same as the GPU run, 0: skip)")
+    ap.add_argument("--cpu-steps", type=int, default=-1, help="oracle steps for cpu_baseline with --full (-1: same as the GPU run, 0: skip)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--vision", action="store_true", help="BASELINE configs[4] (use with --model phi-3.5): add a `vision` object - CLIP tower, projector, fill_kv_cache(320)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: roofline, cpu_baseline + parity, prefill, "
+                                                         "value_128_steps, and at N > 1 the library's own plan and the split-out plan")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the token ids the timed call returned as DIR/tokens.npy (float64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -255,9 +264,10 @@ def main():
     prompt = S.prompt_tokens(cfg, W, 1234)
     t_build = time.time() - t0
 
-    def run_once(plan=None, transport_override=None, emit=True):
+    def run_once(plan=None, transport_override=None, emit=True, dump_dir=None):
         """One configuration of the job: build the context(s), warm up, time K steps, report.  plan: None = the library's own choice
-        (LMRS_SHARD_PLAN if the caller set it), "tp" / "cls" = forced for this run; transport_override: "rccl" / "p2p"."""
+        (LMRS_SHARD_PLAN if the caller set it), "tp" / "cls" = forced for this run; transport_override: "rccl" / "p2p";
+        dump_dir: rank 0 writes the timed call's token ids there."""
         if plan is not None:
             os.environ["LMRS_SHARD_PLAN"] = plan
         # N > 1: ONE decode stream, weight matrices row-split over the N GPUs (one process per GPU), RCCL all-gathers
@@ -338,10 +348,13 @@ def main():
             res = timed_run(model)
             attempts.append({"wall_us_per_step": round(res[3] / K * 1e6, 2), "device_us_per_step": round(res[2] / K * 1e6, 2)})
         first, toks, dev_sec, wall = res
+        if dump_dir and rank == 0:
+            os.makedirs(dump_dir, exist_ok=True)
+            np.save(os.path.join(dump_dir, "tokens.npy"), toks.astype(np.float64))     # (uint32 ids: exact in float64)
         # the driver times few steps at the very first positions; the figure over the full 128-token generate of BASELINE.json's configs
         # (positions W .. W+127: longer contexts, a run long enough to be immune to start-up noise) rides along when K differs
         v128 = None
-        if not sharded and K != 128 and W + 128 <= 8192:
+        if args.full and not sharded and K != 128 and W + 128 <= 8192:
             first128 = model.generate_greedy(prompt, 1)
             device_sync()
             t1 = time.perf_counter(); model.generate_greedy(first128, 128, start_pos=W); device_sync()
@@ -350,11 +363,24 @@ def main():
             del res2
         elapsed = max_over_ranks(dist, wall, ("cpu" if dist.get_backend() == "gloo" else "cuda") if dist is not None else None)
         gen = np.concatenate([first, toks])[: K + 1]          # token ids produced after positions W-1 .. W+K-1
+
+        def replay_pos(iters):
+            """First position of the per-kernel replay (lmrs_bench_step, which continues decoding from the context's state).  It replays the
+            step below the split-attention switch only (LMRS_ATT_SPLIT_POS, default 384, 0: never - INTEGRATION.md): the live position W+K
+            when the replay fits below it, else the context is re-fed the first positions of the same token sequence (prompt, then the greedy
+            tokens) and the replay starts at the last position that fits.  Every rank of a sharded context calls it."""
+            split_pos = int(os.environ.get("LMRS_ATT_SPLIT_POS", "384"))
+            if split_pos <= 0 or W + K + iters + 1 <= split_pos:
+                return W + K
+            p = max(1, split_pos - iters - 1)
+            model.generate_greedy(np.concatenate([prompt, gen])[:p], 1)
+            return p
+
         shard_steps = None
-        if sharded:
+        if sharded and args.full:
             # per-kernel / per-exchange durations inside the sharded step (every rank takes part: the exchanges wait for the peers)
             try:
-                shard_steps = model.bench_step(W + K, 8)
+                shard_steps = model.bench_step(replay_pos(8), 8)
             except Exception as e:                          # noqa: BLE001
                 print(f"[rank {rank}] bench_step: {e}", file=sys.stderr)
             barrier()
@@ -362,77 +388,81 @@ def main():
         out = None
         if rank == 0:
             tok_s = K / elapsed                      # one decode stream, whatever the number of GPUs
-            # whole-path bytes over the timed positions
-            path_bytes = sum(model.step_info(p)[1] for p in range(W, W + K))
-            n_launch = model.step_info(W)[0]
-            # ---- dominant kernel: per-shape live timing with HIP events
-            path = {"bytes_per_step": round(path_bytes / K), "us_per_step": round(elapsed / K * 1e6, 2),
-                    "achieved": round(path_bytes / elapsed / 1e9, 1), "frac": round(path_bytes / elapsed / 1e9 / (HBM_PEAK_GBPS * world), 4),
-                    "kernel_launches_per_step": n_launch, "device_event_us_per_step": round(dev_sec / K * 1e6, 2)}
-            if sharded:
-                # where a sharded step goes - streaming kernels, glue, exchanges, and what is left (launch gaps)
-                split = None
-                if shard_steps:
-                    iters = 8
-                    per = {k: {"us": round(us / n, 3), "launches_per_step": n // iters} for k, (us, _b, n) in shard_steps.items()}
-                    stream_us = sum(us for k, (us, _b, n) in shard_steps.items() if k not in ("exchange", "glue")) / iters
-                    glue_us = shard_steps.get("glue", (0.0, 0, 0))[0] / iters
-                    ex_us = shard_steps.get("exchange", (0.0, 0, 0))[0] / iters
-                    gemv_b = sum(_b for k, (us, _b, n) in shard_steps.items() if k in ("qkv", "wo", "w1w3", "w2", "classifier")) / iters
-                    gemv_us = sum(us for k, (us, _b, n) in shard_steps.items() if k in ("qkv", "wo", "w1w3", "w2", "classifier")) / iters
-                    split = {"stream_us": round(stream_us, 2), "glue_us": round(glue_us, 2),
-                             "exchange_us": round(ex_us, 2) if transport == "p2p" else None,
-                             "gap_us": round(elapsed / K * 1e6 - stream_us - glue_us - (ex_us if transport == "p2p" else 0.0), 2),
-                             "gemv_GBps_this_rank": round(gemv_b / gemv_us / 1e3, 1) if gemv_us else None, "kernels": per,
-                             "note": "rank 0's eager replay of the real step with an event pair per dispatch; a dispatch's duration includes its launch boundary; "
-                                     "exchange_us includes waiting for the slowest peer; with RCCL the collectives carry no events and sit in gap_us"}
-                # weight bytes the job streams per step beyond ONE copy of the model (replicated matrices are read by every GPU): `frac` prices
-                # the single-copy bytes against N x 8 TB/s, so it is a scaling figure, not a streaming efficiency, whenever this is not 0
-                pl = lmrs_amd.shard_plan(model.args, 0, world)
-                a_ = model.args; scb = (1.0 if args.qtype == "q8_0" else 0.5) + 4.0 / 128
-                att_f = a_.n_heads * a_.head_size; kv_f = a_.n_kv_heads * a_.head_size
-                one = a_.n_layers * (a_.dim * (att_f + 2 * kv_f) + att_f * a_.dim + 3 * a_.dim * a_.hidden_dim) * scb + a_.vocab_size * a_.dim * scb
-                per_gpu = a_.n_layers * (a_.dim * (pl["q_heads"][1] + 2 * pl["kv_heads"][1]) * a_.head_size + att_f * pl["dim_rows"][1]
-                                         + 2 * a_.dim * pl["hidden_pairs"][1] + a_.hidden_dim * pl["dim_rows"][1]) * scb + pl["vocab_rows"][1] * a_.dim * scb
-                redundant = int(round(world * per_gpu - one))
-                roofline = {"bound": "hbm", "kernel": "whole sharded step", "achieved": path["achieved"], "redundant_bytes_per_step": redundant,
-                            "bytes_streamed_per_gpu_per_step": int(round(per_gpu)),
-                            "peak": HBM_PEAK_GBPS * world, "unit": "GB/s", "frac": path["frac"], "traffic": None, "path": path,
-                            "transport": transport, "sharded_step_is_one_hipgraph": model.shard_uses_graph(), "step_split": split}
-            else:
-              # the real step, replayed eagerly from the live state with an event pair on every dispatch: each kernel's
-              # duration as it runs inside the step (real predecessor, real activations, positions W+K+1 ...)
-              iters = 8
-              res = model.bench_step(W + K, iters)
-              per, tot_us, tot_b, n_gemv, step_us = {}, 0.0, 0.0, 0, 0.0
-              for name, (us, b, n) in res.items():
-                per[name] = {"us": round(us / n, 3), "MB": round(b / n / 1e6, 3), "GBps": round(b / us / 1e3, 1), "launches_per_step": n // iters}
-                step_us += us / iters
-                if name not in ("attention", "argmax"):
-                  tot_us += us / iters; tot_b += b / iters; n_gemv += n // iters
-              achieved = tot_b / tot_us / 1e3            # GB/s
-              rp_us = rocprof_family_us(cfg.name, args.qtype)
-              roofline = {
-                "bound": "hbm", "kernel": "lmrs::gemv_static_kernel / gemv_kernel / qkv_attn_kernel (fused dequant-GEMV, all shapes of one step; the qkv launch includes the attention workgroups merged into it, the classifier the folded argmax), durations taken inside the real step",
-                # `achieved` / `frac`: the WHOLE timed step (SURVEY.md section 8d bytes per token / measured time per token = path.frac: gaps between the
-                # launches included); `family_*`: the GEMV family alone on its in-step event durations (it excludes the gaps: 1.5 points higher)
-                "achieved": path["achieved"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": path["frac"],
-                "family_achieved": round(achieved, 1), "family_frac": round(achieved / HBM_PEAK_GBPS, 4),
-                "frac_vs_measured_copy": round(path["achieved"] / MEASURED_COPY_GBPS, 4),
-                # the same bytes over rocprofv3's average durations of the same kernels (committed summary of this build, else null).  A LOWER
-                # BOUND, not a second measurement of kernel time: under graph replay the profiler's per-dispatch intervals include each launch's
-                # boundary and overlap their neighbours' - their sum exceeds the timed step itself (round 3: 471 us of "kernels" in a 424 us step)
-                "frac_rocprof": round(tot_b / rp_us / 1e3 / HBM_PEAK_GBPS, 4) if rp_us else None,
-                "frac_rocprof_is": "lower bound (profiler intervals overlap at launch boundaries; see path.frac for the timed step)",
-                "traffic": pmc_traffic(cfg.name, args.qtype),
-                "bytes_per_launch_avg": round(tot_b / n_gemv), "avg_launch_us": round(tot_us / n_gemv, 3), "launches_per_step": n_gemv,
-                "in_step": per, "sum_of_kernel_us_per_step": round(step_us, 2), "kernel_source_hash": kernel_source_hash(),
-                "path": path,
-              }
+            roofline = None
+            if args.full:
+                # whole-path bytes over the timed positions
+                path_bytes = sum(model.step_info(p)[1] for p in range(W, W + K))
+                n_launch = model.step_info(W)[0]
+                # ---- dominant kernel: per-shape live timing with HIP events
+                path = {"bytes_per_step": round(path_bytes / K), "us_per_step": round(elapsed / K * 1e6, 2),
+                        "achieved": round(path_bytes / elapsed / 1e9, 1), "frac": round(path_bytes / elapsed / 1e9 / (HBM_PEAK_GBPS * world), 4),
+                        "kernel_launches_per_step": n_launch, "device_event_us_per_step": round(dev_sec / K * 1e6, 2)}
+                if sharded:
+                    # where a sharded step goes - streaming kernels, glue, exchanges, and what is left (launch gaps)
+                    split = None
+                    if shard_steps:
+                        iters = 8
+                        per = {k: {"us": round(us / n, 3), "launches_per_step": n // iters} for k, (us, _b, n) in shard_steps.items()}
+                        stream_us = sum(us for k, (us, _b, n) in shard_steps.items() if k not in ("exchange", "glue")) / iters
+                        glue_us = shard_steps.get("glue", (0.0, 0, 0))[0] / iters
+                        ex_us = shard_steps.get("exchange", (0.0, 0, 0))[0] / iters
+                        gemv_b = sum(_b for k, (us, _b, n) in shard_steps.items() if k in ("qkv", "wo", "w1w3", "w2", "classifier")) / iters
+                        gemv_us = sum(us for k, (us, _b, n) in shard_steps.items() if k in ("qkv", "wo", "w1w3", "w2", "classifier")) / iters
+                        split = {"stream_us": round(stream_us, 2), "glue_us": round(glue_us, 2),
+                                 "exchange_us": round(ex_us, 2) if transport == "p2p" else None,
+                                 "gap_us": round(elapsed / K * 1e6 - stream_us - glue_us - (ex_us if transport == "p2p" else 0.0), 2),
+                                 "gemv_GBps_this_rank": round(gemv_b / gemv_us / 1e3, 1) if gemv_us else None, "kernels": per,
+                                 "note": "rank 0's eager replay of the real step with an event pair per dispatch; a dispatch's duration includes its launch boundary; "
+                                         "exchange_us includes waiting for the slowest peer; with RCCL the collectives carry no events and sit in gap_us"}
+                    # weight bytes the job streams per step beyond ONE copy of the model (replicated matrices are read by every GPU): `frac` prices
+                    # the single-copy bytes against N x 8 TB/s, so it is a scaling figure, not a streaming efficiency, whenever this is not 0
+                    pl = lmrs_amd.shard_plan(model.args, 0, world)
+                    a_ = model.args; scb = (1.0 if args.qtype == "q8_0" else 0.5) + 4.0 / 128
+                    att_f = a_.n_heads * a_.head_size; kv_f = a_.n_kv_heads * a_.head_size
+                    one = a_.n_layers * (a_.dim * (att_f + 2 * kv_f) + att_f * a_.dim + 3 * a_.dim * a_.hidden_dim) * scb + a_.vocab_size * a_.dim * scb
+                    per_gpu = a_.n_layers * (a_.dim * (pl["q_heads"][1] + 2 * pl["kv_heads"][1]) * a_.head_size + att_f * pl["dim_rows"][1]
+                                             + 2 * a_.dim * pl["hidden_pairs"][1] + a_.hidden_dim * pl["dim_rows"][1]) * scb + pl["vocab_rows"][1] * a_.dim * scb
+                    redundant = int(round(world * per_gpu - one))
+                    roofline = {"bound": "hbm", "kernel": "whole sharded step", "achieved": path["achieved"], "redundant_bytes_per_step": redundant,
+                                "bytes_streamed_per_gpu_per_step": int(round(per_gpu)),
+                                "peak": HBM_PEAK_GBPS * world, "unit": "GB/s", "frac": path["frac"], "traffic": None, "path": path,
+                                "transport": transport, "sharded_step_is_one_hipgraph": model.shard_uses_graph(), "step_split": split}
+                else:
+                  # the real step, replayed eagerly from the live state with an event pair on every dispatch: each kernel's
+                  # duration as it runs inside the step (real predecessor, real activations, positions W+K+1 ... or, past the split-attention
+                  # switch, the last positions below it: `in_step_from_pos`)
+                  iters = 8
+                  in_pos = replay_pos(iters)
+                  res = model.bench_step(in_pos, iters)
+                  per, tot_us, tot_b, n_gemv, step_us = {}, 0.0, 0.0, 0, 0.0
+                  for name, (us, b, n) in res.items():
+                    per[name] = {"us": round(us / n, 3), "MB": round(b / n / 1e6, 3), "GBps": round(b / us / 1e3, 1), "launches_per_step": n // iters}
+                    step_us += us / iters
+                    if name not in ("attention", "argmax"):
+                      tot_us += us / iters; tot_b += b / iters; n_gemv += n // iters
+                  achieved = tot_b / tot_us / 1e3            # GB/s
+                  rp_us = rocprof_family_us(cfg.name, args.qtype)
+                  roofline = {
+                    "bound": "hbm", "kernel": "lmrs::gemv_static_kernel / gemv_kernel / qkv_attn_kernel (fused dequant-GEMV, all shapes of one step; the qkv launch includes the attention workgroups merged into it, the classifier the folded argmax), durations taken inside the real step",
+                    # `achieved` / `frac`: the WHOLE timed step (SURVEY.md section 8d bytes per token / measured time per token = path.frac: gaps between the
+                    # launches included); `family_*`: the GEMV family alone on its in-step event durations (it excludes the gaps: 1.5 points higher)
+                    "achieved": path["achieved"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": path["frac"],
+                    "family_achieved": round(achieved, 1), "family_frac": round(achieved / HBM_PEAK_GBPS, 4),
+                    "frac_vs_measured_copy": round(path["achieved"] / MEASURED_COPY_GBPS, 4),
+                    # the same bytes over rocprofv3's average durations of the same kernels (committed summary of this build, else null).  A LOWER
+                    # BOUND, not a second measurement of kernel time: under graph replay the profiler's per-dispatch intervals include each launch's
+                    # boundary and overlap their neighbours' - their sum exceeds the timed step itself (round 3: 471 us of "kernels" in a 424 us step)
+                    "frac_rocprof": round(tot_b / rp_us / 1e3 / HBM_PEAK_GBPS, 4) if rp_us else None,
+                    "frac_rocprof_is": "lower bound (profiler intervals overlap at launch boundaries; see path.frac for the timed step)",
+                    "traffic": pmc_traffic(cfg.name, args.qtype),
+                    "bytes_per_launch_avg": round(tot_b / n_gemv), "avg_launch_us": round(tot_us / n_gemv, 3), "launches_per_step": n_gemv,
+                    "in_step": per, "in_step_from_pos": in_pos, "sum_of_kernel_us_per_step": round(step_us, 2), "kernel_source_hash": kernel_source_hash(),
+                    "path": path,
+                  }
             # ---- CPU baseline + parity gate
             cpu = None; parity = None
             cpu_steps = K if args.cpu_steps < 0 else args.cpu_steps
-            if cpu_steps > 0:
+            if args.full and cpu_steps > 0:
                 import oracle_lib as O
                 if args.cpu_threads > 0:
                     os.environ["LMRS_REF_THREADS"] = str(args.cpu_threads)
@@ -461,7 +491,7 @@ def main():
                 parity = {"tokens_compared": int(n_new), "tokens_equal": bool((ref == gen[:n_new]).all())}
             # ---- batched forward_layer (fill_kv_cache): the path's only dense contraction, int8 MFMA
             prefill = None
-            if not sharded and args.qtype in ("q8_0", "q4_0"):
+            if args.full and not sharded and args.qtype in ("q8_0", "q4_0"):
                 n_pf = 256
                 emb = model.get_embeddings(S.prompt_tokens(cfg, n_pf, 4321))
                 best = 1e9
@@ -538,7 +568,7 @@ def main():
         return out
 
     if dist is None or os.environ.get("LMRS_SHARD_PLAN") or os.environ.get("LMRS_BENCH_SINGLE_PLAN") == "1" or force_dist:
-        out = run_once()
+        out = run_once(dump_dir=args.dump_outputs)
     else:
         # N > 1.  The headline line is the configuration north_star names: every weight matrix row-split ("tp"), slices exchanged by
         # RCCL all-gathers over xGMI.  The library's OWN choice for this model and world size (for the small models plan "cls" over the
@@ -551,7 +581,7 @@ def main():
         one_dev = os.environ.get("LMRS_BENCH_ONE_DEVICE") == "1"                      # (RCCL refuses two ranks on one device)
 
         def headline():
-            return run_once(plan="tp", transport_override=None if one_dev else "rccl", emit=False)
+            return run_once(plan="tp", transport_override=None if one_dev else "rccl", emit=False, dump_dir=args.dump_outputs)
 
         def library_choice():
             os.environ.pop("LMRS_SHARD_PLAN", None)        # (run_once(plan=...) set it for the headline run)
@@ -569,12 +599,15 @@ def main():
         if any(v % world for v in (cfg.n_kv_heads, cfg.dim, cfg.hidden_dim, cfg.vocab_size)):
             # the row split north_star names does not exist for this model on this many GPUs (Gemma-2-2B's 4 kv heads on 8): the one configuration
             # there is - whole layers on every GPU, the classifier's rows split (plan "cls"; it needs world | vocab_size) - is the line then, and says so
-            out = run_once(plan="cls", transport_override=None if one_dev else os.environ.get("LMRS_BENCH_TRANSPORT"), emit=False)
+            out = run_once(plan="cls", transport_override=None if one_dev else os.environ.get("LMRS_BENCH_TRANSPORT"), emit=False,
+                           dump_dir=args.dump_outputs)
             if rank == 0 and out is not None:
                 out["headline_is"] = f"plan cls: {world} does not divide this model's n_kv_heads / dim / hidden_dim, plan tp does not exist"
                 print(json.dumps(out), flush=True)
         else:
-            out = headline_then_guarded(headline, [("library_choice", library_choice), ("tp_split_out", tp_split_out)], barrier, rank,
+            # (a plain run measures the headline configuration alone; --full adds the library's own choice and the split-out plan)
+            extras = [("library_choice", library_choice), ("tp_split_out", tp_split_out)] if args.full else []
+            out = headline_then_guarded(headline, extras, barrier, rank,
                                         float(os.environ.get("LMRS_BENCH_LIBRARY_CHOICE_TIMEOUT", "240")))
     if dist is not None:
         dist.destroy_process_group()

@@ -956,7 +956,7 @@ def test_bench_fallback_is_taken_by_all_ranks_together(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LMRS_BENCH_ONE_DEVICE="1", LMRS_BENCH_FAIL_RANK="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29597",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--cpu-steps", "6"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--cpu-steps", "6", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
@@ -964,6 +964,41 @@ def test_bench_fallback_is_taken_by_all_ranks_together(tmp_path):
     assert "second attempt" in d["roofline"]["transport"], d["roofline"]["transport"]
     assert "injected failure" in r.stderr                                  # rank 1 reported why it could not connect
     assert d["parity"]["tokens_equal"] and d["n_gpus"] == 2
+
+
+def test_bench_plain_run_dumps_the_timed_tokens(tmp_path):
+    """bench.py without --full: one line with the headline figures and the --full objects null; --dump-outputs writes the K token ids the
+    timed call returned, equal to the CPU oracle's greedy continuation of the same seeded image and prompt."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K, W = 6, 3
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--model", "mini-llama", "--steps", str(K), "--warmup", str(W),
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == W and d["value"] > 0 and d["ms_per_step"] > 0
+    assert all(d[k] is None for k in ("roofline", "cpu_baseline", "parity", "prefill", "value_128_steps")), d
+    toks = np.load(tmp_path / "out" / "tokens.npy")
+    assert toks.dtype == np.float64 and toks.shape == (K,)
+    img = S.build_image("mini-llama", S.Q8_0, seed=1234)                 # (bench.py's seed and prompt)
+    ref = O.Oracle(img).generate_greedy(S.prompt_tokens("mini-llama", W, 1234), K + 1)
+    assert (toks == ref[1:]).all(), (toks, ref)
+
+
+def test_bench_full_run_past_the_split_attention_switch():
+    """bench.py --full whose timed positions run past LMRS_ATT_SPLIT_POS (forced to 24 here; 384 by default): the per-kernel replay, which
+    runs below the switch only, re-feeds the context and starts at the last position that fits (24 - 8 - 1); the run completes with parity."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--model", "mini-llama-long", "--steps", "40", "--warmup", "4", "--cpu-steps", "8", "--full"]
+    r = subprocess.run(cmd, cwd=root, env=dict(os.environ, LMRS_ATT_SPLIT_POS="24"), capture_output=True, text=True, timeout=300)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["roofline"]["in_step_from_pos"] == 15 and d["roofline"]["in_step"], d["roofline"]
+    assert d["parity"]["tokens_equal"] and d["prefill"] is not None and d["value_128_steps"] > 0
 
 
 @pytest.mark.parametrize("cfg,q,split_out", [("mini-llama", S.Q8_0, False), ("mini-gemma", S.Q4_0, False), ("mini-llama", S.Q8_0, True), ("mini-gemma", S.Q8_0, True)])

@@ -23,20 +23,20 @@ while [ $# -gt 0 ]; do
     case $st in
     gemmpipe) make -s -C tools/ubench gemmpipe && timeout 300 tools/ubench/gemmpipe "${GEMMPIPE_ARGS:-}" > $OUT/ubench_gemmpipe.txt 2>&1; tail -5 $OUT/ubench_gemmpipe.txt;;
     tests) timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.txt 2>&1; tail -3 $OUT/pytest_gpu.txt;;
-    bench) timeout 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_20steps.json 2> $OUT/bench.err; timeout 300 python bench.py > $OUT/bench.json 2>> $OUT/bench.err; cat $OUT/bench_20steps.json;;
+    bench) timeout 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_20steps.json 2> $OUT/bench.err; timeout 300 python bench.py --full > $OUT/bench.json 2>> $OUT/bench.err; cat $OUT/bench_20steps.json;;
     models)
-        timeout 400 python bench.py --model gemma-2-2b --qtype q4_0 --steps 64 > $OUT/bench_gemma2b_q4.json 2>> $OUT/bench.err
-        timeout 400 python bench.py --model llama-3.2-3b --steps 64 > $OUT/bench_llama3b.json 2>> $OUT/bench.err
-        timeout 400 python bench.py --model phi-3.5 --steps 64 > $OUT/bench_phi35.json 2>> $OUT/bench.err;;
+        timeout 400 python bench.py --full --model gemma-2-2b --qtype q4_0 --steps 64 > $OUT/bench_gemma2b_q4.json 2>> $OUT/bench.err
+        timeout 400 python bench.py --full --model llama-3.2-3b --steps 64 > $OUT/bench_llama3b.json 2>> $OUT/bench.err
+        timeout 400 python bench.py --full --model phi-3.5 --steps 64 > $OUT/bench_phi35.json 2>> $OUT/bench.err;;
     stats) M=$1; Q=$2; shift 2; N=$(short $M)_$Q
         rm -rf $OUT/st_$N
-        env ${PROF_ENV:-LMRS_NO_GRAPH=1} timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/st_$N -- python bench.py --model $M --qtype $Q --steps 64 --cpu-steps 0 > $OUT/stats_$N.log 2>&1
+        env ${PROF_ENV:-LMRS_NO_GRAPH=1} timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/st_$N -- python bench.py --full --model $M --qtype $Q --steps 64 --cpu-steps 0 > $OUT/stats_$N.log 2>&1
         echo "stats $N rc $?"; cp $(ls $OUT/st_$N/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/kernel_stats_$N.csv 2>/dev/null; rm -rf $OUT/st_$N;;
     pmc) M=$1; Q=$2; shift 2; N=$(short $M)_$Q
         for c in FETCH_SIZE WRITE_SIZE; do
             for try in 1 2 3; do                            # (rocprofv3 1.1's counter collection hangs or dies at start-up now and then, whatever the workload)
                 rm -rf $OUT/pmc_${N}_$c
-                env ${PROF_ENV:-LMRS_NO_GRAPH=1} timeout -k 5 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${N}_$c -- python bench.py --model $M --qtype $Q --steps 16 --warmup 4 --cpu-steps 0 > $OUT/pmc_${N}_$c.log 2>&1
+                env ${PROF_ENV:-LMRS_NO_GRAPH=1} timeout -k 5 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${N}_$c -- python bench.py --full --model $M --qtype $Q --steps 16 --warmup 4 --cpu-steps 0 > $OUT/pmc_${N}_$c.log 2>&1
                 echo "pmc $N $c try $try rc $?"
                 ls $OUT/pmc_${N}_$c/*/*counter_collection.csv > /dev/null 2>&1 && break
             done
@@ -56,7 +56,7 @@ while [ $# -gt 0 ]; do
     crash) M=$1; Q=$2; shift 2            # which of {kernel-argument preload, steps per graph launch} rocprofv3's interceptor dies on (profiles/README.md)
         for v in nokp1 kp4 nokp4; do
             case $v in nokp1) E="LMRS_LIB=$PWD/lm.rs_amd/liblmrs_hip_nokp.so LMRS_STEPS_PER_GRAPH=1";; kp4) E="LMRS_STEPS_PER_GRAPH=4";; nokp4) E="LMRS_LIB=$PWD/lm.rs_amd/liblmrs_hip_nokp.so LMRS_STEPS_PER_GRAPH=4";; esac
-            rm -rf /tmp/cx; env $E timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/cx -- python bench.py --model $M --qtype $Q --steps 16 --cpu-steps 0 > $OUT/crash_$(short $M)_$v.log 2>&1
+            rm -rf /tmp/cx; env $E timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/cx -- python bench.py --full --model $M --qtype $Q --steps 16 --cpu-steps 0 > $OUT/crash_$(short $M)_$v.log 2>&1
             echo "crash-probe $M $v rc $? $(ls /tmp/cx/*/*kernel_stats.csv 2>/dev/null | wc -l) stats files"
         done;;
     sh) bash -c "$1" > $OUT/sh_$(date +%H%M%S).txt 2>&1; shift;;
