@@ -30,6 +30,7 @@
 #include "../../include/lmrs_hip.h"
 #include "lmrs_format.h"
 #include "lmrs_kernels.h"
+#include "lmrs_switches.h"
 
 using namespace lmrs;
 
@@ -71,7 +72,6 @@ struct lmrs_ctx {
     uint32_t* tokens = nullptr; DevState* st = nullptr;
     unsigned long long* dbg = nullptr; int dbg_node = 0;     // LMRS_DEBUG_TIMELINE=1: 8 stamps per kernel node
     // pinned host
-    size_t topp_sort_min = 4096;                   // top-p candidates from which their sort runs on the device (LMRS_TOPP_DEVICE_SORT_MIN, read at create: a host stable sort of 4096 pairs is ~0.25 ms, the device route ~0.2 ms whatever the count)
     unsigned long long* samp_keys = nullptr; float* samp_pairs = nullptr; void* h_pairs = nullptr; int samp_cap = 0;   // lmrs_forward_sample: the device sort of top-p candidates (allocated on first use)
     float* h_logits = nullptr; uint32_t* h_tok = nullptr; DevState* h_st = nullptr; unsigned h_st_next = 0;   // h_st: ring of kStateSlots pinned slots (an async copy may still be reading the previous one)
     hipGraphExec_t g_step = nullptr, g_layers = nullptr;
@@ -83,13 +83,11 @@ struct lmrs_ctx {
     // batched prefill on row shards (plan "tp", Q8_0): the gathered blocks of a token batch - per shard [n_tok x slice int8 | n_tok x slice / 128 scales],
     // pfb_att / pfb_h bytes apart; inside the peer-to-peer arena when that is the transport (peers write them), ordinary memory for RCCL
     char *pfx_att = nullptr, *pfx_h = nullptr, *pfx_x = nullptr; size_t pfb_att = 0, pfb_h = 0, pfb_x = 0; bool pfx_owned = false;   // pfx_x: the split-out plan's f32 slices of wo / w2's output
-    bool tp_prefill = false;                               // decided ONCE, at create (prefill_tp_shapes_ok: shapes and LMRS_NO_BATCHED_PREFILL) - where the blocks live follows from it
+    bool tp_prefill = false;                               // decided at create (prefill_tp_shapes_ok: shapes and LMRS_NO_BATCHED_PREFILL) - where the blocks live follows from it
     float* x2 = nullptr; bool gemma_fused = false;           // Gemma: second residual buffer; norm+add steps folded into the consuming GEMV prologues
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool no_graph = false;                         // LMRS_NO_GRAPH=1 (read at create): steps are enqueued launch by launch (profiling aid, see launch_step)
+    Switches sw;                                   // the environment switches, read at create (lmrs_switches.h)
     std::vector<float*> scales_t;                  // the layers' transposed scale copies (owned)
-    bool no_batched_prefill = false;               // LMRS_NO_BATCHED_PREFILL=1 (read ONCE, at create): fill_kv_cache and prompts go token by token through the decode kernels
-    bool no_fused_rope = false, no_fused_hq = false; // LMRS_NO_PREFILL_FUSION=1 (read at create; A/B aid): the batched prefill with RoPE and the h quantiser as launches of their own
     int att_dim = 0, kv_dim = 0, cls_grid = 0;     // att_dim / kv_dim: THIS shard's query / key-value widths
     int part_stride = 0;                           // floats between two shards' argmax partials: 2 * cls_grid rounded up to 16 bytes (the push transport copies 16 bytes per lane;
                                                    // Llama-3.2-1B on 8 shards has 501 partials per shard)
@@ -148,7 +146,7 @@ constexpr int kPrefillTokens = 512;            // tokens per pass of the batched
 // plan too); everything else feeds its tokens one by one.
 bool prefill_tp_shapes_ok(const lmrs_ctx* c) {
     const lmrs_args& a = c->args;
-    if (c->world < 1 || c->cls_only || c->f32 || c->no_batched_prefill) return false;
+    if (c->world < 1 || c->cls_only || c->f32 || c->sw.no_batched_prefill) return false;
     if (!c->rep_out && c->dim_l % 16) return false;                      // (the split-out plan: wo / w2 rows split too - their slices are whole GEMM row tiles' worth)
     if (a.q_type != LMRS_Q8_0 && a.q_type != LMRS_Q4_0) return false;
     if (c->att_dim % 128 || c->hid_l % 128) return false;
@@ -339,7 +337,7 @@ GemvArgs cls_args(lmrs_ctx* c) {
     if (c->world > 1 || c->comm) {          // sharded: this shard's [values | indices] block of the gathered partials
         g.part_val = c->part + (size_t)c->rank * c->part_stride;
         g.part_idx = reinterpret_cast<int*>(c->part + (size_t)c->rank * c->part_stride) + c->cls_grid;
-        if (c->p2p && !getenv("LMRS_SHARD_SINGLE_PARTIALS")) { g.part_par = c->xseq + c->ex_slot; g.part_par_floats = (int)((size_t)c->world * 2 * kMaxArgmaxParts); }   // the exchange enqueued next takes this slot
+        if (c->p2p) { g.part_par = c->xseq + c->ex_slot; g.part_par_floats = (int)((size_t)c->world * 2 * kMaxArgmaxParts); }   // the exchange enqueued next takes this slot
     } else { g.part_val = c->part_val; g.part_idx = c->part_idx; }
     g.softcap_rows = a.model_type == LMRS_GEMMA ? (int)a.dim : 0;
     if (c->gemma_fused) { g.xin = c->x2; g.delta = c->tmp; g.add_w = c->layers[a.n_layers - 1].rms_post_ffn; g.xout = c->x; }
@@ -396,16 +394,15 @@ int enqueue_step(lmrs_ctx* c) {
 //   * tmp slices (fully row-split form) and the argmax partials: f32 / raw.
 // ------------------------------------------------------------------------------------------------
 struct ExchangeDesc { char* buf; size_t bytes, stride; const float* qsrc; size_t qn; size_t par = 0; bool wide = false; };   // wide: a token batch's block (copied by many workgroups)   // par > 0: double-buffered block, halves `par` bytes apart (exchange_push_kernel picks the half by its sequence number)   // bytes valid per shard, blocks `stride` bytes apart (in place); qsrc: f32 slice still to be quantised into this shard's block
-static bool shard_split_out() { const char* e = getenv("LMRS_SHARD_SPLIT_OUT"); return e && atoi(e) != 0; }   // (read at every create: bench.py measures both forms in one process)
 // Which matrices to split over `world` GPUs.  Row-splitting a layer's matrices costs two exchanges per layer (four in the fully split
 // form): pure latency, a few microseconds each, every layer of every token.  It pays only when the gate / up / down stream a shard no
 // longer reads is longer than that: (w1 + w3 + w2 bytes per layer) x (1 - 1/world) at the ~6.3 TB/s a GPU streams, against ~9 us for two
 // exchanges - about 57 MB.  Below that (the 1B and 2B models at any world size, the 3B / 3.8B ones at 2 and 4) the plan is "cls": every shard
 // runs the layers whole, with the fused single-GPU kernels and no exchange, and only the classifier - the one big stream of the step,
 // 270 MB for Llama-3.2 - is row-split, for ONE exchange of the argmax partials per token.  LMRS_SHARD_PLAN=tp|cls overrides.
-static bool shard_plan_cls_only(const lmrs_args& a, int world) {
+static bool shard_plan_cls_only(const lmrs_args& a, int world, const Switches& sw) {
     if (world <= 1) return false;
-    if (const char* e = getenv("LMRS_SHARD_PLAN")) return !strcmp(e, "cls");
+    if (sw.shard_plan) return sw.shard_plan == 1;
     const double bpe = a.q_type == LMRS_Q4_0 ? 0.5 + 4.0 / 128 : 1.0 + 4.0 / 128;
     const double mlp_bytes = 3.0 * a.dim * a.hidden_dim * bpe;
     return mlp_bytes * (1.0 - 1.0 / world) < 57e6;
@@ -414,8 +411,6 @@ static bool shard_plan_cls_only(const lmrs_args& a, int world) {
 int n_segments(const lmrs_ctx* c) { return 4 * (int)c->args.n_layers + 2; }
 
 static size_t part_half_floats(const lmrs_ctx* c) { return (size_t)c->world * 2 * kMaxArgmaxParts; }
-// (LMRS_SHARD_SINGLE_PARTIALS=1: the single buffer of rounds 2-3, kept so that test_push_exchange_with_a_stalled_peer can be shown to fail without the halves)
-static bool part_double(const lmrs_ctx* c) { static const bool single = getenv("LMRS_SHARD_SINGLE_PARTIALS") != nullptr; return c->p2p && !single; }
 ExchangeDesc exchange_after(lmrs_ctx* c, int seg) {
     const int L4 = 4 * (int)c->args.n_layers;
     const ExchangeDesc none{nullptr, 0, 0, nullptr, 0};
@@ -430,7 +425,7 @@ ExchangeDesc exchange_after(lmrs_ctx* c, int seg) {
     }
     if (seg == L4) {                                             // peer-to-peer: the partials are double-buffered (ArgmaxArgs::part_par)
         ExchangeDesc e = f32s(c->part, (size_t)c->part_stride);
-        if (part_double(c)) e.par = part_half_floats(c) * 4;
+        if (c->p2p) e.par = part_half_floats(c) * 4;
         return e;
     }
     return none;
@@ -519,7 +514,7 @@ int run_segment(lmrs_ctx* c, int seg) {
     ArgmaxArgs m{};
     m.part_val = c->part; m.part_idx = reinterpret_cast<const int*>(c->part) + c->cls_grid; m.n_part = c->cls_grid;
     m.n_groups = c->world; m.group_stride = c->part_stride;
-    if (part_double(c) && c->ex_slot > 0) { m.part_par = c->xseq + (c->ex_slot - 1); m.part_par_floats = (int)part_half_floats(c); }     // the slot of the partials exchange just enqueued
+    if (c->p2p && c->ex_slot > 0) { m.part_par = c->xseq + (c->ex_slot - 1); m.part_par_floats = (int)part_half_floats(c); }     // the slot of the partials exchange just enqueued
     m.logits = c->logits; m.tokens = c->tokens; m.st = c->st; m.seq = c->seq; m.emb = embed_args(c); m.tail_row = unwritten_tail(c);
     HIP_OK(launch_argmax_final(m, c->stream));
     return 0;
@@ -573,7 +568,7 @@ int enqueue_exchange(lmrs_ctx* c, const ExchangeDesc& e) {
             x.peer_flag[w] = reinterpret_cast<unsigned*>(c->peer_base[w] + ((char*)c->xflags - c->xarena)) + (size_t)c->ex_slot * kMaxWorld + c->rank;
         }
         x.my_flags = c->xflags + (size_t)c->ex_slot * kMaxWorld; x.my_seq = c->xseq + c->ex_slot; x.err = c->xerr;
-        { static const long long ms = getenv("LMRS_P2P_TIMEOUT_MS") ? atoll(getenv("LMRS_P2P_TIMEOUT_MS")) : 3000; x.timeout_ticks = ms * 100000ll; }   // 100 MHz wall clock
+        x.timeout_ticks = c->sw.p2p_timeout_ms * 100000ll;   // 100 MHz wall clock
         ++c->ex_slot;
         x.par_bytes = (int)e.par;
         if (e.qsrc) { x.qsrc = e.qsrc; x.qn = (int)e.qn; }      // the slice is quantised by the exchange kernel itself on its way out
@@ -669,7 +664,8 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
 // wo/w2 row first/count, gate-up pair first/count, classifier row first/count.  <0 if `world` does not divide the model.
 extern "C" int lmrs_shard_plan(const lmrs_args* a, int rank, int world, int* plan) {
     if (!a || !plan || world < 1 || rank < 0 || rank >= world) return fail("bad argument");
-    if (shard_plan_cls_only(*a, world)) {                     // the layers whole on every shard, the classifier's rows split
+    const Switches sw = read_switches();
+    if (shard_plan_cls_only(*a, world, sw)) {                 // the layers whole on every shard, the classifier's rows split
         if (a->vocab_size % world) return fail("world must divide vocab_size");
         const int vl = a->vocab_size / world;
         const int p[10] = {0, (int)a->n_heads, 0, (int)a->n_kv_heads, 0, (int)a->dim, 0, (int)a->hidden_dim, rank * vl, vl};
@@ -678,7 +674,7 @@ extern "C" int lmrs_shard_plan(const lmrs_args* a, int rank, int world, int* pla
     }
     if (a->n_kv_heads % world || a->dim % world || a->hidden_dim % world || a->vocab_size % world)
         return fail("world must divide n_kv_heads, dim, hidden_dim and vocab_size");
-    const bool rep = !shard_split_out();                      // wo / w2 rows: replicated on every shard by default
+    const bool rep = !sw.shard_split_out;                     // wo / w2 rows: replicated on every shard by default
     const int nh = a->n_heads / world, nkv = a->n_kv_heads / world, dl = rep ? (int)a->dim : (int)a->dim / world, hl = a->hidden_dim / world, vl = a->vocab_size / world;
     const int p[10] = {rank * nh, nh, rank * nkv, nkv, rep ? 0 : rank * dl, dl, rank * hl, hl, rank * vl, vl};
     memcpy(plan, p, sizeof p);
@@ -827,6 +823,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     *out = nullptr;
     Layout lay; std::string perr;
     if (!parse_layout(file, len, &lay, &perr)) return fail(perr);
+    const Switches sw = read_switches();
     const lmrs_args& a = lay.args;
     const bool f32w = a.q_type == LMRS_Q_NONE;
     if (f32w && (world > 1 || uid)) return fail("q_type None (f32 weights) runs on one GPU only (row sharding is built for the quantised path)");
@@ -845,7 +842,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
 
     // ---- shard plan: whole heads / rows per shard, equal sizes (in-place all-gathers need equal counts)
     const size_t W = (size_t)world;
-    const bool cls_only = !f32w && shard_plan_cls_only(a, world);
+    const bool cls_only = !f32w && shard_plan_cls_only(a, world, sw);
     if (cls_only ? V % W != 0 : world > 1 && (a.n_kv_heads % W || dim % W || hid % W || V % W))
         return fail(cls_only ? "world must divide vocab_size" : "world must divide n_kv_heads, dim, hidden_dim and vocab_size");
     if (a.vocab_size / (uint32_t)world < 4) return fail("vocab_size / world must be at least 4");
@@ -854,14 +851,14 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     // from the gathered att_out / h, so the residual needs no gather of its own - two all-gathers per layer instead of four,
     // for 4 + 17 MB of extra weight reads per layer and shard (1-3 us) against two ~10-20 us latency-bound collectives.
     // LMRS_SHARD_SPLIT_OUT=1 restores the fully row-split form.
-    const bool rep_out = cls_only || !shard_split_out();
+    const bool rep_out = cls_only || !sw.shard_split_out;
     const size_t WL = cls_only ? 1 : W;                                 // the layers' split ("cls": none)
     const size_t att_l = att / WL, kv_l = kv / WL, dim_l = rep_out ? dim : dim / W, hid_l = hid / WL, voc_l = V / W;
     const size_t a0 = cls_only ? 0 : rank * att_l, k0 = cls_only ? 0 : rank * kv_l, d0 = rep_out ? 0 : rank * dim_l, h0 = cls_only ? 0 : rank * hid_l, v0 = rank * voc_l;
     (void)hs;
 
     lmrs_ctx* c = new lmrs_ctx();
-    c->no_batched_prefill = getenv("LMRS_NO_BATCHED_PREFILL") != nullptr;
+    c->sw = sw;
     c->args = a; c->lay = lay; c->device = device; c->q4 = a.q_type == LMRS_Q4_0; c->f32 = f32w;
     c->rank = rank; c->world = world; c->att_full = (int)att;
     c->att_dim = (int)att_l; c->kv_dim = (int)kv_l; c->dim_l = (int)dim_l; c->hid_l = (int)hid_l; c->voc_l = (int)voc_l;
@@ -870,7 +867,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     const bool sharded = world > 1 || uid != nullptr;
     // transport of the exchanges: RCCL when a communicator id is given; otherwise peer-to-peer pushes (separate processes
     // connect through lmrs_p2p_handles / lmrs_p2p_connect; a lock-step group on one device uses plain copies unless LMRS_GROUP_P2P=1)
-    c->p2p = sharded && world > 1 && !uid && (!group_mode || getenv("LMRS_GROUP_P2P"));
+    c->p2p = sharded && world > 1 && !uid && (!group_mode || sw.group_p2p);
     if (c->p2p && world > kMaxWorld) { delete c; return fail("the peer-to-peer transport connects at most " + std::to_string(kMaxWorld) + " shards (the GPUs of one node): pass a communicator id (RCCL) for larger worlds"); }
     auto cleanup = [&]() { lmrs_destroy(c); return -1; };
 #define CK(call) do { if ((call)) return cleanup(); } while (0)
@@ -905,7 +902,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     need(dim * 4); need(att_l * 4); need(kv_l * 4); need(att * 4); need(hid * 4); need(V * 4); need(dim * 4); need(dim * 4);
     need(kMaxArgmaxParts * 4); need(kMaxArgmaxParts * 4); need(W * 2 * kMaxArgmaxParts * 4);
     // quantised exchange payloads (Q8_0, whole 128-groups per shard): one padded block per shard
-    c->qpay = sharded && !cls_only && !c->q4 && att_l % 128 == 0 && hid_l % 128 == 0 && !getenv("LMRS_SHARD_F32_PAYLOAD");
+    c->qpay = sharded && !cls_only && !c->q4 && att_l % 128 == 0 && hid_l % 128 == 0 && !sw.shard_f32_payload;
     c->tp_prefill = sharded && prefill_tp_shapes_ok(c);
     c->blk_att = pad256(att_l + att_l / 32); c->blk_h = pad256(hid_l + hid_l / 32);
     need(W * c->blk_att); need(W * c->blk_h);
@@ -1009,7 +1006,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     if (!c->seq || !c->cls_seq || !c->gran || !c->err || !c->part_pk) { fail("arena overflow"); return cleanup(); }
     HCK(hipMemsetAsync(c->part_pk, 0, kMaxArgmaxParts * 8, c->stream));
     HCK(hipMemsetAsync(c->seq, 0, 4, c->stream)); HCK(hipMemsetAsync(c->cls_seq, 0, 4, c->stream)); HCK(hipMemsetAsync(c->gran, 0, nl * (att_l + 2 * kv_l) * 8, c->stream)); HCK(hipMemsetAsync(c->err, 0, 4, c->stream));
-    if (getenv("LMRS_DEBUG_TIMELINE")) { c->dbg = c->alloc<unsigned long long>(8 * 1024); if (c->dbg) HCK(hipMemsetAsync(c->dbg, 0, 8 * 1024 * 8, c->stream)); }
+    if (sw.debug_timeline) { c->dbg = c->alloc<unsigned long long>(8 * 1024); if (c->dbg) HCK(hipMemsetAsync(c->dbg, 0, 8 * 1024 * 8, c->stream)); }
     c->stage = c->alloc<float>(c->stage_floats);
     if (!c->stage) { fail("arena overflow"); return cleanup(); }
     HCK(hipMemsetAsync(c->k_cache, 0, kvn * 4, c->stream)); HCK(hipMemsetAsync(c->v_cache, 0, kvn * 4, c->stream));   // :302-303
@@ -1029,7 +1026,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     HCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_err), 4, hipHostMallocDefault));
     CK(set_state(c, 0, 0));
     HCK(hipStreamSynchronize(c->stream));
-    if (a.model_type == LMRS_GEMMA && !sharded && !f32w && !getenv("LMRS_GEMMA_UNFUSED")) {
+    if (a.model_type == LMRS_GEMMA && !sharded && !f32w) {
         // fold the two "x += rmsnorm(branch)" steps of a Gemma layer into the consuming GEMV prologues when every launch of the
         // step has a static kernel that can do it (otherwise: the separate addnorm launches)
         GemvArgs q{}; q.q4 = c->q4; q.n = a.dim; q.o = c->att_dim + 2 * c->kv_dim;
@@ -1044,29 +1041,26 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
         c->part_stride = (2 * c->cls_grid + 3) & ~3;
     }
     // (also the "cls" shard plan in its one-process-per-GPU form: there every GPU runs the layers whole, with the single-GPU launches)
-    if ((!sharded || (cls_only && !group_mode)) && !f32w && !(getenv("LMRS_QKV_ATT") && atoi(getenv("LMRS_QKV_ATT")) == 0)) {
+    if ((!sharded || (cls_only && !group_mode)) && !f32w && sw.qkv_att != 0) {
         // qkv + attention as one launch (short contexts) when the model's qkv launch has a merged class for every prologue it uses
         GemvArgs q{}; q.q4 = c->q4; q.n = a.dim; q.o = c->att_dim + 2 * c->kv_dim;
         AttnArgs t{}; t.n_heads = a.n_heads; t.n_kv_heads = a.n_kv_heads; t.head_size = a.head_size; t.gemma = a.model_type == LMRS_GEMMA;
         c->qkv_att = qkv_attn_supported(q, PRO_RMS_QUANT, t) && (!c->gemma_fused || qkv_attn_supported(q, PRO_ADD_RMS_QUANT, t)) &&
                      !(a.model_type == LMRS_GEMMA && !c->gemma_fused);
         c->qa_max_T = a.seq_len < 1024 ? (int)a.seq_len : 1024;
-        if (c->qkv_att && !(getenv("LMRS_QKV_ATT") && atoi(getenv("LMRS_QKV_ATT")) == 1)) c->qa_wave_T = qkv_attn_wave_T((int)a.head_size);   // LMRS_QKV_ATT=1: workgroup form only
+        if (c->qkv_att && sw.qkv_att != 1) c->qa_wave_T = qkv_attn_wave_T((int)a.head_size);   // LMRS_QKV_ATT=1: workgroup form only
         // (the wave forms' prefetch reads whole 64-row blocks of the caches - 128 rows for the 64-wide heads; their form for positions 128 .. 255 clamps its rows to the sequence)
         if (c->qa_wave_T > (int)a.seq_len) c->qa_wave_T = a.head_size == 64 && a.seq_len >= 128 ? (int)a.seq_len : 0;
     }
-    c->no_graph = getenv("LMRS_NO_GRAPH") != nullptr;
-    c->no_fused_rope = c->no_fused_hq = getenv("LMRS_NO_PREFILL_FUSION") != nullptr;
-    if (const char* e = getenv("LMRS_TOPP_DEVICE_SORT_MIN")) c->topp_sort_min = (size_t)atol(e);
-    if (!sharded) { const int k = getenv("LMRS_STEPS_PER_GRAPH") ? atoi(getenv("LMRS_STEPS_PER_GRAPH")) : 4; c->multi_k = k < 1 ? 1 : (k > 64 ? 64 : k); }   // (measured: 4 steps per launch +1.5 % on a 20-step run, no effect on long runs)
-    c->cls_tail = !sharded && !f32w && V < (1u << 20) - 1 && !(getenv("LMRS_CLS_TAIL") && atoi(getenv("LMRS_CLS_TAIL")) == 0);
+    if (!sharded) c->multi_k = sw.steps_per_graph;   // (measured: 4 steps per launch +1.5 % on a 20-step run, no effect on long runs)
+    c->cls_tail = !sharded && !f32w && V < (1u << 20) - 1 && sw.cls_tail;
     if (!sharded) {
         c->qa_mode = qa_mode_for(c, 0);
         CK(capture(c, true, &c->g_step));
         c->qa_mode = 0;                         // the layers-only graph serves fill_kv_cache's token-by-token form at ANY position: separate kernels
         CK(capture(c, false, &c->g_layers));
         // from this position on a step uses the split attention (scores by key chunk, V by dim slice): graphs captured on first use
-        if (!c->dbg || getenv("LMRS_ATT_SPLIT_POS")) { const char* e = getenv("LMRS_ATT_SPLIT_POS"); c->att_split_pos = e ? atoi(e) : 384; }     // (stamped steps: the split form only when asked for)
+        if (!c->dbg || sw.att_split_pos_set) c->att_split_pos = sw.att_split_pos;     // (stamped steps: the split form only when asked for)
         // every graph a call below that threshold can need - per qkv + attention mode the single-step graph and the multi-step one -
         // is captured here rather than inside the first generate call that reaches the mode (a capture is milliseconds: on a
         // 128-token run that crosses the wave -> workgroup switch it was 3 % of the run)
@@ -1089,7 +1083,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
         c->qa_mode = 0;
     }
     // (peer-to-peer contexts capture their step graph in lmrs_p2p_connect, once the peers' arenas are known)
-    if (sharded) { const char* e = getenv("LMRS_ATT_SPLIT_POS"); c->att_split_pos = e ? atoi(e) : 384; }
+    if (sharded) c->att_split_pos = sw.att_split_pos;
     // Row shards over RCCL whose prefill is batched allocate its buffers (the token-batch blocks of the all-gathers among them) HERE: a shard
     // that failed to allocate them inside its first fill_kv_cache would return before the exchange its peers are already waiting in
     // (ncclAllGather has no time-out); at create the failure surfaces on every rank's own call, before any exchange exists.
@@ -1146,7 +1140,7 @@ static int launch_step(lmrs_ctx* c, uint32_t pos) {
     }
     // profiling aid (LMRS_NO_GRAPH=1): the same launches enqueued one by one instead of a graph replay - rocprofv3 1.1's dispatch interceptor
     // segfaults on the graph launches of every model but Llama-3.2-1B (profiles/README.md); token ids are the same either way
-    if (c->no_graph && !sharded && c->g_step) {
+    if (c->sw.no_graph && !sharded && c->g_step) {
         c->qa_mode = want_split ? 0 : qa_mode_for(c, pos); c->att_split_chunks = want_split ? 4 << b : 0; c->dbg_node = 0;
         const int rc = enqueue_step(c);
         c->qa_mode = 0; c->att_split_chunks = 0;
@@ -1253,7 +1247,7 @@ extern "C" int lmrs_forward_sample(lmrs_ctx* c, uint32_t token, uint32_t pos, lm
     // the sequential sum, the division and the cutoff filter on the host (lmrs_text.cpp); the exponentials are still in c->logits on the device
     float sum = 0.0f, cutoff = 0.0f; size_t n0 = 0;
     if (lmrs_sampler_exps_prepare(sampler, c->h_logits, &sum, &cutoff, &n0)) return -1;
-    if (n0 < c->topp_sort_min || !(sum == sum)) return lmrs_sampler_exps_finish(sampler, c->h_logits, nullptr, next);
+    if (n0 < c->sw.topp_sort_min || !(sum == sum)) return lmrs_sampler_exps_finish(sampler, c->h_logits, nullptr, next);
     // many candidates (a flat distribution): their sort (sampler.rs:81) on the device - probabilities re-formed there from the same exponentials and
     // the same sum by the same IEEE division, so the device finds the same n0 candidates (checked) - and only the sorted pairs come back
     int N = sample_sort_min_n();
@@ -1302,7 +1296,7 @@ extern "C" int lmrs_get_embeddings(const lmrs_ctx* cc, const uint32_t* tokens, s
 // everything else takes the token-by-token path below (same results).
 static bool prefill_batched_ok(const lmrs_ctx* c) {
     const lmrs_args& a = c->args;
-    if (c->no_batched_prefill) return false;
+    if (c->sw.no_batched_prefill) return false;
     // (a "cls" shard runs the layers whole: the batched path applies to it as to a single GPU, every shard filling its own cache)
     const bool whole_layers = c->cls_only || (c->world == 1 && !c->comm && c->g_layers);
     if ((a.q_type != LMRS_Q8_0 && a.q_type != LMRS_Q4_0) || !whole_layers) return false;
@@ -1335,7 +1329,7 @@ static int prefill_alloc(lmrs_ctx* c) {
     }
     // The layers' weight scales transposed, [group][row], once: a ring GEMM fetches a group's scales of 64 rows as 256 consecutive bytes instead of 4 bytes
     // from each of 64 lines (GemmArgs::ws_ld; +1/32 of the quantised weights' bytes).  A failed allocation only means the row-major scales stay in use.
-    if (!c->f32 && c->layers.size() && !c->layers[0].sqkvT && !getenv("LMRS_NO_TRANSPOSED_SCALES")) {
+    if (!c->f32 && c->layers.size() && !c->layers[0].sqkvT) {
         const lmrs_args& A = c->args;
         const bool tp = c->world > 1 || c->comm;
         const int dim = (int)A.dim, hid = (int)A.hidden_dim, att_full = tp && !c->cls_only ? c->att_full : c->att_dim;
@@ -1370,9 +1364,8 @@ static int prefill_attention(lmrs_ctx* c, AttnArgs& t, int m, int p0) {
                 if (c->pf_att) { HIP_OK(hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_att); c->pf_att = nullptr; c->pf_att_cap = 0; }
                 HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->pf_att), need * 4)); c->pf_att_cap = need;
             }
-            if (!c->no_fused_rope) t.k_raw = c->pf_k;
-            else HIP_OK(launch_rope_rows(c->pf_q, c->pf_k, c->k_cache, c->rope, t.n_heads, t.n_kv_heads, t.head_size, t.seq_len, t.layer, p0, m, c->stream));
-            HIP_OK(launch_attention_block(t, p0, m, c->pf_att, c->stream));
+            t.k_raw = c->pf_k;
+            HIP_OK(launch_attention_block(t, p0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
             return 0;
         }
     }
@@ -1455,7 +1448,7 @@ static int prefill_layers(lmrs_ctx* c, int m, int p0) {
         if (tp) {
             HIP_OK(launch_gemm_q8(g, gemma ? EPI_GELU : EPI_SWIGLU, c->stream));
             if (all_gather(c->pf_h, hid_l, c->pfx_h, c->pfb_h)) return -1;
-        } else if (!c->no_fused_hq && gemm_q8_hq_fused(dim, 2 * hid, m, q4 != 0)) {
+        } else if (gemm_q8_hq_fused(dim, 2 * hid, m, q4 != 0)) {
             // (the quantiser of h in w1/w3's epilogue: int8 rows + scales in the buffer the f32 rows would have taken)
             g.hq = reinterpret_cast<int8_t*>(c->pf_h); g.hs = reinterpret_cast<float*>(reinterpret_cast<char*>(c->pf_h) + (size_t)kPrefillTokens * hid);
             g.hs_ld = xld;
@@ -1580,7 +1573,7 @@ extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t 
         const uint32_t p = start_pos + (uint32_t)s;
         const int K = c->multi_k;
         const bool split_soon = c->att_split_pos > 0 && (int)(p + K - 1) >= c->att_split_pos;
-        if (K > 1 && c->g_step && !c->dbg && !c->no_graph && s + K <= steps && !split_soon && qa_mode_for(c, p) == qa_mode_for(c, p + K - 1)) {
+        if (K > 1 && c->g_step && !c->dbg && !c->sw.no_graph && s + K <= steps && !split_soon && qa_mode_for(c, p) == qa_mode_for(c, p + K - 1)) {
             const int mode = qa_mode_for(c, p);
             if (!c->g_multi[mode]) {
                 c->qa_mode = mode;
@@ -1639,15 +1632,12 @@ extern "C" int lmrs_bench_gemv(lmrs_ctx* c, int iters, double* us5, double* byte
             default: g = cls_args(c); pro = fz ? PRO_ADD_RMS_QUANT : PRO_RMS_QUANT; epi = EPI_CLS; break;
         }
     };
-    // LMRS_BENCH_HOT_LAYER=k (experiment): every layer GEMV reads layer k's weights, i.e. they are served by the 256 MiB
-    // Infinity Cache instead of HBM - how much faster is a cache-resident weight stream?
-    const int hot = getenv("LMRS_BENCH_HOT_LAYER") ? atoi(getenv("LMRS_BENCH_HOT_LAYER")) : -1;
     if (set_state(c, a.seq_len - 1, 0)) return -1;      // the V row the qkv epilogue scribbles on: the last one
     for (int it = -1; it < iters; ++it) {              // it == -1: untimed warm-up pass
         int i = 0;
         for (int l = 0; l <= nl; ++l)
             for (int which = (l < nl ? 0 : 4); which < (l < nl ? 4 : 5); ++which) {
-                GemvArgs g; int pro, epi; mk(which, l < nl ? (hot >= 0 ? hot : l) : 0, g, pro, epi);
+                GemvArgs g; int pro, epi; mk(which, l < nl ? l : 0, g, pro, epi);
                 set_gemv_launch_events(ev[2 * i], ev[2 * i + 1]);       // events ride on the dispatch itself
                 const hipError_t le = launch_gemv(g, pro, epi, c->stream);
                 set_gemv_launch_events(nullptr, nullptr);
@@ -2004,7 +1994,7 @@ struct lmrs_vision {
     uint32_t dim = 0, hidden = 0, n_layers = 0, n_heads = 0, head_size = 0, patch = 0, image = 0, gs = 0; float eps = 0;
     int qt = LMRS_Q8_0;                            // q_type of the section: Q8_0, Q4_0 or None (f32)
     bool no_scales_t = false;                      // the transposed scale copies could not be allocated: row-major scales stay in use
-    bool no_stray = false;                         // LMRS_VIS_NO_STRAY, read once at create: the 577th query as a tenth block of 64 lanes (A/B aid, tests)
+    Switches sw;                                   // the environment switches, read at create (vis_no_stray)
     float *class_emb = nullptr, *patch_emb = nullptr, *pos_emb = nullptr, *pre_ln = nullptr, *pre_ln_b = nullptr;
     std::vector<VisLayer> layers;
     std::vector<void*> owned;
@@ -2038,7 +2028,7 @@ extern "C" int lmrs_vision_create(const uint8_t* sec, size_t len, int device, lm
     if (op_begin(device)) return -1;
     if (len < 128) return fail("vision section shorter than its 128-byte header");
     lmrs_vision* v = new lmrs_vision();
-    v->no_stray = getenv("LMRS_VIS_NO_STRAY") != nullptr;
+    v->sw = read_switches();
     v->device = device;
     v->dim = rd32(sec); v->hidden = rd32(sec + 4); v->n_layers = rd32(sec + 8); v->n_heads = rd32(sec + 12); v->head_size = rd32(sec + 16);
     memcpy(&v->eps, sec + 20, 4); v->patch = rd32(sec + 24); v->image = rd32(sec + 28);
@@ -2174,7 +2164,7 @@ extern "C" int lmrs_vision_forward(lmrs_vision* v, const float* pixel_values, ui
         GemmArgs g{};
         g.out = v->QKV; g.bias = Y.bqkv; g.att_dim = dim; g.qscale = sqrtf((float)v->head_size);
         if (project(v->AO, q8, Y.wqkv, Y.sqkv, Y.sqkvT, dim, 3 * dim, g, EPI_VQKV)) return -1;
-        HIP_OK(launch_vis_attention(v->QKV, v->AO, v->scratch, (int)num_crops, (int)v->n_heads, T, dim, !v->no_stray, s));
+        HIP_OK(launch_vis_attention(v->QKV, v->AO, v->scratch, (int)num_crops, (int)v->n_heads, T, dim, !v->sw.vis_no_stray, s));
         g = GemmArgs{}; g.out = v->E; g.bias = Y.bo; g.resid = v->X;
         if (project(v->AO, false, Y.wo, Y.so, Y.soT, dim, dim, g, EPI_BIAS_RESID)) return -1;
         HIP_OK(launch_vis_layernorm(v->E, Y.ln2, Y.ln2_b, v->eps, dim, n_tok, q8 ? nullptr : v->AO, v->xq, v->xs, s, xld));

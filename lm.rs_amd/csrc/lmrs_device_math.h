@@ -24,7 +24,6 @@ __device__ __forceinline__ int cluster8_sum(int v) {
 // v = max(v, v of another lane) as ONE instruction: the DPP operand of the max itself.  (Spelled fmaxf(v, dpp_f(v)) hipcc emits three -
 // v_mov_b32_dpp, a canonicalising v_max v, v, v of the moved value, then the max: the quantiser's group maxima were 68 of the 249
 // vector instructions of w2's prologue.)  IEEE v_max_f32: a NaN operand is dropped, as f32::max does (quantization.rs:52).
-#ifndef LMRS_NO_ASM_MAX
 #define LMRS_DPP_MAX(name, ctrl)                                                                                       \
     __device__ __forceinline__ float name(float v) {                                                                   \
         float r;                                                                                                       \
@@ -33,29 +32,16 @@ __device__ __forceinline__ int cluster8_sum(int v) {
         asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v));               \
         return r;                                                                                                      \
     }
-#else
-#define LMRS_DPP_MAX(name, ctrl) __device__ __forceinline__ float name(float v);
-#endif
 LMRS_DPP_MAX(max_quad1, "quad_perm:[1,0,3,2]")
 LMRS_DPP_MAX(max_quad2, "quad_perm:[2,3,0,1]")
 LMRS_DPP_MAX(max_half_mirror, "row_half_mirror")
 LMRS_DPP_MAX(max_mirror, "row_mirror")
-#ifdef LMRS_NO_ASM_MAX
-__device__ __forceinline__ float max_quad1(float v) { return fmaxf(v, dpp_f<0xB1>(v)); }
-__device__ __forceinline__ float max_quad2(float v) { return fmaxf(v, dpp_f<0x4E>(v)); }
-__device__ __forceinline__ float max_half_mirror(float v) { return fmaxf(v, dpp_f<0x141>(v)); }
-__device__ __forceinline__ float max_mirror(float v) { return fmaxf(v, dpp_f<0x140>(v)); }
-#endif
 // max(|a.x|, |a.y|, |a.z|, |a.w|, m) in two instructions (the source modifiers are free; fmaxf(fabsf()) canonicalises every input first)
 __device__ __forceinline__ float absmax4(const float4& a, float m) {
-#ifndef LMRS_NO_ASM_MAX
     float r;
     asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a.x), "v"(a.y), "v"(m));
     asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a.z), "v"(a.w), "v"(r));
     return r;
-#else
-    return fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))), m);
-#endif
 }
 // Max over each aligned cluster of LG lanes (LG = 4 .. 32); every lane of the cluster gets it.
 template <int LG> __device__ __forceinline__ float cluster_max(float v) {
@@ -244,14 +230,10 @@ __device__ __forceinline__ int quant_q8_try(float x, float inv, float& dev) {   
 // FMA), q = q0 + r y (one FMA).  oracle/quant_check.c: equal to m / 127.0f for EVERY float in [1e-30, 1e30] (1.67e9 cases) - the range
 // quant_group_sane admits; every other group goes through the slow path, which divides.
 __device__ __forceinline__ float div127_sane(float m) {
-#ifndef LMRS_NO_FAST_DIV127
     const float y = 0x1.020408p-7f;
     const float q0 = m * y;
     const float r = __builtin_fmaf(-127.0f, q0, m);
     return __builtin_fmaf(r, y, q0);
-#else
-    return m / 127.0f;
-#endif
 }
 
 // (the window: the product is provably within 3.1e-5 of the quotient - 1 ulp of v_rcp_f32, the product's and the division's roundings at

@@ -31,6 +31,7 @@
 #include <mutex>
 #include <map>
 #include <set>
+#include <tuple>
 #include <utility>
 
 #include "lmrs_device_math.h"
@@ -906,8 +907,6 @@ __global__ LMRS_STATIC_BOUNDS(N, NTH) void gemv_static_kernel(LMRS_HOT_PARAMS, c
     X(2048, 16, PRO_RMS_QUANT, EPI_QKV, 256, true) X(2048, 32, PRO_QUANT, EPI_RESID, 256, true) X(2048, 8, PRO_RMS_QUANT, EPI_SWIGLU, 256, true) \
     X(8192, 32, PRO_QUANT, EPI_RESID, 512, true) X(2048, 8, PRO_RMS_QUANT, EPI_CLS, 256, true)
 
-static int env_flag(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 // The class (L, threads) for a launch, or L = 0 when the shape has no static kernel (the generic kernel takes it).
 //   * L: enough workgroups to cover the chip with rows split over as few clusters as possible; w1w3 at 16 lanes per row and
 //     two passes per workgroup (measured best of L = 8/16/32 x grid 256/512/1024 at dim 2048).
@@ -919,11 +918,7 @@ static StaticClass static_class(const GemvArgs& a, int pro, int epi) {
     int L = 0, nt = 256;
     if (!q4) {
         if (a.n == 2048) L = glu ? 16 : (a.o >= 8192 ? 8 : 32);
-#ifndef LMRS_PHI_QKV16
         else if (a.n == 3072) L = (a.o >= 8192 && epi != EPI_QKV) ? 16 : 32;     // (qkv: the merged launch runs in one round of resident workgroups - 24 KB tiles balance its passes better than 48 KB ones)
-#else
-        else if (a.n == 3072) L = a.o >= 8192 ? 16 : 32;
-#endif
         else if (a.n == 2304) L = epi == EPI_CLS ? 8 : 16;
         // (round 4, with the grouped quantiser: 32 lanes per row and 256 threads for w2 - half the waves to dispatch, twice the prologue per
         // lane - measured 423 us per step against 414: removed)
@@ -1084,10 +1079,8 @@ int gemv_grid(const GemvArgs& a, int pro, int epi) {
 }
 
 hipError_t launch_gemv(const GemvArgs& a0, int pro, int epi, hipStream_t s, int grid_hint) {
-    static const int order_barrier = env_flag("LMRS_ORDER_BARRIER", 1);
-    static const int chain_spread = env_flag("LMRS_CHAIN_SPREAD", 1);
     GemvArgs a = a0;
-    a.order_barrier = order_barrier; a.chain_spread = chain_spread;
+    a.order_barrier = a.chain_spread = 1;
     if (a.n % kGS != 0 || a.n > kMaxP * 1024 || a.o <= 0) return hipErrorInvalidValue;
     int grid = grid_hint > 0 ? grid_hint : gemv_grid(a, pro, epi);
     if (grid_hint > 0 && (epi == EPI_SWIGLU || epi == EPI_GELU)) {      // a caller's grid must not give a gate/up workgroup more than the three passes its loop takes
@@ -2667,21 +2660,20 @@ int qkv_attn_wave_T(int head_size) { return qa_wave_T(head_size); }
 // therefore capped at what is resident at once (occupancy query, cached per kernel and LDS size); the surplus passes go to workgroups as second passes.
 static int resident_grid_cap(const void* fn, size_t smem) {
     static std::mutex mu;
-    static std::map<std::pair<const void*, size_t>, int> cache;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find({fn, smem});
-    if (it != cache.end()) return it->second;
+    static std::map<std::tuple<int, const void*, size_t>, int> cache;
     int dev = 0, cus = 0, occ = 0;
     (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find({dev, fn, smem});
+    if (it != cache.end()) return it->second;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kBlock, smem) != hipSuccess || occ <= 0) { (void)hipGetLastError(); occ = 0; }
     const int cap = occ * cus;                                      // 0: unknown - no cap
-    cache[{fn, smem}] = cap;
+    cache[{dev, fn, smem}] = cap;
     return cap;
 }
 static int qkv_attn_grid(const void* fn, size_t smem, int grid, int n_heads) {
-    static const int on = env_flag("LMRS_QKV_ONE_ROUND", 1);
-    const int cap = on ? resident_grid_cap(fn, smem) : 0;
+    const int cap = resident_grid_cap(fn, smem);
     return (cap > n_heads + 64 && grid > cap) ? cap : grid;
 }
 
@@ -2708,10 +2700,9 @@ static hipError_t launch_qkv_attn_class(const QkvAttnArgs& a, int grid, size_t g
 
 // wave: one wave per head (contexts up to qkv_attn_wave_T(head_size)); else one workgroup per head (contexts up to max_T)
 hipError_t launch_qkv_attn(const GemvArgs& g0, int pro, const AttnArgs& t0, int* err, int max_T, bool wave, hipStream_t s) {
-    static const int order_barrier = env_flag("LMRS_ORDER_BARRIER", 1);
     if (!qkv_attn_supported(g0, pro, t0) || !g0.gran || !g0.seq || !err) return hipErrorNotSupported;
     QkvAttnArgs a{g0, t0, err};
-    a.g.order_barrier = order_barrier; a.g.chain_spread = env_flag("LMRS_CHAIN_SPREAD", 1);
+    a.g.order_barrier = a.g.chain_spread = 1;
     a.t.chunk = qa_chunk(t0.head_size);
     const StaticClass sc = static_class(a.g, pro, EPI_QKV);
     const int grid = t0.n_heads + gemv_grid(a.g, pro, EPI_QKV);

@@ -1211,8 +1211,8 @@ __global__ __launch_bounds__(NT) void att_scores_wide_kernel(const float* __rest
 // ~60 instructions of f64 work) and the sum is one chain per query, so a block is cut into four workgroups of 16 queries:
 // lane = (query q, key phase ph), 4 waves x 8 x 4 phases = 128 keys per sweep (small workgroups: all of them resident at once).  max, exp and divide are order-free and shared
 // by all lanes; the chain runs in wave 0 over exponentials already masked to +0.0 past p (exact on a sum >= +0) - pure adds.
-// IN_LDS (T <= kAttLdsKeys): the scores live in LDS between the passes - the chain reads LDS, not memory.
-constexpr int kAttLdsKeys = 2048, kAttSQ = 16, kAttSW = 4;                    // queries and waves per softmax workgroup
+// IN_LDS (T <= kAttLdsKeys, lmrs_switches.h): the scores live in LDS between the passes - the chain reads LDS, not memory.
+constexpr int kAttSQ = 16, kAttSW = 4;                                      // queries and waves per softmax workgroup
 template <bool IN_LDS>
 __global__ __launch_bounds__(kAttSW * 64) void att_softmax_kernel(int pos0, int n_tok, float* scratch, int Tmax) {
     constexpr int SWEEP = kAttSW * 32;
@@ -1410,19 +1410,18 @@ __global__ __launch_bounds__(NW * 64) void att_values_kernel(const float* __rest
 }
 
 bool attention_block_supported(const AttnArgs& a, int n_tok) {
-    static const bool off = getenv("LMRS_NO_BLOCK_ATTENTION") != nullptr;
-    if (a.gemma) return !off && n_tok >= 16 && a.head_size == 256 && a.n_heads % a.n_kv_heads == 0;
-    return !off && n_tok >= 16 && (a.head_size == 64 || a.head_size == 96 || a.head_size == 128) && a.n_heads % a.n_kv_heads == 0;
+    if (a.gemma) return n_tok >= 16 && a.head_size == 256 && a.n_heads % a.n_kv_heads == 0;
+    return n_tok >= 16 && (a.head_size == 64 || a.head_size == 96 || a.head_size == 128) && a.n_heads % a.n_kv_heads == 0;
 }
 
-hipError_t launch_attention_block(const AttnArgs& a, int pos0, int n_tok, float* scratch, hipStream_t s) {
+// lds_keys: longest context whose scores stay in LDS (LMRS_ATT_LDS_KEYS); long_forms: Gemma-2's long-batch forms at any length (LMRS_ATT_LONG_BATCH_FORMS)
+hipError_t launch_attention_block(const AttnArgs& a, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s) {
     const int T = pos0 + n_tok, nqb = (n_tok + kAttQB - 1) / kAttQB, nch = (T + 63) / 64;
     const int kv_dim = a.n_kv_heads * a.head_size;
     float* kc = a.k_cache + (size_t)a.layer * kv_dim * (size_t)a.seq_len;
     const float* kraw = a.k_raw; const float* rope = a.k_raw ? a.rope : nullptr;          // k_raw set: RoPE folded into the score kernel's staging (att_stage)
     const float* vc = a.v_cache + (size_t)a.layer * a.seq_len * kv_dim;
-    const char* lk = getenv("LMRS_ATT_LDS_KEYS");                           // tests: force the memory-resident softmax at short lengths
-    const bool in_lds = T <= (lk ? atoi(lk) : kAttLdsKeys);
+    const bool in_lds = T <= lds_keys;
     const size_t sm = (kAttSW * 64 + kAttSQ + (in_lds ? (size_t)(T + 48) * kAttSQ : 0)) * sizeof(float);
     allow_big_lds(reinterpret_cast<const void*>(att_softmax_kernel<true>));
 #define AB(HS_, NW_, DW_)                                                                                                             \
@@ -1443,7 +1442,6 @@ hipError_t launch_attention_block(const AttnArgs& a, int pos0, int n_tok, float*
         int live64 = 0;
         for (int qb = 0; qb < nqb; ++qb) { const int last = qb * kAttQB + kAttQB - 1 < n_tok - 1 ? qb * kAttQB + kAttQB - 1 : n_tok - 1; live64 += (pos0 + last + 1 + 63) / 64; }
         live64 *= a.n_heads;
-        const bool long_forms = getenv("LMRS_ATT_LONG_BATCH_FORMS") != nullptr;   // tests: the long-batch forms (64-key chunks, 64-dim slices) at a length the CPU path finishes quickly
         if (live64 < 512 && !long_forms) {
             constexpr size_t smem32 = (size_t)(64 + 32) * (256 + 4) * sizeof(float);
             allow_big_lds(reinterpret_cast<const void*>(att_scores_wide_kernel<256, 32, 512>));

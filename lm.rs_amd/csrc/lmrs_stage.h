@@ -68,11 +68,7 @@ template <int N, int NTH = kBlk> struct VecGeom {
     static constexpr int NP = (N + PER - 1) / PER;
     static constexpr bool FULL = (N % PER) == 0;
     static constexpr int G = N / 128;
-#ifndef LMRS_NO_GROUPED
     static constexpr int NPG = N / PER >= 8 ? 8 : N / PER >= 4 ? 4 : N / PER >= 2 ? 2 : 0;     // grouped passes
-#else
-    static constexpr int NPG = 0;
-#endif
     static constexpr int LG = NPG ? 32 / NPG : 32;            // lanes that own one quantisation group of the grouped passes
     // first element of thread t's float4 number i (i: a constant after unrolling)
     __device__ static __forceinline__ int elem(int i, int t) {
@@ -186,18 +182,12 @@ __device__ __forceinline__ void vec_rmsnorm(float4 (&v)[(VecGeom<N, NTH>::NP)], 
                 rms_chain32(p, B);
             }
         }
-#ifndef LMRS_SHFL_RMS_TAIL
         // lanes 0..7 hold the chains' sums: v_readlane_b32 (no LDS crossbar round trip as with __shfl); every lane then computes the same scalar
         const int pi = __float_as_int(p);                    // (the builtin is int -> int: a float argument would be CONVERTED)
         const float p0 = __int_as_float(__builtin_amdgcn_readlane(pi, 0)), p1 = __int_as_float(__builtin_amdgcn_readlane(pi, 1));
         const float p2 = __int_as_float(__builtin_amdgcn_readlane(pi, 2)), p3 = __int_as_float(__builtin_amdgcn_readlane(pi, 3));
         const float p4 = __int_as_float(__builtin_amdgcn_readlane(pi, 4)), p5 = __int_as_float(__builtin_amdgcn_readlane(pi, 5));
         const float p6 = __int_as_float(__builtin_amdgcn_readlane(pi, 6)), p7 = __int_as_float(__builtin_amdgcn_readlane(pi, 7));
-#else
-        const int wl = t & 48;                               // lanes 0..7 of this lane's own row hold the chains' sums
-        const float p0 = __shfl(p, wl + 0), p1 = __shfl(p, wl + 1), p2 = __shfl(p, wl + 2), p3 = __shfl(p, wl + 3);
-        const float p4 = __shfl(p, wl + 4), p5 = __shfl(p, wl + 5), p6 = __shfl(p, wl + 6), p7 = __shfl(p, wl + 7);
-#endif
         if ((t & 63) == 0) {
             float ss = reduce_add8(p0, p1, p2, p3, p4, p5, p6, p7);
             // (N a power of two: the quotient and the product by 2^-k are the same real number, rounded once either way - no division sequence)
@@ -483,11 +473,7 @@ __device__ __forceinline__ float tile_consume(const WTile<RowGeom<N, L, kBlk, Q4
 #pragma unroll
         for (int j = 0; j < R::NC; ++j) {
             float carry = 0.0f;
-#ifdef LMRS_SHFL_CARRY                                               // (A/B build: the ds_bpermute hops of rounds 1-3)
-            if (j > 0) carry = __shfl(acc, (lane & ~(L - 1)) + (j - 1) * R::CL);
-#else
             if (j > 0) carry = cluster_carry<L>(acc, j);
-#endif
             if (cl == j) {
                 acc = carry;
 #pragma unroll

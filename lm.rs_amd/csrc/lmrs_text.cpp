@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/lmrs_hip.h"
+#include "lmrs_switches.h"
 
 namespace lmrs { int text_fail(const char* msg); }
 using lmrs::text_fail;
@@ -113,8 +114,7 @@ extern "C" int lmrs_tokenizer_create(const uint8_t* data, size_t len, lmrs_token
         if (!valid_utf8(data + off, sl)) { delete t; return text_fail("Error reading token string"); }
         t->vocab.emplace_back(reinterpret_cast<const char*>(data + off), sl); off += sl;
     }
-    const char* fl = getenv("LMRS_BSEARCH_FLAVOUR");
-    t->bsearch_flavour = fl ? atoi(fl) : 0;
+    t->bsearch_flavour = lmrs::read_switches().bsearch_flavour;
     *out = t;
     return 0;
     } catch (...) { delete t; return text_fail("out of memory while reading the tokenizer file"); }   // nothing may unwind through the C ABI

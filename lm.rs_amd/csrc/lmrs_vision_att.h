@@ -2,10 +2,7 @@
 #pragma once
 
 constexpr int kVisHS = 64, kVisQB = 64;
-#ifndef LMRS_VIS_KC
-#define LMRS_VIS_KC 24
-#endif
-constexpr int kVisKC = LMRS_VIS_KC;            // keys per score wave
+constexpr int kVisKC = 24;                     // keys per score wave
 __host__ __device__ static int vis_key_chunks(int T) { return (T + kVisKC - 1) / kVisKC; }
 // (+ the per-chunk maxima, one row of 64 per chunk of kVisKC keys, and the 64 row sums)
 __host__ __device__ static size_t vis_slab_floats(int T) { return (size_t)T * kVisQB + 8 * kVisHS * kVisQB + (size_t)(vis_key_chunks(T) + 1) * kVisQB; }

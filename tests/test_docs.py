@@ -43,3 +43,31 @@ def test_every_file_the_documents_name_exists():
                     if not glob.glob(os.path.join(ROOT, e.replace("…", "*"))):
                         missing.add((doc, e))
     assert not missing, f"named in a document but not in the tree: {sorted(missing)}"
+
+
+def _switch_reader():
+    """(body of read_switches in lmrs_switches.h, the header's text with that body cut out)"""
+    txt = open(os.path.join(ROOT, "lm.rs_amd", "csrc", "lmrs_switches.h"), encoding="utf-8").read()
+    m = re.search(r"^inline Switches read_switches\(\) \{\n.*?^\}\n", txt, re.M | re.S)
+    assert m, "lmrs_switches.h: read_switches() not found"
+    return m.group(0), txt[:m.start()] + txt[m.end():]
+
+
+def test_every_library_switch_is_read_once_and_documented():
+    """The library reads its environment switches in read_switches alone (at create), and every one of them has a row in INTEGRATION.md's
+    table of environment switches."""
+    body, rest = _switch_reader()
+    names = set(re.findall(r'getenv\("(LMRS_[A-Z0-9_]+)"\)', body))
+    assert names, "read_switches reads no LMRS_* variable"
+    doc = open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8").read()
+    section = doc.split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    rows = set()
+    for line in section.split("\n"):
+        if line.startswith("| `"):
+            rows |= set(re.findall(r"`(LMRS_[A-Z0-9_]+)", line.split("|")[1]))
+    assert not names - rows, f"switches read by the library without a row in INTEGRATION.md: {sorted(names - rows)}"
+    callers = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "lm.rs_amd", "csrc", "*"))):
+        txt = rest if path.endswith("lmrs_switches.h") else open(path, encoding="utf-8", errors="replace").read()
+        callers += [f"{os.path.basename(path)}:{n + 1}" for n, l in enumerate(txt.split("\n")) if re.search(r"\bgetenv\s*\(", l)]
+    assert not callers, f"getenv outside read_switches (lmrs_switches.h): {callers}"
