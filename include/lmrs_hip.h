@@ -140,6 +140,28 @@ int lmrs_fill_kv_cache(lmrs_ctx* ctx, float* embeddings, uint32_t n, uint32_t cu
 int lmrs_generate_greedy(lmrs_ctx* ctx, const uint32_t* prompt, size_t n_prompt, uint32_t n_new,
                          uint32_t start_pos, uint32_t* out_tokens, double* seconds);
 
+/* ---- scoring a token sequence (extensions, no reference counterpart) -------------------
+ * Both are equivalent to calling Transformer::forward (src/transformer.rs:316-384) once per token: tokens[t] at position
+ * start_pos + t for t = 0 .. n-1, in order.  K/V rows start_pos .. start_pos+n-1 are left as those calls leave them.
+ * Where the shape allows (Q8_0 / Q4_0 Llama and Phi files the batched fill_kv_cache takes, classifier rows a multiple of 16,
+ * n > 1) the layers and the classifier run over the whole batch on the int8 matrix cores; Gemma-2, f32 files and other
+ * shapes run the decode step token by token.  Same values either way.  One-GPU contexts only: contexts of
+ * lmrs_create_sharded / lmrs_group_create are refused.  Errors (NULL arguments, n == 0, start_pos + n > seq_len, a token
+ * >= vocab_size, a sharded context) are reported before any device work and leave the context usable.
+ *
+ * lmrs_forward_tokens: logits[t*vocab .. (t+1)*vocab) = bit for bit what lmrs_forward(tokens[t], start_pos + t) returns after
+ *   the calls for 0..t-1, for every t < n (the unwritten vocab % 4 tail of a Q8_0 / f32 classifier included, as 0.0). */
+int lmrs_forward_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos, float* logits /* n*vocab */);
+/* lmrs_score_tokens: the same pass with the logits kept on the device.
+ *   argmax[t] (n entries, may be NULL): Sampler::sample_argmax of position t (sampler.rs:29-41: first index of the maximum, the
+ *     unwritten vocab % 4 tail counting as 0.0), as lmrs_forward_argmax.
+ *   logprobs[t] (n-1 entries, may be NULL): log softmax(logits_t)[tokens[t+1]], defined as follows.  m = the f32 maximum of the
+ *     vocab_size logits, widened to double; lp = (double)l[y] - m - log(sum_i exp((double)l_i - m)), the sum in double over all
+ *     vocab_size logits (zero tail included); logprobs[t] = lp rounded once to float.
+ *   *sum_logprob (may be NULL): the sum of the n-1 unrounded lp, in double, in position order (0.0 for n = 1). */
+int lmrs_score_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos,
+                      float* logprobs, uint32_t* argmax, double* sum_logprob);
+
 const char* lmrs_last_error(void);
 
 /* ---- L2 free functions, for unit parity (host pointers in and out) ------------------

@@ -25,7 +25,8 @@ Q_NONE, Q8_0, Q4_0 = 0, 1, 2
 # every symbol include/lmrs_hip.h declares (tests/test_abi.py checks the header against this list)
 EXPORTS = [
     "lmrs_create", "lmrs_create_sharded", "lmrs_comm_unique_id", "lmrs_destroy", "lmrs_get_args", "lmrs_forward",
-    "lmrs_forward_argmax", "lmrs_get_embeddings", "lmrs_fill_kv_cache", "lmrs_generate_greedy", "lmrs_last_error",
+    "lmrs_forward_argmax", "lmrs_get_embeddings", "lmrs_fill_kv_cache", "lmrs_generate_greedy", "lmrs_forward_tokens", "lmrs_score_tokens",
+    "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
     "lmrs_group_create", "lmrs_group_forward", "lmrs_shard_plan", "lmrs_shard_uses_graph", "lmrs_comm_ranks", "lmrs_p2p_handle", "lmrs_p2p_connect",
@@ -87,6 +88,8 @@ def lib():
         L.lmrs_get_embeddings.argtypes = [vp, vp, sz, vp]
         L.lmrs_fill_kv_cache.argtypes = [vp, vp, u32, u32, C.POINTER(u32)]
         L.lmrs_generate_greedy.argtypes = [vp, vp, sz, u32, u32, vp, C.POINTER(C.c_double)]
+        L.lmrs_forward_tokens.argtypes = [vp, vp, sz, u32, vp]
+        L.lmrs_score_tokens.argtypes = [vp, vp, sz, u32, vp, vp, C.POINTER(C.c_double)]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.lmrs_op_matmul_q4.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz]
         L.lmrs_op_quantize.argtypes = [C.c_int, vp, vp, vp, sz, sz]
@@ -218,6 +221,21 @@ class Transformer:
         sec = C.c_double()
         _chk(lib().lmrs_generate_greedy(self._h, _p(pr), pr.size, n_new, start_pos, _p(out), C.byref(sec)))
         return (out, sec.value) if timing else out
+
+    def forward_tokens(self, tokens, start_pos: int = 0) -> np.ndarray:
+        """-> float32 [n, vocab_size]: row t = forward(tokens[t], start_pos + t) after the calls for 0..t-1 (lmrs_forward_tokens)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        out = np.empty((t.size, self.args.vocab_size), np.float32)
+        _chk(lib().lmrs_forward_tokens(self._h, _p(t), t.size, start_pos, _p(out)))
+        return out
+
+    def score(self, tokens, start_pos: int = 0):
+        """-> (logprobs float32 [n-1]: log softmax(logits_t)[tokens[t+1]], argmax uint32 [n], sum of the log-probabilities in double)
+        for the same pass as forward_tokens, the logits kept on the device (lmrs_score_tokens)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        lp = np.empty(max(t.size - 1, 0), np.float32); am = np.empty(t.size, np.uint32); s = C.c_double()
+        _chk(lib().lmrs_score_tokens(self._h, _p(t), t.size, start_pos, _p(lp), _p(am), C.byref(s)))
+        return lp, am, s.value
 
     def kv_row(self, which: int, layer: int, pos: int) -> np.ndarray:
         """Verification aid: one KV-cache row in the reference's layout (which: 0 key, 1 value)."""

@@ -30,6 +30,7 @@
 #include "../../include/lmrs_hip.h"
 #include "lmrs_format.h"
 #include "lmrs_kernels.h"
+#include "lmrs_score.h"
 #include "lmrs_switches.h"
 
 using namespace lmrs;
@@ -124,6 +125,9 @@ struct lmrs_ctx {
     // ---- final argmax folded into the classifier launch (ClsTail): packed partials
     bool cls_tail = false; unsigned long long* part_pk = nullptr; unsigned* cls_seq = nullptr;
     int inj_fail_connect = 0, inj_stall_seg = -1; long long inj_stall_ticks = 0;      // lmrs_debug_inject
+    // lmrs_forward_tokens / lmrs_score_tokens (allocated on first use): the [sc_rows][vocab] logits block, the reduction's chunk summaries,
+    // its per-position results on the device and their pinned host copy
+    float* sc_logits = nullptr; int sc_rows = 0; ScorePart* sc_part = nullptr; double* sc_lp = nullptr; uint32_t* sc_idx = nullptr; char* h_sc = nullptr;
 
     template <class T> T* alloc(size_t count) {
         size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
@@ -1107,6 +1111,8 @@ extern "C" void lmrs_destroy(lmrs_ctx* c) {
     for (auto& g : c->g_multi) if (g) (void)hipGraphExecDestroy(g);
     for (void* q : {(void*)c->pf_x, (void*)c->pf_q, (void*)c->pf_k, (void*)c->pf_ao, (void*)c->pf_h, (void*)c->pf_xq, (void*)c->pf_xs, (void*)c->pf_t, (void*)c->pf_att}) if (q) (void)hipFree(q);
     for (float* q : c->scales_t) if (q) (void)hipFree(q);
+    for (void* q : {(void*)c->sc_logits, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_idx}) if (q) (void)hipFree(q);
+    if (c->h_sc) (void)hipHostFree(c->h_sc);
     if (c->pfx_owned) { if (c->pfx_att) (void)hipFree(c->pfx_att); if (c->pfx_h) (void)hipFree(c->pfx_h); if (c->pfx_x) (void)hipFree(c->pfx_x); }
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->h_logits) (void)hipHostFree(c->h_logits);
@@ -1596,6 +1602,143 @@ extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t 
     if (n_new) memcpy(out_tokens, c->h_tok, (size_t)n_new * 4);
     if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
     return 0;
+}
+
+// ------------------------------------------------------------------ scoring: the logits of every position of a token sequence
+// (lmrs_forward_tokens) and the log-probability of each next token (lmrs_score_tokens); no reference counterpart - n calls of
+// Transformer::forward (transformer.rs:316-384), value for value.
+
+constexpr size_t kScoreBlockBytes = (size_t)512 << 20;     // the [tokens][vocab] logits block: at most 512 MiB (Llama-3.2-1B: 263 MB for 512 tokens)
+
+// The batched path: forward_layer over the whole sequence (prefill_pass: the int8 matrix-core GEMMs), then the final rmsnorm + quantise of every
+// token and the classifier as ONE GEMM over the token batch.  Both give what the decode step gives, bit for bit.  Not taken:
+//   * Gemma-2.  The batched layers test Gemma's sliding window against the pass's FIRST position (att_scores_wide_kernel, lmrs_prefill.inc:
+//     wpos = pos0 - the reference's batched quirk, the u32 `pos - t` of transformer.rs:525), so keys of the same batch would be masked that
+//     sequential forward calls keep; Gemma also scales its embeddings by sqrt(dim) in forward only, and soft-caps the logits.
+//   * a classifier whose written rows are not a multiple of 16 (launch_gemm_q8 runs whole 16-row tiles; e.g. a vocabulary of 4102);
+//   * one token (that is one decode step) and everything prefill_batched_ok refuses (f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1).
+// Those run the decode step token by token, as lmrs_generate_greedy feeds a prompt.
+static bool score_batched_ok(const lmrs_ctx* c, size_t n) {
+    return n > 1 && prefill_batched_ok(c) && c->args.model_type != LMRS_GEMMA && cls_rows(c) % 16 == 0;
+}
+
+// all or nothing, like prefill_alloc; `block`: the logits block too (forward_tokens and the batched path need it, token-by-token scoring does not)
+static int score_alloc(lmrs_ctx* c, bool block) {
+    const size_t V = c->args.vocab_size, T = c->args.seq_len, S = (size_t)score_chunks((int)V);
+    const size_t rows = std::min<size_t>(kPrefillTokens, std::max<size_t>(1, kScoreBlockBytes / (V * 4)));
+    if (!c->sc_part) {
+        bool ok = hipMalloc(reinterpret_cast<void**>(&c->sc_part), rows * S * sizeof(ScorePart)) == hipSuccess;
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&c->sc_lp), T * 8) == hipSuccess;
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&c->sc_idx), T * 4) == hipSuccess;
+        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_sc), T * 12, hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (void** p : {(void**)&c->sc_part, (void**)&c->sc_lp, (void**)&c->sc_idx}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+            if (c->h_sc) { (void)hipHostFree(c->h_sc); c->h_sc = nullptr; }
+            return fail("scoring buffers: out of memory");
+        }
+    }
+    if (block && !c->sc_logits) {
+        if (hipMalloc(reinterpret_cast<void**>(&c->sc_logits), rows * V * 4) != hipSuccess) {
+            (void)hipGetLastError(); c->sc_logits = nullptr;
+            return fail("scoring logits block (" + std::to_string(rows * V * 4 >> 20) + " MiB): out of memory");
+        }
+        c->sc_rows = (int)rows;
+    }
+    return 0;
+}
+
+// out_logits != null: lmrs_forward_tokens (n x vocab floats to the host); else lmrs_score_tokens' results
+static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* out_logits, float* logprobs, uint32_t* argmax,
+                       double* sum_logprob) {
+    if (n == 0) return fail("no tokens to score (n == 0)");
+    if (!c || !tokens) return fail("NULL argument");
+    if ((size_t)start_pos + n > c->args.seq_len) return fail("start_pos + n exceeds seq_len");
+    for (size_t i = 0; i < n; ++i) if (tokens[i] >= c->args.vocab_size) return fail("token " + std::to_string(i) + " out of range");
+    if (c->world > 1 || c->comm || c->p2p)
+        return fail("scoring runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
+    HIP_OK(hipSetDevice(c->device));
+    const bool batched = score_batched_ok(c, n);
+    if (score_alloc(c, batched || out_logits)) return -1;
+    const int V = (int)c->args.vocab_size;
+    memcpy(c->h_tok, tokens, n * 4);
+    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+    // rows r0 .. r0 + m - 1 of the sequence, row stride ld, the first `written` columns written (the rest is the classifier's zero tail)
+    auto reduce = [&](const float* rows, int ld, int written, int m, size_t r0) -> int {
+        ScoreArgs s{rows, ld, written, V, m, c->tokens + start_pos + r0 + 1, (int)std::max<long long>(0, (long long)n - 1 - (long long)r0),
+                    c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
+        HIP_OK(launch_score_rows(s, c->stream));
+        return 0;
+    };
+    auto copy_out = [&](const float* rows, int ld, int m, size_t r0) -> int {
+        float* dst = out_logits + r0 * (size_t)V;
+        if (ld == V) { HIP_OK(hipMemcpyAsync(dst, rows, (size_t)m * V * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
+        for (int r = 0; r < m; ++r) memset(dst + (size_t)r * V + ld, 0, (size_t)(V - ld) * 4);   // the unwritten tail [cls_rows, vocab)
+        HIP_OK(hipMemcpy2DAsync(dst, (size_t)V * 4, rows, (size_t)ld * 4, (size_t)ld * 4, m, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    if (batched) {
+        if (prefill_alloc(c)) return -1;
+        const lmrs_args& a = c->args;
+        const int dim = (int)a.dim, o = cls_rows(c);
+        if (set_state(c, start_pos, 0, (int)start_pos)) return -1;
+        for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
+            const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
+            HIP_OK(launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + start_pos + i0, m, dim, c->pf_x, c->stream));
+            if (prefill_pass(c, m, (int)(start_pos + i0))) return -1;
+            // final rmsnorm + quantise of every token (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372)
+            HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, 0, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
+            for (int j0 = 0; j0 < m; j0 += c->sc_rows) {
+                const int mj = std::min(c->sc_rows, m - j0);
+                GemmArgs g{};
+                g.wq = c->cls_q; g.ws = c->cls_s; g.xq = c->pf_xq + (size_t)j0 * dim; g.xs = c->pf_xs + (size_t)j0 * (dim / 128);
+                g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits;
+                HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
+                if (out_logits ? copy_out(c->sc_logits, o, mj, i0 + j0) : reduce(c->sc_logits, o, o, mj, i0 + j0)) return -1;
+            }
+        }
+        if (set_state(c, start_pos + (uint32_t)n, 0)) return -1;
+    } else {
+        // the decode step per token; prompt_end = start_pos + n: every step embeds the next GIVEN token (lmrs_generate_greedy's prompt phase)
+        if (set_state(c, start_pos, start_pos + (uint32_t)n)) return -1;
+        HIP_OK(launch_embed(embed_args(c), c->stream));
+        size_t r0 = 0;                                       // first position held in the logits block (forward_tokens)
+        for (size_t t = 0; t < n; ++t) {
+            if (launch_step(c, start_pos + (uint32_t)t)) return -1;
+            if (!out_logits) { if (reduce(c->logits, V, V, 1, t)) return -1; continue; }
+            HIP_OK(hipMemcpyAsync(c->sc_logits + (t - r0) * V, c->logits, (size_t)V * 4, hipMemcpyDeviceToDevice, c->stream));
+            if (t + 1 - r0 == (size_t)c->sc_rows || t + 1 == n) {
+                if (copy_out(c->sc_logits, V, (int)(t + 1 - r0), r0)) return -1;
+                r0 = t + 1;
+            }
+        }
+    }
+    double* h_lp = reinterpret_cast<double*>(c->h_sc);
+    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8);
+    if (!out_logits) {
+        if (n > 1) HIP_OK(hipMemcpyAsync(h_lp, c->sc_lp, (n - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(h_idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (queue_err(c)) return -1;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (check_err(c)) return -1;
+    if (!out_logits) {
+        double sum = 0.0;
+        for (size_t t = 0; t + 1 < n; ++t) { if (logprobs) logprobs[t] = (float)h_lp[t]; sum += h_lp[t]; }
+        if (argmax) memcpy(argmax, h_idx, n * 4);
+        if (sum_logprob) *sum_logprob = sum;
+    }
+    return 0;
+}
+
+extern "C" int lmrs_forward_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* logits) {
+    if (!logits) return fail("NULL argument");
+    return tokens_pass(c, tokens, n, start_pos, logits, nullptr, nullptr, nullptr);
+}
+
+extern "C" int lmrs_score_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* logprobs, uint32_t* argmax,
+                                 double* sum_logprob) {
+    return tokens_pass(c, tokens, n, start_pos, nullptr, logprobs, argmax, sum_logprob);
 }
 
 // ------------------------------------------------------------------ measurement hooks

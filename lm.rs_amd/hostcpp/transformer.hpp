@@ -59,6 +59,21 @@ public:
         check(lmrs_generate_greedy(ctx_, prompt.data(), prompt.size(), n_new, start_pos, out.data(), seconds));
         return out;
     }
+    // Extensions (no reference counterpart): one forward per token of `tokens` from position start_pos, in one call.
+    // forward_tokens: n x vocab_size logits, row t = forward(tokens[t], start_pos + t).
+    std::vector<float> forward_tokens(const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) {
+        std::vector<float> out(tokens.size() * static_cast<std::size_t>(args.vocab_size));
+        check(lmrs_forward_tokens(ctx_, tokens.data(), tokens.size(), start_pos, out.data()));
+        return out;
+    }
+    // score: log softmax(logits_t)[tokens[t+1]] for t < n-1, the argmax of every position, and the sum of the log-probabilities (double).
+    struct Scores { std::vector<float> logprobs; std::vector<std::uint32_t> argmax; double sum_logprob = 0.0; };
+    Scores score(const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) {
+        Scores s;
+        s.logprobs.resize(tokens.empty() ? 0 : tokens.size() - 1); s.argmax.resize(tokens.size());
+        check(lmrs_score_tokens(ctx_, tokens.data(), tokens.size(), start_pos, s.logprobs.data(), s.argmax.data(), &s.sum_logprob));
+        return s;
+    }
 
 private:
     Transformer() = default;

@@ -35,6 +35,9 @@ extern "C" {
     pub fn lmrs_fill_kv_cache(ctx: *mut LmrsCtx, embeddings: *mut f32, n: u32, curr_pos: u32, new_pos: *mut u32) -> c_int;
     pub fn lmrs_generate_greedy(ctx: *mut LmrsCtx, prompt: *const u32, n_prompt: usize, n_new: u32, start_pos: u32,
                                 out_tokens: *mut u32, seconds: *mut f64) -> c_int;
+    pub fn lmrs_forward_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, logits: *mut f32) -> c_int;
+    pub fn lmrs_score_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, logprobs: *mut f32, argmax: *mut u32,
+                             sum_logprob: *mut f64) -> c_int;
     pub fn lmrs_last_error() -> *const c_char;
 
     pub fn lmrs_vision_create(section: *const u8, len: usize, device: c_int, out: *mut *mut LmrsVision, bytes_consumed: *mut usize) -> c_int;

@@ -118,6 +118,26 @@ impl<'a> Transformer<'a> {
         });
         out
     }
+
+    /// Extension (no reference counterpart): `forward` once per token of `tokens` from position `start_pos`, in one call.  Row t of
+    /// the result (`vocab_size` logits each) is what `forward(tokens[t], start_pos + t)` returns after the calls for 0..t-1.
+    pub fn forward_tokens(&mut self, tokens: &[u32], start_pos: u32) -> Vec<f32> {
+        let mut out = vec![0.0f32; tokens.len() * self.args.vocab_size as usize];
+        check(unsafe { ffi::lmrs_forward_tokens(self.ctx, tokens.as_ptr(), tokens.len(), start_pos, out.as_mut_ptr()) });
+        out
+    }
+
+    /// Extension: the same pass with the logits kept on the device.  Returns (log softmax(logits_t)[tokens[t+1]] for t < n-1,
+    /// `Sampler::sample_argmax` of every position, the sum of the log-probabilities in f64).
+    pub fn score(&mut self, tokens: &[u32], start_pos: u32) -> (Vec<f32>, Vec<u32>, f64) {
+        let mut logprobs = vec![0.0f32; tokens.len().saturating_sub(1)];
+        let mut argmax = vec![0u32; tokens.len()];
+        let mut sum: f64 = 0.0;
+        check(unsafe {
+            ffi::lmrs_score_tokens(self.ctx, tokens.as_ptr(), tokens.len(), start_pos, logprobs.as_mut_ptr(), argmax.as_mut_ptr(), &mut sum)
+        });
+        (logprobs, argmax, sum)
+    }
 }
 
 /// The communicator id rank 0 makes for `new_sharded`.
