@@ -132,9 +132,10 @@ int lmrs_get_embeddings(const lmrs_ctx* ctx, const uint32_t* tokens, size_t n, f
 int lmrs_fill_kv_cache(lmrs_ctx* ctx, float* embeddings, uint32_t n, uint32_t curr_pos, uint32_t* new_pos);
 
 /* ---- the generation loop of src/bin/chat.rs:188-222 on token IDs, greedy ------------
- * Feeds prompt[0..n_prompt) token by token starting at position start_pos (sampler
- * output ignored while the prompt lasts, as chat.rs does), then n_new-1 further steps
- * feeding back the argmax.  out_tokens[i] (i < n_new) = i-th generated token, i.e. the
+ * Feeds prompt[0..n_prompt) starting at position start_pos (sampler output ignored while
+ * the prompt lasts, as chat.rs does: all but the last prompt token go through the batched
+ * pass where lmrs_tokens_path(n_prompt - 1) says so, else token by token - same values),
+ * then n_new-1 further steps feeding back the argmax.  out_tokens[i] (i < n_new) = i-th generated token, i.e. the
  * argmax after step n_prompt-1+i.  Runs device-resident: one host sync at the end.
  * *seconds (optional) = wall time of the whole call's device work (HIP events). */
 int lmrs_generate_greedy(lmrs_ctx* ctx, const uint32_t* prompt, size_t n_prompt, uint32_t n_new,
@@ -143,9 +144,10 @@ int lmrs_generate_greedy(lmrs_ctx* ctx, const uint32_t* prompt, size_t n_prompt,
 /* ---- scoring a token sequence (extensions, no reference counterpart) -------------------
  * Both are equivalent to calling Transformer::forward (src/transformer.rs:316-384) once per token: tokens[t] at position
  * start_pos + t for t = 0 .. n-1, in order.  K/V rows start_pos .. start_pos+n-1 are left as those calls leave them.
- * Where the shape allows (Q8_0 / Q4_0 Llama and Phi files the batched fill_kv_cache takes, classifier rows a multiple of 16,
- * n > 1) the layers and the classifier run over the whole batch on the int8 matrix cores; Gemma-2, f32 files and other
- * shapes run the decode step token by token.  Same values either way.  One-GPU contexts only: contexts of
+ * Where the shape allows (Q8_0 / Q4_0 Llama, Phi and Gemma-2 files the batched fill_kv_cache takes, classifier rows a multiple
+ * of 16, n > 1) the layers and the classifier run over the whole batch on the int8 matrix cores - on Gemma-2 with forward's
+ * semantics, not fill_kv_cache's: embedding rows scaled by sqrt(dim), the 4096-key window tested per position, the first `dim`
+ * logits soft-capped; f32 files and other shapes run the decode step token by token.  Same values either way.  One-GPU contexts only: contexts of
  * lmrs_create_sharded / lmrs_group_create are refused.  Errors (NULL arguments, n == 0, start_pos + n > seq_len, a token
  * >= vocab_size, a sharded context) are reported before any device work and leave the context usable.
  *
@@ -161,6 +163,22 @@ int lmrs_forward_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_
  *   *sum_logprob (may be NULL): the sum of the n-1 unrounded lp, in double, in position order (0.0 for n = 1). */
 int lmrs_score_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos,
                       float* logprobs, uint32_t* argmax, double* sum_logprob);
+
+/* ---- a prompt from token ids (extension, no reference counterpart) ---------------------
+ * Equivalent to calling Transformer::forward (src/transformer.rs:316-384) for tokens[t] at position start_pos + t, t = 0 .. n-1,
+ * and discarding every logits vector: K/V rows start_pos .. start_pos+n-1 are left bit for bit as those calls leave them.
+ * The logits buffer of lmrs_forward is unspecified afterwards.  *new_pos (may be NULL) = start_pos + n.
+ * The token ids go to the device and the layers run over the run on the int8 matrix cores, 512 tokens at a time, where
+ * lmrs_tokens_path says so (neither the final norm nor the classifier runs); else one decode step per token with the classifier's
+ * result ignored.  Same rows either way.  Unlike lmrs_get_embeddings + lmrs_fill_kv_cache this has forward's semantics on Gemma-2
+ * (rows scaled by sqrt(dim), the window per position) and moves no activations through host memory.  Row-sharded contexts with a
+ * transport are accepted (every rank makes the same call).  Errors (NULL arguments, n == 0, start_pos + n > seq_len, a token >=
+ * vocab_size) are reported before any device work and leave the context usable. */
+int lmrs_prefill_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t* new_pos);
+/* Which path lmrs_prefill_tokens (and the prompt of lmrs_generate_greedy, for a prompt of n + 1 tokens) takes for a run of n tokens on
+ * this context: *batched = 1 the matrix-core pass, 0 token by token.  (lmrs_forward_tokens / lmrs_score_tokens keep their own rule:
+ * n > 1, a batched-eligible file, classifier rows a multiple of 16.) */
+int lmrs_tokens_path(const lmrs_ctx* ctx, size_t n, int* batched);
 
 const char* lmrs_last_error(void);
 

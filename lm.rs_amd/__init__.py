@@ -26,6 +26,7 @@ Q_NONE, Q8_0, Q4_0 = 0, 1, 2
 EXPORTS = [
     "lmrs_create", "lmrs_create_sharded", "lmrs_comm_unique_id", "lmrs_destroy", "lmrs_get_args", "lmrs_forward",
     "lmrs_forward_argmax", "lmrs_get_embeddings", "lmrs_fill_kv_cache", "lmrs_generate_greedy", "lmrs_forward_tokens", "lmrs_score_tokens",
+    "lmrs_prefill_tokens", "lmrs_tokens_path",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -90,6 +91,8 @@ def lib():
         L.lmrs_generate_greedy.argtypes = [vp, vp, sz, u32, u32, vp, C.POINTER(C.c_double)]
         L.lmrs_forward_tokens.argtypes = [vp, vp, sz, u32, vp]
         L.lmrs_score_tokens.argtypes = [vp, vp, sz, u32, vp, vp, C.POINTER(C.c_double)]
+        L.lmrs_prefill_tokens.argtypes = [vp, vp, sz, u32, C.POINTER(u32)]
+        L.lmrs_tokens_path.argtypes = [vp, sz, C.POINTER(C.c_int)]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.lmrs_op_matmul_q4.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz]
         L.lmrs_op_quantize.argtypes = [C.c_int, vp, vp, vp, sz, sz]
@@ -236,6 +239,20 @@ class Transformer:
         lp = np.empty(max(t.size - 1, 0), np.float32); am = np.empty(t.size, np.uint32); s = C.c_double()
         _chk(lib().lmrs_score_tokens(self._h, _p(t), t.size, start_pos, _p(lp), _p(am), C.byref(s)))
         return lp, am, s.value
+
+    def prefill_tokens(self, tokens, start_pos: int = 0) -> int:
+        """forward(tokens[t], start_pos + t) for every t with the logits discarded: the K/V rows of a prompt, the token ids going to the
+        device and the layers over the whole run where tokens_path says so (lmrs_prefill_tokens) -> start_pos + n"""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        newp = C.c_uint32()
+        _chk(lib().lmrs_prefill_tokens(self._h, _p(t), t.size, start_pos, C.byref(newp)))
+        return newp.value
+
+    def tokens_path(self, n: int) -> bool:
+        """True: prefill_tokens (and generate_greedy's prompt of n + 1 tokens) runs a run of n tokens as one batched pass (lmrs_tokens_path)"""
+        b = C.c_int()
+        _chk(lib().lmrs_tokens_path(self._h, n, C.byref(b)))
+        return bool(b.value)
 
     def kv_row(self, which: int, layer: int, pos: int) -> np.ndarray:
         """Verification aid: one KV-cache row in the reference's layout (which: 0 key, 1 value)."""

@@ -1548,6 +1548,42 @@ extern "C" int lmrs_fill_kv_cache(lmrs_ctx* c, float* embeddings, uint32_t n, ui
     return 0;
 }
 
+// ------------------------------------------------------------------ runs of token ids through the batched pass
+// A run of n tokens whose logits nobody reads (a prompt: chat.rs:188-193) only has to leave its K/V rows behind.  n calls of Transformer::forward are
+// forward_layer over the batch with three differences that only Gemma-2 shows: forward scales the embedding rows by sqrt(dim) (transformer.rs:326-332;
+// fill_kv_cache takes its rows as given), every call tests the 4096-key window against its OWN position (one forward_layer(sl = n) call tests the
+// first position for all: win_base, lmrs_kernels.h), and the logits' first `dim` columns are soft-capped (tokens_pass).
+// Below a run length the decode steps are cheaper than the pass (its GEMMs run whole token tiles).  Llama / Phi: 8, the measured crossover of
+// lmrs_generate_greedy's prompt (a 16-token pass of Llama-3.2-1B: 1.9 ms, about 4.5 decode steps).  Gemma-2: 8 as well, measured with
+// tools/prompt_rate.py on Gemma-2-2B Q4_0 (profiles/prompt_rate_gemma2b_q4.txt): 4 tokens 4.04 ms batched against 3.37 ms of decode steps, 8
+// tokens 4.01 against 6.71 ms - the smallest measured run at which the pass wins by more than the spread of three repetitions.
+constexpr size_t kTokensBatchMin = 8, kTokensBatchMinGemma = 8;
+static size_t tokens_batch_min(const lmrs_ctx* c) {
+    if (c->sw.tokens_batch_min > 0) return (size_t)c->sw.tokens_batch_min;
+    return c->args.model_type == LMRS_GEMMA ? kTokensBatchMinGemma : kTokensBatchMin;
+}
+static bool tokens_batched(const lmrs_ctx* c, size_t n) { return n >= tokens_batch_min(c) && (prefill_batched_ok(c) || prefill_tp_ok(c)); }
+
+// the state of a batched pass that stands for forward calls from position pos on (only Gemma's kernels read it)
+static int begin_token_pass(lmrs_ctx* c, uint32_t pos) {
+    return c->args.model_type == LMRS_GEMMA ? set_state(c, pos, 0, kWinPerQuery) : 0;
+}
+static hipError_t token_rows(lmrs_ctx* c, uint32_t pos, int m) {        // embedding rows of c->tokens[pos .. pos + m) -> pf_x, as forward builds them
+    const float scale = c->args.model_type == LMRS_GEMMA ? sqrtf((float)c->args.dim) : 0.0f;
+    return launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + pos, m, (int)c->args.dim, c->pf_x, c->stream, scale);
+}
+// K/V rows start_pos .. start_pos + n - 1 from c->tokens, kPrefillTokens at a time; the caller sets the state that follows
+static int prefill_token_run(lmrs_ctx* c, uint32_t start_pos, size_t n) {
+    if (prefill_alloc(c)) return -1;
+    if (begin_token_pass(c, start_pos)) return -1;
+    for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
+        const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
+        HIP_OK(token_rows(c, start_pos + (uint32_t)i0, m));
+        if (prefill_pass(c, m, (int)(start_pos + i0))) return -1;
+    }
+    return 0;
+}
+
 extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t n_prompt, uint32_t n_new, uint32_t start_pos,
                                     uint32_t* out_tokens, double* seconds) {
     if (!c || !prompt || (!out_tokens && n_new)) return fail("NULL argument");
@@ -1563,15 +1599,9 @@ extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t 
     // prompt tokens except the last only have to leave their K/V rows behind, which is forward_layer over a batch - the
     // matrix-core path of fill_kv_cache, value for value what the per-token passes produce.
     size_t done = 0;
-    if (n_prompt >= 9 && (prefill_batched_ok(c) || prefill_tp_ok(c)) && c->args.model_type != LMRS_GEMMA) {      // (Gemma scales its embeddings in the embed kernel)
-        if (prefill_alloc(c)) return -1;
-        const size_t m_total = n_prompt - 1;
-        for (size_t i0 = 0; i0 < m_total; i0 += kPrefillTokens) {
-            const int m = (int)std::min<size_t>(kPrefillTokens, m_total - i0);
-            HIP_OK(launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + start_pos + i0, m, (int)c->args.dim, c->pf_x, c->stream));
-            if (prefill_pass(c, m, (int)(start_pos + i0))) return -1;
-        }
-        done = m_total;
+    if (tokens_batched(c, n_prompt - 1)) {
+        if (prefill_token_run(c, start_pos, n_prompt - 1)) return -1;
+        done = n_prompt - 1;
     }
     if (set_state(c, start_pos + (uint32_t)done, start_pos + (uint32_t)n_prompt)) return -1;
     HIP_OK(launch_embed(embed_args(c), c->stream));
@@ -1619,7 +1649,7 @@ constexpr size_t kScoreBlockBytes = (size_t)512 << 20;     // the [tokens][vocab
 //   * one token (that is one decode step) and everything prefill_batched_ok refuses (f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1).
 // Those run the decode step token by token, as lmrs_generate_greedy feeds a prompt.
 static bool score_batched_ok(const lmrs_ctx* c, size_t n) {
-    return n > 1 && prefill_batched_ok(c) && c->args.model_type != LMRS_GEMMA && cls_rows(c) % 16 == 0;
+    return n > 1 && prefill_batched_ok(c) && cls_rows(c) % 16 == 0;
 }
 
 // all or nothing, like prefill_alloc; `block`: the logits block too (forward_tokens and the batched path need it, token-by-token scoring does not)
@@ -1681,19 +1711,21 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
         if (prefill_alloc(c)) return -1;
         const lmrs_args& a = c->args;
         const int dim = (int)a.dim, o = cls_rows(c);
-        if (set_state(c, start_pos, 0, (int)start_pos)) return -1;
+        const bool gemma = a.model_type == LMRS_GEMMA;
+        if (set_state(c, start_pos, 0, gemma ? kWinPerQuery : (int)start_pos)) return -1;
         for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
             const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
-            HIP_OK(launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + start_pos + i0, m, dim, c->pf_x, c->stream));
+            HIP_OK(token_rows(c, start_pos + (uint32_t)i0, m));
             if (prefill_pass(c, m, (int)(start_pos + i0))) return -1;
             // final rmsnorm + quantise of every token (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372)
-            HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, 0, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
+            HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
             for (int j0 = 0; j0 < m; j0 += c->sc_rows) {
                 const int mj = std::min(c->sc_rows, m - j0);
                 GemmArgs g{};
                 g.wq = c->cls_q; g.ws = c->cls_s; g.xq = c->pf_xq + (size_t)j0 * dim; g.xs = c->pf_xs + (size_t)j0 * (dim / 128);
                 g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits;
                 HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
+                if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));     // (:375-381)
                 if (out_logits ? copy_out(c->sc_logits, o, mj, i0 + j0) : reduce(c->sc_logits, o, o, mj, i0 + j0)) return -1;
             }
         }
@@ -1739,6 +1771,38 @@ extern "C" int lmrs_forward_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n
 extern "C" int lmrs_score_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* logprobs, uint32_t* argmax,
                                  double* sum_logprob) {
     return tokens_pass(c, tokens, n, start_pos, nullptr, logprobs, argmax, sum_logprob);
+}
+
+// ------------------------------------------------------------------ a prompt from token ids (no reference counterpart: the loop of chat.rs:188-193
+// with every sampler result ignored)
+extern "C" int lmrs_tokens_path(const lmrs_ctx* c, size_t n, int* batched) {
+    if (!c || !batched) return fail("NULL argument");
+    *batched = tokens_batched(c, n) ? 1 : 0;
+    return 0;
+}
+
+extern "C" int lmrs_prefill_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t* new_pos) {
+    if (n == 0) return fail("no tokens to ingest (n == 0)");
+    if (!c || !tokens) return fail("NULL argument");
+    if ((size_t)start_pos + n > c->args.seq_len) return fail("start_pos + n exceeds seq_len");
+    for (size_t i = 0; i < n; ++i) if (tokens[i] >= c->args.vocab_size) return fail("token " + std::to_string(i) + " out of range");
+    HIP_OK(hipSetDevice(c->device));
+    memcpy(c->h_tok, tokens, n * 4);
+    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+    if (tokens_batched(c, n)) {
+        if (prefill_token_run(c, start_pos, n)) return -1;
+        if (set_state(c, start_pos + (uint32_t)n, 0)) return -1;
+    } else {
+        // the decode step per token, prompt_end past the run: every step embeds the next GIVEN token and its classifier's result goes nowhere
+        if (set_state(c, start_pos, start_pos + (uint32_t)n)) return -1;
+        HIP_OK(launch_embed(embed_args(c), c->stream));
+        for (size_t t = 0; t < n; ++t) if (launch_step(c, start_pos + (uint32_t)t)) return -1;
+    }
+    if (queue_err(c)) return -1;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (check_err(c)) return -1;
+    if (new_pos) *new_pos = start_pos + (uint32_t)n;
+    return 0;
 }
 
 // ------------------------------------------------------------------ measurement hooks

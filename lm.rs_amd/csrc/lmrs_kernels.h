@@ -11,8 +11,12 @@ struct DevState {
     int pos;          // position of the token being processed
     int prompt_end;   // absolute position from which the argmax is written back as the next input
     int step_count;   // statistics
-    int win_base;     // >= 0: first position of a batched forward_layer call (Gemma window quirk, see attention_body); < 0: decode
+    int win_base;     // >= 0: first position of a batched forward_layer call (Gemma window quirk, see attention_body); < 0: decode;
+                      // kWinPerQuery: a batched pass that stands for n forward calls - every query tests the window against its own position
 };
+// (any negative win_base makes the per-token attention forms test the window against the token's own position; the block form of the
+// batched pass tells -1, a plain batched call whose state nobody set, from kWinPerQuery)
+constexpr int kWinPerQuery = -2;
 
 enum Prologue { PRO_PREQ = 0, PRO_QUANT = 1, PRO_RMS_QUANT = 2, PRO_ADD_RMS_QUANT = 3 };   // 3: x + rmsnorm(delta), then rmsnorm, quantise (static kernels only)
 enum Epilogue { EPI_STORE = 0, EPI_RESID = 1, EPI_QKV = 2, EPI_SWIGLU = 3, EPI_CLS = 4, EPI_GELU = 5,
@@ -127,7 +131,8 @@ hipError_t launch_embed(const EmbedArgs& a, hipStream_t s);
 hipError_t launch_addvec(float* x, const float* d, int n, hipStream_t st);
 hipError_t launch_addnorm(float* x, const float* delta, const float* w, int n, float eps, hipStream_t st);   // Gemma: x += rmsnorm(delta, 1 + w)
 hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s);
-hipError_t launch_dequant_rows(const void* q, const float* s, int q4, const uint32_t* tokens, int n_tok, int dim, float* out, hipStream_t st);
+// scale != 0: every dequantised value * scale, one f32 multiply (Gemma's sqrt(dim) of transformer.rs:326-332, as embed_kernel)
+hipError_t launch_dequant_rows(const void* q, const float* s, int q4, const uint32_t* tokens, int n_tok, int dim, float* out, hipStream_t st, float scale = 0.0f);
 
 // ---- the parallel part of Sampler::sample (sampler.rs:109-129, temperature != 0): logits[i] /= temperature (:115), the maximum, and
 // logits[i] = exp(logits[i] - max) (functional.rs:126-133) in place.  The sequential chains behind it run on the host (lmrs_sampler_sample_exps).

@@ -2956,13 +2956,17 @@ hipError_t launch_embed(const EmbedArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-__global__ void dequant_rows_kernel(const void* q, const float* s, int q4, const uint32_t* tokens, int dim, float* out) {
+__global__ void dequant_rows_kernel(const void* q, const float* s, int q4, const uint32_t* tokens, int dim, float* out, float scale, int do_scale) {
     const uint32_t token = tokens[blockIdx.x];
-    for (int i = threadIdx.x; i < dim; i += blockDim.x) out[(size_t)blockIdx.x * dim + i] = dequant_elem(q, s, q4, (size_t)token * dim + i);
+    for (int i = threadIdx.x; i < dim; i += blockDim.x) {
+        float v = dequant_elem(q, s, q4, (size_t)token * dim + i);
+        if (do_scale) v = v * scale;                                        // (embed_kernel's multiply)
+        out[(size_t)blockIdx.x * dim + i] = v;
+    }
 }
 
-hipError_t launch_dequant_rows(const void* q, const float* s, int q4, const uint32_t* tokens, int n_tok, int dim, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(dequant_rows_kernel, dim3(n_tok), dim3(256), 0, st, q, s, q4, tokens, dim, out);
+hipError_t launch_dequant_rows(const void* q, const float* s, int q4, const uint32_t* tokens, int n_tok, int dim, float* out, hipStream_t st, float scale) {
+    hipLaunchKernelGGL(dequant_rows_kernel, dim3(n_tok), dim3(256), 0, st, q, s, q4, tokens, dim, out, scale, scale != 0.0f ? 1 : 0);
     return hipGetLastError();
 }
 

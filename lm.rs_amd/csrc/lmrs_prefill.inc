@@ -1139,7 +1139,8 @@ __global__ __launch_bounds__(256) void att_scores_kernel(const float* __restrict
 // The same for Gemma-2's 256-wide heads (transformer.rs:507-526): a lane cannot hold a 256-float query row next to the staged keys, and the chain over
 // the head dims may not be cut - so the dims are walked in TWO passes of 128 with the query half in registers, the 16 partial sums of the wave's 16 keys
 // carried from the first pass to the second (same chain, same order).  Then the soft-cap - score / 50, f64 tanh, * 50 - and the window term with the
-// reference's u32 arithmetic on the FIRST position of the forward_layer call (st->win_base: the quirk attention_body documents).
+// reference's u32 arithmetic on the FIRST position of the forward_layer call (st->win_base: the quirk attention_body documents) - or, when the pass
+// stands for n forward calls (win_base == kWinPerQuery), on each query's OWN position, which is what the decode step tests.
 template <int HS, int NK, int NT>
 __global__ __launch_bounds__(NT) void att_scores_wide_kernel(const float* __restrict__ qrows, float* kc, float* __restrict__ scratch, const DevState* __restrict__ st, const float* __restrict__ k_raw,
                                                               const float* __restrict__ rope, int n_heads, int n_kv_heads, int seq_len, int pos0, int n_tok, int Tmax) {
@@ -1192,7 +1193,7 @@ __global__ __launch_bounds__(NT) void att_scores_wide_kernel(const float* __rest
         }
     }
     const float sqrt_hs = sqrtf((float)HS);
-    const int wb = st->win_base, wpos = wb >= 0 ? wb : pos0;
+    const int wb = st->win_base, wpos = wb >= 0 ? wb : (wb == kWinPerQuery ? b.p : pos0);
 #pragma unroll
     for (int i = 0; i < KW; ++i) {
         if (i < nk) {                                                        // wave-uniform

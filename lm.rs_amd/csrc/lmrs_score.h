@@ -24,4 +24,8 @@ struct ScoreArgs {
 };
 hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t s);
 
+// logits[r * ld + i] = 30 * (float)tanh((double)(logits[r * ld + i] / 30)) for r < rows, i < cols (cols <= ld): Gemma-2's soft-cap of the first
+// `dim` logits (transformer.rs:375-381), the decode classifier epilogue's arithmetic over a block of rows
+hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStream_t s);
+
 }  // namespace lmrs

@@ -7,6 +7,9 @@
 // l[y] - max - log(sum).  Llama's 128 256 logits are 63 workgroups per row: one token alone spreads over a quarter of the chip's CUs,
 // 512 tokens over 32 k workgroups.  The rescaled sum differs from a direct sum of exp(l - max) by a few double ulps, far below the f32
 // rounding of the result.  The summation order depends on the vocabulary size alone: a row gives the same bits in any launch.
+//
+// softcap_rows_kernel: Gemma-2's soft-cap of the first `dim` logits of every row of the block, between the batched classifier GEMM and the
+// reduction (the decode classifier applies it in its epilogue).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -116,7 +119,27 @@ __global__ __launch_bounds__(kLanes) void score_merge_kernel(const ScoreArgs a) 
     }
 }
 
+// Gemma-2's soft-cap of the first `cols` logits (transformer.rs:375-381) over a block of rows: l / 30, (float)tanh((double)l), * 30 - the three
+// roundings of the decode classifier's epilogue (EPI_CLS, lmrs_kernels.hip) with the same device tanh, so a row carries the decode step's bits.
+// grid (ceil(cols / 256), rows)
+__global__ __launch_bounds__(kLanes) void softcap_rows_kernel(float* logits, int ld, int cols) {
+    const int i = blockIdx.x * kLanes + threadIdx.x;
+    if (i >= cols) return;
+    float* p = logits + (size_t)blockIdx.y * ld + i;
+    float v = *p;
+    v = v / 30.0f;
+    v = (float)tanh((double)v);
+    v = v * 30.0f;
+    *p = v;
+}
+
 }  // namespace
+
+hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStream_t s) {
+    if (!logits || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(softcap_rows_kernel, dim3((cols + kLanes - 1) / kLanes, rows), dim3(kLanes), 0, s, logits, ld, cols);
+    return hipGetLastError();
+}
 
 hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t s) {
     if (a.rows <= 0 || a.rows > 65535 || a.vocab <= 0 || a.written < 0 || a.written > a.vocab || a.ld < a.written || !a.part || !a.out_idx ||

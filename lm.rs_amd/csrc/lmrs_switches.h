@@ -11,6 +11,7 @@ constexpr int kAttLdsKeys = 2048;        // longest context whose block-softmax 
 
 struct Switches {
     bool no_batched_prefill = false;     // LMRS_NO_BATCHED_PREFILL: fill_kv_cache and prompts go token by token through the decode kernels
+    int tokens_batch_min = 0;            // LMRS_TOKENS_BATCH_MIN: shortest run of tokens lmrs_prefill_tokens / a prompt batches (0: the measured default; tools/prompt_rate.py)
     bool no_graph = false;               // LMRS_NO_GRAPH: a step's launches enqueued one by one (profiling aid, see launch_step)
     bool debug_timeline = false;         // LMRS_DEBUG_TIMELINE: in-kernel wall-clock stamps
     bool shard_f32_payload = false;      // LMRS_SHARD_F32_PAYLOAD: row shards exchange f32 slices
@@ -33,6 +34,7 @@ inline Switches read_switches() {
     Switches s;
     const char* e;
     s.no_batched_prefill = getenv("LMRS_NO_BATCHED_PREFILL") != nullptr;
+    if ((e = getenv("LMRS_TOKENS_BATCH_MIN"))) { const int k = atoi(e); s.tokens_batch_min = k < 2 ? 2 : k; }
     s.no_graph = getenv("LMRS_NO_GRAPH") != nullptr;
     s.debug_timeline = getenv("LMRS_DEBUG_TIMELINE") != nullptr;
     s.shard_f32_payload = getenv("LMRS_SHARD_F32_PAYLOAD") != nullptr;

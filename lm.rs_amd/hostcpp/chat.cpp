@@ -1,6 +1,11 @@
 // chat.cpp — the reference's chat binary (src/bin/chat.rs) over the C++ mirrors, text in / text out: the same command line
 // (--model, --tokenizer, --temperature, --top-p, --seed, --show-metrics), the same loop (:148-227): read a line, wrap it in the
-// model family's chat template, feed the prompt token by token, sample until EOS, print the pieces.  Llama's system prompt with
+// model family's chat template, feed the prompt, sample until EOS, print the pieces.  The reference feeds a prompt one forward per token and
+// throws every sampler result but the last away (:188-193, :214-215).  Where those discarded calls leave no trace in the sampler - temperature 0
+// (argmax) and sample_mult (top-p <= 0 or >= 1): the random number is random_f32(seed) of a seed that never advances - all but the last prompt
+// token go in ONE prefill_tokens call and the loop continues at the last one.  sample_topp is different: it sorts its WHOLE candidate vector on
+// every call (sampler.rs:81), entries of earlier calls included, so a prompt step's probabilities can decide a later draw: with 0 < top-p < 1
+// the prompt is fed step by step as before.  --show-metrics counts the loop's steps: prefilled tokens and their time are in neither figure.  Llama's system prompt with
 // today's date (:159-169) is reproduced; --date "23 Sep 2024" pins it (the reference always uses the clock), which makes runs
 // repeatable.  Images (--image) need PHI3VProcessor::process, host image code outside this library: see image_prefill.cpp.
 // At temperature 0 the sampler's argmax runs on the device (forward_argmax): no logits leave HBM.
@@ -26,6 +31,7 @@ int main(int argc, char** argv) {
     float temperature = 0.7f, top_p = 0.9f;
     bool have_seed = false, show_metrics = false; std::uint64_t seed = 0;
     long max_tokens = -1;                                   // (not in the reference) stop after this many sampled tokens in total: for tests
+    long turn_tokens = -1;                                  // (not in the reference) the token sampled as a turn's N-th is replaced by EOS: turns of random-weight test models end
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -37,6 +43,7 @@ int main(int argc, char** argv) {
         else if (a == "--show-metrics") show_metrics = true;
         else if (a == "--date") date = val();
         else if (a == "--max-tokens") max_tokens = std::atol(val());
+        else if (a == "--turn-tokens") turn_tokens = std::atol(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (model_path.empty()) { std::fprintf(stderr, "usage: %s --model model.lmrs [--tokenizer tokenizer.bin] [--temperature T] [--top-p P] [--seed S] [--show-metrics]\n", argv[0]); return 2; }
@@ -58,7 +65,8 @@ int main(int argc, char** argv) {
         std::size_t user_idx = 0, num_prompt_tokens = 0;
         float total_tokens = 0.0f, total_duration = 0.0f;
         std::vector<std::uint32_t> prompt_tokens;
-        long sampled = 0;
+        long sampled = 0, turn_sampled = 0;
+        const bool prompt_steps_leave_no_trace = temperature == 0.0f || top_p <= 0.0f || top_p >= 1.0f;
         for (;;) {
             if (user_turn) {
                 std::printf("You: "); std::fflush(stdout);
@@ -80,6 +88,11 @@ int main(int argc, char** argv) {
                 num_prompt_tokens = prompt_tokens.size();
                 user_turn = false; user_idx = 0;
                 std::printf("Assistant:\n");
+                turn_sampled = 0;
+                if (num_prompt_tokens > 1 && prompt_steps_leave_no_trace) {                       // the K/V rows of all but the last prompt token
+                    pos = model.prefill_tokens(prompt_tokens.data(), num_prompt_tokens - 1, pos);
+                    user_idx = num_prompt_tokens - 1;
+                }
             }
             if (user_idx < num_prompt_tokens) token = prompt_tokens[user_idx++];                  // :188-193
             else token = next;
@@ -94,6 +107,7 @@ int main(int argc, char** argv) {
             if (temperature == 0.0f) next = model.forward_argmax(token, pos);                     // :214-215, argmax fused on the device
             else next = sampler.forward_sample(model, token, pos);   // :115-128: scaling, maximum and exponentials on the device, the two sequential chains and sample_mult / sample_topp on the host
             pos += 1;
+            if (user_idx >= num_prompt_tokens && turn_tokens >= 0 && ++turn_sampled >= turn_tokens) next = tokenizer.eos;
             if (user_idx >= num_prompt_tokens && next != tokenizer.eos && !(mt == ModelType::GEMMA && next == 107)) {   // :218-222
                 std::fputs(tokenizer.decode(next).c_str(), stdout); std::fflush(stdout);
             }

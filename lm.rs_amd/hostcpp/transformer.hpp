@@ -59,6 +59,15 @@ public:
         check(lmrs_generate_greedy(ctx_, prompt.data(), prompt.size(), n_new, start_pos, out.data(), seconds));
         return out;
     }
+    // Extension (no reference counterpart): forward(tokens[t], start_pos + t) for every t with the logits discarded - a prompt's K/V rows,
+    // from token ids, batched on the device where the library says so (lmrs_tokens_path) -> start_pos + n.
+    std::uint32_t prefill_tokens(const std::uint32_t* tokens, std::size_t n, std::uint32_t start_pos = 0) {
+        std::uint32_t np = 0;
+        check(lmrs_prefill_tokens(ctx_, tokens, n, start_pos, &np));
+        return np;
+    }
+    std::uint32_t prefill_tokens(const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) { return prefill_tokens(tokens.data(), tokens.size(), start_pos); }
+    bool tokens_path(std::size_t n) const { int b = 0; check(lmrs_tokens_path(ctx_, n, &b)); return b != 0; }
     // Extensions (no reference counterpart): one forward per token of `tokens` from position start_pos, in one call.
     // forward_tokens: n x vocab_size logits, row t = forward(tokens[t], start_pos + t).
     std::vector<float> forward_tokens(const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) {

@@ -38,6 +38,8 @@ extern "C" {
     pub fn lmrs_forward_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, logits: *mut f32) -> c_int;
     pub fn lmrs_score_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, logprobs: *mut f32, argmax: *mut u32,
                              sum_logprob: *mut f64) -> c_int;
+    pub fn lmrs_prefill_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, new_pos: *mut u32) -> c_int;
+    pub fn lmrs_tokens_path(ctx: *const LmrsCtx, n: usize, batched: *mut c_int) -> c_int;
     pub fn lmrs_last_error() -> *const c_char;
 
     pub fn lmrs_vision_create(section: *const u8, len: usize, device: c_int, out: *mut *mut LmrsVision, bytes_consumed: *mut usize) -> c_int;

@@ -138,6 +138,21 @@ impl<'a> Transformer<'a> {
         });
         (logprobs, argmax, sum)
     }
+
+    /// Extension: `forward(tokens[t], start_pos + t)` for every t with the logits discarded - the K/V rows of a prompt from token ids,
+    /// one batched pass on the device where `tokens_path` says so.  Returns `start_pos + tokens.len()`.
+    pub fn prefill_tokens(&mut self, tokens: &[u32], start_pos: u32) -> u32 {
+        let mut new_pos: u32 = 0;
+        check(unsafe { ffi::lmrs_prefill_tokens(self.ctx, tokens.as_ptr(), tokens.len(), start_pos, &mut new_pos) });
+        new_pos
+    }
+
+    /// Whether `prefill_tokens` runs a run of `n` tokens as one batched pass on this context.
+    pub fn tokens_path(&self, n: usize) -> bool {
+        let mut batched: std::os::raw::c_int = 0;
+        check(unsafe { ffi::lmrs_tokens_path(self.ctx, n, &mut batched) });
+        batched != 0
+    }
 }
 
 /// The communicator id rank 0 makes for `new_sharded`.
