@@ -75,9 +75,11 @@ struct lmrs_ctx {
     // pinned host
     unsigned long long* samp_keys = nullptr; float* samp_pairs = nullptr; void* h_pairs = nullptr; int samp_cap = 0;   // lmrs_forward_sample: the device sort of top-p candidates (allocated on first use)
     float* h_logits = nullptr; uint32_t* h_tok = nullptr; DevState* h_st = nullptr; unsigned h_st_next = 0;   // h_st: ring of kStateSlots pinned slots (an async copy may still be reading the previous one)
-    hipGraphExec_t g_step = nullptr, g_layers = nullptr;
-    // long contexts: step graphs whose attention is the split pair, one per context bucket (256-key chunks: 4, 8, 16, 32)
-    hipGraphExec_t g_step_long[4] = {nullptr, nullptr, nullptr, nullptr}; float* att_S = nullptr; int att_split_chunks = 0; int att_split_pos = 0;
+    // the step graphs by form (StepForm: qkv + attention mode 0..2 | 3 + split-attention bucket 0..3) and steps per launch ([0] one, [1] multi_k):
+    // step_graph captures a missing one; the graph of position 0's form (primary_graph) is what says "this context replays graphs"
+    hipGraphExec_t g_steps[7][2] = {}, g_layers = nullptr;
+    // long contexts: from att_split_pos on a step's attention is the split pair (256-key chunks: 4, 8, 16, 32 by context bucket), scores in att_S
+    float* att_S = nullptr; int att_split_pos = 0;
     // batched forward_layer (fill_kv_cache): device buffers for kPrefillTokens tokens, allocated on first use
     float *pf_x = nullptr, *pf_q = nullptr, *pf_k = nullptr, *pf_ao = nullptr, *pf_h = nullptr, *pf_xs = nullptr, *pf_t = nullptr; int8_t* pf_xq = nullptr; float* pf_att = nullptr; size_t pf_att_cap = 0;
     bool pf_ready = false;                                 // every prefill buffer above is allocated
@@ -115,13 +117,12 @@ struct lmrs_ctx {
     int* err = nullptr; int* h_err = nullptr;      // error word of the bounded in-launch waits (merged qkv + attention launch, classifier tail)
     // ---- merged qkv + attention launch (launch_qkv_attn): per-layer {value, tag} granules, the step sequence number the tags are
     // made of (bumped by the last kernel of every step, never reset), and the graph of the separate kernels for the steps it does not cover
-    // qa_mode (what enqueue_layer launches): 0 the separate kernels, 1 merged with one workgroup per head (pos < qa_max_T), 2 merged with one
-    // wave per head - per 64 keys of a 64-wide head - (pos < qa_wave_T).  g_step is the graph of the best mode; g_step_alt[m] the others, captured on first use.
-    bool qkv_att = false; int qa_mode = 0; unsigned long long* gran = nullptr; unsigned* seq = nullptr; int qa_max_T = 0, qa_wave_T = 0;
-    hipGraphExec_t g_step_alt[3] = {nullptr, nullptr, nullptr};
+    // what enqueue_layer launches is StepForm::qa_mode: 0 the separate kernels, 1 merged with one workgroup per head (pos < qa_max_T), 2 merged with
+    // one wave per head - per 64 keys of a 64-wide head - (pos < qa_wave_T)
+    bool qkv_att = false; unsigned long long* gran = nullptr; unsigned* seq = nullptr; int qa_max_T = 0, qa_wave_T = 0;
     // several decode steps per graph launch (position and tokens live on the device, a step needs nothing from the host): lmrs_generate_greedy
-    // replays g_multi[mode] while multi_k steps remain inside one mode
-    int multi_k = 1; hipGraphExec_t g_multi[3] = {nullptr, nullptr, nullptr};
+    // replays the multi_k-step graph of a form while multi_k steps remain inside it
+    int multi_k = 1;
     // ---- final argmax folded into the classifier launch (ClsTail): packed partials
     bool cls_tail = false; unsigned long long* part_pk = nullptr; unsigned* cls_seq = nullptr;
     int inj_fail_connect = 0, inj_stall_seg = -1; long long inj_stall_ticks = 0;      // lmrs_debug_inject
@@ -162,11 +163,26 @@ bool prefill_tp_shapes_ok(const lmrs_ctx* c) {
 // bytes of one shard's block for a slice of n_l values per token: [kPrefillTokens x n_l int8 | kPrefillTokens x n_l / 128 f32]
 size_t prefill_tp_block(size_t n_l) { return pad256((size_t)kPrefillTokens * n_l + (size_t)kPrefillTokens * (n_l / 128) * 4); }
 
-// how a step at position `pos` runs qkv + attention (lmrs_ctx::qa_mode)
-int qa_mode_for(const lmrs_ctx* c, uint32_t pos) {
-    if (!c->qkv_att) return 0;
-    if ((int)pos < c->qa_wave_T) return 2;
-    return (int)pos < c->qa_max_T ? 1 : 0;
+// The form of one decode step: how it runs qkv + attention (qa_mode, see lmrs_ctx::qkv_att) and, when its attention is the split pair, over how many
+// 256-key chunks (then qa_mode is 0: the merged launch has no split form).  A value handed down to the enqueue functions, never context state.
+struct StepForm { int qa_mode = 0, split_chunks = 0; };
+// The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
+// it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
+// passes of fill_kv_cache).
+StepForm step_form_for(const lmrs_ctx* c, uint32_t pos, bool merged = true) {
+    StepForm f;
+    if (c->att_split_pos > 0 && (int)pos >= c->att_split_pos) {
+        int b = 0;
+        while (b < 3 && pos >= (1024u << b)) ++b;
+        f.split_chunks = 4 << b;
+    } else if (merged && c->qkv_att) f.qa_mode = (int)pos < c->qa_wave_T ? 2 : ((int)pos < c->qa_max_T ? 1 : 0);
+    return f;
+}
+// the score scratch of the split attention, allocated when the first split step is about to be enqueued
+int split_scratch(lmrs_ctx* c, StepForm f) {
+    if (!f.split_chunks || c->att_S) return 0;
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->att_S), attention_split_scratch_floats(c->att_dim / (int)c->args.head_size, (int)c->args.seq_len) * 4));
+    return 0;
 }
 
 // RoPE terms, transformer.rs:446-482 (libm powf/cosf/sinf/logf exactly where the reference calls them).
@@ -214,7 +230,7 @@ extern "C" int lmrs_rope_terms(const lmrs_args* args, uint32_t pos, uint32_t j, 
 
 // one decoder layer of an unquantised model (q_type None): the same launches with the f32 matmul (lmrs_f32.inc); Gemma's
 // x += rmsnorm(branch) steps as separate launches
-int enqueue_layer_f32(lmrs_ctx* c, int l) {
+int enqueue_layer_f32(lmrs_ctx* c, StepForm f, int l) {
     const lmrs_args& a = c->args;
     const DevLayer& L = c->layers[l];
     const bool gemma = a.model_type == LMRS_GEMMA;
@@ -228,7 +244,7 @@ int enqueue_layer_f32(lmrs_ctx* c, int l) {
     t.q = c->q; t.k_raw = c->k_raw; t.k_cache = c->k_cache; t.v_cache = c->v_cache; t.rope = c->rope; t.out = c->att_out;
     t.n_heads = a.n_heads; t.n_kv_heads = a.n_kv_heads; t.head_size = a.head_size; t.seq_len = a.seq_len; t.layer = l; t.gemma = gemma; t.st = c->st;
     set_launch_tag(1);
-    if (c->att_split_chunks) HIP_OK(launch_attention_split(t, c->att_S, c->att_split_chunks, c->stream));
+    if (f.split_chunks) HIP_OK(launch_attention_split(t, c->att_S, f.split_chunks, c->stream));
     else HIP_OK(launch_attention(t, c->stream));
     set_launch_tag(2);
     g.wq = L.wo; g.n = c->att_dim; g.o = a.dim; g.xin = c->att_out; g.out = gemma ? c->tmp : c->x;
@@ -247,8 +263,8 @@ int enqueue_layer_f32(lmrs_ctx* c, int l) {
 }
 
 // one decoder layer (transformer.rs:388-657) as 5 fused launches
-int enqueue_layer(lmrs_ctx* c, int l) {
-    if (c->f32) return enqueue_layer_f32(c, l);
+int enqueue_layer(lmrs_ctx* c, StepForm f, int l) {
+    if (c->f32) return enqueue_layer_f32(c, f, l);
     const lmrs_args& a = c->args;
     const DevLayer& L = c->layers[l];
     const bool gemma = a.model_type == LMRS_GEMMA;
@@ -269,18 +285,18 @@ int enqueue_layer(lmrs_ctx* c, int l) {
     t.q = c->q; t.k_raw = c->k_raw; t.k_cache = c->k_cache; t.v_cache = c->v_cache; t.rope = c->rope; t.out = c->att_out;
     t.n_heads = a.n_heads; t.n_kv_heads = a.n_kv_heads; t.head_size = a.head_size; t.seq_len = a.seq_len; t.layer = l;
     t.gemma = gemma; t.st = c->st;
-    if (c->qa_mode && !c->att_split_chunks) {
+    if (f.qa_mode && !f.split_chunks) {
         // 1 + 2 as ONE launch: the attention workgroups poll the granules the qkv workgroups write (launch_qkv_attn)
         g.gran = c->gran + (size_t)l * (c->att_dim + 2 * c->kv_dim); g.seq = c->seq;
         t.dbg = c->dbg ? c->dbg + 8 * (c->dbg_node++) : nullptr;
-        HIP_OK(launch_qkv_attn(g, pending ? PRO_ADD_RMS_QUANT : PRO_RMS_QUANT, t, c->err, c->qa_max_T, c->qa_mode == 2, c->stream));
+        HIP_OK(launch_qkv_attn(g, pending ? PRO_ADD_RMS_QUANT : PRO_RMS_QUANT, t, c->err, c->qa_max_T, f.qa_mode == 2, c->stream));
         g.gran = nullptr; g.seq = nullptr;
     } else {
     HIP_OK(launch_gemv(g, pending ? PRO_ADD_RMS_QUANT : PRO_RMS_QUANT, EPI_QKV, c->stream));
     // 2. RoPE + attention                                               (:443-544)
     t.dbg = c->dbg ? c->dbg + 8 * (c->dbg_node++) : nullptr;
     set_launch_tag(1);
-    if (c->att_split_chunks) HIP_OK(launch_attention_split(t, c->att_S, c->att_split_chunks, c->stream));
+    if (f.split_chunks) HIP_OK(launch_attention_split(t, c->att_S, f.split_chunks, c->stream));
     else HIP_OK(launch_attention(t, c->stream));
     }
     g.delta = nullptr; g.add_w = nullptr; g.xout = nullptr;
@@ -358,10 +374,9 @@ EmbedArgs embed_args(lmrs_ctx* c) {
 
 // One decode step minus the embedding of its input token: that row is produced by the previous step's
 // argmax kernel (or by launch_embed for the first step of a call), which saves a dependent launch per token.
-int enqueue_step(lmrs_ctx* c) {
+int enqueue_step(lmrs_ctx* c, StepForm f) {
     const lmrs_args& a = c->args;
-    for (uint32_t l = 0; l < a.n_layers; ++l) if (enqueue_layer(c, (int)l)) return -1;
-    c->dbg_node = c->dbg_node;   // (nodes numbered in launch order)
+    for (uint32_t l = 0; l < a.n_layers; ++l) if (enqueue_layer(c, f, (int)l)) return -1;
     GemvArgs g = cls_args(c);                                   // final rmsnorm + quantize | classifier | argmax partials (:341-381)
     g.dbg = c->dbg ? c->dbg + 8 * (c->dbg_node++) : nullptr;
     set_launch_tag(5);
@@ -436,11 +451,11 @@ ExchangeDesc exchange_after(lmrs_ctx* c, int seg) {
 }
 
 // layers_only: the per-layer segments without classifier / argmax (fill_kv_cache on a sharded context: the finished residual in x)
-int run_segment(lmrs_ctx* c, int seg) {
+int run_segment(lmrs_ctx* c, StepForm f, int seg) {
     const lmrs_args& a = c->args;
     const int L4 = 4 * (int)a.n_layers;
     // plan "cls": a layer is the five fused launches of the single-GPU step (its first segment runs all of it)
-    if (c->cls_only && seg < L4) return (seg & 3) == 0 ? enqueue_layer(c, seg >> 2) : 0;
+    if (c->cls_only && seg < L4) return (seg & 3) == 0 ? enqueue_layer(c, f, seg >> 2) : 0;
     const bool gemma = a.model_type == LMRS_GEMMA;
     GemvArgs g{};
     g.q4 = c->q4; g.eps = a.rms_norm_eps; g.add_unit = gemma; g.st = c->st;
@@ -478,7 +493,7 @@ int run_segment(lmrs_ctx* c, int seg) {
                 t.out = c->att_out + c->a0;
                 t.n_heads = c->att_dim / a.head_size; t.n_kv_heads = c->kv_dim / a.head_size; t.head_size = a.head_size;
                 t.seq_len = a.seq_len; t.layer = l; t.gemma = gemma; t.st = c->st;
-                if (c->att_split_chunks) HIP_OK(launch_attention_split(t, c->att_S, c->att_split_chunks, c->stream));
+                if (f.split_chunks) HIP_OK(launch_attention_split(t, c->att_S, f.split_chunks, c->stream));
                 else HIP_OK(launch_attention(t, c->stream));
                 set_launch_tag(7);
                 if (c->qpay && !c->p2p) {
@@ -532,11 +547,12 @@ int run_segment(lmrs_ctx* c, int seg) {
 
 int enqueue_exchange(lmrs_ctx* c, const ExchangeDesc& e);     // P2P push kernel or RCCL all-gather (below)
 
-// the sharded step (or only its layer segments) on this shard's stream, exchanges between the segments
-int enqueue_step_sharded(lmrs_ctx* c, bool layers_only = false) {
+// the sharded step (or only its layer segments) on this shard's stream, exchanges between the segments; every step takes the exchange slots from 0
+int enqueue_step_sharded(lmrs_ctx* c, StepForm f, bool layers_only = false) {
     const int ns = layers_only ? 4 * (int)c->args.n_layers : n_segments(c);
+    c->ex_slot = 0;
     for (int s = 0; s < ns; ++s) {
-        if (run_segment(c, s)) return -1;
+        if (run_segment(c, f, s)) return -1;
         const ExchangeDesc e = exchange_after(c, s);
         if (e.buf && enqueue_exchange(c, e)) return -1;
         if (e.buf && s == c->inj_stall_seg) hipLaunchKernelGGL(stall_kernel, dim3(1), dim3(1), 0, c->stream, c->inj_stall_ticks);
@@ -585,14 +601,14 @@ int enqueue_exchange(lmrs_ctx* c, const ExchangeDesc& e) {
     return 0;
 }
 
-int capture(lmrs_ctx* c, bool full, hipGraphExec_t* out, int n_steps = 1) {
+int capture(lmrs_ctx* c, StepForm f, bool full, hipGraphExec_t* out, int n_steps = 1) {
     hipGraph_t graph = nullptr;
-    c->dbg_node = 0; c->ex_slot = 0;
+    c->dbg_node = 0;
     HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     int rc = 0;
-    if (full) { for (int k = 0; k < n_steps && !rc; ++k) rc = c->world > 1 || c->comm ? enqueue_step_sharded(c) : enqueue_step(c); }
+    if (full) { for (int k = 0; k < n_steps && !rc; ++k) rc = c->world > 1 || c->comm ? enqueue_step_sharded(c, f) : enqueue_step(c, f); }
     else {
-        for (uint32_t l = 0; l < c->args.n_layers && !rc; ++l) rc = enqueue_layer(c, (int)l);
+        for (uint32_t l = 0; l < c->args.n_layers && !rc; ++l) rc = enqueue_layer(c, f, (int)l);
         if (!rc) rc = enqueue_finish_residual(c);
         if (!rc) hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, c->stream, c->st, c->seq);
     }
@@ -603,6 +619,28 @@ int capture(lmrs_ctx* c, bool full, hipGraphExec_t* out, int n_steps = 1) {
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     return 0;
+}
+
+// ---- the table of step graphs (lmrs_ctx::g_steps): the graph of `k` steps of form `f`, captured when it is not there yet; null: the capture failed
+hipGraphExec_t step_graph(lmrs_ctx* c, StepForm f, int k = 1) {
+    hipGraphExec_t& g = c->g_steps[f.split_chunks ? __builtin_ctz(f.split_chunks) + 1 : f.qa_mode][k > 1];      // (chunks 4, 8, 16, 32 -> 3 .. 6)
+    if (!g && capture(c, f, true, &g, k)) g = nullptr;
+    return g;
+}
+int replay_steps(lmrs_ctx* c, StepForm f, int k = 1) {
+    hipGraphExec_t g = step_graph(c, f, k);
+    if (!g) return -1;
+    HIP_OK(hipGraphLaunch(g, c->stream));
+    return 0;
+}
+// the graph a context that replays graphs always has: one step of position 0's form (captured at create; sharded contexts: when the runtime accepted it)
+hipGraphExec_t primary_graph(const lmrs_ctx* c) { return c->g_steps[step_form_for(c, 0).qa_mode][0]; }
+// a sharded context's primary graph - or, when the runtime refuses the exchanges inside a capture, every step enqueued call by call
+void capture_sharded_step(lmrs_ctx* c) {
+    if (!step_graph(c, step_form_for(c, 0))) { c->eager = true; (void)hipGetLastError(); g_err.clear(); }
+}
+void destroy_step_graphs(lmrs_ctx* c) {
+    for (auto& forms : c->g_steps) for (hipGraphExec_t& g : forms) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
 }
 
 // host->device copy of one tensor payload, optionally row-interleaved (dst row = 2*r + phase)
@@ -649,6 +687,12 @@ int check_err(lmrs_ctx* c) {
     if (*c->h_err) return fail("in-launch synchronisation timed out at stage " + std::to_string(*c->h_err - 1) + " (results of this call are invalid)");
     return 0;
 }
+// the end of every call that ran steps or passes: the error word's copy, the synchronise, the checks
+int finish_call(lmrs_ctx* c) {
+    if (queue_err(c)) return -1;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return check_err(c);
+}
 
 }  // namespace
 
@@ -693,7 +737,7 @@ extern "C" int lmrs_comm_ranks(const lmrs_ctx* c) {
     int n = 0;
     return ncclCommCount(c->comm, &n) == ncclSuccess ? n : -1;
 }
-extern "C" int lmrs_shard_uses_graph(const lmrs_ctx* c) { return !c || !(c->comm || c->p2p) ? -1 : (c->g_step ? 1 : 0); }
+extern "C" int lmrs_shard_uses_graph(const lmrs_ctx* c) { return !c || !(c->comm || c->p2p) ? -1 : (primary_graph(c) ? 1 : 0); }
 
 extern "C" int lmrs_create_sharded(const uint8_t* file, size_t len, int device, int rank, int world, const void* uid,
                                    lmrs_ctx** out, size_t* bytes_consumed) {
@@ -767,9 +811,7 @@ extern "C" int lmrs_p2p_connect(lmrs_ctx* c, const void* handles /* world x 64 b
             if (got != 1000.0f + (float)w) return fail("peer-to-peer handshake: the block of rank " + std::to_string(w) + " did not arrive");
         }
     }
-    c->qa_mode = qa_mode_for(c, 0);
-    if (capture(c, true, &c->g_step)) { c->g_step = nullptr; c->eager = true; (void)hipGetLastError(); g_err.clear(); }
-    c->qa_mode = 0;
+    capture_sharded_step(c);
     return 0;
 }
 
@@ -793,12 +835,12 @@ extern "C" int lmrs_group_forward(lmrs_ctx** sh, int world, uint32_t token, uint
     if (c0->p2p) {
         // every shard's whole step on its own stream, all in flight at once: the exchanges are the push kernels, the shards really
         // wait for each other on the device (as W processes on W GPUs would)
-        for (int r = 0; r < world; ++r) { sh[r]->ex_slot = 0; if (enqueue_step_sharded(sh[r])) return -1; }
+        for (int r = 0; r < world; ++r) if (enqueue_step_sharded(sh[r], StepForm{})) return -1;
         HIP_OK(hipDeviceSynchronize());
         for (int r = 0; r < world; ++r) if (check_err(sh[r])) return -1;
     } else
     for (int s = 0; s < ns; ++s) {
-        for (int r = 0; r < world; ++r) if (run_segment(sh[r], s)) return -1;
+        for (int r = 0; r < world; ++r) if (run_segment(sh[r], StepForm{}, s)) return -1;
         HIP_OK(hipDeviceSynchronize());
         const ExchangeDesc g0 = exchange_after(c0, s);
         if (!g0.buf) continue;
@@ -1059,10 +1101,8 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     if (!sharded) c->multi_k = sw.steps_per_graph;   // (measured: 4 steps per launch +1.5 % on a 20-step run, no effect on long runs)
     c->cls_tail = !sharded && !f32w && V < (1u << 20) - 1 && sw.cls_tail;
     if (!sharded) {
-        c->qa_mode = qa_mode_for(c, 0);
-        CK(capture(c, true, &c->g_step));
-        c->qa_mode = 0;                         // the layers-only graph serves fill_kv_cache's token-by-token form at ANY position: separate kernels
-        CK(capture(c, false, &c->g_layers));
+        CK(!step_graph(c, step_form_for(c, 0)));
+        CK(capture(c, StepForm{}, false, &c->g_layers));      // (fill_kv_cache's token-by-token form at ANY position: the separate kernels)
         // from this position on a step uses the split attention (scores by key chunk, V by dim slice): graphs captured on first use
         if (!c->dbg || sw.att_split_pos_set) c->att_split_pos = sw.att_split_pos;     // (stamped steps: the split form only when asked for)
         // every graph a call below that threshold can need - per qkv + attention mode the single-step graph and the multi-step one -
@@ -1072,19 +1112,13 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
             for (int mode = 1; mode <= 2; ++mode) {
                 if (mode == 2 && c->qa_wave_T <= 0) continue;
                 if (mode == 1 && c->qa_wave_T >= c->qa_max_T) continue;
-                c->qa_mode = mode;
-                int rc = 0;
-                if (mode != qa_mode_for(c, 0)) rc = capture(c, true, &c->g_step_alt[mode]);
-                if (!rc && c->multi_k > 1) rc = capture(c, true, &c->g_multi[mode], c->multi_k);
-                c->qa_mode = 0;
-                CK(rc);
+                CK(!step_graph(c, StepForm{mode, 0}));
+                if (c->multi_k > 1) CK(!step_graph(c, StepForm{mode, 0}, c->multi_k));
             }
         }
     } else if (c->comm) {
         // RCCL collectives inside a captured graph: use it when the runtime accepts it, else enqueue every step
-        c->qa_mode = qa_mode_for(c, 0);
-        if (capture(c, true, &c->g_step)) { c->g_step = nullptr; c->eager = true; (void)hipGetLastError(); g_err.clear(); }
-        c->qa_mode = 0;
+        capture_sharded_step(c);
     }
     // (peer-to-peer contexts capture their step graph in lmrs_p2p_connect, once the peers' arenas are known)
     if (sharded) c->att_split_pos = sw.att_split_pos;
@@ -1103,12 +1137,9 @@ extern "C" void lmrs_destroy(lmrs_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->g_step) (void)hipGraphExecDestroy(c->g_step);
-    for (auto& g : c->g_step_long) if (g) (void)hipGraphExecDestroy(g);
+    destroy_step_graphs(c);
     if (c->att_S) (void)hipFree(c->att_S);
     if (c->g_layers) (void)hipGraphExecDestroy(c->g_layers);
-    for (auto& g : c->g_step_alt) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& g : c->g_multi) if (g) (void)hipGraphExecDestroy(g);
     for (void* q : {(void*)c->pf_x, (void*)c->pf_q, (void*)c->pf_k, (void*)c->pf_ao, (void*)c->pf_h, (void*)c->pf_xq, (void*)c->pf_xs, (void*)c->pf_t, (void*)c->pf_att}) if (q) (void)hipFree(q);
     for (float* q : c->scales_t) if (q) (void)hipFree(q);
     for (void* q : {(void*)c->sc_logits, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_idx}) if (q) (void)hipFree(q);
@@ -1133,57 +1164,21 @@ extern "C" void lmrs_destroy(lmrs_ctx* c) {
 
 extern "C" const lmrs_args* lmrs_get_args(const lmrs_ctx* c) { return c ? &c->args : nullptr; }
 
-// one decode step on the context's stream: the captured graph, or (sharded, capture refused) eager launches
+// one decode step on the context's stream: the replay of its form's graph, or eager launches
 static int launch_step(lmrs_ctx* c, uint32_t pos) {
     const bool sharded = c->comm || c->p2p;
     if (c->p2p && !c->p2p_ready) return fail("peer-to-peer transport: peers not connected yet (lmrs_p2p_connect)");
     if (sharded && c->world > 1 && !c->comm && !c->p2p) return fail("this context is a member of a lock-step shard group: drive it with lmrs_group_forward");
-    const bool want_split = c->att_split_pos > 0 && (int)pos >= c->att_split_pos;
-    int b = 0;                                               // bucket b covers positions below 1024 << b
-    if (want_split) {
-        while (b < 3 && pos >= (1024u << b)) ++b;
-        if (!c->att_S) HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->att_S), attention_split_scratch_floats(c->att_dim / (int)c->args.head_size, (int)c->args.seq_len) * 4));
-    }
-    // profiling aid (LMRS_NO_GRAPH=1): the same launches enqueued one by one instead of a graph replay - rocprofv3 1.1's dispatch interceptor
-    // segfaults on the graph launches of every model but Llama-3.2-1B (profiles/README.md); token ids are the same either way
-    if (c->sw.no_graph && !sharded && c->g_step) {
-        c->qa_mode = want_split ? 0 : qa_mode_for(c, pos); c->att_split_chunks = want_split ? 4 << b : 0; c->dbg_node = 0;
-        const int rc = enqueue_step(c);
-        c->qa_mode = 0; c->att_split_chunks = 0;
-        return rc;
-    }
-    if (c->g_step) {
-        if (want_split) {
-            if (!c->g_step_long[b]) {
-                c->att_split_chunks = 4 << b;
-                const int rc = capture(c, true, &c->g_step_long[b]);
-                c->att_split_chunks = 0;
-                if (rc) return -1;
-            }
-            HIP_OK(hipGraphLaunch(c->g_step_long[b], c->stream));
-            return 0;
-        }
-        const int mode = qa_mode_for(c, pos);
-        if (mode != qa_mode_for(c, 0)) {                      // past the context the primary graph's merged launch covers
-            if (!c->g_step_alt[mode]) {
-                c->qa_mode = mode;
-                const int rc = capture(c, true, &c->g_step_alt[mode]);
-                c->qa_mode = 0;
-                if (rc) return -1;
-            }
-            HIP_OK(hipGraphLaunch(c->g_step_alt[mode], c->stream));
-            return 0;
-        }
-        HIP_OK(hipGraphLaunch(c->g_step, c->stream));
-        return 0;
-    }
-    if (sharded && c->eager) {                               // the runtime refused to capture the collectives: enqueue every step
-        c->att_split_chunks = want_split ? 4 << b : 0; c->ex_slot = 0;
-        const int rc = enqueue_step_sharded(c);
-        c->att_split_chunks = 0;
-        return rc;
-    }
-    return fail("this context is a member of a lock-step shard group: drive it with lmrs_group_forward");
+    // Eager: a sharded step whose exchanges the runtime refused to capture (it runs the separate kernels), and the profiling aid LMRS_NO_GRAPH=1 - the
+    // launches of the graph enqueued one by one: rocprofv3 1.1's dispatch interceptor segfaults on the graph launches of every model but Llama-3.2-1B
+    // (profiles/README.md); token ids are the same either way
+    const bool graphs = primary_graph(c) != nullptr, eager = graphs ? c->sw.no_graph && !sharded : sharded && c->eager;
+    const StepForm f = step_form_for(c, pos, /*merged=*/graphs);
+    if (split_scratch(c, f)) return -1;
+    if (!graphs && !eager) return fail("this context is a member of a lock-step shard group: drive it with lmrs_group_forward");
+    if (!eager) return replay_steps(c, f);
+    c->dbg_node = 0;
+    return sharded ? enqueue_step_sharded(c, f) : enqueue_step(c, f);
 }
 
 static int step_once(lmrs_ctx* c, uint32_t token, uint32_t pos) {
@@ -1208,9 +1203,7 @@ extern "C" int lmrs_forward(lmrs_ctx* c, uint32_t token, uint32_t pos, float** l
         if (rc) return -1;
     }
     HIP_OK(hipMemcpyAsync(c->h_logits, c->logits, (size_t)c->args.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    if (finish_call(c)) return -1;
     if (logits) *logits = c->h_logits;
     return 0;
 }
@@ -1218,9 +1211,7 @@ extern "C" int lmrs_forward(lmrs_ctx* c, uint32_t token, uint32_t pos, float** l
 extern "C" int lmrs_forward_argmax(lmrs_ctx* c, uint32_t token, uint32_t pos, uint32_t* next) {
     if (step_once(c, token, pos)) return -1;
     HIP_OK(hipMemcpyAsync(c->h_tok + 1, c->tokens + pos + 1, 4, hipMemcpyDeviceToHost, c->stream));
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    if (finish_call(c)) return -1;
     if (next) *next = c->h_tok[1];
     return 0;
 }
@@ -1247,9 +1238,7 @@ extern "C" int lmrs_forward_sample(lmrs_ctx* c, uint32_t token, uint32_t pos, lm
     SampleArgs sa{c->logits, (int)n, temp, c->part_val};                                  // (scratch: the argmax partials)
     HIP_OK(launch_sample_exps(sa, c->stream));
     HIP_OK(hipMemcpyAsync(c->h_logits, c->logits, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    if (finish_call(c)) return -1;
     // the sequential sum, the division and the cutoff filter on the host (lmrs_text.cpp); the exponentials are still in c->logits on the device
     float sum = 0.0f, cutoff = 0.0f; size_t n0 = 0;
     if (lmrs_sampler_exps_prepare(sampler, c->h_logits, &sum, &cutoff, &n0)) return -1;
@@ -1478,72 +1467,64 @@ static int prefill_pass(lmrs_ctx* c, int m, int p0) {
     return prefill_layers(c, m, p0);
 }
 
+// forward_layer over rows p0 .. p0 + n - 1, kPrefillTokens at a time (a later chunk only needs the K/V rows of the earlier ones, exactly as inside
+// the reference's single call): produce(i0, m) leaves the embedding rows of a chunk in pf_x, consume(i0, m) takes its finished residual rows from there
+template <class Produce, class Consume> static int prefill_chunks(lmrs_ctx* c, uint32_t p0, size_t n, Produce produce, Consume consume) {
+    for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
+        const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
+        if (produce(i0, m) || prefill_pass(c, m, (int)(p0 + i0)) || consume(i0, m)) return -1;
+    }
+    return 0;
+}
+// DevState::win_base of a pass over the positions from pos on (only Gemma-2's kernels read it).  One forward_layer(sl = n) call - fill_kv_cache, batched
+// or token by token - tests the 4096-key window against its FIRST position for every token (the u32 `pos - t` of transformer.rs:525); a pass that
+// stands for n Transformer::forward calls (the token entry points) tests every token against its OWN position: kWinPerQuery (lmrs_kernels.h)
+static int pass_win_base(const lmrs_ctx* c, uint32_t pos, bool forward_calls) {
+    return forward_calls && c->args.model_type == LMRS_GEMMA ? kWinPerQuery : (int)pos;
+}
+
 extern "C" int lmrs_fill_kv_cache(lmrs_ctx* c, float* embeddings, uint32_t n, uint32_t curr_pos, uint32_t* new_pos) {
     if (!c || !embeddings) return fail("NULL argument");
     if ((size_t)curr_pos + n > c->args.seq_len) return fail("positions out of range");
     HIP_OK(hipSetDevice(c->device));
+    const size_t dim = c->args.dim;
     const bool tp_batched = n > 1 && prefill_tp_ok(c);
-    if (!c->g_layers && !tp_batched && !(c->cls_only && n > 1 && prefill_batched_ok(c))) {
-        // Row-sharded context: forward_layer(sl = n) is, value for value, n single-token passes through the layers; each token goes
-        // through the sharded layer segments (exchanges included), every shard ends with the whole residual stream in x.
-        if (!(c->comm || (c->p2p && c->p2p_ready))) return fail("fill_kv_cache: this sharded context has no transport (lock-step groups are driven by lmrs_group_forward)");
-        const size_t dim = c->args.dim;
-        if (set_state(c, curr_pos, 0, (int)curr_pos)) return -1;
-        const int chunks0 = c->att_split_chunks;
+    // Row-sharded context without a batched pass: each token goes through the sharded layer segments (exchanges included), every shard ends with the
+    // whole residual stream in x
+    const bool by_segments = !c->g_layers && !tp_batched && !(c->cls_only && n > 1 && prefill_batched_ok(c));
+    if (by_segments && !(c->comm || (c->p2p && c->p2p_ready))) return fail("fill_kv_cache: this sharded context has no transport (lock-step groups are driven by lmrs_group_forward)");
+    const bool batched = !by_segments && (tp_batched || prefill_batched_ok(c)) && n > 1;
+    if (batched) {
+        // forward_layer(sl = n): GEMMs over the token batch on the int8 matrix cores
+        if (prefill_alloc(c)) return -1;
+        if (set_state(c, curr_pos, 0, pass_win_base(c, curr_pos, false))) return -1;
+        auto upload_rows = [&](size_t i0, int m) -> int {
+            HIP_OK(hipMemcpyAsync(c->pf_x, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
+            if (i0 == 0) HIP_OK(hipEventRecord(c->ev0, c->stream));                     // (measurement: the layers without the first upload / the last download)
+            return 0;
+        };
+        auto download_rows = [&](size_t i0, int m) -> int {
+            if (i0 + kPrefillTokens >= n) HIP_OK(hipEventRecord(c->ev1, c->stream));
+            HIP_OK(hipMemcpyAsync(embeddings + i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (prefill_chunks(c, curr_pos, n, upload_rows, download_rows)) return -1;
+        if (set_state(c, curr_pos + n, 0)) return -1;
+    } else {
+        // forward_layer(sl = n) for every layer is, value for value, n single-token passes through the layers (causal; each token's arithmetic only
+        // sees tokens <= itself): the layers-only graph of the decode step or, on row shards, the step's layer segments
+        if (set_state(c, curr_pos, 0, pass_win_base(c, curr_pos, false))) return -1;
         for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t pos = curr_pos + i;
-            int b = 0;
-            if (c->att_split_pos > 0 && (int)pos >= c->att_split_pos) {
-                while (b < 3 && pos >= (1024u << b)) ++b;
-                if (!c->att_S) HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->att_S), attention_split_scratch_floats(c->att_dim / (int)c->args.head_size, (int)c->args.seq_len) * 4));
-                c->att_split_chunks = 4 << b;
-            } else c->att_split_chunks = 0;
+            const StepForm f = step_form_for(c, curr_pos + i, /*merged=*/false);
+            if (by_segments && split_scratch(c, f)) return -1;
             HIP_OK(hipMemcpyAsync(c->x, embeddings + (size_t)i * dim, dim * 4, hipMemcpyHostToDevice, c->stream));
-            c->ex_slot = 0;
-            if (enqueue_step_sharded(c, true)) { c->att_split_chunks = chunks0; return -1; }
+            if (!by_segments) HIP_OK(hipGraphLaunch(c->g_layers, c->stream));
+            else if (enqueue_step_sharded(c, f, /*layers_only=*/true)) return -1;
             HIP_OK(hipMemcpyAsync(embeddings + (size_t)i * dim, c->x, dim * 4, hipMemcpyDeviceToHost, c->stream));
         }
-        c->att_split_chunks = chunks0;
-        if (queue_err(c)) return -1;
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (check_err(c)) return -1;
-        if (new_pos) *new_pos = curr_pos + n;
-        return 0;
     }
-    if ((tp_batched || prefill_batched_ok(c)) && n > 1) {
-        // forward_layer(sl = n): GEMMs over the token batch on the int8 matrix cores, kPrefillTokens tokens at a time
-        // (a later chunk only needs the K/V rows of the earlier ones, exactly as inside the reference's single call).
-        if (prefill_alloc(c)) return -1;
-        const size_t dim = c->args.dim;
-        if (set_state(c, curr_pos, 0, (int)curr_pos)) return -1;      // Gemma's window test sees curr_pos for every token of the call
-        for (uint32_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
-            const int m = (int)std::min<uint32_t>(kPrefillTokens, n - i0);
-            HIP_OK(hipMemcpyAsync(c->pf_x, embeddings + (size_t)i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
-            if (i0 == 0) HIP_OK(hipEventRecord(c->ev0, c->stream));                     // (measurement: the layers without the first upload / the last download)
-            if (prefill_pass(c, m, (int)(curr_pos + i0))) return -1;
-            if (i0 + kPrefillTokens >= n) HIP_OK(hipEventRecord(c->ev1, c->stream));
-            HIP_OK(hipMemcpyAsync(embeddings + (size_t)i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (set_state(c, curr_pos + n, 0)) return -1;
-        if (queue_err(c)) return -1;
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (check_err(c)) return -1;
-        { float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_fill_ms = ms; }
-        if (new_pos) *new_pos = curr_pos + n;
-        return 0;
-    }
-    // forward_layer(sl = n) for every layer is, value for value, n single-token passes through the
-    // layers (causal; each token's arithmetic only sees tokens <= itself), so the decode graph is reused.
-    const size_t dim = c->args.dim;
-    if (set_state(c, curr_pos, 0, (int)curr_pos)) return -1;      // one forward_layer(sl = n) call: Gemma's window test sees curr_pos for every token
-    for (uint32_t i = 0; i < n; ++i) {
-        HIP_OK(hipMemcpyAsync(c->x, embeddings + (size_t)i * dim, dim * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipGraphLaunch(c->g_layers, c->stream));
-        HIP_OK(hipMemcpyAsync(embeddings + (size_t)i * dim, c->x, dim * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    if (finish_call(c)) return -1;
+    if (batched) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_fill_ms = ms; }
     if (new_pos) *new_pos = curr_pos + n;
     return 0;
 }
@@ -1564,36 +1545,49 @@ static size_t tokens_batch_min(const lmrs_ctx* c) {
 }
 static bool tokens_batched(const lmrs_ctx* c, size_t n) { return n >= tokens_batch_min(c) && (prefill_batched_ok(c) || prefill_tp_ok(c)); }
 
-// the state of a batched pass that stands for forward calls from position pos on (only Gemma's kernels read it)
-static int begin_token_pass(lmrs_ctx* c, uint32_t pos) {
-    return c->args.model_type == LMRS_GEMMA ? set_state(c, pos, 0, kWinPerQuery) : 0;
+// The arguments every entry point that takes a run of token ids checks, in this order; `span`: the positions the call will touch from start_pos on
+static int check_tokens(const lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, size_t span) {
+    if (n == 0) return fail("no tokens given (n == 0)");
+    if (!c || !tokens) return fail("NULL argument");
+    if ((size_t)start_pos + span > c->args.seq_len) return fail("start_pos + " + std::to_string(span) + " positions exceeds seq_len");
+    for (size_t i = 0; i < n; ++i) if (tokens[i] >= c->args.vocab_size) return fail("token " + std::to_string(i) + " out of range");
+    return 0;
 }
-static hipError_t token_rows(lmrs_ctx* c, uint32_t pos, int m) {        // embedding rows of c->tokens[pos .. pos + m) -> pf_x, as forward builds them
+static int upload_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos) {      // -> c->tokens[start_pos ..), through the pinned h_tok
+    memcpy(c->h_tok, tokens, n * 4);
+    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+static int stage_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, size_t span) {
+    if (check_tokens(c, tokens, n, start_pos, span)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    return upload_tokens(c, tokens, n, start_pos);
+}
+static int token_rows(lmrs_ctx* c, uint32_t pos, int m) {        // embedding rows of c->tokens[pos .. pos + m) -> pf_x, as forward builds them
     const float scale = c->args.model_type == LMRS_GEMMA ? sqrtf((float)c->args.dim) : 0.0f;
-    return launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + pos, m, (int)c->args.dim, c->pf_x, c->stream, scale);
+    HIP_OK(launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + pos, m, (int)c->args.dim, c->pf_x, c->stream, scale));
+    return 0;
 }
-// K/V rows start_pos .. start_pos + n - 1 from c->tokens, kPrefillTokens at a time; the caller sets the state that follows
+// K/V rows start_pos .. start_pos + n - 1 from c->tokens; the caller sets the state that follows (the pass's own: only Gemma's kernels read one)
 static int prefill_token_run(lmrs_ctx* c, uint32_t start_pos, size_t n) {
     if (prefill_alloc(c)) return -1;
-    if (begin_token_pass(c, start_pos)) return -1;
-    for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
-        const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
-        HIP_OK(token_rows(c, start_pos + (uint32_t)i0, m));
-        if (prefill_pass(c, m, (int)(start_pos + i0))) return -1;
-    }
+    if (c->args.model_type == LMRS_GEMMA && set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
+    return prefill_chunks(c, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); }, [](size_t, int) { return 0; });
+}
+// The decode step per token for n GIVEN tokens, already in c->tokens: prompt_end = start_pos + n makes every step embed the next given token instead
+// of its own result (lmrs_generate_greedy's prompt phase); per_step(t) is enqueued behind step t, whose logits are in c->logits then
+template <class PerStep> static int decode_given_tokens(lmrs_ctx* c, uint32_t start_pos, size_t n, PerStep per_step) {
+    if (set_state(c, start_pos, start_pos + (uint32_t)n)) return -1;
+    HIP_OK(launch_embed(embed_args(c), c->stream));
+    for (size_t t = 0; t < n; ++t) if (launch_step(c, start_pos + (uint32_t)t) || per_step(t)) return -1;
     return 0;
 }
 
 extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t n_prompt, uint32_t n_new, uint32_t start_pos,
                                     uint32_t* out_tokens, double* seconds) {
     if (!c || !prompt || (!out_tokens && n_new)) return fail("NULL argument");
-    if (n_prompt == 0) return fail("empty prompt");
     const size_t steps = n_prompt + (n_new ? n_new - 1 : 0);
-    if ((size_t)start_pos + steps > c->args.seq_len) return fail("prompt + generation exceeds seq_len");
-    for (size_t i = 0; i < n_prompt; ++i) if (prompt[i] >= c->args.vocab_size) return fail("token out of range");
-    HIP_OK(hipSetDevice(c->device));
-    memcpy(c->h_tok, prompt, n_prompt * 4);
-    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n_prompt * 4, hipMemcpyHostToDevice, c->stream));
+    if (stage_tokens(c, prompt, n_prompt, start_pos, steps)) return -1;
     HIP_OK(hipEventRecord(c->ev0, c->stream));
     // The reference feeds the prompt token by token and discards every logits vector but the last (chat.rs:188-193): all
     // prompt tokens except the last only have to leave their K/V rows behind, which is forward_layer over a batch - the
@@ -1603,32 +1597,22 @@ extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t 
         if (prefill_token_run(c, start_pos, n_prompt - 1)) return -1;
         done = n_prompt - 1;
     }
+    // (not decode_given_tokens: the steps run on past the prompt, several per graph launch where that is possible)
     if (set_state(c, start_pos + (uint32_t)done, start_pos + (uint32_t)n_prompt)) return -1;
     HIP_OK(launch_embed(embed_args(c), c->stream));
+    const int K = c->multi_k;
+    const bool multi = K > 1 && primary_graph(c) && !c->dbg && !c->sw.no_graph;
     for (size_t s = done; s < steps;) {
         const uint32_t p = start_pos + (uint32_t)s;
-        const int K = c->multi_k;
-        const bool split_soon = c->att_split_pos > 0 && (int)(p + K - 1) >= c->att_split_pos;
-        if (K > 1 && c->g_step && !c->dbg && !c->sw.no_graph && s + K <= steps && !split_soon && qa_mode_for(c, p) == qa_mode_for(c, p + K - 1)) {
-            const int mode = qa_mode_for(c, p);
-            if (!c->g_multi[mode]) {
-                c->qa_mode = mode;
-                const int rc = capture(c, true, &c->g_multi[mode], K);
-                c->qa_mode = 0;
-                if (rc) return -1;
-            }
-            HIP_OK(hipGraphLaunch(c->g_multi[mode], c->stream));
-            s += K;
-            continue;
-        }
-        if (launch_step(c, p)) return -1;
-        ++s;
+        const StepForm f = step_form_for(c, p), last = step_form_for(c, p + K - 1);
+        // K steps in one launch while they fit the run and stay inside one form, below the split attention
+        const bool k_steps = multi && s + K <= steps && !last.split_chunks && f.qa_mode == last.qa_mode;
+        if (k_steps ? replay_steps(c, f, K) : launch_step(c, p)) return -1;
+        s += k_steps ? K : 1;
     }
     HIP_OK(hipEventRecord(c->ev1, c->stream));
     if (n_new) HIP_OK(hipMemcpyAsync(c->h_tok, c->tokens + start_pos + n_prompt, (size_t)n_new * 4, hipMemcpyDeviceToHost, c->stream));
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    if (finish_call(c)) return -1;
     if (n_new) memcpy(out_tokens, c->h_tok, (size_t)n_new * 4);
     if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
     return 0;
@@ -1641,10 +1625,9 @@ extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t 
 constexpr size_t kScoreBlockBytes = (size_t)512 << 20;     // the [tokens][vocab] logits block: at most 512 MiB (Llama-3.2-1B: 263 MB for 512 tokens)
 
 // The batched path: forward_layer over the whole sequence (prefill_pass: the int8 matrix-core GEMMs), then the final rmsnorm + quantise of every
-// token and the classifier as ONE GEMM over the token batch.  Both give what the decode step gives, bit for bit.  Not taken:
-//   * Gemma-2.  The batched layers test Gemma's sliding window against the pass's FIRST position (att_scores_wide_kernel, lmrs_prefill.inc:
-//     wpos = pos0 - the reference's batched quirk, the u32 `pos - t` of transformer.rs:525), so keys of the same batch would be masked that
-//     sequential forward calls keep; Gemma also scales its embeddings by sqrt(dim) in forward only, and soft-caps the logits.
+// token and the classifier as ONE GEMM over the token batch.  Both give what the decode step gives, bit for bit; Gemma-2 too, with
+// what only forward calls do: embedding rows scaled by sqrt(dim) (token_rows), the window tested per query (pass_win_base), logits soft-capped.
+// Not taken:
 //   * a classifier whose written rows are not a multiple of 16 (launch_gemm_q8 runs whole 16-row tiles; e.g. a vocabulary of 4102);
 //   * one token (that is one decode step) and everything prefill_batched_ok refuses (f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1).
 // Those run the decode step token by token, as lmrs_generate_greedy feeds a prompt.
@@ -1681,18 +1664,15 @@ static int score_alloc(lmrs_ctx* c, bool block) {
 // out_logits != null: lmrs_forward_tokens (n x vocab floats to the host); else lmrs_score_tokens' results
 static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* out_logits, float* logprobs, uint32_t* argmax,
                        double* sum_logprob) {
-    if (n == 0) return fail("no tokens to score (n == 0)");
-    if (!c || !tokens) return fail("NULL argument");
-    if ((size_t)start_pos + n > c->args.seq_len) return fail("start_pos + n exceeds seq_len");
-    for (size_t i = 0; i < n; ++i) if (tokens[i] >= c->args.vocab_size) return fail("token " + std::to_string(i) + " out of range");
+    // (stage_tokens in its two halves: the refusal and the first-use allocations sit between the checks and the upload, where they always did)
+    if (check_tokens(c, tokens, n, start_pos, n)) return -1;
     if (c->world > 1 || c->comm || c->p2p)
         return fail("scoring runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
     HIP_OK(hipSetDevice(c->device));
     const bool batched = score_batched_ok(c, n);
     if (score_alloc(c, batched || out_logits)) return -1;
     const int V = (int)c->args.vocab_size;
-    memcpy(c->h_tok, tokens, n * 4);
-    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+    if (upload_tokens(c, tokens, n, start_pos)) return -1;
     // rows r0 .. r0 + m - 1 of the sequence, row stride ld, the first `written` columns written (the rest is the classifier's zero tail)
     auto reduce = [&](const float* rows, int ld, int written, int m, size_t r0) -> int {
         ScoreArgs s{rows, ld, written, V, m, c->tokens + start_pos + r0 + 1, (int)std::max<long long>(0, (long long)n - 1 - (long long)r0),
@@ -1712,12 +1692,9 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
         const lmrs_args& a = c->args;
         const int dim = (int)a.dim, o = cls_rows(c);
         const bool gemma = a.model_type == LMRS_GEMMA;
-        if (set_state(c, start_pos, 0, gemma ? kWinPerQuery : (int)start_pos)) return -1;
-        for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
-            const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
-            HIP_OK(token_rows(c, start_pos + (uint32_t)i0, m));
-            if (prefill_pass(c, m, (int)(start_pos + i0))) return -1;
-            // final rmsnorm + quantise of every token (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372)
+        if (set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
+        // final rmsnorm + quantise of every token (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372)
+        auto classify = [&](size_t i0, int m) -> int {
             HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
             for (int j0 = 0; j0 < m; j0 += c->sc_rows) {
                 const int mj = std::min(c->sc_rows, m - j0);
@@ -1728,22 +1705,22 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
                 if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));     // (:375-381)
                 if (out_logits ? copy_out(c->sc_logits, o, mj, i0 + j0) : reduce(c->sc_logits, o, o, mj, i0 + j0)) return -1;
             }
-        }
+            return 0;
+        };
+        if (prefill_chunks(c, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); }, classify)) return -1;
         if (set_state(c, start_pos + (uint32_t)n, 0)) return -1;
     } else {
-        // the decode step per token; prompt_end = start_pos + n: every step embeds the next GIVEN token (lmrs_generate_greedy's prompt phase)
-        if (set_state(c, start_pos, start_pos + (uint32_t)n)) return -1;
-        HIP_OK(launch_embed(embed_args(c), c->stream));
         size_t r0 = 0;                                       // first position held in the logits block (forward_tokens)
-        for (size_t t = 0; t < n; ++t) {
-            if (launch_step(c, start_pos + (uint32_t)t)) return -1;
-            if (!out_logits) { if (reduce(c->logits, V, V, 1, t)) return -1; continue; }
+        auto keep_logits = [&](size_t t) -> int {
+            if (!out_logits) return reduce(c->logits, V, V, 1, t);
             HIP_OK(hipMemcpyAsync(c->sc_logits + (t - r0) * V, c->logits, (size_t)V * 4, hipMemcpyDeviceToDevice, c->stream));
             if (t + 1 - r0 == (size_t)c->sc_rows || t + 1 == n) {
                 if (copy_out(c->sc_logits, V, (int)(t + 1 - r0), r0)) return -1;
                 r0 = t + 1;
             }
-        }
+            return 0;
+        };
+        if (decode_given_tokens(c, start_pos, n, keep_logits)) return -1;
     }
     double* h_lp = reinterpret_cast<double*>(c->h_sc);
     uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8);
@@ -1751,9 +1728,7 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
         if (n > 1) HIP_OK(hipMemcpyAsync(h_lp, c->sc_lp, (n - 1) * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipMemcpyAsync(h_idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
     }
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    if (finish_call(c)) return -1;
     if (!out_logits) {
         double sum = 0.0;
         for (size_t t = 0; t + 1 < n; ++t) { if (logprobs) logprobs[t] = (float)h_lp[t]; sum += h_lp[t]; }
@@ -1782,25 +1757,12 @@ extern "C" int lmrs_tokens_path(const lmrs_ctx* c, size_t n, int* batched) {
 }
 
 extern "C" int lmrs_prefill_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t* new_pos) {
-    if (n == 0) return fail("no tokens to ingest (n == 0)");
-    if (!c || !tokens) return fail("NULL argument");
-    if ((size_t)start_pos + n > c->args.seq_len) return fail("start_pos + n exceeds seq_len");
-    for (size_t i = 0; i < n; ++i) if (tokens[i] >= c->args.vocab_size) return fail("token " + std::to_string(i) + " out of range");
-    HIP_OK(hipSetDevice(c->device));
-    memcpy(c->h_tok, tokens, n * 4);
-    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+    if (stage_tokens(c, tokens, n, start_pos, n)) return -1;
     if (tokens_batched(c, n)) {
         if (prefill_token_run(c, start_pos, n)) return -1;
         if (set_state(c, start_pos + (uint32_t)n, 0)) return -1;
-    } else {
-        // the decode step per token, prompt_end past the run: every step embeds the next GIVEN token and its classifier's result goes nowhere
-        if (set_state(c, start_pos, start_pos + (uint32_t)n)) return -1;
-        HIP_OK(launch_embed(embed_args(c), c->stream));
-        for (size_t t = 0; t < n; ++t) if (launch_step(c, start_pos + (uint32_t)t)) return -1;
-    }
-    if (queue_err(c)) return -1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (check_err(c)) return -1;
+    } else if (decode_given_tokens(c, start_pos, n, [](size_t) { return 0; })) return -1;      // (the classifier's result of every step goes nowhere)
+    if (finish_call(c)) return -1;
     if (new_pos) *new_pos = start_pos + (uint32_t)n;
     return 0;
 }
@@ -1876,7 +1838,7 @@ extern "C" int lmrs_bench_gemv(lmrs_ctx* c, int iters, double* us5, double* byte
 extern "C" int lmrs_bench_step(lmrs_ctx* c, uint32_t pos, int iters, double* us9, double* bytes9, int* count9) {
     if (!c || iters <= 0 || !us9 || !bytes9 || !count9) return fail("bad argument");
     const bool sharded = c->comm || c->p2p;
-    if (sharded ? !(c->comm || c->p2p_ready) : !c->g_step) return fail("lmrs_bench_step: the context cannot run a step by itself");
+    if (sharded ? !(c->comm || c->p2p_ready) : !primary_graph(c)) return fail("lmrs_bench_step: the context cannot run a step by itself");
     if ((size_t)pos + iters + 1 > c->args.seq_len) return fail("positions out of range");
     if (c->att_split_pos > 0 && (int)(pos + iters + 1) > c->att_split_pos) return fail("lmrs_bench_step: positions below the split-attention threshold only");
     HIP_OK(hipSetDevice(c->device));
@@ -1885,9 +1847,9 @@ extern "C" int lmrs_bench_step(lmrs_ctx* c, uint32_t pos, int iters, double* us9
     const double bpe = c->q4 ? 0.5 : 1.0, sc = bpe + 4.0 / 128.0, dim = a.dim, att = c->att_dim, kv = c->kv_dim, attf = c->att_full, hidf = a.hidden_dim;
     const double wbytes[9] = {dim * (att + 2 * kv) * sc, 0, attf * c->dim_l * sc, 2.0 * dim * c->hid_l * sc, hidf * c->dim_l * sc, (double)c->voc_l * dim * sc, 0, 0, 0};
     if (set_state(c, pos, 0)) return -1;
-    const int qmode = qa_mode_for(c, pos + iters);       // the launches of the graph the timed run replayed (the mode of the last position)
-    const bool merged = qmode != 0;
-    auto one_step = [&]() -> int { c->ex_slot = 0; c->qa_mode = qmode; const int r = sharded ? enqueue_step_sharded(c) : enqueue_step(c); c->qa_mode = 0; return r; };
+    const StepForm form = step_form_for(c, pos + iters);       // the launches of the graph the timed run replayed (the form of the last position)
+    const bool merged = form.qa_mode != 0;
+    auto one_step = [&]() -> int { return sharded ? enqueue_step_sharded(c, form) : enqueue_step(c, form); };
     // dry pass (also the untimed warm-up: the first eager launches pay one-off costs): how many launches does a step have?
     hipEvent_t dummy[2]; int dtag[1];
     HIP_OK(hipEventCreate(&dummy[0])); HIP_OK(hipEventCreate(&dummy[1]));
@@ -1964,8 +1926,7 @@ extern "C" int lmrs_debug_inject(lmrs_ctx* c, int what, int a, int b) {
         if (!(c->comm || c->p2p)) return fail("not a row-sharded context");
         HIP_OK(hipSetDevice(c->device));
         HIP_OK(hipStreamSynchronize(c->stream));
-        if (c->g_step) { (void)hipGraphExecDestroy(c->g_step); c->g_step = nullptr; }
-        for (auto& g : c->g_step_long) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        destroy_step_graphs(c);
         c->eager = true; c->inj_stall_seg = a; c->inj_stall_ticks = (long long)b * 100;          // 100 MHz wall clock
         return 0;
     }
@@ -1989,7 +1950,7 @@ extern "C" int lmrs_step_info(const lmrs_ctx* c, uint32_t pos, int* n_launches, 
     double b = L * ((dim * att + 2 * dim * kv + att * dim + 3 * dim * hid) * (bpe + 4.0 / 128.0) + n_norm * dim * 4) + V * dim * (bpe + 4.0 / 128.0) +
                dim * 4 + L * 2 * kv * 4 * ((double)pos + 2);
     if (algo_bytes) *algo_bytes = b;
-    if (n_launches) *n_launches = (a.model_type == LMRS_GEMMA && !c->gemma_fused ? 7 : (qa_mode_for(c, pos) && !(c->att_split_pos > 0 && (int)pos >= c->att_split_pos) ? 4 : 5)) * (int)a.n_layers + (c->cls_tail ? 1 : 2);
+    if (n_launches) *n_launches = (a.model_type == LMRS_GEMMA && !c->gemma_fused ? 7 : (step_form_for(c, pos).qa_mode ? 4 : 5)) * (int)a.n_layers + (c->cls_tail ? 1 : 2);
     return 0;
 }
 
