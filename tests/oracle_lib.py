@@ -19,6 +19,20 @@ class Args(C.Structure):
         ("multimodal", C.c_uint8), ("_pad", C.c_uint8), ("group_size", C.c_uint32)]
 
 
+class Stats(C.Structure):
+    """lmrs_ref_stats (oracle/lmrs_oracle.c): which numerical regimes the oracle's forward passes visited since stats_reset()."""
+    _fields_ = [(n, C.c_uint64) for n in ("att_exp_zero", "att_exp_subnormal", "score_cap_sat", "score_cap_bend", "logit_cap_sat")] + [
+        ("q_zero", C.c_uint64 * 5)] + [(n, C.c_uint64) for n in ("silu_exp_inf", "silu_arg_above_88", "gelu_tanh_sat")] + [
+        ("max_scale_ratio", C.c_double)]
+
+    Q_SITES = ("x", "att", "xb2", "h", "final")
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "q_zero"}
+        d.update({"q_zero_" + s: int(self.q_zero[i]) for i, s in enumerate(self.Q_SITES)})
+        return d
+
+
 def build_oracle(force: bool = False):
     src = os.path.join(ORACLE_DIR, "lmrs_oracle.c")
     if force or not os.path.exists(ORACLE_SO) or os.path.getmtime(ORACLE_SO) < os.path.getmtime(src):
@@ -66,6 +80,8 @@ def lib():
         L.lmrs_ref_sampler_new.argtypes = [u32, C.c_float, C.c_float, C.c_uint64]; L.lmrs_ref_sampler_new.restype = vp
         L.lmrs_ref_sampler_free.argtypes = [vp]; L.lmrs_ref_sampler_free.restype = None
         L.lmrs_ref_sampler_sample.argtypes = [vp, vp]; L.lmrs_ref_sampler_sample.restype = C.c_int64
+        L.lmrs_ref_stats_reset.argtypes = []; L.lmrs_ref_stats_reset.restype = None
+        L.lmrs_ref_stats_get.argtypes = [C.POINTER(Stats)]; L.lmrs_ref_stats_get.restype = None
         _lib = L
     return _lib
 
@@ -217,6 +233,18 @@ class Sampler:
         if t < 0:
             raise RuntimeError("sample_topp: no candidate above the cutoff (the reference panics)")
         return t
+
+
+def stats_reset():
+    lib().lmrs_ref_stats_reset()
+
+
+def stats() -> dict:
+    """The regime witnesses since the last stats_reset(), over every Oracle of this process.  The oracle's own OpenMP team is counted
+    atomically; the scale ratio, reset and get are not synchronised: call the oracle from one Python thread between stats_reset() and stats()."""
+    st = Stats()
+    lib().lmrs_ref_stats_get(C.byref(st))
+    return st.as_dict()
 
 
 def threads() -> int:

@@ -176,9 +176,12 @@ def image_size(cfg: ModelCfg, q_type: int, gs: int = 128) -> int:
     return n
 
 
-def build_image(cfg: ModelCfg | str, q_type: int = Q8_0, seed: int = 1234, gs: int = 128, threads: int | None = None, multimodal: int = 0) -> np.ndarray:
+def build_image(cfg: ModelCfg | str, q_type: int = Q8_0, seed: int = 1234, gs: int = 128, threads: int | None = None, multimodal: int = 0,
+                transform=None) -> np.ndarray:
     """Returns the whole LMRS image as a uint8 array (pass .ctypes.data / len to lmrs_create).
-    multimodal = 1 sets the header flag (export.py:84); the vision and processor sections (tools/synth_vision.py) follow the image."""
+    multimodal = 1 sets the header flag (export.py:84); the vision and processor sections (tools/synth_vision.py) follow the image.
+    transform(family_name, layer, row0, w) -> w: applied to every f32 master slice (rows row0.. of a family / layer) before it is
+    quantised and written; it must be a pure function of its arguments (slices run on a thread pool).  None: the bytes as ever."""
     if isinstance(cfg, str):
         cfg = CONFIGS[cfg]
     if q_type != Q_NONE:
@@ -209,6 +212,9 @@ def build_image(cfg: ModelCfg | str, q_type: int = Q8_0, seed: int = 1234, gs: i
         fi, layer, row0, rows, q_base, s_base, kind = t
         C = families(cfg)[fi][4]
         w = float_tensor(cfg, seed, fi, layer, row0, rows)
+        if transform is not None:
+            w = np.ascontiguousarray(transform(families(cfg)[fi][0], layer, row0, w), np.float32)
+            assert w.shape == (rows, C)
         if kind == "n" or q_type == Q_NONE:
             b = w.reshape(-1).view(np.uint8)
             o = q_base + row0 * C * 4
