@@ -1264,12 +1264,116 @@ __device__ __forceinline__ float att_score_chain(f32x4v (&kk)[NG], __amdgpu_buff
     return score;
 }
 
+// ---- the phases every attention form shares (the forms differ in who owns which keys, where the chains cross waves and how many barriers
+// there are; what follows is the same in all of them and lives here once) ----
+// One RoPE pair (transformer.rs:480-491) with the host-built (fcr, fci) table: four multiplies, one subtract, one add, in this order.
+__device__ __forceinline__ float2 rope_rotate(float v0, float v1, float fcr, float fci) {
+    const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
+    return make_float2(a0 - a1, b0 + b1);
+}
+// Dims j and j + half of the key of position `pos` into a blocked key array k[dim / 4][S][4]: the K cache of one kv head (att_k_head), or a
+// wave form's LDS tile (S = its TW).
+__device__ __forceinline__ void k_store_pair(float* k, int S, int pos, int j, int half, float r0, float r1) {
+    k[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
+    k[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
+}
+// Gemma-2's score soft-cap and window term (transformer.rs:518-526).  The window test is u32 arithmetic as in the reference (:525); wpos is
+// the position the reference tests against (see attention_body).
+__device__ __forceinline__ float gemma_cap_window(float score, int wpos, int t) {
+    score = score / 50.0f;
+    score = (float)tanh((double)score);
+    score = score * 50.0f;
+    return score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
+}
+// The score dot of one lane's key out of LDS (the wave forms with a K tile): dim group g of the key is the float4 k[g * ks] (ks = the
+// tile's TW; 1 for a key that lies contiguous), the rotated query is qs.  Batches of GB = 4 dim groups (8 x 16-byte LDS reads) ping-pong one
+// ahead of the adds; the running sum passes through an opaque asm per batch so that the next batch's reads are ISSUED before this batch's
+// arithmetic.  One sequential chain over the head dims, as att_score_chain.
+template <int HS4>
+__device__ __forceinline__ float tile_score(const float4* k, int ks, const float* qs) {
+    constexpr int GB = 4;
+    static_assert(HS4 % (2 * GB) == 0, "head size");
+    const float4* q4 = reinterpret_cast<const float4*>(qs);
+    auto dot = [](float score, const float4 (&q)[GB], const float4 (&kk)[GB]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+            float pr;
+            pr = q[u].x * kk[u].x; score = score + pr;
+            pr = q[u].y * kk[u].y; score = score + pr;
+            pr = q[u].z * kk[u].z; score = score + pr;
+            pr = q[u].w * kk[u].w; score = score + pr;
+        }
+        return score;
+    };
+    float score = 0.0f;
+    float4 ka[GB], qa[GB], kb[GB], qb[GB];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) { ka[u] = k[u * ks]; qa[u] = q4[u]; }
+#pragma unroll
+    for (int g0 = 0; g0 < HS4; g0 += 2 * GB) {
+#pragma unroll
+        for (int u = 0; u < GB; ++u) { kb[u] = k[(g0 + GB + u) * ks]; qb[u] = q4[g0 + GB + u]; }
+        asm volatile("" : "+v"(score) : : "memory");
+        score = dot(score, qa, ka);
+        if (g0 + 2 * GB < HS4) {
+#pragma unroll
+            for (int u = 0; u < GB; ++u) { ka[u] = k[(g0 + 2 * GB + u) * ks]; qa[u] = q4[g0 + 2 * GB + u]; }
+        }
+        asm volatile("" : "+v"(score) : : "memory");
+        score = dot(score, qb, kb);
+    }
+    return score;
+}
+// The in-launch hand-off of the merged qkv + attention launch (qkv_attn_kernel): q, the raw key and the value row of this position are
+// produced by the GEMV workgroups of the SAME launch as 8-byte {value, tag} granules (EPI_QKV_TAG).
+struct AttTag { const unsigned long long* gran; unsigned tag; int att_dim, kv_dim; int* err; };
+// Poll this lane's NG granules gp[] until the whole wave sees the launch's tag in all of them; xg[] = the granules.  A sweep is one load of
+// each granule; two sweeps are in flight (a sweep's latency, not up to twice it, after the producer's store).  Every call is bounded: after
+// kTagSpinMax rounds - or as soon as another wave has given up - the wave sets *tg.err (stage = layer + 1, first reporter wins) and goes on
+// with whatever the last sweep held.  The host then rejects the whole call ("in-launch synchronisation timed out": check_err), so which
+// stale sweep a timed-out wave computes with is unobservable; every form shares this one choice.
+template <int NG>
+__device__ __forceinline__ void poll_granules(const unsigned long long* const (&gp)[NG], const AttTag& tg, int layer, unsigned long long (&xg)[NG]) {
+    auto sweep = [&](unsigned long long (&x)[NG]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < NG; ++k) x[k] = __hip_atomic_load(gp[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto fresh = [&](const unsigned long long (&x)[NG]) __attribute__((always_inline)) {
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < NG; ++k) ok = ok && (unsigned)(x[k] >> 32) == tg.tag;
+        return __all(ok) != 0;
+    };
+    auto take = [&](const unsigned long long (&x)[NG]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < NG; ++k) xg[k] = x[k];
+    };
+    unsigned long long xa[NG], xb[NG];
+    sweep(xa);
+    for (unsigned spins = 0;; ++spins) {
+        sweep(xb);
+        if (fresh(xa)) { take(xa); break; }
+        sweep(xa);
+        if (fresh(xb)) { take(xb); break; }
+        if (spins > kTagSpinMax || (spins & 1023) == 1023) {         // bounded: report and finish with garbage instead of hanging
+            const int e = __hip_atomic_load(tg.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (e != 0 || spins > kTagSpinMax) {
+                if (e == 0) __hip_atomic_store(tg.err, layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                take(xb);
+                break;
+            }
+        }
+    }
+}
+// This lane's three granules of head dim d: q of query head h, the raw key and the value row of kv head kvh.
+__device__ __forceinline__ void granules_of(const AttTag& tg, int h, int kvh, int hs, int d, const unsigned long long** gp) {
+    gp[0] = tg.gran + h * hs + d; gp[1] = tg.gran + tg.att_dim + kvh * hs + d; gp[2] = tg.gran + tg.att_dim + tg.kv_dim + kvh * hs + d;
+}
+
 // GEMMA: score soft-cap + window mask (a compile-time switch: the f64 tanh is ~230 instructions and a dozen registers)
 // ROT (batched prefill): q is already rotated and the key of `pos` already in the cache (rope_rows_kernel).
-// TAG (merged qkv + attention launch): q, the raw key and the value row of this position are produced by the GEMV workgroups of
-// the SAME launch as 8-byte {value, tag} granules (EPI_QKV_TAG); the lanes that need them poll the granules themselves, after
-// all K / V loads of the earlier positions have been issued.
-struct AttTag { const unsigned long long* gran; unsigned tag; int att_dim, kv_dim; int* err; };
+// TAG (merged qkv + attention launch, AttTag): the lanes that need q, the raw key and the value row of this position poll the granules
+// themselves, after all K / V loads of the earlier positions have been issued.
 template <int HS, int NF, bool COH, bool PRE = false, bool GEMMA = false, bool ROT = false, bool TAG = false>
 __device__ __forceinline__ void attention_body(const AttnArgs& a, int h, int pos, char* smem, uint64_t etab, const AttPre& pre = AttPre(), const AttTag& tg = AttTag()) {
     static_assert(!PRE || HS / 2 <= kBlock, "one RoPE pair per lane");
@@ -1306,35 +1410,11 @@ __device__ __forceinline__ void attention_body(const AttnArgs& a, int h, int pos
     if constexpr (TAG) {
         cs_tag = *reinterpret_cast<const float2*>(a.rope + ((size_t)pos * half + (tid < half ? tid : 0)) * 2);   // ahead of the polls
         if (tid < HS) {
-            const unsigned long long* gq = tg.gran + h * HS + tid;
-            const unsigned long long* gk = tg.gran + tg.att_dim + kvh * HS + tid;
-            const unsigned long long* gv = tg.gran + tg.att_dim + tg.kv_dim + kvh * HS + tid;
-            unsigned long long x0, x1, x2, y0, y1, y2;
-            auto fresh = [&](unsigned long long p0, unsigned long long p1, unsigned long long p2) __attribute__((always_inline)) {
-                return __all((unsigned)(p0 >> 32) == tg.tag && (unsigned)(p1 >> 32) == tg.tag && (unsigned)(p2 >> 32) == tg.tag) != 0;
-            };
-            // two sweeps in flight (a sweep's latency, not up to twice it, after the store)
-            x0 = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            x1 = __hip_atomic_load(gk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            x2 = __hip_atomic_load(gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (unsigned spins = 0;; ++spins) {
-                y0 = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                y1 = __hip_atomic_load(gk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                y2 = __hip_atomic_load(gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (fresh(x0, x1, x2)) break;
-                x0 = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                x1 = __hip_atomic_load(gk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                x2 = __hip_atomic_load(gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (fresh(y0, y1, y2)) { x0 = y0; x1 = y1; x2 = y2; break; }
-                if (spins > kTagSpinMax || (spins & 1023) == 1023) {     // bounded: report and finish with garbage instead of hanging
-                    const int e = __hip_atomic_load(tg.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (e != 0 || spins > kTagSpinMax) {
-                        if (e == 0) __hip_atomic_store(tg.err, a.layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-            }
-            q[tid] = __uint_as_float((unsigned)x0); kn[tid] = __uint_as_float((unsigned)x1); vn[tid] = __uint_as_float((unsigned)x2);
+            const unsigned long long* gp[3];
+            unsigned long long xg[3];
+            granules_of(tg, h, kvh, HS, tid, gp);
+            poll_granules<3>(gp, tg, a.layer, xg);
+            q[tid] = __uint_as_float((unsigned)xg[0]); kn[tid] = __uint_as_float((unsigned)xg[1]); vn[tid] = __uint_as_float((unsigned)xg[2]);
         }
         lds_barrier();
         ATT_STAMP(1);
@@ -1344,36 +1424,17 @@ __device__ __forceinline__ void attention_body(const AttnArgs& a, int h, int pos
         float2 cs;
         if constexpr (PRE) cs = pre.cs; else if constexpr (TAG) cs = cs_tag; else cs = *reinterpret_cast<const float2*>(a.rope + ((size_t)pos * half + j) * 2);
         const float fcr = cs.x, fci = cs.y;
-        if constexpr (TAG) {                                   // raw values in place in LDS; this thread owns both halves of pair j
-            {
-                const float v0 = q[j], v1 = q[j + half];
-                const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-                q[j] = a0 - a1; q[j + half] = b0 + b1;
-            }
-            const float v0 = kn[j], v1 = kn[j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            const float r0 = a0 - a1, r1 = b0 + b1;
-            kn[j] = r0; kn[j + half] = r1;
-            kT[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
-            kT[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
-            continue;
-        }
-        {
-            const float v0 = PRE ? pre.q0 : ld_f32<COH>(a.q + h * HS + j), v1 = PRE ? pre.q1 : ld_f32<COH>(a.q + h * HS + j + half);
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            q[j] = a0 - a1; q[j + half] = b0 + b1;
-        }
-        {
-            const float v0 = PRE ? pre.k0 : ld_f32<COH>(a.k_raw + kvh * HS + j), v1 = PRE ? pre.k1 : ld_f32<COH>(a.k_raw + kvh * HS + j + half);
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            const float r0 = a0 - a1, r1 = b0 + b1;
-            kn[j] = r0; kn[j + half] = r1;
-            // Every head of the kv head stores the (identical) new key: the score loads below then find it in memory like
-            // every other key - the waves of a workgroup share the CU's L1, so store, vmcnt(0), barrier, load is coherent -
-            // and later launches read it from there anyway.
-            kT[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
-            kT[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
-        }
+        // the raw pair: TAG - in place in LDS (this thread owns both halves of pair j); PRE - loaded by the caller; else from memory
+        const float q0 = TAG ? q[j] : PRE ? pre.q0 : ld_f32<COH>(a.q + h * HS + j), q1 = TAG ? q[j + half] : PRE ? pre.q1 : ld_f32<COH>(a.q + h * HS + j + half);
+        const float2 rq = rope_rotate(q0, q1, fcr, fci);
+        q[j] = rq.x; q[j + half] = rq.y;
+        const float k0 = TAG ? kn[j] : PRE ? pre.k0 : ld_f32<COH>(a.k_raw + kvh * HS + j), k1 = TAG ? kn[j + half] : PRE ? pre.k1 : ld_f32<COH>(a.k_raw + kvh * HS + j + half);
+        const float2 rk = rope_rotate(k0, k1, fcr, fci);
+        kn[j] = rk.x; kn[j + half] = rk.y;
+        // Every head of the kv head stores the (identical) new key: the score loads below then find it in memory like
+        // every other key - the waves of a workgroup share the CU's L1, so store, vmcnt(0), barrier, load is coherent -
+        // and later launches read it from there anyway.
+        k_store_pair(kT, S, pos, j, half, rk.x, rk.y);
         if constexpr (COH) {
             vn[j] = ld_f32<true>(vbase + (size_t)pos * kv_dim + j);
             vn[j + half] = ld_f32<true>(vbase + (size_t)pos * kv_dim + j + half);
@@ -1400,12 +1461,7 @@ __device__ __forceinline__ void attention_body(const AttnArgs& a, int h, int pos
     float lmax = __uint_as_float(0xff800000u);
     auto finish_score = [&](float score, int t) __attribute__((always_inline)) {
         score = score / sqrt_hs;
-        if constexpr (GEMMA) {                         // transformer.rs:518-526
-            score = score / 50.0f;
-            score = (float)tanh((double)score);
-            score = score * 50.0f;
-            score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);   // :525, u32 arithmetic as in the reference
-        }
+        if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
         if (t < T) { att[t] = score; lmax = fmaxf(lmax, score); }
     };
     finish_score(att_score_chain<HS, KG>(kk, krs, tc0 * 16, q, S), tid);                 // timesteps 0..255
@@ -1579,6 +1635,8 @@ __device__ __forceinline__ void attention_wave_tag(const AttnArgs& a, const int 
     }
     // Values: v[t] = v_t[this lane's dims], one 256-byte row per load (buffer loads: the row offset is a scalar), blocks of 16 rows
     // NESTED so that the whole prefetch has ONE join (a join after every block made hipcc drain the loads there: 5.8 us for 100 rows).
+    // (Each wave form keeps its own copy of this construct: one shared helper for the four was tried and changed the generated code of the
+    // 96- and 128-wide classes - 1 KB at 128 - where every other shared phase moved it by a few instructions.)
     float v[ND][TW];
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vbase), 0, 0x7fffffff, 0x00020000);
     const int vrow = kv_dim * 4;
@@ -1606,50 +1664,13 @@ __device__ __forceinline__ void attention_wave_tag(const AttnArgs& a, const int 
         for (int i = 0; i < ND; ++i) { v[i][t] = t < pos ? v[i][t] : 0.0f; asm volatile("" : "+v"(v[i][t])); }
     if (a.dbg && lane == 0 && blockIdx.x == 0) a.dbg[1] = wall_clock64();
 
-    // ---- q, raw k, v of this position: poll the granules (two sweeps in flight: a sweep's latency, not twice it, after the store)
+    // ---- q, raw k, v of this position: poll the granules (lane d: q[d], k[d], v[d])
     unsigned long long xg[3 * ND];
     {
         const unsigned long long* gp[3 * ND];
 #pragma unroll
-        for (int i = 0; i < ND; ++i) {
-            const int d = lane + 64 * i, dc = d < HS ? d : 0;
-            gp[3 * i] = tg.gran + h * HS + dc; gp[3 * i + 1] = tg.gran + tg.att_dim + kvh * HS + dc; gp[3 * i + 2] = tg.gran + tg.att_dim + tg.kv_dim + kvh * HS + dc;
-        }
-        auto sweep = [&](unsigned long long (&x)[3 * ND]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < 3 * ND; ++k) x[k] = __hip_atomic_load(gp[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        auto fresh = [&](const unsigned long long (&x)[3 * ND]) __attribute__((always_inline)) {
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 3 * ND; ++k) ok = ok && (unsigned)(x[k] >> 32) == tg.tag;
-            return __all(ok) != 0;
-        };
-        unsigned long long xa[3 * ND], xb[3 * ND];
-        sweep(xa);
-        for (unsigned spins = 0;; ++spins) {
-            sweep(xb);
-            if (fresh(xa)) {
-#pragma unroll
-                for (int k = 0; k < 3 * ND; ++k) xg[k] = xa[k];
-                break;
-            }
-            sweep(xa);
-            if (fresh(xb)) {
-#pragma unroll
-                for (int k = 0; k < 3 * ND; ++k) xg[k] = xb[k];
-                break;
-            }
-            if (spins > kTagSpinMax || (spins & 1023) == 1023) {     // bounded: report and finish with garbage instead of hanging
-                const int e = __hip_atomic_load(tg.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (e != 0 || spins > kTagSpinMax) {
-                    if (e == 0) __hip_atomic_store(tg.err, a.layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int k = 0; k < 3 * ND; ++k) xg[k] = xb[k];
-                    break;
-                }
-            }
-        }
+        for (int i = 0; i < ND; ++i) { const int d = lane + 64 * i; granules_of(tg, h, kvh, HS, d < HS ? d : 0, gp + 3 * i); }
+        poll_granules<3 * ND>(gp, tg, a.layer, xg);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (loads return in order: the key tile's DMA landed before the granules did)
     if (a.dbg && lane == 0 && blockIdx.x == 0) a.dbg[2] = wall_clock64();
@@ -1666,19 +1687,11 @@ __device__ __forceinline__ void attention_wave_tag(const AttnArgs& a, const int 
     for (int i = 0; i < NH2; ++i) {
         const int j = lane + 64 * i;
         if (j < half) {
-            const float fcr = cs[i].x, fci = cs[i].y;
-            {
-                const float v0 = qs[j], v1 = qs[j + half];
-                const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-                qs[j] = a0 - a1; qs[j + half] = b0 + b1;
-            }
-            const float v0 = kn[j], v1 = kn[j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            const float r0 = a0 - a1, r1 = b0 + b1;
-            kT[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
-            kT[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
-            reinterpret_cast<float*>(kt)[(((j >> 2) * TW + pos) << 2) + (j & 3)] = r0;
-            reinterpret_cast<float*>(kt)[((((j + half) >> 2) * TW + pos) << 2) + ((j + half) & 3)] = r1;
+            const float2 rq = rope_rotate(qs[j], qs[j + half], cs[i].x, cs[i].y);
+            qs[j] = rq.x; qs[j + half] = rq.y;
+            const float2 rk = rope_rotate(kn[j], kn[j + half], cs[i].x, cs[i].y);
+            k_store_pair(kT, S, pos, j, half, rk.x, rk.y);
+            k_store_pair(reinterpret_cast<float*>(kt), TW, pos, j, half, rk.x, rk.y);
         }
     }
     if (a.dbg && lane == 0 && blockIdx.x == 0) a.dbg[3] = wall_clock64();
@@ -1694,48 +1707,8 @@ __device__ __forceinline__ void attention_wave_tag(const AttnArgs& a, const int 
         sc[p] = ninf;
         if (64 * p < T) {                                           // wave-uniform
             const int t = 64 * p + lane;
-            float score = 0.0f;
-            // batches of 4 dim groups (8 x 16-byte LDS reads) ping-pong one ahead of the adds; the running sum passes through an
-            // opaque asm per batch so that the next batch's reads are ISSUED before this batch's arithmetic
-            constexpr int GB = 4;
-            static_assert(HS4 % (2 * GB) == 0, "head size");
-            float4 ka[GB], qa[GB], kb[GB], qb[GB];
-#pragma unroll
-            for (int u = 0; u < GB; ++u) { ka[u] = kt[u * TW + t]; qa[u] = reinterpret_cast<const float4*>(qs)[u]; }
-#pragma unroll
-            for (int g0 = 0; g0 < HS4; g0 += 2 * GB) {
-#pragma unroll
-                for (int u = 0; u < GB; ++u) { kb[u] = kt[(g0 + GB + u) * TW + t]; qb[u] = reinterpret_cast<const float4*>(qs)[g0 + GB + u]; }
-                asm volatile("" : "+v"(score) : : "memory");
-#pragma unroll
-                for (int u = 0; u < GB; ++u) {
-                    float pr;
-                    pr = qa[u].x * ka[u].x; score = score + pr;
-                    pr = qa[u].y * ka[u].y; score = score + pr;
-                    pr = qa[u].z * ka[u].z; score = score + pr;
-                    pr = qa[u].w * ka[u].w; score = score + pr;
-                }
-                if (g0 + 2 * GB < HS4) {
-#pragma unroll
-                    for (int u = 0; u < GB; ++u) { ka[u] = kt[(g0 + 2 * GB + u) * TW + t]; qa[u] = reinterpret_cast<const float4*>(qs)[g0 + 2 * GB + u]; }
-                }
-                asm volatile("" : "+v"(score) : : "memory");
-#pragma unroll
-                for (int u = 0; u < GB; ++u) {
-                    float pr;
-                    pr = qb[u].x * kb[u].x; score = score + pr;
-                    pr = qb[u].y * kb[u].y; score = score + pr;
-                    pr = qb[u].z * kb[u].z; score = score + pr;
-                    pr = qb[u].w * kb[u].w; score = score + pr;
-                }
-            }
-            score = score / sqrt_hs;
-            if constexpr (GEMMA) {                                  // transformer.rs:518-526
-                score = score / 50.0f;
-                score = (float)tanh((double)score);
-                score = score * 50.0f;
-                score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
-            }
+            float score = tile_score<HS4>(kt + t, TW, qs) / sqrt_hs;
+            if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
             sc[p] = t < T ? score : ninf;
             lmax = fmaxf(lmax, sc[p]);
         }
@@ -1866,33 +1839,9 @@ __device__ __forceinline__ void attention_pair_tag(const AttnArgs& a, const int 
     // ---- q, raw k, v of this position: poll the granules (both waves: no hand-off before the scores)
     unsigned long long xg[3];
     {
-        const unsigned long long* gp[3] = {tg.gran + h * HS + lane, tg.gran + tg.att_dim + kvh * HS + lane, tg.gran + tg.att_dim + tg.kv_dim + kvh * HS + lane};
-        auto sweep = [&](unsigned long long (&x)[3]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = __hip_atomic_load(gp[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        auto fresh = [&](const unsigned long long (&x)[3]) __attribute__((always_inline)) {
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ok = ok && (unsigned)(x[k] >> 32) == tg.tag;
-            return __all(ok) != 0;
-        };
-        unsigned long long xa[3], xb[3];
-        sweep(xa);
-        for (unsigned spins = 0;; ++spins) {
-            sweep(xb);
-            if (fresh(xa)) { xg[0] = xa[0]; xg[1] = xa[1]; xg[2] = xa[2]; break; }
-            sweep(xa);
-            if (fresh(xb)) { xg[0] = xb[0]; xg[1] = xb[1]; xg[2] = xb[2]; break; }
-            if (spins > kTagSpinMax || (spins & 1023) == 1023) {     // bounded: report and finish with garbage instead of hanging
-                const int e = __hip_atomic_load(tg.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (e != 0 || spins > kTagSpinMax) {
-                    if (e == 0) __hip_atomic_store(tg.err, a.layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    xg[0] = xb[0]; xg[1] = xb[1]; xg[2] = xb[2];
-                    break;
-                }
-            }
-        }
+        const unsigned long long* gp[3];
+        granules_of(tg, h, kvh, HS, lane, gp);
+        poll_granules<3>(gp, tg, a.layer, xg);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (loads return in order: the key tile's DMA landed before the granules did)
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[2] = wall_clock64();
@@ -1902,23 +1851,11 @@ __device__ __forceinline__ void attention_pair_tag(const AttnArgs& a, const int 
     // position `pos` into the LDS tile
     if (lane < half) {
         const int j = lane;
-        const float fcr = cs.x, fci = cs.y;
-        {
-            const float v0 = qs[j], v1 = qs[j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            qs[j] = a0 - a1; qs[j + half] = b0 + b1;
-        }
-        const float v0 = kn[j], v1 = kn[j + half];
-        const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-        const float r0 = a0 - a1, r1 = b0 + b1;
-        if (wv == 0) {
-            kT[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
-            kT[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
-        }
-        if ((pos >> 6) == (two ? wv : 0)) {
-            reinterpret_cast<float*>(kt)[(((j >> 2) * TW + pos) << 2) + (j & 3)] = r0;
-            reinterpret_cast<float*>(kt)[((((j + half) >> 2) * TW + pos) << 2) + ((j + half) & 3)] = r1;
-        }
+        const float2 rq = rope_rotate(qs[j], qs[j + half], cs.x, cs.y);
+        qs[j] = rq.x; qs[j + half] = rq.y;
+        const float2 rk = rope_rotate(kn[j], kn[j + half], cs.x, cs.y);
+        if (wv == 0) k_store_pair(kT, S, pos, j, half, rk.x, rk.y);
+        if ((pos >> 6) == (two ? wv : 0)) k_store_pair(reinterpret_cast<float*>(kt), TW, pos, j, half, rk.x, rk.y);
     }
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[3] = wall_clock64();
 
@@ -1929,45 +1866,8 @@ __device__ __forceinline__ void attention_pair_tag(const AttnArgs& a, const int 
     const int t = tb + lane;
     float sc;
     {
-        float score = 0.0f;
-        constexpr int GB = 4;
-        float4 ka[GB], qa[GB], kb[GB], qb[GB];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) { ka[u] = kt[u * TW + t]; qa[u] = reinterpret_cast<const float4*>(qs)[u]; }
-#pragma unroll
-        for (int g0 = 0; g0 < HS4; g0 += 2 * GB) {
-#pragma unroll
-            for (int u = 0; u < GB; ++u) { kb[u] = kt[(g0 + GB + u) * TW + t]; qb[u] = reinterpret_cast<const float4*>(qs)[g0 + GB + u]; }
-            asm volatile("" : "+v"(score) : : "memory");
-#pragma unroll
-            for (int u = 0; u < GB; ++u) {
-                float pr;
-                pr = qa[u].x * ka[u].x; score = score + pr;
-                pr = qa[u].y * ka[u].y; score = score + pr;
-                pr = qa[u].z * ka[u].z; score = score + pr;
-                pr = qa[u].w * ka[u].w; score = score + pr;
-            }
-            if (g0 + 2 * GB < HS4) {
-#pragma unroll
-                for (int u = 0; u < GB; ++u) { ka[u] = kt[(g0 + 2 * GB + u) * TW + t]; qa[u] = reinterpret_cast<const float4*>(qs)[g0 + 2 * GB + u]; }
-            }
-            asm volatile("" : "+v"(score) : : "memory");
-#pragma unroll
-            for (int u = 0; u < GB; ++u) {
-                float pr;
-                pr = qb[u].x * kb[u].x; score = score + pr;
-                pr = qb[u].y * kb[u].y; score = score + pr;
-                pr = qb[u].z * kb[u].z; score = score + pr;
-                pr = qb[u].w * kb[u].w; score = score + pr;
-            }
-        }
-        score = score / sqrt_hs;
-        if constexpr (GEMMA) {                                      // transformer.rs:518-526
-            score = score / 50.0f;
-            score = (float)tanh((double)score);
-            score = score * 50.0f;
-            score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
-        }
+        float score = tile_score<HS4>(kt + t, TW, qs) / sqrt_hs;
+        if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
         sc = t < T ? score : ninf;
     }
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[4] = wall_clock64();
@@ -2130,33 +2030,9 @@ __device__ __forceinline__ void attention_multi_tag(const AttnArgs& a, const int
     // ---- q, raw k, v of this position: poll the granules (every wave: no hand-off before the scores)
     unsigned long long xg[3];
     {
-        const unsigned long long* gp[3] = {tg.gran + h * HS + lane, tg.gran + tg.att_dim + kvh * HS + lane, tg.gran + tg.att_dim + tg.kv_dim + kvh * HS + lane};
-        auto sweep = [&](unsigned long long (&x)[3]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = __hip_atomic_load(gp[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        auto fresh = [&](const unsigned long long (&x)[3]) __attribute__((always_inline)) {
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ok = ok && (unsigned)(x[k] >> 32) == tg.tag;
-            return __all(ok) != 0;
-        };
-        unsigned long long xa[3], xb[3];
-        sweep(xa);
-        for (unsigned spins = 0;; ++spins) {
-            sweep(xb);
-            if (fresh(xa)) { xg[0] = xa[0]; xg[1] = xa[1]; xg[2] = xa[2]; break; }
-            sweep(xa);
-            if (fresh(xb)) { xg[0] = xb[0]; xg[1] = xb[1]; xg[2] = xb[2]; break; }
-            if (spins > kTagSpinMax || (spins & 1023) == 1023) {     // bounded: report and finish with garbage instead of hanging
-                const int e = __hip_atomic_load(tg.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (e != 0 || spins > kTagSpinMax) {
-                    if (e == 0) __hip_atomic_store(tg.err, a.layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    xg[0] = xb[0]; xg[1] = xb[1]; xg[2] = xb[2];
-                    break;
-                }
-            }
-        }
+        const unsigned long long* gp[3];
+        granules_of(tg, h, kvh, HS, lane, gp);
+        poll_granules<3>(gp, tg, a.layer, xg);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[2] = wall_clock64();
@@ -2167,20 +2043,11 @@ __device__ __forceinline__ void attention_multi_tag(const AttnArgs& a, const int
     const bool own_pos = (pos >> 6) == wv;
     if (lane < half) {
         const int j = lane;
-        const float fcr = cs.x, fci = cs.y;
-        {
-            const float v0 = qs[j], v1 = qs[j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            qs[j] = a0 - a1; qs[j + half] = b0 + b1;
-        }
-        const float v0 = kn[j], v1 = kn[j + half];
-        const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-        const float r0 = a0 - a1, r1 = b0 + b1;
-        kn[j] = r0; kn[j + half] = r1;
-        if (wv == 0) {
-            kT[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
-            kT[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
-        }
+        const float2 rq = rope_rotate(qs[j], qs[j + half], cs.x, cs.y);
+        qs[j] = rq.x; qs[j + half] = rq.y;
+        const float2 rk = rope_rotate(kn[j], kn[j + half], cs.x, cs.y);
+        kn[j] = rk.x; kn[j + half] = rk.y;
+        if (wv == 0) k_store_pair(kT, S, pos, j, half, rk.x, rk.y);
     }
     if (own_pos) {                                                  // wave-uniform
 #pragma unroll
@@ -2209,12 +2076,7 @@ __device__ __forceinline__ void attention_multi_tag(const AttnArgs& a, const int
             pr = q4.w * kreg[g][3]; score = score + pr;
         }
         score = score / sqrt_hs;
-        if constexpr (GEMMA) {                                      // transformer.rs:518-526
-            score = score / 50.0f;
-            score = (float)tanh((double)score);
-            score = score * 50.0f;
-            score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
-        }
+        if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
         sc = t < T ? score : ninf;
     }
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[4] = wall_clock64();
@@ -2393,45 +2255,8 @@ __device__ __forceinline__ void attention_quad_tag(const AttnArgs& a, const int 
     {
         const unsigned long long* gp[3 * ND];
 #pragma unroll
-        for (int i = 0; i < ND; ++i) {
-            const int d = lane + 64 * i, dc = d < HS ? d : 0;
-            gp[3 * i] = tg.gran + h * HS + dc; gp[3 * i + 1] = tg.gran + tg.att_dim + kvh * HS + dc; gp[3 * i + 2] = tg.gran + tg.att_dim + tg.kv_dim + kvh * HS + dc;
-        }
-        auto sweep = [&](unsigned long long (&x)[3 * ND]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < 3 * ND; ++k) x[k] = __hip_atomic_load(gp[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        auto fresh = [&](const unsigned long long (&x)[3 * ND]) __attribute__((always_inline)) {
-            unsigned bad = 0u;
-#pragma unroll
-            for (int k = 0; k < 3 * ND; ++k) bad |= (unsigned)(x[k] >> 32) ^ tg.tag;
-            return __all(bad == 0u) != 0;
-        };
-        unsigned long long xa[3 * ND], xb[3 * ND];
-        sweep(xa);
-        for (unsigned spins = 0;; ++spins) {
-            sweep(xb);
-            if (fresh(xa)) {
-#pragma unroll
-                for (int k = 0; k < 3 * ND; ++k) xg[k] = xa[k];
-                break;
-            }
-            sweep(xa);
-            if (fresh(xb)) {
-#pragma unroll
-                for (int k = 0; k < 3 * ND; ++k) xg[k] = xb[k];
-                break;
-            }
-            if (spins > kTagSpinMax || (spins & 1023) == 1023) {     // bounded: report and finish with garbage instead of hanging
-                const int e = __hip_atomic_load(tg.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (e != 0 || spins > kTagSpinMax) {
-                    if (e == 0) __hip_atomic_store(tg.err, a.layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int k = 0; k < 3 * ND; ++k) xg[k] = xb[k];
-                    break;
-                }
-            }
-        }
+        for (int i = 0; i < ND; ++i) { const int d = lane + 64 * i; granules_of(tg, h, kvh, HS, d < HS ? d : 0, gp + 3 * i); }
+        poll_granules<3 * ND>(gp, tg, a.layer, xg);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (loads return in order: this wave's share of the key tile landed before the granules did)
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[2] = wall_clock64();
@@ -2448,20 +2273,11 @@ __device__ __forceinline__ void attention_quad_tag(const AttnArgs& a, const int 
     for (int i = 0; i < NH2; ++i) {
         const int j = lane + 64 * i;
         if (j < half) {
-            const float fcr = cs[i].x, fci = cs[i].y;
-            {
-                const float v0 = qs[j], v1 = qs[j + half];
-                const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-                qs[j] = a0 - a1; qs[j + half] = b0 + b1;
-            }
-            const float v0 = kn[j], v1 = kn[j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            const float r0 = a0 - a1, r1 = b0 + b1;
-            kn[j] = r0; kn[j + half] = r1;
-            if (wv == 0) {
-                kT[(((size_t)(j >> 2) * S + pos) << 2) + (j & 3)] = r0;
-                kT[(((size_t)((j + half) >> 2) * S + pos) << 2) + ((j + half) & 3)] = r1;
-            }
+            const float2 rq = rope_rotate(qs[j], qs[j + half], cs[i].x, cs[i].y);
+            qs[j] = rq.x; qs[j + half] = rq.y;
+            const float2 rk = rope_rotate(kn[j], kn[j + half], cs[i].x, cs[i].y);
+            kn[j] = rk.x; kn[j + half] = rk.y;
+            if (wv == 0) k_store_pair(kT, S, pos, j, half, rk.x, rk.y);
         }
     }
     lds_barrier();                                                  // every wave's share of the K tile has landed
@@ -2476,48 +2292,9 @@ __device__ __forceinline__ void attention_quad_tag(const AttnArgs& a, const int 
     const int t = tb + (mine ? lane : 0);
     float sc;
     {
-        const float4* kb4 = (t == pos) ? reinterpret_cast<const float4*>(kn) : kt + t;
-        const int ks = (t == pos) ? 1 : TWK;
-        float score = 0.0f;
-        constexpr int GB = 4;
-        static_assert(HS4 % (2 * GB) == 0, "head size");
-        float4 ka[GB], qa[GB], kb[GB], qb[GB];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) { ka[u] = kb4[u * ks]; qa[u] = reinterpret_cast<const float4*>(qs)[u]; }
-#pragma unroll
-        for (int g0 = 0; g0 < HS4; g0 += 2 * GB) {
-#pragma unroll
-            for (int u = 0; u < GB; ++u) { kb[u] = kb4[(g0 + GB + u) * ks]; qb[u] = reinterpret_cast<const float4*>(qs)[g0 + GB + u]; }
-            asm volatile("" : "+v"(score) : : "memory");
-#pragma unroll
-            for (int u = 0; u < GB; ++u) {
-                float pr;
-                pr = qa[u].x * ka[u].x; score = score + pr;
-                pr = qa[u].y * ka[u].y; score = score + pr;
-                pr = qa[u].z * ka[u].z; score = score + pr;
-                pr = qa[u].w * ka[u].w; score = score + pr;
-            }
-            if (g0 + 2 * GB < HS4) {
-#pragma unroll
-                for (int u = 0; u < GB; ++u) { ka[u] = kb4[(g0 + 2 * GB + u) * ks]; qa[u] = reinterpret_cast<const float4*>(qs)[g0 + 2 * GB + u]; }
-            }
-            asm volatile("" : "+v"(score) : : "memory");
-#pragma unroll
-            for (int u = 0; u < GB; ++u) {
-                float pr;
-                pr = qb[u].x * kb[u].x; score = score + pr;
-                pr = qb[u].y * kb[u].y; score = score + pr;
-                pr = qb[u].z * kb[u].z; score = score + pr;
-                pr = qb[u].w * kb[u].w; score = score + pr;
-            }
-        }
-        score = score / sqrt_hs;
-        if constexpr (GEMMA) {                                      // transformer.rs:518-526
-            score = score / 50.0f;
-            score = (float)tanh((double)score);
-            score = score * 50.0f;
-            score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
-        }
+        const bool own = t == pos;
+        float score = tile_score<HS4>(own ? reinterpret_cast<const float4*>(kn) : kt + t, own ? 1 : TWK, qs) / sqrt_hs;
+        if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
         sc = (mine && t < T) ? score : ninf;
     }
     if (a.dbg && lane == 0 && wv == 0 && blockIdx.x == 0) a.dbg[4] = wall_clock64();
@@ -2743,19 +2520,12 @@ __global__ __launch_bounds__(kBlock) void attention_split_scores_kernel(const At
     const bool mine = pos >= t0 && pos < t0 + kBlock;       // this chunk holds the new key: rotate it, store it (every head of the kv head: same values)
     for (int j = tid; j < half; j += kBlock) {              // RoPE (transformer.rs:480-491), as in attention_body
         const float2 cs = *reinterpret_cast<const float2*>(a.rope + ((size_t)pos * half + j) * 2);
-        const float fcr = cs.x, fci = cs.y;
-        {
-            const float v0 = a.q[h * HS + j], v1 = a.q[h * HS + j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            q[j] = a0 - a1; q[j + half] = b0 + b1;
-        }
+        const float2 rq = rope_rotate(a.q[h * HS + j], a.q[h * HS + j + half], cs.x, cs.y);
+        q[j] = rq.x; q[j + half] = rq.y;
         if (mine) {
-            const float v0 = a.k_raw[kvh * HS + j], v1 = a.k_raw[kvh * HS + j + half];
-            const float a0 = v0 * fcr, a1 = v1 * fci, b0 = v0 * fci, b1 = v1 * fcr;
-            const float r0 = a0 - a1, r1 = b0 + b1;
-            kn[j] = r0; kn[j + half] = r1;
-            kT[(((size_t)(j >> 2) * SQ + pos) << 2) + (j & 3)] = r0;
-            kT[(((size_t)((j + half) >> 2) * SQ + pos) << 2) + ((j + half) & 3)] = r1;
+            const float2 rk = rope_rotate(a.k_raw[kvh * HS + j], a.k_raw[kvh * HS + j + half], cs.x, cs.y);
+            kn[j] = rk.x; kn[j + half] = rk.y;
+            k_store_pair(kT, SQ, pos, j, half, rk.x, rk.y);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2769,12 +2539,7 @@ __global__ __launch_bounds__(kBlock) void attention_split_scores_kernel(const At
     const float sqrt_hs = sqrtf((float)HS);
     float score = att_score_chain<HS, KG>(kk, krs, tc * 16, q, SQ);
     score = score / sqrt_hs;
-    if constexpr (GEMMA) {                                  // transformer.rs:518-526
-        score = score / 50.0f;
-        score = (float)tanh((double)score);
-        score = score * 50.0f;
-        score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
-    }
+    if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
     if (t < T) S[(size_t)h * SQ + t] = score;
 }
 

@@ -1198,12 +1198,7 @@ __global__ __launch_bounds__(NT) void att_scores_wide_kernel(const float* __rest
     for (int i = 0; i < KW; ++i) {
         if (i < nk) {                                                        // wave-uniform
             const int t = c0 + i;
-            float score = part[i] / sqrt_hs;
-            score = score / 50.0f;                                           // transformer.rs:518-526
-            score = (float)tanh((double)score);
-            score = score * 50.0f;
-            score = score + (((unsigned)(wpos - t) <= 4096u) ? 0.0f : -2.3819763e38f);
-            S[(size_t)t * kAttQB] = score;
+            S[(size_t)t * kAttQB] = gemma_cap_window(part[i] / sqrt_hs, wpos, t);
         }
     }
 }
