@@ -115,6 +115,12 @@ int lmrs_forward(lmrs_ctx* ctx, uint32_t token, uint32_t pos, float** logits);
  * maximum) on the device; no logits leave HBM. */
 int lmrs_forward_argmax(lmrs_ctx* ctx, uint32_t token, uint32_t pos, uint32_t* next);
 
+/* Same step (Transformer::forward, src/transformer.rs:316-384) followed by the selection of the k first candidates on the device, in the order
+ * lmrs_score_tokens_topk documents (rank 0 = lmrs_forward_argmax's token): idx[j] = the rank-j index, logits_k[j] = its raw f32 logit (not a
+ * log-probability: a sampler applies its own temperature first).  2k words cross to the host instead of vocab_size floats; the context is left
+ * as lmrs_forward leaves it.  1 <= k <= 256, k <= vocab_size.  One-GPU contexts only (extension, no reference counterpart). */
+int lmrs_forward_topk(lmrs_ctx* ctx, uint32_t token, uint32_t pos, uint32_t k, uint32_t* idx /* k */, float* logits_k /* k */);
+
 /* ---- Transformer::get_embeddings  (src/transformer.rs:659-669) -------------------- */
 int lmrs_get_embeddings(const lmrs_ctx* ctx, const uint32_t* tokens, size_t n, float* out /* n*dim */);
 
@@ -163,6 +169,19 @@ int lmrs_forward_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_
  *   *sum_logprob (may be NULL): the sum of the n-1 unrounded lp, in double, in position order (0.0 for n = 1). */
 int lmrs_score_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos,
                       float* logprobs, uint32_t* argmax, double* sum_logprob);
+/* lmrs_score_tokens_topk: lmrs_score_tokens - the same pass, K/V rows, error rules and refusal of sharded contexts, and logprobs, argmax and
+ *   *sum_logprob bit for bit its results - with the k first next-token candidates of every position, 1 <= k <= 256, k <= vocab_size (else an
+ *   error before any device work).  The candidate order: all vocab_size logits take part (the unwritten tail as 0.0); the larger value first,
+ *   -0.0 == +0.0; equal values by ascending index (sample_argmax's "first index of the maximum", extended); a NaN after every number, NaNs by
+ *   ascending index - but a NaN at index 0 takes rank 0, as sampler.rs:29-41 never displaces it: rank 0 is argmax[t] in every case.
+ *   topk_idx[t*k + j] (n*k entries): the rank-j index of position t.
+ *   topk_logprob[t*k + j] (n*k entries): (double)l[idx] - m - log(sum) rounded once to float, with the m and the sum of logprobs[t]: where
+ *     tokens[t+1] is among the k its entry equals logprobs[t] bit for bit.
+ *   target_rank[t] (n-1 entries, may be NULL): the number of candidates that precede tokens[t+1] in that order (0: it is the argmax), exact for
+ *     any rank - it is counted over the whole row, not capped at k. */
+int lmrs_score_tokens_topk(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t k,
+                           float* logprobs, uint32_t* argmax, double* sum_logprob,
+                           uint32_t* topk_idx /* n*k */, float* topk_logprob /* n*k */, uint32_t* target_rank /* n-1, may be NULL */);
 
 /* ---- a prompt from token ids (extension, no reference counterpart) ---------------------
  * Equivalent to calling Transformer::forward (src/transformer.rs:316-384) for tokens[t] at position start_pos + t, t = 0 .. n-1,
@@ -212,6 +231,10 @@ int lmrs_op_tanh_cast(int device, float* y, const float* x, size_t n, double c);
  * maximum and exponentials on the device, the two sequential chains on the host): they are scaled and softmax-ed IN PLACE (as the reference does
  * to the slice) and *token = the draw for the random number rnd.  Unit parity for lmrs_forward_sample. */
 int lmrs_op_sample_mult(int device, float* logits, size_t n, float temperature, float rnd, uint32_t* token);
+/* The selection kernels of lmrs_score_tokens_topk / lmrs_forward_topk on one caller-supplied row of n logits of which the first `written` exist
+ * (the rest count as 0.0 and are never read): idx[j], val[j] = the rank-j index and its raw value, j < k.  Unit parity for the ordering rule (NaNs,
+ * signed zeros, equal values, k = n); extension, no reference counterpart.  k = 0, k > 256 and k > n are refused before the device is touched. */
+int lmrs_op_topk(int device, const float* logits, size_t n, size_t written, uint32_t k, uint32_t* idx, float* val);
 
 /* ---- measurement hooks (bench.py) ---------------------------------------------------
  * Runs, `iters` times, the dequant-GEMV launches of ONE decode step in step order (per layer: qkv, wo,

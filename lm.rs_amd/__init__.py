@@ -26,7 +26,7 @@ Q_NONE, Q8_0, Q4_0 = 0, 1, 2
 EXPORTS = [
     "lmrs_create", "lmrs_create_sharded", "lmrs_comm_unique_id", "lmrs_destroy", "lmrs_get_args", "lmrs_forward",
     "lmrs_forward_argmax", "lmrs_get_embeddings", "lmrs_fill_kv_cache", "lmrs_generate_greedy", "lmrs_forward_tokens", "lmrs_score_tokens",
-    "lmrs_prefill_tokens", "lmrs_tokens_path",
+    "lmrs_prefill_tokens", "lmrs_tokens_path", "lmrs_score_tokens_topk", "lmrs_forward_topk", "lmrs_op_topk",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -91,6 +91,9 @@ def lib():
         L.lmrs_generate_greedy.argtypes = [vp, vp, sz, u32, u32, vp, C.POINTER(C.c_double)]
         L.lmrs_forward_tokens.argtypes = [vp, vp, sz, u32, vp]
         L.lmrs_score_tokens.argtypes = [vp, vp, sz, u32, vp, vp, C.POINTER(C.c_double)]
+        L.lmrs_score_tokens_topk.argtypes = [vp, vp, sz, u32, u32, vp, vp, C.POINTER(C.c_double), vp, vp, vp]
+        L.lmrs_forward_topk.argtypes = [vp, u32, u32, u32, vp, vp]
+        L.lmrs_op_topk.argtypes = [C.c_int, vp, sz, sz, u32, vp, vp]
         L.lmrs_prefill_tokens.argtypes = [vp, vp, sz, u32, C.POINTER(u32)]
         L.lmrs_tokens_path.argtypes = [vp, sz, C.POINTER(C.c_int)]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
@@ -239,6 +242,24 @@ class Transformer:
         lp = np.empty(max(t.size - 1, 0), np.float32); am = np.empty(t.size, np.uint32); s = C.c_double()
         _chk(lib().lmrs_score_tokens(self._h, _p(t), t.size, start_pos, _p(lp), _p(am), C.byref(s)))
         return lp, am, s.value
+
+    def score_topk(self, tokens, k: int, start_pos: int = 0):
+        """score() with the k most likely next tokens of every position -> (logprobs, argmax, sum - bit for bit score()'s -, topk_idx uint32 [n, k],
+        topk_logprob float32 [n, k], target_rank uint32 [n-1]).  Order: larger logit first, equal logits by ascending index, NaNs last (a NaN at
+        index 0 first, as the argmax has it); topk_logprob shares logprobs' maximum and sum; target_rank[t] counts the candidates that precede
+        tokens[t+1], whatever k is (lmrs_score_tokens_topk)."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        lp = np.empty(max(t.size - 1, 0), np.float32); am = np.empty(t.size, np.uint32); s = C.c_double()
+        ti = np.empty((t.size, max(int(k), 0)), np.uint32); tl = np.empty(ti.shape, np.float32); rk = np.empty(lp.size, np.uint32)
+        _chk(lib().lmrs_score_tokens_topk(self._h, _p(t), t.size, start_pos, k, _p(lp), _p(am), C.byref(s), _p(ti), _p(tl), _p(rk)))
+        return lp, am, s.value, ti, tl, rk
+
+    def forward_topk(self, token: int, pos: int, k: int):
+        """forward() with the selection on the device -> (idx uint32 [k], raw logits float32 [k]) in score_topk's order; 2k words cross to the
+        host, the state afterwards is forward()'s (lmrs_forward_topk)."""
+        idx = np.empty(max(int(k), 0), np.uint32); val = np.empty(idx.size, np.float32)
+        _chk(lib().lmrs_forward_topk(self._h, token, pos, k, _p(idx), _p(val)))
+        return idx, val
 
     def prefill_tokens(self, tokens, start_pos: int = 0) -> int:
         """forward(tokens[t], start_pos + t) for every t with the logits discarded: the K/V rows of a prompt, the token ids going to the
@@ -403,6 +424,15 @@ def softmax(x, device=0):
     x = np.array(x, np.float32, copy=True)
     _chk(lib().lmrs_op_softmax(device, _p(x), x.size))
     return x
+
+
+def topk(logits, k: int, written=None, device=0):
+    """The selection kernels of score_topk / forward_topk on one row: `logits` holds the first `written` (default: all) of n = len(logits)
+    entries, the rest count as 0.0 -> (idx uint32 [k], values float32 [k]) in rank order (lmrs_op_topk)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    idx = np.empty(max(int(k), 0), np.uint32); val = np.empty(idx.size, np.float32)
+    _chk(lib().lmrs_op_topk(device, _p(lg), lg.size, lg.size if written is None else written, k, _p(idx), _p(val)))
+    return idx, val
 
 
 def classifier_argmax(x, rms_w, wq, ws, eps, device=0):

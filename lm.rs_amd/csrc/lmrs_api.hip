@@ -129,6 +129,10 @@ struct lmrs_ctx {
     // lmrs_forward_tokens / lmrs_score_tokens (allocated on first use): the [sc_rows][vocab] logits block, the reduction's chunk summaries,
     // its per-position results on the device and their pinned host copy
     float* sc_logits = nullptr; int sc_rows = 0; ScorePart* sc_part = nullptr; double* sc_lp = nullptr; uint32_t* sc_idx = nullptr; char* h_sc = nullptr;
+    // lmrs_score_tokens_topk / lmrs_forward_topk (allocated on first use, for tk_rows rows of tk_k candidates): the selection's keys and counts between
+    // its two launches, the seq_len x tk_k results (index, value) and the seq_len target ranks, and their pinned host copy
+    unsigned long long* tk_cand = nullptr; uint32_t* tk_cnt = nullptr; uint32_t* tk_idx = nullptr; float* tk_val = nullptr; uint32_t* tk_rank = nullptr;
+    char* h_tk = nullptr; int tk_rows = 0, tk_k = 0;
 
     template <class T> T* alloc(size_t count) {
         size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
@@ -1133,6 +1137,12 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     return 0;
 }
 
+static void topk_free(lmrs_ctx* c) {
+    for (void** p : {(void**)&c->tk_cand, (void**)&c->tk_cnt, (void**)&c->tk_idx, (void**)&c->tk_val, (void**)&c->tk_rank}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (c->h_tk) { (void)hipHostFree(c->h_tk); c->h_tk = nullptr; }
+    c->tk_rows = c->tk_k = 0;
+}
+
 extern "C" void lmrs_destroy(lmrs_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -1144,6 +1154,7 @@ extern "C" void lmrs_destroy(lmrs_ctx* c) {
     for (float* q : c->scales_t) if (q) (void)hipFree(q);
     for (void* q : {(void*)c->sc_logits, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_idx}) if (q) (void)hipFree(q);
     if (c->h_sc) (void)hipHostFree(c->h_sc);
+    topk_free(c);
     if (c->pfx_owned) { if (c->pfx_att) (void)hipFree(c->pfx_att); if (c->pfx_h) (void)hipFree(c->pfx_h); if (c->pfx_x) (void)hipFree(c->pfx_x); }
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->h_logits) (void)hipHostFree(c->h_logits);
@@ -1661,16 +1672,49 @@ static int score_alloc(lmrs_ctx* c, bool block) {
     return 0;
 }
 
-// out_logits != null: lmrs_forward_tokens (n x vocab floats to the host); else lmrs_score_tokens' results
+// The k of the top-k entry points, checked before anything else (`vocab` 0: not known yet)
+static int topk_check_k(uint32_t k, uint32_t vocab) {
+    if (k == 0 || k > (uint32_t)kTopkMax) return fail("top-k: k = " + std::to_string(k) + " is outside 1 .. " + std::to_string(kTopkMax));
+    if (vocab && k > vocab) return fail("top-k: k = " + std::to_string(k) + " exceeds vocab_size = " + std::to_string(vocab));
+    return 0;
+}
+
+// all or nothing, like score_alloc; made anew when a call asks for more rows per launch or a larger k than the buffers hold
+static int topk_alloc(lmrs_ctx* c, int rows, int k) {
+    if (c->tk_cand && rows <= c->tk_rows && k <= c->tk_k) return 0;
+    rows = std::max(rows, c->tk_rows); k = std::max(k, c->tk_k);
+    topk_free(c);
+    const size_t T = c->args.seq_len, S = (size_t)score_chunks((int)c->args.vocab_size);
+    bool ok = hipMalloc(reinterpret_cast<void**>(&c->tk_cand), (size_t)rows * S * k * 8) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_cnt), (size_t)rows * S * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_idx), T * k * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_val), T * k * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_rank), T * 4) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_tk), T * k * 8 + T * 4, hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        topk_free(c);
+        return fail("top-k buffers: out of memory");
+    }
+    c->tk_rows = rows; c->tk_k = k;
+    return 0;
+}
+
+// lmrs_score_tokens_topk's further results (k == 0: none are asked for)
+struct TopkOut { uint32_t k; uint32_t* idx; float* logprob; uint32_t* rank; };
+
+// out_logits != null: lmrs_forward_tokens (n x vocab floats to the host); else lmrs_score_tokens' results, and with tk.k those of the top-k form
 static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* out_logits, float* logprobs, uint32_t* argmax,
-                       double* sum_logprob) {
+                       double* sum_logprob, const TopkOut& tk = TopkOut{0, nullptr, nullptr, nullptr}) {
     // (stage_tokens in its two halves: the refusal and the first-use allocations sit between the checks and the upload, where they always did)
     if (check_tokens(c, tokens, n, start_pos, n)) return -1;
+    if (tk.k && topk_check_k(tk.k, c->args.vocab_size)) return -1;
     if (c->world > 1 || c->comm || c->p2p)
         return fail("scoring runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
     HIP_OK(hipSetDevice(c->device));
     const bool batched = score_batched_ok(c, n);
     if (score_alloc(c, batched || out_logits)) return -1;
+    if (tk.k && topk_alloc(c, batched ? c->sc_rows : 1, (int)tk.k)) return -1;
     const int V = (int)c->args.vocab_size;
     if (upload_tokens(c, tokens, n, start_pos)) return -1;
     // rows r0 .. r0 + m - 1 of the sequence, row stride ld, the first `written` columns written (the rest is the classifier's zero tail)
@@ -1678,6 +1722,11 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
         ScoreArgs s{rows, ld, written, V, m, c->tokens + start_pos + r0 + 1, (int)std::max<long long>(0, (long long)n - 1 - (long long)r0),
                     c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
         HIP_OK(launch_score_rows(s, c->stream));
+        if (!tk.k) return 0;
+        // the selection over the same rows, behind the reduction whose chunk summaries give the log-probabilities their m and sum
+        TopkArgs t{rows, ld, written, V, m, (int)tk.k, s.tgt, s.n_tgt, c->sc_part, c->tk_cand, c->tk_cnt,
+                   c->tk_idx + r0 * tk.k, c->tk_val + r0 * tk.k, c->tk_rank + r0};
+        HIP_OK(launch_topk_rows(t, c->stream));
         return 0;
     };
     auto copy_out = [&](const float* rows, int ld, int m, size_t r0) -> int {
@@ -1728,7 +1777,17 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
         if (n > 1) HIP_OK(hipMemcpyAsync(h_lp, c->sc_lp, (n - 1) * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipMemcpyAsync(h_idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
     }
+    const size_t nk = n * tk.k;                                                             // h_tk: nk indices, nk log-probabilities, n - 1 ranks
+    if (tk.k) {
+        HIP_OK(hipMemcpyAsync(c->h_tk, c->tk_idx, nk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(c->h_tk + nk * 4, c->tk_val, nk * 4, hipMemcpyDeviceToHost, c->stream));
+        if (tk.rank && n > 1) HIP_OK(hipMemcpyAsync(c->h_tk + nk * 8, c->tk_rank, (n - 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    }
     if (finish_call(c)) return -1;
+    if (tk.k) {
+        memcpy(tk.idx, c->h_tk, nk * 4); memcpy(tk.logprob, c->h_tk + nk * 4, nk * 4);
+        if (tk.rank && n > 1) memcpy(tk.rank, c->h_tk + nk * 8, (n - 1) * 4);
+    }
     if (!out_logits) {
         double sum = 0.0;
         for (size_t t = 0; t + 1 < n; ++t) { if (logprobs) logprobs[t] = (float)h_lp[t]; sum += h_lp[t]; }
@@ -1746,6 +1805,34 @@ extern "C" int lmrs_forward_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n
 extern "C" int lmrs_score_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* logprobs, uint32_t* argmax,
                                  double* sum_logprob) {
     return tokens_pass(c, tokens, n, start_pos, nullptr, logprobs, argmax, sum_logprob);
+}
+
+extern "C" int lmrs_score_tokens_topk(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t k, float* logprobs, uint32_t* argmax,
+                                      double* sum_logprob, uint32_t* topk_idx, float* topk_logprob, uint32_t* target_rank) {
+    if (topk_check_k(k, 0)) return -1;
+    if (!topk_idx || !topk_logprob) return fail("NULL argument");
+    return tokens_pass(c, tokens, n, start_pos, nullptr, logprobs, argmax, sum_logprob, TopkOut{k, topk_idx, topk_logprob, target_rank});
+}
+
+// lmrs_forward with the selection behind the step instead of the copy of the logits: 2k words cross to the host
+extern "C" int lmrs_forward_topk(lmrs_ctx* c, uint32_t token, uint32_t pos, uint32_t k, uint32_t* idx, float* logits_k) {
+    if (topk_check_k(k, 0)) return -1;
+    if (!c || !idx || !logits_k) return fail("NULL argument");
+    if (topk_check_k(k, c->args.vocab_size)) return -1;
+    if (c->world > 1 || c->comm || c->p2p)
+        return fail("top-k runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
+    if (token >= c->args.vocab_size || pos >= c->args.seq_len) return step_once(c, token, pos);          // (its message; nothing is enqueued)
+    HIP_OK(hipSetDevice(c->device));
+    if (topk_alloc(c, 1, (int)k)) return -1;
+    if (step_once(c, token, pos)) return -1;
+    const int V = (int)c->args.vocab_size;
+    TopkArgs t{c->logits, V, V, V, 1, (int)k, nullptr, 0, nullptr, c->tk_cand, c->tk_cnt, c->tk_idx, c->tk_val, nullptr};
+    HIP_OK(launch_topk_rows(t, c->stream));
+    HIP_OK(hipMemcpyAsync(c->h_tk, c->tk_idx, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(c->h_tk + (size_t)k * 4, c->tk_val, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (finish_call(c)) return -1;
+    memcpy(idx, c->h_tk, (size_t)k * 4); memcpy(logits_k, c->h_tk + (size_t)k * 4, (size_t)k * 4);
+    return 0;
 }
 
 // ------------------------------------------------------------------ a prompt from token ids (no reference counterpart: the loop of chat.rs:188-193
@@ -2124,6 +2211,25 @@ extern "C" int lmrs_op_sample_mult(int device, float* logits, size_t n, float te
     for (size_t i = 0; i < n; ++i) logits[i] = logits[i] / sum;
     float cdf = 0.0f; *token = (uint32_t)(n - 1);
     for (size_t i = 0; i < n; ++i) { cdf = cdf + logits[i]; if (rnd < cdf) { *token = (uint32_t)i; break; } }
+    return 0;
+}
+
+// launch_topk_rows on one caller-supplied row: the ordering rule on the cases whole models do not reach (NaNs, signed zeros, rows of equal values,
+// k = n).  Columns [written, n) are never uploaded - the device row holds NaN patterns there - and count as 0.0.
+extern "C" int lmrs_op_topk(int device, const float* logits, size_t n, size_t written, uint32_t k, uint32_t* idx, float* val) {
+    if (!logits || !idx || !val) return fail("NULL argument");
+    if (n == 0 || n > (size_t)0x7FFFFFFF || written > n) return fail("lmrs_op_topk: need 1 <= n < 2^31 and written <= n");
+    if (topk_check_k(k, (uint32_t)n)) return -1;
+    if (op_begin(device)) return -1;
+    Scratch S; const size_t C = (size_t)score_chunks((int)n);
+    void *dl = S.get(n * 4), *dc = S.get(C * k * 8), *di = S.get((size_t)k * 4), *dv = S.get((size_t)k * 4);
+    if (!dl || !dc || !di || !dv) return fail("hipMalloc failed");
+    HIP_OK(hipMemset(dl, 0xFF, n * 4));
+    HIP_OK(hipMemcpy(dl, logits, written * 4, hipMemcpyHostToDevice));
+    TopkArgs t{static_cast<float*>(dl), (int)n, (int)written, (int)n, 1, (int)k, nullptr, 0, nullptr, static_cast<unsigned long long*>(dc), nullptr,
+               static_cast<uint32_t*>(di), static_cast<float*>(dv), nullptr};
+    HIP_OK(launch_topk_rows(t, nullptr));
+    HIP_OK(hipMemcpy(idx, di, (size_t)k * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(val, dv, (size_t)k * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // lmrs_score.h — launch interface of the scoring reduction (lmrs_score.hip): per-row argmax and log-softmax of a target over
-// blocks of logits, for lmrs_score_tokens (include/lmrs_hip.h).
+// blocks of logits, for lmrs_score_tokens (include/lmrs_hip.h), and the k first candidates of every row, for lmrs_score_tokens_topk / lmrs_forward_topk.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +23,24 @@ struct ScoreArgs {
     ScorePart* part; double* out_lp; uint32_t* out_idx;
 };
 hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t s);
+
+// The k first candidates of every row of the same kind of block, in this order: all `vocab` entries take part (zero tail included); the larger
+// value first, -0.0 == +0.0; equal values by ascending index; a NaN after every number, NaNs by ascending index - but a NaN at index 0 takes
+// rank 0, so that rank 0 is out_idx of launch_score_rows in every case.  1 <= k <= kTopkMax, k <= vocab.
+//   out_idx[r * k + j] = the rank-j index; out_val[r * k + j] = its f32 logit - or, with `part` (the chunk summaries launch_score_rows left for
+//   the SAME rows), (double)l - m - log(sum) rounded once to float, m and sum exactly those of that row's out_lp;
+//   out_rank[r] (r < n_tgt, tgt as in ScoreArgs; optional) = the number of candidates that precede entry tgt[r]: exact for any rank.
+// cand: rows * score_chunks(vocab) * k keys, cnt: rows * score_chunks(vocab) counts (scratch between the two launches).  The chunking is that
+// of the scores and no result depends on the order in which lanes or workgroups arrive: a row gives the same bits in any launch.
+constexpr int kTopkMax = 256;
+struct TopkArgs {
+    const float* logits; int ld, written, vocab, rows, k;
+    const uint32_t* tgt; int n_tgt;
+    const ScorePart* part;
+    unsigned long long* cand; uint32_t* cnt;
+    uint32_t* out_idx; float* out_val; uint32_t* out_rank;
+};
+hipError_t launch_topk_rows(const TopkArgs& a, hipStream_t s);
 
 // logits[r * ld + i] = 30 * (float)tanh((double)(logits[r * ld + i] / 30)) for r < rows, i < cols (cols <= ld): Gemma-2's soft-cap of the first
 // `dim` logits (transformer.rs:375-381), the decode classifier epilogue's arithmetic over a block of rows

@@ -8,6 +8,9 @@
 // 512 tokens over 32 k workgroups.  The rescaled sum differs from a direct sum of exp(l - max) by a few double ulps, far below the f32
 // rounding of the result.  The summation order depends on the vocabulary size alone: a row gives the same bits in any launch.
 //
+// topk_chunk_kernel / topk_merge_kernel: the k first candidates of every row over the same chunking (lmrs_score_tokens_topk, lmrs_forward_topk):
+// described where they stand.
+//
 // softcap_rows_kernel: Gemma-2's soft-cap of the first `dim` logits of every row of the block, between the batched classifier GEMM and the
 // reduction (the decode classifier applies it in its epilogue).
 #include <hip/hip_runtime.h>
@@ -38,7 +41,25 @@ __device__ __forceinline__ double wave_sum(double s) {
     return s;
 }
 
-// grid (chunks of the row, rows).  VEC: rows start 16-byte aligned (ld % 4 == 0): float4 loads wherever four written values are whole
+// A lane's eight logits of the chunk at c0: element e is column chunk_index(c0, tid, e); columns from `written` on read as 0.0 (past `vocab`: the
+// caller masks them).  VEC: rows start 16-byte aligned (ld % 4 == 0): float4 loads wherever four written values are whole
+__device__ __forceinline__ int chunk_index(int c0, int tid, int e) { return c0 + 4 * (tid + (e >> 2) * kLanes) + (e & 3); }
+template <bool VEC>
+__device__ __forceinline__ void load_chunk(const float* row, int c0, int written, int tid, float (&v)[kPerLane]) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int i0 = c0 + 4 * (tid + k * kLanes);
+        if (VEC && i0 + 3 < written) {
+            const float4 f = *reinterpret_cast<const float4*>(row + i0);
+            v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[4 * k + j] = i0 + j < written ? row[i0 + j] : 0.0f;
+        }
+    }
+}
+
+// grid (chunks of the row, rows)
 template <bool VEC>
 __global__ __launch_bounds__(kLanes) void score_chunk_kernel(const ScoreArgs a) {
     __shared__ float s_max[kLanes / 64];
@@ -48,22 +69,12 @@ __global__ __launch_bounds__(kLanes) void score_chunk_kernel(const ScoreArgs a) 
     const float* row = a.logits + (size_t)blockIdx.y * a.ld;
     const int c0 = blockIdx.x * kScoreChunk;
     float v[kPerLane];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int i0 = c0 + 4 * (tid + k * kLanes);
-        if (VEC && i0 + 3 < a.written) {
-            const float4 f = *reinterpret_cast<const float4*>(row + i0);
-            v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[4 * k + j] = i0 + j < a.written ? row[i0 + j] : 0.0f;   // (past `vocab`: masked below)
-        }
-    }
+    load_chunk<VEC>(row, c0, a.written, tid, v);
     // the lane's first maximum (its indices ascend), NaNs skipped; then the workgroup's
     float m = -INFINITY; int mi = INT_MAX;
 #pragma unroll
     for (int e = 0; e < kPerLane; ++e) {
-        const int i = c0 + 4 * (tid + (e >> 2) * kLanes) + (e & 3);
+        const int i = chunk_index(c0, tid, e);
         if (i < a.vocab && v[e] == v[e] && (v[e] > m || mi == INT_MAX)) { m = v[e]; mi = i; }
     }
     wave_max(m, mi);
@@ -78,7 +89,7 @@ __global__ __launch_bounds__(kLanes) void score_chunk_kernel(const ScoreArgs a) 
         const double md = (double)m;
 #pragma unroll
         for (int e = 0; e < kPerLane; ++e) {
-            const int i = c0 + 4 * (tid + (e >> 2) * kLanes) + (e & 3);
+            const int i = chunk_index(c0, tid, e);
             if (i < a.vocab) s += exp((double)v[e] - md);
         }
     }
@@ -91,22 +102,29 @@ __global__ __launch_bounds__(kLanes) void score_chunk_kernel(const ScoreArgs a) 
     }
 }
 
-// one wave per row (four rows per workgroup)
-__global__ __launch_bounds__(kLanes) void score_merge_kernel(const ScoreArgs a) {
-    const int r = blockIdx.x * (kLanes / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= a.rows) return;                                                // (wave-uniform)
-    const int S = score_chunks(a.vocab);
-    const ScorePart* pp = a.part + (size_t)r * S;
-    float m = -INFINITY; int mi = INT_MAX;
+// One wave merges a row's S chunk summaries: the f32 maximum m, its first index mi (INT_MAX: no number in the row) and
+// s = sum_c s_c * exp(max_c - m) in double; every lane ends with the same three
+__device__ __forceinline__ void row_max_sum(const ScorePart* pp, int S, int lane, float& m, int& mi, double& s) {
+    m = -INFINITY; mi = INT_MAX;
     for (int c = lane; c < S; c += 64) take_max(m, mi, pp[c].max, pp[c].idx);
     wave_max(m, mi);
     const double md = (double)m;
-    double s = 0.0;
+    s = 0.0;
     for (int c = lane; c < S; c += 64) {
         const ScorePart q = pp[c];
         if (q.max != -INFINITY) s += q.sum * exp((double)q.max - md);
     }
     s = wave_sum(s);
+}
+
+// one wave per row (four rows per workgroup)
+__global__ __launch_bounds__(kLanes) void score_merge_kernel(const ScoreArgs a) {
+    const int r = blockIdx.x * (kLanes / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= a.rows) return;                                                // (wave-uniform)
+    const int S = score_chunks(a.vocab);
+    float m; int mi; double s;
+    row_max_sum(a.part + (size_t)r * S, S, lane, m, mi, s);
+    const double md = (double)m;
     if (lane == 0) {
         const float* row = a.logits + (size_t)r * a.ld;
         const float l0 = a.written > 0 ? row[0] : 0.0f;
@@ -116,6 +134,150 @@ __global__ __launch_bounds__(kLanes) void score_merge_kernel(const ScoreArgs a) 
             const float ly = y < (uint32_t)a.written ? row[y] : 0.0f;
             a.out_lp[r] = (double)ly - md - log(s);
         }
+    }
+}
+
+// ------------------------------------------------------------------ top-k of every row (launch_topk_rows)
+// Every entry becomes one 64-bit key whose descending order IS the candidate order of lmrs_score.h: the value's bits made monotone in the high word
+// (-0.0 folded onto +0.0, a NaN 0 - below -inf -, a NaN at index 0 the largest word of all), ~index in the low word.  Keys are unique and never 0.
+// Two launches over the scores' chunking.  topk_chunk_kernel: a workgroup finds the min(k, entries)-th largest key of its 2048 by a radix select,
+// eight bits a round from the top (a 256-bin count in LDS, one bin per lane; it stops at the first round whose bin is wanted whole: two or three
+// rounds on ordinary logits), and writes the keys from there up to its k slots (0 fills a short chunk): one pass over HBM.  topk_merge_kernel: a
+// workgroup per row runs the same select for the k-th key of the row's S * k candidates and places each survivor at the number of survivors above
+// it.  The slot a key lands in between the two depends on the order of arrival; the select and the placement look at key values alone, so
+// nothing that is written out does.  The counts are integer sums.
+__device__ __forceinline__ unsigned long long topk_key(float f, int i) {
+    unsigned b = __float_as_uint(f), hi;
+    if (f != f) hi = i == 0 ? 0xFFFFFFFFu : 0u;
+    else {
+        if (b == 0x80000000u) b = 0u;
+        hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    }
+    return ((unsigned long long)hi << 32) | (unsigned)~(unsigned)i;
+}
+
+struct SelectLds { unsigned hist[kLanes]; unsigned wtot[kLanes / 64]; unsigned pick[3]; };
+
+// The workgroup's r-th largest of keys[0 .. n) (all lanes call it; 1 <= r <= the number of non-zero keys, which are unique), or that key with its
+// low bits cleared when every key sharing the bits above is wanted: `key >= the result` holds for exactly r keys.
+__device__ __forceinline__ unsigned long long block_kth_key(const unsigned long long* keys, int n, unsigned r, SelectLds& L) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long pfx = 0, known = 0;                                  // the bits decided so far, and their mask
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        L.hist[tid] = 0;
+        __syncthreads();
+        for (int j = tid; j < n; j += kLanes) {
+            const unsigned long long key = keys[j];
+            if ((key & known) == pfx) atomicAdd(&L.hist[(unsigned)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        // lane = bin: the keys in higher bins, by a suffix sum over the wave and the waves' totals
+        const unsigned h = L.hist[tid];
+        unsigned x = h;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_down(x, off); if (lane + off < 64) x += y; }
+        if (lane == 0) L.wtot[wave] = x;
+        __syncthreads();
+        unsigned above = x - h;
+        for (int w = wave + 1; w < kLanes / 64; ++w) above += L.wtot[w];
+        if (above < r && r <= above + h) { L.pick[0] = (unsigned)tid; L.pick[1] = r - above; L.pick[2] = h; }   // (one bin)
+        __syncthreads();
+        pfx |= (unsigned long long)L.pick[0] << shift; known |= 0xFFull << shift;
+        r = L.pick[1];
+        if (r == L.pick[2]) break;                                          // the whole bin is wanted (at shift 0: the one key)
+    }
+    return pfx;
+}
+
+__device__ __forceinline__ unsigned wave_sum_u32(unsigned s) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+
+static_assert(kTopkMax <= kLanes, "a lane per candidate slot");
+
+// grid (chunks of the row, rows), as score_chunk_kernel
+template <bool VEC>
+__global__ __launch_bounds__(kLanes) void topk_chunk_kernel(const TopkArgs a) {
+    __shared__ unsigned long long s_keys[kScoreChunk];
+    __shared__ SelectLds s_sel;
+    __shared__ unsigned s_n[2];                                             // slots handed out; keys ahead of the target
+    const int tid = threadIdx.x;
+    const float* row = a.logits + (size_t)blockIdx.y * a.ld;
+    const int c0 = blockIdx.x * kScoreChunk;
+    float v[kPerLane];
+    load_chunk<VEC>(row, c0, a.written, tid, v);
+    if (tid < 2) s_n[tid] = 0;
+    unsigned long long key[kPerLane];
+#pragma unroll
+    for (int e = 0; e < kPerLane; ++e) {
+        const int i = chunk_index(c0, tid, e);
+        key[e] = i < a.vocab ? topk_key(v[e], i) : 0ull;
+        s_keys[e * kLanes + tid] = key[e];
+    }
+    const bool ranked = a.out_rank && (int)blockIdx.y < a.n_tgt;            // (uniform)
+    unsigned ahead = 0;
+    if (ranked) {
+        const uint32_t y = a.tgt[blockIdx.y];
+        const unsigned long long ky = topk_key(y < (uint32_t)a.written ? row[y] : 0.0f, (int)y);
+#pragma unroll
+        for (int e = 0; e < kPerLane; ++e) ahead += key[e] > ky;
+        ahead = wave_sum_u32(ahead);
+    }
+    __syncthreads();
+    if (ranked && (tid & 63) == 0) atomicAdd(&s_n[1], ahead);
+    const unsigned r = (unsigned)min(a.k, min(kScoreChunk, a.vocab - c0));
+    const unsigned long long kth = block_kth_key(s_keys, kScoreChunk, r, s_sel);
+    const size_t part = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    unsigned long long* out = a.cand + part * a.k;
+#pragma unroll
+    for (int e = 0; e < kPerLane; ++e)
+        if (key[e] >= kth) {
+            const unsigned slot = atomicAdd(&s_n[0], 1u);
+            if (slot < r) out[slot] = key[e];
+        }
+    if (tid >= (int)r && tid < a.k) out[tid] = 0ull;
+    if (ranked && tid == 0) a.cnt[part] = s_n[1];                           // (complete: the select's barriers lie behind the four adds)
+}
+
+// one workgroup per row
+__global__ __launch_bounds__(kLanes) void topk_merge_kernel(const TopkArgs a) {
+    __shared__ unsigned long long s_top[kTopkMax];
+    __shared__ SelectLds s_sel;
+    __shared__ unsigned s_n;
+    const int tid = threadIdx.x, lane = tid & 63, r = blockIdx.x, S = score_chunks(a.vocab), n = S * a.k;
+    const unsigned long long* cand = a.cand + (size_t)r * n;
+    if (tid == 0) s_n = 0;
+    const unsigned long long kth = block_kth_key(cand, n, (unsigned)a.k, s_sel);
+    for (int j = tid; j < n; j += kLanes) {
+        const unsigned long long key = cand[j];
+        if (key >= kth) {
+            const unsigned slot = atomicAdd(&s_n, 1u);
+            if (slot < (unsigned)a.k) s_top[slot] = key;
+        }
+    }
+    __syncthreads();
+    double md = 0.0, ls = 0.0;
+    if (a.part) {                                                           // the row's m and log(sum) as score_merge_kernel forms them
+        float m; int mi; double s;
+        row_max_sum(a.part + (size_t)r * S, S, lane, m, mi, s);
+        md = (double)m; ls = log(s);
+    }
+    if (tid < a.k) {
+        const unsigned long long key = s_top[tid];
+        int rank = 0;
+        for (int i = 0; i < a.k; ++i) rank += s_top[i] > key;
+        const uint32_t idx = ~(uint32_t)key;
+        const float l = idx < (uint32_t)a.written ? a.logits[(size_t)r * a.ld + idx] : 0.0f;
+        a.out_idx[(size_t)r * a.k + rank] = idx;
+        a.out_val[(size_t)r * a.k + rank] = a.part ? (float)((double)l - md - ls) : l;
+    }
+    if (a.out_rank && r < a.n_tgt && tid < 64) {
+        unsigned ahead = 0;
+        for (int c = lane; c < S; c += 64) ahead += a.cnt[(size_t)r * S + c];
+        ahead = wave_sum_u32(ahead);
+        if (lane == 0) a.out_rank[r] = ahead;
     }
 }
 
@@ -151,6 +313,19 @@ hipError_t launch_score_rows(const ScoreArgs& a, hipStream_t s) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(score_merge_kernel, dim3((a.rows + kLanes / 64 - 1) / (kLanes / 64)), dim3(kLanes), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_rows(const TopkArgs& a, hipStream_t s) {
+    if (a.rows <= 0 || a.rows > 65535 || a.vocab <= 0 || a.written < 0 || a.written > a.vocab || a.ld < a.written || a.k < 1 || a.k > kTopkMax ||
+        a.k > a.vocab || !a.logits || !a.cand || !a.out_idx || !a.out_val || (a.out_rank && a.n_tgt > 0 && (!a.tgt || !a.cnt)))
+        return hipErrorInvalidValue;
+    const dim3 grid(score_chunks(a.vocab), a.rows);
+    if (a.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.logits) & 15) == 0) hipLaunchKernelGGL(topk_chunk_kernel<true>, grid, dim3(kLanes), 0, s, a);
+    else hipLaunchKernelGGL(topk_chunk_kernel<false>, grid, dim3(kLanes), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(a.rows), dim3(kLanes), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,8 +1,10 @@
 // perplexity.cpp — perplexity of a text under a model (an extension; no reference counterpart): the text is tokenized with BOS
 // (Tokenizer::encode, src/tokenizer.rs:66-151), cut into windows of --ctx tokens that start --stride tokens apart, and every window is
 // scored from position 0 with Transformer::score (lmrs_score_tokens).  Each token after the first is counted once, in the first window
-// that predicts it; nll is the sum of -log p over those tokens, in double, in token order.  Prints one JSON line {"tokens", "nll", "ppl"}.
-//   usage: perplexity --model m.lmrs --tokenizer tokenizer.bin --text file.txt [--ctx N (default min(seq_len, 512))] [--stride N (default ctx)]
+// that predicts it; nll is the sum of -log p over those tokens, in double, in token order.  Prints one JSON line {"tokens", "nll", "ppl"};
+// with --topk K (Transformer::score_topk, lmrs_score_tokens_topk) also "top1" and "topk", the share of counted tokens that were the model's first
+// / among its K first candidates, and "mean_rank", the mean number of candidates ahead of the token.
+//   usage: perplexity --model m.lmrs --tokenizer tokenizer.bin --text file.txt [--ctx N (default min(seq_len, 512))] [--stride N (default ctx)] [--topk K]
 //   g++ -O2 -std=c++17 perplexity.cpp -I../../include -L.. -llmrs_hip -Wl,-rpath,'$ORIGIN/..' -o perplexity
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -22,7 +24,7 @@
 
 int main(int argc, char** argv) {
     std::string model_path, tok_path, text_path;
-    long ctx_arg = 0, stride_arg = 0;
+    long ctx_arg = 0, stride_arg = 0, topk = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--model") model_path = argv[i + 1];
@@ -30,10 +32,11 @@ int main(int argc, char** argv) {
         else if (k == "--text") text_path = argv[i + 1];
         else if (k == "--ctx") ctx_arg = std::atol(argv[i + 1]);
         else if (k == "--stride") stride_arg = std::atol(argv[i + 1]);
+        else if (k == "--topk") { topk = std::atol(argv[i + 1]); if (topk < 1) { std::fprintf(stderr, "--topk needs K >= 1\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (model_path.empty() || tok_path.empty() || text_path.empty()) {
-        std::fprintf(stderr, "usage: %s --model m.lmrs --tokenizer tokenizer.bin --text file.txt [--ctx N] [--stride N]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s --model m.lmrs --tokenizer tokenizer.bin --text file.txt [--ctx N] [--stride N] [--topk K]\n", argv[0]);
         return 2;
     }
     std::ifstream tf(text_path, std::ios::binary);
@@ -55,19 +58,27 @@ int main(int argc, char** argv) {
         const std::size_t stride = stride_arg > 0 ? static_cast<std::size_t>(stride_arg) : ctx;
         if (ctx < 2 || ctx > model.args.seq_len || stride > ctx) { std::fprintf(stderr, "need 2 <= ctx <= seq_len and 1 <= stride <= ctx\n"); return 2; }
         if (N < 2) { std::fprintf(stderr, "the text is %zu token(s): nothing to predict\n", N); return 1; }
-        double nll = 0.0;
-        std::size_t counted = 0, done = 1;                                 // done: first token not yet predicted
+        double nll = 0.0, rank_sum = 0.0;
+        std::size_t counted = 0, done = 1, top1 = 0, topk_hits = 0;        // done: first token not yet predicted
         for (std::size_t b = 0;; b += stride) {
             const std::size_t e = std::min(b + ctx, N);
             if (done < e) {
                 const std::vector<std::uint32_t> win(ids.begin() + b, ids.begin() + e);
-                const auto s = model.score(win, 0);
-                for (std::size_t j = std::max(b + 1, done); j < e; ++j) { nll -= static_cast<double>(s.logprobs[j - b - 1]); ++counted; }
+                const auto s = topk ? model.score_topk(win, static_cast<std::uint32_t>(topk), 0) : lmrs_host::Transformer::ScoreTopk{model.score(win, 0)};
+                for (std::size_t j = std::max(b + 1, done); j < e; ++j) {
+                    nll -= static_cast<double>(s.logprobs[j - b - 1]); ++counted;
+                    if (!topk) continue;
+                    const std::uint32_t r = s.target_rank[j - b - 1];
+                    top1 += r == 0; topk_hits += r < static_cast<std::uint32_t>(topk); rank_sum += r;
+                }
                 done = e;
             }
             if (e == N) break;
         }
-        std::printf("{\"tokens\": %zu, \"nll\": %.17g, \"ppl\": %.17g}\n", counted, nll, std::exp(nll / static_cast<double>(counted)));
+        std::printf("{\"tokens\": %zu, \"nll\": %.17g, \"ppl\": %.17g", counted, nll, std::exp(nll / static_cast<double>(counted)));
+        if (topk) std::printf(", \"k\": %ld, \"top1\": %.6f, \"topk\": %.6f, \"mean_rank\": %.3f", topk, static_cast<double>(top1) / counted,
+                              static_cast<double>(topk_hits) / counted, rank_sum / counted);
+        std::printf("}\n");
     } catch (const lmrs_host::Panic& e) { std::fprintf(stderr, "panic: %s\n", e.what()); return 101; }
     return 0;
 }

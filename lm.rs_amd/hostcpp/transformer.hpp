@@ -83,6 +83,25 @@ public:
         check(lmrs_score_tokens(ctx_, tokens.data(), tokens.size(), start_pos, s.logprobs.data(), s.argmax.data(), &s.sum_logprob));
         return s;
     }
+    // score_topk: score with the k first next-token candidates of every position (1 <= k <= 256, k <= vocab_size), selected on the device: the
+    // larger logit first, equal logits by ascending index, NaNs last (a NaN at index 0 first: rank 0 is argmax[t]).  topk_idx / topk_logprob:
+    // n x k, the log-probabilities with logprobs' maximum and sum; target_rank[t]: the candidates that precede tokens[t+1], whatever k is.
+    struct ScoreTopk : Scores { std::uint32_t k = 0; std::vector<std::uint32_t> topk_idx; std::vector<float> topk_logprob; std::vector<std::uint32_t> target_rank; };
+    ScoreTopk score_topk(const std::vector<std::uint32_t>& tokens, std::uint32_t k, std::uint32_t start_pos = 0) {
+        ScoreTopk s;
+        const std::size_t n = tokens.size();
+        s.k = k; s.logprobs.resize(n ? n - 1 : 0); s.argmax.resize(n); s.target_rank.resize(n ? n - 1 : 0);
+        s.topk_idx.resize(n * k); s.topk_logprob.resize(n * k);
+        check(lmrs_score_tokens_topk(ctx_, tokens.data(), n, start_pos, k, s.logprobs.data(), s.argmax.data(), &s.sum_logprob, s.topk_idx.data(),
+                                     s.topk_logprob.data(), s.target_rank.data()));
+        return s;
+    }
+    // forward + the selection of the k first candidates on the device -> (indices, their raw logits) in score_topk's order; 2k words cross to the host.
+    std::pair<std::vector<std::uint32_t>, std::vector<float>> forward_topk(std::uint32_t token, std::uint32_t pos, std::uint32_t k) {
+        std::vector<std::uint32_t> idx(k); std::vector<float> val(k);
+        check(lmrs_forward_topk(ctx_, token, pos, k, idx.data(), val.data()));
+        return {std::move(idx), std::move(val)};
+    }
 
 private:
     Transformer() = default;

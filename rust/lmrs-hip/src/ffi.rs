@@ -38,6 +38,10 @@ extern "C" {
     pub fn lmrs_forward_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, logits: *mut f32) -> c_int;
     pub fn lmrs_score_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, logprobs: *mut f32, argmax: *mut u32,
                              sum_logprob: *mut f64) -> c_int;
+    pub fn lmrs_score_tokens_topk(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, k: u32, logprobs: *mut f32, argmax: *mut u32,
+                                  sum_logprob: *mut f64, topk_idx: *mut u32, topk_logprob: *mut f32, target_rank: *mut u32) -> c_int;
+    pub fn lmrs_forward_topk(ctx: *mut LmrsCtx, token: u32, pos: u32, k: u32, idx: *mut u32, logits_k: *mut f32) -> c_int;
+    pub fn lmrs_op_topk(device: c_int, logits: *const f32, n: usize, written: usize, k: u32, idx: *mut u32, val: *mut f32) -> c_int;
     pub fn lmrs_prefill_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, new_pos: *mut u32) -> c_int;
     pub fn lmrs_tokens_path(ctx: *const LmrsCtx, n: usize, batched: *mut c_int) -> c_int;
     pub fn lmrs_last_error() -> *const c_char;

@@ -46,6 +46,16 @@ pub struct TransformerArgs {
     pub(crate) group_size: u32,
 }
 
+pub struct ScoreTopk {
+    pub logprobs: Vec<f32>,
+    pub argmax: Vec<u32>,
+    pub sum_logprob: f64,
+    /// n x k, row t = the candidates of position t in rank order
+    pub topk_idx: Vec<u32>,
+    pub topk_logprob: Vec<f32>,
+    pub target_rank: Vec<u32>,
+}
+
 pub struct Transformer<'a> {
     pub args: TransformerArgs,
     ctx: *mut LmrsCtx,
@@ -137,6 +147,36 @@ impl<'a> Transformer<'a> {
             ffi::lmrs_score_tokens(self.ctx, tokens.as_ptr(), tokens.len(), start_pos, logprobs.as_mut_ptr(), argmax.as_mut_ptr(), &mut sum)
         });
         (logprobs, argmax, sum)
+    }
+
+    /// Extension: `score` with the `k` first next-token candidates of every position (1 <= k <= 256, k <= vocab_size), selected on the
+    /// device.  Order: the larger logit first, equal logits by ascending index, NaNs last - a NaN at index 0 first, as `sample_argmax`
+    /// has it, so rank 0 is `argmax[t]`.  `topk_logprob` shares the maximum and the sum of `logprobs`; `target_rank[t]` counts the
+    /// candidates that precede `tokens[t+1]`, whatever `k` is.
+    pub fn score_topk(&mut self, tokens: &[u32], k: u32, start_pos: u32) -> ScoreTopk {
+        let n = tokens.len();
+        let mut s = ScoreTopk {
+            logprobs: vec![0.0f32; n.saturating_sub(1)],
+            argmax: vec![0u32; n],
+            sum_logprob: 0.0,
+            topk_idx: vec![0u32; n * k as usize],
+            topk_logprob: vec![0.0f32; n * k as usize],
+            target_rank: vec![0u32; n.saturating_sub(1)],
+        };
+        check(unsafe {
+            ffi::lmrs_score_tokens_topk(self.ctx, tokens.as_ptr(), n, start_pos, k, s.logprobs.as_mut_ptr(), s.argmax.as_mut_ptr(),
+                                        &mut s.sum_logprob, s.topk_idx.as_mut_ptr(), s.topk_logprob.as_mut_ptr(), s.target_rank.as_mut_ptr())
+        });
+        s
+    }
+
+    /// Extension: `forward` followed by the selection of the `k` first candidates on the device, in `score_topk`'s order: (indices, their
+    /// raw logits).  2k words cross to the host instead of `vocab_size` floats; the state afterwards is `forward`'s.
+    pub fn forward_topk(&mut self, token: u32, pos: u32, k: u32) -> (Vec<u32>, Vec<f32>) {
+        let mut idx = vec![0u32; k as usize];
+        let mut val = vec![0.0f32; k as usize];
+        check(unsafe { ffi::lmrs_forward_topk(self.ctx, token, pos, k, idx.as_mut_ptr(), val.as_mut_ptr()) });
+        (idx, val)
     }
 
     /// Extension: `forward(tokens[t], start_pos + t)` for every t with the logits discarded - the K/V rows of a prompt from token ids,

@@ -2,7 +2,10 @@
 the batched path (forward_layer and the classifier over the token batch on the int8 matrix cores) against the token-by-token path (a second
 context created with LMRS_NO_BATCHED_PREFILL=1: one decode step per token), and lmrs_forward_tokens at 512 tokens (all logits to the host).
 Best of three calls after one warm-up, host wall clock around the whole call.
-usage: python tools/score_rate.py [model] [q8_0|q4_0]"""
+--topk K[,K...]: instead, what the k first candidates of every position cost (lmrs_score_tokens_topk) - 512 tokens on the batched path, plain
+score and score_topk(K) by turns, three repetitions of the best-of-three each, and a decode step with the logits copied (forward) against one
+with the selection on the device (forward_topk).
+usage: python tools/score_rate.py [model] [q8_0|q4_0] [--topk K[,K...]]"""
 import os
 import sys
 import time
@@ -22,10 +25,43 @@ def best_ms(fn, reps=3):
     return min(out) * 1e3
 
 
-model = sys.argv[1] if len(sys.argv) > 1 else "llama-3.2-1b"
-qt = S.Q4_0 if len(sys.argv) > 2 and sys.argv[2] == "q4_0" else S.Q8_0
+argv = sys.argv[1:]
+topk = []
+if "--topk" in argv:
+    i = argv.index("--topk")
+    topk = [int(k) for k in argv[i + 1].split(",")]
+    del argv[i:i + 2]
+model = argv[0] if len(argv) > 0 else "llama-3.2-1b"
+qt = S.Q4_0 if len(argv) > 1 and argv[1] == "q4_0" else S.Q8_0
 img = S.build_image(model, qt, 1234)
 batched = lmrs_amd.Transformer(img)
+if topk:
+    toks = S.prompt_tokens(model, 512, 7)
+    print(f"{model} {'Q4_0' if qt == S.Q4_0 else 'Q8_0'}: 512 tokens, wall clock (ms), best of 3 calls, three repetitions")
+    plain = batched.score(toks, 0)
+    for rep in range(3):
+        line = f"  rep {rep}: score {best_ms(lambda: batched.score(toks, 0)):7.3f}"
+        for k in topk:
+            line += f"   score_topk({k}) {best_ms(lambda: batched.score_topk(toks, k, 0)):7.3f}"
+        print(line)
+    for k in topk:
+        r = batched.score_topk(toks, k, 0)
+        same = np.array_equal(r[0].view(np.uint32), plain[0].view(np.uint32)) and np.array_equal(r[1], plain[1]) and r[2] == plain[2]
+        print(f"  k={k}: logprobs / argmax / sum are score()'s bits: {same}   rank 0 is the argmax: {np.array_equal(r[3][:, 0], r[1])}"
+              f"   top-1 {np.mean(r[5] == 0):.4f} top-{k} {np.mean(r[5] < k):.4f} mean target rank {np.mean(r[5]):.1f}")
+    steps = 200
+    def decode(step):
+        t0 = time.perf_counter()
+        for i in range(steps):
+            step(int(toks[i]), i)
+        return (time.perf_counter() - t0) / steps * 1e6
+    decode(lambda t, p: batched.forward(t, p))
+    line = f"  decode, us/token over {steps} steps: forward {decode(lambda t, p: batched.forward(t, p)):7.1f}   forward_argmax {decode(batched.forward_argmax):7.1f}"
+    for k in topk:
+        decode(lambda t, p: batched.forward_topk(t, p, k))
+        line += f"   forward_topk({k}) {decode(lambda t, p: batched.forward_topk(t, p, k)):7.1f}"
+    print(line)
+    sys.exit(0)
 os.environ["LMRS_NO_BATCHED_PREFILL"] = "1"              # (read at create)
 token = lmrs_amd.Transformer(img)
 del os.environ["LMRS_NO_BATCHED_PREFILL"]
