@@ -199,6 +199,35 @@ int lmrs_prefill_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_
  * n > 1, a batched-eligible file, classifier rows a multiple of 16.) */
 int lmrs_tokens_path(const lmrs_ctx* ctx, size_t n, int* batched);
 
+/* ---- short runs in one weight pass: verifying drafted tokens (extensions, no reference counterpart) -------------------
+ * lmrs_verify_tokens replaces n calls of Transformer::forward (src/transformer.rs:316-384) + Sampler::sample_argmax (sampler.rs:29-41):
+ * tokens[0] at start_pos is the last confirmed token, tokens[1..n) are drafts.
+ *   argmax[t] (n entries) = lmrs_forward_argmax(tokens[t], start_pos + t) after the calls for 0..t-1.
+ *   *n_accept = the number of leading drafts with tokens[t+1] == argmax[t]  (0 .. n-1).
+ * K/V rows start_pos .. start_pos+n-1 are left as those calls leave them; rows past start_pos + *n_accept belong to rejected drafts
+ * and are rewritten by whatever runs at those positions next.  2 <= n <= 16.
+ * After a partial acceptance the next pass starts at start_pos + *n_accept + 1 with argmax[*n_accept] as its tokens[0] (argmax[0 .. *n_accept]
+ * are the *n_accept + 1 tokens the call has produced).
+ * Where lmrs_score_tokens would run its batched pass the run goes through that chain with every GEMM - the layers' and the classifier - in the
+ * skinny weight-streaming form: the weights cross HBM once for the n tokens.  f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1 and classifier
+ * rows that are no multiple of 16 run the decode step per token: same values.  One-GPU contexts only.  Errors (NULL arguments, n outside 2 .. 16,
+ * start_pos + n > seq_len, a token >= vocab_size, a sharded context) are reported before any device work and leave the context usable. */
+int lmrs_verify_tokens(lmrs_ctx* ctx, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t* argmax, uint32_t* n_accept);
+
+/* Host only, no device: prompt-lookup drafting (no reference counterpart).  The longest suffix of hist[0..n_hist) of length <= ngram_max (>= 1)
+ * that also occurs earlier in hist (an occurrence that starts before the suffix does; it may overlap it); the tokens that followed its LATEST
+ * earlier occurrence, at most max_draft of them and never past the end of hist -> draft, *n_draft (0: no match, also for n_hist < 2). */
+int lmrs_draft_lookup(const uint32_t* hist, size_t n_hist, uint32_t ngram_max, uint32_t max_draft, uint32_t* draft, uint32_t* n_draft);
+
+/* lmrs_generate_greedy's contract and out_tokens, bit for bit (the loop of src/bin/chat.rs:188-222 at temperature 0), produced by draft
+ * (lmrs_draft_lookup over prompt + output so far) and verify (lmrs_verify_tokens' pass); a position without a draft is one ordinary decode
+ * step (lmrs_forward_argmax).  max_draft 1..15, ngram_max >= 1.  The loop synchronises with the host once per pass or step.
+ * stats4 (may be NULL; four counts, each at most n_new): [0] verify passes, [1] drafted tokens, [2] accepted tokens, [3] plain decode steps; a pass yields its accepted drafts
+ * and one more token, a plain step one token, and the last pass is never drafted past n_new:  [0] + [2] + [3] == n_new,  [2] <= [1].
+ * *seconds (optional) = host wall time of the whole call.  One-GPU contexts only; errors as lmrs_generate_greedy's, before any device work. */
+int lmrs_generate_speculative(lmrs_ctx* ctx, const uint32_t* prompt, size_t n_prompt, uint32_t n_new, uint32_t start_pos,
+                              uint32_t max_draft, uint32_t ngram_max, uint32_t* out_tokens, uint32_t* stats4, double* seconds);
+
 const char* lmrs_last_error(void);
 
 /* ---- L2 free functions, for unit parity (host pointers in and out) ------------------
@@ -280,6 +309,12 @@ int lmrs_debug_gemm_tile(uint32_t n, uint32_t o, uint32_t n_tok, int q4, int* ti
  * tile).  Unit-parity aid, no reference counterpart. */
 int lmrs_debug_w13_quant(int device, int8_t* hq, float* hs, const int8_t* xq, const float* xs, const int8_t* wq, const float* ws,
                          size_t n, size_t o, size_t n_tok, int gemma);
+/* The skinny weight-streaming GEMM of lmrs_verify_tokens' pass (gemm_skinny_kernel; matmul_q8 / matmul_q4 of functional.rs:173-250 with
+ * sl = n_tok, 1 <= n_tok <= 16) on caller-supplied operands: out[t*o + r], n a multiple of 256, o of 16, row-major scales.  q4 = 0: xq n_tok x n int8,
+ * wq o x n int8.  q4 = 1: xq n_tok x n/2 and wq o x n/2 packed bytes as the reference packs Q4_0 (the hook de-interleaves the activations into the
+ * int8 rows the batched pass keeps).  Unit-parity aid, no reference counterpart. */
+int lmrs_debug_gemm_skinny(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                           size_t n, size_t o, size_t n_tok, int q4);
 
 /* ---- CLIP image tower of the multimodal models  (src/vision.rs) ---------------------------
  * lmrs_vision_create   <- VisionTransformer::new(data) -> (VisionTransformer, usize)   vision.rs:99-243

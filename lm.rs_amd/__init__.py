@@ -27,6 +27,7 @@ EXPORTS = [
     "lmrs_create", "lmrs_create_sharded", "lmrs_comm_unique_id", "lmrs_destroy", "lmrs_get_args", "lmrs_forward",
     "lmrs_forward_argmax", "lmrs_get_embeddings", "lmrs_fill_kv_cache", "lmrs_generate_greedy", "lmrs_forward_tokens", "lmrs_score_tokens",
     "lmrs_prefill_tokens", "lmrs_tokens_path", "lmrs_score_tokens_topk", "lmrs_forward_topk", "lmrs_op_topk",
+    "lmrs_verify_tokens", "lmrs_draft_lookup", "lmrs_generate_speculative", "lmrs_debug_gemm_skinny",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -96,6 +97,10 @@ def lib():
         L.lmrs_op_topk.argtypes = [C.c_int, vp, sz, sz, u32, vp, vp]
         L.lmrs_prefill_tokens.argtypes = [vp, vp, sz, u32, C.POINTER(u32)]
         L.lmrs_tokens_path.argtypes = [vp, sz, C.POINTER(C.c_int)]
+        L.lmrs_verify_tokens.argtypes = [vp, vp, sz, u32, vp, C.POINTER(u32)]
+        L.lmrs_draft_lookup.argtypes = [vp, sz, u32, u32, vp, C.POINTER(u32)]
+        L.lmrs_generate_speculative.argtypes = [vp, vp, sz, u32, u32, u32, u32, vp, vp, C.POINTER(C.c_double)]
+        L.lmrs_debug_gemm_skinny.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, C.c_int]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.lmrs_op_matmul_q4.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz]
         L.lmrs_op_quantize.argtypes = [C.c_int, vp, vp, vp, sz, sz]
@@ -274,6 +279,24 @@ class Transformer:
         b = C.c_int()
         _chk(lib().lmrs_tokens_path(self._h, n, C.byref(b)))
         return bool(b.value)
+
+    def verify_tokens(self, tokens, start_pos: int = 0):
+        """tokens[0] = the last confirmed token at start_pos, tokens[1:] = drafts (2 <= n <= 16) -> (argmax uint32 [n]: forward_argmax of every
+        position, n_accept: the leading drafts with tokens[t+1] == argmax[t]) in one pass over the weights where score() would run batched
+        (lmrs_verify_tokens).  The next pass starts at start_pos + n_accept + 1 with argmax[n_accept]."""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        am = np.empty(t.size, np.uint32); acc = C.c_uint32()
+        _chk(lib().lmrs_verify_tokens(self._h, _p(t), t.size, start_pos, _p(am), C.byref(acc)))
+        return am, acc.value
+
+    def generate_speculative(self, prompt, n_new: int, start_pos: int = 0, max_draft: int = 7, ngram_max: int = 3, timing: bool = False):
+        """generate_greedy's tokens, bit for bit, by prompt-lookup drafting (draft_lookup) and verify passes (lmrs_generate_speculative) ->
+        (tokens uint32 [n_new], stats uint32 [4]: verify passes, drafted, accepted, plain decode steps; passes + accepted + plain == n_new)
+        (and host seconds if timing)."""
+        pr = np.ascontiguousarray(prompt, np.uint32).reshape(-1)
+        out = np.zeros(n_new, np.uint32); st = np.zeros(4, np.uint32); sec = C.c_double()
+        _chk(lib().lmrs_generate_speculative(self._h, _p(pr), pr.size, n_new, start_pos, max_draft, ngram_max, _p(out), _p(st), C.byref(sec)))
+        return (out, st, sec.value) if timing else (out, st)
 
     def kv_row(self, which: int, layer: int, pos: int) -> np.ndarray:
         """Verification aid: one KV-cache row in the reference's layout (which: 0 key, 1 value)."""
@@ -503,6 +526,23 @@ def rope_terms(model_type: int, rope_theta: float, head_size: int, pos: int, j: 
     c, s_ = C.c_float(), C.c_float()
     _chk(lib().lmrs_rope_terms(C.byref(a), pos, j, C.byref(c), C.byref(s_)))
     return np.float32(c.value), np.float32(s_.value)
+
+
+def draft_lookup(hist, ngram_max: int, max_draft: int) -> np.ndarray:
+    """Prompt-lookup drafting, host only: the tokens that followed the latest earlier occurrence of the longest suffix of `hist` of at most
+    ngram_max tokens, at most max_draft of them (empty: no match) (lmrs_draft_lookup)."""
+    h = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    d = np.zeros(max(int(max_draft), 1), np.uint32); n = C.c_uint32()
+    _chk(lib().lmrs_draft_lookup(_p(h), h.size, ngram_max, max_draft, _p(d), C.byref(n)))
+    return d[:n.value].copy()
+
+
+def debug_gemm_skinny(xq, xs, wq, ws, n: int, o: int, n_tok: int, q4: bool = False, device: int = 0) -> np.ndarray:
+    """The skinny GEMM of verify_tokens' pass on caller-supplied operands -> float32 [n_tok, o] (lmrs_debug_gemm_skinny)."""
+    xq = np.ascontiguousarray(xq); xs = np.ascontiguousarray(xs, np.float32); wq = np.ascontiguousarray(wq); ws = np.ascontiguousarray(ws, np.float32)
+    out = np.empty((n_tok, o), np.float32)
+    _chk(lib().lmrs_debug_gemm_skinny(device, _p(out), _p(xq), _p(xs), _p(wq), _p(ws), n, o, n_tok, int(bool(q4))))
+    return out
 
 
 def gemm_tile(n: int, o: int, n_tok: int, q4: bool = False):

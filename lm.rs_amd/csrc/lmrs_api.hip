@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -83,6 +84,7 @@ struct lmrs_ctx {
     // batched forward_layer (fill_kv_cache): device buffers for kPrefillTokens tokens, allocated on first use
     float *pf_x = nullptr, *pf_q = nullptr, *pf_k = nullptr, *pf_ao = nullptr, *pf_h = nullptr, *pf_xs = nullptr, *pf_t = nullptr; int8_t* pf_xq = nullptr; float* pf_att = nullptr; size_t pf_att_cap = 0;
     bool pf_ready = false;                                 // every prefill buffer above is allocated
+    bool skinny_pass = false;                              // set around the layers of a short pass (short_pass): their GEMMs take the skinny form (GemmArgs::skinny)
     // batched prefill on row shards (plan "tp", Q8_0): the gathered blocks of a token batch - per shard [n_tok x slice int8 | n_tok x slice / 128 scales],
     // pfb_att / pfb_h bytes apart; inside the peer-to-peer arena when that is the transport (peers write them), ordinary memory for RCCL
     char *pfx_att = nullptr, *pfx_h = nullptr, *pfx_x = nullptr; size_t pfb_att = 0, pfb_h = 0, pfb_x = 0; bool pfx_owned = false;   // pfx_x: the split-out plan's f32 slices of wo / w2's output
@@ -1428,7 +1430,7 @@ static int prefill_layers(lmrs_ctx* c, int m, int p0) {
     for (uint32_t l = 0; l < a.n_layers; ++l) {
         const DevLayer& L = c->layers[l];
         GemmArgs g{};
-        g.xq = c->pf_xq; g.xs = c->pf_xs; g.n_tok = m; g.q4 = q4; g.xs_ld = xld;
+        g.xq = c->pf_xq; g.xs = c->pf_xs; g.n_tok = m; g.q4 = q4; g.xs_ld = xld; g.skinny = c->skinny_pass;
         // [x += rmsnorm(previous ffn out)] rmsnorm + quantize | Wqkv | q, raw k, v rows -> cache      (transformer.rs:409-431)
         if (gemma && l > 0) HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, c->pf_t, c->layers[l - 1].rms_post_ffn, eps, 1, 2, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
         else HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, nullptr, nullptr, eps, gemma, 1, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
@@ -1854,6 +1856,120 @@ extern "C" int lmrs_prefill_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n
     return 0;
 }
 
+// ------------------------------------------------------------------ short runs in one weight pass: verifying drafted tokens, speculative greedy generate
+// (no reference counterpart: n calls of Transformer::forward + sample_argmax, value for value)
+constexpr size_t kShortPassMax = 16;           // one 16-token MFMA tile: the skinny GEMM's token axis (gemm_skinny_kernel)
+
+// The batched chain of tokens_pass for m <= 16 tokens already in c->tokens[start_pos ..), every GEMM - the layers' and the classifier - in the skinny form:
+// one pass over the weights.  The per-position sample_argmax goes to c->sc_idx[0 .. m) on the device.  Eligible wherever score_batched_ok holds; the rest
+// (f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1, classifier rows that are no multiple of 16) runs the decode step per token: same values.
+static int short_pass(lmrs_ctx* c, uint32_t start_pos, size_t m) {
+    const bool batched = score_batched_ok(c, m);
+    if (score_alloc(c, batched)) return -1;
+    const int V = (int)c->args.vocab_size;
+    auto reduce = [&](const float* rows, int ld, int written, int mm, size_t r0) -> int {
+        ScoreArgs s{rows, ld, written, V, mm, c->tokens + start_pos + r0 + 1, (int)std::max<long long>(0, (long long)m - 1 - (long long)r0),
+                    c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
+        HIP_OK(launch_score_rows(s, c->stream));
+        return 0;
+    };
+    if (!batched) return decode_given_tokens(c, start_pos, m, [&](size_t t) { return reduce(c->logits, V, V, 1, t); });
+    if (prefill_alloc(c)) return -1;
+    const lmrs_args& a = c->args;
+    const int dim = (int)a.dim, o = cls_rows(c);
+    const bool gemma = a.model_type == LMRS_GEMMA;
+    if (set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
+    if (token_rows(c, start_pos, (int)m)) return -1;
+    c->skinny_pass = true;
+    const int rc = prefill_pass(c, (int)m, (int)start_pos);
+    c->skinny_pass = false;
+    if (rc) return -1;
+    HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, (int)m, c->pf_xq, c->pf_xs, c->stream));
+    GemmArgs g{};
+    g.wq = c->cls_q; g.ws = c->cls_s; g.xq = c->pf_xq; g.xs = c->pf_xs; g.n = dim; g.o = o; g.n_tok = (int)m; g.q4 = c->q4; g.out = c->sc_logits; g.skinny = 1;
+    HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
+    if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), (int)m, c->stream));
+    if (reduce(c->sc_logits, o, o, (int)m, 0)) return -1;
+    return set_state(c, start_pos + (uint32_t)m, 0);
+}
+static int refuse_sharded(const lmrs_ctx* c, const char* what) {
+    if (c->world > 1 || c->comm || c->p2p)
+        return fail(std::string(what) + " runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
+    return 0;
+}
+// one verify pass over c->h_tok[0 .. n) at start_pos -> argmax (host, n entries), *n_accept; the arguments are checked by the caller
+static int verify_run(lmrs_ctx* c, size_t n, uint32_t start_pos, uint32_t* argmax, uint32_t* n_accept) {
+    HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+    if (short_pass(c, start_pos, n)) return -1;
+    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8);
+    HIP_OK(hipMemcpyAsync(h_idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (finish_call(c)) return -1;
+    memcpy(argmax, h_idx, n * 4);
+    uint32_t acc = 0;
+    while (acc + 1 < n && c->h_tok[acc + 1] == argmax[acc]) ++acc;
+    *n_accept = acc;
+    return 0;
+}
+
+extern "C" int lmrs_verify_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t* argmax, uint32_t* n_accept) {
+    if (check_tokens(c, tokens, n, start_pos, n)) return -1;
+    if (!argmax || !n_accept) return fail("NULL argument");
+    if (n < 2 || n > kShortPassMax) return fail("lmrs_verify_tokens: n = " + std::to_string(n) + " is outside 2 .. " + std::to_string(kShortPassMax));
+    if (refuse_sharded(c, "lmrs_verify_tokens")) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    memcpy(c->h_tok, tokens, n * 4);
+    return verify_run(c, n, start_pos, argmax, n_accept);
+}
+
+extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, size_t n_prompt, uint32_t n_new, uint32_t start_pos,
+                                         uint32_t max_draft, uint32_t ngram_max, uint32_t* out_tokens, uint32_t* stats4, double* seconds) {
+    if (!c || !prompt || (!out_tokens && n_new)) return fail("NULL argument");
+    const size_t steps = n_prompt + (n_new ? n_new - 1 : 0);
+    if (check_tokens(c, prompt, n_prompt, start_pos, steps)) return -1;
+    if (max_draft < 1 || max_draft >= kShortPassMax) return fail("lmrs_generate_speculative: max_draft = " + std::to_string(max_draft) + " is outside 1 .. " + std::to_string(kShortPassMax - 1));
+    if (ngram_max < 1) return fail("lmrs_generate_speculative: ngram_max must be at least 1");
+    if (refuse_sharded(c, "lmrs_generate_speculative")) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t st[4] = {0, 0, 0, 0};
+    // the prompt but its last token only leaves K/V rows behind, as in lmrs_generate_greedy (n_new == 0: the whole prompt, as there)
+    const size_t n_fill = n_new ? n_prompt - 1 : n_prompt;
+    if (n_fill) {
+        if (upload_tokens(c, prompt, n_fill, start_pos)) return -1;
+        if (tokens_batched(c, n_fill)) {
+            if (prefill_token_run(c, start_pos, n_fill)) return -1;
+            if (set_state(c, start_pos + (uint32_t)n_fill, 0)) return -1;
+        } else if (decode_given_tokens(c, start_pos, n_fill, [](size_t) { return 0; })) return -1;
+        if (finish_call(c)) return -1;
+    }
+    std::vector<uint32_t> hist(prompt, prompt + n_prompt);
+    hist.reserve(n_prompt + n_new);
+    uint32_t pos = start_pos + (uint32_t)n_prompt - 1, draft[kShortPassMax], am[kShortPassMax];
+    for (uint32_t done = 0; done < n_new;) {
+        // hist ends with the last confirmed token, which runs at `pos`; a pass of 1 + k tokens gives at most k + 1 new ones
+        uint32_t k = 0;
+        const uint32_t room = std::min<uint32_t>(max_draft, n_new - done - 1);
+        if (room && lmrs_draft_lookup(hist.data(), hist.size(), ngram_max, room, draft, &k)) return -1;
+        uint32_t got = 1;
+        if (k) {
+            uint32_t acc = 0;
+            c->h_tok[0] = hist.back();
+            memcpy(c->h_tok + 1, draft, (size_t)k * 4);
+            if (verify_run(c, (size_t)k + 1, pos, am, &acc)) return -1;
+            got = acc + 1; st[0] += 1; st[1] += k; st[2] += acc;
+        } else {
+            if (lmrs_forward_argmax(c, hist.back(), pos, am)) return -1;
+            st[3] += 1;
+        }
+        for (uint32_t i = 0; i < got; ++i) { out_tokens[done + i] = am[i]; hist.push_back(am[i]); }
+        done += got; pos += got;
+    }
+    if (stats4) memcpy(stats4, st, sizeof st);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+
 // ------------------------------------------------------------------ measurement hooks
 // The GEMV launches of one decode step, in step order (per layer qkv, wo, w1w3, w2; then the classifier),
 // so that the weight stream is the real one (1.27 GB for Llama-3.2-1B: nothing is re-served by the 256 MiB
@@ -2097,6 +2213,37 @@ extern "C" int lmrs_debug_w13_quant(int device, int8_t* hq, float* hs, const int
     g.n = (int)n; g.o = (int)o; g.n_tok = (int)n_tok; g.hq = static_cast<int8_t*>(dq); g.hs = static_cast<float*>(ds);
     HIP_OK(launch_gemm_q8(g, gemma ? EPI_GELU_Q : EPI_SWIGLU_Q, nullptr));
     HIP_OK(hipMemcpy(hq, dq, n_tok * (o / 2), hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(hs, ds, n_tok * (o / 256) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int lmrs_debug_gemm_skinny(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                                      size_t n, size_t o, size_t n_tok, int q4) {
+    if (!out || !xq || !xs || !wq || !ws) return fail("NULL argument");
+    if (n == 0 || n % 256 || o == 0 || o % 16 || n_tok < 1 || n_tok > kShortPassMax) return fail("lmrs_debug_gemm_skinny: n must be a positive multiple of 256, o of 16, n_tok 1 .. 16");
+    if (op_begin(device)) return -1;
+    Scratch S; const size_t G = n / 128, wb = q4 ? n / 2 : n;
+    // Q4_0: the activations arrive as the reference packs them (element 2b in the low nibble of byte b, biased by 8) and go to the device as the int8 (q - 8)
+    // rows the batched pass keeps: de-interleaved within every 8 elements, evens then odds (rows_prologue_kernel)
+    std::vector<int8_t> x8;
+    if (q4) {
+        x8.resize(n_tok * n);
+        const uint8_t* xp = reinterpret_cast<const uint8_t*>(xq);
+        for (size_t t = 0; t < n_tok; ++t)
+            for (size_t e = 0; e < n; e += 8)
+                for (size_t b = 0; b < 4; ++b) {
+                    const uint8_t v = xp[t * (n / 2) + e / 2 + b];
+                    x8[t * n + e + b] = (int8_t)((int)(v & 0x0F) - 8); x8[t * n + e + 4 + b] = (int8_t)((int)(v >> 4) - 8);
+                }
+    }
+    void *dx = S.get(n_tok * n), *dxs = S.get(n_tok * G * 4), *dw = S.get(o * wb), *dws = S.get(o * G * 4), *dout = S.get(n_tok * o * 4);
+    if (!dx || !dxs || !dw || !dws || !dout) return fail("hipMalloc failed");
+    HIP_OK(hipMemcpy(dx, q4 ? x8.data() : xq, n_tok * n, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(dxs, xs, n_tok * G * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dw, wq, o * wb, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(dws, ws, o * G * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dout, 0, n_tok * o * 4));
+    GemmArgs g{}; g.wq = dw; g.ws = static_cast<float*>(dws); g.xq = static_cast<const int8_t*>(dx); g.xs = static_cast<const float*>(dxs);
+    g.n = (int)n; g.o = (int)o; g.n_tok = (int)n_tok; g.q4 = q4 ? 1 : 0; g.out = static_cast<float*>(dout); g.skinny = 1;
+    HIP_OK(launch_gemm_q8(g, EPI_STORE, nullptr));
+    HIP_OK(hipMemcpy(out, dout, n_tok * o * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

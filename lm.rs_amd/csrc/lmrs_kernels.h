@@ -186,6 +186,9 @@ struct GemmArgs {
     // ws_ld: weights (the library keeps a transposed copy of the layers' scales for the batched path); xs_ld / hs_ld: activations in / quantised h out.
     int ws_ld, xs_ld, hs_ld;
     int8_t* hq; float* hs;                                                       // EPI_SWIGLU_Q / EPI_GELU_Q: quantised h [n_tok][o/2] int8 + scales [n_tok][o/256]
+    // 1 and n_tok <= 16: the weight-streaming skinny kernel (gemm_skinny_kernel, lmrs_prefill.inc) - one 16-token tile, every weight byte read once; row-major
+    // scales only (ws_ld = xs_ld = 0); EPI_STORE / RESID / QKV / SWIGLU / GELU.  0 (every caller but the short token pass): the dispatch as it always was.
+    int skinny;
 };
 bool gemm_q8_hq_fused(int n, int o, int n_tok, bool q4);                         // host only: this w1/w3 launch can take the quantising epilogue
 hipError_t launch_gemm_q8(const GemmArgs& a, int epi, hipStream_t s);

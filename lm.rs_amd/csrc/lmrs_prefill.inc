@@ -812,8 +812,140 @@ static hipError_t launch_gemm_q8_epi(const GemmArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((gemm_q8_kernel<EPI, 2, 4, 1>), dim3(rt, tt), dim3(64), sc1, s, a);
     return hipGetLastError();
 }
+// ------------------------------------------------------------------------------------------------
+// Skinny GEMM: 1 .. 16 tokens (GemmArgs::skinny; a drafted run to verify, a chat turn, a prompt tail).  The token axis is ONE 16-wide MFMA tile, so a pass
+// is a weight stream, like a decode step's GEMVs: every weight byte is read from HBM once (wide non-temporal loads) whatever n_tok is, and what has to be
+// found is bytes in flight, not MFMAs.  A workgroup of NW waves owns 16 MT weight rows; wave w takes the groups g = w (mod NW) - its loads, MFMAs and the two
+// multiplies per element need no order - keeps D groups of fragments in flight in registers and parks its products ((isum as f32) * ws) * xs in LDS, [g][tile][lane].
+// Only the ADD is ordered (the reference adds a row's group products in ascending group order): after the one barrier of the kernel wave m adds the products
+// of row tile m, g = 0 .. G - 1, and runs the epilogue.  Same operations in the same order per element as gemm_q8_kernel: bit-identical.
+// Activations: the n_tok int8 rows are MFMA fragments straight from global memory (L2: they are a few KB .. 144 KB and every workgroup reads them), one pair
+// of fragments per group shared by the MT row tiles of a wave; tokens past the batch are a duplicate of the last one and never stored.  The group scales of
+// a wave's own groups are staged in LDS by that wave before its first group ([i][row] / [i][token], as gemm_q8_kernel: no loop-carried loaded scalars).
+// Scale layout: ROW-MAJOR only (ws [o][n/128], xs [n_tok][n/128]; ws_ld / xs_ld must be 0 - the launcher refuses others): what a pass below 48 tokens uses.
+// ------------------------------------------------------------------------------------------------
+#ifndef LMRS_SKINNY_DEPTH
+#define LMRS_SKINNY_DEPTH 2                                      // groups of fragments a wave keeps in flight (measured: 4 is slower, profiles/ab_skinny_tile.txt; A/B builds: make V=.. EXTRA=-DLMRS_SKINNY_DEPTH=4)
+#endif
+#ifndef LMRS_SKINNY_WIDE_ROWS
+#define LMRS_SKINNY_WIDE_ROWS 8192                               // launches of at least this many rows take the 32-row tiles
+#endif
+template <int EPI, int MT, int NW, bool Q4 = false>
+__global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(const GemmArgs a) {
+    constexpr int D = LMRS_SKINNY_DEPTH;
+    constexpr int NR = 16 * MT;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lr = lane & 15, kb = lane >> 4;
+    const int K = a.n, G = K / 128, GW = (G + NW - 1) / NW;      // GW: groups per wave, rounded up (a wave's surplus turns re-load its last group, their products go to the dump slot G)
+    const int WB = Q4 ? K / 2 : K;
+    const int r0 = blockIdx.x * NR;
+    f32x4m* P = reinterpret_cast<f32x4m*>(smem_raw);             // [G + 1][MT][64 lanes] products
+    float* wsl = reinterpret_cast<float*>(smem_raw + (size_t)(G + 1) * MT * 1024) + (size_t)wave * GW * (NR + 16);   // this wave's groups: [GW][NR]
+    float* xsl = wsl + (size_t)GW * NR;                                                                              //                     [GW][16]
+    const int8_t* wrow[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        int r = r0 + m * 16; r = r < a.o ? r : a.o - 16;         // a ragged last tile re-does the previous one (o is a multiple of 16)
+        wrow[m] = static_cast<const int8_t*>(a.wq) + (size_t)(r + lr) * WB + kb * (Q4 ? 8 : 16);
+    }
+    const int8_t* xrow;
+    { const int t = lr < a.n_tok ? lr : a.n_tok - 1; xrow = a.xq + (size_t)t * K + kb * 16; }
+    typedef int i32x2m __attribute__((ext_vector_type(2)));
+    using WFrag = std::conditional_t<Q4, i32x2m, i32x4m>;        // Q4: the packed bytes stay packed until the MFMA (half the registers in flight)
+    struct Frag { WFrag w0[MT], w1[MT]; i32x4m x0, x1; };
+    auto group_of = [&](int i) __attribute__((always_inline)) { const int g = i * NW + wave; return g < G ? g : G - 1; };     // (clamped: always a valid address)
+    auto load = [&](Frag& f, int g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            f.w0[m] = __builtin_nontemporal_load(reinterpret_cast<const WFrag*>(wrow[m] + (size_t)g * (Q4 ? 64 : 128)));
+            f.w1[m] = __builtin_nontemporal_load(reinterpret_cast<const WFrag*>(wrow[m] + (size_t)g * (Q4 ? 64 : 128) + (Q4 ? 32 : 64)));
+        }
+        f.x0 = *reinterpret_cast<const i32x4m*>(xrow + (size_t)g * 128);
+        f.x1 = *reinterpret_cast<const i32x4m*>(xrow + (size_t)g * 128 + 64);
+    };
+    Frag f[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) load(f[k], group_of(k));         // the weight stream starts before the scales are staged
+    {   // group scales of this wave's groups (turn i -> group_of(i)): lane -> (row, turn phase) / (token, turn phase)
+        int r = r0 + (lane % NR); r = r < a.o ? r : a.o - 1;
+        const float* wsp = a.ws + (size_t)r * G;
+        for (int i = lane / NR; i < GW; i += 64 / NR) wsl[i * NR + (lane % NR)] = wsp[group_of(i)];
+        const int t = lr < a.n_tok ? lr : a.n_tok - 1;
+        const float* xsp = a.xs + (size_t)t * G;
+        for (int i = kb; i < GW; i += 4) xsl[i * 16 + lr] = xsp[group_of(i)];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                             // (each wave reads only the scales it wrote)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    auto use = [&](const Frag& fr, int i) __attribute__((always_inline)) {
+        const int ic = i < GW ? i : GW - 1, g = i * NW + wave, slot = (i < GW && g < G) ? g : G;
+        const float xsv = xsl[ic * 16 + lr];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const f32x4m wsv = *reinterpret_cast<const f32x4m*>(wsl + ic * NR + m * 16 + kb * 4);     // the 4 weight rows this lane holds
+            i32x4m w0, w1, c = {0, 0, 0, 0};
+            if constexpr (Q4) { w0 = q4_fragment(fr.w0[m].x, fr.w0[m].y); w1 = q4_fragment(fr.w1[m].x, fr.w1[m].y); }
+            else { w0 = fr.w0[m]; w1 = fr.w1[m]; }
+            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, fr.x0, c, 0, 0, 0);                           // D[row = weight row][col = token]
+            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, fr.x1, c, 0, 0, 0);
+            f32x4m p;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { float q = (float)c[e] * wsv[e]; p[e] = q * xsv; }             // ((ival as f32) * w.s[..]) * x.s[..]
+            P[((size_t)slot * MT + m) * 64 + lane] = p;
+        }
+    };
+    for (int i = 0; i < GW; i += D) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            use(f[k], i + k);
+            { const int in = i + k + D; load(f[k], group_of(in < GW ? in : GW - 1)); }      // unconditional (the tail re-loads the wave's last group: no load under a branch)
+        }
+    }
+    __syncthreads();
+    // ---- the ordered sum: wave m < MT adds the products of row tile m in ascending group order, then the epilogue of gemm_q8_kernel
+    if (wave < MT) {
+        const int m = wave;
+        f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+        for (int g = 0; g < G; ++g) {
+            const f32x4m v = P[((size_t)g * MT + m) * 64 + lane];
+            acc[0] = acc[0] + v[0]; acc[1] = acc[1] + v[1]; acc[2] = acc[2] + v[2]; acc[3] = acc[3] + v[3];
+        }
+        if (r0 + m * 16 < a.o && lr < a.n_tok) gemm_epilogue<EPI>(a, r0 + m * 16 + kb * 4, lr, acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+static size_t gemm_skinny_lds(int n, int mt, int nw) {
+    const int G = n / 128, GW = (G + nw - 1) / nw;
+    return (size_t)(G + 1) * mt * 1024 + (size_t)nw * GW * (16 * mt + 16) * sizeof(float);
+}
+// The tile by shape: launches of few rows (wo, w2, qkv: a few hundred 16-row tiles) put 8 waves on every tile, so that the launch has a few thousand waves'
+// loads in flight; the wide ones (w1/w3, the classifier) take 32-row tiles of 4 waves, whose two row tiles share the activation fragments.
+template <int EPI, bool Q4>
+static hipError_t launch_gemm_skinny(const GemmArgs& a, hipStream_t s) {
+    if (a.ws_ld || a.xs_ld || a.n_tok > 16) return hipErrorInvalidValue;
+    const size_t wide = gemm_skinny_lds(a.n, 2, 4), narrow = gemm_skinny_lds(a.n, 1, 8);
+    if (a.o >= LMRS_SKINNY_WIDE_ROWS && wide <= 64 * 1024) {
+        hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 4, Q4>), dim3((a.o + 31) / 32), dim3(256), wide, s, a);
+        return hipGetLastError();
+    }
+    if (narrow > 150 * 1024) return hipErrorInvalidValue;
+    allow_big_lds(reinterpret_cast<const void*>(gemm_skinny_kernel<EPI, 1, 8, Q4>));
+    hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 1, 8, Q4>), dim3(a.o / 16), dim3(512), narrow, s, a);
+    return hipGetLastError();
+}
+static hipError_t launch_gemm_skinny_epi(const GemmArgs& a, int epi, hipStream_t s) {
+#define SK(E_) case E_: return a.q4 ? launch_gemm_skinny<E_, true>(a, s) : launch_gemm_skinny<E_, false>(a, s)
+    switch (epi) {
+        SK(EPI_STORE); SK(EPI_RESID); SK(EPI_QKV); SK(EPI_SWIGLU); SK(EPI_GELU);
+        default: return hipErrorInvalidValue;                     // (the text pass's epilogues only; the quantising forms are not needed below 128-token tiles)
+    }
+#undef SK
+}
+
 hipError_t launch_gemm_q8(const GemmArgs& a, int epi, hipStream_t s) {
     if (a.n % 256 || a.o % 16 || a.n_tok <= 0) return hipErrorInvalidValue;
+    if (a.skinny && a.n_tok <= 16) return launch_gemm_skinny_epi(a, epi, s);
     switch (epi) {
         case EPI_STORE: return launch_gemm_q8_epi<EPI_STORE>(a, s);
         case EPI_RESID: return launch_gemm_q8_epi<EPI_RESID>(a, s);

@@ -373,3 +373,22 @@ extern "C" int lmrs_sampler_sample(lmrs_sampler* s, float* logits, uint32_t* nex
         if (logits[i] >= cutoff) { s->probindex[n0].index = (uint32_t)i; s->probindex[n0].prob = logits[i]; ++n0; }
     return topp_tail(s, n0, rnd, next);
 }
+
+// ------------------------------------------------------------------ prompt-lookup drafting (lmrs_generate_speculative; no reference counterpart)
+extern "C" int lmrs_draft_lookup(const uint32_t* hist, size_t n_hist, uint32_t ngram_max, uint32_t max_draft, uint32_t* draft, uint32_t* n_draft) {
+    if (!n_draft || (!hist && n_hist) || (!draft && max_draft)) return lmrs::text_fail("NULL argument");
+    if (ngram_max < 1) return lmrs::text_fail("lmrs_draft_lookup: ngram_max must be at least 1");
+    *n_draft = 0;
+    if (n_hist < 2 || max_draft == 0) return 0;
+    for (size_t L = std::min<size_t>(ngram_max, n_hist - 1); L >= 1; --L) {           // the longest suffix first
+        const uint32_t* suf = hist + n_hist - L;
+        for (size_t s = n_hist - L; s-- > 0;) {                                        // its latest earlier occurrence first
+            if (memcmp(hist + s, suf, L * 4)) continue;
+            const size_t k = std::min<size_t>(max_draft, n_hist - (s + L));
+            memcpy(draft, hist + s + L, k * 4);
+            *n_draft = (uint32_t)k;
+            return 0;
+        }
+    }
+    return 0;
+}

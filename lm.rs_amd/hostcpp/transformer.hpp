@@ -67,6 +67,26 @@ public:
         return np;
     }
     std::uint32_t prefill_tokens(const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) { return prefill_tokens(tokens.data(), tokens.size(), start_pos); }
+    // Extensions (lmrs_verify_tokens / lmrs_generate_speculative): tokens[0] = the last confirmed token at start_pos, tokens[1..) = drafts -> the
+    // argmax of every position and the number of accepted drafts, in one pass over the weights; generate_greedy's tokens by draft and verify
+    struct Verified { std::vector<std::uint32_t> argmax; std::uint32_t n_accept = 0; };
+    Verified verify_tokens(const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) {
+        Verified v; v.argmax.resize(tokens.size());
+        check(lmrs_verify_tokens(ctx_, tokens.data(), tokens.size(), start_pos, v.argmax.data(), &v.n_accept));
+        return v;
+    }
+    std::vector<std::uint32_t> generate_speculative(const std::vector<std::uint32_t>& prompt, std::uint32_t n_new, std::uint32_t start_pos = 0,
+                                                    std::uint32_t max_draft = 7, std::uint32_t ngram_max = 3, std::uint32_t* stats4 = nullptr, double* seconds = nullptr) {
+        std::vector<std::uint32_t> out(n_new);
+        check(lmrs_generate_speculative(ctx_, prompt.data(), prompt.size(), n_new, start_pos, max_draft, ngram_max, out.data(), stats4, seconds));
+        return out;
+    }
+    static std::vector<std::uint32_t> draft_lookup(const std::vector<std::uint32_t>& hist, std::uint32_t ngram_max, std::uint32_t max_draft) {
+        std::vector<std::uint32_t> d(max_draft); std::uint32_t n = 0;
+        check(lmrs_draft_lookup(hist.data(), hist.size(), ngram_max, max_draft, d.data(), &n));
+        d.resize(n);
+        return d;
+    }
     bool tokens_path(std::size_t n) const { int b = 0; check(lmrs_tokens_path(ctx_, n, &b)); return b != 0; }
     // Extensions (no reference counterpart): one forward per token of `tokens` from position start_pos, in one call.
     // forward_tokens: n x vocab_size logits, row t = forward(tokens[t], start_pos + t).

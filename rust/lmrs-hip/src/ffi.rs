@@ -44,6 +44,12 @@ extern "C" {
     pub fn lmrs_op_topk(device: c_int, logits: *const f32, n: usize, written: usize, k: u32, idx: *mut u32, val: *mut f32) -> c_int;
     pub fn lmrs_prefill_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, new_pos: *mut u32) -> c_int;
     pub fn lmrs_tokens_path(ctx: *const LmrsCtx, n: usize, batched: *mut c_int) -> c_int;
+    pub fn lmrs_verify_tokens(ctx: *mut LmrsCtx, tokens: *const u32, n: usize, start_pos: u32, argmax: *mut u32, n_accept: *mut u32) -> c_int;
+    pub fn lmrs_draft_lookup(hist: *const u32, n_hist: usize, ngram_max: u32, max_draft: u32, draft: *mut u32, n_draft: *mut u32) -> c_int;
+    pub fn lmrs_generate_speculative(ctx: *mut LmrsCtx, prompt: *const u32, n_prompt: usize, n_new: u32, start_pos: u32, max_draft: u32,
+                                     ngram_max: u32, out_tokens: *mut u32, stats4: *mut u32, seconds: *mut f64) -> c_int;
+    pub fn lmrs_debug_gemm_skinny(device: c_int, out: *mut f32, xq: *const i8, xs: *const f32, wq: *const u8, ws: *const f32,
+                                  n: usize, o: usize, n_tok: usize, q4: c_int) -> c_int;
     pub fn lmrs_last_error() -> *const c_char;
 
     pub fn lmrs_vision_create(section: *const u8, len: usize, device: c_int, out: *mut *mut LmrsVision, bytes_consumed: *mut usize) -> c_int;

@@ -187,12 +187,44 @@ impl<'a> Transformer<'a> {
         new_pos
     }
 
+    /// Extension: `tokens[0]` is the last confirmed token at `start_pos`, `tokens[1..]` are drafts (2 <= n <= 16).  Returns (`forward_argmax`
+    /// of every position, the number of leading drafts with `tokens[t + 1] == argmax[t]`), from one pass over the weights where `score`
+    /// would run batched.  The next pass starts at `start_pos + n_accept + 1` with `argmax[n_accept]`.
+    pub fn verify_tokens(&mut self, tokens: &[u32], start_pos: u32) -> (Vec<u32>, u32) {
+        let mut argmax = vec![0u32; tokens.len()];
+        let mut n_accept: u32 = 0;
+        check(unsafe { ffi::lmrs_verify_tokens(self.ctx, tokens.as_ptr(), tokens.len(), start_pos, argmax.as_mut_ptr(), &mut n_accept) });
+        (argmax, n_accept)
+    }
+
+    /// Extension: `generate_greedy`'s tokens, bit for bit, by prompt-lookup drafting (`draft_lookup`) and verify passes.  Returns (the `n_new`
+    /// ids, [verify passes, drafted tokens, accepted tokens, plain decode steps]); passes + accepted + plain == n_new.
+    pub fn generate_speculative(&mut self, prompt: &[u32], n_new: u32, start_pos: u32, max_draft: u32, ngram_max: u32) -> (Vec<u32>, [u32; 4]) {
+        let mut out = vec![0u32; n_new as usize];
+        let mut stats = [0u32; 4];
+        check(unsafe {
+            ffi::lmrs_generate_speculative(self.ctx, prompt.as_ptr(), prompt.len(), n_new, start_pos, max_draft, ngram_max, out.as_mut_ptr(),
+                                           stats.as_mut_ptr(), ptr::null_mut())
+        });
+        (out, stats)
+    }
+
     /// Whether `prefill_tokens` runs a run of `n` tokens as one batched pass on this context.
     pub fn tokens_path(&self, n: usize) -> bool {
         let mut batched: std::os::raw::c_int = 0;
         check(unsafe { ffi::lmrs_tokens_path(self.ctx, n, &mut batched) });
         batched != 0
     }
+}
+
+/// Prompt-lookup drafting, host only: the tokens that followed the latest earlier occurrence of the longest suffix of `hist` of at most
+/// `ngram_max` tokens, at most `max_draft` of them (empty: no match).
+pub fn draft_lookup(hist: &[u32], ngram_max: u32, max_draft: u32) -> Vec<u32> {
+    let mut draft = vec![0u32; max_draft as usize];
+    let mut n: u32 = 0;
+    check(unsafe { ffi::lmrs_draft_lookup(hist.as_ptr(), hist.len(), ngram_max, max_draft, draft.as_mut_ptr(), &mut n) });
+    draft.truncate(n as usize);
+    draft
 }
 
 /// The communicator id rank 0 makes for `new_sharded`.
