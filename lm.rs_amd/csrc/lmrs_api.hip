@@ -84,7 +84,6 @@ struct lmrs_ctx {
     // batched forward_layer (fill_kv_cache): device buffers for kPrefillTokens tokens, allocated on first use
     float *pf_x = nullptr, *pf_q = nullptr, *pf_k = nullptr, *pf_ao = nullptr, *pf_h = nullptr, *pf_xs = nullptr, *pf_t = nullptr; int8_t* pf_xq = nullptr; float* pf_att = nullptr; size_t pf_att_cap = 0;
     bool pf_ready = false;                                 // every prefill buffer above is allocated
-    bool skinny_pass = false;                              // set around the layers of a short pass (short_pass): their GEMMs take the skinny form (GemmArgs::skinny)
     // batched prefill on row shards (plan "tp", Q8_0): the gathered blocks of a token batch - per shard [n_tok x slice int8 | n_tok x slice / 128 scales],
     // pfb_att / pfb_h bytes apart; inside the peer-to-peer arena when that is the transport (peers write them), ordinary memory for RCCL
     char *pfx_att = nullptr, *pfx_h = nullptr, *pfx_x = nullptr; size_t pfb_att = 0, pfb_h = 0, pfb_x = 0; bool pfx_owned = false;   // pfx_x: the split-out plan's f32 slices of wo / w2's output
@@ -172,6 +171,8 @@ size_t prefill_tp_block(size_t n_l) { return pad256((size_t)kPrefillTokens * n_l
 // The form of one decode step: how it runs qkv + attention (qa_mode, see lmrs_ctx::qkv_att) and, when its attention is the split pair, over how many
 // 256-key chunks (then qa_mode is 0: the merged launch has no split form).  A value handed down to the enqueue functions, never context state.
 struct StepForm { int qa_mode = 0, split_chunks = 0; };
+// The form of one batched pass, a value in the same way: skinny = every GEMM of it, the layers' and the classifier's, in the 16-token form (GemmArgs::skinny)
+struct PassForm { bool skinny = false; };
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1392,7 +1393,7 @@ static int prefill_attention(lmrs_ctx* c, AttnArgs& t, int m, int p0) {
 // and h blocks are TWO buffers: a peer can only write block A of layer l + 1 after it has seen this shard's flag of exchange H of layer l, which
 // this shard raises after it has consumed A of layer l (stream order) - and the other way round.
 static bool row_sharded(const lmrs_ctx* c);
-static int prefill_layers(lmrs_ctx* c, int m, int p0) {
+static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
     const lmrs_args& a = c->args;
     const bool tp = row_sharded(c);
     const int dim = (int)a.dim, hid = (int)a.hidden_dim, att = c->att_dim, kv = c->kv_dim, hs = (int)a.head_size, q4 = c->q4, W = c->world;
@@ -1430,7 +1431,7 @@ static int prefill_layers(lmrs_ctx* c, int m, int p0) {
     for (uint32_t l = 0; l < a.n_layers; ++l) {
         const DevLayer& L = c->layers[l];
         GemmArgs g{};
-        g.xq = c->pf_xq; g.xs = c->pf_xs; g.n_tok = m; g.q4 = q4; g.xs_ld = xld; g.skinny = c->skinny_pass;
+        g.xq = c->pf_xq; g.xs = c->pf_xs; g.n_tok = m; g.q4 = q4; g.xs_ld = xld; g.skinny = form.skinny;
         // [x += rmsnorm(previous ffn out)] rmsnorm + quantize | Wqkv | q, raw k, v rows -> cache      (transformer.rs:409-431)
         if (gemma && l > 0) HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, c->pf_t, c->layers[l - 1].rms_post_ffn, eps, 1, 2, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
         else HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, nullptr, nullptr, eps, gemma, 1, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
@@ -1475,17 +1476,17 @@ static int prefill_layers(lmrs_ctx* c, int m, int p0) {
 // (a communicator of ONE rank counts as a row-sharded context - the RCCL branch of the batched path can then run, and be tested, on a one-GPU box)
 static bool row_sharded(const lmrs_ctx* c) { return (c->world > 1 || c->comm) && !c->cls_only; }
 static bool prefill_tp_ok(const lmrs_ctx* c) { return c->tp_prefill && row_sharded(c) && (c->comm || (c->p2p && c->p2p_ready && c->pfx_att)); }
-static int prefill_pass(lmrs_ctx* c, int m, int p0) {
+static int prefill_pass(lmrs_ctx* c, PassForm form, int m, int p0) {
     if (row_sharded(c)) c->ex_slot = 0;
-    return prefill_layers(c, m, p0);
+    return prefill_layers(c, form, m, p0);
 }
 
 // forward_layer over rows p0 .. p0 + n - 1, kPrefillTokens at a time (a later chunk only needs the K/V rows of the earlier ones, exactly as inside
 // the reference's single call): produce(i0, m) leaves the embedding rows of a chunk in pf_x, consume(i0, m) takes its finished residual rows from there
-template <class Produce, class Consume> static int prefill_chunks(lmrs_ctx* c, uint32_t p0, size_t n, Produce produce, Consume consume) {
+template <class Produce, class Consume> static int prefill_chunks(lmrs_ctx* c, PassForm form, uint32_t p0, size_t n, Produce produce, Consume consume) {
     for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens) {
         const int m = (int)std::min<size_t>(kPrefillTokens, n - i0);
-        if (produce(i0, m) || prefill_pass(c, m, (int)(p0 + i0)) || consume(i0, m)) return -1;
+        if (produce(i0, m) || prefill_pass(c, form, m, (int)(p0 + i0)) || consume(i0, m)) return -1;
     }
     return 0;
 }
@@ -1521,7 +1522,7 @@ extern "C" int lmrs_fill_kv_cache(lmrs_ctx* c, float* embeddings, uint32_t n, ui
             HIP_OK(hipMemcpyAsync(embeddings + i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));
             return 0;
         };
-        if (prefill_chunks(c, curr_pos, n, upload_rows, download_rows)) return -1;
+        if (prefill_chunks(c, PassForm{}, curr_pos, n, upload_rows, download_rows)) return -1;
         if (set_state(c, curr_pos + n, 0)) return -1;
     } else {
         // forward_layer(sl = n) for every layer is, value for value, n single-token passes through the layers (causal; each token's arithmetic only
@@ -1566,6 +1567,12 @@ static int check_tokens(const lmrs_ctx* c, const uint32_t* tokens, size_t n, uin
     for (size_t i = 0; i < n; ++i) if (tokens[i] >= c->args.vocab_size) return fail("token " + std::to_string(i) + " out of range");
     return 0;
 }
+// The refusal of the entry points that have no sharded form; `what`: the subject of the sentence
+static int refuse_sharded(const lmrs_ctx* c, const char* what) {
+    if (c->world > 1 || c->comm || c->p2p)
+        return fail(std::string(what) + " runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
+    return 0;
+}
 static int upload_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos) {      // -> c->tokens[start_pos ..), through the pinned h_tok
     memcpy(c->h_tok, tokens, n * 4);
     HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1585,7 +1592,7 @@ static int token_rows(lmrs_ctx* c, uint32_t pos, int m) {        // embedding ro
 static int prefill_token_run(lmrs_ctx* c, uint32_t start_pos, size_t n) {
     if (prefill_alloc(c)) return -1;
     if (c->args.model_type == LMRS_GEMMA && set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
-    return prefill_chunks(c, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); }, [](size_t, int) { return 0; });
+    return prefill_chunks(c, PassForm{}, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); }, [](size_t, int) { return 0; });
 }
 // The decode step per token for n GIVEN tokens, already in c->tokens: prompt_end = start_pos + n makes every step embed the next given token instead
 // of its own result (lmrs_generate_greedy's prompt phase); per_step(t) is enqueued behind step t, whose logits are in c->logits then
@@ -1594,6 +1601,12 @@ template <class PerStep> static int decode_given_tokens(lmrs_ctx* c, uint32_t st
     HIP_OK(launch_embed(embed_args(c), c->stream));
     for (size_t t = 0; t < n; ++t) if (launch_step(c, start_pos + (uint32_t)t) || per_step(t)) return -1;
     return 0;
+}
+// A run nobody reads the logits of: K/V rows start_pos .. start_pos + n - 1 from c->tokens and the state behind them - the batched pass from
+// tokens_batch_min tokens on, else the decode steps (the classifier's result of every step goes nowhere)
+static int fill_given_tokens(lmrs_ctx* c, uint32_t start_pos, size_t n) {
+    if (!tokens_batched(c, n)) return decode_given_tokens(c, start_pos, n, [](size_t) { return 0; });
+    return prefill_token_run(c, start_pos, n) || set_state(c, start_pos + (uint32_t)n, 0) ? -1 : 0;
 }
 
 extern "C" int lmrs_generate_greedy(lmrs_ctx* c, const uint32_t* prompt, size_t n_prompt, uint32_t n_new, uint32_t start_pos,
@@ -1705,79 +1718,99 @@ static int topk_alloc(lmrs_ctx* c, int rows, int k) {
 // lmrs_score_tokens_topk's further results (k == 0: none are asked for)
 struct TopkOut { uint32_t k; uint32_t* idx; float* logprob; uint32_t* rank; };
 
+// The pinned h_sc in its two halves (score_alloc): seq_len doubles for the log-probabilities, then seq_len indices
+struct HostScores { double* lp; uint32_t* idx; };
+static HostScores host_scores(const lmrs_ctx* c) { return {reinterpret_cast<double*>(c->h_sc), reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8)}; }
+
+// What becomes of the logits rows of a run of n tokens in c->tokens[start_pos ..).  out_logits != null: they go to the host as they are
+// (lmrs_forward_tokens); else the reduction of every row - the next token's log-probability to c->sc_lp, sample_argmax to c->sc_idx - and with k the
+// selection behind it (c->tk_idx / tk_val / tk_rank)
+struct RowSink { uint32_t start_pos; size_t n; float* out_logits; uint32_t k; };
+
+// rows r0 .. r0 + m - 1 of the run, ld columns written at row stride ld (the rest up to vocab_size is the classifier's zero tail)
+static int reduce_rows(lmrs_ctx* c, const RowSink& to, const float* rows, int ld, int m, size_t r0) {
+    const int V = (int)c->args.vocab_size;
+    ScoreArgs s{rows, ld, ld, V, m, c->tokens + to.start_pos + r0 + 1, (int)std::max<long long>(0, (long long)to.n - 1 - (long long)r0),
+                c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
+    HIP_OK(launch_score_rows(s, c->stream));
+    if (!to.k) return 0;
+    // the selection over the same rows, behind the reduction whose chunk summaries give the log-probabilities their m and sum
+    TopkArgs t{rows, ld, ld, V, m, (int)to.k, s.tgt, s.n_tgt, c->sc_part, c->tk_cand, c->tk_cnt,
+               c->tk_idx + r0 * to.k, c->tk_val + r0 * to.k, c->tk_rank + r0};
+    HIP_OK(launch_topk_rows(t, c->stream));
+    return 0;
+}
+static int copy_out_rows(lmrs_ctx* c, const RowSink& to, const float* rows, int ld, int m, size_t r0) {
+    const int V = (int)c->args.vocab_size;
+    float* dst = to.out_logits + r0 * (size_t)V;
+    if (ld == V) { HIP_OK(hipMemcpyAsync(dst, rows, (size_t)m * V * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
+    for (int r = 0; r < m; ++r) memset(dst + (size_t)r * V + ld, 0, (size_t)(V - ld) * 4);   // the unwritten tail [cls_rows, vocab)
+    HIP_OK(hipMemcpy2DAsync(dst, (size_t)V * 4, rows, (size_t)ld * 4, (size_t)ld * 4, m, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+// The tail of a batched chunk behind its layers, rows i0 .. i0 + m - 1 of the run in pf_x: final rmsnorm + quantise of every token
+// (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372) in the pass's form, a slab of the logits block's sc_rows
+// rows at a time; Gemma's soft-cap (:375-381); every slab to the sink
+static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, size_t i0, int m) {
+    const lmrs_args& a = c->args;
+    const int dim = (int)a.dim, o = cls_rows(c);
+    const bool gemma = a.model_type == LMRS_GEMMA;
+    HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
+    for (int j0 = 0; j0 < m; j0 += c->sc_rows) {
+        const int mj = std::min(c->sc_rows, m - j0);
+        GemmArgs g{};
+        g.wq = c->cls_q; g.ws = c->cls_s; g.xq = c->pf_xq + (size_t)j0 * dim; g.xs = c->pf_xs + (size_t)j0 * (dim / 128);
+        g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits; g.skinny = form.skinny;
+        HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
+        if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));
+        if (to.out_logits ? copy_out_rows(c, to, c->sc_logits, o, mj, i0 + j0) : reduce_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
+    }
+    return 0;
+}
+
+// The logits rows of a run to their sink; the tokens are in c->tokens and score_alloc / topk_alloc are done.  batched (score_batched_ok): the chain
+// above, kPrefillTokens at a time, in the given form; else the decode step per token (the form says nothing there): same values
+static int run_tokens(lmrs_ctx* c, const RowSink& to, PassForm form, bool batched) {
+    const uint32_t start_pos = to.start_pos;
+    const size_t n = to.n;
+    if (batched) {
+        if (prefill_alloc(c)) return -1;
+        if (set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
+        if (prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); },
+                           [&](size_t i0, int m) { return classify_rows(c, form, to, i0, m); })) return -1;
+        return set_state(c, start_pos + (uint32_t)n, 0);
+    }
+    const size_t V = c->args.vocab_size;
+    size_t r0 = 0;                                       // first position held in the logits block (forward_tokens)
+    return decode_given_tokens(c, start_pos, n, [&](size_t t) -> int {
+        if (!to.out_logits) return reduce_rows(c, to, c->logits, (int)V, 1, t);
+        HIP_OK(hipMemcpyAsync(c->sc_logits + (t - r0) * V, c->logits, V * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (t + 1 - r0 == (size_t)c->sc_rows || t + 1 == n) {
+            if (copy_out_rows(c, to, c->sc_logits, (int)V, (int)(t + 1 - r0), r0)) return -1;
+            r0 = t + 1;
+        }
+        return 0;
+    });
+}
+
 // out_logits != null: lmrs_forward_tokens (n x vocab floats to the host); else lmrs_score_tokens' results, and with tk.k those of the top-k form
 static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, float* out_logits, float* logprobs, uint32_t* argmax,
                        double* sum_logprob, const TopkOut& tk = TopkOut{0, nullptr, nullptr, nullptr}) {
     // (stage_tokens in its two halves: the refusal and the first-use allocations sit between the checks and the upload, where they always did)
     if (check_tokens(c, tokens, n, start_pos, n)) return -1;
     if (tk.k && topk_check_k(tk.k, c->args.vocab_size)) return -1;
-    if (c->world > 1 || c->comm || c->p2p)
-        return fail("scoring runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
+    if (refuse_sharded(c, "scoring")) return -1;
     HIP_OK(hipSetDevice(c->device));
     const bool batched = score_batched_ok(c, n);
     if (score_alloc(c, batched || out_logits)) return -1;
     if (tk.k && topk_alloc(c, batched ? c->sc_rows : 1, (int)tk.k)) return -1;
-    const int V = (int)c->args.vocab_size;
     if (upload_tokens(c, tokens, n, start_pos)) return -1;
-    // rows r0 .. r0 + m - 1 of the sequence, row stride ld, the first `written` columns written (the rest is the classifier's zero tail)
-    auto reduce = [&](const float* rows, int ld, int written, int m, size_t r0) -> int {
-        ScoreArgs s{rows, ld, written, V, m, c->tokens + start_pos + r0 + 1, (int)std::max<long long>(0, (long long)n - 1 - (long long)r0),
-                    c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
-        HIP_OK(launch_score_rows(s, c->stream));
-        if (!tk.k) return 0;
-        // the selection over the same rows, behind the reduction whose chunk summaries give the log-probabilities their m and sum
-        TopkArgs t{rows, ld, written, V, m, (int)tk.k, s.tgt, s.n_tgt, c->sc_part, c->tk_cand, c->tk_cnt,
-                   c->tk_idx + r0 * tk.k, c->tk_val + r0 * tk.k, c->tk_rank + r0};
-        HIP_OK(launch_topk_rows(t, c->stream));
-        return 0;
-    };
-    auto copy_out = [&](const float* rows, int ld, int m, size_t r0) -> int {
-        float* dst = out_logits + r0 * (size_t)V;
-        if (ld == V) { HIP_OK(hipMemcpyAsync(dst, rows, (size_t)m * V * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
-        for (int r = 0; r < m; ++r) memset(dst + (size_t)r * V + ld, 0, (size_t)(V - ld) * 4);   // the unwritten tail [cls_rows, vocab)
-        HIP_OK(hipMemcpy2DAsync(dst, (size_t)V * 4, rows, (size_t)ld * 4, (size_t)ld * 4, m, hipMemcpyDeviceToHost, c->stream));
-        return 0;
-    };
-    if (batched) {
-        if (prefill_alloc(c)) return -1;
-        const lmrs_args& a = c->args;
-        const int dim = (int)a.dim, o = cls_rows(c);
-        const bool gemma = a.model_type == LMRS_GEMMA;
-        if (set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
-        // final rmsnorm + quantise of every token (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372)
-        auto classify = [&](size_t i0, int m) -> int {
-            HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
-            for (int j0 = 0; j0 < m; j0 += c->sc_rows) {
-                const int mj = std::min(c->sc_rows, m - j0);
-                GemmArgs g{};
-                g.wq = c->cls_q; g.ws = c->cls_s; g.xq = c->pf_xq + (size_t)j0 * dim; g.xs = c->pf_xs + (size_t)j0 * (dim / 128);
-                g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits;
-                HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
-                if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));     // (:375-381)
-                if (out_logits ? copy_out(c->sc_logits, o, mj, i0 + j0) : reduce(c->sc_logits, o, o, mj, i0 + j0)) return -1;
-            }
-            return 0;
-        };
-        if (prefill_chunks(c, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); }, classify)) return -1;
-        if (set_state(c, start_pos + (uint32_t)n, 0)) return -1;
-    } else {
-        size_t r0 = 0;                                       // first position held in the logits block (forward_tokens)
-        auto keep_logits = [&](size_t t) -> int {
-            if (!out_logits) return reduce(c->logits, V, V, 1, t);
-            HIP_OK(hipMemcpyAsync(c->sc_logits + (t - r0) * V, c->logits, (size_t)V * 4, hipMemcpyDeviceToDevice, c->stream));
-            if (t + 1 - r0 == (size_t)c->sc_rows || t + 1 == n) {
-                if (copy_out(c->sc_logits, V, (int)(t + 1 - r0), r0)) return -1;
-                r0 = t + 1;
-            }
-            return 0;
-        };
-        if (decode_given_tokens(c, start_pos, n, keep_logits)) return -1;
-    }
-    double* h_lp = reinterpret_cast<double*>(c->h_sc);
-    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8);
+    if (run_tokens(c, RowSink{start_pos, n, out_logits, tk.k}, PassForm{}, batched)) return -1;
+    const HostScores h = host_scores(c);
     if (!out_logits) {
-        if (n > 1) HIP_OK(hipMemcpyAsync(h_lp, c->sc_lp, (n - 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(h_idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (n > 1) HIP_OK(hipMemcpyAsync(h.lp, c->sc_lp, (n - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(h.idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
     }
     const size_t nk = n * tk.k;                                                             // h_tk: nk indices, nk log-probabilities, n - 1 ranks
     if (tk.k) {
@@ -1792,8 +1825,8 @@ static int tokens_pass(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t s
     }
     if (!out_logits) {
         double sum = 0.0;
-        for (size_t t = 0; t + 1 < n; ++t) { if (logprobs) logprobs[t] = (float)h_lp[t]; sum += h_lp[t]; }
-        if (argmax) memcpy(argmax, h_idx, n * 4);
+        for (size_t t = 0; t + 1 < n; ++t) { if (logprobs) logprobs[t] = (float)h.lp[t]; sum += h.lp[t]; }
+        if (argmax) memcpy(argmax, h.idx, n * 4);
         if (sum_logprob) *sum_logprob = sum;
     }
     return 0;
@@ -1821,8 +1854,7 @@ extern "C" int lmrs_forward_topk(lmrs_ctx* c, uint32_t token, uint32_t pos, uint
     if (topk_check_k(k, 0)) return -1;
     if (!c || !idx || !logits_k) return fail("NULL argument");
     if (topk_check_k(k, c->args.vocab_size)) return -1;
-    if (c->world > 1 || c->comm || c->p2p)
-        return fail("top-k runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
+    if (refuse_sharded(c, "top-k")) return -1;
     if (token >= c->args.vocab_size || pos >= c->args.seq_len) return step_once(c, token, pos);          // (its message; nothing is enqueued)
     HIP_OK(hipSetDevice(c->device));
     if (topk_alloc(c, 1, (int)k)) return -1;
@@ -1847,11 +1879,7 @@ extern "C" int lmrs_tokens_path(const lmrs_ctx* c, size_t n, int* batched) {
 
 extern "C" int lmrs_prefill_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t start_pos, uint32_t* new_pos) {
     if (stage_tokens(c, tokens, n, start_pos, n)) return -1;
-    if (tokens_batched(c, n)) {
-        if (prefill_token_run(c, start_pos, n)) return -1;
-        if (set_state(c, start_pos + (uint32_t)n, 0)) return -1;
-    } else if (decode_given_tokens(c, start_pos, n, [](size_t) { return 0; })) return -1;      // (the classifier's result of every step goes nowhere)
-    if (finish_call(c)) return -1;
+    if (fill_given_tokens(c, start_pos, n) || finish_call(c)) return -1;
     if (new_pos) *new_pos = start_pos + (uint32_t)n;
     return 0;
 }
@@ -1860,48 +1888,20 @@ extern "C" int lmrs_prefill_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n
 // (no reference counterpart: n calls of Transformer::forward + sample_argmax, value for value)
 constexpr size_t kShortPassMax = 16;           // one 16-token MFMA tile: the skinny GEMM's token axis (gemm_skinny_kernel)
 
-// The batched chain of tokens_pass for m <= 16 tokens already in c->tokens[start_pos ..), every GEMM - the layers' and the classifier - in the skinny form:
-// one pass over the weights.  The per-position sample_argmax goes to c->sc_idx[0 .. m) on the device.  Eligible wherever score_batched_ok holds; the rest
-// (f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1, classifier rows that are no multiple of 16) runs the decode step per token: same values.
+// tokens_pass's chain (run_tokens) for m <= 16 tokens already in c->tokens[start_pos ..), with the skinny form - every GEMM, the layers' and the
+// classifier's: one pass over the weights - and the reduction as its sink: the per-position sample_argmax goes to c->sc_idx[0 .. m) on the device.
+// Batched wherever score_batched_ok holds; the rest (f32 files, other geometries, LMRS_NO_BATCHED_PREFILL=1, classifier rows that are no multiple
+// of 16) runs the decode step per token: same values.
 static int short_pass(lmrs_ctx* c, uint32_t start_pos, size_t m) {
     const bool batched = score_batched_ok(c, m);
     if (score_alloc(c, batched)) return -1;
-    const int V = (int)c->args.vocab_size;
-    auto reduce = [&](const float* rows, int ld, int written, int mm, size_t r0) -> int {
-        ScoreArgs s{rows, ld, written, V, mm, c->tokens + start_pos + r0 + 1, (int)std::max<long long>(0, (long long)m - 1 - (long long)r0),
-                    c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
-        HIP_OK(launch_score_rows(s, c->stream));
-        return 0;
-    };
-    if (!batched) return decode_given_tokens(c, start_pos, m, [&](size_t t) { return reduce(c->logits, V, V, 1, t); });
-    if (prefill_alloc(c)) return -1;
-    const lmrs_args& a = c->args;
-    const int dim = (int)a.dim, o = cls_rows(c);
-    const bool gemma = a.model_type == LMRS_GEMMA;
-    if (set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
-    if (token_rows(c, start_pos, (int)m)) return -1;
-    c->skinny_pass = true;
-    const int rc = prefill_pass(c, (int)m, (int)start_pos);
-    c->skinny_pass = false;
-    if (rc) return -1;
-    HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, (int)m, c->pf_xq, c->pf_xs, c->stream));
-    GemmArgs g{};
-    g.wq = c->cls_q; g.ws = c->cls_s; g.xq = c->pf_xq; g.xs = c->pf_xs; g.n = dim; g.o = o; g.n_tok = (int)m; g.q4 = c->q4; g.out = c->sc_logits; g.skinny = 1;
-    HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
-    if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), (int)m, c->stream));
-    if (reduce(c->sc_logits, o, o, (int)m, 0)) return -1;
-    return set_state(c, start_pos + (uint32_t)m, 0);
-}
-static int refuse_sharded(const lmrs_ctx* c, const char* what) {
-    if (c->world > 1 || c->comm || c->p2p)
-        return fail(std::string(what) + " runs on single-GPU contexts only (lmrs_create); contexts of lmrs_create_sharded / lmrs_group_create are not supported");
-    return 0;
+    return run_tokens(c, RowSink{start_pos, m, nullptr, 0}, PassForm{/*skinny=*/true}, batched);
 }
 // one verify pass over c->h_tok[0 .. n) at start_pos -> argmax (host, n entries), *n_accept; the arguments are checked by the caller
 static int verify_run(lmrs_ctx* c, size_t n, uint32_t start_pos, uint32_t* argmax, uint32_t* n_accept) {
     HIP_OK(hipMemcpyAsync(c->tokens + start_pos, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
     if (short_pass(c, start_pos, n)) return -1;
-    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8);
+    uint32_t* h_idx = host_scores(c).idx;
     HIP_OK(hipMemcpyAsync(h_idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
     if (finish_call(c)) return -1;
     memcpy(argmax, h_idx, n * 4);
@@ -1935,12 +1935,7 @@ extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, si
     // the prompt but its last token only leaves K/V rows behind, as in lmrs_generate_greedy (n_new == 0: the whole prompt, as there)
     const size_t n_fill = n_new ? n_prompt - 1 : n_prompt;
     if (n_fill) {
-        if (upload_tokens(c, prompt, n_fill, start_pos)) return -1;
-        if (tokens_batched(c, n_fill)) {
-            if (prefill_token_run(c, start_pos, n_fill)) return -1;
-            if (set_state(c, start_pos + (uint32_t)n_fill, 0)) return -1;
-        } else if (decode_given_tokens(c, start_pos, n_fill, [](size_t) { return 0; })) return -1;
-        if (finish_call(c)) return -1;
+        if (upload_tokens(c, prompt, n_fill, start_pos) || fill_given_tokens(c, start_pos, n_fill) || finish_call(c)) return -1;
     }
     std::vector<uint32_t> hist(prompt, prompt + n_prompt);
     hist.reserve(n_prompt + n_new);

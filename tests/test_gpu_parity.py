@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from parity_rules import assert_bit_equal, bits, ref_argmax
 from tools import synth_lmrs as S
 
 pytestmark = pytest.mark.gpu
@@ -16,17 +17,6 @@ pytestmark = pytest.mark.gpu
 def L():
     import lmrs_amd
     return lmrs_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bit_equal(a, b, what=""):
-    a = np.asarray(a); b = np.asarray(b)
-    assert a.shape == b.shape, what
-    ne = np.flatnonzero(bits(a) != bits(b)) if a.dtype == np.float32 else np.flatnonzero(a != b)
-    assert ne.size == 0, f"{what}: {ne.size}/{a.size} elements differ, first at {ne[:5]}: {a.ravel()[ne[:5]]} vs {b.ravel()[ne[:5]]}"
 
 
 # ------------------------------------------------------------------ L2 free functions
@@ -330,7 +320,7 @@ def test_mini_models_logits_bit_exact(L, cfg):
         lg = m.forward(t, pos)
         lo = orc.forward(t, pos)
         assert_bit_equal(lg, lo, f"{cfg} logits at pos {pos}")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
         assert m.forward_argmax(t, pos) == tok        # re-running a position is idempotent
     for l in range(m.args.n_layers):                   # the KV cache rows behind those logits, every layer, first / middle / last position
         for pos in (0, 7, 19):
@@ -350,7 +340,7 @@ def test_mini_q4_and_gemma_logits_bit_exact(L, cfg, q):
         t = int(prompt[pos]) if pos < len(prompt) else tok
         lo = orc.forward(t, pos)
         assert_bit_equal(m.forward(t, pos), lo, f"{cfg} q{q} logits at pos {pos}")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
 
 
 @pytest.mark.parametrize("i", range(18))
@@ -366,7 +356,7 @@ def test_random_geometries_single_token_and_batched(L, i):
     for pos in range(5):
         lo = orc.forward(tok, pos)
         assert_bit_equal(m.forward(tok, pos), lo, f"{cfg} q{q} logits at pos {pos}")
-        nxt = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        nxt = ref_argmax(lo)
         assert m.forward_argmax(tok, pos) == nxt
         tok = nxt
     n_tok = int(rng.integers(18, 90))
@@ -377,7 +367,7 @@ def test_random_geometries_single_token_and_batched(L, i):
     for pos in range(5 + n_tok, 5 + n_tok + 2):
         lo = orc.forward(tok, pos)
         assert_bit_equal(m.forward(tok, pos), lo, f"{cfg} q{q}: decode at {pos} on the prefilled cache")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
 
 
 @pytest.mark.parametrize("n,o,sl", [(256, 64, 5), (2048, 3072, 70), (8192, 2048, 33), (3072, 48, 129), (256, 16384, 130), (512, 16400, 257)])
@@ -439,7 +429,7 @@ def test_fill_kv_cache_batched_prefill(L, cfg, q, n_tok, pos0):
     for pos in range(pos0 + n_tok, pos0 + n_tok + 3):
         lo = orc.forward(t, pos)
         assert_bit_equal(m.forward(t, pos), lo, f"decode at {pos} on the prefilled cache")
-        t = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        t = ref_argmax(lo)
 
 
 @pytest.mark.parametrize("q,n_tok,pos0", [(S.Q8_0, 150, 7), (S.Q4_0, 90, 0)])
@@ -512,7 +502,7 @@ def test_unquantised_models_logits_bit_exact(L, cfg):
         t = int(prompt[pos]) if pos < len(prompt) else tok
         lo = orc.forward(t, pos)
         assert_bit_equal(m.forward(t, pos), lo, f"{cfg} f32 logits at pos {pos}")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
     e_dev = m.get_embeddings(prompt); e_ref = orc.get_embeddings(prompt)
     assert_bit_equal(e_dev, e_ref, "get_embeddings (f32 table)")
     a = e_dev.copy(); b = e_ref.copy()
@@ -572,7 +562,7 @@ def test_argmax_edge_cases(L, case):
     xq, xs = O.quantize(O.rmsnorm(x, w, 1e-5))
     ref = O.matmul_q8(xq, xs, wq.reshape(-1), ws.reshape(-1), x.size, o)
     assert_bit_equal(lg, ref, f"{case}: logits")
-    want = int(O.lib().lmrs_ref_argmax(ref.ctypes.data, ref.size))
+    want = ref_argmax(ref)
     assert tok == want, f"{case}: device {tok}, reference {want} (logit[tok] = {ref[tok]}, logit[want] = {ref[want]})"
     expect = {"tie_first_wins": 77, "nan_at_zero": 0, "nan_elsewhere": 1234, "all_minus_inf": 0, "max_in_last_row": o - 1,
               "tie_across_workgroups": 40, "plus_inf_tie": 17}[case]
@@ -748,7 +738,7 @@ def test_row_sharding_is_bit_identical(L, monkeypatch, cfg, q, world, mode):
         lg, nxt = grp.forward(t, pos)
         lo = orc.forward(t, pos)
         assert_bit_equal(lg, lo, f"{cfg} world={world} {mode} logits at pos {pos}")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
         assert nxt == tok
     grp.close()
 
@@ -771,7 +761,7 @@ def test_row_sharding_full_size_3b(L, monkeypatch):
         lg, nxt = grp.forward(t, pos)
         lo = orc.forward(t, pos)
         assert_bit_equal(lg, lo, f"3B tp8 logits at pos {pos}")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
         assert nxt == tok
     grp.close()
 
@@ -797,7 +787,7 @@ def test_row_sharding_on_random_geometries(L, monkeypatch, i):
         lg, nxt = grp.forward(tok, pos)
         lo = orc.forward(tok, pos)
         assert_bit_equal(lg, lo, f"{cfg} q{q} two shards, logits at pos {pos}")
-        tok = int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+        tok = ref_argmax(lo)
         assert nxt == tok
     grp.close()
 
@@ -1084,7 +1074,7 @@ def test_classifier_tags_survive_2047_layers_only_steps(L, monkeypatch):
     t0 = 17
     first = m.forward_argmax(t0, 0)
     lo0 = orc.forward(t0, 0)
-    assert first == int(O.lib().lmrs_ref_argmax(lo0.ctypes.data, lo0.size))
+    assert first == ref_argmax(lo0)
     toks = S.prompt_tokens(cfg, 64, 92)
     emb = m.get_embeddings(toks)
     done = 0
@@ -1096,7 +1086,7 @@ def test_classifier_tags_survive_2047_layers_only_steps(L, monkeypatch):
     e2 = orc.get_embeddings(toks[:63])
     assert orc.fill_kv_cache(e2, 1) == 64                     # (the fills rewrite the same rows with the same values: one suffices here)
     lo = orc.forward(int(first), 64)
-    assert m.forward_argmax(int(first), 64) == int(O.lib().lmrs_ref_argmax(lo.ctypes.data, lo.size))
+    assert m.forward_argmax(int(first), 64) == ref_argmax(lo)
     assert_bit_equal(m.forward(int(first), 64), lo, "logits after the 2047 layers-only steps")
 
 
@@ -1395,7 +1385,7 @@ def test_chat_program_text_in_text_out(L, tmp_path, temperature):
         token = prompt[i] if i < len(prompt) else nxt
         lg = orc.forward(int(token), pos); pos += 1
         if temperature == 0.0:
-            nxt = int(O.lib().lmrs_ref_argmax(lg.ctypes.data, lg.size))
+            nxt = ref_argmax(lg)
         else:                                                   # every call sorts the candidate vector (stale entries stay): run them all, as chat.rs does
             nxt = smp.sample([np.float32(v) for v in lg])
         if i >= len(prompt) - 1 and nxt != tk.eos:

@@ -1,6 +1,6 @@
 """lmrs_prefill_tokens / lmrs_tokens_path (include/lmrs_hip.h) and Gemma-2 on the batched token path: a run of token ids leaves the K/V rows
 that one Transformer::forward per token leaves (transformer.rs:316-384), whichever path the library takes.  The reference is the CPU oracle's
-SEQUENTIAL forward; every comparison is on uint32 views, except log-probabilities (the rule of tests/test_score.py: one f32 ulp of a float64
+SEQUENTIAL forward; every comparison is on uint32 views, except log-probabilities (the rule of tests/parity_rules.py: one f32 ulp of a float64
 log-softmax of the oracle's logits, the sum to 1e-9 relative)."""
 import ctypes
 import dataclasses
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from parity_rules import assert_bit_equal, bits, check_after, check_kv_rows, check_scores, oracle_rows
 from tools import synth_lmrs as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,59 +24,6 @@ gpu = pytest.mark.gpu
 def L():
     import lmrs_amd
     return lmrs_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bit_equal(a, b, what=""):
-    a = np.asarray(a); b = np.asarray(b)
-    assert a.shape == b.shape, f"{what}: shapes {a.shape} vs {b.shape}"
-    ne = np.flatnonzero(bits(a) != bits(b))
-    assert ne.size == 0, f"{what}: {ne.size}/{a.size} elements differ, first at {ne[:5]}: {a.ravel()[ne[:5]]} vs {b.ravel()[ne[:5]]}"
-
-
-def oracle_rows(orc, toks, start):
-    return np.stack([orc.forward(int(t), start + i).copy() for i, t in enumerate(toks)])
-
-
-def ref_argmax(row):
-    row = np.ascontiguousarray(row)
-    return int(O.lib().lmrs_ref_argmax(row.ctypes.data, row.size))
-
-
-def check_scores(got, rows, toks, what):
-    """(logprobs, argmax, sum) of the library against the oracle's logits: the argmax of lmrs_ref_argmax, log-probabilities within one
-    f32 ulp of a float64 log-softmax (m = the f32 maximum, the sum over every logit), their double sum to 1e-9 relative."""
-    lp, am, s = got
-    n = len(toks)
-    assert lp.shape == (n - 1,) and am.shape == (n,)
-    assert am.tolist() == [ref_argmax(r) for r in rows], f"{what}: argmax"
-    x = rows.astype(np.float64)
-    m = rows.max(axis=1).astype(np.float64)
-    lse = np.log(np.exp(x - m[:, None]).sum(axis=1))
-    want = x[np.arange(n - 1), np.asarray(toks[1:], np.int64)] - m[:-1] - lse[:-1]
-    w32 = want.astype(np.float32)
-    assert np.all(np.abs(lp.astype(np.float64) - w32.astype(np.float64)) <= np.spacing(np.abs(w32)).astype(np.float64)), \
-        f"{what}: log-probabilities more than 1 ulp from float64, worst {np.max(np.abs(lp - w32))}"
-    assert abs(s - want.sum()) <= 1e-9 * abs(want.sum()), f"{what}: sum {s} vs {want.sum()}"
-
-
-def check_rows(m, orc, positions, what):
-    nl = orc.args.n_layers
-    for layer in (0, nl - 1):
-        for p in positions:
-            for which in (0, 1):
-                assert_bit_equal(m.kv_row(which, layer, p), orc.kv_row(which, layer, p), f"{what}: {'kv'[which]} row layer {layer} pos {p}")
-
-
-def check_after(m, orc, n, start, what):
-    """K/V rows of the first and last layer at three positions, and one forward at start + n, against the oracle's."""
-    check_rows(m, orc, sorted({start, start + n // 2, start + n - 1}), what)
-    if start + n < orc.args.seq_len:
-        t = 7 % orc.args.vocab_size
-        assert_bit_equal(m.forward(t, start + n), orc.forward(t, start + n), f"{what}: forward at {start + n} after the call")
 
 
 def _random_cfg():
@@ -179,7 +127,7 @@ def test_gemma_window_is_tested_per_query_in_a_batched_pass():
     want = oracle_rows(orc, toks[n0:], n0)
     print(f"\noracle: {n0 + n1} sequential steps in {time.time() - t0:.1f} s")
     assert_bit_equal(got, want, "logits of the 80 positions 4080 .. 4159")
-    check_rows(m, orc, [0, 2040, n0 - 1, n0, n0 + 17, n0 + 18, n0 + 40, n0 + n1 - 1], "window")
+    check_kv_rows(m, orc, [0, 2040, n0 - 1, n0, n0 + 17, n0 + 18, n0 + 40, n0 + n1 - 1], "window")
     # teeth
     for p in range(63):
         orc.forward(int((toks[p] + 1) % cfg.vocab_size), p)
@@ -205,13 +153,13 @@ def test_gemma_fill_kv_cache_keeps_the_batched_call_semantics(L, order):
         a = m.get_embeddings(ta); b = orc.get_embeddings(ta)
         assert m.fill_kv_cache(a, pos) == orc.fill_kv_cache(b, pos) == pos + 50
         assert_bit_equal(a, b, f"{order}: residual stream after fill_kv_cache at {pos}")
-        check_rows(m, orc, [pos, pos + 25, pos + 49], f"{order}: fill_kv_cache at {pos}")
+        check_kv_rows(m, orc, [pos, pos + 25, pos + 49], f"{order}: fill_kv_cache at {pos}")
 
     def prefill(pos):
         assert m.prefill_tokens(tb, pos) == pos + 60
         for i, t in enumerate(tb):
             orc.forward(int(t), pos + i)
-        check_rows(m, orc, [pos, pos + 30, pos + 59], f"{order}: prefill_tokens at {pos}")
+        check_kv_rows(m, orc, [pos, pos + 30, pos + 59], f"{order}: prefill_tokens at {pos}")
 
     if order == "prefill_first":
         prefill(0); fill(60)
@@ -266,7 +214,7 @@ def test_gemma_2b_q4_prefill_tokens_at_full_size(L):
     orc = O.Oracle(img)
     want = orc.generate_greedy(toks, 8, 0)
     assert ids.tolist() == want.tolist()
-    check_rows(m, orc, [0, 150, 299], "gemma-2-2b")
+    check_kv_rows(m, orc, [0, 150, 299], "gemma-2-2b")
 
 
 # ------------------------------------------------------------------ 8. the chat program

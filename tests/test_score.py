@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from parity_rules import assert_bit_equal, check_after, check_scores, oracle_rows
 from tools import synth_lmrs as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,58 +22,6 @@ gpu = pytest.mark.gpu
 def L():
     import lmrs_amd
     return lmrs_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bit_equal(a, b, what=""):
-    a = np.asarray(a); b = np.asarray(b)
-    assert a.shape == b.shape, f"{what}: shapes {a.shape} vs {b.shape}"
-    ne = np.flatnonzero(bits(a) != bits(b))
-    assert ne.size == 0, f"{what}: {ne.size}/{a.size} elements differ, first at {ne[:5]}: {a.ravel()[ne[:5]]} vs {b.ravel()[ne[:5]]}"
-
-
-def oracle_rows(orc, toks, start):
-    return np.stack([orc.forward(int(t), start + i).copy() for i, t in enumerate(toks)])
-
-
-def ref_argmax(row):
-    row = np.ascontiguousarray(row)
-    return int(O.lib().lmrs_ref_argmax(row.ctypes.data, row.size))
-
-
-def check_scores(got, rows, toks, what):
-    """(logprobs, argmax, sum) of the library against the oracle's logits: the argmax of lmrs_ref_argmax, log-probabilities within one
-    f32 ulp of a float64 log-softmax (m = the f32 maximum, the sum over every logit), their double sum to 1e-9 relative."""
-    lp, am, s = got
-    n = len(toks)
-    assert lp.shape == (n - 1,) and am.shape == (n,)
-    assert am.tolist() == [ref_argmax(r) for r in rows], f"{what}: argmax"
-    x = rows.astype(np.float64)
-    m = rows.max(axis=1).astype(np.float64)
-    lse = np.log(np.exp(x - m[:, None]).sum(axis=1))
-    want = x[np.arange(n - 1), np.asarray(toks[1:], np.int64)] - m[:-1] - lse[:-1]
-    w32 = want.astype(np.float32)
-    assert np.all(np.abs(lp.astype(np.float64) - w32.astype(np.float64)) <= np.spacing(np.abs(w32)).astype(np.float64)), \
-        f"{what}: log-probabilities more than 1 ulp from float64, worst {np.max(np.abs(lp - w32))}"
-    if n > 1:
-        assert abs(s - want.sum()) <= 1e-9 * abs(want.sum()), f"{what}: sum {s} vs {want.sum()}"
-    else:
-        assert s == 0.0
-
-
-def check_after(m, orc, toks, start, what):
-    """K/V rows of the first and last layer at three positions, and one forward at start + n, against the oracle's."""
-    n = len(toks); nl = orc.args.n_layers
-    for layer in (0, nl - 1):
-        for p in sorted({start, start + n // 2, start + n - 1}):
-            for which in (0, 1):
-                assert_bit_equal(m.kv_row(which, layer, p), orc.kv_row(which, layer, p), f"{what}: {'kv'[which]} row layer {layer} pos {p}")
-    if start + n < orc.args.seq_len:
-        t = 7 % orc.args.vocab_size
-        assert_bit_equal(m.forward(t, start + n), orc.forward(t, start + n), f"{what}: forward at {start + n} after the call")
 
 
 def _random_cfg():
@@ -103,7 +52,7 @@ def test_forward_tokens_matches_sequential_forward(L, cfg, q, n, start):
     got = m.forward_tokens(toks, start)
     want = oracle_rows(orc, toks, start)
     assert_bit_equal(got, want, f"{cfg} q{q} n={n}: logits of every position")
-    check_after(m, orc, toks, start, f"{cfg} q{q} n={n}")
+    check_after(m, orc, n, start, f"{cfg} q{q} n={n}")
 
 
 SCORE_CASES = [("mini-llama", S.Q8_0, 70, 5), ("mini-llama", S.Q4_0, 70, 5), ("mini-phi", S.Q8_0, 140, 0), ("mini-llama-v4102", S.Q8_0, 40, 2),
@@ -119,7 +68,7 @@ def test_score_tokens_matches_the_oracle(L, cfg, q, n, start):
     got = m.score(toks, start)
     rows = oracle_rows(orc, toks, start)
     check_scores(got, rows, toks, f"{cfg} q{q} n={n}")
-    check_after(m, orc, toks, start, f"{cfg} q{q} n={n}")
+    check_after(m, orc, n, start, f"{cfg} q{q} n={n}")
 
 
 @gpu

@@ -16,7 +16,7 @@ import pytest
 import numpy_ref as NR
 import oracle_lib as O
 import stress_models as SM
-from test_score import check_scores          # the rule for log-probabilities: one f32 ulp of a float64 log-softmax of the oracle's logits
+from parity_rules import assert_bit_equal, check_scores, ref_argmax
 from tools import synth_lmrs as S
 
 gpu = pytest.mark.gpu
@@ -35,22 +35,6 @@ def recipes_for(cfg, only=ALL):
 
 
 MATRIX = [(c, q, r) for c, q in CASES for r in recipes_for(c)] + [("mini-llama", S.Q_NONE, "peaked"), ("mini-llama", S.Q_NONE, "glu_extremes")]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bit_equal(a, b, what=""):
-    a = np.asarray(a); b = np.asarray(b)
-    assert a.shape == b.shape, f"{what}: shapes {a.shape} vs {b.shape}"
-    ne = np.flatnonzero(bits(a) != bits(b)) if a.dtype == np.float32 else np.flatnonzero(a != b)
-    assert ne.size == 0, f"{what}: {ne.size}/{a.size} elements differ, first at {ne[:5]}: {a.ravel()[ne[:5]]} vs {b.ravel()[ne[:5]]}"
-
-
-def ref_argmax(row):
-    row = np.ascontiguousarray(row)
-    return int(O.lib().lmrs_ref_argmax(row.ctypes.data, row.size))
 
 
 # ------------------------------------------------------------------ witnesses
@@ -314,7 +298,7 @@ TOKEN_MATRIX = [(c, q, r) for c, q in CASES for r in recipes_for(c, TOKEN_RECIPE
 @pytest.mark.parametrize("cfg,q,recipe", TOKEN_MATRIX)
 def test_token_entry_points(L, cfg, q, recipe):
     """forward_tokens, score_tokens and prefill_tokens over the decode run's tokens as ONE batched pass (asserted: lmrs_tokens_path, Gemma-2
-    included): logits of every position bit for bit, log-probabilities by test_score.py's rule, K/V rows and the forward that follows."""
+    included): logits of every position bit for bit, log-probabilities by parity_rules.py's rule, K/V rows and the forward that follows."""
     n = N_DECODE[cfg]
     img, c, toks, rows, kv, st = oracle_decode(cfg, q, recipe, n)
     check_witness(recipe, c, q, st, rows, n)

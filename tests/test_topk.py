@@ -1,7 +1,7 @@
 """lmrs_score_tokens_topk / lmrs_forward_topk / lmrs_op_topk (include/lmrs_hip.h): the k first next-token candidates of a position, selected on
 the device.  The reference is the CPU oracle's SEQUENTIAL forward (one call per token), its rows ranked on the host by rank_row below - a stable
 sort on (-value, index) with the NaN rules of the header - never a second call into the library.  Indices must be equal; log-probabilities
-follow tests/test_score.py's rule (one f32 ulp of a float64 log-softmax of the oracle's logits: check_scores itself on the results
+follow tests/parity_rules.py's rule (one f32 ulp of a float64 log-softmax of the oracle's logits: check_scores itself on the results
 lmrs_score_tokens also has, topk_rule - the same arithmetic over k columns instead of one target - on the rest)."""
 import ctypes
 import dataclasses
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-import test_score as TS                              # check_scores, oracle_rows, assert_bit_equal: the scoring tests' rules and reference
+from parity_rules import assert_bit_equal, assert_within_one_ulp, check_scores, log_softmax64, oracle_rows, ref_argmax
 from tools import synth_lmrs as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,12 +43,8 @@ def rank_row(row):
 
 def topk_rule(tl, ti, rows, what):
     """check_scores' rule for log-probabilities, over the k indices ti[t] of every row instead of one target"""
-    x = rows.astype(np.float64)
-    m = rows.max(axis=1).astype(np.float64)
-    lse = np.log(np.exp(x - m[:, None]).sum(axis=1))
-    w32 = (np.take_along_axis(x, ti.astype(np.int64), axis=1) - m[:, None] - lse[:, None]).astype(np.float32)
-    assert np.all(np.abs(tl.astype(np.float64) - w32.astype(np.float64)) <= np.spacing(np.abs(w32)).astype(np.float64)), \
-        f"{what}: top-k log-probabilities more than 1 ulp from float64, worst {np.max(np.abs(tl - w32))}"
+    x, m, lse = log_softmax64(rows)
+    assert_within_one_ulp(tl, np.take_along_axis(x, ti.astype(np.int64), axis=1) - m[:, None] - lse[:, None], f"{what}: top-k log-probabilities")
 
 
 def guided_tokens(orc, cfg, n, start, seed, picks=(0, 2, None, 7, 300, 1, None, 40)):
@@ -68,9 +64,9 @@ def check_topk(L, img, got, rows, toks, start, k, what, inside_min=0):
     lp, am, s, ti, tl, rk = got
     n = len(toks)
     assert ti.shape == (n, k) and tl.shape == (n, k) and rk.shape == (n - 1,)
-    TS.check_scores((lp, am, s), rows, toks, what)
+    check_scores((lp, am, s), rows, toks, what)
     plain = L.Transformer(img).score(toks, start)
-    TS.assert_bit_equal(lp, plain[0], f"{what}: logprobs against score()")
+    assert_bit_equal(lp, plain[0], f"{what}: logprobs against score()")
     assert am.tolist() == plain[1].tolist() and s == plain[2], f"{what}: argmax / sum against score()"
     orders = [rank_row(r) for r in rows]
     want = np.stack([o[:k] for o in orders])
@@ -82,7 +78,7 @@ def check_topk(L, img, got, rows, toks, start, k, what, inside_min=0):
     assert rk.tolist() == want_rk.tolist(), f"{what}: target_rank"
     inside = np.flatnonzero(rk < k)
     assert inside.size >= inside_min, f"{what}: {inside.size} targets inside the top {k}"
-    TS.assert_bit_equal(tl[inside, rk[inside]], lp[inside], f"{what}: the target's entry against logprobs")
+    assert_bit_equal(tl[inside, rk[inside]], lp[inside], f"{what}: the target's entry against logprobs")
     return orders
 
 
@@ -141,7 +137,7 @@ def test_rank_row_agrees_with_the_reference_argmax_at_rank_0():
     for r in rows:
         o = rank_row(r)
         assert sorted(o.tolist()) == list(range(r.size))
-        assert int(o[0]) == TS.ref_argmax(r)
+        assert int(o[0]) == ref_argmax(r)
     o = rank_row(rows[3])
     assert o[0] == 200 and o[-2:].tolist() == [5, 9]
     assert rank_row(rows[2])[0] == 0 and rank_row(rows[4]).tolist() == [0, 1, 3, 2]
@@ -221,7 +217,7 @@ def test_zero_tail_on_the_token_path(L):
     img = S.build_image(cfg, S.Q8_0, seed=61, transform=_sunk_logits)
     toks = S.prompt_tokens(cfg, 20, 61)
     m = L.Transformer(img)
-    rows = TS.oracle_rows(O.Oracle(img), toks, 0)
+    rows = oracle_rows(O.Oracle(img), toks, 0)
     assert np.isfinite(rows).all() and not rows[:, 4100:].any()
     kth = -np.sort(-rows, axis=1)[:, k - 1]
     sunk = np.flatnonzero(kth <= 0)
@@ -280,9 +276,9 @@ def test_a_row_does_not_depend_on_the_call_around_it(L):
     m = L.Transformer(img)
     a, b = m.score_topk(toks[:25], 20, 0), m.score_topk(toks[25:], 20, 25)
     assert (np.concatenate([a[3], b[3]]) == one[3]).all()
-    TS.assert_bit_equal(np.concatenate([a[4], b[4]]), one[4], "top-k log-probabilities, one call against 25 + 15")
+    assert_bit_equal(np.concatenate([a[4], b[4]]), one[4], "top-k log-probabilities, one call against 25 + 15")
     assert np.concatenate([a[5], b[5]]).tolist() == np.delete(one[5], 24).tolist()
-    rows = TS.oracle_rows(O.Oracle(img), toks, 0)
+    rows = oracle_rows(O.Oracle(img), toks, 0)
     assert (one[3] == np.stack([rank_row(r)[:20] for r in rows])).all()
 
 
@@ -299,7 +295,7 @@ def test_score_topk_errors_leave_the_context_usable(L):
     with pytest.raises(L.LmrsError, match="k = 200 exceeds vocab_size = 128"):
         ms.forward_topk(1, 0, 200)
     stoks = S.prompt_tokens(small, 9, 3)
-    check_topk(L, simg, ms.score_topk(stoks, 128, 0), TS.oracle_rows(O.Oracle(simg), stoks, 0), stoks, 0, 128, "k = vocab_size = 128")
+    check_topk(L, simg, ms.score_topk(stoks, 128, 0), oracle_rows(O.Oracle(simg), stoks, 0), stoks, 0, 128, "k = vocab_size = 128")
     with pytest.raises(L.LmrsError, match="outside 1 .. 256"):
         m.score_topk(toks, 0)
     bad = toks.copy(); bad[5] = m.args.vocab_size
@@ -310,7 +306,7 @@ def test_score_topk_errors_leave_the_context_usable(L):
     rc = L.lib().lmrs_score_tokens_topk(grp._arr[0], toks.ctypes.data, toks.size, 0, 4, None, None, None, ti.ctypes.data, tl.ctypes.data, None)
     assert rc != 0 and "single-GPU" in L.lib().lmrs_last_error().decode()
     grp.close()
-    rows = TS.oracle_rows(O.Oracle(img), toks, 0)
+    rows = oracle_rows(O.Oracle(img), toks, 0)
     check_topk(L, img, m.score_topk(toks, 4, 0), rows, toks, 0, 4, "after the errors")
     check_topk(L, img, m.score_topk(toks, 100, 0), rows, toks, 0, 100, "a larger k on the same context")
 
@@ -328,8 +324,8 @@ def test_forward_topk_matches_the_ranked_oracle_logits(L, q):
         row = orc.forward(int(toks[pos]), pos).copy()
         want = rank_row(row)[:k]
         assert (idx == want).all(), f"step {pos}: {idx[:8]} vs {want[:8]}"
-        TS.assert_bit_equal(val, row[want], f"step {pos}: raw logits of the top {k}")
-    TS.assert_bit_equal(m.forward(int(toks[12]), 12), orc.forward(int(toks[12]), 12), "forward after 12 forward_topk steps")
+        assert_bit_equal(val, row[want], f"step {pos}: raw logits of the top {k}")
+    assert_bit_equal(m.forward(int(toks[12]), 12), orc.forward(int(toks[12]), 12), "forward after 12 forward_topk steps")
 
 
 @gpu
@@ -367,5 +363,5 @@ def test_ordering_rule_on_hand_made_rows(L, what, row, written, k):
     idx, val = L.topk(row, k, written)
     want = rank_row(full)[:k]
     assert (idx == want).all(), f"{what}: {idx[:10]} vs {want[:10]}"
-    TS.assert_bit_equal(val, full[want], what)
-    assert int(idx[0]) == TS.ref_argmax(full), what
+    assert_bit_equal(val, full[want], what)
+    assert int(idx[0]) == ref_argmax(full), what

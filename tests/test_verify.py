@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from parity_rules import assert_bit_equal, check_kv_rows, check_scores, oracle_rows, ref_argmax, run_positions
 from tools import synth_lmrs as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,33 +22,9 @@ def L():
     return lmrs_amd
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bit_equal(a, b, what=""):
-    a = np.asarray(a); b = np.asarray(b)
-    assert a.shape == b.shape, f"{what}: shapes {a.shape} vs {b.shape}"
-    ne = np.flatnonzero(bits(a) != bits(b))
-    assert ne.size == 0, f"{what}: {ne.size}/{a.size} elements differ, first at {ne[:5]}: {a.ravel()[ne[:5]]} vs {b.ravel()[ne[:5]]}"
-
-
-def ref_argmax(row):
-    row = np.ascontiguousarray(row)
-    return int(O.lib().lmrs_ref_argmax(row.ctypes.data, row.size))
-
-
 def oracle_argmax(orc, toks, start):
     """sample_argmax of the oracle's sequential forward for toks[i] at start + i"""
     return [ref_argmax(orc.forward(int(t), start + i)) for i, t in enumerate(toks)]
-
-
-def check_kv(m, orc, start, n, what):
-    nl = orc.args.n_layers
-    for layer in (0, nl - 1):
-        for p in sorted({start, start + n // 2, start + n - 1}):
-            for which in (0, 1):
-                assert_bit_equal(m.kv_row(which, layer, p), orc.kv_row(which, layer, p), f"{what}: {'kv'[which]} row layer {layer} pos {p}")
 
 
 def check_forward_after(m, orc, pos, what):
@@ -158,7 +135,7 @@ def _verify_patterns(L, m, orc, start, what, ns=NS):
         assert want == G[1:n + 1]
         am, acc = m.verify_tokens(toks, start)
         assert am.tolist() == want and acc == n - 1, f"{what} n {n}: true continuation"
-        check_kv(m, orc, start, n, f"{what} n {n} true")
+        check_kv_rows(m, orc, run_positions(start, n), f"{what} n {n} true")
         check_forward_after(m, orc, start + n, f"{what} n {n} true")
         # draft j corrupted: the drafts before it accepted, the argmax of every position still forward's for the tokens given
         for j in sorted({0, n - 2}):
@@ -166,7 +143,7 @@ def _verify_patterns(L, m, orc, start, what, ns=NS):
             want = oracle_argmax(orc, bad, start)
             am, acc = m.verify_tokens(bad, start)
             assert am.tolist() == want and acc == j, f"{what} n {n}: draft {j} corrupted"
-            check_kv(m, orc, start, n, f"{what} n {n} corrupt {j}")
+            check_kv_rows(m, orc, run_positions(start, n), f"{what} n {n} corrupt {j}")
             # the next pass: from start + n_accept + 1 with argmax[n_accept], over the stale rows of the rejected drafts
             assert int(am[acc]) == G[j + 1]
             nxt = np.array(G[j + 1:j + 1 + n], np.uint32)
@@ -211,6 +188,58 @@ def test_the_token_run_rules_have_not_moved(L):
     assert m.tokens_path(4) is False and m.tokens_path(60) is True
     m.verify_tokens(S.prompt_tokens("mini-llama", 4, 1), 0)
     assert m.tokens_path(4) is False and m.tokens_path(60) is True
+
+
+@gpu
+@pytest.mark.parametrize("cfg,q", [("mini-llama", S.Q8_0), ("mini-gemma", S.Q4_0)])
+def test_token_entry_points_interleaved_on_one_context(L, cfg, q):
+    """Every token entry point on ONE context, each call starting where the one before it ended and judged by its own rule against the
+    oracle's sequential forward: passes of both forms (up to 16 tokens: skinny; more: tiled) and runs on both sides of the batch minimum of 8
+    follow each other, so a form or a state that outlived its call would show in the next one.  No forward between the calls: the K/V rows
+    are read back instead, and the single forward comes last."""
+    img = S.build_image(cfg, q, seed=67)
+    m = L.Transformer(img); orc = O.Oracle(img)
+    V = m.args.vocab_size
+    toks = S.prompt_tokens(cfg, 60, 67)
+    at = {"pos": 0}
+
+    def run(n, continuation=False):
+        """the next n tokens (or the oracle's own greedy continuation of the next one), their position, the oracle's logits rows for them"""
+        pos = at["pos"]; at["pos"] += n
+        t = np.array(_true_continuation(orc, toks[pos], pos, n), np.uint32) if continuation else toks[pos:pos + n].copy()
+        return t, pos, oracle_rows(orc, t, pos)
+
+    def verify(n, what, continuation=False):
+        t, pos, rows = run(n, continuation)
+        am, acc = m.verify_tokens(t, pos)
+        want = [ref_argmax(r) for r in rows]
+        want_acc = 0
+        while want_acc + 1 < n and int(t[want_acc + 1]) == want[want_acc]:
+            want_acc += 1
+        assert am.tolist() == want and acc == want_acc, f"{cfg} q{q} {what}"
+        assert not continuation or acc == n - 1
+        check_kv_rows(m, orc, run_positions(pos, n), f"{cfg} q{q} {what}")
+
+    verify(16, "1. verify_tokens of 16")
+    t, pos, rows = run(20)
+    check_scores(m.score(t, pos), rows, t, f"{cfg} q{q} 2. score of 20")
+    check_kv_rows(m, orc, run_positions(pos, 20), f"{cfg} q{q} 2. score of 20")
+    verify(5, "3. verify_tokens of 5", continuation=True)
+    t, pos, rows = run(9)
+    assert m.tokens_path(9) and m.prefill_tokens(t, pos) == pos + 9
+    check_kv_rows(m, orc, run_positions(pos, 9), f"{cfg} q{q} 4. prefill_tokens of 9")
+    t, pos, rows = run(3)
+    assert not m.tokens_path(3)
+    assert_bit_equal(m.forward_tokens(t, pos), rows, f"{cfg} q{q} 5. forward_tokens of 3")
+    check_kv_rows(m, orc, run_positions(pos, 3), f"{cfg} q{q} 5. forward_tokens of 3")
+    bad = toks[:12].copy(); bad[7] = V
+    with pytest.raises(L.LmrsError, match="token 7 out of range"):
+        m.score(bad, at["pos"])
+    verify(2, "7. verify_tokens of 2", continuation=True)
+    pos = at["pos"]
+    assert pos == 16 + 20 + 5 + 9 + 3 + 2
+    assert_bit_equal(m.forward(int(toks[pos]), pos), orc.forward(int(toks[pos]), pos), f"{cfg} q{q} 8. forward at {pos}")
+    check_kv_rows(m, orc, [0, 15, 16, 35, 36, 40, 41, 49, 50, 52, 53, 54, pos], f"{cfg} q{q}: the rows of every call at the end")
 
 
 # ---------------------------------------------------------------------------------------------- 4. generate_speculative
