@@ -228,6 +228,47 @@ int lmrs_draft_lookup(const uint32_t* hist, size_t n_hist, uint32_t ngram_max, u
 int lmrs_generate_speculative(lmrs_ctx* ctx, const uint32_t* prompt, size_t n_prompt, uint32_t n_new, uint32_t start_pos,
                               uint32_t max_draft, uint32_t ngram_max, uint32_t* out_tokens, uint32_t* stats4, double* seconds);
 
+/* ---- multi-sequence decode: up to 16 sequences a step over one copy of the weights (extensions, no reference counterpart) -------------------
+ * A batch is n_slots K/V caches beside the context's own; a step (lmrs_batch_forward) is ONE weight pass - the skinny form of lmrs_verify_tokens'
+ * pass - whose rows are tokens of DIFFERENT sequences, each at its own position over its own slot.  Every output is bit for bit what the same tokens
+ * give through lmrs_forward / lmrs_forward_argmax on a context that holds only that sequence (Gemma-2: rows scaled by sqrt(dim), the window per row,
+ * both soft caps).  The context's own cache is a 17th, private sequence: no batch call changes anything a call on ctx can observe, and batch and
+ * context calls may interleave freely.
+ * Errors (NULL arguments, n outside 1 .. 16, a slot >= n_slots, a slot twice in one call, a token >= vocab_size, pos (+ n_new - 1) >= seq_len,
+ * fork with n_pos > seq_len or src == dst) are reported before any device work and leave ctx and batch usable. */
+#define LMRS_BATCH_CTX 0xFFFFFFFFu   /* lmrs_batch_fork's src_slot: the context's own cache */
+typedef struct lmrs_batch lmrs_batch;
+
+/* n_slots KV caches (1 .. 16) beside ctx's own, same layout and seq_len, on ctx's device; ctx's weights,
+ * stream and scratch are shared (ctx and its batches are ONE not-thread-safe object; destroy batches first).
+ * Refused, each with its own message: sharded and group contexts; contexts without the batched pass for short runs (f32 files, other
+ * geometries, classifier rows that are no multiple of 16, LMRS_NO_BATCHED_PREFILL=1) - there is no token-by-token form.  Allocation is
+ * all or nothing; the message gives the bytes wanted (n_slots * 2 * n_layers * seq_len * kv_dim * 4). */
+int  lmrs_batch_create(lmrs_ctx* ctx, uint32_t n_slots, lmrs_batch** out);
+void lmrs_batch_destroy(lmrs_batch* b);
+
+/* == lmrs_prefill_tokens, into slot's cache: rows start_pos .. start_pos+n-1 as n forward calls leave them */
+int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n, uint32_t start_pos);
+
+/* rows [0, n_pos) of every layer, K and V: src -> dst (LMRS_BATCH_CTX as src = ctx's own cache): a shared
+ * system prompt or best-of-n prefilled once */
+int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_slot, uint32_t n_pos);
+
+/* ONE weight pass for n rows (1 .. 16), row i = Transformer::forward(tokens[i], pos[i]) (src/transformer.rs:316-384) on slot[i]'s cache +
+ * Sampler::sample_argmax (sampler.rs:29-41).  Slots distinct within a call, any order, any subset.
+ * argmax[i] (n); logits (may be NULL): n*vocab floats as lmrs_forward_tokens writes a row. */
+int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens,
+                       const uint32_t* pos, uint32_t* argmax, float* logits);
+
+/* n_new greedy steps for n rows, device-resident, one host sync at the end.
+ * out_tokens[i*n_new + j] = argmax after feeding row i's j-th token (the first is tokens[i] at pos[i]):
+ * per row lmrs_generate_greedy's out_tokens for a one-token prompt on that slot.  *seconds optional (HIP events). */
+int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens,
+                               const uint32_t* pos, uint32_t n_new, uint32_t* out_tokens, double* seconds);
+
+/* verification aid, as lmrs_debug_kv */
+int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out);
+
 const char* lmrs_last_error(void);
 
 /* ---- L2 free functions, for unit parity (host pointers in and out) ------------------

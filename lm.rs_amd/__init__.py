@@ -28,6 +28,8 @@ EXPORTS = [
     "lmrs_forward_argmax", "lmrs_get_embeddings", "lmrs_fill_kv_cache", "lmrs_generate_greedy", "lmrs_forward_tokens", "lmrs_score_tokens",
     "lmrs_prefill_tokens", "lmrs_tokens_path", "lmrs_score_tokens_topk", "lmrs_forward_topk", "lmrs_op_topk",
     "lmrs_verify_tokens", "lmrs_draft_lookup", "lmrs_generate_speculative", "lmrs_debug_gemm_skinny",
+    "lmrs_batch_create", "lmrs_batch_destroy", "lmrs_batch_prefill", "lmrs_batch_fork", "lmrs_batch_forward", "lmrs_batch_generate_greedy",
+    "lmrs_batch_debug_kv",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -101,6 +103,13 @@ def lib():
         L.lmrs_draft_lookup.argtypes = [vp, sz, u32, u32, vp, C.POINTER(u32)]
         L.lmrs_generate_speculative.argtypes = [vp, vp, sz, u32, u32, u32, u32, vp, vp, C.POINTER(C.c_double)]
         L.lmrs_debug_gemm_skinny.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, C.c_int]
+        L.lmrs_batch_create.argtypes = [vp, u32, C.POINTER(vp)]
+        L.lmrs_batch_destroy.argtypes = [vp]; L.lmrs_batch_destroy.restype = None
+        L.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
+        L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
+        L.lmrs_batch_forward.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.lmrs_batch_generate_greedy.argtypes = [vp, u32, vp, vp, vp, u32, vp, C.POINTER(C.c_double)]
+        L.lmrs_batch_debug_kv.argtypes = [vp, u32, C.c_int, u32, u32, vp]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.lmrs_op_matmul_q4.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz]
         L.lmrs_op_quantize.argtypes = [C.c_int, vp, vp, vp, sz, sz]
@@ -357,6 +366,70 @@ class Transformer:
         n, b = C.c_int(), C.c_double()
         _chk(lib().lmrs_step_info(self._h, pos, C.byref(n), C.byref(b)))
         return n.value, b.value
+
+
+BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BATCH_CTX)
+
+
+class Batch:
+    """n_slots (1 .. 16) more K/V caches beside a Transformer's own, stepped together: one pass over the weights serves one token of up to 16
+    DIFFERENT sequences, each at its own position (lmrs_batch_*).  Every result is bit for bit what forward / forward_argmax give on a model that
+    holds only that sequence.  The model's own cache is untouched by every call here; close the batch before the model."""
+
+    def __init__(self, model: Transformer, n_slots: int):
+        h = C.c_void_p()
+        _chk(lib().lmrs_batch_create(model._h, n_slots, C.byref(h)))
+        self._h, self.model, self.n_slots = h, model, n_slots
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.model, "_h", None):
+                lib().lmrs_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def prefill(self, slot: int, tokens, start_pos: int = 0) -> int:
+        """Transformer.prefill_tokens into `slot`'s cache -> start_pos + n (lmrs_batch_prefill)"""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        _chk(lib().lmrs_batch_prefill(self._h, slot, _p(t), t.size, start_pos))
+        return start_pos + t.size
+
+    def fork(self, src: int, dst: int, n_pos: int) -> None:
+        """K/V rows [0, n_pos) of slot `src` (BATCH_CTX: the model's own cache) -> slot `dst` (lmrs_batch_fork)"""
+        _chk(lib().lmrs_batch_fork(self._h, src, dst, n_pos))
+
+    @staticmethod
+    def _rows(slots, tokens, pos):
+        s, t, p = (np.ascontiguousarray(x, np.uint32).reshape(-1) for x in (slots, tokens, pos))
+        if not s.size == t.size == p.size:
+            raise LmrsError("slots, tokens and pos must have one entry per row")
+        return s, t, p
+
+    def forward(self, slots, tokens, pos, logits: bool = False):
+        """One pass: row i = forward(tokens[i], pos[i]) on slot slots[i] -> argmax uint32 [n] (and the logits float32 [n, vocab_size] if asked)
+        (lmrs_batch_forward)"""
+        s, t, p = self._rows(slots, tokens, pos)
+        am = np.empty(s.size, np.uint32)
+        lg = np.empty((s.size, self.model.args.vocab_size), np.float32) if logits else None
+        _chk(lib().lmrs_batch_forward(self._h, s.size, _p(s), _p(t), _p(p), _p(am), _p(lg) if logits else None))
+        return (am, lg) if logits else am
+
+    def generate_greedy(self, slots, tokens, pos, n_new: int, timing: bool = False):
+        """n_new greedy steps of every row on the device -> uint32 [n, n_new]: row i = Transformer.generate_greedy([tokens[i]], n_new, pos[i]) on its
+        slot (and device seconds if timing) (lmrs_batch_generate_greedy)"""
+        s, t, p = self._rows(slots, tokens, pos)
+        out = np.zeros((s.size, n_new), np.uint32); sec = C.c_double()
+        _chk(lib().lmrs_batch_generate_greedy(self._h, s.size, _p(s), _p(t), _p(p), n_new, _p(out), C.byref(sec)))
+        return (out, sec.value) if timing else out
+
+    def kv_row(self, slot: int, which: int, layer: int, pos: int) -> np.ndarray:
+        """Transformer.kv_row of `slot`'s cache (lmrs_batch_debug_kv)"""
+        out = np.empty(self.model.args.n_kv_heads * self.model.args.head_size, np.float32)
+        _chk(lib().lmrs_batch_debug_kv(self._h, slot, which, layer, pos, _p(out)))
+        return out
+
+    debug_kv = kv_row
 
 
 def shard_plan(args: TransformerArgs, rank: int, world: int) -> dict:

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -172,7 +173,10 @@ size_t prefill_tp_block(size_t n_l) { return pad256((size_t)kPrefillTokens * n_l
 // 256-key chunks (then qa_mode is 0: the merged launch has no split form).  A value handed down to the enqueue functions, never context state.
 struct StepForm { int qa_mode = 0, split_chunks = 0; };
 // The form of one batched pass, a value in the same way: skinny = every GEMM of it, the layers' and the classifier's, in the 16-token form (GemmArgs::skinny)
-struct PassForm { bool skinny = false; };
+// rows: the pass is lmrs_batch_forward's - row r is one token of its own sequence (the device row table, lmrs_kernels.h; max_T = the deepest row's
+// position + 1); null: m consecutive positions of one sequence, as always.  k_cache / v_cache: the caches the pass reads and writes - a batch's (with
+// rows: the base the table's offsets count from); null: the context's own
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; };
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1378,7 +1382,7 @@ static int prefill_attention(lmrs_ctx* c, AttnArgs& t, int m, int p0) {
             return 0;
         }
     }
-    HIP_OK(launch_rope_rows(c->pf_q, c->pf_k, c->k_cache, c->rope, t.n_heads, t.n_kv_heads, t.head_size, t.seq_len, t.layer, p0, m, c->stream));
+    HIP_OK(launch_rope_rows(c->pf_q, c->pf_k, t.k_cache, c->rope, t.n_heads, t.n_kv_heads, t.head_size, t.seq_len, t.layer, p0, m, c->stream));
     HIP_OK(launch_attention_rows(t, p0, m, c->stream));
     return 0;
 }
@@ -1400,6 +1404,7 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
     const int att_full = tp ? c->att_full : att, hid_l = tp ? c->hid_l : hid;
     const bool gemma = a.model_type == LMRS_GEMMA;
     const float eps = a.rms_norm_eps;
+    float* const k_cache = form.k_cache ? form.k_cache : c->k_cache; float* const v_cache = form.v_cache ? form.v_cache : c->v_cache;
     // scale layouts of this pass: from 48 tokens on every GEMM is a ring kernel, which takes TRANSPOSED scales ([group][row]: GemmArgs::ws_ld / xs_ld) -
     // the weights' transposed copies (prefill_alloc) and activation scales written that way by their producers, leading dimension kPrefillTokens
     const bool trs = m >= 48 && c->layers[0].sqkvT != nullptr;
@@ -1435,15 +1440,20 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
         // [x += rmsnorm(previous ffn out)] rmsnorm + quantize | Wqkv | q, raw k, v rows -> cache      (transformer.rs:409-431)
         if (gemma && l > 0) HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, c->pf_t, c->layers[l - 1].rms_post_ffn, eps, 1, 2, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
         else HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, nullptr, nullptr, eps, gemma, 1, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
-        g.wq = L.wqkv; g.ws = trs ? L.sqkvT : L.sqkv; g.ws_ld = trs ? att + 2 * kv : 0; g.n = dim; g.o = att + 2 * kv; g.out = c->pf_q; g.k_raw = c->pf_k; g.v_cache = c->v_cache;
+        g.wq = L.wqkv; g.ws = trs ? L.sqkvT : L.sqkv; g.ws_ld = trs ? att + 2 * kv : 0; g.n = dim; g.o = att + 2 * kv; g.out = c->pf_q; g.k_raw = c->pf_k; g.v_cache = v_cache;
         g.att_dim = att; g.kv_dim = kv; g.seq_len = (int)a.seq_len; g.layer = (int)l; g.pos0 = p0;
-        HIP_OK(launch_gemm_q8(g, EPI_QKV, c->stream));
+        // (a row table: the rows' positions are not consecutive - q | raw k | v stay one [m][att + 2 kv] block in pf_q, plain stores as EPI_QKV's)
+        HIP_OK(launch_gemm_q8(g, form.rows ? EPI_STORE : EPI_QKV, c->stream));
         // RoPE, keys into the cache; attention (this shard's heads)                    (:443-544)
         AttnArgs t{};
-        t.q = c->pf_q; t.k_raw = nullptr; t.k_cache = c->k_cache; t.v_cache = c->v_cache; t.rope = c->rope; t.out = c->pf_ao;
+        t.q = c->pf_q; t.k_raw = nullptr; t.k_cache = k_cache; t.v_cache = v_cache; t.rope = c->rope; t.out = c->pf_ao;
         t.n_heads = att / hs; t.n_kv_heads = kv / hs; t.head_size = hs; t.seq_len = (int)a.seq_len; t.layer = (int)l;
         t.gemma = gemma; t.st = c->st;
-        if (prefill_attention(c, t, m, p0)) return -1;
+        if (form.rows) {
+            // every row at its own position in its own slot: rotation, K / V rows into the slots, one attention workgroup per (head, row)
+            HIP_OK(launch_rope_scatter_rows(c->pf_q, k_cache, v_cache, c->rope, form.rows, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
+            HIP_OK(launch_attention_table(t, form.rows, m, form.max_T, c->stream));
+        } else if (prefill_attention(c, t, m, p0)) return -1;
         // quantize | Wo | x += ... (Gemma: -> pf_t)                                     (:550-576)
         if (tp) { if (all_gather(c->pf_ao, att, c->pfx_att, c->pfb_att)) return -1; }
         else HIP_OK(launch_rows_prologue(c->pf_ao, nullptr, nullptr, nullptr, 0.f, 0, 0, q4, att, m, c->pf_xq, c->pf_xs, c->stream, xld));
@@ -1583,16 +1593,16 @@ static int stage_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n, uint32_t 
     HIP_OK(hipSetDevice(c->device));
     return upload_tokens(c, tokens, n, start_pos);
 }
-static int token_rows(lmrs_ctx* c, uint32_t pos, int m) {        // embedding rows of c->tokens[pos .. pos + m) -> pf_x, as forward builds them
+static int token_rows(lmrs_ctx* c, const uint32_t* tokens, int m) {        // embedding rows of the device tokens[0 .. m) -> pf_x, as forward builds them
     const float scale = c->args.model_type == LMRS_GEMMA ? sqrtf((float)c->args.dim) : 0.0f;
-    HIP_OK(launch_dequant_rows(c->emb_q, c->emb_s, c->q4, c->tokens + pos, m, (int)c->args.dim, c->pf_x, c->stream, scale));
+    HIP_OK(launch_dequant_rows(c->emb_q, c->emb_s, c->q4, tokens, m, (int)c->args.dim, c->pf_x, c->stream, scale));
     return 0;
 }
 // K/V rows start_pos .. start_pos + n - 1 from c->tokens; the caller sets the state that follows (the pass's own: only Gemma's kernels read one)
 static int prefill_token_run(lmrs_ctx* c, uint32_t start_pos, size_t n) {
     if (prefill_alloc(c)) return -1;
     if (c->args.model_type == LMRS_GEMMA && set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
-    return prefill_chunks(c, PassForm{}, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); }, [](size_t, int) { return 0; });
+    return prefill_chunks(c, PassForm{}, start_pos, n, [&](size_t i0, int m) { return token_rows(c, c->tokens + start_pos + i0, m); }, [](size_t, int) { return 0; });
 }
 // The decode step per token for n GIVEN tokens, already in c->tokens: prompt_end = start_pos + n makes every step embed the next given token instead
 // of its own result (lmrs_generate_greedy's prompt phase); per_step(t) is enqueued behind step t, whose logits are in c->logits then
@@ -1725,12 +1735,13 @@ static HostScores host_scores(const lmrs_ctx* c) { return {reinterpret_cast<doub
 // What becomes of the logits rows of a run of n tokens in c->tokens[start_pos ..).  out_logits != null: they go to the host as they are
 // (lmrs_forward_tokens); else the reduction of every row - the next token's log-probability to c->sc_lp, sample_argmax to c->sc_idx - and with k the
 // selection behind it (c->tk_idx / tk_val / tk_rank)
-struct RowSink { uint32_t start_pos; size_t n; float* out_logits; uint32_t k; };
+// targets: row r's next token (c->tokens) is the target of its log-probability; false: the rows are not a run (a row table) - sample_argmax only
+struct RowSink { uint32_t start_pos; size_t n; float* out_logits; uint32_t k; bool targets = true; };
 
 // rows r0 .. r0 + m - 1 of the run, ld columns written at row stride ld (the rest up to vocab_size is the classifier's zero tail)
 static int reduce_rows(lmrs_ctx* c, const RowSink& to, const float* rows, int ld, int m, size_t r0) {
     const int V = (int)c->args.vocab_size;
-    ScoreArgs s{rows, ld, ld, V, m, c->tokens + to.start_pos + r0 + 1, (int)std::max<long long>(0, (long long)to.n - 1 - (long long)r0),
+    ScoreArgs s{rows, ld, ld, V, m, c->tokens + to.start_pos + r0 + 1, to.targets ? (int)std::max<long long>(0, (long long)to.n - 1 - (long long)r0) : 0,
                 c->sc_part, c->sc_lp + r0, c->sc_idx + r0};
     HIP_OK(launch_score_rows(s, c->stream));
     if (!to.k) return 0;
@@ -1776,10 +1787,12 @@ static int run_tokens(lmrs_ctx* c, const RowSink& to, PassForm form, bool batche
     const size_t n = to.n;
     if (batched) {
         if (prefill_alloc(c)) return -1;
-        if (set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
-        if (prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, start_pos + (uint32_t)i0, m); },
+        // (a row table: the positions live in the table and a call may enqueue many passes - its caller sets the one state, batch_state)
+        if (!form.rows && set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
+        // (a row table: its token column is the run, n <= kRowTableMax rows - one chunk)
+        if (prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, form.rows ? form.rows->tok : c->tokens + start_pos + i0, m); },
                            [&](size_t i0, int m) { return classify_rows(c, form, to, i0, m); })) return -1;
-        return set_state(c, start_pos + (uint32_t)n, 0);
+        return form.rows ? 0 : set_state(c, start_pos + (uint32_t)n, 0);
     }
     const size_t V = c->args.vocab_size;
     size_t r0 = 0;                                       // first position held in the logits block (forward_tokens)
@@ -1965,6 +1978,200 @@ extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, si
 }
 
 
+// ------------------------------------------------------------------ multi-sequence decode: up to 16 sequences a step over the context's weights
+// (no reference counterpart: per row Transformer::forward + sample_argmax on a cache of its own, value for value).  A batch is n_slots more K/V
+// caches of the context's layout; a step is run_tokens' batched arm, skinny, with a row table (PassForm::rows) - the qkv rows stay in scratch, one
+// launch rotates them and scatters K / V into the rows' slots, and attention_rows_kernel's workgroups take slot and position from the table.
+static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out);   // (with lmrs_debug_kv below)
+struct lmrs_batch {
+    lmrs_ctx* c = nullptr; uint32_t n_slots = 0;
+    float* kv = nullptr; size_t slot_floats = 0;        // [n_slots][K cache | V cache], slot_floats floats each: one allocation
+    RowTable *tab = nullptr, *h_tab = nullptr;          // the pass's row table and its pinned source
+    uint32_t *tokens = nullptr;                         // a prefill's token run (seq_len)
+    uint32_t *out = nullptr, *h_out = nullptr;          // generate_greedy: [n_new][n] results of the passes, and their pinned copy (seq_len x 16)
+    float* k_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->k_cache : kv + (size_t)slot * 2 * slot_floats; }
+    float* v_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->v_cache : kv + (size_t)slot * 2 * slot_floats + slot_floats; }
+};
+
+extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->c->device);
+    (void)hipStreamSynchronize(b->c->stream);
+    for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out}) if (p) (void)hipFree(p);
+    if (b->h_tab) (void)hipHostFree(b->h_tab);
+    if (b->h_out) (void)hipHostFree(b->h_out);
+    delete b;
+}
+
+extern "C" int lmrs_batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out) {
+    if (!c || !out) return fail("NULL argument");
+    *out = nullptr;
+    if (n_slots < 1 || n_slots > (uint32_t)kRowTableMax) return fail("lmrs_batch_create: n_slots = " + std::to_string(n_slots) + " is outside 1 .. " + std::to_string(kRowTableMax));
+    const lmrs_args& a = c->args;
+    // the refusals, one message each: there is no token-by-token form of a batch step (the decode graphs' cache pointers are baked at capture)
+    if (c->world > 1 && !c->comm && !c->p2p) return fail("lmrs_batch_create: members of a lock-step shard group (lmrs_group_create) are not supported");
+    if (c->world > 1 || c->comm || c->p2p) return fail("lmrs_batch_create: sharded contexts (lmrs_create_sharded) are not supported");
+    if (c->f32) return fail("lmrs_batch_create: unquantised (f32) files have no batched pass");
+    if (c->sw.no_batched_prefill) return fail("lmrs_batch_create: the batched pass is switched off (LMRS_NO_BATCHED_PREFILL=1)");
+    if (!prefill_batched_ok(c)) return fail("lmrs_batch_create: the batched pass is not built for this model's geometry");
+    if (cls_rows(c) % 16) return fail("lmrs_batch_create: " + std::to_string(cls_rows(c)) + " classifier rows are not a multiple of 16");
+    if (!score_batched_ok(c, 2)) return fail("lmrs_batch_create: this context has no batched pass for short runs");
+    HIP_OK(hipSetDevice(c->device));
+    if (prefill_alloc(c) || score_alloc(c, true)) return -1;
+    if (c->sc_rows < kRowTableMax) return fail("lmrs_batch_create: the logits block holds fewer than " + std::to_string(kRowTableMax) + " rows of this vocabulary");
+    lmrs_batch* b = new lmrs_batch;
+    b->c = c; b->n_slots = n_slots; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
+    const size_t bytes = (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&b->kv), bytes) == hipSuccess;                         // all or nothing: one allocation
+    if (!ok) { (void)hipGetLastError(); b->kv = nullptr; lmrs_batch_destroy(b); return fail("lmrs_batch_create: " + std::to_string(bytes) + " bytes of K/V caches for " + std::to_string(n_slots) + " slots: out of memory"); }
+    ok = hipMalloc(reinterpret_cast<void**>(&b->tab), sizeof(RowTable)) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->tokens), T * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->out), T * kRowTableMax * 4) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_tab), sizeof(RowTable), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_out), T * kRowTableMax * 4, hipHostMallocDefault) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail("lmrs_batch_create: row table and result buffers: out of memory"); }
+    if (hipMemsetAsync(b->kv, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail("lmrs_batch_create: clearing the caches failed"); }
+    *out = b;
+    return 0;
+}
+
+// A batch call that fails after it began to enqueue drains the stream before it returns: nothing queued may still read the pinned row table or the
+// state slot that the next call rewrites (ctx and batch stay usable); the failure's message stands
+static int batch_failed(lmrs_ctx* c) { (void)hipStreamSynchronize(c->stream); c->err_queued = false; return -1; }
+// the one DevState of a batch call (only Gemma's kernels read it: every row tests the window against its own position)
+static int batch_state(lmrs_ctx* c) { return set_state(c, 0, 0, pass_win_base(c, 0, true)); }
+
+extern "C" int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n, uint32_t start_pos) {
+    if (!b) return fail("NULL argument");
+    lmrs_ctx* c = b->c;
+    if (check_tokens(c, tokens, n, start_pos, n)) return -1;
+    if (slot >= b->n_slots) return fail("lmrs_batch_prefill: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if (n == 1) {                                        // one token: lmrs_batch_forward's pass with nobody reading its result
+        uint32_t am = 0;
+        return lmrs_batch_forward(b, 1, &slot, tokens, &start_pos, &am, nullptr);
+    }
+    HIP_OK(hipSetDevice(c->device));
+    memcpy(c->h_tok, tokens, n * 4);
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->tokens, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+        if (batch_state(c)) return -1;
+        PassForm form; form.skinny = n < kShortPassMax; form.k_cache = b->k_of(slot); form.v_cache = b->v_of(slot);
+        return prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, b->tokens + i0, m); }, [](size_t, int) { return 0; });
+    };
+    if (enqueue()) return batch_failed(c);
+    return finish_call(c);
+}
+
+extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_slot, uint32_t n_pos) {
+    if (!b) return fail("NULL argument");
+    lmrs_ctx* c = b->c;
+    const lmrs_args& a = c->args;
+    if ((src_slot != LMRS_BATCH_CTX && src_slot >= b->n_slots) || dst_slot >= b->n_slots)
+        return fail("lmrs_batch_fork: slots " + std::to_string(src_slot) + " -> " + std::to_string(dst_slot) + " of " + std::to_string(b->n_slots));
+    if (src_slot == dst_slot) return fail("lmrs_batch_fork: source and destination are the same slot");
+    if (n_pos > a.seq_len) return fail("lmrs_batch_fork: n_pos = " + std::to_string(n_pos) + " exceeds seq_len");
+    if (n_pos == 0) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t S = a.seq_len, kv = (size_t)c->kv_dim;
+    // K: [layer][kv head][head / 4] pieces of S x 4 floats, the first n_pos x 4 of each; V: [layer] pieces of S x kv floats, the first n_pos x kv
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpy2DAsync(b->k_of(dst_slot), S * 16, b->k_of(src_slot), S * 16, (size_t)n_pos * 16, (size_t)a.n_layers * kv / 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_OK(hipMemcpy2DAsync(b->v_of(dst_slot), S * kv * 4, b->v_of(src_slot), S * kv * 4, (size_t)n_pos * kv * 4, a.n_layers, hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    };
+    if (enqueue()) return batch_failed(c);
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The arguments of a step, checked before any device work; then the pinned row table, sorted by descending position (the deepest attention workgroups
+// dispatch first; the order is the same for every pass of a call, all positions moving together): order[r] = the caller's row behind table row r
+static int batch_rows(lmrs_batch* b, const char* what, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, uint32_t span, int* order) {
+    const lmrs_ctx* c = b->c;
+    if (n < 1 || n > (uint32_t)kRowTableMax) return fail(std::string(what) + ": n = " + std::to_string(n) + " is outside 1 .. " + std::to_string(kRowTableMax));
+    uint32_t seen = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (slot[i] >= b->n_slots) return fail(std::string(what) + ": row " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
+        if (seen >> slot[i] & 1u) return fail(std::string(what) + ": slot " + std::to_string(slot[i]) + " appears twice");
+        seen |= 1u << slot[i];
+        if (tokens[i] >= c->args.vocab_size) return fail(std::string(what) + ": token " + std::to_string(i) + " out of range");
+        if ((size_t)pos[i] + span > c->args.seq_len) return fail(std::string(what) + ": row " + std::to_string(i) + ": pos + " + std::to_string(span) + " positions exceeds seq_len");
+    }
+    for (uint32_t i = 0; i < n; ++i) order[i] = (int)i;
+    std::stable_sort(order, order + n, [&](int x, int y) { return pos[x] > pos[y]; });
+    for (uint32_t r = 0; r < n; ++r) {
+        const int i = order[r];
+        b->h_tab->off[r] = (unsigned long long)slot[i] * 2 * b->slot_floats; b->h_tab->pos[r] = (int)pos[i]; b->h_tab->tok[r] = tokens[i];
+    }
+    return 0;
+}
+// one pass over the device table's rows as they stand; step: how far the rows have moved since batch_rows (sizes the attention's score vector)
+static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logits) {
+    lmrs_ctx* c = b->c;
+    PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
+    RowSink to{0, n, out_logits, 0}; to.targets = false;
+    return run_tokens(c, to, form, /*batched=*/true);
+}
+
+extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, uint32_t* argmax, float* logits) {
+    if (!b || !slot || !tokens || !pos || !argmax) return fail("NULL argument");
+    lmrs_ctx* c = b->c;
+    int order[kRowTableMax];
+    if (batch_rows(b, "lmrs_batch_forward", n, slot, tokens, pos, 1, order)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t V = c->args.vocab_size;
+    std::vector<float> rows(logits ? n * V : 0);         // the pass's rows in table order
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
+        if (batch_state(c)) return -1;
+        if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx
+        if (logits && copy_out_rows(c, RowSink{0, n, rows.data(), 0}, c->sc_logits, cls_rows(c), (int)n, 0)) return -1;
+        HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    if (enqueue()) return batch_failed(c);
+    if (finish_call(c)) return -1;
+    for (uint32_t r = 0; r < n; ++r) {
+        argmax[order[r]] = b->h_out[r];
+        if (logits) memcpy(logits + (size_t)order[r] * V, rows.data() + (size_t)r * V, V * 4);
+    }
+    return 0;
+}
+
+extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, uint32_t n_new,
+                                          uint32_t* out_tokens, double* seconds) {
+    if (!b || !slot || !tokens || !pos || (!out_tokens && n_new)) return fail("NULL argument");
+    lmrs_ctx* c = b->c;
+    int order[kRowTableMax];
+    if (batch_rows(b, "lmrs_batch_generate_greedy", n, slot, tokens, pos, n_new ? n_new : 1, order)) return -1;
+    if (!n_new) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
+        if (batch_state(c)) return -1;
+        HIP_OK(hipEventRecord(c->ev0, c->stream));
+        for (uint32_t j = 0; j < n_new; ++j) {
+            // the pass, then its results -> out[j][..], the rows' next tokens, their positions + 1: nothing of a step crosses to the host
+            if (batch_pass(b, n, j, nullptr)) return -1;
+            HIP_OK(launch_table_advance(b->tab, c->sc_idx, b->out + (size_t)j * n, (int)n, c->stream));
+        }
+        HIP_OK(hipEventRecord(c->ev1, c->stream));
+        HIP_OK(hipMemcpyAsync(b->h_out, b->out, (size_t)n_new * n * 4, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    if (enqueue()) return batch_failed(c);
+    if (finish_call(c)) return -1;
+    for (uint32_t j = 0; j < n_new; ++j) for (uint32_t r = 0; r < n; ++r) out_tokens[(size_t)order[r] * n_new + j] = b->h_out[(size_t)j * n + r];
+    if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
+    return 0;
+}
+
+extern "C" int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out) {
+    if (!b || !out) return fail("NULL argument");
+    if (slot >= b->n_slots) return fail("lmrs_batch_debug_kv: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    return debug_kv_row(b->c, b->k_of(slot), b->v_of(slot), which, layer, pos, out);
+}
+
 // ------------------------------------------------------------------ measurement hooks
 // The GEMV launches of one decode step, in step order (per layer qkv, wo, w1w3, w2; then the classifier),
 // so that the weight stream is the real one (1.27 GB for Llama-3.2-1B: nothing is re-served by the 256 MiB
@@ -2097,17 +2304,20 @@ extern "C" int lmrs_debug_timeline(lmrs_ctx* c, unsigned long long* out, int max
 // Verification aid (no reference counterpart): one row of the KV cache in the reference's layout (transformer.rs:302-303, 413:
 // kv_dim floats of layer `layer`, position `pos`).  V is stored that way; K is stored blocked for the score lanes
 // ([kv head][head/4][seq_len][4], see attention_body) and is gathered back here.
-extern "C" int lmrs_debug_kv(lmrs_ctx* c, int which, uint32_t layer, uint32_t pos, float* out) {
-    if (!c || !out) return fail("NULL argument");
+static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out) {
     if (which < 0 || which > 1 || layer >= c->args.n_layers || pos >= c->args.seq_len) return fail("bad layer / position");
     HIP_OK(hipSetDevice(c->device));
     HIP_OK(hipStreamSynchronize(c->stream));
     const size_t S = c->args.seq_len, hs = c->args.head_size, kv = (size_t)c->kv_dim, nkv = kv / hs;
-    if (which == 1) { HIP_OK(hipMemcpy(out, c->v_cache + ((size_t)layer * S + pos) * kv, kv * 4, hipMemcpyDeviceToHost)); return 0; }
-    const float* kl = c->k_cache + (size_t)layer * nkv * hs * S;
+    if (which == 1) { HIP_OK(hipMemcpy(out, v_cache + ((size_t)layer * S + pos) * kv, kv * 4, hipMemcpyDeviceToHost)); return 0; }
+    const float* kl = k_cache + (size_t)layer * nkv * hs * S;
     for (size_t h = 0; h < nkv; ++h)
         HIP_OK(hipMemcpy2D(out + h * hs, 16, kl + h * hs * S + pos * 4, S * 16, 16, hs / 4, hipMemcpyDeviceToHost));   // hs/4 words of 4 dims, S*16 bytes apart
     return 0;
+}
+extern "C" int lmrs_debug_kv(lmrs_ctx* c, int which, uint32_t layer, uint32_t pos, float* out) {
+    if (!c || !out) return fail("NULL argument");
+    return debug_kv_row(c, c->k_cache, c->v_cache, which, layer, pos, out);
 }
 
 extern "C" int lmrs_last_fill_ms(const lmrs_ctx* c, double* ms) {

@@ -207,6 +207,19 @@ bool attention_block_supported(const AttnArgs& a, int n_tok);
 size_t attention_block_scratch_floats(int n_heads, int n_tok, int T);
 hipError_t launch_attention_block(const AttnArgs& a, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s);
 hipError_t launch_attention_rows(const AttnArgs& a, int pos0, int n_tok, hipStream_t s);
+// ---- multi-sequence pass (lmrs_batch_forward): row r of a pass of up to kRowTableMax rows is ONE token of its own sequence.  The device row table: where
+// the row's K / V caches start (floats from the k_cache / v_cache the launch is given: every slot of a batch has the context's cache layout), its position,
+// its token.  Columns, so that `tok` is a token run for launch_dequant_rows.  The host sorts the rows by descending position (deepest attention first).
+constexpr int kRowTableMax = 16;
+struct RowTable { unsigned long long off[kRowTableMax]; int pos[kRowTableMax]; uint32_t tok[kRowTableMax]; };
+// RoPE + scatter of the rows the qkv GEMM left as one [n_rows][att + 2 kv] block (EPI_STORE): q rotated in place with the row's own position, the rotated
+// key into the blocked K cache of the row's slot, the value row into its V cache (transformer.rs:413-431, 443-495)
+hipError_t launch_rope_scatter_rows(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowTable* rows, int n_heads, int n_kv_heads, int hs,
+                                    int seq_len, int layer, int n_rows, hipStream_t s);
+// attention_rows_kernel's workgroups over the table: a.q = the block above (row stride att + 2 kv), a.out [n_rows][att]; max_T: the deepest row's pos + 1
+hipError_t launch_attention_table(const AttnArgs& a, const RowTable* rows, int n_rows, int max_T, hipStream_t s);
+// behind a pass's reduction: out[r] = idx[r], the row's next token = idx[r], its position + 1 (lmrs_batch_generate_greedy's device loop)
+hipError_t launch_table_advance(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s);
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

@@ -1101,6 +1101,67 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(const AttnArgs a
 }
 
 // ------------------------------------------------------------------------------------------------
+// Multi-sequence pass (RowTable, lmrs_kernels.h): row r is one token of its own sequence, at its own position, over its own K / V cache.
+// RoPE + scatter: rope_rows_kernel's rotation (the same four products, one difference and one sum per pair) on the rows of the qkv block, q in place,
+// the key into the slot's blocked K cache, and the value row - which EPI_QKV would have stored itself - into the slot's V cache.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rope_scatter_rows_kernel(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowTable* rows,
+                                                                 int n_heads, int n_kv_heads, int hs, int seq_len, int layer) {
+    const int r = blockIdx.x, pos = rows->pos[r], half = hs / 2;
+    const int att = n_heads * hs, kv = n_kv_heads * hs;
+    const size_t off = (size_t)rows->off[r];
+    float* row = qkv + (size_t)r * (att + 2 * kv);
+    for (int i = threadIdx.x; i < (n_heads + n_kv_heads) * half; i += blockDim.x) {
+        const int hh = i / half, j = i - hh * half;
+        const float2 cs = *reinterpret_cast<const float2*>(rope + ((size_t)pos * half + j) * 2);
+        if (hh < n_heads) {
+            float* p = row + hh * hs;
+            const float2 rq = rope_rotate(p[j], p[j + half], cs.x, cs.y);
+            p[j] = rq.x; p[j + half] = rq.y;
+        } else {
+            const int kvh = hh - n_heads;
+            const float* p = row + att + kvh * hs;
+            const float2 rk = rope_rotate(p[j], p[j + half], cs.x, cs.y);
+            k_store_pair(k_cache + off + ((size_t)layer * n_kv_heads + kvh) * hs * (size_t)seq_len, seq_len, pos, j, half, rk.x, rk.y);
+        }
+    }
+    const float4* v = reinterpret_cast<const float4*>(row + att + kv);                       // (att, kv multiples of 4: prefill_batched_ok)
+    float4* vd = reinterpret_cast<float4*>(v_cache + off + ((size_t)layer * seq_len + pos) * kv);
+    for (int i = threadIdx.x; i < kv / 4; i += blockDim.x) vd[i] = v[i];
+}
+
+hipError_t launch_rope_scatter_rows(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowTable* rows, int n_heads, int n_kv_heads, int hs,
+                                    int seq_len, int layer, int n_rows, hipStream_t s) {
+    if (n_rows < 1 || n_rows > kRowTableMax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rope_scatter_rows_kernel, dim3(n_rows), dim3(256), 0, s, qkv, k_cache, v_cache, rope, rows, n_heads, n_kv_heads, hs, seq_len, layer);
+    return hipGetLastError();
+}
+
+// attention_rows_kernel over the table: grid (heads, rows); the workgroup takes its slot and position from its row and runs the same body.  The host
+// has sorted the rows by descending position, so y = 0 is the deepest one.
+template <int HS, bool GEMMA>
+__global__ __launch_bounds__(kBlock) void attention_table_kernel(const AttnArgs a0, const RowTable* rows) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    AttnArgs a = a0;
+    const int h = blockIdx.x, r = blockIdx.y, att = a.n_heads * HS, kv = a.n_kv_heads * HS;
+    const size_t off = (size_t)rows->off[r];
+    a.q = a0.q + (size_t)r * (att + 2 * kv); a.out = a0.out + (size_t)r * att; a.dbg = nullptr;
+    a.k_cache = a0.k_cache + off; a.v_cache = a0.v_cache + off;
+    const uint64_t etab = exp2f_tab_lane();
+    attention_body<HS, kAttF4, false, false, GEMMA, true>(a, h, rows->pos[r], smem, etab);
+}
+
+__global__ void table_advance_kernel(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows) {
+    const int r = threadIdx.x;
+    if (r < n_rows) { const uint32_t t = idx[r]; out[r] = t; rows->tok[r] = t; rows->pos[r] += 1; }
+}
+hipError_t launch_table_advance(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s) {
+    if (n_rows < 1 || n_rows > kRowTableMax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(table_advance_kernel, dim3(1), dim3(64), 0, s, rows, idx, out, n_rows);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // The same attention for BLOCKS of 64 query tokens of one head (Llama / Phi): one lane per query.
 // The per-(token, head) kernel above re-reads the whole K and V of its kv head for every query - 16 384 workgroups and
 // ~2 GB of cache traffic per layer at 512 tokens; here a key or value row staged once serves 64 queries.  The reference's
@@ -1612,4 +1673,20 @@ hipError_t launch_attention_rows(const AttnArgs& a0, int pos0, int n_tok, hipStr
     if (a.gemma) { if (a.head_size == 256) AR(256, true) return hipErrorInvalidValue; }
     switch (a.head_size) { case 64: AR(64, false) case 96: AR(96, false) case 128: AR(128, false) default: return hipErrorInvalidValue; }
 #undef AR
+}
+
+hipError_t launch_attention_table(const AttnArgs& a0, const RowTable* rows, int n_rows, int max_T, hipStream_t s) {
+    AttnArgs a = a0;
+    a.chunk = 64;                                                          // as launch_attention_rows: the small LDS footprint
+    if (n_rows < 1 || n_rows > kRowTableMax || max_T < 1 || max_T > a.seq_len || a.chunk * (a.head_size / 4) > kAttF4 * kBlock) return hipErrorInvalidValue;
+    const size_t smem = attention_smem(a.head_size, a.chunk, max_T);
+#define AT(HS_, G_)                                                                                                                   \
+    {                                                                                                                                 \
+        allow_big_lds(reinterpret_cast<const void*>(attention_table_kernel<HS_, G_>));                                                \
+        hipLaunchKernelGGL((attention_table_kernel<HS_, G_>), dim3(a.n_heads, n_rows), dim3(kBlock), smem, s, a, rows);                \
+        return hipGetLastError();                                                                                                     \
+    }
+    if (a.gemma) { if (a.head_size == 256) AT(256, true) return hipErrorInvalidValue; }
+    switch (a.head_size) { case 64: AT(64, false) case 96: AT(96, false) case 128: AT(128, false) default: return hipErrorInvalidValue; }
+#undef AT
 }

@@ -20,6 +20,8 @@ inline void check(int rc) { if (rc != 0) throw Panic(lmrs_last_error()); }
 
 using TransformerArgs = lmrs_args;
 
+class Batch;
+
 class Transformer {
 public:
     TransformerArgs args{};
@@ -124,9 +126,48 @@ public:
     }
 
 private:
+    friend class Batch;
     Transformer() = default;
     void reset() { if (ctx_) { lmrs_destroy(ctx_); ctx_ = nullptr; } }
     lmrs_ctx* ctx_ = nullptr;
+};
+
+// Extension (lmrs_batch_*): n_slots (1 .. 16) K/V caches beside the transformer's own, stepped together - one pass over the weights serves one
+// token of up to 16 different sequences.  Every result is bit for bit forward's on a transformer that holds only that sequence; the transformer's
+// own cache is untouched.  Destroy the batch before its transformer.
+class Batch {
+public:
+    static constexpr std::uint32_t CTX = LMRS_BATCH_CTX;           // fork's source: the transformer's own cache
+    Batch(Transformer& t, std::uint32_t n_slots) : vocab_size_(t.args.vocab_size) { check(lmrs_batch_create(t.ctx_, n_slots, &b_)); }
+    Batch(const Batch&) = delete;
+    Batch& operator=(const Batch&) = delete;
+    ~Batch() { if (b_) lmrs_batch_destroy(b_); }
+    void prefill(std::uint32_t slot, const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) {
+        check(lmrs_batch_prefill(b_, slot, tokens.data(), tokens.size(), start_pos));
+    }
+    void fork(std::uint32_t src_slot, std::uint32_t dst_slot, std::uint32_t n_pos) { check(lmrs_batch_fork(b_, src_slot, dst_slot, n_pos)); }
+    // row i = forward(tokens[i], pos[i]) on slot[i] -> the argmax of every row; logits (optional): n x vocab_size
+    std::vector<std::uint32_t> forward(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
+                                       std::vector<float>* logits = nullptr) {
+        if (slot.size() != tokens.size() || slot.size() != pos.size()) throw Panic("Batch::forward: one slot, token and position per row");
+        std::vector<std::uint32_t> argmax(slot.size());
+        if (logits) logits->resize(slot.size() * vocab_size_);
+        check(lmrs_batch_forward(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), tokens.data(), pos.data(), argmax.data(), logits ? logits->data() : nullptr));
+        return argmax;
+    }
+    // n_new greedy steps of every row on the device: out[i * n_new + j]
+    std::vector<std::uint32_t> generate_greedy(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
+                                               std::uint32_t n_new, double* seconds = nullptr) {
+        if (slot.size() != tokens.size() || slot.size() != pos.size()) throw Panic("Batch::generate_greedy: one slot, token and position per row");
+        std::vector<std::uint32_t> out(slot.size() * n_new);
+        check(lmrs_batch_generate_greedy(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), tokens.data(), pos.data(), n_new, out.data(), seconds));
+        return out;
+    }
+    void debug_kv(std::uint32_t slot, int which, std::uint32_t layer, std::uint32_t pos, float* out) { check(lmrs_batch_debug_kv(b_, slot, which, layer, pos, out)); }
+
+private:
+    lmrs_batch* b_ = nullptr;
+    std::size_t vocab_size_ = 0;
 };
 
 }  // namespace lmrs_host

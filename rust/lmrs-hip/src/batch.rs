@@ -1,0 +1,61 @@
+//! `Batch`: up to 16 sequences a step over the weights of one `Transformer` (extension, no reference counterpart; include/lmrs_hip.h,
+//! `lmrs_batch_*`).  Each slot is a K/V cache of its own; every result is bit for bit what `Transformer::forward` gives on a context that holds
+//! only that sequence.  The borrow keeps the transformer alive and un-aliased while the batch exists.
+use std::ptr;
+
+use crate::ffi::{self, check, LmrsBatch};
+use crate::transformer::Transformer;
+
+/// `fork`'s source: the transformer's own cache.
+pub const BATCH_CTX: u32 = 0xFFFF_FFFF;
+
+pub struct Batch<'t, 'a> {
+    b: *mut LmrsBatch,
+    vocab_size: usize,
+    _t: &'t mut Transformer<'a>,
+}
+
+impl<'t, 'a> Batch<'t, 'a> {
+    pub fn new(t: &'t mut Transformer<'a>, n_slots: u32) -> Batch<'t, 'a> {
+        let mut b: *mut LmrsBatch = ptr::null_mut();
+        check(unsafe { ffi::lmrs_batch_create(t.ctx(), n_slots, &mut b) });
+        let vocab_size = t.args.vocab_size as usize;
+        Batch { b, vocab_size, _t: t }
+    }
+
+    /// `Transformer::prefill_tokens` into `slot`'s cache.
+    pub fn prefill(&mut self, slot: u32, tokens: &[u32], start_pos: u32) {
+        check(unsafe { ffi::lmrs_batch_prefill(self.b, slot, tokens.as_ptr(), tokens.len(), start_pos) });
+    }
+
+    /// K/V rows `[0, n_pos)` of `src` (`BATCH_CTX`: the transformer's own cache) into `dst`.
+    pub fn fork(&mut self, src: u32, dst: u32, n_pos: u32) {
+        check(unsafe { ffi::lmrs_batch_fork(self.b, src, dst, n_pos) });
+    }
+
+    /// One weight pass: row i = forward(tokens[i], pos[i]) on slot[i].  Returns the argmax of every row and, if asked, the n x vocab logits.
+    pub fn forward(&mut self, slot: &[u32], tokens: &[u32], pos: &[u32], want_logits: bool) -> (Vec<u32>, Vec<f32>) {
+        assert!(slot.len() == tokens.len() && slot.len() == pos.len(), "one slot, token and position per row");
+        let mut argmax = vec![0u32; slot.len()];
+        let mut logits = vec![0f32; if want_logits { slot.len() * self.vocab_size } else { 0 }];
+        let lp = if want_logits { logits.as_mut_ptr() } else { ptr::null_mut() };
+        check(unsafe { ffi::lmrs_batch_forward(self.b, slot.len() as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), argmax.as_mut_ptr(), lp) });
+        (argmax, logits)
+    }
+
+    /// `n_new` greedy steps of every row on the device: out[i * n_new + j].
+    pub fn generate_greedy(&mut self, slot: &[u32], tokens: &[u32], pos: &[u32], n_new: u32) -> Vec<u32> {
+        assert!(slot.len() == tokens.len() && slot.len() == pos.len(), "one slot, token and position per row");
+        let mut out = vec![0u32; slot.len() * n_new as usize];
+        check(unsafe {
+            ffi::lmrs_batch_generate_greedy(self.b, slot.len() as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), n_new, out.as_mut_ptr(), ptr::null_mut())
+        });
+        out
+    }
+}
+
+impl<'t, 'a> Drop for Batch<'t, 'a> {
+    fn drop(&mut self) {
+        unsafe { ffi::lmrs_batch_destroy(self.b) }
+    }
+}

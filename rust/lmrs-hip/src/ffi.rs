@@ -21,6 +21,10 @@ pub struct LmrsProcessor {
 pub struct LmrsSampler {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct LmrsBatch {
+    _private: [u8; 0],
+}
 
 extern "C" {
     pub fn lmrs_create(file: *const u8, len: usize, device: c_int, out: *mut *mut LmrsCtx, bytes_consumed: *mut usize) -> c_int;
@@ -78,4 +82,18 @@ pub(crate) fn check(rc: c_int) {
 /// Device index for every `new`: LMRS_HIP_DEVICE (default 0).  One process per GPU: a multi-GPU launcher sets it per rank.
 pub(crate) fn device() -> c_int {
     std::env::var("LMRS_HIP_DEVICE").ok().and_then(|s| s.parse().ok()).unwrap_or(0)
+}
+
+// Multi-sequence decode (include/lmrs_hip.h, lmrs_batch_*): the entry points over the batch handle, a block of their own (tests/test_batch.py
+// checks their presence; `crate::batch::Batch` is the wrapper).
+extern "C" {
+    pub fn lmrs_batch_create(ctx: *mut LmrsCtx, n_slots: u32, out: *mut *mut LmrsBatch) -> c_int;
+    pub fn lmrs_batch_destroy(b: *mut LmrsBatch);
+    pub fn lmrs_batch_prefill(b: *mut LmrsBatch, slot: u32, tokens: *const u32, n: usize, start_pos: u32) -> c_int;
+    pub fn lmrs_batch_fork(b: *mut LmrsBatch, src_slot: u32, dst_slot: u32, n_pos: u32) -> c_int;
+    pub fn lmrs_batch_forward(b: *mut LmrsBatch, n: u32, slot: *const u32, tokens: *const u32, pos: *const u32, argmax: *mut u32,
+                              logits: *mut f32) -> c_int;
+    pub fn lmrs_batch_generate_greedy(b: *mut LmrsBatch, n: u32, slot: *const u32, tokens: *const u32, pos: *const u32, n_new: u32,
+                                      out_tokens: *mut u32, seconds: *mut f64) -> c_int;
+    pub fn lmrs_batch_debug_kv(b: *mut LmrsBatch, slot: u32, which: c_int, layer: u32, pos: u32, out: *mut f32) -> c_int;
 }

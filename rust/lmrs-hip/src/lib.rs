@@ -5,6 +5,7 @@
 //! modules in place of its own.  `sampler::Sampler` has the reference's signatures and adds
 //! `Transformer::forward_sample` (the draw on the device); lm.rs's own sampler keeps working on `forward`'s logits.  Tokenizer,
 //! the chat / web / desktop binaries and the image pre-processing (`PHI3VProcessor::process`) stay lm.rs's own code.
+pub mod batch;
 pub mod ffi;
 pub mod sampler;
 pub mod transformer;

@@ -1,0 +1,94 @@
+"""What a multi-sequence decode step yields on a full-size synthetic model, in one process: aggregate tokens per second of lmrs_batch_generate_greedy
+over 64 steps at n = 1, 2, 4, 8, 16 rows standing at about 100 positions, against lmrs_generate_greedy over the same 64 steps on the context's own cache
+(the single-sequence decode step: the baseline), then n = 16 and the baseline again with the rows at about 1030 positions.  Both calls report device
+time (HIP events around their steps): median of 5 after 2 warm-ups, with the minimum and the maximum.  Every row's token ids are compared with the
+single-sequence run of the same prompt in the same process.  Last, one lmrs_batch_fork of 1030 positions at full size, timed and checked.
+usage: python tools/batch_rate.py [model] [q8_0|q4_0]
+       (writes profiles/batch_decode_llama1b.txt for llama-3.2-1b q8_0, profiles/batch_decode_gemma2b_q4.txt for gemma-2-2b q4_0)"""
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import bench  # noqa: E402
+import lmrs_amd  # noqa: E402
+from tools import synth_lmrs as S  # noqa: E402
+
+STEPS, ROWS = 64, 16
+OUT = {("llama-3.2-1b", S.Q8_0): "batch_decode_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_decode_gemma2b_q4.txt"}
+
+
+def timed(fn, reps=5, warm=2):
+    """fn() -> (ids, device seconds); -> (ids of the last run, median, min, max in microseconds)"""
+    for _ in range(warm):
+        fn()
+    runs = [fn() for _ in range(reps)]
+    us = [sec * 1e6 for _, sec in runs]
+    return runs[-1][0], statistics.median(us), min(us), max(us)
+
+
+def main():
+    model = sys.argv[1] if len(sys.argv) > 1 else "llama-3.2-1b"
+    qname = sys.argv[2] if len(sys.argv) > 2 else "q8_0"
+    qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True); lines.append(s)
+
+    img = S.build_image(model, qt, 1234)
+    m = lmrs_amd.Transformer(img)
+    b = lmrs_amd.Batch(m, ROWS)
+    say(f"python tools/batch_rate.py {model} {qname}")
+    say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
+    say(f"{STEPS} greedy steps per call, device time of the steps (HIP events inside the call); median of 5 after 2 warm-ups (min .. max)")
+    first_win = None
+    for depth in (100, 1030):
+        prompts = [S.prompt_tokens(model, depth + 1, 100 + i) for i in range(ROWS)]        # row i: depth tokens in its cache, the next one fed first
+        for i, p in enumerate(prompts):
+            b.prefill(i, p[:depth], 0)
+        singles = []
+        for p in prompts:                                    # the single-sequence ids of every row's prompt, and the baseline's time from row 0's
+            m.prefill_tokens(p[:depth], 0)
+            singles.append(m.generate_greedy(p[depth:], STEPS, depth))
+        m.prefill_tokens(prompts[0][:depth], 0)
+        _, base, lo, hi = timed(lambda: m.generate_greedy(prompts[0][depth:], STEPS, depth, timing=True))
+        base_rate = STEPS / base * 1e6
+        say(f"rows at {depth} positions")
+        say(f"  lmrs_generate_greedy (one sequence)   {base / STEPS:8.1f} us per step ({lo / STEPS:.1f} .. {hi / STEPS:.1f})   {base_rate:9.1f} tok/s")
+        for n in ((1, 2, 4, 8, 16) if depth == 100 else (16,)):
+            slots = list(range(n))
+            ids, us, lo, hi = timed(lambda: b.generate_greedy(slots, [int(p[depth]) for p in prompts[:n]], [depth] * n, STEPS, timing=True))
+            same = all(ids[i].tolist() == singles[i].tolist() for i in range(n))
+            rate = n * STEPS / us * 1e6
+            if depth == 100 and first_win is None and rate > base_rate:
+                first_win = n
+            say(f"  lmrs_batch_generate_greedy n={n:2d}       {us / STEPS:8.1f} us per pass ({lo / STEPS:.1f} .. {hi / STEPS:.1f})   {rate:9.1f} tok/s aggregate"
+                f"   {rate / base_rate:5.2f}x the baseline   same tokens as the single-sequence runs: {same}")
+        if depth == 100:
+            say(f"  the batch first beats the baseline at n = {first_win}")
+    # lmrs_batch_fork at full size (its V copy's pitch is seq_len x kv_dim x 4 bytes): slot 0's 1030 rows into slot 1 and from the context's own cache
+    # into slot 2, the copied rows compared, and slot 1 continued as slot 0's prompt is
+    depth, nl = 1030, m.args.n_layers
+    t0 = time.perf_counter(); b.fork(0, 1, depth); fork_ms = (time.perf_counter() - t0) * 1e3
+    m.prefill_tokens(prompts[0][:depth], 0)
+    b.fork(lmrs_amd.BATCH_CTX, 2, depth)
+    rows_equal = all((b.kv_row(dst, w, l, p).view(np.uint32) == b.kv_row(0, w, l, p).view(np.uint32)).all()
+                     for dst in (1, 2) for w in (0, 1) for l in (0, nl // 2, nl - 1) for p in (0, 517, depth - 1))
+    ids = b.generate_greedy([2, 1], [int(prompts[0][depth])] * 2, [depth] * 2, STEPS)
+    same = ids[0].tolist() == ids[1].tolist() == singles[0].tolist()
+    bytes_moved = 2 * nl * depth * m.args.n_kv_heads * m.args.head_size * 4
+    say(f"lmrs_batch_fork of {depth} positions ({bytes_moved / 1e6:.1f} MB of K and V rows, host wall time of the synchronous call): {fork_ms:.2f} ms; "
+        f"copied rows bit-equal: {rows_equal}; a forked slot continues with the single-sequence tokens: {same}")
+    name = OUT.get((model, qt))
+    if name:
+        path = os.environ.get("BATCH_RATE_OUT") or os.path.join(ROOT, "profiles", name)
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
