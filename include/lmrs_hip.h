@@ -266,6 +266,22 @@ int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slot, const ui
 int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens,
                                const uint32_t* pos, uint32_t n_new, uint32_t* out_tokens, double* seconds);
 
+/* ONE weight pass over n_runs runs (1 .. 16).  Run i = tokens[t_i .. t_i + run_len[i]) (t_i = sum of the earlier run_len) at positions
+ * start_pos[i] .. start_pos[i] + run_len[i] - 1 of slot[i]: per row Transformer::forward (src/transformer.rs:316-384) on a context that
+ * holds only that sequence, in position order - a prompt (chunk) to admit, a draft to verify, or one decode row, mixed freely; at most 512
+ * rows in all, a slot in at most one run.  Outputs for the LAST n_out[i] rows of run i (0: K/V rows only), packed in run order, ascending
+ * position within a run; O = sum of n_out (O == 0: neither the final norm nor the classifier runs).
+ *   argmax (O; may be NULL when O == 0): Sampler::sample_argmax (sampler.rs:29-41) of every output row;
+ *   logits (may be NULL): O * vocab floats as lmrs_forward_tokens writes a row;
+ *   k > 0: topk_idx / topk_logprob (O * k each), order and log-probability exactly as lmrs_score_tokens_topk defines them; k <= 256, k <= vocab.
+ * K/V rows are left as the per-token calls leave them; rows of rejected drafts are stale and rewritten by whatever runs at those positions
+ * next, as with lmrs_verify_tokens.  Errors, each with a message of its own and before any device work: a NULL array, n_runs outside 1 .. 16, a
+ * run_len of 0, more than 512 rows, a slot >= n_slots or in two runs, n_out > run_len, start_pos + run_len > seq_len, a token >= vocab_size, k
+ * out of range or without its two arrays, O > 0 without argmax. */
+int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                            const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
+                            uint32_t k, uint32_t* topk_idx, float* topk_logprob);
+
 /* verification aid, as lmrs_debug_kv */
 int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out);
 

@@ -29,7 +29,7 @@ EXPORTS = [
     "lmrs_prefill_tokens", "lmrs_tokens_path", "lmrs_score_tokens_topk", "lmrs_forward_topk", "lmrs_op_topk",
     "lmrs_verify_tokens", "lmrs_draft_lookup", "lmrs_generate_speculative", "lmrs_debug_gemm_skinny",
     "lmrs_batch_create", "lmrs_batch_destroy", "lmrs_batch_prefill", "lmrs_batch_fork", "lmrs_batch_forward", "lmrs_batch_generate_greedy",
-    "lmrs_batch_debug_kv",
+    "lmrs_batch_debug_kv", "lmrs_batch_forward_runs",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -110,6 +110,7 @@ def lib():
         L.lmrs_batch_forward.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.lmrs_batch_generate_greedy.argtypes = [vp, u32, vp, vp, vp, u32, vp, C.POINTER(C.c_double)]
         L.lmrs_batch_debug_kv.argtypes = [vp, u32, C.c_int, u32, u32, vp]
+        L.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.lmrs_op_matmul_q4.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz]
         L.lmrs_op_quantize.argtypes = [C.c_int, vp, vp, vp, sz, sz]
@@ -414,6 +415,24 @@ class Batch:
         lg = np.empty((s.size, self.model.args.vocab_size), np.float32) if logits else None
         _chk(lib().lmrs_batch_forward(self._h, s.size, _p(s), _p(t), _p(p), _p(am), _p(lg) if logits else None))
         return (am, lg) if logits else am
+
+    def forward_runs(self, runs, k: int = 0, logits: bool = False):
+        """One pass over runs = [(slot, start_pos, tokens, n_out), ...]: run i feeds its tokens at start_pos .. of its slot (a prompt chunk, a draft, one
+        decode row; a slot in at most one run, at most 512 tokens in all) and returns outputs for its LAST n_out rows, packed in run order: argmax uint32 [O];
+        with logits also float32 [O, vocab_size]; with k > 0 also topk_idx uint32 [O, k] and topk_logprob float32 [O, k] as score_tokens_topk defines
+        them -> argmax, or the tuple (argmax[, logits][, topk_idx, topk_logprob])  (lmrs_batch_forward_runs)"""
+        toks = [np.ascontiguousarray(r[2], np.uint32).reshape(-1) for r in runs]
+        s, p, no = (np.array([r[i] for r in runs], np.uint32) for i in (0, 1, 3))
+        n = np.array([t.size for t in toks], np.uint32)
+        t = np.concatenate(toks) if toks else np.empty(0, np.uint32)
+        O, V = int(no.astype(np.int64).sum()), self.model.args.vocab_size
+        am = np.empty(O, np.uint32)
+        lg = np.empty((O, V), np.float32) if logits else None
+        ti, tl = (np.empty((O, k), np.uint32), np.empty((O, k), np.float32)) if k else (None, None)
+        _chk(lib().lmrs_batch_forward_runs(self._h, len(runs), _p(s), _p(p), _p(n), _p(no), _p(t), _p(am) if O else None, _p(lg) if logits else None,
+                                           k, _p(ti) if k else None, _p(tl) if k else None))
+        out = (am,) + ((lg,) if logits else ()) + ((ti, tl) if k else ())
+        return out if len(out) > 1 else am
 
     def generate_greedy(self, slots, tokens, pos, n_new: int, timing: bool = False):
         """n_new greedy steps of every row on the device -> uint32 [n, n_new]: row i = Transformer.generate_greedy([tokens[i]], n_new, pos[i]) on its

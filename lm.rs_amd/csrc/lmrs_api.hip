@@ -176,7 +176,9 @@ struct StepForm { int qa_mode = 0, split_chunks = 0; };
 // rows: the pass is lmrs_batch_forward's - row r is one token of its own sequence (the device row table, lmrs_kernels.h; max_T = the deepest row's
 // position + 1); null: m consecutive positions of one sequence, as always.  k_cache / v_cache: the caches the pass reads and writes - a batch's (with
 // rows: the base the table's offsets count from); null: the context's own
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; };
+// runs (runs.tok != null): the pass is lmrs_batch_forward_runs' - a table of up to kRunRowsMax rows, several of them consecutive positions of one slot; its
+// qkv block is wider than pf_q at that many rows, so the pass brings a buffer of its own (qkv; null: pf_q, as every other pass).
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; };
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1405,6 +1407,8 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
     const bool gemma = a.model_type == LMRS_GEMMA;
     const float eps = a.rms_norm_eps;
     float* const k_cache = form.k_cache ? form.k_cache : c->k_cache; float* const v_cache = form.v_cache ? form.v_cache : c->v_cache;
+    float* const qkv = form.qkv ? form.qkv : c->pf_q;
+    const bool table = form.rows || form.runs.tok;
     // scale layouts of this pass: from 48 tokens on every GEMM is a ring kernel, which takes TRANSPOSED scales ([group][row]: GemmArgs::ws_ld / xs_ld) -
     // the weights' transposed copies (prefill_alloc) and activation scales written that way by their producers, leading dimension kPrefillTokens
     const bool trs = m >= 48 && c->layers[0].sqkvT != nullptr;
@@ -1440,19 +1444,24 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
         // [x += rmsnorm(previous ffn out)] rmsnorm + quantize | Wqkv | q, raw k, v rows -> cache      (transformer.rs:409-431)
         if (gemma && l > 0) HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, c->pf_t, c->layers[l - 1].rms_post_ffn, eps, 1, 2, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
         else HIP_OK(launch_rows_prologue(c->pf_x, L.rms_att, nullptr, nullptr, eps, gemma, 1, q4, dim, m, c->pf_xq, c->pf_xs, c->stream, xld));
-        g.wq = L.wqkv; g.ws = trs ? L.sqkvT : L.sqkv; g.ws_ld = trs ? att + 2 * kv : 0; g.n = dim; g.o = att + 2 * kv; g.out = c->pf_q; g.k_raw = c->pf_k; g.v_cache = v_cache;
+        g.wq = L.wqkv; g.ws = trs ? L.sqkvT : L.sqkv; g.ws_ld = trs ? att + 2 * kv : 0; g.n = dim; g.o = att + 2 * kv; g.out = qkv; g.k_raw = c->pf_k; g.v_cache = v_cache;
         g.att_dim = att; g.kv_dim = kv; g.seq_len = (int)a.seq_len; g.layer = (int)l; g.pos0 = p0;
-        // (a row table: the rows' positions are not consecutive - q | raw k | v stay one [m][att + 2 kv] block in pf_q, plain stores as EPI_QKV's)
-        HIP_OK(launch_gemm_q8(g, form.rows ? EPI_STORE : EPI_QKV, c->stream));
+        // (a row table: the rows' positions are not consecutive - q | raw k | v stay one [m][att + 2 kv] block in pf_q, plain stores as EPI_QKV's;
+        // from 48 rows on the ring kernel writes it with the scales transposed as for EPI_QKV: ws_ld = the block's width, xs_ld = kPrefillTokens)
+        HIP_OK(launch_gemm_q8(g, table ? EPI_STORE : EPI_QKV, c->stream));
         // RoPE, keys into the cache; attention (this shard's heads)                    (:443-544)
         AttnArgs t{};
-        t.q = c->pf_q; t.k_raw = nullptr; t.k_cache = k_cache; t.v_cache = v_cache; t.rope = c->rope; t.out = c->pf_ao;
+        t.q = qkv; t.k_raw = nullptr; t.k_cache = k_cache; t.v_cache = v_cache; t.rope = c->rope; t.out = c->pf_ao;
         t.n_heads = att / hs; t.n_kv_heads = kv / hs; t.head_size = hs; t.seq_len = (int)a.seq_len; t.layer = (int)l;
         t.gemma = gemma; t.st = c->st;
         if (form.rows) {
             // every row at its own position in its own slot: rotation, K / V rows into the slots, one attention workgroup per (head, row)
             HIP_OK(launch_rope_scatter_rows(c->pf_q, k_cache, v_cache, c->rope, form.rows, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
             HIP_OK(launch_attention_table(t, form.rows, m, form.max_T, c->stream));
+        } else if (form.runs.tok) {
+            // the same over the long table: a row also sees the earlier rows of its own run, all stored before the attention launch starts
+            HIP_OK(launch_rope_scatter_runs(qkv, k_cache, v_cache, c->rope, form.runs, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
+            HIP_OK(launch_attention_runs(t, form.runs, m, form.max_T, c->stream));
         } else if (prefill_attention(c, t, m, p0)) return -1;
         // quantize | Wo | x += ... (Gemma: -> pf_t)                                     (:550-576)
         if (tp) { if (all_gather(c->pf_ao, att, c->pfx_att, c->pfb_att)) return -1; }
@@ -1671,9 +1680,12 @@ static bool score_batched_ok(const lmrs_ctx* c, size_t n) {
     return n > 1 && prefill_batched_ok(c) && cls_rows(c) % 16 == 0;
 }
 
+// rows whose reductions one call can hold: a token run is at most seq_len long, a ragged batch pass (lmrs_batch_forward_runs) kPrefillTokens rows of any positions
+static size_t score_cap(const lmrs_ctx* c) { return std::max<size_t>(c->args.seq_len, kPrefillTokens); }
+
 // all or nothing, like prefill_alloc; `block`: the logits block too (forward_tokens and the batched path need it, token-by-token scoring does not)
 static int score_alloc(lmrs_ctx* c, bool block) {
-    const size_t V = c->args.vocab_size, T = c->args.seq_len, S = (size_t)score_chunks((int)V);
+    const size_t V = c->args.vocab_size, T = score_cap(c), S = (size_t)score_chunks((int)V);
     const size_t rows = std::min<size_t>(kPrefillTokens, std::max<size_t>(1, kScoreBlockBytes / (V * 4)));
     if (!c->sc_part) {
         bool ok = hipMalloc(reinterpret_cast<void**>(&c->sc_part), rows * S * sizeof(ScorePart)) == hipSuccess;
@@ -1709,7 +1721,7 @@ static int topk_alloc(lmrs_ctx* c, int rows, int k) {
     if (c->tk_cand && rows <= c->tk_rows && k <= c->tk_k) return 0;
     rows = std::max(rows, c->tk_rows); k = std::max(k, c->tk_k);
     topk_free(c);
-    const size_t T = c->args.seq_len, S = (size_t)score_chunks((int)c->args.vocab_size);
+    const size_t T = score_cap(c), S = (size_t)score_chunks((int)c->args.vocab_size);
     bool ok = hipMalloc(reinterpret_cast<void**>(&c->tk_cand), (size_t)rows * S * k * 8) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_cnt), (size_t)rows * S * 4) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_idx), T * k * 4) == hipSuccess;
@@ -1728,15 +1740,16 @@ static int topk_alloc(lmrs_ctx* c, int rows, int k) {
 // lmrs_score_tokens_topk's further results (k == 0: none are asked for)
 struct TopkOut { uint32_t k; uint32_t* idx; float* logprob; uint32_t* rank; };
 
-// The pinned h_sc in its two halves (score_alloc): seq_len doubles for the log-probabilities, then seq_len indices
+// The pinned h_sc in its two halves (score_alloc): score_cap doubles for the log-probabilities, then score_cap indices
 struct HostScores { double* lp; uint32_t* idx; };
-static HostScores host_scores(const lmrs_ctx* c) { return {reinterpret_cast<double*>(c->h_sc), reinterpret_cast<uint32_t*>(c->h_sc + (size_t)c->args.seq_len * 8)}; }
+static HostScores host_scores(const lmrs_ctx* c) { return {reinterpret_cast<double*>(c->h_sc), reinterpret_cast<uint32_t*>(c->h_sc + score_cap(c) * 8)}; }
 
 // What becomes of the logits rows of a run of n tokens in c->tokens[start_pos ..).  out_logits != null: they go to the host as they are
 // (lmrs_forward_tokens); else the reduction of every row - the next token's log-probability to c->sc_lp, sample_argmax to c->sc_idx - and with k the
 // selection behind it (c->tk_idx / tk_val / tk_rank)
 // targets: row r's next token (c->tokens) is the target of its log-probability; false: the rows are not a run (a row table) - sample_argmax only
-struct RowSink { uint32_t start_pos; size_t n; float* out_logits; uint32_t k; bool targets = true; };
+// reduce_too: out_logits AND the reduction, both from the same slab (lmrs_batch_forward_runs)
+struct RowSink { uint32_t start_pos; size_t n; float* out_logits; uint32_t k; bool targets = true; bool reduce_too = false; };
 
 // rows r0 .. r0 + m - 1 of the run, ld columns written at row stride ld (the rest up to vocab_size is the classifier's zero tail)
 static int reduce_rows(lmrs_ctx* c, const RowSink& to, const float* rows, int ld, int m, size_t r0) {
@@ -1760,14 +1773,14 @@ static int copy_out_rows(lmrs_ctx* c, const RowSink& to, const float* rows, int 
     return 0;
 }
 
-// The tail of a batched chunk behind its layers, rows i0 .. i0 + m - 1 of the run in pf_x: final rmsnorm + quantise of every token
+// The tail of a batched chunk behind its layers, rows i0 .. i0 + m - 1 of the run in x (pf_x, or the rows a ragged pass picked from it): final rmsnorm + quantise of every token
 // (transformer.rs:341-343), row-major scales; the classifier over the batch (:345-372) in the pass's form, a slab of the logits block's sc_rows
 // rows at a time; Gemma's soft-cap (:375-381); every slab to the sink
-static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, size_t i0, int m) {
+static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, float* x, size_t i0, int m) {
     const lmrs_args& a = c->args;
     const int dim = (int)a.dim, o = cls_rows(c);
     const bool gemma = a.model_type == LMRS_GEMMA;
-    HIP_OK(launch_rows_prologue(c->pf_x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
+    HIP_OK(launch_rows_prologue(x, c->rms_final, nullptr, nullptr, a.rms_norm_eps, gemma, 1, c->q4, dim, m, c->pf_xq, c->pf_xs, c->stream));
     for (int j0 = 0; j0 < m; j0 += c->sc_rows) {
         const int mj = std::min(c->sc_rows, m - j0);
         GemmArgs g{};
@@ -1775,7 +1788,8 @@ static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, size_t i
         g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits; g.skinny = form.skinny;
         HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
         if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));
-        if (to.out_logits ? copy_out_rows(c, to, c->sc_logits, o, mj, i0 + j0) : reduce_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
+        if (to.out_logits && copy_out_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
+        if ((!to.out_logits || to.reduce_too) && reduce_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
     }
     return 0;
 }
@@ -1791,7 +1805,7 @@ static int run_tokens(lmrs_ctx* c, const RowSink& to, PassForm form, bool batche
         if (!form.rows && set_state(c, start_pos, 0, pass_win_base(c, start_pos, true))) return -1;
         // (a row table: its token column is the run, n <= kRowTableMax rows - one chunk)
         if (prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, form.rows ? form.rows->tok : c->tokens + start_pos + i0, m); },
-                           [&](size_t i0, int m) { return classify_rows(c, form, to, i0, m); })) return -1;
+                           [&](size_t i0, int m) { return classify_rows(c, form, to, c->pf_x, i0, m); })) return -1;
         return form.rows ? 0 : set_state(c, start_pos + (uint32_t)n, 0);
     }
     const size_t V = c->args.vocab_size;
@@ -1983,12 +1997,17 @@ extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, si
 // caches of the context's layout; a step is run_tokens' batched arm, skinny, with a row table (PassForm::rows) - the qkv rows stay in scratch, one
 // launch rotates them and scatters K / V into the rows' slots, and attention_rows_kernel's workgroups take slot and position from the table.
 static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out);   // (with lmrs_debug_kv below)
+// the ragged pass's table (lmrs_batch_forward_runs): RowTable's columns for kRunRowsMax rows, and sel - the table rows whose outputs were asked for, in output order
+struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
 struct lmrs_batch {
     lmrs_ctx* c = nullptr; uint32_t n_slots = 0;
     float* kv = nullptr; size_t slot_floats = 0;        // [n_slots][K cache | V cache], slot_floats floats each: one allocation
     RowTable *tab = nullptr, *h_tab = nullptr;          // the pass's row table and its pinned source
     uint32_t *tokens = nullptr;                         // a prefill's token run (seq_len)
     uint32_t *out = nullptr, *h_out = nullptr;          // generate_greedy: [n_new][n] results of the passes, and their pinned copy (seq_len x 16)
+    RunTable *runs = nullptr, *h_runs = nullptr;        // forward_runs: the long table and its pinned source,
+    float *runs_qkv = nullptr, *runs_x = nullptr;       // its [kRunRowsMax][att + 2 kv] qkv block and the [kRunRowsMax][dim] rows picked for the classifier
+    RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
     float* k_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->k_cache : kv + (size_t)slot * 2 * slot_floats; }
     float* v_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->v_cache : kv + (size_t)slot * 2 * slot_floats + slot_floats; }
 };
@@ -1997,8 +2016,9 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->c->device);
     (void)hipStreamSynchronize(b->c->stream);
-    for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x}) if (p) (void)hipFree(p);
     if (b->h_tab) (void)hipHostFree(b->h_tab);
+    if (b->h_runs) (void)hipHostFree(b->h_runs);
     if (b->h_out) (void)hipHostFree(b->h_out);
     delete b;
 }
@@ -2029,6 +2049,10 @@ extern "C" int lmrs_batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->out), T * kRowTableMax * 4) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_tab), sizeof(RowTable), hipHostMallocDefault) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_out), T * kRowTableMax * 4, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs), sizeof(RunTable)) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_runs), sizeof(RunTable), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_qkv), (size_t)kRunRowsMax * (c->att_dim + 2 * c->kv_dim) * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_x), (size_t)kRunRowsMax * a.dim * 4) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail("lmrs_batch_create: row table and result buffers: out of memory"); }
     if (hipMemsetAsync(b->kv, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail("lmrs_batch_create: clearing the caches failed"); }
     *out = b;
@@ -2163,6 +2187,82 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     if (finish_call(c)) return -1;
     for (uint32_t j = 0; j < n_new; ++j) for (uint32_t r = 0; r < n; ++r) out_tokens[(size_t)order[r] * n_new + j] = b->h_out[(size_t)j * n + r];
     if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
+    return 0;
+}
+
+// ------------------------------------------------------------------ the ragged batch pass: runs of consecutive tokens, one run per slot, one weight pass
+// (no reference counterpart: per row Transformer::forward on a cache that holds only the row's sequence, in position order).  run_tokens' batched arm with the
+// long table: rows sorted by descending position, the GEMMs skinny up to 16 rows and launch_gemm_q8's dispatch above, the qkv block in a buffer of the
+// batch's own; behind the layers the rows whose outputs were asked for are made consecutive and only they go through the final norm and the classifier.
+static_assert(kRunRowsMax == kPrefillTokens, "a ragged pass is one chunk of the batched pass");
+extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                       const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
+                                       uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
+    const std::string what = "lmrs_batch_forward_runs: ";
+    if (!b || !slot || !start_pos || !run_len || !n_out || !tokens) return fail(what + "NULL argument");
+    lmrs_ctx* c = b->c;
+    const lmrs_args& a = c->args;
+    if (n_runs < 1 || n_runs > (uint32_t)kRowTableMax) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(kRowTableMax));
+    size_t R = 0, O = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) {
+        if (run_len[i] < 1) return fail(what + "run " + std::to_string(i) + ": run_len is 0");
+        if ((R += run_len[i]) > (size_t)kRunRowsMax) return fail(what + "the runs hold more than " + std::to_string(kRunRowsMax) + " rows");
+    }
+    uint32_t seen = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) {
+        const std::string run = what + "run " + std::to_string(i) + ": ";
+        if (slot[i] >= b->n_slots) return fail(run + "slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
+        if (seen >> slot[i] & 1u) return fail(what + "slot " + std::to_string(slot[i]) + " appears in more than one run");
+        seen |= 1u << slot[i];
+        if (n_out[i] > run_len[i]) return fail(run + "n_out = " + std::to_string(n_out[i]) + " exceeds run_len = " + std::to_string(run_len[i]));
+        if ((size_t)start_pos[i] + run_len[i] > a.seq_len) return fail(run + "start_pos + run_len exceeds seq_len");
+        O += n_out[i];
+    }
+    for (size_t j = 0; j < R; ++j) if (tokens[j] >= a.vocab_size) return fail(what + "token " + std::to_string(j) + " out of range");
+    if (k && topk_check_k(k, a.vocab_size)) return -1;
+    if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
+    if (O && !argmax) return fail(what + "argmax is NULL with " + std::to_string(O) + " output rows asked for");
+    // the pinned table: caller row j (run order, ascending position) behind table row r, deepest first; sel[o] = the table row of output o
+    struct Row { uint32_t run, pos; };
+    std::vector<Row> rows; rows.reserve(R);
+    for (uint32_t i = 0; i < n_runs; ++i) for (uint32_t j = 0; j < run_len[i]; ++j) rows.push_back(Row{i, start_pos[i] + j});
+    std::vector<int> order(R), at(R);
+    for (size_t j = 0; j < R; ++j) order[j] = (int)j;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return rows[x].pos > rows[y].pos; });
+    RunTable* h = b->h_runs;
+    for (size_t r = 0; r < R; ++r) {
+        const int j = order[r];
+        h->off[r] = (unsigned long long)slot[rows[j].run] * 2 * b->slot_floats; h->pos[r] = (int)rows[j].pos; h->tok[r] = tokens[j];
+        at[j] = (int)r;
+    }
+    for (size_t i = 0, j = 0, o = 0; i < n_runs; j += run_len[i], ++i)
+        for (uint32_t u = run_len[i] - n_out[i]; u < run_len[i]; ++u) h->sel[o++] = (uint32_t)at[j + u];
+    HIP_OK(hipSetDevice(c->device));
+    if (k && O && topk_alloc(c, c->sc_rows, (int)k)) return -1;
+    const HostScores hs = host_scores(c);
+    const size_t nk = O * k;
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->runs, h, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+        if (batch_state(c)) return -1;
+        PassForm form; form.skinny = R <= kShortPassMax; form.runs = b->runs_view(); form.max_T = h->pos[0] + 1; form.qkv = b->runs_qkv;
+        form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
+        if (token_rows(c, form.runs.tok, (int)R) || prefill_pass(c, form, (int)R, 0)) return -1;
+        if (!O) return 0;                                // K/V rows only: neither the final norm nor the classifier runs
+        HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)a.dim, (int)O, c->stream));
+        PassForm cls; cls.skinny = O <= kShortPassMax;
+        RowSink to{0, O, logits, k}; to.targets = false; to.reduce_too = true;
+        if (classify_rows(c, cls, to, b->runs_x, 0, (int)O)) return -1;
+        HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream));
+        if (k) {
+            HIP_OK(hipMemcpyAsync(c->h_tk, c->tk_idx, nk * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(c->h_tk + nk * 4, c->tk_val, nk * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
+    };
+    if (enqueue()) return batch_failed(c);
+    if (finish_call(c)) return -1;
+    if (O) memcpy(argmax, hs.idx, O * 4);
+    if (O && k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
     return 0;
 }
 

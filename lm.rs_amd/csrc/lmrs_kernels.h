@@ -220,6 +220,17 @@ hipError_t launch_rope_scatter_rows(float* qkv, float* k_cache, float* v_cache, 
 hipError_t launch_attention_table(const AttnArgs& a, const RowTable* rows, int n_rows, int max_T, hipStream_t s);
 // behind a pass's reduction: out[r] = idx[r], the row's next token = idx[r], its position + 1 (lmrs_batch_generate_greedy's device loop)
 hipError_t launch_table_advance(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s);
+// ---- ragged pass (lmrs_batch_forward_runs): up to kRunRowsMax rows, several of them consecutive tokens of ONE slot.  The same three columns as device arrays
+// of their own, handed to the kernels by value; RowTable and its two kernels stay as they are (their size is part of lmrs_batch_forward's pass).
+constexpr int kRunRowsMax = 512;                                                // = the batched pass's kPrefillTokens
+struct RowView { const unsigned long long* off; const int* pos; const uint32_t* tok; };
+// launch_rope_scatter_rows / launch_attention_table over a RowView (new kernels over the same rotation, stores and attention body).  Every row's K / V is in
+// its slot before the attention launch starts, so a row sees the earlier rows of its own run.
+hipError_t launch_rope_scatter_runs(float* qkv, float* k_cache, float* v_cache, const float* rope, RowView rows, int n_heads, int n_kv_heads, int hs,
+                                    int seq_len, int layer, int n_rows, hipStream_t s);
+hipError_t launch_attention_runs(const AttnArgs& a, RowView rows, int n_rows, int max_T, hipStream_t s);
+// dst[r][0 .. n) = src[sel[r]][0 .. n), r < n_rows (n a multiple of 4): the rows of a pass whose logits were asked for, made consecutive for the classifier
+hipError_t launch_select_rows(const float* src, const uint32_t* sel, float* dst, int n, int n_rows, hipStream_t s);
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

@@ -1105,12 +1105,10 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(const AttnArgs a
 // RoPE + scatter: rope_rows_kernel's rotation (the same four products, one difference and one sum per pair) on the rows of the qkv block, q in place,
 // the key into the slot's blocked K cache, and the value row - which EPI_QKV would have stored itself - into the slot's V cache.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rope_scatter_rows_kernel(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowTable* rows,
-                                                                 int n_heads, int n_kv_heads, int hs, int seq_len, int layer) {
-    const int r = blockIdx.x, pos = rows->pos[r], half = hs / 2;
-    const int att = n_heads * hs, kv = n_kv_heads * hs;
-    const size_t off = (size_t)rows->off[r];
-    float* row = qkv + (size_t)r * (att + 2 * kv);
+// (one row of it: shared with the ragged pass's kernel below)
+__device__ __forceinline__ void rope_scatter_row(float* row, float* k_slot, float* v_slot, const float* rope, int pos, int n_heads, int n_kv_heads, int hs,
+                                                 int seq_len, int layer) {
+    const int half = hs / 2, att = n_heads * hs, kv = n_kv_heads * hs;
     for (int i = threadIdx.x; i < (n_heads + n_kv_heads) * half; i += blockDim.x) {
         const int hh = i / half, j = i - hh * half;
         const float2 cs = *reinterpret_cast<const float2*>(rope + ((size_t)pos * half + j) * 2);
@@ -1122,12 +1120,25 @@ __global__ __launch_bounds__(256) void rope_scatter_rows_kernel(float* qkv, floa
             const int kvh = hh - n_heads;
             const float* p = row + att + kvh * hs;
             const float2 rk = rope_rotate(p[j], p[j + half], cs.x, cs.y);
-            k_store_pair(k_cache + off + ((size_t)layer * n_kv_heads + kvh) * hs * (size_t)seq_len, seq_len, pos, j, half, rk.x, rk.y);
+            k_store_pair(k_slot + ((size_t)layer * n_kv_heads + kvh) * hs * (size_t)seq_len, seq_len, pos, j, half, rk.x, rk.y);
         }
     }
     const float4* v = reinterpret_cast<const float4*>(row + att + kv);                       // (att, kv multiples of 4: prefill_batched_ok)
-    float4* vd = reinterpret_cast<float4*>(v_cache + off + ((size_t)layer * seq_len + pos) * kv);
+    float4* vd = reinterpret_cast<float4*>(v_slot + ((size_t)layer * seq_len + pos) * kv);
     for (int i = threadIdx.x; i < kv / 4; i += blockDim.x) vd[i] = v[i];
+}
+__global__ __launch_bounds__(256) void rope_scatter_rows_kernel(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowTable* rows,
+                                                                 int n_heads, int n_kv_heads, int hs, int seq_len, int layer) {
+    const int r = blockIdx.x;
+    const size_t off = (size_t)rows->off[r];
+    rope_scatter_row(qkv + (size_t)r * (n_heads + 2 * n_kv_heads) * hs, k_cache + off, v_cache + off, rope, rows->pos[r], n_heads, n_kv_heads, hs, seq_len, layer);
+}
+// the ragged pass (RowView): rows of one run share a slot at consecutive positions - distinct cache rows, so the order of the workgroups does not matter
+__global__ __launch_bounds__(256) void rope_scatter_runs_kernel(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowView rows,
+                                                                 int n_heads, int n_kv_heads, int hs, int seq_len, int layer) {
+    const int r = blockIdx.x;
+    const size_t off = (size_t)rows.off[r];
+    rope_scatter_row(qkv + (size_t)r * (n_heads + 2 * n_kv_heads) * hs, k_cache + off, v_cache + off, rope, rows.pos[r], n_heads, n_kv_heads, hs, seq_len, layer);
 }
 
 hipError_t launch_rope_scatter_rows(float* qkv, float* k_cache, float* v_cache, const float* rope, const RowTable* rows, int n_heads, int n_kv_heads, int hs,
@@ -1136,19 +1147,49 @@ hipError_t launch_rope_scatter_rows(float* qkv, float* k_cache, float* v_cache, 
     hipLaunchKernelGGL(rope_scatter_rows_kernel, dim3(n_rows), dim3(256), 0, s, qkv, k_cache, v_cache, rope, rows, n_heads, n_kv_heads, hs, seq_len, layer);
     return hipGetLastError();
 }
+hipError_t launch_rope_scatter_runs(float* qkv, float* k_cache, float* v_cache, const float* rope, RowView rows, int n_heads, int n_kv_heads, int hs,
+                                    int seq_len, int layer, int n_rows, hipStream_t s) {
+    if (n_rows < 1 || n_rows > kRunRowsMax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rope_scatter_runs_kernel, dim3(n_rows), dim3(256), 0, s, qkv, k_cache, v_cache, rope, rows, n_heads, n_kv_heads, hs, seq_len, layer);
+    return hipGetLastError();
+}
 
 // attention_rows_kernel over the table: grid (heads, rows); the workgroup takes its slot and position from its row and runs the same body.  The host
 // has sorted the rows by descending position, so y = 0 is the deepest one.
 template <int HS, bool GEMMA>
-__global__ __launch_bounds__(kBlock) void attention_table_kernel(const AttnArgs a0, const RowTable* rows) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void attention_table_row(const AttnArgs& a0, int r, size_t off, int pos, char* smem) {
     AttnArgs a = a0;
-    const int h = blockIdx.x, r = blockIdx.y, att = a.n_heads * HS, kv = a.n_kv_heads * HS;
-    const size_t off = (size_t)rows->off[r];
+    const int h = blockIdx.x, att = a.n_heads * HS, kv = a.n_kv_heads * HS;
     a.q = a0.q + (size_t)r * (att + 2 * kv); a.out = a0.out + (size_t)r * att; a.dbg = nullptr;
     a.k_cache = a0.k_cache + off; a.v_cache = a0.v_cache + off;
     const uint64_t etab = exp2f_tab_lane();
-    attention_body<HS, kAttF4, false, false, GEMMA, true>(a, h, rows->pos[r], smem, etab);
+    attention_body<HS, kAttF4, false, false, GEMMA, true>(a, h, pos, smem, etab);
+}
+template <int HS, bool GEMMA>
+__global__ __launch_bounds__(kBlock) void attention_table_kernel(const AttnArgs a0, const RowTable* rows) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int r = blockIdx.y;
+    attention_table_row<HS, GEMMA>(a0, r, (size_t)rows->off[r], rows->pos[r], smem);
+}
+// the ragged pass: the same workgroup per (head, row) over a RowView.  Row r of a run at position p reads keys 0 .. p of its slot - the rows of its own run
+// at earlier positions among them, which rope_scatter_runs_kernel has stored before this launch starts; the later ones are never read.
+template <int HS, bool GEMMA>
+__global__ __launch_bounds__(kBlock) void attention_runs_kernel(const AttnArgs a0, const RowView rows) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int r = blockIdx.y;
+    attention_table_row<HS, GEMMA>(a0, r, (size_t)rows.off[r], rows.pos[r], smem);
+}
+
+// the requested rows of a pass made consecutive (lmrs_batch_forward_runs' classifier runs over these only)
+__global__ __launch_bounds__(256) void select_rows_kernel(const float* src, const uint32_t* sel, float* dst, int n4) {
+    const float4* s = reinterpret_cast<const float4*>(src) + (size_t)sel[blockIdx.x] * n4;
+    float4* d = reinterpret_cast<float4*>(dst) + (size_t)blockIdx.x * n4;
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) d[i] = s[i];
+}
+hipError_t launch_select_rows(const float* src, const uint32_t* sel, float* dst, int n, int n_rows, hipStream_t s) {
+    if (n_rows < 1 || n_rows > kRunRowsMax || n % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(select_rows_kernel, dim3(n_rows), dim3(256), 0, s, src, sel, dst, n / 4);
+    return hipGetLastError();
 }
 
 __global__ void table_advance_kernel(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows) {
@@ -1684,6 +1725,23 @@ hipError_t launch_attention_table(const AttnArgs& a0, const RowTable* rows, int 
     {                                                                                                                                 \
         allow_big_lds(reinterpret_cast<const void*>(attention_table_kernel<HS_, G_>));                                                \
         hipLaunchKernelGGL((attention_table_kernel<HS_, G_>), dim3(a.n_heads, n_rows), dim3(kBlock), smem, s, a, rows);                \
+        return hipGetLastError();                                                                                                     \
+    }
+    if (a.gemma) { if (a.head_size == 256) AT(256, true) return hipErrorInvalidValue; }
+    switch (a.head_size) { case 64: AT(64, false) case 96: AT(96, false) case 128: AT(128, false) default: return hipErrorInvalidValue; }
+#undef AT
+}
+
+// launch_attention_table over a RowView of up to kRunRowsMax rows
+hipError_t launch_attention_runs(const AttnArgs& a0, RowView rows, int n_rows, int max_T, hipStream_t s) {
+    AttnArgs a = a0;
+    a.chunk = 64;
+    if (n_rows < 1 || n_rows > kRunRowsMax || max_T < 1 || max_T > a.seq_len || a.chunk * (a.head_size / 4) > kAttF4 * kBlock) return hipErrorInvalidValue;
+    const size_t smem = attention_smem(a.head_size, a.chunk, max_T);
+#define AT(HS_, G_)                                                                                                                   \
+    {                                                                                                                                 \
+        allow_big_lds(reinterpret_cast<const void*>(attention_runs_kernel<HS_, G_>));                                                 \
+        hipLaunchKernelGGL((attention_runs_kernel<HS_, G_>), dim3(a.n_heads, n_rows), dim3(kBlock), smem, s, a, rows);                 \
         return hipGetLastError();                                                                                                     \
     }
     if (a.gemma) { if (a.head_size == 256) AT(256, true) return hipErrorInvalidValue; }

@@ -163,6 +163,27 @@ public:
         check(lmrs_batch_generate_greedy(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), tokens.data(), pos.data(), n_new, out.data(), seconds));
         return out;
     }
+    // One pass over runs of consecutive tokens, one run per slot (a prompt chunk, a draft to verify, one decode row; at most 512 tokens in all): outputs for
+    // the LAST n_out rows of every run, packed in run order - argmax always, logits (x vocab_size) and the k first candidates with their log-probabilities
+    // (x k, as lmrs_score_tokens_topk defines them) when asked for  (lmrs_batch_forward_runs)
+    struct Run { std::uint32_t slot, start_pos; std::vector<std::uint32_t> tokens; std::uint32_t n_out; };
+    struct RunsOut { std::vector<std::uint32_t> argmax; std::vector<float> logits; std::vector<std::uint32_t> topk_idx; std::vector<float> topk_logprob; };
+    RunsOut forward_runs(const std::vector<Run>& runs, std::uint32_t k = 0, bool logits = false) {
+        std::vector<std::uint32_t> slot, start, len, n_out, tokens;
+        std::size_t rows = 0;
+        for (const Run& r : runs) {
+            slot.push_back(r.slot); start.push_back(r.start_pos); len.push_back(static_cast<std::uint32_t>(r.tokens.size())); n_out.push_back(r.n_out);
+            tokens.insert(tokens.end(), r.tokens.begin(), r.tokens.end());
+            rows += r.n_out;
+        }
+        RunsOut o;
+        o.argmax.resize(rows); o.topk_idx.resize(rows * k); o.topk_logprob.resize(rows * k);
+        if (logits) o.logits.resize(rows * vocab_size_);
+        check(lmrs_batch_forward_runs(b_, static_cast<std::uint32_t>(runs.size()), slot.data(), start.data(), len.data(), n_out.data(), tokens.data(),
+                                      rows ? o.argmax.data() : nullptr, logits ? o.logits.data() : nullptr, k, k ? o.topk_idx.data() : nullptr,
+                                      k ? o.topk_logprob.data() : nullptr));
+        return o;
+    }
     void debug_kv(std::uint32_t slot, int which, std::uint32_t layer, std::uint32_t pos, float* out) { check(lmrs_batch_debug_kv(b_, slot, which, layer, pos, out)); }
 
 private:
