@@ -317,6 +317,19 @@ int lmrs_op_tanh_cast(int device, float* y, const float* x, size_t n, double c);
  * maximum and exponentials on the device, the two sequential chains on the host): they are scaled and softmax-ed IN PLACE (as the reference does
  * to the slice) and *token = the draw for the random number rnd.  Unit parity for lmrs_forward_sample. */
 int lmrs_op_sample_mult(int device, float* logits, size_t n, float temperature, float rnd, uint32_t* token);
+/* The kernels of lmrs_batch_forward_sample on caller-supplied rows: Sampler::sample (sampler.rs:109-129) for n_rows (1 .. 16) rows of n logits (any
+ * n >= 1), row r with temperature[r], top_p[r] and the random number rnd[r], everything on the device.  rows: scaled and softmax-ed IN PLACE (rows of
+ * temperature 0 are not touched).  sample_mult rows (top_p <= 0 or >= 1): token[r] = the draw (sampler.rs:43-55).  top-p rows: n0[r] = the candidates
+ * with prob >= (1 - top_p) / (n - 1) and, if pairs != NULL, pairs[r * n .. r * n + n0[r]) = {f32 prob, u32 index} in ascending index order - what
+ * sampler.rs:74-80 leaves in probindex[0 .. n0) and what lmrs_sampler_topp_pairs takes.  token / n0 of the other rows: 0.  Everything else is refused
+ * before the device is touched. */
+int lmrs_op_sample_rows(int device, float* rows, size_t n_rows, size_t n, const float* temperature, const float* top_p, const float* rnd,
+                        uint32_t* token, uint32_t* n0, void* pairs);
+/* Measurement: the six launches behind lmrs_op_sample_rows (scale + maxima, exponentials, the sum chain, the division, the cdf chain, the ordered
+ * candidates) on n_rows rows of n logits whose chains walk all n terms: us6[k] = device microseconds of launch k summed over iters runs (HIP events
+ * on the dispatches, one warm-up run before them); *clock_mhz (optional) = the device's nominal shader clock.  tools/sample_rate.py turns launches 2
+ * and 4 into cycles per term. */
+int lmrs_bench_sample_rows(int device, size_t n_rows, size_t n, int iters, double* us6, double* clock_mhz);
 /* The selection kernels of lmrs_score_tokens_topk / lmrs_forward_topk on one caller-supplied row of n logits of which the first `written` exist
  * (the rest count as 0.0 and are never read): idx[j], val[j] = the rank-j index and its raw value, j < k.  Unit parity for the ordering rule (NaNs,
  * signed zeros, equal values, k = n); extension, no reference counterpart.  k = 0, k > 256 and k > n are refused before the device is touched. */
@@ -449,6 +462,10 @@ int lmrs_sampler_sample(lmrs_sampler* s, float* logits, uint32_t* next);
  * elsewhere: pairs = n0 candidates {f32 prob, u32 index} with prob >= (1 - top_p) / (vocab_size - 1), in index order - what :74-80 leaves
  * in probindex[0 .. n0).  A stand-alone host entry point: the library itself goes through lmrs_sampler_exps_prepare / _finish. */
 int lmrs_sampler_topp_pairs(lmrs_sampler* s, const void* pairs, size_t n0, uint32_t* next);
+/* The same for a caller that has also sorted this call's n0 candidates: sorted_pairs by descending prob, ties in index order - exactly what the
+ * stable sort of :81 makes of the index-ordered candidates (lmrs_batch_forward_sample sorts a flat row's candidates on the device).  The merge
+ * with the stale rest of the persistent vector, the cumulative cut and the draw run here. */
+int lmrs_sampler_topp_sorted_pairs(lmrs_sampler* s, const void* sorted_pairs, size_t n0, uint32_t* next);
 /* Sampler::sample from the softmax's exponentials on (functional.rs:134-139, then sampler.rs:119-128): exps[i] = exp(logits[i] / temperature - max)
  * were formed elsewhere (lmrs_forward_sample forms them on the device); the sequential sum, the division, and sample_mult / sample_topp run here.
  * exps become the probabilities in place.  Same token and probabilities as lmrs_sampler_sample on the logits. */
@@ -472,6 +489,26 @@ int lmrs_sampler_info(const lmrs_sampler* s, uint32_t* vocab_size, float* temper
  * add is ~1 ns on a host core and ~2.5 ns on one GPU lane; this split was measured at profiles/r5_sampler_rate.txt.  Same token as
  * lmrs_forward + lmrs_sampler_sample in every case.  One-GPU contexts (sharded ones copy the gathered logits). */
 int lmrs_forward_sample(lmrs_ctx* ctx, uint32_t token, uint32_t pos, lmrs_sampler* sampler, uint32_t* next);
+/* lmrs_batch_forward with a sampler per row (extension): ONE weight pass for n rows (1 .. 16), row i = Transformer::forward(tokens[i], pos[i]) on
+ * slot[i]'s cache followed by Sampler::sample (sampler.rs:109-129) with samplers[i].  next[i] is, bit for bit, what lmrs_forward_sample returns for
+ * that sampler on a context that holds only that sequence; the K/V rows are as lmrs_batch_forward leaves them; rows may mix samplers freely.
+ * Temperature-0 rows take the pass's own argmax.  The others are sampled ON THE DEVICE, all rows at once: scaling, maximum and exponentials in
+ * parallel; then the softmax sum and sample_mult's running cdf - one sequential f32 chain per row, which is why lmrs_forward_sample leaves them to
+ * the host - as one chain per row side by side (16 rows cost the device the time of one, the host the time of 16); top-p rows leave their
+ * candidates {prob, index} in index order.  ONE transfer brings back every row's token or candidate count and the first 4096
+ * (LMRS_TOPP_DEVICE_SORT_MIN) candidates: 8 bytes a row for argmax / sample_mult rows instead of the vocab_size floats lmrs_batch_forward's logits
+ * cost.  Top-p rows finish on the host in row order - lmrs_sampler_topp_pairs, each sampler's persistent vector updated exactly as that call
+ * updates it; a row with 4096 candidates or more (a flat distribution) first has them sorted on the device (as lmrs_forward_sample does), one
+ * such row at a time behind a second synchronise, and finishes through lmrs_sampler_topp_sorted_pairs.
+ * There is no device-resident sampled loop: sample_topp's stale candidate vector lives in the host sampler, so a loop that includes the default
+ * sampler cannot run a step without a host round trip.
+ * Errors, each with a message of its own, before any device work, batch, context and samplers left usable: everything lmrs_batch_forward checks;
+ * a NULL array; a NULL sampler (the row is named); a sampler made for another vocabulary size; a top-p sampler that appears twice in one call (it
+ * carries state; argmax and sample_mult samplers are stateless and may be shared); a vocabulary whose last vocab_size % 4 logits the classifier
+ * leaves unwritten.  A top-p row without a candidate fails the call with sample_topp's message and the row's number (the reference panics there).
+ * The candidate buffers (16 * (vocab_size + 1) * 8 bytes on the device) are allocated at the first call with a sampled row, all or nothing. */
+int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
+                              lmrs_sampler* const* samplers, uint32_t* next);
 
 #ifdef __cplusplus
 }

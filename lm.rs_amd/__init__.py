@@ -29,7 +29,7 @@ EXPORTS = [
     "lmrs_prefill_tokens", "lmrs_tokens_path", "lmrs_score_tokens_topk", "lmrs_forward_topk", "lmrs_op_topk",
     "lmrs_verify_tokens", "lmrs_draft_lookup", "lmrs_generate_speculative", "lmrs_debug_gemm_skinny",
     "lmrs_batch_create", "lmrs_batch_destroy", "lmrs_batch_prefill", "lmrs_batch_fork", "lmrs_batch_forward", "lmrs_batch_generate_greedy",
-    "lmrs_batch_debug_kv", "lmrs_batch_forward_runs",
+    "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -111,6 +111,10 @@ def lib():
         L.lmrs_batch_generate_greedy.argtypes = [vp, u32, vp, vp, vp, u32, vp, C.POINTER(C.c_double)]
         L.lmrs_batch_debug_kv.argtypes = [vp, u32, C.c_int, u32, u32, vp]
         L.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.lmrs_batch_forward_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.lmrs_op_sample_rows.argtypes = [C.c_int, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.lmrs_sampler_topp_sorted_pairs.argtypes = [vp, vp, sz, C.POINTER(u32)]
+        L.lmrs_bench_sample_rows.argtypes = [C.c_int, sz, sz, C.c_int, vp, C.POINTER(C.c_double)]
         L.lmrs_op_matmul_q8.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.lmrs_op_matmul_q4.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz]
         L.lmrs_op_quantize.argtypes = [C.c_int, vp, vp, vp, sz, sz]
@@ -416,6 +420,18 @@ class Batch:
         _chk(lib().lmrs_batch_forward(self._h, s.size, _p(s), _p(t), _p(p), _p(am), _p(lg) if logits else None))
         return (am, lg) if logits else am
 
+    def forward_sample(self, slots, tokens, pos, samplers):
+        """One pass, then Sampler.sample per row ON THE DEVICE: row i = forward(tokens[i], pos[i]) on slot slots[i], sampled with samplers[i] (one
+        Sampler per row; rows may mix argmax, sample_mult and top-p samplers; a top-p sampler in at most one row) -> next uint32 [n], bit for bit
+        Transformer.forward_sample's token for that sampler on a model that holds only that sequence (lmrs_batch_forward_sample)"""
+        s, t, p = self._rows(slots, tokens, pos)
+        if len(samplers) != s.size:
+            raise LmrsError("slots, tokens, pos and samplers must have one entry per row")
+        hs = (C.c_void_p * max(s.size, 1))(*[None if x is None else x._h for x in samplers])
+        nxt = np.empty(s.size, np.uint32)
+        _chk(lib().lmrs_batch_forward_sample(self._h, s.size, _p(s), _p(t), _p(p), C.cast(hs, C.c_void_p), _p(nxt)))
+        return nxt
+
     def forward_runs(self, runs, k: int = 0, logits: bool = False):
         """One pass over runs = [(slot, start_pos, tokens, n_out), ...]: run i feeds its tokens at start_pos .. of its slot (a prompt chunk, a draft, one
         decode row; a slot in at most one run, at most 512 tokens in all) and returns outputs for its LAST n_out rows, packed in run order: argmax uint32 [O];
@@ -573,6 +589,32 @@ def sample_mult(logits, temperature: float, rnd: float, device=0):
     tok = C.c_uint32()
     _chk(lib().lmrs_op_sample_mult(device, _p(lg), lg.size, C.c_float(temperature), C.c_float(rnd), C.byref(tok)))
     return tok.value, lg
+
+
+def op_sample_rows(rows, temperature, top_p, rnd, pairs: bool = True, device=0):
+    """Sampler::sample on the device for up to 16 rows of logits at once, row r with temperature[r], top_p[r] and the random number rnd[r]
+    (lmrs_op_sample_rows) -> (probabilities float32 [n_rows, n] - rows of temperature 0 untouched -, token uint32 [n_rows] of the sample_mult rows,
+    n0 uint32 [n_rows] of the top-p rows, and with pairs a list of the top-p rows' candidates (prob float32 [n0], index uint32 [n0]) in index order)"""
+    x = np.ascontiguousarray(rows, np.float32).copy()
+    if x.ndim != 2:
+        raise LmrsError("op_sample_rows: rows must be [n_rows, n]")
+    t, p, r = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (temperature, top_p, rnd))
+    if not t.size == p.size == r.size == x.shape[0]:
+        raise LmrsError("op_sample_rows: one temperature, top_p and rnd per row")
+    tok, n0 = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.uint32)
+    pr = np.zeros(x.shape, dtype=[("prob", np.float32), ("index", np.uint32)]) if pairs else None
+    _chk(lib().lmrs_op_sample_rows(device, _p(x), x.shape[0], x.shape[1], _p(t), _p(p), _p(r), _p(tok), _p(n0), _p(pr) if pairs else None))
+    if not pairs:
+        return x, tok, n0
+    return x, tok, n0, [(pr[i, : n0[i]]["prob"].copy(), pr[i, : n0[i]]["index"].copy()) for i in range(x.shape[0])]
+
+
+def bench_sample_rows(n_rows: int, n: int, iters: int = 5, device=0):
+    """device microseconds per run of the six launches behind op_sample_rows with both chains walking all n terms, and the nominal shader clock in MHz
+    (lmrs_bench_sample_rows)"""
+    us = np.zeros(6, np.float64); mhz = C.c_double()
+    _chk(lib().lmrs_bench_sample_rows(device, n_rows, n, iters, _p(us), C.byref(mhz)))
+    return us / iters, mhz.value
 
 
 def tanh_cast(x, c=1.0, device=0):
@@ -743,6 +785,14 @@ class Sampler:
         pairs["prob"] = prob; pairs["index"] = index
         nxt = C.c_uint32()
         _chk(lib().lmrs_sampler_topp_pairs(self._h, _p(pairs) if prob.size else None, prob.size, C.byref(nxt)))
+        return nxt.value
+
+    def topp_sorted_pairs(self, prob: np.ndarray, index: np.ndarray) -> int:
+        """topp_pairs for candidates the caller has also sorted, by descending prob, ties in index order (lmrs_sampler_topp_sorted_pairs)"""
+        pairs = np.zeros(prob.size, dtype=[("prob", np.float32), ("index", np.uint32)])
+        pairs["prob"] = prob; pairs["index"] = index
+        nxt = C.c_uint32()
+        _chk(lib().lmrs_sampler_topp_sorted_pairs(self._h, _p(pairs) if prob.size else None, prob.size, C.byref(nxt)))
         return nxt.value
 
     def info(self):

@@ -1236,6 +1236,21 @@ extern "C" int lmrs_forward_argmax(lmrs_ctx* c, uint32_t token, uint32_t pos, ui
     return 0;
 }
 
+// the device sort's buffers (launch_sample_topp_sort): keys, the count word behind them, the sorted pairs and their pinned copy - once, for the whole
+// vocabulary of n entries, at the first call that sorts N keys
+static int samp_sort_alloc(lmrs_ctx* c, int N, size_t n) {
+    if (c->samp_keys && c->samp_cap >= N) return 0;
+    if (c->samp_keys) { (void)hipFree(c->samp_keys); c->samp_keys = nullptr; }
+    if (c->samp_pairs) { (void)hipFree(c->samp_pairs); c->samp_pairs = nullptr; }
+    if (c->h_pairs) { (void)hipHostFree(c->h_pairs); c->h_pairs = nullptr; }
+    int cap = sample_sort_min_n();
+    while ((size_t)cap < n) cap <<= 1;                                               // once, for the whole vocabulary
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->samp_keys), (size_t)cap * 8 + 256));
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->samp_pairs), (size_t)cap * 8));
+    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->h_pairs), (size_t)cap * 8 + 8, hipHostMallocDefault));
+    c->samp_cap = cap;
+    return 0;
+}
 struct lmrs_sampler;
 extern "C" int lmrs_sampler_info(const lmrs_sampler* s, uint32_t* vocab_size, float* temperature, float* top_p, float* rnd);
 extern "C" int lmrs_sampler_sample(lmrs_sampler* s, float* logits, uint32_t* next);
@@ -1267,17 +1282,7 @@ extern "C" int lmrs_forward_sample(lmrs_ctx* c, uint32_t token, uint32_t pos, lm
     // the same sum by the same IEEE division, so the device finds the same n0 candidates (checked) - and only the sorted pairs come back
     int N = sample_sort_min_n();
     while ((size_t)N < n0) N <<= 1;
-    if (!c->samp_keys || c->samp_cap < N) {
-        if (c->samp_keys) { (void)hipFree(c->samp_keys); c->samp_keys = nullptr; }
-        if (c->samp_pairs) { (void)hipFree(c->samp_pairs); c->samp_pairs = nullptr; }
-        if (c->h_pairs) { (void)hipHostFree(c->h_pairs); c->h_pairs = nullptr; }
-        int cap = sample_sort_min_n();
-        while ((size_t)cap < n) cap <<= 1;                                               // once, for the whole vocabulary
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->samp_keys), (size_t)cap * 8 + 256));
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->samp_pairs), (size_t)cap * 8));
-        HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->h_pairs), (size_t)cap * 8 + 8, hipHostMallocDefault));
-        c->samp_cap = cap;
-    }
+    if (samp_sort_alloc(c, N, n)) return -1;
     unsigned* count = reinterpret_cast<unsigned*>(c->samp_keys + c->samp_cap);           // (the word behind the keys)
     HIP_OK(launch_sample_topp_sort(c->logits, (int)n, sum, cutoff, N, c->samp_keys, count, c->samp_pairs, c->stream));
     HIP_OK(hipMemcpyAsync(c->h_pairs, c->samp_pairs, n0 * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2007,6 +2012,10 @@ struct lmrs_batch {
     uint32_t *out = nullptr, *h_out = nullptr;          // generate_greedy: [n_new][n] results of the passes, and their pinned copy (seq_len x 16)
     RunTable *runs = nullptr, *h_runs = nullptr;        // forward_runs: the long table and its pinned source,
     float *runs_qkv = nullptr, *runs_x = nullptr;       // its [kRunRowsMax][att + 2 kv] qkv block and the [kRunRowsMax][dim] rows picked for the classifier
+    // forward_sample (allocated at the first call with a sampled row, all or nothing): the rows' sampler table and its pinned source, launch_sample_rows'
+    // scratch, the result blocks ([kRowTableMax][vocab + 1] words: {token, n0}, then the candidates) and the pinned copy of their heads (head_words each)
+    SampleRow *samp_tab = nullptr, *h_samp_tab = nullptr; float* samp_scratch = nullptr;
+    unsigned long long *samp_out = nullptr, *h_samp_heads = nullptr; size_t head_words = 0;
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
     float* k_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->k_cache : kv + (size_t)slot * 2 * slot_floats; }
     float* v_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->v_cache : kv + (size_t)slot * 2 * slot_floats + slot_floats; }
@@ -2016,7 +2025,9 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->c->device);
     (void)hipStreamSynchronize(b->c->stream);
-    for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x, (void*)b->samp_tab, (void*)b->samp_scratch, (void*)b->samp_out}) if (p) (void)hipFree(p);
+    if (b->h_samp_tab) (void)hipHostFree(b->h_samp_tab);
+    if (b->h_samp_heads) (void)hipHostFree(b->h_samp_heads);
     if (b->h_tab) (void)hipHostFree(b->h_tab);
     if (b->h_runs) (void)hipHostFree(b->h_runs);
     if (b->h_out) (void)hipHostFree(b->h_out);
@@ -2187,6 +2198,110 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     if (finish_call(c)) return -1;
     for (uint32_t j = 0; j < n_new; ++j) for (uint32_t r = 0; r < n; ++r) out_tokens[(size_t)order[r] * n_new + j] = b->h_out[(size_t)j * n + r];
     if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
+    return 0;
+}
+
+// ------------------------------------------------------------------ the sampled step: lmrs_batch_forward's pass, then Sampler::sample per row
+// (per row Transformer::forward + Sampler::sample, sampler.rs:109-129, with the row's own sampler: bit for bit lmrs_forward_sample on a context that holds
+// only that sequence).  Temperature-0 rows take the pass's reduction; the others go through launch_sample_rows over the logits block, in place - the two
+// sequential chains of every row side by side on the device.  One transfer brings back each row's {token, n0} and the head of its candidates; sample_topp's
+// persistent vector lives in the host sampler, so top-p rows finish there (lmrs_sampler_topp_pairs), a flat row through the device sort first.
+extern "C" int lmrs_sampler_topp_pairs(lmrs_sampler* s, const void* pairs, size_t n0, uint32_t* next);
+extern "C" int lmrs_sampler_topp_sorted_pairs(lmrs_sampler* s, const void* sorted_pairs, size_t n0, uint32_t* next);
+static size_t sample_scratch_floats(size_t rows) { return rows * (kSampleRowsGrid + 1) + rows + rows * kSampleRowsGrid; }
+static SampleRowsArgs sample_rows_args(float* rows, int n_rows, int ld, int n, const SampleRow* tab, const uint32_t* argmax, float* scratch, unsigned long long* out) {
+    float* sum = scratch + (size_t)n_rows * (kSampleRowsGrid + 1);
+    return SampleRowsArgs{rows, n_rows, ld, n, tab, argmax, scratch, sum, reinterpret_cast<unsigned*>(sum + n_rows), out};
+}
+static int batch_sample_alloc(lmrs_batch* b) {
+    if (b->samp_out) return 0;
+    const lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, R = kRowTableMax, head = 1 + std::min<size_t>(V, c->sw.topp_sort_min);
+    bool ok = hipMalloc(reinterpret_cast<void**>(&b->samp_tab), R * sizeof(SampleRow)) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_samp_tab), R * sizeof(SampleRow), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->samp_scratch), sample_scratch_floats(R) * 4) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_samp_heads), R * head * 8, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->samp_out), R * (V + 1) * 8) == hipSuccess;      // (last: what every later call tests)
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void** p : {(void**)&b->samp_tab, (void**)&b->samp_scratch, (void**)&b->samp_out}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        for (void** p : {(void**)&b->h_samp_tab, (void**)&b->h_samp_heads}) if (*p) { (void)hipHostFree(*p); *p = nullptr; }
+        return fail("lmrs_batch_forward_sample: " + std::to_string(R * (V + 1) * 8) + " bytes of candidate buffers: out of memory");
+    }
+    b->head_words = head;
+    return 0;
+}
+
+extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
+                                         lmrs_sampler* const* samplers, uint32_t* next) {
+    const std::string what = "lmrs_batch_forward_sample: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (!slot || !tokens || !pos || !samplers || !next) return fail(what + "NULL array");
+    lmrs_ctx* c = b->c;
+    int order[kRowTableMax], at[kRowTableMax];
+    if (batch_rows(b, "lmrs_batch_forward_sample", n, slot, tokens, pos, 1, order)) return -1;
+    const size_t V = c->args.vocab_size;
+    SampleRow par[kRowTableMax]; bool topp[kRowTableMax]; bool sampled = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string row = what + "row " + std::to_string(i) + ": ";
+        if (!samplers[i]) return fail(row + "the sampler is NULL");
+        uint32_t vs = 0;
+        if (lmrs_sampler_info(samplers[i], &vs, &par[i].temperature, &par[i].top_p, &par[i].rnd)) return -1;
+        if (vs != V) return fail(row + "the sampler was made for another vocabulary size (" + std::to_string(vs) + ", the model has " + std::to_string(V) + ")");
+        topp[i] = par[i].temperature != 0.0f && !(par[i].top_p <= 0.0f || par[i].top_p >= 1.0f);         // sampler.rs:117-126
+        sampled = sampled || par[i].temperature != 0.0f;
+        // (a top-p sampler carries its candidate vector from call to call: two rows of one call cannot both be "the next call")
+        for (uint32_t j = 0; j < i && topp[i]; ++j)
+            if (samplers[j] == samplers[i]) return fail(row + "the top-p sampler of row " + std::to_string(j) + " appears twice (it carries state from call to call)");
+    }
+    if (sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
+    HIP_OK(hipSetDevice(c->device));
+    if (sampled && batch_sample_alloc(b)) return -1;
+    for (uint32_t r = 0; r < n; ++r) { at[order[r]] = (int)r; if (sampled) b->h_samp_tab[r] = par[order[r]]; }
+    const size_t head = b->head_words;
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
+        if (batch_state(c)) return -1;
+        if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx; the rows stay in sc_logits
+        if (!sampled) { HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
+        HIP_OK(hipMemcpyAsync(b->samp_tab, b->h_samp_tab, n * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(launch_sample_rows(sample_rows_args(c->sc_logits, (int)n, (int)V, (int)V, b->samp_tab, c->sc_idx, b->samp_scratch, b->samp_out), c->stream));
+        // THE transfer: every row's {token, n0} and the first head - 1 of its candidates
+        HIP_OK(hipMemcpy2DAsync(b->h_samp_heads, head * 8, b->samp_out, (V + 1) * 8, head * 8, n, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    if (enqueue()) return batch_failed(c);
+    if (finish_call(c)) return -1;
+    if (!sampled) { for (uint32_t r = 0; r < n; ++r) next[order[r]] = b->h_out[r]; return 0; }
+    for (uint32_t i = 0; i < n; ++i) {                   // in row order: the host samplers move as n calls of lmrs_forward_sample would move them
+        const int r = at[i];
+        const unsigned long long* blk = b->h_samp_heads + (size_t)r * head;
+        const uint32_t tok = (uint32_t)blk[0], n0 = (uint32_t)(blk[0] >> 32);
+        if (!topp[i]) { next[i] = tok; continue; }
+        if (n0 > V) return fail(what + "row " + std::to_string(i) + ": the device reported " + std::to_string(n0) + " candidates");
+        if (n0 < c->sw.topp_sort_min || n0 == 0) {
+            if (lmrs_sampler_topp_pairs(samplers[i], blk + 1, n0, &next[i])) return fail(what + "row " + std::to_string(i) + ": " + g_err);
+            continue;
+        }
+        // a flat row: the candidates' sort (sampler.rs:81) on the device, over the row's probabilities as they stand in the logits block - p / 1.0f is p, so
+        // the keys are those of the probabilities the filter saw and the sort must find the same n0
+        int N = sample_sort_min_n();
+        while ((size_t)N < n0) N <<= 1;
+        if (samp_sort_alloc(c, N, V)) return -1;
+        const float cutoff = (1.0f - par[i].top_p) / (float)(V - 1);
+        unsigned* count = reinterpret_cast<unsigned*>(c->samp_keys + c->samp_cap);
+        auto sort = [&]() -> int {
+            HIP_OK(launch_sample_topp_sort(c->sc_logits + (size_t)r * V, (int)V, 1.0f, cutoff, N, c->samp_keys, count, c->samp_pairs, c->stream));
+            HIP_OK(hipMemcpyAsync(c->h_pairs, c->samp_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(c->h_pairs) + (size_t)c->samp_cap * 8, count, 4, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (sort()) return batch_failed(c);
+        HIP_OK(hipStreamSynchronize(c->stream));
+        unsigned dev_n0 = 0; memcpy(&dev_n0, reinterpret_cast<char*>(c->h_pairs) + (size_t)c->samp_cap * 8, 4);
+        if (dev_n0 != n0) return fail(what + "row " + std::to_string(i) + ": the sort found " + std::to_string(dev_n0) + " top-p candidates, the filter " + std::to_string(n0));
+        if (lmrs_sampler_topp_sorted_pairs(samplers[i], c->h_pairs, n0, &next[i])) return fail(what + "row " + std::to_string(i) + ": " + g_err);
+    }
     return 0;
 }
 
@@ -2663,6 +2778,71 @@ extern "C" int lmrs_op_sample_mult(int device, float* logits, size_t n, float te
     for (size_t i = 0; i < n; ++i) logits[i] = logits[i] / sum;
     float cdf = 0.0f; *token = (uint32_t)(n - 1);
     for (size_t i = 0; i < n; ++i) { cdf = cdf + logits[i]; if (rnd < cdf) { *token = (uint32_t)i; break; } }
+    return 0;
+}
+
+// launch_sample_rows on caller-supplied rows (unit parity against Sampler::sample on the same logits): the rows become the probabilities of their softmax
+// (temperature 0: untouched), token[r] for sample_mult rows, n0[r] and pairs[r * n ..] - {f32 prob, u32 index} in index order - for top-p rows
+extern "C" int lmrs_op_sample_rows(int device, float* rows, size_t n_rows, size_t n, const float* temperature, const float* top_p, const float* rnd,
+                                   uint32_t* token, uint32_t* n0, void* pairs) {
+    if (!rows || !temperature || !top_p || !rnd || !token || !n0) return fail("lmrs_op_sample_rows: NULL argument");
+    if (n_rows < 1 || n_rows > (size_t)kSampleRowsMax) return fail("lmrs_op_sample_rows: n_rows = " + std::to_string(n_rows) + " is outside 1 .. " + std::to_string(kSampleRowsMax));
+    if (n < 1 || n > (size_t)0x7FFFFFFF / 2) return fail("lmrs_op_sample_rows: need 1 <= n < 2^30");
+    if (op_begin(device)) return -1;
+    Scratch S;
+    void *dl = S.get(n_rows * n * 4), *dt = S.get(n_rows * sizeof(SampleRow)), *ds = S.get(sample_scratch_floats(n_rows) * 4), *dout = S.get(n_rows * (n + 1) * 8);
+    if (!dl || !dt || !ds || !dout) return fail("hipMalloc failed");
+    std::vector<SampleRow> tab(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) tab[r] = SampleRow{temperature[r], top_p[r], rnd[r]};
+    HIP_OK(hipMemcpy(dl, rows, n_rows * n * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dt, tab.data(), n_rows * sizeof(SampleRow), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dout, 0, n_rows * (n + 1) * 8));
+    HIP_OK(launch_sample_rows(sample_rows_args(static_cast<float*>(dl), (int)n_rows, (int)n, (int)n, static_cast<const SampleRow*>(dt), nullptr,
+                                               static_cast<float*>(ds), static_cast<unsigned long long*>(dout)), nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(rows, dl, n_rows * n * 4, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < n_rows; ++r) {
+        unsigned long long h = 0;
+        const char* blk = static_cast<const char*>(dout) + r * (n + 1) * 8;
+        HIP_OK(hipMemcpy(&h, blk, 8, hipMemcpyDeviceToHost));
+        token[r] = (uint32_t)h; n0[r] = (uint32_t)(h >> 32);
+        if (n0[r] > n) return fail("lmrs_op_sample_rows: row " + std::to_string(r) + ": the device reported " + std::to_string(n0[r]) + " candidates");
+        if (pairs && n0[r]) HIP_OK(hipMemcpy(static_cast<char*>(pairs) + r * n * 8, blk + 8, (size_t)n0[r] * 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// measurement: the six launches of launch_sample_rows on n_rows rows of n equal logits, every row a sample_mult row whose random number no cdf reaches - both
+// chains walk all n terms.  us6[k] = the device time of launch k (HIP events on the dispatch itself), summed over iters runs after one warm-up;
+// *clock_mhz = the device's nominal shader clock
+extern "C" int lmrs_bench_sample_rows(int device, size_t n_rows, size_t n, int iters, double* us6, double* clock_mhz) {
+    if (!us6 || iters < 1 || n_rows < 1 || n_rows > (size_t)kSampleRowsMax || n < 1 || n > (size_t)0x7FFFFFFF / 2) return fail("lmrs_bench_sample_rows: bad argument");
+    if (op_begin(device)) return -1;
+    Scratch S;
+    void *dl = S.get(n_rows * n * 4), *dt = S.get(n_rows * sizeof(SampleRow)), *ds = S.get(sample_scratch_floats(n_rows) * 4), *dout = S.get(n_rows * (n + 1) * 8);
+    if (!dl || !dt || !ds || !dout) return fail("hipMalloc failed");
+    std::vector<SampleRow> tab(n_rows, SampleRow{0.8f, 1.0f, 2.0f});
+    HIP_OK(hipMemcpy(dt, tab.data(), n_rows * sizeof(SampleRow), hipMemcpyHostToDevice));
+    const SampleRowsArgs a = sample_rows_args(static_cast<float*>(dl), (int)n_rows, (int)n, (int)n, static_cast<const SampleRow*>(dt), nullptr,
+                                              static_cast<float*>(ds), static_cast<unsigned long long*>(dout));
+    hipEvent_t ev[12]; int tags[6];
+    for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+    for (int k = 0; k < 6; ++k) us6[k] = 0.0;
+    int rc = 0;
+    for (int it = -1; it < iters && !rc; ++it) {
+        if (hipMemset(dl, 0, n_rows * n * 4) != hipSuccess) { rc = fail("hipMemset failed"); break; }
+        set_launch_event_pool(ev, 6, tags);
+        const hipError_t le = launch_sample_rows(a, nullptr);
+        const int used = launch_event_pool_used();
+        set_launch_event_pool(nullptr, 0);
+        if (le != hipSuccess || hipDeviceSynchronize() != hipSuccess || used != 6) { rc = fail("lmrs_bench_sample_rows: the launches failed"); break; }
+        for (int k = 0; k < 6 && it >= 0; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess) { rc = fail("hipEventElapsedTime failed"); break; } us6[k] += (double)ms * 1e3; }
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    if (rc) return -1;
+    int khz = 0;
+    HIP_OK(hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, device));
+    if (clock_mhz) *clock_mhz = khz / 1000.0;
     return 0;
 }
 

@@ -144,6 +144,20 @@ hipError_t launch_sample_exps(const SampleArgs& a, hipStream_t s);
 hipError_t launch_sample_topp_sort(const float* exps, int n, float sum, float cutoff, int N, unsigned long long* keys, unsigned* count, float* pairs_out, hipStream_t s);
 int sample_sort_min_n();
 
+// ---- Sampler::sample on up to kRowTableMax logit rows at once (lmrs_batch_forward_sample; see lmrs_kernels.hip): row r = rows + r * ld, n entries, sampled
+// with tab[r] (device memory); temperature 0: the row is not touched and its token is argmax[r] (argmax null: 0).  In place: the rows become probabilities.
+// out: n_rows blocks of (n + 1) 8-byte words - word 0 = {u32 token (argmax / sample_mult rows), u32 n0 (top-p rows, else 0)}, then a top-p row's n0
+// candidates {f32 prob, u32 index} in ascending index order.  part: n_rows * (kSampleRowsGrid + 1) floats, sum: n_rows floats, cnt: n_rows * kSampleRowsGrid words.
+struct SampleRow { float temperature, top_p, rnd; };
+constexpr int kSampleRowsGrid = 64;
+constexpr int kSampleRowsMax = 16;               // = kRowTableMax
+struct SampleRowsArgs {
+    float* rows; int n_rows, ld, n;
+    const SampleRow* tab; const uint32_t* argmax;
+    float* part; float* sum; unsigned* cnt; unsigned long long* out;
+};
+hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s);
+
 // thin kernels over the same device functions, for the lmrs_op_* unit-parity entry points
 hipError_t launch_quantize(const float* x, void* q, float* s, int n, int q4, hipStream_t st);
 // batched prefill on row shards (Q8_0): this shard's slices of n_tok tokens quantised into its exchange block; the gathered blocks as a GEMM operand

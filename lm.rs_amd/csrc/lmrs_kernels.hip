@@ -2769,32 +2769,35 @@ hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s) {
 // sample_topp's sort run on the host (lmrs_sampler_sample_exps, lmrs_text.cpp): round 4 ran the chains here in one wave, lane by lane
 // through the add's DPP operand (~2.5 ns per term against ~1 ns on a host core) and measured it slower than copying the logits.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void sample_scale_max_kernel(const SampleArgs a) {
+// (the bodies as device functions of a row: the one-row kernels below and the many-row kernels of launch_sample_rows run the same code)
+__device__ __forceinline__ void sample_scale_max_row(float* logits, int n, float temperature, float* part) {
     __shared__ float red[kBlock / 64];
     float m = __uint_as_float(0xff800000u);
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock) {
-        const float v = a.logits[i] / a.temperature;
-        a.logits[i] = v;
-        if (i == 0) a.part[gridDim.x] = v;                        // x[0]: where the reference's max scan starts (step 2 needs it after block 0 has overwritten it)
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const float v = logits[i] / temperature;
+        logits[i] = v;
+        if (i == 0) part[gridDim.x] = v;                          // x[0]: where the reference's max scan starts (step 2 needs it after block 0 has overwritten it)
         m = fmaxf(m, v);                                          // (NaNs are skipped here; a NaN at index 0 is put back in step 2)
     }
     m = wave64_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) a.part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
-__global__ __launch_bounds__(kBlock) void sample_exp_kernel(const SampleArgs a, int n_part) {
+__device__ __forceinline__ void sample_exp_row(float* logits, int n, const float* part, int n_part) {
     __shared__ float red[kBlock / 64];
     float m = __uint_as_float(0xff800000u);
-    for (int i = threadIdx.x; i < n_part; i += kBlock) m = fmaxf(m, a.part[i]);
+    for (int i = threadIdx.x; i < n_part; i += kBlock) m = fmaxf(m, part[i]);
     m = wave64_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float x0 = a.part[n_part];
+    const float x0 = part[n_part];
     if (!(x0 == x0)) mx = x0;                                    // max_val starts at x[0] and only moves on a strict `>`: a NaN there stays
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock) a.logits[i] = expf_glibc(a.logits[i] - mx);
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) logits[i] = expf_glibc(logits[i] - mx);
 }
+__global__ __launch_bounds__(kBlock) void sample_scale_max_kernel(const SampleArgs a) { sample_scale_max_row(a.logits, a.n, a.temperature, a.part); }
+__global__ __launch_bounds__(kBlock) void sample_exp_kernel(const SampleArgs a, int n_part) { sample_exp_row(a.logits, a.n, a.part, n_part); }
 // ------------------------------------------------------------------------------------------------
 // sample_topp's sort (sampler.rs:67-81) on the device, for distributions where most of the vocabulary passes the cutoff (a flat one: > 64 k
 // candidates, 7 ms per token in a host stable sort).  The reference fills its candidates in INDEX order and sorts them stably by descending
@@ -2884,6 +2887,186 @@ hipError_t launch_sample_exps(const SampleArgs& a, hipStream_t s) {
     if (a.n <= 0 || !a.logits || !a.part) return hipErrorInvalidValue;
     LMRS_LAUNCH_GRID(sample_scale_max_kernel, dim3(kSampleGrid), kBlock, 0, s, a);
     LMRS_LAUNCH_GRID(sample_exp_kernel, dim3(kSampleGrid), kBlock, 0, s, a, (int)kSampleGrid);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sampler::sample (sampler.rs:109-129) on up to kRowTableMax logit rows at once (launch_sample_rows: lmrs_batch_forward_sample), each row with its own
+// temperature, top_p and random number (the device table a.tab).  Rows of temperature 0 (sample_argmax) are left alone.  Per row, in place:
+//   1. / temperature, maxima; 2. exponentials - the one-row kernels' device functions, one grid row per logits row               [grid x rows]
+//   3. the softmax sum: ONE f32 chain over the n exponentials in index order (functional.rs:134)                                  [one workgroup per row]
+//   4. p = e / sum (:137-139) over contiguous spans of indices, and the span's count of top-p candidates (p >= cutoff, sampler.rs:71-75)  [grid x rows]
+//   5. sample_mult rows: the running cdf, the first i with rnd < cdf, else n - 1 (sampler.rs:43-55) - a chain again, left at the hit   [one workgroup per row]
+//   6. top-p rows: the candidates {p, index} in ASCENDING INDEX order (what sampler.rs:74-80 writes into probindex[0 .. n0)) and n0    [grid x rows]
+// The chains (3, 5): the rows run side by side, one workgroup each; ONE lane of it adds, and nothing it adds crosses lanes.  The other threads only feed
+// it: kRowsChunk floats of the row at a time through two LDS buffers (global loads of chunk c + 1 are in flight while chunk c is added), and the lane
+// reads kRowsUnroll float4 vectors ahead of its adds, the two register sets taken by turns so that the loop holds nothing but the adds (a wave's VALU
+// instruction issues every 4 cycles: every move or compare beside an add is a term's worth of time).  The cdf tests once per 32 terms - the cdf of
+// non-negative terms never falls, so the first hit lies in the first group whose LAST value passes (or is NaN) - and re-walks that group term by term.
+// Result block of row r: a.out + r * (n + 1) words of 8 bytes - word 0 = {token, n0}, then the candidates.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRowsChunk = 2048;                                  // floats of a row per LDS buffer
+constexpr int kRowsUnroll = 8;                                    // float4 vectors per register set: 32 terms
+__host__ __device__ inline int sample_rows_span(int n) {         // indices per workgroup of steps 4 and 6: whole blocks of kBlock
+    const int per = (n + kSampleRowsGrid - 1) / kSampleRowsGrid;
+    return (per + kBlock - 1) / kBlock * kBlock;
+}
+__device__ __forceinline__ bool sample_row_is_topp(float top_p) { return !(top_p <= 0.0f || top_p >= 1.0f); }        // sampler.rs:121
+__device__ __forceinline__ unsigned* sample_row_head(const SampleRowsArgs& a, int r) { return reinterpret_cast<unsigned*>(a.out + (size_t)r * ((size_t)a.n + 1)); }
+
+__global__ __launch_bounds__(kBlock) void batch_sample_scale_max_kernel(const SampleRowsArgs a) {
+    const int r = blockIdx.y;
+    const float t = a.tab[r].temperature;
+    if (t == 0.0f) return;
+    sample_scale_max_row(a.rows + (size_t)r * a.ld, a.n, t, a.part + r * (kSampleRowsGrid + 1));
+}
+__global__ __launch_bounds__(kBlock) void batch_sample_exp_kernel(const SampleRowsArgs a) {
+    const int r = blockIdx.y;
+    if (a.tab[r].temperature == 0.0f) return;
+    sample_exp_row(a.rows + (size_t)r * a.ld, a.n, a.part + r * (kSampleRowsGrid + 1), kSampleRowsGrid);
+}
+// 32 terms onto the chain; CDF: true when the walk is over (found = the token)
+template <bool CDF>
+__device__ __forceinline__ bool sample_chain_group(const float4 (&v)[kRowsUnroll], float& acc, float rnd, int i0, int n, int& found) {
+    const float start = acc;
+#pragma unroll
+    for (int u = 0; u < kRowsUnroll; ++u) { acc = acc + v[u].x; acc = acc + v[u].y; acc = acc + v[u].z; acc = acc + v[u].w; }
+    if (!CDF || acc <= rnd) return false;                         // (one compare per group: rnd < acc, or acc is NaN)
+    float cdf = start;
+#pragma unroll
+    for (int u = 0; u < kRowsUnroll; ++u) {
+        const float t[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cdf = cdf + t[k];
+            const int i = i0 + 4 * u + k;
+            if (found < 0 && rnd < cdf && i < n) found = i;
+        }
+    }
+    if (found < 0 && !(acc == acc)) found = n - 1;                // a NaN: no later value can pass
+    return found >= 0;                                            // (a NaN random number passes nowhere: the walk goes on to n - 1)
+}
+template <bool CDF>
+__global__ __launch_bounds__(kBlock) void batch_sample_chain_kernel(const SampleRowsArgs a) {
+    __shared__ __attribute__((aligned(16))) float buf[2 * kRowsChunk + 4 * kRowsUnroll];         // two buffers; the pad: the lane's last read-ahead of a chunk (never added)
+    __shared__ int stop;
+    const int r = blockIdx.x, tid = threadIdx.x, n = a.n;
+    const SampleRow sr = a.tab[r];
+    if (CDF) {
+        unsigned* head = sample_row_head(a, r);
+        if (tid == 0) head[1] = 0;
+        if (sr.temperature == 0.0f) { if (tid == 0) head[0] = a.argmax ? a.argmax[r] : 0u; return; }
+        if (sample_row_is_topp(sr.top_p)) return;
+    } else if (sr.temperature == 0.0f) return;
+    const float* x = a.rows + (size_t)r * a.ld;
+    constexpr int kPer = kRowsChunk / kBlock, kVecs = kRowsChunk / 4;
+    static_assert(kVecs % (2 * kRowsUnroll) == 0, "the two register sets take whole turns");
+    constexpr int kTurns = CDF ? 1 : kVecs / (2 * kRowsUnroll);
+    float nx[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) { const int i = tid + k * kBlock; buf[i] = i < n ? x[i] : 0.0f; }             // (beyond n: +0.0, which moves neither chain)
+    if (tid == 0) stop = 0;
+    __syncthreads();
+    float acc = 0.0f;
+    int found = -1;
+    const int n_chunks = (n + kRowsChunk - 1) / kRowsChunk;
+    for (int c = 0; c < n_chunks; ++c) {
+        const bool more = c + 1 < n_chunks;
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) { const int i = (c + 1) * kRowsChunk + tid + k * kBlock; nx[k] = i < n ? x[i] : 0.0f; }
+        }
+        if (tid == 0) {
+            const float4* L = reinterpret_cast<const float4*>(buf + (c & 1) * kRowsChunk);
+            float4 va[kRowsUnroll], vb[kRowsUnroll];
+#pragma unroll
+            for (int u = 0; u < kRowsUnroll; ++u) va[u] = L[u];
+            // (the sum's loop is unrolled whole: a rolled one carries both register sets round the back edge and pays a copy of one per turn)
+#pragma unroll kTurns
+            for (int g = 0; g < kVecs; g += 2 * kRowsUnroll) {
+#pragma unroll
+                for (int u = 0; u < kRowsUnroll; ++u) vb[u] = L[g + kRowsUnroll + u];
+                if (sample_chain_group<CDF>(va, acc, sr.rnd, c * kRowsChunk + 4 * g, n, found)) { stop = 1; break; }
+                __builtin_amdgcn_sched_barrier(0);                // (the reload below must not be hoisted above the adds that still read the set: it would cost a copy of it)
+#pragma unroll
+                for (int u = 0; u < kRowsUnroll; ++u) va[u] = L[g + 2 * kRowsUnroll + u];         // (unconditional: a chunk's last one reads past it and is dropped)
+                if (sample_chain_group<CDF>(vb, acc, sr.rnd, c * kRowsChunk + 4 * (g + kRowsUnroll), n, found)) { stop = 1; break; }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) buf[((c + 1) & 1) * kRowsChunk + tid + k * kBlock] = nx[k];
+        }
+        __syncthreads();                                          // chunk c + 1 is whole; the lane is done with buffer c & 1, which chunk c + 2 overwrites
+        if (CDF && stop) break;
+    }
+    if (tid == 0) {
+        if (CDF) sample_row_head(a, r)[0] = (unsigned)(found >= 0 ? found : n - 1);
+        else a.sum[r] = acc;
+    }
+}
+__global__ __launch_bounds__(kBlock) void batch_sample_div_kernel(const SampleRowsArgs a) {
+    __shared__ unsigned total;
+    const int r = blockIdx.y, tid = threadIdx.x, n = a.n;
+    const SampleRow sr = a.tab[r];
+    if (sr.temperature == 0.0f) return;
+    float* x = a.rows + (size_t)r * a.ld;
+    const float sum = a.sum[r];
+    const float cutoff = (1.0f - sr.top_p) / (float)(n - 1);      // sampler.rs:71, in f32
+    const int span = sample_rows_span(n), i0 = blockIdx.x * span, i1 = i0 + span < n ? i0 + span : n;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    unsigned cnt = 0;
+    for (int i = i0 + tid; i < i1; i += kBlock) { const float p = x[i] / sum; x[i] = p; cnt += p >= cutoff ? 1u : 0u; }       // (NaN: never a candidate)
+    if (!sample_row_is_topp(sr.top_p)) return;
+    if (cnt) atomicAdd(&total, cnt);
+    __syncthreads();
+    if (tid == 0) a.cnt[r * kSampleRowsGrid + blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kBlock) void batch_sample_pairs_kernel(const SampleRowsArgs a) {
+    __shared__ unsigned wave_cnt[kBlock / 64];
+    __shared__ unsigned base_s;
+    const int r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n;
+    const SampleRow sr = a.tab[r];
+    if (sr.temperature == 0.0f || !sample_row_is_topp(sr.top_p)) return;
+    const float* x = a.rows + (size_t)r * a.ld;
+    const float cutoff = (1.0f - sr.top_p) / (float)(n - 1);
+    if (tid == 0) {                                               // the candidates of the spans before this one
+        unsigned b = 0;
+        for (int k = 0; k < (int)blockIdx.x; ++k) b += a.cnt[r * kSampleRowsGrid + k];
+        base_s = b;
+        if (blockIdx.x == kSampleRowsGrid - 1) sample_row_head(a, r)[1] = b + a.cnt[r * kSampleRowsGrid + blockIdx.x];       // n0
+    }
+    __syncthreads();
+    unsigned base = base_s;
+    unsigned long long* out = a.out + (size_t)r * ((size_t)n + 1) + 1;
+    const int span = sample_rows_span(n), i0 = blockIdx.x * span;
+    for (int j = i0; j < i0 + span && j < n; j += kBlock) {       // blocks of kBlock indices in order; inside a block: wave by wave, lane by lane
+        const int i = j + tid;
+        float p = 0.0f; bool in = false;
+        if (i < n) { p = x[i]; in = p >= cutoff; }
+        const unsigned long long m = __ballot(in);
+        if (lane == 0) wave_cnt[w] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < kBlock / 64; ++k) { const unsigned ck = wave_cnt[k]; if (k < w) before += ck; all += ck; }
+        if (in) out[base + before + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)(unsigned)i << 32) | __float_as_uint(p);   // {prob, index} as sampler.rs:4-8
+        base += all;
+        __syncthreads();
+    }
+}
+hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s) {
+    static_assert(kSampleRowsMax == kRowTableMax, "a sampled block is a batch pass's rows");
+    if (a.n_rows < 1 || a.n_rows > kSampleRowsMax || a.n < 1 || a.ld < a.n || !a.rows || !a.tab || !a.part || !a.sum || !a.cnt || !a.out) return hipErrorInvalidValue;
+    const dim3 grid(kSampleRowsGrid, a.n_rows);
+    LMRS_LAUNCH_GRID(batch_sample_scale_max_kernel, grid, kBlock, 0, s, a);
+    LMRS_LAUNCH_GRID(batch_sample_exp_kernel, grid, kBlock, 0, s, a);
+    LMRS_LAUNCH_GRID(batch_sample_chain_kernel<false>, dim3(a.n_rows), kBlock, 0, s, a);
+    LMRS_LAUNCH_GRID(batch_sample_div_kernel, grid, kBlock, 0, s, a);
+    LMRS_LAUNCH_GRID(batch_sample_chain_kernel<true>, dim3(a.n_rows), kBlock, 0, s, a);
+    LMRS_LAUNCH_GRID(batch_sample_pairs_kernel, grid, kBlock, 0, s, a);
     return hipGetLastError();
 }
 

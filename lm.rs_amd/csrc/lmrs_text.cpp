@@ -295,6 +295,17 @@ extern "C" int lmrs_sampler_topp_pairs(lmrs_sampler* s, const void* pairs, size_
     return topp_tail(s, n0, random_f32(s->seed), next);
 }
 
+// lmrs_sampler_topp_pairs for a caller that has also SORTED this call's n0 candidates, by (prob descending, index ascending) - what the stable sort of
+// the index-ordered candidates gives (lmrs_batch_forward_sample's flat rows: launch_sample_topp_sort on the device).  The merge with the persistent
+// vector's ordered rest, the cumulative cut and the draw run here: topp_tail(presorted).
+extern "C" int lmrs_sampler_topp_sorted_pairs(lmrs_sampler* s, const void* sorted_pairs, size_t n0, uint32_t* next) {
+    if (!s || (!sorted_pairs && n0) || !next) return text_fail("NULL argument");
+    if (!(s->top_p > 0.0f && s->top_p < 1.0f) || s->temperature == 0.0f) return text_fail("not a top-p sampler");
+    if (n0 > s->probindex.size()) return text_fail("more candidates than the vocabulary has entries");
+    if (n0) memcpy(s->probindex.data(), sorted_pairs, n0 * sizeof(lmrs_sampler::ProbIndex));
+    return topp_tail(s, n0, random_f32(s->seed), next, true);
+}
+
 // Sampler::sample from the softmax's exponentials on (functional.rs:134-139, sampler.rs:119-128), for a caller that formed
 // exps[i] = exp(logits[i] / temperature - max) elsewhere (lmrs_forward_sample: on the device, the only part of the sampler that is parallel work).
 // What is left is the reference's two sequential chains - the softmax sum and the running cdf (or the candidates' sort) - and those run

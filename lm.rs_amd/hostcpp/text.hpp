@@ -55,6 +55,8 @@ public:
     std::uint32_t sample(float* logits) { std::uint32_t next = 0; check(lmrs_sampler_sample(h_, logits, &next)); return next; }
     // model.forward(token, pos) followed by sample(logits), the draw made on the device: only the token id comes back (lmrs_forward_sample)
     std::uint32_t forward_sample(Transformer& model, std::uint32_t token, std::uint32_t pos) { return model.forward_sample(token, pos, h_); }
+    // the C handle, for Batch::forward_sample's row of samplers
+    lmrs_sampler* handle() const { return h_; }
 
 private:
     lmrs_sampler* h_ = nullptr;

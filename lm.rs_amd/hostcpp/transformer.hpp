@@ -155,6 +155,16 @@ public:
         check(lmrs_batch_forward(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), tokens.data(), pos.data(), argmax.data(), logits ? logits->data() : nullptr));
         return argmax;
     }
+    // forward with a sampler per row, sampled on the device: row i = forward(tokens[i], pos[i]) on slot[i] followed by Sampler::sample with samplers[i]
+    // (Sampler::handle(), text.hpp) -> next[i], bit for bit Transformer::forward_sample's token on a transformer that holds only that sequence.  Rows may
+    // mix samplers; a top-p sampler in at most one row of a call  (lmrs_batch_forward_sample)
+    std::vector<std::uint32_t> forward_sample(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
+                                              const std::vector<lmrs_sampler*>& samplers) {
+        if (slot.size() != tokens.size() || slot.size() != pos.size() || slot.size() != samplers.size()) throw Panic("Batch::forward_sample: one slot, token, position and sampler per row");
+        std::vector<std::uint32_t> next(slot.size());
+        check(lmrs_batch_forward_sample(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), tokens.data(), pos.data(), samplers.data(), next.data()));
+        return next;
+    }
     // n_new greedy steps of every row on the device: out[i * n_new + j]
     std::vector<std::uint32_t> generate_greedy(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
                                                std::uint32_t n_new, double* seconds = nullptr) {

@@ -1,10 +1,19 @@
 //! `Batch`: up to 16 sequences a step over the weights of one `Transformer` (extension, no reference counterpart; include/lmrs_hip.h,
 //! `lmrs_batch_*`).  Each slot is a K/V cache of its own; every result is bit for bit what `Transformer::forward` gives on a context that holds
 //! only that sequence.  The borrow keeps the transformer alive and un-aliased while the batch exists.
+use std::os::raw::c_int;
 use std::ptr;
 
-use crate::ffi::{self, check, LmrsBatch};
+use crate::ffi::{self, check, LmrsBatch, LmrsSampler};
+use crate::sampler::Sampler;
 use crate::transformer::Transformer;
+
+// The sampled step (include/lmrs_hip.h, lmrs_batch_forward_sample): declared beside its only caller; the batch block of ffi.rs holds the greedy entry
+// points (tests/test_batch_sample_host.py compares this declaration with the header).
+extern "C" {
+    pub fn lmrs_batch_forward_sample(b: *mut LmrsBatch, n: u32, slot: *const u32, tokens: *const u32, pos: *const u32,
+                                     samplers: *const *mut LmrsSampler, next: *mut u32) -> c_int;
+}
 
 /// `fork`'s source: the transformer's own cache.
 pub const BATCH_CTX: u32 = 0xFFFF_FFFF;
@@ -41,6 +50,18 @@ impl<'t, 'a> Batch<'t, 'a> {
         let lp = if want_logits { logits.as_mut_ptr() } else { ptr::null_mut() };
         check(unsafe { ffi::lmrs_batch_forward(self.b, slot.len() as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), argmax.as_mut_ptr(), lp) });
         (argmax, logits)
+    }
+
+    /// `forward` with a sampler per row, sampled on the device: next[i] = `Transformer::forward_sample(tokens[i], pos[i], samplers[i])` on slot[i].
+    /// Rows may mix samplers; a top-p sampler serves one row of a call (the `&mut` borrows already say so).
+    pub fn forward_sample(&mut self, slot: &[u32], tokens: &[u32], pos: &[u32], samplers: &mut [&mut Sampler]) -> Vec<u32> {
+        assert!(slot.len() == tokens.len() && slot.len() == pos.len() && slot.len() == samplers.len(), "one slot, token, position and sampler per row");
+        let handles: Vec<*mut LmrsSampler> = samplers.iter().map(|s| s.handle).collect();
+        let mut next = vec![0u32; slot.len()];
+        check(unsafe {
+            lmrs_batch_forward_sample(self.b, slot.len() as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), handles.as_ptr(), next.as_mut_ptr())
+        });
+        next
     }
 
     /// `n_new` greedy steps of every row on the device: out[i * n_new + j].

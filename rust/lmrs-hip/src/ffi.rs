@@ -69,6 +69,9 @@ extern "C" {
     pub fn lmrs_sampler_destroy(s: *mut LmrsSampler);
     pub fn lmrs_sampler_sample(s: *mut LmrsSampler, logits: *mut f32, next: *mut u32) -> c_int;
     pub fn lmrs_forward_sample(ctx: *mut LmrsCtx, token: u32, pos: u32, sampler: *mut LmrsSampler, next: *mut u32) -> c_int;
+    pub fn lmrs_sampler_topp_sorted_pairs(s: *mut LmrsSampler, sorted_pairs: *const c_void, n0: usize, next: *mut u32) -> c_int;
+    pub fn lmrs_op_sample_rows(device: c_int, rows: *mut f32, n_rows: usize, n: usize, temperature: *const f32, top_p: *const f32, rnd: *const f32,
+                               token: *mut u32, n0: *mut u32, pairs: *mut c_void) -> c_int;
 }
 
 /// The reference panics (`assert!` / `expect`); the C ABI returns a status and a message.  Same behaviour for the caller.
