@@ -246,6 +246,15 @@ typedef struct lmrs_batch lmrs_batch;
  * all or nothing; the message gives the bytes wanted (n_slots * 2 * n_layers * seq_len * kv_dim * 4). */
 int  lmrs_batch_create(lmrs_ctx* ctx, uint32_t n_slots, lmrs_batch** out);
 void lmrs_batch_destroy(lmrs_batch* b);
+/* lmrs_batch_create with up to 64 slots: a WIDE batch.  Same refusals (each message opens with this call's name), same allocation rule (all or
+ * nothing, the message gives the bytes).  On a wide batch every batch call below works as documented with 64 where it says 16: lmrs_batch_forward
+ * and lmrs_batch_generate_greedy take n up to 64, lmrs_batch_forward_runs up to 64 runs (still at most 512 rows), slots go up to 63; a pass of
+ * 17 .. 64 rows is still ONE weight pass (up to 47 rows gemm_stream_kernel: the skinny kernel's weight stream against 2 .. 3 token tiles; from 48
+ * on the ring kernels of the batched pass) and every output is bit for bit the single-sequence value.  Calls with 16 rows or fewer take the same path as on a batch of lmrs_batch_create.
+ * lmrs_batch_forward_sample keeps 16 rows a call on any batch. */
+int  lmrs_batch_create_wide(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, lmrs_batch** out);
+/* 16 for lmrs_batch_create's batches, 64 for wide ones: the most rows (lmrs_batch_forward, _generate_greedy) and runs (_forward_runs) a call takes. */
+int  lmrs_batch_width(const lmrs_batch* b, uint32_t* width);
 
 /* == lmrs_prefill_tokens, into slot's cache: rows start_pos .. start_pos+n-1 as n forward calls leave them */
 int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n, uint32_t start_pos);
@@ -385,6 +394,10 @@ int lmrs_debug_w13_quant(int device, int8_t* hq, float* hs, const int8_t* xq, co
  * int8 rows the batched pass keeps).  Unit-parity aid, no reference counterpart. */
 int lmrs_debug_gemm_skinny(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
                            size_t n, size_t o, size_t n_tok, int q4);
+/* The same for the stream GEMM of a batch pass of 17 .. 47 rows (gemm_stream_kernel), here at any 1 <= n_tok <= 64: lmrs_debug_gemm_skinny's operands and
+ * shape rules; anything else is refused with this hook's name in the message. */
+int lmrs_debug_gemm_wide(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                         size_t n, size_t o, size_t n_tok, int q4);
 
 /* ---- CLIP image tower of the multimodal models  (src/vision.rs) ---------------------------
  * lmrs_vision_create   <- VisionTransformer::new(data) -> (VisionTransformer, usize)   vision.rs:99-243

@@ -29,7 +29,7 @@ EXPORTS = [
     "lmrs_prefill_tokens", "lmrs_tokens_path", "lmrs_score_tokens_topk", "lmrs_forward_topk", "lmrs_op_topk",
     "lmrs_verify_tokens", "lmrs_draft_lookup", "lmrs_generate_speculative", "lmrs_debug_gemm_skinny",
     "lmrs_batch_create", "lmrs_batch_destroy", "lmrs_batch_prefill", "lmrs_batch_fork", "lmrs_batch_forward", "lmrs_batch_generate_greedy",
-    "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
+    "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -103,7 +103,10 @@ def lib():
         L.lmrs_draft_lookup.argtypes = [vp, sz, u32, u32, vp, C.POINTER(u32)]
         L.lmrs_generate_speculative.argtypes = [vp, vp, sz, u32, u32, u32, u32, vp, vp, C.POINTER(C.c_double)]
         L.lmrs_debug_gemm_skinny.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, C.c_int]
+        L.lmrs_debug_gemm_wide.argtypes = [C.c_int, vp, vp, vp, vp, vp, sz, sz, sz, C.c_int]
         L.lmrs_batch_create.argtypes = [vp, u32, C.POINTER(vp)]
+        L.lmrs_batch_create_wide.argtypes = [vp, u32, C.POINTER(vp)]
+        L.lmrs_batch_width.argtypes = [vp, C.POINTER(u32)]
         L.lmrs_batch_destroy.argtypes = [vp]; L.lmrs_batch_destroy.restype = None
         L.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
         L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
@@ -379,12 +382,21 @@ BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BA
 class Batch:
     """n_slots (1 .. 16) more K/V caches beside a Transformer's own, stepped together: one pass over the weights serves one token of up to 16
     DIFFERENT sequences, each at its own position (lmrs_batch_*).  Every result is bit for bit what forward / forward_argmax give on a model that
-    holds only that sequence.  The model's own cache is untouched by every call here; close the batch before the model."""
+    holds only that sequence.  The model's own cache is untouched by every call here; close the batch before the model.
+    wide=True: up to 64 slots, and forward / generate_greedy / forward_runs take up to 64 rows or runs a call (lmrs_batch_create_wide; forward_sample
+    keeps 16 rows)."""
 
-    def __init__(self, model: Transformer, n_slots: int):
+    def __init__(self, model: Transformer, n_slots: int, wide: bool = False):
         h = C.c_void_p()
-        _chk(lib().lmrs_batch_create(model._h, n_slots, C.byref(h)))
+        _chk((lib().lmrs_batch_create_wide if wide else lib().lmrs_batch_create)(model._h, n_slots, C.byref(h)))
         self._h, self.model, self.n_slots = h, model, n_slots
+
+    @property
+    def width(self) -> int:
+        """The most rows (forward, generate_greedy) and runs (forward_runs) a call takes: 16, or 64 for a wide batch (lmrs_batch_width)"""
+        w = C.c_uint32()
+        _chk(lib().lmrs_batch_width(self._h, C.byref(w)))
+        return w.value
 
     def close(self):
         if getattr(self, "_h", None):
@@ -669,6 +681,14 @@ def draft_lookup(hist, ngram_max: int, max_draft: int) -> np.ndarray:
     d = np.zeros(max(int(max_draft), 1), np.uint32); n = C.c_uint32()
     _chk(lib().lmrs_draft_lookup(_p(h), h.size, ngram_max, max_draft, _p(d), C.byref(n)))
     return d[:n.value].copy()
+
+
+def debug_gemm_wide(xq, xs, wq, ws, n: int, o: int, n_tok: int, q4: bool = False, device: int = 0) -> np.ndarray:
+    """The stream GEMM of a 17 .. 47-row batch pass on caller-supplied operands, here at any 1 <= n_tok <= 64 -> float32 [n_tok, o] (lmrs_debug_gemm_wide)."""
+    xq = np.ascontiguousarray(xq); xs = np.ascontiguousarray(xs, np.float32); wq = np.ascontiguousarray(wq); ws = np.ascontiguousarray(ws, np.float32)
+    out = np.empty((n_tok, o), np.float32)
+    _chk(lib().lmrs_debug_gemm_wide(device, _p(out), _p(xq), _p(xs), _p(wq), _p(ws), n, o, n_tok, int(bool(q4))))
+    return out
 
 
 def debug_gemm_skinny(xq, xs, wq, ws, n: int, o: int, n_tok: int, q4: bool = False, device: int = 0) -> np.ndarray:

@@ -172,7 +172,7 @@ size_t prefill_tp_block(size_t n_l) { return pad256((size_t)kPrefillTokens * n_l
 // The form of one decode step: how it runs qkv + attention (qa_mode, see lmrs_ctx::qkv_att) and, when its attention is the split pair, over how many
 // 256-key chunks (then qa_mode is 0: the merged launch has no split form).  A value handed down to the enqueue functions, never context state.
 struct StepForm { int qa_mode = 0, split_chunks = 0; };
-// The form of one batched pass, a value in the same way: skinny = every GEMM of it, the layers' and the classifier's, in the 16-token form (GemmArgs::skinny)
+// The form of one batched pass, a value in the same way: skinny = every GEMM of it, the layers' and the classifier's, in the weight-streaming forms (GemmArgs::skinny: up to 16 rows, a batch pass up to 64)
 // rows: the pass is lmrs_batch_forward's - row r is one token of its own sequence (the device row table, lmrs_kernels.h; max_T = the deepest row's
 // position + 1); null: m consecutive positions of one sequence, as always.  k_cache / v_cache: the caches the pass reads and writes - a batch's (with
 // rows: the base the table's offsets count from); null: the context's own
@@ -1416,7 +1416,8 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
     const bool table = form.rows || form.runs.tok;
     // scale layouts of this pass: from 48 tokens on every GEMM is a ring kernel, which takes TRANSPOSED scales ([group][row]: GemmArgs::ws_ld / xs_ld) -
     // the weights' transposed copies (prefill_alloc) and activation scales written that way by their producers, leading dimension kPrefillTokens
-    const bool trs = m >= 48 && c->layers[0].sqkvT != nullptr;
+    // (the weight-streaming forms - PassForm::skinny, up to 64 rows - take row-major scales at any row count)
+    const bool trs = m >= 48 && !form.skinny && c->layers[0].sqkvT != nullptr;
     const int xld = trs ? kPrefillTokens : 0;
     auto all_gather = [&](const float* mine, int n_l, char* blocks, size_t cap) -> int {          // mine: [m][n_l] f32 -> pf_xq / pf_xs [m][W * n_l]
         const size_t s_off = (size_t)m * n_l, bytes = s_off + (size_t)m * (n_l / 128) * 4, stride = pad256(bytes);
@@ -1919,6 +1920,9 @@ extern "C" int lmrs_prefill_tokens(lmrs_ctx* c, const uint32_t* tokens, size_t n
 // ------------------------------------------------------------------ short runs in one weight pass: verifying drafted tokens, speculative greedy generate
 // (no reference counterpart: n calls of Transformer::forward + sample_argmax, value for value)
 constexpr size_t kShortPassMax = 16;           // one 16-token MFMA tile: the skinny GEMM's token axis (gemm_skinny_kernel)
+// a batch pass's GEMMs stream the weights up to this many rows (gemm_stream_kernel above 16).  Measured (profiles/batch_wide_*.txt): against
+// the direct kernels the stream kernel wins at 17 .. 47 rows on both models; from 48 rows on the ring kernels beat it (the kernel itself serves up to 64)
+constexpr size_t kStreamPassMax = 47;
 
 // tokens_pass's chain (run_tokens) for m <= 16 tokens already in c->tokens[start_pos ..), with the skinny form - every GEMM, the layers' and the
 // classifier's: one pass over the weights - and the reduction as its sink: the per-position sample_argmax goes to c->sc_idx[0 .. m) on the device.
@@ -2003,9 +2007,11 @@ extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, si
 // launch rotates them and scatters K / V into the rows' slots, and attention_rows_kernel's workgroups take slot and position from the table.
 static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out);   // (with lmrs_debug_kv below)
 // the ragged pass's table (lmrs_batch_forward_runs): RowTable's columns for kRunRowsMax rows, and sel - the table rows whose outputs were asked for, in output order
+constexpr uint32_t kWideBatchMax = 64;         // a wide batch's slots, rows and runs
 struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
 struct lmrs_batch {
     lmrs_ctx* c = nullptr; uint32_t n_slots = 0;
+    uint32_t width = kRowTableMax;                      // the most rows / runs a call takes: 16, or kWideBatchMax for lmrs_batch_create_wide's batches
     float* kv = nullptr; size_t slot_floats = 0;        // [n_slots][K cache | V cache], slot_floats floats each: one allocation
     RowTable *tab = nullptr, *h_tab = nullptr;          // the pass's row table and its pinned source
     uint32_t *tokens = nullptr;                         // a prefill's token run (seq_len)
@@ -2034,39 +2040,48 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     delete b;
 }
 
-extern "C" int lmrs_batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out) {
+// lmrs_batch_create / lmrs_batch_create_wide: `name` opens every message, width is the batch's row and slot limit
+static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width) {
     if (!c || !out) return fail("NULL argument");
     *out = nullptr;
-    if (n_slots < 1 || n_slots > (uint32_t)kRowTableMax) return fail("lmrs_batch_create: n_slots = " + std::to_string(n_slots) + " is outside 1 .. " + std::to_string(kRowTableMax));
+    if (n_slots < 1 || n_slots > width) return fail(name + ": n_slots = " + std::to_string(n_slots) + " is outside 1 .. " + std::to_string(width));
     const lmrs_args& a = c->args;
     // the refusals, one message each: there is no token-by-token form of a batch step (the decode graphs' cache pointers are baked at capture)
-    if (c->world > 1 && !c->comm && !c->p2p) return fail("lmrs_batch_create: members of a lock-step shard group (lmrs_group_create) are not supported");
-    if (c->world > 1 || c->comm || c->p2p) return fail("lmrs_batch_create: sharded contexts (lmrs_create_sharded) are not supported");
-    if (c->f32) return fail("lmrs_batch_create: unquantised (f32) files have no batched pass");
-    if (c->sw.no_batched_prefill) return fail("lmrs_batch_create: the batched pass is switched off (LMRS_NO_BATCHED_PREFILL=1)");
-    if (!prefill_batched_ok(c)) return fail("lmrs_batch_create: the batched pass is not built for this model's geometry");
-    if (cls_rows(c) % 16) return fail("lmrs_batch_create: " + std::to_string(cls_rows(c)) + " classifier rows are not a multiple of 16");
-    if (!score_batched_ok(c, 2)) return fail("lmrs_batch_create: this context has no batched pass for short runs");
+    if (c->world > 1 && !c->comm && !c->p2p) return fail(name + ": members of a lock-step shard group (lmrs_group_create) are not supported");
+    if (c->world > 1 || c->comm || c->p2p) return fail(name + ": sharded contexts (lmrs_create_sharded) are not supported");
+    if (c->f32) return fail(name + ": unquantised (f32) files have no batched pass");
+    if (c->sw.no_batched_prefill) return fail(name + ": the batched pass is switched off (LMRS_NO_BATCHED_PREFILL=1)");
+    if (!prefill_batched_ok(c)) return fail(name + ": the batched pass is not built for this model's geometry");
+    if (cls_rows(c) % 16) return fail(name + ": " + std::to_string(cls_rows(c)) + " classifier rows are not a multiple of 16");
+    if (!score_batched_ok(c, 2)) return fail(name + ": this context has no batched pass for short runs");
     HIP_OK(hipSetDevice(c->device));
     if (prefill_alloc(c) || score_alloc(c, true)) return -1;
-    if (c->sc_rows < kRowTableMax) return fail("lmrs_batch_create: the logits block holds fewer than " + std::to_string(kRowTableMax) + " rows of this vocabulary");
+    if (c->sc_rows < kRowTableMax) return fail(name + ": the logits block holds fewer than " + std::to_string(kRowTableMax) + " rows of this vocabulary");
     lmrs_batch* b = new lmrs_batch;
-    b->c = c; b->n_slots = n_slots; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
+    b->c = c; b->n_slots = n_slots; b->width = width; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
     const size_t bytes = (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
     bool ok = hipMalloc(reinterpret_cast<void**>(&b->kv), bytes) == hipSuccess;                         // all or nothing: one allocation
-    if (!ok) { (void)hipGetLastError(); b->kv = nullptr; lmrs_batch_destroy(b); return fail("lmrs_batch_create: " + std::to_string(bytes) + " bytes of K/V caches for " + std::to_string(n_slots) + " slots: out of memory"); }
+    if (!ok) { (void)hipGetLastError(); b->kv = nullptr; lmrs_batch_destroy(b); return fail(name + ": " + std::to_string(bytes) + " bytes of K/V caches for " + std::to_string(n_slots) + " slots: out of memory"); }
     ok = hipMalloc(reinterpret_cast<void**>(&b->tab), sizeof(RowTable)) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->tokens), T * 4) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->out), T * kRowTableMax * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->out), T * width * 4) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_tab), sizeof(RowTable), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_out), T * kRowTableMax * 4, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_out), T * width * 4, hipHostMallocDefault) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs), sizeof(RunTable)) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_runs), sizeof(RunTable), hipHostMallocDefault) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_qkv), (size_t)kRunRowsMax * (c->att_dim + 2 * c->kv_dim) * 4) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_x), (size_t)kRunRowsMax * a.dim * 4) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail("lmrs_batch_create: row table and result buffers: out of memory"); }
-    if (hipMemsetAsync(b->kv, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail("lmrs_batch_create: clearing the caches failed"); }
+    if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": row table and result buffers: out of memory"); }
+    if (hipMemsetAsync(b->kv, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail(name + ": clearing the caches failed"); }
     *out = b;
+    return 0;
+}
+
+extern "C" int lmrs_batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out) { return batch_create(c, n_slots, out, "lmrs_batch_create", kRowTableMax); }
+extern "C" int lmrs_batch_create_wide(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out) { return batch_create(c, n_slots, out, "lmrs_batch_create_wide", kWideBatchMax); }
+extern "C" int lmrs_batch_width(const lmrs_batch* b, uint32_t* width) {
+    if (!b || !width) return fail("NULL argument");
+    *width = b->width;
     return 0;
 }
 
@@ -2119,19 +2134,62 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
     return 0;
 }
 
+// The pinned long table (RunTable) of a pass over n_runs runs, the arguments checked by the caller: caller row j (run order, ascending position) behind table
+// row r, deepest first; sel[o] = the table row of output o.  *rows / *outs: the table's rows and the outputs asked for.
+static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len, const uint32_t* n_out,
+                       const uint32_t* tokens, size_t* rows_out, size_t* outs) {
+    struct Row { uint32_t run, pos; };
+    std::vector<Row> rows;
+    for (uint32_t i = 0; i < n_runs; ++i) for (uint32_t j = 0; j < (run_len ? run_len[i] : 1u); ++j) rows.push_back(Row{i, start_pos[i] + j});
+    const size_t R = rows.size();
+    std::vector<int> order(R), at(R);
+    for (size_t j = 0; j < R; ++j) order[j] = (int)j;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return rows[x].pos > rows[y].pos; });
+    RunTable* h = b->h_runs;
+    for (size_t r = 0; r < R; ++r) {
+        const int j = order[r];
+        h->off[r] = (unsigned long long)slot[rows[j].run] * 2 * b->slot_floats; h->pos[r] = (int)rows[j].pos; h->tok[r] = tokens[j];
+        at[j] = (int)r;
+    }
+    size_t o = 0;
+    for (size_t i = 0, j = 0; i < n_runs; ++i) {
+        const uint32_t len = run_len ? run_len[i] : 1u, no = n_out ? n_out[i] : 1u;
+        for (uint32_t u = len - no; u < len; ++u) h->sel[o++] = (uint32_t)at[j + u];
+        j += len;
+    }
+    *rows_out = R; *outs = o;
+}
+// One pass over the device's long table as it stands: R rows through the layers, then the O rows of sel through the final norm and the classifier to
+// their sink.  step: how far the rows have moved since runs_table (sizes the attention's score vector).  Every GEMM in the weight-streaming forms up to
+// kStreamPassMax rows - the skinny kernel up to 16, the stream kernel above - and launch_gemm_q8's dispatch beyond.
+static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to) {
+    lmrs_ctx* c = b->c;
+    PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
+    form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
+    if (token_rows(c, form.runs.tok, (int)R) || prefill_pass(c, form, (int)R, 0)) return -1;
+    if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
+    HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
+    PassForm cls; cls.skinny = O <= kStreamPassMax;
+    to.targets = false;
+    return classify_rows(c, cls, to, b->runs_x, 0, (int)O);
+}
+
 // The arguments of a step, checked before any device work; then the pinned row table, sorted by descending position (the deepest attention workgroups
 // dispatch first; the order is the same for every pass of a call, all positions moving together): order[r] = the caller's row behind table row r
-static int batch_rows(lmrs_batch* b, const char* what, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, uint32_t span, int* order) {
+// cap: the most rows the call takes (the batch's width; 16 for the sampled step).  Above kRowTableMax rows the pass is the ragged one with runs of one
+// token (runs_table: outputs in the caller's row order, `order` is not written)
+static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, uint32_t span, int* order) {
     const lmrs_ctx* c = b->c;
-    if (n < 1 || n > (uint32_t)kRowTableMax) return fail(std::string(what) + ": n = " + std::to_string(n) + " is outside 1 .. " + std::to_string(kRowTableMax));
-    uint32_t seen = 0;
+    if (n < 1 || n > cap) return fail(std::string(what) + ": n = " + std::to_string(n) + " is outside 1 .. " + std::to_string(cap));
+    uint64_t seen = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (slot[i] >= b->n_slots) return fail(std::string(what) + ": row " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
         if (seen >> slot[i] & 1u) return fail(std::string(what) + ": slot " + std::to_string(slot[i]) + " appears twice");
-        seen |= 1u << slot[i];
+        seen |= uint64_t(1) << slot[i];
         if (tokens[i] >= c->args.vocab_size) return fail(std::string(what) + ": token " + std::to_string(i) + " out of range");
         if ((size_t)pos[i] + span > c->args.seq_len) return fail(std::string(what) + ": row " + std::to_string(i) + ": pos + " + std::to_string(span) + " positions exceeds seq_len");
     }
+    if (n > (uint32_t)kRowTableMax) { size_t R, O; runs_table(b, n, slot, pos, nullptr, nullptr, tokens, &R, &O); return 0; }
     for (uint32_t i = 0; i < n; ++i) order[i] = (int)i;
     std::stable_sort(order, order + n, [&](int x, int y) { return pos[x] > pos[y]; });
     for (uint32_t r = 0; r < n; ++r) {
@@ -2152,9 +2210,24 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
     if (!b || !slot || !tokens || !pos || !argmax) return fail("NULL argument");
     lmrs_ctx* c = b->c;
     int order[kRowTableMax];
-    if (batch_rows(b, "lmrs_batch_forward", n, slot, tokens, pos, 1, order)) return -1;
+    if (batch_rows(b, "lmrs_batch_forward", b->width, n, slot, tokens, pos, 1, order)) return -1;
     HIP_OK(hipSetDevice(c->device));
     const size_t V = c->args.vocab_size;
+    if (n > (uint32_t)kRowTableMax) {                    // a wide step: the long table, outputs in the caller's order straight to their places
+        const HostScores hs = host_scores(c);
+        auto enqueue = [&]() -> int {
+            HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+            if (batch_state(c)) return -1;
+            RowSink to{0, n, logits, 0}; to.reduce_too = true;
+            if (runs_pass(b, n, n, 0, to)) return -1;
+            HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (enqueue()) return batch_failed(c);
+        if (finish_call(c)) return -1;
+        memcpy(argmax, hs.idx, n * 4);
+        return 0;
+    }
     std::vector<float> rows(logits ? n * V : 0);         // the pass's rows in table order
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
@@ -2178,14 +2251,20 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     if (!b || !slot || !tokens || !pos || (!out_tokens && n_new)) return fail("NULL argument");
     lmrs_ctx* c = b->c;
     int order[kRowTableMax];
-    if (batch_rows(b, "lmrs_batch_generate_greedy", n, slot, tokens, pos, n_new ? n_new : 1, order)) return -1;
+    if (batch_rows(b, "lmrs_batch_generate_greedy", b->width, n, slot, tokens, pos, n_new ? n_new : 1, order)) return -1;
     if (!n_new) return 0;
     HIP_OK(hipSetDevice(c->device));
+    const bool wide = n > (uint32_t)kRowTableMax;        // the long table: results in the caller's row order
     auto enqueue = [&]() -> int {
-        HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
+        if (wide) HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+        else HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
         if (batch_state(c)) return -1;
         HIP_OK(hipEventRecord(c->ev0, c->stream));
-        for (uint32_t j = 0; j < n_new; ++j) {
+        for (uint32_t j = 0; j < n_new && wide; ++j) {
+            if (runs_pass(b, n, n, j, RowSink{0, n, nullptr, 0})) return -1;
+            HIP_OK(launch_runs_advance(b->runs->pos, b->runs->tok, b->runs->sel, c->sc_idx, b->out + (size_t)j * n, (int)n, c->stream));
+        }
+        for (uint32_t j = 0; j < n_new && !wide; ++j) {
             // the pass, then its results -> out[j][..], the rows' next tokens, their positions + 1: nothing of a step crosses to the host
             if (batch_pass(b, n, j, nullptr)) return -1;
             HIP_OK(launch_table_advance(b->tab, c->sc_idx, b->out + (size_t)j * n, (int)n, c->stream));
@@ -2196,7 +2275,7 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     };
     if (enqueue()) return batch_failed(c);
     if (finish_call(c)) return -1;
-    for (uint32_t j = 0; j < n_new; ++j) for (uint32_t r = 0; r < n; ++r) out_tokens[(size_t)order[r] * n_new + j] = b->h_out[(size_t)j * n + r];
+    for (uint32_t j = 0; j < n_new; ++j) for (uint32_t r = 0; r < n; ++r) out_tokens[(size_t)(wide ? r : (uint32_t)order[r]) * n_new + j] = b->h_out[(size_t)j * n + r];
     if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
     return 0;
 }
@@ -2239,7 +2318,7 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
     if (!slot || !tokens || !pos || !samplers || !next) return fail(what + "NULL array");
     lmrs_ctx* c = b->c;
     int order[kRowTableMax], at[kRowTableMax];
-    if (batch_rows(b, "lmrs_batch_forward_sample", n, slot, tokens, pos, 1, order)) return -1;
+    if (batch_rows(b, "lmrs_batch_forward_sample", kRowTableMax, n, slot, tokens, pos, 1, order)) return -1;
     const size_t V = c->args.vocab_size;
     SampleRow par[kRowTableMax]; bool topp[kRowTableMax]; bool sampled = false;
     for (uint32_t i = 0; i < n; ++i) {
@@ -2317,18 +2396,18 @@ extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uin
     if (!b || !slot || !start_pos || !run_len || !n_out || !tokens) return fail(what + "NULL argument");
     lmrs_ctx* c = b->c;
     const lmrs_args& a = c->args;
-    if (n_runs < 1 || n_runs > (uint32_t)kRowTableMax) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(kRowTableMax));
+    if (n_runs < 1 || n_runs > b->width) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(b->width));
     size_t R = 0, O = 0;
     for (uint32_t i = 0; i < n_runs; ++i) {
         if (run_len[i] < 1) return fail(what + "run " + std::to_string(i) + ": run_len is 0");
         if ((R += run_len[i]) > (size_t)kRunRowsMax) return fail(what + "the runs hold more than " + std::to_string(kRunRowsMax) + " rows");
     }
-    uint32_t seen = 0;
+    uint64_t seen = 0;
     for (uint32_t i = 0; i < n_runs; ++i) {
         const std::string run = what + "run " + std::to_string(i) + ": ";
         if (slot[i] >= b->n_slots) return fail(run + "slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
         if (seen >> slot[i] & 1u) return fail(what + "slot " + std::to_string(slot[i]) + " appears in more than one run");
-        seen |= 1u << slot[i];
+        seen |= uint64_t(1) << slot[i];
         if (n_out[i] > run_len[i]) return fail(run + "n_out = " + std::to_string(n_out[i]) + " exceeds run_len = " + std::to_string(run_len[i]));
         if ((size_t)start_pos[i] + run_len[i] > a.seq_len) return fail(run + "start_pos + run_len exceeds seq_len");
         O += n_out[i];
@@ -2337,36 +2416,17 @@ extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uin
     if (k && topk_check_k(k, a.vocab_size)) return -1;
     if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
     if (O && !argmax) return fail(what + "argmax is NULL with " + std::to_string(O) + " output rows asked for");
-    // the pinned table: caller row j (run order, ascending position) behind table row r, deepest first; sel[o] = the table row of output o
-    struct Row { uint32_t run, pos; };
-    std::vector<Row> rows; rows.reserve(R);
-    for (uint32_t i = 0; i < n_runs; ++i) for (uint32_t j = 0; j < run_len[i]; ++j) rows.push_back(Row{i, start_pos[i] + j});
-    std::vector<int> order(R), at(R);
-    for (size_t j = 0; j < R; ++j) order[j] = (int)j;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return rows[x].pos > rows[y].pos; });
-    RunTable* h = b->h_runs;
-    for (size_t r = 0; r < R; ++r) {
-        const int j = order[r];
-        h->off[r] = (unsigned long long)slot[rows[j].run] * 2 * b->slot_floats; h->pos[r] = (int)rows[j].pos; h->tok[r] = tokens[j];
-        at[j] = (int)r;
-    }
-    for (size_t i = 0, j = 0, o = 0; i < n_runs; j += run_len[i], ++i)
-        for (uint32_t u = run_len[i] - n_out[i]; u < run_len[i]; ++u) h->sel[o++] = (uint32_t)at[j + u];
+    runs_table(b, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O);
     HIP_OK(hipSetDevice(c->device));
     if (k && O && topk_alloc(c, c->sc_rows, (int)k)) return -1;
     const HostScores hs = host_scores(c);
     const size_t nk = O * k;
     auto enqueue = [&]() -> int {
-        HIP_OK(hipMemcpyAsync(b->runs, h, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
         if (batch_state(c)) return -1;
-        PassForm form; form.skinny = R <= kShortPassMax; form.runs = b->runs_view(); form.max_T = h->pos[0] + 1; form.qkv = b->runs_qkv;
-        form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
-        if (token_rows(c, form.runs.tok, (int)R) || prefill_pass(c, form, (int)R, 0)) return -1;
-        if (!O) return 0;                                // K/V rows only: neither the final norm nor the classifier runs
-        HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)a.dim, (int)O, c->stream));
-        PassForm cls; cls.skinny = O <= kShortPassMax;
-        RowSink to{0, O, logits, k}; to.targets = false; to.reduce_too = true;
-        if (classify_rows(c, cls, to, b->runs_x, 0, (int)O)) return -1;
+        RowSink to{0, O, logits, k}; to.reduce_too = true;
+        if (runs_pass(b, R, O, 0, to)) return -1;
+        if (!O) return 0;
         HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream));
         if (k) {
             HIP_OK(hipMemcpyAsync(c->h_tk, c->tk_idx, nk * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2636,10 +2696,9 @@ extern "C" int lmrs_debug_w13_quant(int device, int8_t* hq, float* hs, const int
     return 0;
 }
 
-extern "C" int lmrs_debug_gemm_skinny(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
-                                      size_t n, size_t o, size_t n_tok, int q4) {
-    if (!out || !xq || !xs || !wq || !ws) return fail("NULL argument");
-    if (n == 0 || n % 256 || o == 0 || o % 16 || n_tok < 1 || n_tok > kShortPassMax) return fail("lmrs_debug_gemm_skinny: n must be a positive multiple of 256, o of 16, n_tok 1 .. 16");
+// lmrs_debug_gemm_skinny / lmrs_debug_gemm_wide behind their checks: the operands to the device, one launch (stream: gemm_stream_kernel at any n_tok it
+// serves; else launch_gemm_q8's skinny dispatch), the rows back
+static int debug_gemm_rows(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws, size_t n, size_t o, size_t n_tok, int q4, bool stream) {
     if (op_begin(device)) return -1;
     Scratch S; const size_t G = n / 128, wb = q4 ? n / 2 : n;
     // Q4_0: the activations arrive as the reference packs them (element 2b in the low nibble of byte b, biased by 8) and go to the device as the int8 (q - 8)
@@ -2662,9 +2721,21 @@ extern "C" int lmrs_debug_gemm_skinny(int device, float* out, const int8_t* xq, 
     HIP_OK(hipMemset(dout, 0, n_tok * o * 4));
     GemmArgs g{}; g.wq = dw; g.ws = static_cast<float*>(dws); g.xq = static_cast<const int8_t*>(dx); g.xs = static_cast<const float*>(dxs);
     g.n = (int)n; g.o = (int)o; g.n_tok = (int)n_tok; g.q4 = q4 ? 1 : 0; g.out = static_cast<float*>(dout); g.skinny = 1;
-    HIP_OK(launch_gemm_q8(g, EPI_STORE, nullptr));
+    HIP_OK(stream ? launch_gemm_stream_store(g, nullptr) : launch_gemm_q8(g, EPI_STORE, nullptr));
     HIP_OK(hipMemcpy(out, dout, n_tok * o * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+extern "C" int lmrs_debug_gemm_skinny(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                                      size_t n, size_t o, size_t n_tok, int q4) {
+    if (!out || !xq || !xs || !wq || !ws) return fail("NULL argument");
+    if (n == 0 || n % 256 || o == 0 || o % 16 || n_tok < 1 || n_tok > kShortPassMax) return fail("lmrs_debug_gemm_skinny: n must be a positive multiple of 256, o of 16, n_tok 1 .. 16");
+    return debug_gemm_rows(device, out, xq, xs, wq, ws, n, o, n_tok, q4, false);
+}
+extern "C" int lmrs_debug_gemm_wide(int device, float* out, const int8_t* xq, const float* xs, const uint8_t* wq, const float* ws,
+                                    size_t n, size_t o, size_t n_tok, int q4) {
+    if (!out || !xq || !xs || !wq || !ws) return fail("lmrs_debug_gemm_wide: NULL argument");
+    if (n == 0 || n % 256 || o == 0 || o % 16 || n_tok < 1 || n_tok > kWideBatchMax) return fail("lmrs_debug_gemm_wide: n must be a positive multiple of 256, o of 16, n_tok 1 .. 64");
+    return debug_gemm_rows(device, out, xq, xs, wq, ws, n, o, n_tok, q4, true);
 }
 
 extern "C" int lmrs_op_matmul_q4(int device, float* xout, const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws,

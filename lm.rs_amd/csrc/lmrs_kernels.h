@@ -202,8 +202,11 @@ struct GemmArgs {
     int8_t* hq; float* hs;                                                       // EPI_SWIGLU_Q / EPI_GELU_Q: quantised h [n_tok][o/2] int8 + scales [n_tok][o/256]
     // 1 and n_tok <= 16: the weight-streaming skinny kernel (gemm_skinny_kernel, lmrs_prefill.inc) - one 16-token tile, every weight byte read once; row-major
     // scales only (ws_ld = xs_ld = 0); EPI_STORE / RESID / QKV / SWIGLU / GELU.  0 (every caller but the short token pass): the dispatch as it always was.
+    // 1 and 17 <= n_tok <= 64 (a batch pass only, which asks for it up to 47 rows): the same stream against 2 .. 4 token tiles (gemm_stream_kernel), same layouts
+    // and epilogues.
     int skinny;
 };
+hipError_t launch_gemm_stream_store(const GemmArgs& a, hipStream_t s);           // gemm_stream_kernel with EPI_STORE at 1 <= n_tok <= 64 (lmrs_debug_gemm_wide)
 bool gemm_q8_hq_fused(int n, int o, int n_tok, bool q4);                         // host only: this w1/w3 launch can take the quantising epilogue
 hipError_t launch_gemm_q8(const GemmArgs& a, int epi, hipStream_t s);
 struct GemmTile { int tm, tn, waves; };                                        // weight rows x tokens of a workgroup's output tile, waves per workgroup
@@ -234,6 +237,9 @@ hipError_t launch_rope_scatter_rows(float* qkv, float* k_cache, float* v_cache, 
 hipError_t launch_attention_table(const AttnArgs& a, const RowTable* rows, int n_rows, int max_T, hipStream_t s);
 // behind a pass's reduction: out[r] = idx[r], the row's next token = idx[r], its position + 1 (lmrs_batch_generate_greedy's device loop)
 hipError_t launch_table_advance(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s);
+// the same step over the long table's columns (a wide batch's device loop above kRowTableMax rows): output o belongs to table row sel[o] - out[o] = idx[o],
+// that row's next token = idx[o], its position + 1
+hipError_t launch_runs_advance(int* pos, uint32_t* tok, const uint32_t* sel, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s);
 // ---- ragged pass (lmrs_batch_forward_runs): up to kRunRowsMax rows, several of them consecutive tokens of ONE slot.  The same three columns as device arrays
 // of their own, handed to the kernels by value; RowTable and its two kernels stay as they are (their size is part of lmrs_batch_forward's pass).
 constexpr int kRunRowsMax = 512;                                                // = the batched pass's kPrefillTokens

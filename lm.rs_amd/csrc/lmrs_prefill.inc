@@ -942,10 +942,179 @@ static hipError_t launch_gemm_skinny_epi(const GemmArgs& a, int epi, hipStream_t
     }
 #undef SK
 }
+// ------------------------------------------------------------------------------------------------
+// Stream GEMM: 17 .. 47 tokens of a batch pass (GemmArgs::skinny with more than one token tile; the kernel itself serves 1 .. 64, the callers' limit is measured).  The skinny kernel's
+// weight stream - every weight byte read from HBM once, wide non-temporal loads, Q4_0 rows packed until the MFMA - against NT = 2 .. 4 token tiles: a weight
+// fragment in registers meets all NT activation tiles before it is dropped.  The skinny kernel parks EVERY group's products in LDS ((G + 1) x MT KiB per
+// token tile: 260 KiB for K = 8192 at four tiles), so here K goes in ROUNDS of NW groups, one per wave: round t's products ((isum as f32) * ws) * xs go to
+// slab t & 1 ([wave][token tile][row tile][lane]); behind the round's barrier the adder waves - one per output tile, tile q on wave q mod NW - add the
+// round's products to an accumulator they keep in registers, in ascending group order, while every wave forms round t + 1's products in the other slab.
+// One barrier per round: slab t & 1 is written again in round t + 2, behind the barrier of round t + 1, which the adds of round t precede.
+// Same operations in the same order per element as gemm_skinny_kernel / gemm_q8_kernel: bit-identical.  Tokens past n_tok duplicate the last token and are
+// never stored; a ragged last row tile re-does the previous one.  Scales: ROW-MAJOR only, staged per wave as the skinny kernel stages them.
+// One group of fragments in flight per wave (LMRS_STREAM_DEPTH): the registers a second one takes cost more resident waves than it hides latency.
+// LDS: 2 NW NT MT KiB of slabs (64 KiB at four token tiles) + the scales (23 KiB for K = 9216).
+// ------------------------------------------------------------------------------------------------
+#ifndef LMRS_STREAM_DEPTH
+#define LMRS_STREAM_DEPTH 1                                      // groups of fragments a wave keeps in flight (measured: 2 is slower at every row count, profiles/ab_stream_tile.txt; A/B builds: make V=.. EXTRA=-DLMRS_STREAM_DEPTH=2)
+#endif
+#ifndef LMRS_STREAM_WIDE_ROWS
+#define LMRS_STREAM_WIDE_ROWS 8192                               // launches of at least this many rows take the 32-row tiles of 4 waves (as LMRS_SKINNY_WIDE_ROWS)
+#endif
+template <int EPI, int NT, int MT, int NW, bool Q4 = false>
+__global__ __launch_bounds__(64 * NW) void gemm_stream_kernel(const GemmArgs a) {
+    constexpr int D = LMRS_STREAM_DEPTH;
+    constexpr int NR = 16 * MT, TK = 16 * NT, NQ = NT * MT, NA = (NQ + NW - 1) / NW;      // NQ output tiles, NA of them per adder wave
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lr = lane & 15, kb = lane >> 4;
+    const int K = a.n, G = K / 128, GW = (G + NW - 1) / NW;      // GW rounds; a wave without a group in the last round re-does group G - 1, nobody adds its products
+    const int WB = Q4 ? K / 2 : K;
+    const int r0 = blockIdx.x * NR;
+    f32x4m* P = reinterpret_cast<f32x4m*>(smem_raw);             // [2][NW][NQ][64 lanes] products
+    float* wsl = reinterpret_cast<float*>(smem_raw + (size_t)2 * NW * NQ * 1024) + (size_t)wave * GW * (NR + TK);     // this wave's groups: [GW][NR]
+    float* xsl = wsl + (size_t)GW * NR;                                                                               //                     [GW][TK]
+    const int8_t* wrow[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        int r = r0 + m * 16; r = r < a.o ? r : a.o - 16;         // a ragged last tile re-does the previous one (o is a multiple of 16)
+        wrow[m] = static_cast<const int8_t*>(a.wq) + (size_t)(r + lr) * WB + kb * (Q4 ? 8 : 16);
+    }
+    const int8_t* xrow[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) { int t = j * 16 + lr; t = t < a.n_tok ? t : a.n_tok - 1; xrow[j] = a.xq + (size_t)t * K + kb * 16; }
+    typedef int i32x2m __attribute__((ext_vector_type(2)));
+    using WFrag = std::conditional_t<Q4, i32x2m, i32x4m>;
+    struct Frag { WFrag w0[MT], w1[MT]; i32x4m x0[NT], x1[NT]; };
+    auto group_of = [&](int i) __attribute__((always_inline)) { const int g = i * NW + wave; return g < G ? g : G - 1; };     // (clamped: always a valid address)
+    auto load = [&](Frag& f, int g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            f.w0[m] = __builtin_nontemporal_load(reinterpret_cast<const WFrag*>(wrow[m] + (size_t)g * (Q4 ? 64 : 128)));
+            f.w1[m] = __builtin_nontemporal_load(reinterpret_cast<const WFrag*>(wrow[m] + (size_t)g * (Q4 ? 64 : 128) + (Q4 ? 32 : 64)));
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            f.x0[j] = *reinterpret_cast<const i32x4m*>(xrow[j] + (size_t)g * 128);
+            f.x1[j] = *reinterpret_cast<const i32x4m*>(xrow[j] + (size_t)g * 128 + 64);
+        }
+    };
+    Frag f[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) load(f[k], group_of(k < GW ? k : GW - 1));      // the weight stream starts before the scales are staged
+    for (int e = lane; e < GW * NR; e += 64) {                  // group scales of this wave's groups (round i -> group_of(i))
+        const int i = e / NR; int r = r0 + (e - i * NR); r = r < a.o ? r : a.o - 1;
+        wsl[e] = a.ws[(size_t)r * G + group_of(i)];
+    }
+    for (int e = lane; e < GW * TK; e += 64) {
+        const int i = e / TK; int t = e - i * TK; t = t < a.n_tok ? t : a.n_tok - 1;
+        xsl[e] = a.xs[(size_t)t * G + group_of(i)];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                             // (each wave reads only the scales it wrote)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    auto use = [&](const Frag& fr, int i) __attribute__((always_inline)) {
+        f32x4m* slab = P + ((size_t)(i & 1) * NW + wave) * NQ * 64;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const f32x4m wsv = *reinterpret_cast<const f32x4m*>(wsl + i * NR + m * 16 + kb * 4);      // the 4 weight rows this lane holds
+            i32x4m w0, w1;
+            if constexpr (Q4) { w0 = q4_fragment(fr.w0[m].x, fr.w0[m].y); w1 = q4_fragment(fr.w1[m].x, fr.w1[m].y); }
+            else { w0 = fr.w0[m]; w1 = fr.w1[m]; }
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {                       // the fragment against every token tile
+                const float xsv = xsl[i * TK + j * 16 + lr];
+                i32x4m c = {0, 0, 0, 0};
+                c = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, fr.x0[j], c, 0, 0, 0);                    // D[row = weight row][col = token]
+                c = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, fr.x1[j], c, 0, 0, 0);
+                f32x4m p;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { float q = (float)c[e] * wsv[e]; p[e] = q * xsv; }         // ((ival as f32) * w.s[..]) * x.s[..]
+                slab[(j * MT + m) * 64 + lane] = p;
+            }
+        }
+    };
+    f32x4m acc[NA];
+#pragma unroll
+    for (int u = 0; u < NA; ++u) acc[u] = f32x4m{0.f, 0.f, 0.f, 0.f};
+    // the ordered sum of round i: its groups i NW .. in ascending order onto the tiles this wave owns
+    auto add = [&](int i) __attribute__((always_inline)) {
+        const int cnt = G - i * NW < NW ? G - i * NW : NW;
+#pragma unroll
+        for (int u = 0; u < NA; ++u) {
+            const int q = wave + u * NW;
+            if (q < NQ) {
+                const f32x4m* src = P + (size_t)(i & 1) * NW * NQ * 64 + q * 64 + lane;
+                for (int w = 0; w < cnt; ++w) {
+                    const f32x4m v = src[(size_t)w * NQ * 64];
+                    acc[u][0] = acc[u][0] + v[0]; acc[u][1] = acc[u][1] + v[1]; acc[u][2] = acc[u][2] + v[2]; acc[u][3] = acc[u][3] + v[3];
+                }
+            }
+        }
+    };
+    for (int i = 0; i < GW; i += D) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            if (i + k < GW) {                                    // (uniform over the workgroup: every wave meets the same barriers)
+                use(f[k], i + k);
+                { const int in = i + k + D; load(f[k], group_of(in < GW ? in : GW - 1)); }
+                if (i + k > 0) add(i + k - 1);                   // round i + k - 1's adds under this round's loads
+                __syncthreads();
+            }
+        }
+    }
+    add(GW - 1);
+#pragma unroll
+    for (int u = 0; u < NA; ++u) {
+        const int q = wave + u * NW, j = q / MT, m = q - j * MT, t = j * 16 + lr;
+        if (q < NQ && r0 + m * 16 < a.o && t < a.n_tok) gemm_epilogue<EPI>(a, r0 + m * 16 + kb * 4, t, acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+    }
+}
+constexpr int kStreamTokens = 64;                                // four token tiles
+static size_t gemm_stream_lds(int n, int nt, int mt, int nw) {
+    const int G = n / 128, GW = (G + nw - 1) / nw;
+    return (size_t)2 * nw * nt * mt * 1024 + (size_t)nw * GW * (16 * mt + 16 * nt) * sizeof(float);
+}
+// The tile by shape, as the skinny kernel's: few rows (wo, w2, qkv) on 16-row tiles of 8 waves, the wide launches (w1/w3, the classifier) on 32-row tiles of
+// 4 waves, whose two row tiles share the activation fragments (half the L2 traffic per weight byte).
+template <int EPI, int NT, bool Q4>
+static hipError_t launch_gemm_stream_nt(const GemmArgs& a, hipStream_t s) {
+    const size_t wide = gemm_stream_lds(a.n, NT, 2, 4), narrow = gemm_stream_lds(a.n, NT, 1, 8);
+    if (wide > 150 * 1024 || narrow > 150 * 1024) return hipErrorInvalidValue;
+    if (a.o >= LMRS_STREAM_WIDE_ROWS) {
+        allow_big_lds(reinterpret_cast<const void*>(gemm_stream_kernel<EPI, NT, 2, 4, Q4>));
+        hipLaunchKernelGGL((gemm_stream_kernel<EPI, NT, 2, 4, Q4>), dim3((a.o + 31) / 32), dim3(256), wide, s, a);
+        return hipGetLastError();
+    }
+    allow_big_lds(reinterpret_cast<const void*>(gemm_stream_kernel<EPI, NT, 1, 8, Q4>));
+    hipLaunchKernelGGL((gemm_stream_kernel<EPI, NT, 1, 8, Q4>), dim3(a.o / 16), dim3(512), narrow, s, a);
+    return hipGetLastError();
+}
+template <int EPI, bool Q4>
+static hipError_t launch_gemm_stream(const GemmArgs& a, hipStream_t s) {
+    if (a.ws_ld || a.xs_ld || a.n_tok > kStreamTokens) return hipErrorInvalidValue;
+    if (a.n_tok <= 32) return launch_gemm_stream_nt<EPI, 2, Q4>(a, s);
+    if (a.n_tok <= 48) return launch_gemm_stream_nt<EPI, 3, Q4>(a, s);
+    return launch_gemm_stream_nt<EPI, 4, Q4>(a, s);
+}
+static hipError_t launch_gemm_stream_epi(const GemmArgs& a, int epi, hipStream_t s) {
+#define ST(E_) case E_: return a.q4 ? launch_gemm_stream<E_, true>(a, s) : launch_gemm_stream<E_, false>(a, s)
+    switch (epi) {
+        ST(EPI_STORE); ST(EPI_RESID); ST(EPI_QKV); ST(EPI_SWIGLU); ST(EPI_GELU);
+        default: return hipErrorInvalidValue;                     // (the text pass's epilogues, as launch_gemm_skinny_epi)
+    }
+#undef ST
+}
+// lmrs_debug_gemm_wide: the stream kernel at any n_tok it serves (the dispatch below sends it 17 .. 64, its callers ask up to 47)
+hipError_t launch_gemm_stream_store(const GemmArgs& a, hipStream_t s) {
+    if (a.n % 256 || a.o % 16 || a.n_tok <= 0) return hipErrorInvalidValue;
+    return launch_gemm_stream_epi(a, EPI_STORE, s);
+}
 
 hipError_t launch_gemm_q8(const GemmArgs& a, int epi, hipStream_t s) {
     if (a.n % 256 || a.o % 16 || a.n_tok <= 0) return hipErrorInvalidValue;
     if (a.skinny && a.n_tok <= 16) return launch_gemm_skinny_epi(a, epi, s);
+    if (a.skinny && a.n_tok <= kStreamTokens) return launch_gemm_stream_epi(a, epi, s);
     switch (epi) {
         case EPI_STORE: return launch_gemm_q8_epi<EPI_STORE>(a, s);
         case EPI_RESID: return launch_gemm_q8_epi<EPI_RESID>(a, s);
@@ -1199,6 +1368,16 @@ __global__ void table_advance_kernel(RowTable* rows, const uint32_t* idx, uint32
 hipError_t launch_table_advance(RowTable* rows, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s) {
     if (n_rows < 1 || n_rows > kRowTableMax) return hipErrorInvalidValue;
     hipLaunchKernelGGL(table_advance_kernel, dim3(1), dim3(64), 0, s, rows, idx, out, n_rows);
+    return hipGetLastError();
+}
+// (the long table: the outputs are in the caller's row order, sel[o] is the table row behind output o - every row once)
+__global__ void runs_advance_kernel(int* pos, uint32_t* tok, const uint32_t* sel, const uint32_t* idx, uint32_t* out, int n_rows) {
+    const int o = threadIdx.x;
+    if (o < n_rows) { const uint32_t t = idx[o], r = sel[o]; out[o] = t; tok[r] = t; pos[r] += 1; }
+}
+hipError_t launch_runs_advance(int* pos, uint32_t* tok, const uint32_t* sel, const uint32_t* idx, uint32_t* out, int n_rows, hipStream_t s) {
+    if (n_rows < 1 || n_rows > 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(runs_advance_kernel, dim3(1), dim3(64), 0, s, pos, tok, sel, idx, out, n_rows);
     return hipGetLastError();
 }
 

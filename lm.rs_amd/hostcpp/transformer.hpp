@@ -20,6 +20,14 @@ inline void check(int rc) { if (rc != 0) throw Panic(lmrs_last_error()); }
 
 using TransformerArgs = lmrs_args;
 
+// Unit-parity aid: the stream GEMM of a batch pass of 17 .. 47 rows on caller-supplied operands, here at any 1 <= n_tok <= 64  (lmrs_debug_gemm_wide)
+inline std::vector<float> debug_gemm_wide(const std::int8_t* xq, const float* xs, const std::uint8_t* wq, const float* ws, std::size_t n, std::size_t o,
+                                          std::size_t n_tok, bool q4, int device = 0) {
+    std::vector<float> out(n_tok * o);
+    check(lmrs_debug_gemm_wide(device, out.data(), xq, xs, wq, ws, n, o, n_tok, q4 ? 1 : 0));
+    return out;
+}
+
 class Batch;
 
 class Transformer {
@@ -138,7 +146,12 @@ private:
 class Batch {
 public:
     static constexpr std::uint32_t CTX = LMRS_BATCH_CTX;           // fork's source: the transformer's own cache
-    Batch(Transformer& t, std::uint32_t n_slots) : vocab_size_(t.args.vocab_size) { check(lmrs_batch_create(t.ctx_, n_slots, &b_)); }
+    // wide: up to 64 slots, and forward / generate_greedy / forward_runs take up to 64 rows or runs a call (lmrs_batch_create_wide)
+    Batch(Transformer& t, std::uint32_t n_slots, bool wide = false) : vocab_size_(t.args.vocab_size) {
+        check(wide ? lmrs_batch_create_wide(t.ctx_, n_slots, &b_) : lmrs_batch_create(t.ctx_, n_slots, &b_));
+    }
+    // the most rows (forward, generate_greedy) and runs (forward_runs) a call takes: 16, or 64 for a wide batch  (lmrs_batch_width)
+    std::uint32_t width() const { std::uint32_t w = 0; check(lmrs_batch_width(b_, &w)); return w; }
     Batch(const Batch&) = delete;
     Batch& operator=(const Batch&) = delete;
     ~Batch() { if (b_) lmrs_batch_destroy(b_); }

@@ -1,4 +1,4 @@
-//! `Batch`: up to 16 sequences a step over the weights of one `Transformer` (extension, no reference counterpart; include/lmrs_hip.h,
+//! `Batch`: up to 16 sequences a step (64 with `Batch::new_wide`) over the weights of one `Transformer` (extension, no reference counterpart; include/lmrs_hip.h,
 //! `lmrs_batch_*`).  Each slot is a K/V cache of its own; every result is bit for bit what `Transformer::forward` gives on a context that holds
 //! only that sequence.  The borrow keeps the transformer alive and un-aliased while the batch exists.
 use std::os::raw::c_int;
@@ -13,6 +13,9 @@ use crate::transformer::Transformer;
 extern "C" {
     pub fn lmrs_batch_forward_sample(b: *mut LmrsBatch, n: u32, slot: *const u32, tokens: *const u32, pos: *const u32,
                                      samplers: *const *mut LmrsSampler, next: *mut u32) -> c_int;
+    // the wide batch (lmrs_batch_create_wide): declared here for the same reason (tests/test_batch_wide_host.py compares them with the header)
+    pub fn lmrs_batch_create_wide(ctx: *mut ffi::LmrsCtx, n_slots: u32, out: *mut *mut LmrsBatch) -> c_int;
+    pub fn lmrs_batch_width(b: *const LmrsBatch, width: *mut u32) -> c_int;
 }
 
 /// `fork`'s source: the transformer's own cache.
@@ -30,6 +33,21 @@ impl<'t, 'a> Batch<'t, 'a> {
         check(unsafe { ffi::lmrs_batch_create(t.ctx(), n_slots, &mut b) });
         let vocab_size = t.args.vocab_size as usize;
         Batch { b, vocab_size, _t: t }
+    }
+
+    /// Up to 64 slots, and up to 64 rows a call of `forward` / `generate_greedy` (`forward_sample` keeps 16).
+    pub fn new_wide(t: &'t mut Transformer<'a>, n_slots: u32) -> Batch<'t, 'a> {
+        let mut b: *mut LmrsBatch = ptr::null_mut();
+        check(unsafe { lmrs_batch_create_wide(t.ctx(), n_slots, &mut b) });
+        let vocab_size = t.args.vocab_size as usize;
+        Batch { b, vocab_size, _t: t }
+    }
+
+    /// The most rows a call takes: 16, or 64 for a wide batch.
+    pub fn width(&self) -> u32 {
+        let mut w = 0u32;
+        check(unsafe { lmrs_batch_width(self.b, &mut w) });
+        w
     }
 
     /// `Transformer::prefill_tokens` into `slot`'s cache.

@@ -54,6 +54,8 @@ extern "C" {
                                      ngram_max: u32, out_tokens: *mut u32, stats4: *mut u32, seconds: *mut f64) -> c_int;
     pub fn lmrs_debug_gemm_skinny(device: c_int, out: *mut f32, xq: *const i8, xs: *const f32, wq: *const u8, ws: *const f32,
                                   n: usize, o: usize, n_tok: usize, q4: c_int) -> c_int;
+    pub fn lmrs_debug_gemm_wide(device: c_int, out: *mut f32, xq: *const i8, xs: *const f32, wq: *const u8, ws: *const f32,
+                                n: usize, o: usize, n_tok: usize, q4: c_int) -> c_int;
     pub fn lmrs_last_error() -> *const c_char;
 
     pub fn lmrs_vision_create(section: *const u8, len: usize, device: c_int, out: *mut *mut LmrsVision, bytes_consumed: *mut usize) -> c_int;

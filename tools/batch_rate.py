@@ -4,7 +4,12 @@ over 64 steps at n = 1, 2, 4, 8, 16 rows standing at about 100 positions, agains
 time (HIP events around their steps): median of 5 after 2 warm-ups, with the minimum and the maximum.  Every row's token ids are compared with the
 single-sequence run of the same prompt in the same process.  Last, one lmrs_batch_fork of 1030 positions at full size, timed and checked.
 usage: python tools/batch_rate.py [model] [q8_0|q4_0]
-       (writes profiles/batch_decode_llama1b.txt for llama-3.2-1b q8_0, profiles/batch_decode_gemma2b_q4.txt for gemma-2-2b q4_0)"""
+       (writes profiles/batch_decode_llama1b.txt for llama-3.2-1b q8_0, profiles/batch_decode_gemma2b_q4.txt for gemma-2-2b q4_0)
+       python tools/batch_rate.py --wide [model] [q8_0|q4_0]
+--wide: the same protocol on a WIDE batch (lmrs_batch_create_wide) - n = 16, 17, 24, 32, 47, 48, 64 rows at about 100 positions and n = 64 at about 1030 -
+and, before it, the time of ONE ragged pass (lmrs_batch_forward_runs, 16 runs on 16 slots at 100 positions, every row's output asked for) of 16 .. 64 rows:
+host time of 64 synchronous calls / 64, median of 5 after 2 warm-ups.  That call exists without the wide batch too, so on a build that lacks
+lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: the two trees of an A/B run by turns.  BATCH_RATE_OUT names the file written."""
 import os
 import statistics
 import sys
@@ -30,7 +35,70 @@ def timed(fn, reps=5, warm=2):
     return runs[-1][0], statistics.median(us), min(us), max(us)
 
 
+WIDE_ROWS = (16, 17, 24, 32, 47, 48, 64)
+
+
+def wide_main(argv):
+    model = argv[0] if argv else "llama-3.2-1b"
+    qname = argv[1] if len(argv) > 1 else "q8_0"
+    qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True); lines.append(s)
+
+    has_wide = hasattr(lmrs_amd.lib(), "lmrs_batch_create_wide")
+    rows_max = 64 if has_wide else ROWS
+    img = S.build_image(model, qt, 1234)
+    m = lmrs_amd.Transformer(img)
+    b = lmrs_amd.Batch(m, 64, wide=True) if has_wide else lmrs_amd.Batch(m, ROWS)
+    say(f"python tools/batch_rate.py --wide {model} {qname}" + ("" if has_wide else "   (a build without lmrs_batch_create_wide: the shared lines only)"))
+    say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}; LMRS_LIB={os.path.basename(os.environ.get('LMRS_LIB', ''))}")
+    for depth in (100, 1030):
+        prompts = [S.prompt_tokens(model, depth + 8, 100 + i) for i in range(rows_max)]    # row i: depth tokens in its cache, the next ones fed first
+        for i, p in enumerate(prompts):
+            b.prefill(i, p[:depth], 0)
+        if depth == 100:
+            say(f"one ragged pass (lmrs_batch_forward_runs): R rows as 16 runs on 16 slots at {depth} positions, every row's output asked for; host time of {STEPS} "
+                f"synchronous calls / {STEPS}, median of 5 after 2 warm-ups (min .. max)")
+            for R in WIDE_ROWS:
+                lens = [R // 16 + (1 if i < R % 16 else 0) for i in range(16)]
+                runs = [(i, depth, [int(t) for t in prompts[i][depth:depth + n]], n) for i, n in enumerate(lens)]
+
+                def calls():
+                    t0 = time.perf_counter()
+                    for _ in range(STEPS):
+                        am = b.forward_runs(runs)
+                    return am, time.perf_counter() - t0
+                am, us, lo, hi = timed(calls)
+                say(f"  R={R:2d}   {us / STEPS:8.1f} us per pass ({lo / STEPS:.1f} .. {hi / STEPS:.1f})   argmax checksum {int(am.astype(np.uint64).sum())}")
+        singles = []
+        for p in prompts:                                    # the single-sequence ids of every row's prompt, and the baseline's time from row 0's
+            m.prefill_tokens(p[:depth], 0)
+            singles.append(m.generate_greedy(p[depth:depth + 1], STEPS, depth))
+        m.prefill_tokens(prompts[0][:depth], 0)
+        _, base, lo, hi = timed(lambda: m.generate_greedy(prompts[0][depth:depth + 1], STEPS, depth, timing=True))
+        base_rate = STEPS / base * 1e6
+        say(f"rows at {depth} positions: {STEPS} greedy steps per call, device time of the steps (HIP events inside the call); median of 5 after 2 warm-ups (min .. max)")
+        say(f"  lmrs_generate_greedy (one sequence)   {base / STEPS:8.1f} us per step ({lo / STEPS:.1f} .. {hi / STEPS:.1f})   {base_rate:9.1f} tok/s")
+        for n in (WIDE_ROWS if depth == 100 else (64,)):
+            if n > rows_max:
+                continue
+            slots = list(range(n))
+            ids, us, lo, hi = timed(lambda: b.generate_greedy(slots, [int(p[depth]) for p in prompts[:n]], [depth] * n, STEPS, timing=True))
+            same = all(ids[i].tolist() == singles[i].tolist() for i in range(n))
+            rate = n * STEPS / us * 1e6
+            say(f"  lmrs_batch_generate_greedy n={n:2d}       {us / STEPS:8.1f} us per pass ({lo / STEPS:.1f} .. {hi / STEPS:.1f})   {rate:9.1f} tok/s aggregate"
+                f"   {rate / base_rate:5.2f}x the baseline   same tokens as the single-sequence runs: {same}")
+    path = os.environ.get("BATCH_RATE_OUT")
+    if path:
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--wide":
+        return wide_main(sys.argv[2:])
     model = sys.argv[1] if len(sys.argv) > 1 else "llama-3.2-1b"
     qname = sys.argv[2] if len(sys.argv) > 2 else "q8_0"
     qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
