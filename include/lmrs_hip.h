@@ -522,6 +522,35 @@ int lmrs_forward_sample(lmrs_ctx* ctx, uint32_t token, uint32_t pos, lmrs_sample
  * The candidate buffers (16 * (vocab_size + 1) * 8 bytes on the device) are allocated at the first call with a sampled row, all or nothing. */
 int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
                               lmrs_sampler* const* samplers, uint32_t* next);
+/* lmrs_batch_forward_runs with a sampler per run (extension): ONE weight pass over n_runs runs - the same runs, the same limits (1 .. lmrs_batch_width
+ * runs, at most 512 rows, a slot in at most one run) - and the LAST row of every run whose samplers[i] is not NULL goes through Sampler::sample
+ * (sampler.rs:109-129) with that sampler.  A NULL entry leaves the run's K/V rows only (a prompt chunk that is not the last) and next[i] = 0; when
+ * every entry is NULL neither the final norm nor the classifier runs.  next[i] is, bit for bit, what lmrs_forward_sample returns for that sampler
+ * after the run's tokens on a context that holds only that sequence; the K/V rows are as lmrs_batch_forward_runs leaves them; runs may mix argmax,
+ * sample_mult and top-p samplers.  With runs of one token on a wide batch this is the sampled decode step of up to 64 sequences; with a prompt beside
+ * the decode rows the prompt's first token is sampled in the pass that admits it.
+ * The sampled rows go through lmrs_batch_forward_sample's six launches, up to the batch's width of them, and ONE transfer brings back every row's
+ * token or candidate count and the first 4096 (LMRS_TOPP_DEVICE_SORT_MIN) candidates.  Top-p rows finish on the host in run order: a peaked row
+ * through lmrs_sampler_topp_pairs; the rows with 4096 candidates or more (flat distributions) are first sorted on the device ALL TOGETHER - keys
+ * straight from the candidates the filter left, one bitonic network with the row in the grid's second dimension, the rows padded to the power of two
+ * that holds the longest - behind ONE second synchronise however many they are, and finish through lmrs_sampler_topp_sorted_pairs.  The host
+ * finishes do not overlap the copies.  There is no device-resident loop, for the reason given above.
+ * Errors, each with a message of its own that opens with this call's name, before any device work, batch, context and samplers left usable:
+ * everything lmrs_batch_forward_runs checks for these arguments; a NULL array; a sampler made for another vocabulary size (the run is named); a
+ * top-p sampler in two runs of one call; a sampled (temperature != 0) output on a vocabulary whose last vocab_size % 4 logits the classifier leaves
+ * unwritten; a logits block that holds fewer rows than the outputs asked for.  A top-p row without a candidate fails the call with sample_topp's
+ * message and the run's number.
+ * Buffers of this call's own, allocated at the first sampled call, all or nothing, the message gives the bytes: rows * (vocab_size + 1) * 8 bytes
+ * of result blocks on the device for the sampled rows of the call in whole sixteens (made anew when a later call samples more rows), and from the
+ * first call with a flat row F * N * 8 bytes of keys on the device and as many pinned (F flat rows, N the power of two >= their longest candidate
+ * list, >= 8192; made anew when a call needs more: 64 MiB for 64 rows of a 128 k vocabulary).  lmrs_batch_forward_sample's buffers are not touched. */
+int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                   const uint32_t* tokens, lmrs_sampler* const* samplers, uint32_t* next);
+/* The sort of lmrs_batch_forward_runs_sample's flat rows on caller-supplied candidates, ONE call of its launcher: pairs = n_rows (1 .. 64) rows of ld
+ * (1 .. 2^24) entries {f32 prob >= 0, u32 index}, the first n0[r] (<= ld) of row r in ascending index order.  sorted (n_rows x ld): row r's first
+ * n0[r] entries by descending prob, ties by ascending index - what the stable sort of sampler.rs:81 makes of them; the rest of the row, and a row
+ * with n0 = 0, is not written.  Everything else is refused before the device is touched. */
+int lmrs_op_sort_candidates(int device, const void* pairs, size_t n_rows, size_t ld, const uint32_t* n0, void* sorted);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@ EXPORTS = [
     "lmrs_verify_tokens", "lmrs_draft_lookup", "lmrs_generate_speculative", "lmrs_debug_gemm_skinny",
     "lmrs_batch_create", "lmrs_batch_destroy", "lmrs_batch_prefill", "lmrs_batch_fork", "lmrs_batch_forward", "lmrs_batch_generate_greedy",
     "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
+    "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -115,6 +116,8 @@ def lib():
         L.lmrs_batch_debug_kv.argtypes = [vp, u32, C.c_int, u32, u32, vp]
         L.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
         L.lmrs_batch_forward_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.lmrs_batch_forward_runs_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        L.lmrs_op_sort_candidates.argtypes = [C.c_int, vp, sz, sz, vp, vp]
         L.lmrs_op_sample_rows.argtypes = [C.c_int, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.lmrs_sampler_topp_sorted_pairs.argtypes = [vp, vp, sz, C.POINTER(u32)]
         L.lmrs_bench_sample_rows.argtypes = [C.c_int, sz, sz, C.c_int, vp, C.POINTER(C.c_double)]
@@ -383,8 +386,8 @@ class Batch:
     """n_slots (1 .. 16) more K/V caches beside a Transformer's own, stepped together: one pass over the weights serves one token of up to 16
     DIFFERENT sequences, each at its own position (lmrs_batch_*).  Every result is bit for bit what forward / forward_argmax give on a model that
     holds only that sequence.  The model's own cache is untouched by every call here; close the batch before the model.
-    wide=True: up to 64 slots, and forward / generate_greedy / forward_runs take up to 64 rows or runs a call (lmrs_batch_create_wide; forward_sample
-    keeps 16 rows)."""
+    wide=True: up to 64 slots, and forward / generate_greedy / forward_runs / forward_runs_sample take up to 64 rows or runs a call
+    (lmrs_batch_create_wide; forward_sample keeps 16 rows)."""
 
     def __init__(self, model: Transformer, n_slots: int, wide: bool = False):
         h = C.c_void_p()
@@ -461,6 +464,21 @@ class Batch:
                                            k, _p(ti) if k else None, _p(tl) if k else None))
         out = (am,) + ((lg,) if logits else ()) + ((ti, tl) if k else ())
         return out if len(out) > 1 else am
+
+    def forward_runs_sample(self, runs):
+        """forward_runs' pass over runs = [(slot, start_pos, tokens, sampler_or_None), ...] with the LAST row of every run that has a Sampler sampled
+        ON THE DEVICE with it; None: the run leaves its K/V rows only (a prompt chunk that is not the last).  Up to `width` runs, 512 tokens in all; runs
+        may mix argmax, sample_mult and top-p samplers, a top-p sampler in at most one run -> next uint32 [n_runs] (0 for a None entry), bit for bit
+        Transformer.forward_sample's token for that sampler after the run's tokens on a model that holds only that sequence
+        (lmrs_batch_forward_runs_sample)"""
+        toks = [np.ascontiguousarray(r[2], np.uint32).reshape(-1) for r in runs]
+        s, p = (np.array([r[i] for r in runs], np.uint32) for i in (0, 1))
+        n = np.array([t.size for t in toks], np.uint32)
+        t = np.concatenate(toks) if toks else np.empty(0, np.uint32)
+        hs = (C.c_void_p * max(len(runs), 1))(*[None if r[3] is None else r[3]._h for r in runs])
+        nxt = np.zeros(len(runs), np.uint32)
+        _chk(lib().lmrs_batch_forward_runs_sample(self._h, len(runs), _p(s), _p(p), _p(n), _p(t), C.cast(hs, C.c_void_p), _p(nxt)))
+        return nxt
 
     def generate_greedy(self, slots, tokens, pos, n_new: int, timing: bool = False):
         """n_new greedy steps of every row on the device -> uint32 [n, n_new]: row i = Transformer.generate_greedy([tokens[i]], n_new, pos[i]) on its
@@ -619,6 +637,24 @@ def op_sample_rows(rows, temperature, top_p, rnd, pairs: bool = True, device=0):
     if not pairs:
         return x, tok, n0
     return x, tok, n0, [(pr[i, : n0[i]]["prob"].copy(), pr[i, : n0[i]]["index"].copy()) for i in range(x.shape[0])]
+
+
+PAIR = np.dtype([("prob", np.float32), ("index", np.uint32)])
+
+
+def op_sort_candidates(pairs, n0, device=0):
+    """The device sort of forward_runs_sample's flat top-p rows on caller-supplied candidates, all rows in one call of its launcher: pairs [n_rows, ld]
+    of PAIR (prob >= 0), the first n0[r] of row r in ascending index order -> a copy whose row r has its first n0[r] entries by descending prob, ties by
+    ascending index; everything else as it was (lmrs_op_sort_candidates)"""
+    x = np.ascontiguousarray(pairs, PAIR)
+    if x.ndim != 2:
+        raise LmrsError("op_sort_candidates: pairs must be [n_rows, ld]")
+    n = np.ascontiguousarray(n0, np.uint32).reshape(-1)
+    if n.size != x.shape[0]:
+        raise LmrsError("op_sort_candidates: one n0 per row")
+    out = x.copy()
+    _chk(lib().lmrs_op_sort_candidates(device, _p(x), x.shape[0], x.shape[1], _p(n), _p(out)))
+    return out
 
 
 def bench_sample_rows(n_rows: int, n: int, iters: int = 5, device=0):

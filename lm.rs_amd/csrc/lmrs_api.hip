@@ -2022,6 +2022,10 @@ struct lmrs_batch {
     // scratch, the result blocks ([kRowTableMax][vocab + 1] words: {token, n0}, then the candidates) and the pinned copy of their heads (head_words each)
     SampleRow *samp_tab = nullptr, *h_samp_tab = nullptr; float* samp_scratch = nullptr;
     unsigned long long *samp_out = nullptr, *h_samp_heads = nullptr; size_t head_words = 0;
+    // forward_runs_sample's own set of the same (rs_rows rows, grown on demand), and the flat rows' keys / sorted pairs with their pinned copy (cs_words words)
+    SampleRow *rs_tab = nullptr, *h_rs_tab = nullptr; float* rs_scratch = nullptr;
+    unsigned long long *rs_out = nullptr, *h_rs_heads = nullptr; size_t rs_rows = 0, rs_head_words = 0;
+    unsigned long long *cs_keys = nullptr, *h_cs_pairs = nullptr; size_t cs_words = 0;
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
     float* k_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->k_cache : kv + (size_t)slot * 2 * slot_floats; }
     float* v_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->v_cache : kv + (size_t)slot * 2 * slot_floats + slot_floats; }
@@ -2032,6 +2036,8 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     (void)hipSetDevice(b->c->device);
     (void)hipStreamSynchronize(b->c->stream);
     for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x, (void*)b->samp_tab, (void*)b->samp_scratch, (void*)b->samp_out}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)b->rs_tab, (void*)b->rs_scratch, (void*)b->rs_out, (void*)b->cs_keys}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)b->h_rs_tab, (void*)b->h_rs_heads, (void*)b->h_cs_pairs}) if (p) (void)hipHostFree(p);
     if (b->h_samp_tab) (void)hipHostFree(b->h_samp_tab);
     if (b->h_samp_heads) (void)hipHostFree(b->h_samp_heads);
     if (b->h_tab) (void)hipHostFree(b->h_tab);
@@ -2389,13 +2395,10 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
 // long table: rows sorted by descending position, the GEMMs skinny up to 16 rows and launch_gemm_q8's dispatch above, the qkv block in a buffer of the
 // batch's own; behind the layers the rows whose outputs were asked for are made consecutive and only they go through the final norm and the classifier.
 static_assert(kRunRowsMax == kPrefillTokens, "a ragged pass is one chunk of the batched pass");
-extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
-                                       const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
-                                       uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
-    const std::string what = "lmrs_batch_forward_runs: ";
-    if (!b || !slot || !start_pos || !run_len || !n_out || !tokens) return fail(what + "NULL argument");
-    lmrs_ctx* c = b->c;
-    const lmrs_args& a = c->args;
+// The runs of a ragged pass, checked before any device work (`what` opens every message): *rows / *outs = the rows they hold and the outputs asked for
+static int runs_check(const lmrs_batch* b, const std::string& what, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                      const uint32_t* n_out, const uint32_t* tokens, size_t* rows, size_t* outs) {
+    const lmrs_args& a = b->c->args;
     if (n_runs < 1 || n_runs > b->width) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(b->width));
     size_t R = 0, O = 0;
     for (uint32_t i = 0; i < n_runs; ++i) {
@@ -2413,6 +2416,18 @@ extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uin
         O += n_out[i];
     }
     for (size_t j = 0; j < R; ++j) if (tokens[j] >= a.vocab_size) return fail(what + "token " + std::to_string(j) + " out of range");
+    *rows = R; *outs = O;
+    return 0;
+}
+extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                       const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
+                                       uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
+    const std::string what = "lmrs_batch_forward_runs: ";
+    if (!b || !slot || !start_pos || !run_len || !n_out || !tokens) return fail(what + "NULL argument");
+    lmrs_ctx* c = b->c;
+    const lmrs_args& a = c->args;
+    size_t R = 0, O = 0;
+    if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O)) return -1;
     if (k && topk_check_k(k, a.vocab_size)) return -1;
     if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
     if (O && !argmax) return fail(what + "argmax is NULL with " + std::to_string(O) + " output rows asked for");
@@ -2438,6 +2453,143 @@ extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uin
     if (finish_call(c)) return -1;
     if (O) memcpy(argmax, hs.idx, O * 4);
     if (O && k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
+    return 0;
+}
+
+// ------------------------------------------------------------------ the sampled ragged pass: lmrs_batch_forward_runs' pass, then Sampler::sample on the last row of every run
+// (per run Transformer::forward over its tokens + Sampler::sample, sampler.rs:109-129, with the run's own sampler: bit for bit lmrs_forward_sample after the
+// run's tokens on a context that holds only that sequence).  The O sampled rows stand in the logits block in run order (runs_table's sel), so
+// launch_sample_rows takes them as lmrs_batch_forward_sample's rows, up to the batch's width of them; the flat top-p rows of the call - n0 known after the
+// first synchronise - are sorted together (launch_cand_sort) behind ONE second synchronise.  The buffers are this call's own: lmrs_batch_forward_sample's
+// stay as that call documents them.
+static void runs_sample_free(lmrs_batch* b) {
+    for (void** p : {(void**)&b->rs_tab, (void**)&b->rs_scratch, (void**)&b->rs_out}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (void** p : {(void**)&b->h_rs_tab, (void**)&b->h_rs_heads}) if (*p) { (void)hipHostFree(*p); *p = nullptr; }
+    b->rs_rows = 0;
+}
+static void cand_sort_free(lmrs_batch* b) {
+    if (b->cs_keys) { (void)hipFree(b->cs_keys); b->cs_keys = nullptr; }
+    if (b->h_cs_pairs) { (void)hipHostFree(b->h_cs_pairs); b->h_cs_pairs = nullptr; }
+    b->cs_words = 0;
+}
+// room for `rows` sampled rows (whole sixteens, the batch's width at the most): all or nothing, made anew when a call needs more rows than they hold
+static int runs_sample_alloc(lmrs_batch* b, size_t rows) {
+    if (b->rs_rows >= rows) return 0;
+    runs_sample_free(b);
+    const lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, R = std::min<size_t>(b->width, (rows + 15) / 16 * 16), head = 1 + std::min<size_t>(V, c->sw.topp_sort_min);
+    bool ok = hipMalloc(reinterpret_cast<void**>(&b->rs_tab), R * sizeof(SampleRow)) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_rs_tab), R * sizeof(SampleRow), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->rs_scratch), sample_scratch_floats(R) * 4) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_rs_heads), R * head * 8, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->rs_out), R * (V + 1) * 8) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        runs_sample_free(b);
+        return fail("lmrs_batch_forward_runs_sample: " + std::to_string(R * (V + 1) * 8) + " bytes of candidate buffers for " + std::to_string(R) + " rows: out of memory");
+    }
+    b->rs_rows = R; b->rs_head_words = head;
+    return 0;
+}
+// F rows of N keys on the device and their pinned copy: all or nothing, made anew when a call sorts more
+static int cand_sort_alloc(lmrs_batch* b, size_t F, size_t N) {
+    if (b->cs_words >= F * N) return 0;
+    cand_sort_free(b);
+    bool ok = hipMalloc(reinterpret_cast<void**>(&b->cs_keys), F * N * 8) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_cs_pairs), F * N * 8, hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        cand_sort_free(b);
+        return fail("lmrs_batch_forward_runs_sample: " + std::to_string(F * N * 8) + " bytes of sort buffers for " + std::to_string(F) + " flat top-p rows: out of memory");
+    }
+    b->cs_words = F * N;
+    return 0;
+}
+
+extern "C" int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                              const uint32_t* tokens, lmrs_sampler* const* samplers, uint32_t* next) {
+    const std::string what = "lmrs_batch_forward_runs_sample: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (!slot || !start_pos || !run_len || !tokens || !samplers || !next) return fail(what + "NULL array");
+    lmrs_ctx* c = b->c;
+    if (n_runs < 1 || n_runs > b->width) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(b->width));
+    uint32_t n_out[kWideBatchMax]; int out_of[kWideBatchMax];                    // out_of[i]: run i's row among the outputs (-1: none)
+    size_t R = 0, O = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) { n_out[i] = samplers[i] ? 1u : 0u; out_of[i] = samplers[i] ? (int)O++ : -1; }
+    if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O)) return -1;
+    const size_t V = c->args.vocab_size;
+    SampleRow par[kWideBatchMax]; bool topp[kWideBatchMax]; bool sampled = false;
+    for (uint32_t i = 0; i < n_runs; ++i) {
+        topp[i] = false;
+        if (!samplers[i]) continue;
+        const std::string run = what + "run " + std::to_string(i) + ": ";
+        uint32_t vs = 0;
+        if (lmrs_sampler_info(samplers[i], &vs, &par[i].temperature, &par[i].top_p, &par[i].rnd)) return -1;
+        if (vs != V) return fail(run + "the sampler was made for another vocabulary size (" + std::to_string(vs) + ", the model has " + std::to_string(V) + ")");
+        topp[i] = par[i].temperature != 0.0f && !(par[i].top_p <= 0.0f || par[i].top_p >= 1.0f);         // sampler.rs:117-126
+        sampled = sampled || par[i].temperature != 0.0f;
+        // (a top-p sampler carries its candidate vector from call to call: two runs of one call cannot both be "the next call")
+        for (uint32_t j = 0; j < i && topp[i]; ++j)
+            if (samplers[j] == samplers[i]) return fail(run + "the top-p sampler of run " + std::to_string(j) + " appears twice (it carries state from call to call)");
+    }
+    if (sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
+    if (O > (size_t)c->sc_rows) return fail(what + "the logits block holds " + std::to_string(c->sc_rows) + " rows of this vocabulary, " + std::to_string(O) + " outputs were asked for");
+    runs_table(b, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O);
+    HIP_OK(hipSetDevice(c->device));
+    if (sampled && runs_sample_alloc(b, O)) return -1;
+    for (uint32_t i = 0; i < n_runs; ++i) { next[i] = 0; if (sampled && out_of[i] >= 0) b->h_rs_tab[out_of[i]] = par[i]; }
+    const size_t head = b->rs_head_words;
+    const HostScores hs = host_scores(c);
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+        if (batch_state(c)) return -1;
+        if (runs_pass(b, R, O, 0, RowSink{0, O, nullptr, 0})) return -1;          // the reduction: sample_argmax of every output row -> sc_idx; the rows stay in sc_logits
+        if (!O) return 0;
+        if (!sampled) { HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
+        HIP_OK(hipMemcpyAsync(b->rs_tab, b->h_rs_tab, O * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(launch_sample_rows(sample_rows_args(c->sc_logits, (int)O, (int)V, (int)V, b->rs_tab, c->sc_idx, b->rs_scratch, b->rs_out), c->stream, (int)b->width));
+        // THE transfer: every row's {token, n0} and the first head - 1 of its candidates
+        HIP_OK(hipMemcpy2DAsync(b->h_rs_heads, head * 8, b->rs_out, (V + 1) * 8, head * 8, O, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    if (enqueue()) return batch_failed(c);
+    if (finish_call(c)) return -1;
+    if (!O) return 0;
+    if (!sampled) { for (uint32_t i = 0; i < n_runs; ++i) if (out_of[i] >= 0) next[i] = hs.idx[out_of[i]]; return 0; }
+    // the flat rows of the call (a top-p row with LMRS_TOPP_DEVICE_SORT_MIN candidates or more): one table, one sequence of launches, one synchronise
+    CandSortArgs cs{}; int flat_of[kWideBatchMax]; size_t n0_max = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) {
+        flat_of[i] = -1;
+        if (!topp[i]) continue;
+        const uint32_t n0 = (uint32_t)(b->h_rs_heads[(size_t)out_of[i] * head] >> 32);
+        if (n0 > V) return fail(what + "run " + std::to_string(i) + ": the device reported " + std::to_string(n0) + " candidates");
+        if (n0 < c->sw.topp_sort_min || n0 == 0) continue;
+        flat_of[i] = cs.n_rows; cs.t.row[cs.n_rows] = (unsigned)out_of[i]; cs.t.n0[cs.n_rows] = n0; ++cs.n_rows;
+        n0_max = std::max<size_t>(n0_max, n0);
+    }
+    if (cs.n_rows) {
+        cs.N = sample_sort_min_n();
+        while ((size_t)cs.N < n0_max) cs.N <<= 1;
+        if (cand_sort_alloc(b, (size_t)cs.n_rows, (size_t)cs.N)) return -1;
+        cs.src = b->rs_out + 1; cs.ld = V + 1; cs.keys = b->cs_keys;
+        auto sort = [&]() -> int {
+            HIP_OK(launch_cand_sort(cs, c->stream));
+            for (int f = 0; f < cs.n_rows; ++f)
+                HIP_OK(hipMemcpyAsync(b->h_cs_pairs + (size_t)f * cs.N, b->cs_keys + (size_t)f * cs.N, (size_t)cs.t.n0[f] * 8, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (sort()) return batch_failed(c);
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    for (uint32_t i = 0; i < n_runs; ++i) {              // in run order: the host samplers move as n_runs calls of lmrs_forward_sample would move them
+        if (out_of[i] < 0) continue;
+        const unsigned long long* blk = b->h_rs_heads + (size_t)out_of[i] * head;
+        const uint32_t tok = (uint32_t)blk[0], n0 = (uint32_t)(blk[0] >> 32);
+        if (!topp[i]) { next[i] = tok; continue; }
+        const int rc = flat_of[i] < 0 ? lmrs_sampler_topp_pairs(samplers[i], blk + 1, n0, &next[i])
+                                      : lmrs_sampler_topp_sorted_pairs(samplers[i], b->h_cs_pairs + (size_t)flat_of[i] * cs.N, n0, &next[i]);
+        if (rc) return fail(what + "run " + std::to_string(i) + ": " + g_err);
+    }
     return 0;
 }
 
@@ -2880,6 +3032,37 @@ extern "C" int lmrs_op_sample_rows(int device, float* rows, size_t n_rows, size_
         if (n0[r] > n) return fail("lmrs_op_sample_rows: row " + std::to_string(r) + ": the device reported " + std::to_string(n0[r]) + " candidates");
         if (pairs && n0[r]) HIP_OK(hipMemcpy(static_cast<char*>(pairs) + r * n * 8, blk + 8, (size_t)n0[r] * 8, hipMemcpyDeviceToHost));
     }
+    return 0;
+}
+
+// launch_cand_sort on caller-supplied candidates (unit parity against a stable sort by descending probability): ONE call of the launcher over every
+// row with candidates, the rows padded to the power of two that holds the longest
+static_assert(kCandSortRowsMax == (int)kWideBatchMax, "the flat rows of a call are at most a wide batch's runs");
+extern "C" int lmrs_op_sort_candidates(int device, const void* pairs, size_t n_rows, size_t ld, const uint32_t* n0, void* sorted) {
+    const std::string what = "lmrs_op_sort_candidates: ";
+    if (!pairs || !n0 || !sorted) return fail(what + "NULL argument");
+    if (n_rows < 1 || n_rows > (size_t)kCandSortRowsMax) return fail(what + "n_rows = " + std::to_string(n_rows) + " is outside 1 .. " + std::to_string(kCandSortRowsMax));
+    if (ld < 1 || ld > ((size_t)1 << 24)) return fail(what + "need 1 <= ld <= 2^24");
+    CandSortArgs cs{}; size_t n0_max = 0;
+    for (size_t r = 0; r < n_rows; ++r) {
+        if (n0[r] > ld) return fail(what + "row " + std::to_string(r) + ": n0 = " + std::to_string(n0[r]) + " exceeds ld = " + std::to_string(ld));
+        if (!n0[r]) continue;
+        cs.t.row[cs.n_rows] = (unsigned)r; cs.t.n0[cs.n_rows] = n0[r]; ++cs.n_rows;
+        n0_max = std::max<size_t>(n0_max, n0[r]);
+    }
+    if (!cs.n_rows) return 0;
+    if (op_begin(device)) return -1;
+    cs.N = sample_sort_min_n();
+    while ((size_t)cs.N < n0_max) cs.N <<= 1;
+    Scratch S;
+    void *dp = S.get(n_rows * ld * 8), *dk = S.get((size_t)cs.n_rows * cs.N * 8);
+    if (!dp || !dk) return fail("hipMalloc failed");
+    HIP_OK(hipMemcpy(dp, pairs, n_rows * ld * 8, hipMemcpyHostToDevice));
+    cs.src = static_cast<const unsigned long long*>(dp); cs.ld = ld; cs.keys = static_cast<unsigned long long*>(dk);
+    HIP_OK(launch_cand_sort(cs, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    for (int f = 0; f < cs.n_rows; ++f)
+        HIP_OK(hipMemcpy(static_cast<char*>(sorted) + (size_t)cs.t.row[f] * ld * 8, cs.keys + (size_t)f * cs.N, (size_t)cs.t.n0[f] * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -156,7 +156,17 @@ struct SampleRowsArgs {
     const SampleRow* tab; const uint32_t* argmax;
     float* part; float* sum; unsigned* cnt; unsigned long long* out;
 };
-hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s);
+// max_rows: the caller's row cap (kSampleRowsMax; lmrs_batch_forward_runs_sample passes its batch's width - the kernels take the row from blockIdx)
+hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s, int max_rows = kSampleRowsMax);
+
+// ---- the candidates of up to kCandSortRowsMax top-p rows sorted together (lmrs_batch_forward_runs_sample's flat rows; see lmrs_kernels.hip).  Row f of the
+// call: n0[f] (1 .. N) candidates {f32 prob >= 0, u32 index} in index order at src + row[f] * ld (8-byte words: launch_sample_rows' result blocks behind
+// their head word, ld = n + 1).  keys: n_rows * N words; afterwards keys + f * N holds row f's n0[f] pairs by descending prob, ties by ascending index.
+// N: a power of two >= every n0, >= sample_sort_min_n().  The table travels in the kernel arguments.  All asynchronous on `s`.
+constexpr int kCandSortRowsMax = 64;
+struct CandSortRows { unsigned row[kCandSortRowsMax]; unsigned n0[kCandSortRowsMax]; };
+struct CandSortArgs { const unsigned long long* src; size_t ld; unsigned long long* keys; int N, n_rows; CandSortRows t; };
+hipError_t launch_cand_sort(const CandSortArgs& a, hipStream_t s);
 
 // thin kernels over the same device functions, for the lmrs_op_* unit-parity entry points
 hipError_t launch_quantize(const float* x, void* q, float* s, int n, int q4, hipStream_t st);

@@ -3057,9 +3057,9 @@ __global__ __launch_bounds__(kBlock) void batch_sample_pairs_kernel(const Sample
         __syncthreads();
     }
 }
-hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s) {
+hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s, int max_rows) {
     static_assert(kSampleRowsMax == kRowTableMax, "a sampled block is a batch pass's rows");
-    if (a.n_rows < 1 || a.n_rows > kSampleRowsMax || a.n < 1 || a.ld < a.n || !a.rows || !a.tab || !a.part || !a.sum || !a.cnt || !a.out) return hipErrorInvalidValue;
+    if (a.n_rows < 1 || a.n_rows > max_rows || a.n < 1 || a.ld < a.n || !a.rows || !a.tab || !a.part || !a.sum || !a.cnt || !a.out) return hipErrorInvalidValue;
     const dim3 grid(kSampleRowsGrid, a.n_rows);
     LMRS_LAUNCH_GRID(batch_sample_scale_max_kernel, grid, kBlock, 0, s, a);
     LMRS_LAUNCH_GRID(batch_sample_exp_kernel, grid, kBlock, 0, s, a);
@@ -3067,6 +3067,81 @@ hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t s) {
     LMRS_LAUNCH_GRID(batch_sample_div_kernel, grid, kBlock, 0, s, a);
     LMRS_LAUNCH_GRID(batch_sample_chain_kernel<true>, dim3(a.n_rows), kBlock, 0, s, a);
     LMRS_LAUNCH_GRID(batch_sample_pairs_kernel, grid, kBlock, 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// sample_topp's sort (sampler.rs:81) for ALL flat rows of a call at once (launch_cand_sort: lmrs_batch_forward_runs_sample).  The one-row route above filters
+// the probabilities again and compacts them with atomics; here batch_sample_pairs_kernel has already left every row's n0 candidates {prob, index} in index
+// order, so a key is one word of the row's result block turned round - (~bits(prob) << 32) | index, the rows padded with ~0 to a common power of two N -
+// and the network is the one above with the row in blockIdx.y: F rows give a local launch F * N / kSortBlock workgroups instead of N / kSortBlock.
+// Unique keys, ascending: the reference's stable-sort permutation (the argument at sample_keys_kernel).  The pairs come back in place over the keys.
+// (The one-row kernels are left as they are: their resources are pinned.)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void cand_sort_keys_kernel(const CandSortArgs a) {
+    const int f = blockIdx.y, n0 = (int)a.t.n0[f];
+    const unsigned long long* src = a.src + (size_t)a.t.row[f] * a.ld;
+    unsigned long long* keys = a.keys + (size_t)f * a.N;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.N; i += gridDim.x * kBlock) {
+        unsigned long long key = ~0ull;
+        if (i < n0) { const unsigned long long w = src[i]; key = ((unsigned long long)(~(unsigned)w) << 32) | (w >> 32); }       // w = {prob, index}: prob in the low word
+        keys[i] = key;
+    }
+}
+// TAIL false: sorts every block of kSortBlock keys of every row (stages k = 2 .. kSortBlock); TAIL true: the steps j = kSortBlock / 2 .. 1 of stage k
+template <bool TAIL>
+__global__ __launch_bounds__(kSortThreads) void cand_sort_local_kernel(unsigned long long* keys_all, int N, int k_outer) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long* t = reinterpret_cast<unsigned long long*>(smem);
+    const int base = blockIdx.x * kSortBlock;
+    unsigned long long* keys = keys_all + (size_t)blockIdx.y * N + base;
+    for (int i = threadIdx.x; i < kSortBlock; i += kSortThreads) t[i] = keys[i];
+    __syncthreads();
+    for (int k = TAIL ? k_outer : 2; k <= (TAIL ? k_outer : kSortBlock); k <<= 1) {
+        for (int j = (TAIL ? kSortBlock : k) >> 1; j > 0; j >>= 1) {
+            for (int q = threadIdx.x; q < kSortBlock / 2; q += kSortThreads) {
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;        // the pair (i, i + j)
+                const bool up = ((base + i) & k) == 0;
+                const unsigned long long x = t[i], y = t[l];
+                if ((x > y) == up) { t[i] = y; t[l] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = threadIdx.x; i < kSortBlock; i += kSortThreads) keys[i] = t[i];
+}
+__global__ __launch_bounds__(kBlock) void cand_sort_global_kernel(unsigned long long* keys_all, int N, int j, int k) {
+    unsigned long long* keys = keys_all + (size_t)blockIdx.y * N;
+    for (int q = blockIdx.x * kBlock + threadIdx.x; q < N / 2; q += gridDim.x * kBlock) {
+        const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
+        const bool up = (i & k) == 0;
+        const unsigned long long x = keys[i], y = keys[l];
+        if ((x > y) == up) { keys[i] = y; keys[l] = x; }
+    }
+}
+__global__ __launch_bounds__(kBlock) void cand_sort_pairs_kernel(const CandSortArgs a) {       // keys -> {prob, index} as sampler.rs:4-8, in place
+    const int f = blockIdx.y, n0 = (int)a.t.n0[f];
+    unsigned long long* keys = a.keys + (size_t)f * a.N;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n0; i += gridDim.x * kBlock) {
+        const unsigned long long key = keys[i];
+        keys[i] = (key << 32) | (unsigned long long)(~(unsigned)(key >> 32));
+    }
+}
+hipError_t launch_cand_sort(const CandSortArgs& a, hipStream_t s) {
+    if (a.N < kSortBlock || (a.N & (a.N - 1)) != 0 || a.n_rows < 1 || a.n_rows > kCandSortRowsMax || !a.src || !a.keys) return hipErrorInvalidValue;
+    for (int f = 0; f < a.n_rows; ++f) if (a.t.n0[f] < 1 || a.t.n0[f] > (unsigned)a.N || a.t.n0[f] > a.ld) return hipErrorInvalidValue;
+    const unsigned F = (unsigned)a.n_rows;
+    const int wide = a.N / kBlock < 256 ? a.N / kBlock : 256, half = a.N / 2 / kBlock < 256 ? a.N / 2 / kBlock : 256;
+    hipLaunchKernelGGL(cand_sort_keys_kernel, dim3(wide, F), dim3(kBlock), 0, s, a);
+    allow_big_lds(reinterpret_cast<const void*>(cand_sort_local_kernel<false>));
+    allow_big_lds(reinterpret_cast<const void*>(cand_sort_local_kernel<true>));
+    const size_t smem = (size_t)kSortBlock * 8;
+    hipLaunchKernelGGL(cand_sort_local_kernel<false>, dim3(a.N / kSortBlock, F), dim3(kSortThreads), smem, s, a.keys, a.N, 0);
+    for (int k = 2 * kSortBlock; k <= a.N; k <<= 1) {
+        for (int j = k >> 1; j >= kSortBlock; j >>= 1) hipLaunchKernelGGL(cand_sort_global_kernel, dim3(half, F), dim3(kBlock), 0, s, a.keys, a.N, j, k);
+        hipLaunchKernelGGL(cand_sort_local_kernel<true>, dim3(a.N / kSortBlock, F), dim3(kSortThreads), smem, s, a.keys, a.N, k);
+    }
+    hipLaunchKernelGGL(cand_sort_pairs_kernel, dim3(wide, F), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -28,6 +28,16 @@ inline std::vector<float> debug_gemm_wide(const std::int8_t* xq, const float* xs
     return out;
 }
 
+// Unit-parity aid: the sort of forward_runs_sample's flat top-p rows on caller-supplied candidates, every row in one call of its launcher.  pairs: n_rows
+// rows of ld {prob, index} entries, the first n0[r] of row r in index order -> a copy with those entries by descending prob, ties in index order
+// (lmrs_op_sort_candidates)
+struct ProbIndex { float prob; std::uint32_t index; };
+inline std::vector<ProbIndex> op_sort_candidates(const std::vector<ProbIndex>& pairs, std::size_t ld, const std::vector<std::uint32_t>& n0, int device = 0) {
+    std::vector<ProbIndex> sorted(pairs);
+    check(lmrs_op_sort_candidates(device, pairs.data(), n0.size(), ld, n0.data(), sorted.data()));
+    return sorted;
+}
+
 class Batch;
 
 class Transformer {
@@ -146,7 +156,7 @@ private:
 class Batch {
 public:
     static constexpr std::uint32_t CTX = LMRS_BATCH_CTX;           // fork's source: the transformer's own cache
-    // wide: up to 64 slots, and forward / generate_greedy / forward_runs take up to 64 rows or runs a call (lmrs_batch_create_wide)
+    // wide: up to 64 slots, and forward / generate_greedy / forward_runs / forward_runs_sample take up to 64 rows or runs a call (lmrs_batch_create_wide)
     Batch(Transformer& t, std::uint32_t n_slots, bool wide = false) : vocab_size_(t.args.vocab_size) {
         check(wide ? lmrs_batch_create_wide(t.ctx_, n_slots, &b_) : lmrs_batch_create(t.ctx_, n_slots, &b_));
     }
@@ -206,6 +216,22 @@ public:
                                       rows ? o.argmax.data() : nullptr, logits ? o.logits.data() : nullptr, k, k ? o.topk_idx.data() : nullptr,
                                       k ? o.topk_logprob.data() : nullptr));
         return o;
+    }
+    // forward_runs with a sampler per run, sampled on the device: the LAST row of every run whose sampler (Sampler::handle(), text.hpp) is not null goes
+    // through Sampler::sample with it -> next[i], bit for bit Transformer::forward_sample's token after the run's tokens on a transformer that holds only
+    // that sequence; a null sampler leaves the run's K/V rows only and next[i] = 0.  Up to width() runs; runs may mix samplers, a top-p sampler in at most
+    // one run of a call  (lmrs_batch_forward_runs_sample)
+    struct SampledRun { std::uint32_t slot, start_pos; std::vector<std::uint32_t> tokens; lmrs_sampler* sampler; };
+    std::vector<std::uint32_t> forward_runs_sample(const std::vector<SampledRun>& runs) {
+        std::vector<std::uint32_t> slot, start, len, tokens, next(runs.size());
+        std::vector<lmrs_sampler*> samplers;
+        for (const SampledRun& r : runs) {
+            slot.push_back(r.slot); start.push_back(r.start_pos); len.push_back(static_cast<std::uint32_t>(r.tokens.size())); samplers.push_back(r.sampler);
+            tokens.insert(tokens.end(), r.tokens.begin(), r.tokens.end());
+        }
+        check(lmrs_batch_forward_runs_sample(b_, static_cast<std::uint32_t>(runs.size()), slot.data(), start.data(), len.data(), tokens.data(), samplers.data(),
+                                             next.data()));
+        return next;
     }
     void debug_kv(std::uint32_t slot, int which, std::uint32_t layer, std::uint32_t pos, float* out) { check(lmrs_batch_debug_kv(b_, slot, which, layer, pos, out)); }
 

@@ -16,6 +16,17 @@ extern "C" {
     // the wide batch (lmrs_batch_create_wide): declared here for the same reason (tests/test_batch_wide_host.py compares them with the header)
     pub fn lmrs_batch_create_wide(ctx: *mut ffi::LmrsCtx, n_slots: u32, out: *mut *mut LmrsBatch) -> c_int;
     pub fn lmrs_batch_width(b: *const LmrsBatch, width: *mut u32) -> c_int;
+    // the sampled ragged pass: declared here as the sampled step is (tests/test_batch_runs_sample_host.py compares it with the header)
+    pub fn lmrs_batch_forward_runs_sample(b: *mut LmrsBatch, n_runs: u32, slot: *const u32, start_pos: *const u32, run_len: *const u32,
+                                          tokens: *const u32, samplers: *const *mut LmrsSampler, next: *mut u32) -> c_int;
+}
+
+/// One run of `Batch::forward_runs_sample`: `tokens` at `start_pos ..` of `slot`; `sampler`: the run's last row is sampled with it, `None`: K/V rows only.
+pub struct SampledRun<'r, 's> {
+    pub slot: u32,
+    pub start_pos: u32,
+    pub tokens: &'r [u32],
+    pub sampler: Option<&'s mut Sampler>,
 }
 
 /// `fork`'s source: the transformer's own cache.
@@ -78,6 +89,27 @@ impl<'t, 'a> Batch<'t, 'a> {
         let mut next = vec![0u32; slot.len()];
         check(unsafe {
             lmrs_batch_forward_sample(self.b, slot.len() as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), handles.as_ptr(), next.as_mut_ptr())
+        });
+        next
+    }
+
+    /// One weight pass over runs of consecutive tokens, one run per slot (a prompt to admit, one decode row; at most `width()` runs and 512 tokens),
+    /// the last row of every run that has a sampler sampled on the device with it: next[i] = `Transformer::forward_sample` after the run's tokens on
+    /// a transformer that holds only that sequence, 0 for a run without a sampler (a prompt chunk that is not the last).
+    pub fn forward_runs_sample(&mut self, runs: &mut [SampledRun]) -> Vec<u32> {
+        let (mut slot, mut start, mut len, mut tokens) = (Vec::new(), Vec::new(), Vec::new(), Vec::new());
+        let mut handles: Vec<*mut LmrsSampler> = Vec::new();
+        for r in runs.iter() {
+            slot.push(r.slot);
+            start.push(r.start_pos);
+            len.push(r.tokens.len() as u32);
+            tokens.extend_from_slice(r.tokens);
+            handles.push(r.sampler.as_ref().map_or(ptr::null_mut(), |s| s.handle));
+        }
+        let mut next = vec![0u32; runs.len()];
+        check(unsafe {
+            lmrs_batch_forward_runs_sample(self.b, runs.len() as u32, slot.as_ptr(), start.as_ptr(), len.as_ptr(), tokens.as_ptr(), handles.as_ptr(),
+                                           next.as_mut_ptr())
         });
         next
     }

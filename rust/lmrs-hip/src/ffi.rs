@@ -74,6 +74,7 @@ extern "C" {
     pub fn lmrs_sampler_topp_sorted_pairs(s: *mut LmrsSampler, sorted_pairs: *const c_void, n0: usize, next: *mut u32) -> c_int;
     pub fn lmrs_op_sample_rows(device: c_int, rows: *mut f32, n_rows: usize, n: usize, temperature: *const f32, top_p: *const f32, rnd: *const f32,
                                token: *mut u32, n0: *mut u32, pairs: *mut c_void) -> c_int;
+    pub fn lmrs_op_sort_candidates(device: c_int, pairs: *const c_void, n_rows: usize, ld: usize, n0: *const u32, sorted: *mut c_void) -> c_int;
 }
 
 /// The reference panics (`assert!` / `expect`); the C ABI returns a status and a message.  Same behaviour for the caller.
