@@ -546,6 +546,51 @@ int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, c
  * list, >= 8192; made anew when a call needs more: 64 MiB for 64 rows of a 128 k vocabulary).  lmrs_batch_forward_sample's buffers are not touched. */
 int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
                                    const uint32_t* tokens, lmrs_sampler* const* samplers, uint32_t* next);
+/* ---- embedding rows in a batch (extensions): the rows of a pass need not be born from token ids.  The reference's multimodal chat loop
+ * (src/bin/chat.rs:84-121) splices the image features of PHI3VProcessor::forward between two get_embeddings blocks and hands the rows to
+ * Transformer::fill_kv_cache (transformer.rs:672-684), which runs forward_layer (:388-657) over them as they are.  The three calls below do that
+ * on a batch slot; the layers never look at where a row came from, so only the source of the rows differs from the token calls. */
+/* == lmrs_fill_kv_cache(embeddings, n, start_pos) on a context that holds only slot's sequence: ONE fill_kv_cache call of the reference
+ * (transformer.rs:672-684; forward_layer, :388-657) run into slot's cache.  embeddings: n rows of dim floats (fill_kv_cache's `embeddings`), taken as
+ * given - no sqrt(dim) scale on Gemma-2 - and never written; n: fill_kv_cache's `n`; start_pos: its `curr_pos`.  Gemma-2's 4096-key window is tested
+ * against start_pos for EVERY row, as one forward_layer(sl = n) call tests it (the u32 `pos - t` of transformer.rs:525) and as lmrs_fill_kv_cache does.
+ * The rows go 512 at a time through the batched pass (the skinny form below 16 rows; one row through the long table's pass).  residual (n*dim, may
+ * be NULL): what the reference leaves in its mutated argument, the residual stream behind the last layer; NULL: nothing is downloaded, which is what
+ * this call saves over lmrs_fill_kv_cache + lmrs_batch_fork.  Q4_0 files with n > 1 give the token-by-token values, the documented deviation of
+ * lmrs_fill_kv_cache.  The context's own cache and the other slots are untouched.
+ * Errors, each with a message of its own that opens with this call's name, before any device work, batch and context left usable: a NULL batch or
+ * embeddings, n == 0, slot >= n_slots, start_pos + n > seq_len.  Non-finite values in the rows are not an error: the reference does not check them. */
+int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const float* embeddings /* n*dim */, uint32_t n,
+                                  uint32_t start_pos, float* residual /* n*dim, may be NULL */);
+/* lmrs_batch_forward_runs with a kind per run: run_kind[i] = 0, run i is a token run, exactly a run of lmrs_batch_forward_runs; 1, an EMBEDDING run -
+ * row j of it is fill_kv_cache(&row, 1, start_pos[i] + j) (transformer.rs:672-684; forward_layer, :388-657) on a context that holds only that
+ * sequence: the row is taken as given (no sqrt(dim) scale on Gemma-2), Gemma-2's window is tested against the row's OWN position, the rest is the
+ * chain every row of the pass shares.  This differs from lmrs_batch_prefill_embeddings - ONE fill_kv_cache(n) call, the window on its first position -
+ * only on Gemma-2 past 4096 positions.
+ *   tokens: one id per row of the TOKEN runs only, packed in run order; embeddings: dim floats per row of the EMBEDDING runs only, packed in run
+ *   order, never written; either may be NULL when the call has no run of its kind.
+ * An embedding run may ask for outputs (n_out): its rows then go through the final norm and the classifier like any other row - on Llama / Phi the
+ * tail of Transformer::forward (transformer.rs:316-384), on Gemma-2 with both soft caps, as for token rows.  All limits are lmrs_batch_forward_runs'
+ * own: at most 512 rows, at most lmrs_batch_width runs, a slot in at most one run; outputs, K/V rows and stale rows as that call documents them.
+ * With run_kind all zero the results are bit for bit lmrs_batch_forward_runs' (the same launches).  A call with an embedding run uploads the rows
+ * into a [512][dim] f32 block on the device (allocated at the first such call, all or nothing, the message gives the bytes) and ONE launch,
+ * source_rows_kernel, stands where the token rows' dequantisation stands: per row the token's embedding with that launch's exact arithmetic, or a
+ * copy of the staged row.
+ * Errors, each with a message of its own that opens with this call's name, before any device work, batch and context left usable: everything
+ * lmrs_batch_forward_runs checks; a run_kind other than 0 or 1 (the run is named); tokens NULL with a token run present; embeddings NULL with an
+ * embedding run present.  Non-finite values in the rows are not an error. */
+int lmrs_batch_forward_runs_embed(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                  const uint32_t* n_out, const uint32_t* run_kind /* 0 tokens, 1 embeddings */, const uint32_t* tokens,
+                                  const float* embeddings, uint32_t* argmax, float* logits,
+                                  uint32_t k, uint32_t* topk_idx, float* topk_logprob);
+/* lmrs_batch_forward_runs_sample with a kind per run: run_kind, tokens and embeddings as lmrs_batch_forward_runs_embed takes them (row j of an
+ * embedding run = fill_kv_cache(&row, 1, start_pos[i] + j), transformer.rs:672-684; forward_layer, :388-657), samplers and next as
+ * lmrs_batch_forward_runs_sample takes them: the last row of an embedding run that has a sampler is sampled like a token run's.  With run_kind all
+ * zero next and the samplers' states are bit for bit lmrs_batch_forward_runs_sample's.  Errors: everything that call checks, and the three of
+ * lmrs_batch_forward_runs_embed, each message opening with this call's name, before any device work; batch, context and samplers left usable. */
+int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                         const uint32_t* run_kind, const uint32_t* tokens, const float* embeddings,
+                                         lmrs_sampler* const* samplers, uint32_t* next);
 /* The sort of lmrs_batch_forward_runs_sample's flat rows on caller-supplied candidates, ONE call of its launcher: pairs = n_rows (1 .. 64) rows of ld
  * (1 .. 2^24) entries {f32 prob >= 0, u32 index}, the first n0[r] (<= ld) of row r in ascending index order.  sorted (n_rows x ld): row r's first
  * n0[r] entries by descending prob, ties by ascending index - what the stable sort of sampler.rs:81 makes of them; the rest of the row, and a row

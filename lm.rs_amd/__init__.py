@@ -31,6 +31,7 @@ EXPORTS = [
     "lmrs_batch_create", "lmrs_batch_destroy", "lmrs_batch_prefill", "lmrs_batch_fork", "lmrs_batch_forward", "lmrs_batch_generate_greedy",
     "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
+    "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -117,6 +118,9 @@ def lib():
         L.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
         L.lmrs_batch_forward_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.lmrs_batch_forward_runs_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        L.lmrs_batch_prefill_embeddings.argtypes = [vp, u32, vp, u32, u32, vp]
+        L.lmrs_batch_forward_runs_embed.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.lmrs_batch_forward_runs_embed_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lmrs_op_sort_candidates.argtypes = [C.c_int, vp, sz, sz, vp, vp]
         L.lmrs_op_sample_rows.argtypes = [C.c_int, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.lmrs_sampler_topp_sorted_pairs.argtypes = [vp, vp, sz, C.POINTER(u32)]
@@ -379,6 +383,11 @@ class Transformer:
         return n.value, b.value
 
 
+def _is_embed_run(rows) -> bool:
+    """a run's rows are embeddings: a 2-D float32 array (token ids come as lists or integer arrays)"""
+    return isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.dtype == np.float32
+
+
 BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BATCH_CTX)
 
 
@@ -414,6 +423,36 @@ class Batch:
         t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
         _chk(lib().lmrs_batch_prefill(self._h, slot, _p(t), t.size, start_pos))
         return start_pos + t.size
+
+    def prefill_embeddings(self, slot: int, embeddings, start_pos: int = 0, residual: bool = False):
+        """ONE Transformer.fill_kv_cache call into `slot`'s cache: embeddings float32 [n, dim], taken as given and never written -> start_pos + n, or
+        with residual=True the tuple (start_pos + n, float32 [n, dim] as the reference leaves its mutated argument); without it nothing is downloaded
+        (lmrs_batch_prefill_embeddings)"""
+        e = np.ascontiguousarray(embeddings, np.float32)
+        dim = self.model.args.dim
+        if e.size % dim:
+            raise LmrsError(f"embeddings must hold whole rows of dim = {dim} floats")
+        n = e.size // dim
+        res = np.empty((n, dim), np.float32) if residual else None
+        _chk(lib().lmrs_batch_prefill_embeddings(self._h, slot, _p(e) if n else None, n, start_pos, _p(res) if residual else None))
+        return (start_pos + n, res) if residual else start_pos + n
+
+    def _run_rows(self, runs):
+        """the rows of runs whose third entry is a token list or a 2-D float32 array of embedding rows -> (run_len, run_kind, tokens, embeddings)"""
+        dim = self.model.args.dim
+        n, kind, toks, embs = [], [], [], []
+        for i, r in enumerate(runs):
+            if _is_embed_run(r[2]):
+                e = np.ascontiguousarray(r[2], np.float32)
+                if e.shape[1] != dim:
+                    raise LmrsError(f"run {i}: embedding rows hold {e.shape[1]} floats, the model's dim is {dim}")
+                n.append(e.shape[0]); kind.append(1); embs.append(e.reshape(-1))
+            else:
+                t = np.ascontiguousarray(r[2], np.uint32).reshape(-1)
+                n.append(t.size); kind.append(0); toks.append(t)
+        t = np.concatenate(toks) if toks else np.empty(0, np.uint32)
+        e = np.concatenate(embs) if embs else np.empty(0, np.float32)
+        return np.array(n, np.uint32), np.array(kind, np.uint32), t, e
 
     def fork(self, src: int, dst: int, n_pos: int) -> None:
         """K/V rows [0, n_pos) of slot `src` (BATCH_CTX: the model's own cache) -> slot `dst` (lmrs_batch_fork)"""
@@ -451,7 +490,20 @@ class Batch:
         """One pass over runs = [(slot, start_pos, tokens, n_out), ...]: run i feeds its tokens at start_pos .. of its slot (a prompt chunk, a draft, one
         decode row; a slot in at most one run, at most 512 tokens in all) and returns outputs for its LAST n_out rows, packed in run order: argmax uint32 [O];
         with logits also float32 [O, vocab_size]; with k > 0 also topk_idx uint32 [O, k] and topk_logprob float32 [O, k] as score_tokens_topk defines
-        them -> argmax, or the tuple (argmax[, logits][, topk_idx, topk_logprob])  (lmrs_batch_forward_runs)"""
+        them -> argmax, or the tuple (argmax[, logits][, topk_idx, topk_logprob])  (lmrs_batch_forward_runs)
+        A run's `tokens` may be a 2-D float32 array [rows, dim] instead: embedding rows, each taken as fill_kv_cache(row, 1, its position) takes it
+        (image features beside decode rows); a call with such a run goes through lmrs_batch_forward_runs_embed"""
+        if any(_is_embed_run(r[2]) for r in runs):
+            s, p, no = (np.array([r[i] for r in runs], np.uint32) for i in (0, 1, 3))
+            n, kind, t, e = self._run_rows(runs)
+            O, V = int(no.astype(np.int64).sum()), self.model.args.vocab_size
+            am = np.empty(O, np.uint32)
+            lg = np.empty((O, V), np.float32) if logits else None
+            ti, tl = (np.empty((O, k), np.uint32), np.empty((O, k), np.float32)) if k else (None, None)
+            _chk(lib().lmrs_batch_forward_runs_embed(self._h, len(runs), _p(s), _p(p), _p(n), _p(no), _p(kind), _p(t) if t.size else None, _p(e),
+                                                     _p(am) if O else None, _p(lg) if logits else None, k, _p(ti) if k else None, _p(tl) if k else None))
+            out = (am,) + ((lg,) if logits else ()) + ((ti, tl) if k else ())
+            return out if len(out) > 1 else am
         toks = [np.ascontiguousarray(r[2], np.uint32).reshape(-1) for r in runs]
         s, p, no = (np.array([r[i] for r in runs], np.uint32) for i in (0, 1, 3))
         n = np.array([t.size for t in toks], np.uint32)
@@ -470,7 +522,16 @@ class Batch:
         ON THE DEVICE with it; None: the run leaves its K/V rows only (a prompt chunk that is not the last).  Up to `width` runs, 512 tokens in all; runs
         may mix argmax, sample_mult and top-p samplers, a top-p sampler in at most one run -> next uint32 [n_runs] (0 for a None entry), bit for bit
         Transformer.forward_sample's token for that sampler after the run's tokens on a model that holds only that sequence
-        (lmrs_batch_forward_runs_sample)"""
+        (lmrs_batch_forward_runs_sample).  A run's `tokens` may be a 2-D float32 array of embedding rows, as in forward_runs
+        (lmrs_batch_forward_runs_embed_sample)"""
+        if any(_is_embed_run(r[2]) for r in runs):
+            s, p = (np.array([r[i] for r in runs], np.uint32) for i in (0, 1))
+            n, kind, t, e = self._run_rows(runs)
+            hs = (C.c_void_p * max(len(runs), 1))(*[None if r[3] is None else r[3]._h for r in runs])
+            nxt = np.zeros(len(runs), np.uint32)
+            _chk(lib().lmrs_batch_forward_runs_embed_sample(self._h, len(runs), _p(s), _p(p), _p(n), _p(kind), _p(t) if t.size else None, _p(e),
+                                                            C.cast(hs, C.c_void_p), _p(nxt)))
+            return nxt
         toks = [np.ascontiguousarray(r[2], np.uint32).reshape(-1) for r in runs]
         s, p = (np.array([r[i] for r in runs], np.uint32) for i in (0, 1))
         n = np.array([t.size for t in toks], np.uint32)

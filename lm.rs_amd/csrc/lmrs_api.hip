@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/lmrs_hip.h"
+#include "lmrs_device_math.h"
 #include "lmrs_format.h"
 #include "lmrs_kernels.h"
 #include "lmrs_score.h"
@@ -2026,6 +2027,7 @@ struct lmrs_batch {
     SampleRow *rs_tab = nullptr, *h_rs_tab = nullptr; float* rs_scratch = nullptr;
     unsigned long long *rs_out = nullptr, *h_rs_heads = nullptr; size_t rs_rows = 0, rs_head_words = 0;
     unsigned long long *cs_keys = nullptr, *h_cs_pairs = nullptr; size_t cs_words = 0;
+    float* embed_stage = nullptr;                       // the embedding rows of a ragged pass, [kRunRowsMax][dim] in caller order (allocated at the first call that has one)
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
     float* k_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->k_cache : kv + (size_t)slot * 2 * slot_floats; }
     float* v_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->v_cache : kv + (size_t)slot * 2 * slot_floats + slot_floats; }
@@ -2036,7 +2038,7 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     (void)hipSetDevice(b->c->device);
     (void)hipStreamSynchronize(b->c->stream);
     for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x, (void*)b->samp_tab, (void*)b->samp_scratch, (void*)b->samp_out}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->rs_tab, (void*)b->rs_scratch, (void*)b->rs_out, (void*)b->cs_keys}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)b->rs_tab, (void*)b->rs_scratch, (void*)b->rs_out, (void*)b->cs_keys, (void*)b->embed_stage}) if (p) (void)hipFree(p);
     for (void* p : {(void*)b->h_rs_tab, (void*)b->h_rs_heads, (void*)b->h_cs_pairs}) if (p) (void)hipHostFree(p);
     if (b->h_samp_tab) (void)hipHostFree(b->h_samp_tab);
     if (b->h_samp_heads) (void)hipHostFree(b->h_samp_heads);
@@ -2142,11 +2144,17 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
 
 // The pinned long table (RunTable) of a pass over n_runs runs, the arguments checked by the caller: caller row j (run order, ascending position) behind table
 // row r, deepest first; sel[o] = the table row of output o.  *rows / *outs: the table's rows and the outputs asked for.
+// Where the rows of a ragged pass come from: kind[i] = 0, run i's rows are the next run_len[i] ids of `tokens`; 1, the next run_len[i] rows (dim floats each) of
+// `embeddings`.  kind null: every run is a token run (the token entry points).  The table's `tok` column then carries a source word per row
+// (source_rows_kernel below): the token id, or kRowFromStage | the row's place among the call's embedding rows.
+struct RunRows { const uint32_t* kind; const uint32_t* tokens; const float* embeddings; };
 static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len, const uint32_t* n_out,
-                       const uint32_t* tokens, size_t* rows_out, size_t* outs) {
-    struct Row { uint32_t run, pos; };
+                       RunRows src, size_t* rows_out, size_t* outs) {
+    struct Row { uint32_t run, pos, word; };
     std::vector<Row> rows;
-    for (uint32_t i = 0; i < n_runs; ++i) for (uint32_t j = 0; j < (run_len ? run_len[i] : 1u); ++j) rows.push_back(Row{i, start_pos[i] + j});
+    uint32_t n_tok = 0, n_emb = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) for (uint32_t j = 0; j < (run_len ? run_len[i] : 1u); ++j)
+        rows.push_back(Row{i, start_pos[i] + j, src.kind && src.kind[i] ? kRowFromStage | n_emb++ : src.tokens[n_tok++]});
     const size_t R = rows.size();
     std::vector<int> order(R), at(R);
     for (size_t j = 0; j < R; ++j) order[j] = (int)j;
@@ -2154,7 +2162,7 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
     RunTable* h = b->h_runs;
     for (size_t r = 0; r < R; ++r) {
         const int j = order[r];
-        h->off[r] = (unsigned long long)slot[rows[j].run] * 2 * b->slot_floats; h->pos[r] = (int)rows[j].pos; h->tok[r] = tokens[j];
+        h->off[r] = (unsigned long long)slot[rows[j].run] * 2 * b->slot_floats; h->pos[r] = (int)rows[j].pos; h->tok[r] = rows[j].word;
         at[j] = (int)r;
     }
     size_t o = 0;
@@ -2168,11 +2176,42 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
 // One pass over the device's long table as it stands: R rows through the layers, then the O rows of sel through the final norm and the classifier to
 // their sink.  step: how far the rows have moved since runs_table (sizes the attention's score vector).  Every GEMM in the weight-streaming forms up to
 // kStreamPassMax rows - the skinny kernel up to 16, the stream kernel above - and launch_gemm_q8's dispatch beyond.
-static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to) {
+// The rows of a ragged pass that has an embedding run (lmrs_batch_forward_runs_embed): one workgroup per table row, where launch_dequant_rows stands in a
+// token-only pass.  (In this file, not beside dequant_rows_kernel: the code object of lmrs_kernels.hip - every kernel of the decode step and of the passes -
+// stays byte for byte what it was; dequant_elem is shared through lmrs_device_math.h.)  src[r] without kRowFromStage is a token id - dequant_rows_kernel's loop and arithmetic, Gemma's one f32 multiply included; with it, the
+// low bits name a row of the staged block (the caller's embedding rows, f32), copied as it is, 16 bytes a lane: fill_kv_cache takes its rows as given.
+__global__ __launch_bounds__(256) void source_rows_kernel(const void* q, const float* s, int q4, const uint32_t* src, const float* staged, int dim, float* out,
+                                                          float scale, int do_scale) {
+    const uint32_t w = src[blockIdx.x];
+    if (w & kRowFromStage) {
+        const float4* from = reinterpret_cast<const float4*>(staged) + (size_t)(w & ~kRowFromStage) * (dim / 4);
+        float4* to = reinterpret_cast<float4*>(out) + (size_t)blockIdx.x * (dim / 4);
+        for (int i = threadIdx.x; i < dim / 4; i += blockDim.x) to[i] = from[i];
+        return;
+    }
+    for (int i = threadIdx.x; i < dim; i += blockDim.x) {
+        float v = dequant_elem(q, s, q4, (size_t)w * dim + i);
+        if (do_scale) v = v * scale;                                        // (embed_kernel's multiply)
+        out[(size_t)blockIdx.x * dim + i] = v;
+    }
+}
+static hipError_t launch_source_rows(const void* q, const float* s, int q4, const uint32_t* src, const float* staged, int n_rows, int dim, float* out, hipStream_t st,
+                              float scale) {
+    if (n_rows < 1 || n_rows > kRunRowsMax || dim < 4 || dim % 4 || !staged) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(source_rows_kernel, dim3(n_rows), dim3(256), 0, st, q, s, q4, src, staged, dim, out, scale, scale != 0.0f ? 1 : 0);
+    return hipGetLastError();
+}
+// staged: the pass has embedding rows, uploaded to that block - the rows come from launch_source_rows instead of token_rows
+static int source_rows(lmrs_ctx* c, const uint32_t* src, const float* staged, int m) {       // token_rows with a source word per row
+    const float scale = c->args.model_type == LMRS_GEMMA ? sqrtf((float)c->args.dim) : 0.0f;
+    HIP_OK(launch_source_rows(c->emb_q, c->emb_s, c->q4, src, staged, m, (int)c->args.dim, c->pf_x, c->stream, scale));
+    return 0;
+}
+static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to, const float* staged = nullptr) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
     form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
-    if (token_rows(c, form.runs.tok, (int)R) || prefill_pass(c, form, (int)R, 0)) return -1;
+    if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
     PassForm cls; cls.skinny = O <= kStreamPassMax;
@@ -2195,7 +2234,7 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
         if (tokens[i] >= c->args.vocab_size) return fail(std::string(what) + ": token " + std::to_string(i) + " out of range");
         if ((size_t)pos[i] + span > c->args.seq_len) return fail(std::string(what) + ": row " + std::to_string(i) + ": pos + " + std::to_string(span) + " positions exceeds seq_len");
     }
-    if (n > (uint32_t)kRowTableMax) { size_t R, O; runs_table(b, n, slot, pos, nullptr, nullptr, tokens, &R, &O); return 0; }
+    if (n > (uint32_t)kRowTableMax) { size_t R, O; runs_table(b, n, slot, pos, nullptr, nullptr, RunRows{nullptr, tokens, nullptr}, &R, &O); return 0; }
     for (uint32_t i = 0; i < n; ++i) order[i] = (int)i;
     std::stable_sort(order, order + n, [&](int x, int y) { return pos[x] > pos[y]; });
     for (uint32_t r = 0; r < n; ++r) {
@@ -2396,14 +2435,17 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
 // batch's own; behind the layers the rows whose outputs were asked for are made consecutive and only they go through the final norm and the classifier.
 static_assert(kRunRowsMax == kPrefillTokens, "a ragged pass is one chunk of the batched pass");
 // The runs of a ragged pass, checked before any device work (`what` opens every message): *rows / *outs = the rows they hold and the outputs asked for
+// src.kind != null (the calls that take embedding runs): *embeds = the rows of the embedding runs; a kind other than 0 / 1, and a NULL array whose kind is present, are refused
 static int runs_check(const lmrs_batch* b, const std::string& what, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
-                      const uint32_t* n_out, const uint32_t* tokens, size_t* rows, size_t* outs) {
+                      const uint32_t* n_out, RunRows src, size_t* rows, size_t* outs, size_t* embeds = nullptr) {
     const lmrs_args& a = b->c->args;
     if (n_runs < 1 || n_runs > b->width) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(b->width));
-    size_t R = 0, O = 0;
+    size_t R = 0, O = 0, E = 0;
     for (uint32_t i = 0; i < n_runs; ++i) {
         if (run_len[i] < 1) return fail(what + "run " + std::to_string(i) + ": run_len is 0");
         if ((R += run_len[i]) > (size_t)kRunRowsMax) return fail(what + "the runs hold more than " + std::to_string(kRunRowsMax) + " rows");
+        if (src.kind && src.kind[i] > 1) return fail(what + "run " + std::to_string(i) + ": run_kind = " + std::to_string(src.kind[i]) + " is neither 0 (tokens) nor 1 (embeddings)");
+        if (src.kind && src.kind[i]) E += run_len[i];
     }
     uint64_t seen = 0;
     for (uint32_t i = 0; i < n_runs; ++i) {
@@ -2415,32 +2457,45 @@ static int runs_check(const lmrs_batch* b, const std::string& what, uint32_t n_r
         if ((size_t)start_pos[i] + run_len[i] > a.seq_len) return fail(run + "start_pos + run_len exceeds seq_len");
         O += n_out[i];
     }
-    for (size_t j = 0; j < R; ++j) if (tokens[j] >= a.vocab_size) return fail(what + "token " + std::to_string(j) + " out of range");
+    if (R > E && !src.tokens) return fail(what + "tokens is NULL with a token run present");
+    if (E && !src.embeddings) return fail(what + "embeddings is NULL with an embedding run present");
+    for (size_t j = 0; j < R - E; ++j) if (src.tokens[j] >= a.vocab_size) return fail(what + "token " + std::to_string(j) + " out of range");
     *rows = R; *outs = O;
+    if (embeds) *embeds = E;
     return 0;
 }
-extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
-                                       const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
-                                       uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
-    const std::string what = "lmrs_batch_forward_runs: ";
-    if (!b || !slot || !start_pos || !run_len || !n_out || !tokens) return fail(what + "NULL argument");
+// the staged block of a pass with embedding rows: all or nothing, at the first call that has one
+static int embed_stage_alloc(lmrs_batch* b, const std::string& what) {
+    if (b->embed_stage) return 0;
+    const size_t bytes = (size_t)kRunRowsMax * b->c->args.dim * 4;
+    if (hipMalloc(reinterpret_cast<void**>(&b->embed_stage), bytes) != hipSuccess) {
+        (void)hipGetLastError(); b->embed_stage = nullptr;
+        return fail(what + std::to_string(bytes) + " bytes of staging for " + std::to_string(kRunRowsMax) + " embedding rows: out of memory");
+    }
+    return 0;
+}
+// lmrs_batch_forward_runs and lmrs_batch_forward_runs_embed: the arguments' NULL checks are the caller's, `what` opens every message
+static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                             const uint32_t* n_out, RunRows src, uint32_t* argmax, float* logits, uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
     lmrs_ctx* c = b->c;
     const lmrs_args& a = c->args;
-    size_t R = 0, O = 0;
-    if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O)) return -1;
+    size_t R = 0, O = 0, E = 0;
+    if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, src, &R, &O, &E)) return -1;
     if (k && topk_check_k(k, a.vocab_size)) return -1;
     if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
     if (O && !argmax) return fail(what + "argmax is NULL with " + std::to_string(O) + " output rows asked for");
-    runs_table(b, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O);
+    runs_table(b, n_runs, slot, start_pos, run_len, n_out, src, &R, &O);
     HIP_OK(hipSetDevice(c->device));
     if (k && O && topk_alloc(c, c->sc_rows, (int)k)) return -1;
+    if (E && embed_stage_alloc(b, what)) return -1;
     const HostScores hs = host_scores(c);
     const size_t nk = O * k;
     auto enqueue = [&]() -> int {
+        if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * a.dim * 4, hipMemcpyHostToDevice, c->stream));     // the call's embedding rows, in caller order
         HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
         if (batch_state(c)) return -1;
         RowSink to{0, O, logits, k}; to.reduce_too = true;
-        if (runs_pass(b, R, O, 0, to)) return -1;
+        if (runs_pass(b, R, O, 0, to, E ? b->embed_stage : nullptr)) return -1;
         if (!O) return 0;
         HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream));
         if (k) {
@@ -2454,6 +2509,23 @@ extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uin
     if (O) memcpy(argmax, hs.idx, O * 4);
     if (O && k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
     return 0;
+}
+extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                       const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
+                                       uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
+    const std::string what = "lmrs_batch_forward_runs: ";
+    if (!b || !slot || !start_pos || !run_len || !n_out || !tokens) return fail(what + "NULL argument");
+    return forward_runs_from(what, b, n_runs, slot, start_pos, run_len, n_out, RunRows{nullptr, tokens, nullptr}, argmax, logits, k, topk_idx, topk_logprob);
+}
+// Runs of embedding rows beside runs of tokens (Transformer::fill_kv_cache, transformer.rs:672-684, one row at a time - forward_layer, :388-657, with
+// the row as given - where a token run is Transformer::forward): the same pass, the rows' source apart
+extern "C" int lmrs_batch_forward_runs_embed(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                             const uint32_t* n_out, const uint32_t* run_kind, const uint32_t* tokens, const float* embeddings,
+                                             uint32_t* argmax, float* logits, uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
+    const std::string what = "lmrs_batch_forward_runs_embed: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (!slot || !start_pos || !run_len || !n_out || !run_kind) return fail(what + "NULL array");
+    return forward_runs_from(what, b, n_runs, slot, start_pos, run_len, n_out, RunRows{run_kind, tokens, embeddings}, argmax, logits, k, topk_idx, topk_logprob);
 }
 
 // ------------------------------------------------------------------ the sampled ragged pass: lmrs_batch_forward_runs' pass, then Sampler::sample on the last row of every run
@@ -2506,17 +2578,15 @@ static int cand_sort_alloc(lmrs_batch* b, size_t F, size_t N) {
     return 0;
 }
 
-extern "C" int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
-                                              const uint32_t* tokens, lmrs_sampler* const* samplers, uint32_t* next) {
-    const std::string what = "lmrs_batch_forward_runs_sample: ";
-    if (!b) return fail(what + "NULL argument (the batch)");
-    if (!slot || !start_pos || !run_len || !tokens || !samplers || !next) return fail(what + "NULL array");
+// lmrs_batch_forward_runs_sample and lmrs_batch_forward_runs_embed_sample: the arguments' NULL checks are the caller's, `what` opens every message
+static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                    RunRows src, lmrs_sampler* const* samplers, uint32_t* next) {
     lmrs_ctx* c = b->c;
     if (n_runs < 1 || n_runs > b->width) return fail(what + "n_runs = " + std::to_string(n_runs) + " is outside 1 .. " + std::to_string(b->width));
     uint32_t n_out[kWideBatchMax]; int out_of[kWideBatchMax];                    // out_of[i]: run i's row among the outputs (-1: none)
-    size_t R = 0, O = 0;
+    size_t R = 0, O = 0, E = 0;
     for (uint32_t i = 0; i < n_runs; ++i) { n_out[i] = samplers[i] ? 1u : 0u; out_of[i] = samplers[i] ? (int)O++ : -1; }
-    if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O)) return -1;
+    if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, src, &R, &O, &E)) return -1;
     const size_t V = c->args.vocab_size;
     SampleRow par[kWideBatchMax]; bool topp[kWideBatchMax]; bool sampled = false;
     for (uint32_t i = 0; i < n_runs; ++i) {
@@ -2534,16 +2604,18 @@ extern "C" int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, co
     }
     if (sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
     if (O > (size_t)c->sc_rows) return fail(what + "the logits block holds " + std::to_string(c->sc_rows) + " rows of this vocabulary, " + std::to_string(O) + " outputs were asked for");
-    runs_table(b, n_runs, slot, start_pos, run_len, n_out, tokens, &R, &O);
+    runs_table(b, n_runs, slot, start_pos, run_len, n_out, src, &R, &O);
     HIP_OK(hipSetDevice(c->device));
     if (sampled && runs_sample_alloc(b, O)) return -1;
+    if (E && embed_stage_alloc(b, what)) return -1;
     for (uint32_t i = 0; i < n_runs; ++i) { next[i] = 0; if (sampled && out_of[i] >= 0) b->h_rs_tab[out_of[i]] = par[i]; }
     const size_t head = b->rs_head_words;
     const HostScores hs = host_scores(c);
     auto enqueue = [&]() -> int {
+        if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * c->args.dim * 4, hipMemcpyHostToDevice, c->stream));
         HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
         if (batch_state(c)) return -1;
-        if (runs_pass(b, R, O, 0, RowSink{0, O, nullptr, 0})) return -1;          // the reduction: sample_argmax of every output row -> sc_idx; the rows stay in sc_logits
+        if (runs_pass(b, R, O, 0, RowSink{0, O, nullptr, 0}, E ? b->embed_stage : nullptr)) return -1;          // the reduction: sample_argmax of every output row -> sc_idx; the rows stay in sc_logits
         if (!O) return 0;
         if (!sampled) { HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
         HIP_OK(hipMemcpyAsync(b->rs_tab, b->h_rs_tab, O * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
@@ -2591,6 +2663,70 @@ extern "C" int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, co
         if (rc) return fail(what + "run " + std::to_string(i) + ": " + g_err);
     }
     return 0;
+}
+extern "C" int lmrs_batch_forward_runs_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                              const uint32_t* tokens, lmrs_sampler* const* samplers, uint32_t* next) {
+    const std::string what = "lmrs_batch_forward_runs_sample: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (!slot || !start_pos || !run_len || !tokens || !samplers || !next) return fail(what + "NULL array");
+    return forward_runs_sample_from(what, b, n_runs, slot, start_pos, run_len, RunRows{nullptr, tokens, nullptr}, samplers, next);
+}
+extern "C" int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
+                                                    const uint32_t* run_kind, const uint32_t* tokens, const float* embeddings,
+                                                    lmrs_sampler* const* samplers, uint32_t* next) {
+    const std::string what = "lmrs_batch_forward_runs_embed_sample: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (!slot || !start_pos || !run_len || !run_kind || !samplers || !next) return fail(what + "NULL array");
+    return forward_runs_sample_from(what, b, n_runs, slot, start_pos, run_len, RunRows{run_kind, tokens, embeddings}, samplers, next);
+}
+
+// ------------------------------------------------------------------ embedding rows into a slot: ONE fill_kv_cache call (transformer.rs:672-684) on the slot's cache
+// (lmrs_fill_kv_cache's batched arm with the slot's caches in the pass's form: the rows as given, the window on start_pos for every row, 512 rows a chunk;
+// the residual rows come back only when asked for).  One row goes through the long table with an embedding row in it, as lmrs_batch_prefill's one token
+// goes through the table pass.
+extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const float* embeddings, uint32_t n, uint32_t start_pos, float* residual) {
+    const std::string what = "lmrs_batch_prefill_embeddings: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    lmrs_ctx* c = b->c;
+    const lmrs_args& a = c->args;
+    if (n == 0) return fail(what + "no rows given (n == 0)");
+    if (!embeddings) return fail(what + "NULL argument (embeddings)");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if ((size_t)start_pos + n > a.seq_len) return fail(what + "start_pos + n = " + std::to_string((size_t)start_pos + n) + " exceeds seq_len = " + std::to_string(a.seq_len));
+    HIP_OK(hipSetDevice(c->device));
+    const size_t dim = a.dim;
+    const int win = pass_win_base(c, start_pos, false);
+    if (n == 1) {
+        const uint32_t one = 1, none = 0;
+        size_t R = 0, O = 0;
+        if (embed_stage_alloc(b, what)) return -1;
+        runs_table(b, 1, &slot, &start_pos, &one, &none, RunRows{&one, nullptr, embeddings}, &R, &O);
+        auto enqueue = [&]() -> int {
+            HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings, dim * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+            if (set_state(c, start_pos, 0, win)) return -1;
+            if (runs_pass(b, 1, 0, 0, RowSink{0, 0, nullptr, 0}, b->embed_stage)) return -1;
+            if (residual) HIP_OK(hipMemcpyAsync(residual, c->pf_x, dim * 4, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (enqueue()) return batch_failed(c);
+        return finish_call(c);
+    }
+    auto enqueue = [&]() -> int {
+        if (set_state(c, start_pos, 0, win)) return -1;
+        PassForm form; form.skinny = n < kShortPassMax; form.k_cache = b->k_of(slot); form.v_cache = b->v_of(slot);
+        auto upload_rows = [&](size_t i0, int m) -> int {
+            HIP_OK(hipMemcpyAsync(c->pf_x, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
+            return 0;
+        };
+        auto download_rows = [&](size_t i0, int m) -> int {
+            if (residual) HIP_OK(hipMemcpyAsync(residual + i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        return prefill_chunks(c, form, start_pos, n, upload_rows, download_rows);
+    };
+    if (enqueue()) return batch_failed(c);
+    return finish_call(c);
 }
 
 extern "C" int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out) {

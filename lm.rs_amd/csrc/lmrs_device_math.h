@@ -280,4 +280,18 @@ __device__ __forceinline__ float reduce_add8(float v0, float v1, float v2, float
     return d0 + d1;
 }
 
+constexpr int kGS = 128;             // quantisation group size (the reference exporter always uses 128)
+
+// ------------------------------------------------------------------------------------------------
+// Embedding row element (transformer.rs:324-332; quantization.rs:25-42) - dequantised on the fly, which is bit-identical to reading
+// the reference's load-time f32 copy of the table.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float dequant_elem(const void* q, const float* s, int q4, size_t idx) {     // q4: 0 Q8_0, 1 Q4_0, 2 f32 table (q_type None)
+    if (q4 == 2) return reinterpret_cast<const float*>(q)[idx];
+    if (!q4) return (float)reinterpret_cast<const int8_t*>(q)[idx] * s[idx / kGS];
+    const int8_t v = reinterpret_cast<const int8_t*>(q)[idx >> 1];
+    const int nib = (idx & 1) ? ((v >> 4) & 0x0F) - 8 : (v & 0x0F) - 8;
+    return (float)nib * s[idx / kGS];
+}
+
 }  // namespace lmrs

@@ -261,6 +261,9 @@ hipError_t launch_rope_scatter_runs(float* qkv, float* k_cache, float* v_cache, 
 hipError_t launch_attention_runs(const AttnArgs& a, RowView rows, int n_rows, int max_T, hipStream_t s);
 // dst[r][0 .. n) = src[sel[r]][0 .. n), r < n_rows (n a multiple of 4): the rows of a pass whose logits were asked for, made consecutive for the classifier
 hipError_t launch_select_rows(const float* src, const uint32_t* sel, float* dst, int n, int n_rows, hipStream_t s);
+// A ragged pass with embedding runs (source_rows_kernel, lmrs_api.hip): the `tok` column carries a source word per row - a token id (< 2^31: vocab_size is
+// far below), or kRowFromStage | s for row s of the staged block of embedding rows
+constexpr uint32_t kRowFromStage = 0x80000000u;
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

@@ -41,7 +41,6 @@
 namespace lmrs {
 
 constexpr int kBlock = 256;          // 4 waves
-constexpr int kGS = 128;             // quantisation group size (the reference exporter always uses 128)
 
 // ------------------------------------------------------------------------------------------------
 // Activation prologue device functions (shared by the fused GEMV and the lmrs_op_* kernels)
@@ -195,18 +194,6 @@ __device__ __forceinline__ void load_vec(float4 (&v)[NP], const float* __restric
             if (e < n) v[i] = *reinterpret_cast<const float4*>(x + e);
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Embedding row element (transformer.rs:324-332; quantization.rs:25-42) - dequantised on the fly, which is bit-identical to reading
-// the reference's load-time f32 copy of the table.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dequant_elem(const void* q, const float* s, int q4, size_t idx) {     // q4: 0 Q8_0, 1 Q4_0, 2 f32 table (q_type None)
-    if (q4 == 2) return reinterpret_cast<const float*>(q)[idx];
-    if (!q4) return (float)reinterpret_cast<const int8_t*>(q)[idx] * s[idx / kGS];
-    const int8_t v = reinterpret_cast<const int8_t*>(q)[idx >> 1];
-    const int nib = (idx & 1) ? ((v >> 4) & 0x0F) - 8 : (v & 0x0F) - 8;
-    return (float)nib * s[idx / kGS];
 }
 
 // sample_argmax (sampler.rs:29-41) over per-thread candidates (larger value wins, ties -> lower index = first index of the maximum),

@@ -168,6 +168,12 @@ public:
     void prefill(std::uint32_t slot, const std::vector<std::uint32_t>& tokens, std::uint32_t start_pos = 0) {
         check(lmrs_batch_prefill(b_, slot, tokens.data(), tokens.size(), start_pos));
     }
+    // ONE fill_kv_cache call (transformer.rs:672-684) into slot's cache: n = embeddings.size() / dim rows, taken as given, at start_pos ..; residual
+    // (optional): what the reference leaves in its mutated argument - without it nothing is downloaded  (lmrs_batch_prefill_embeddings)
+    void prefill_embeddings(std::uint32_t slot, const std::vector<float>& embeddings, std::uint32_t n, std::uint32_t start_pos = 0, std::vector<float>* residual = nullptr) {
+        if (residual) residual->resize(embeddings.size());
+        check(lmrs_batch_prefill_embeddings(b_, slot, embeddings.data(), n, start_pos, residual ? residual->data() : nullptr));
+    }
     void fork(std::uint32_t src_slot, std::uint32_t dst_slot, std::uint32_t n_pos) { check(lmrs_batch_fork(b_, src_slot, dst_slot, n_pos)); }
     // row i = forward(tokens[i], pos[i]) on slot[i] -> the argmax of every row; logits (optional): n x vocab_size
     std::vector<std::uint32_t> forward(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
@@ -199,19 +205,34 @@ public:
     // One pass over runs of consecutive tokens, one run per slot (a prompt chunk, a draft to verify, one decode row; at most 512 tokens in all): outputs for
     // the LAST n_out rows of every run, packed in run order - argmax always, logits (x vocab_size) and the k first candidates with their log-probabilities
     // (x k, as lmrs_score_tokens_topk defines them) when asked for  (lmrs_batch_forward_runs)
-    struct Run { std::uint32_t slot, start_pos; std::vector<std::uint32_t> tokens; std::uint32_t n_out; };
+    // A run with `embeddings` (rows x dim floats, `tokens` empty) feeds those rows instead of token ids, each as fill_kv_cache(&row, 1, its position)
+    // takes it; the call then goes through lmrs_batch_forward_runs_embed
+    struct Run { std::uint32_t slot, start_pos; std::vector<std::uint32_t> tokens; std::uint32_t n_out; std::vector<float> embeddings = {}; std::uint32_t n_embed = 0; };
     struct RunsOut { std::vector<std::uint32_t> argmax; std::vector<float> logits; std::vector<std::uint32_t> topk_idx; std::vector<float> topk_logprob; };
     RunsOut forward_runs(const std::vector<Run>& runs, std::uint32_t k = 0, bool logits = false) {
-        std::vector<std::uint32_t> slot, start, len, n_out, tokens;
+        std::vector<std::uint32_t> slot, start, len, n_out, tokens, kind;
+        std::vector<float> embeddings;
         std::size_t rows = 0;
+        bool embed = false;
         for (const Run& r : runs) {
-            slot.push_back(r.slot); start.push_back(r.start_pos); len.push_back(static_cast<std::uint32_t>(r.tokens.size())); n_out.push_back(r.n_out);
+            const bool e = r.n_embed > 0;
+            if (e && !r.tokens.empty()) throw Panic("Batch::forward_runs: a run holds tokens or embeddings, not both");
+            slot.push_back(r.slot); start.push_back(r.start_pos); len.push_back(e ? r.n_embed : static_cast<std::uint32_t>(r.tokens.size())); n_out.push_back(r.n_out);
+            kind.push_back(e ? 1u : 0u);
             tokens.insert(tokens.end(), r.tokens.begin(), r.tokens.end());
+            embeddings.insert(embeddings.end(), r.embeddings.begin(), r.embeddings.end());
             rows += r.n_out;
+            embed = embed || e;
         }
         RunsOut o;
         o.argmax.resize(rows); o.topk_idx.resize(rows * k); o.topk_logprob.resize(rows * k);
         if (logits) o.logits.resize(rows * vocab_size_);
+        if (embed) {
+            check(lmrs_batch_forward_runs_embed(b_, static_cast<std::uint32_t>(runs.size()), slot.data(), start.data(), len.data(), n_out.data(), kind.data(),
+                                                tokens.empty() ? nullptr : tokens.data(), embeddings.data(), rows ? o.argmax.data() : nullptr,
+                                                logits ? o.logits.data() : nullptr, k, k ? o.topk_idx.data() : nullptr, k ? o.topk_logprob.data() : nullptr));
+            return o;
+        }
         check(lmrs_batch_forward_runs(b_, static_cast<std::uint32_t>(runs.size()), slot.data(), start.data(), len.data(), n_out.data(), tokens.data(),
                                       rows ? o.argmax.data() : nullptr, logits ? o.logits.data() : nullptr, k, k ? o.topk_idx.data() : nullptr,
                                       k ? o.topk_logprob.data() : nullptr));
@@ -221,13 +242,26 @@ public:
     // through Sampler::sample with it -> next[i], bit for bit Transformer::forward_sample's token after the run's tokens on a transformer that holds only
     // that sequence; a null sampler leaves the run's K/V rows only and next[i] = 0.  Up to width() runs; runs may mix samplers, a top-p sampler in at most
     // one run of a call  (lmrs_batch_forward_runs_sample)
-    struct SampledRun { std::uint32_t slot, start_pos; std::vector<std::uint32_t> tokens; lmrs_sampler* sampler; };
+    // (a run with `embeddings`, as in Run: the call goes through lmrs_batch_forward_runs_embed_sample)
+    struct SampledRun { std::uint32_t slot, start_pos; std::vector<std::uint32_t> tokens; lmrs_sampler* sampler; std::vector<float> embeddings = {}; std::uint32_t n_embed = 0; };
     std::vector<std::uint32_t> forward_runs_sample(const std::vector<SampledRun>& runs) {
-        std::vector<std::uint32_t> slot, start, len, tokens, next(runs.size());
+        std::vector<std::uint32_t> slot, start, len, tokens, kind, next(runs.size());
+        std::vector<float> embeddings;
         std::vector<lmrs_sampler*> samplers;
+        bool embed = false;
         for (const SampledRun& r : runs) {
-            slot.push_back(r.slot); start.push_back(r.start_pos); len.push_back(static_cast<std::uint32_t>(r.tokens.size())); samplers.push_back(r.sampler);
+            const bool e = r.n_embed > 0;
+            if (e && !r.tokens.empty()) throw Panic("Batch::forward_runs_sample: a run holds tokens or embeddings, not both");
+            slot.push_back(r.slot); start.push_back(r.start_pos); len.push_back(e ? r.n_embed : static_cast<std::uint32_t>(r.tokens.size())); samplers.push_back(r.sampler);
+            kind.push_back(e ? 1u : 0u);
             tokens.insert(tokens.end(), r.tokens.begin(), r.tokens.end());
+            embeddings.insert(embeddings.end(), r.embeddings.begin(), r.embeddings.end());
+            embed = embed || e;
+        }
+        if (embed) {
+            check(lmrs_batch_forward_runs_embed_sample(b_, static_cast<std::uint32_t>(runs.size()), slot.data(), start.data(), len.data(), kind.data(),
+                                                       tokens.empty() ? nullptr : tokens.data(), embeddings.data(), samplers.data(), next.data()));
+            return next;
         }
         check(lmrs_batch_forward_runs_sample(b_, static_cast<std::uint32_t>(runs.size()), slot.data(), start.data(), len.data(), tokens.data(), samplers.data(),
                                              next.data()));

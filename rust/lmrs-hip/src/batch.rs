@@ -19,6 +19,28 @@ extern "C" {
     // the sampled ragged pass: declared here as the sampled step is (tests/test_batch_runs_sample_host.py compares it with the header)
     pub fn lmrs_batch_forward_runs_sample(b: *mut LmrsBatch, n_runs: u32, slot: *const u32, start_pos: *const u32, run_len: *const u32,
                                           tokens: *const u32, samplers: *const *mut LmrsSampler, next: *mut u32) -> c_int;
+    // embedding rows in a slot and in the ragged passes: declared here as the sampled calls are (tests/test_batch_embed_host.py compares them with the header)
+    pub fn lmrs_batch_prefill_embeddings(b: *mut LmrsBatch, slot: u32, embeddings: *const f32, n: u32, start_pos: u32, residual: *mut f32) -> c_int;
+    pub fn lmrs_batch_forward_runs_embed(b: *mut LmrsBatch, n_runs: u32, slot: *const u32, start_pos: *const u32, run_len: *const u32, n_out: *const u32,
+                                         run_kind: *const u32, tokens: *const u32, embeddings: *const f32, argmax: *mut u32, logits: *mut f32,
+                                         k: u32, topk_idx: *mut u32, topk_logprob: *mut f32) -> c_int;
+    pub fn lmrs_batch_forward_runs_embed_sample(b: *mut LmrsBatch, n_runs: u32, slot: *const u32, start_pos: *const u32, run_len: *const u32,
+                                                run_kind: *const u32, tokens: *const u32, embeddings: *const f32,
+                                                samplers: *const *mut LmrsSampler, next: *mut u32) -> c_int;
+}
+
+/// What a run of `Batch::forward_runs_embed` feeds: token ids, or rows of `dim` floats taken as `Transformer::fill_kv_cache` takes them.
+pub enum RunRows<'r> {
+    Tokens(&'r [u32]),
+    Embeddings(&'r [f32]),
+}
+
+/// One run of `Batch::forward_runs_embed`: `rows` at `start_pos ..` of `slot`, outputs for its last `n_out` rows.
+pub struct EmbedRun<'r> {
+    pub slot: u32,
+    pub start_pos: u32,
+    pub rows: RunRows<'r>,
+    pub n_out: u32,
 }
 
 /// One run of `Batch::forward_runs_sample`: `tokens` at `start_pos ..` of `slot`; `sampler`: the run's last row is sampled with it, `None`: K/V rows only.
@@ -64,6 +86,55 @@ impl<'t, 'a> Batch<'t, 'a> {
     /// `Transformer::prefill_tokens` into `slot`'s cache.
     pub fn prefill(&mut self, slot: u32, tokens: &[u32], start_pos: u32) {
         check(unsafe { ffi::lmrs_batch_prefill(self.b, slot, tokens.as_ptr(), tokens.len(), start_pos) });
+    }
+
+    /// ONE `Transformer::fill_kv_cache` call into `slot`'s cache: `embeddings.len() / dim` rows, taken as given, from `start_pos` on.  With
+    /// `residual` the rows come back as the reference leaves them in its mutated argument; without it nothing is downloaded.
+    pub fn prefill_embeddings(&mut self, slot: u32, embeddings: &[f32], dim: usize, start_pos: u32, residual: Option<&mut [f32]>) {
+        assert!(dim > 0 && embeddings.len() % dim == 0, "whole rows of dim floats");
+        let rp = match residual {
+            Some(r) => {
+                assert!(r.len() == embeddings.len(), "residual holds as many floats as embeddings");
+                r.as_mut_ptr()
+            }
+            None => ptr::null_mut(),
+        };
+        check(unsafe { lmrs_batch_prefill_embeddings(self.b, slot, embeddings.as_ptr(), (embeddings.len() / dim) as u32, start_pos, rp) });
+    }
+
+    /// One weight pass over runs of tokens and runs of embedding rows (`dim` floats a row), one run per slot: the argmax of every output row, in run
+    /// order.  Row j of an embedding run is `fill_kv_cache(&row, 1, start_pos + j)` on a transformer that holds only that sequence.
+    pub fn forward_runs_embed(&mut self, runs: &[EmbedRun], dim: usize) -> Vec<u32> {
+        let (mut slot, mut start, mut len, mut n_out, mut kind) = (Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new());
+        let (mut tokens, mut embeddings): (Vec<u32>, Vec<f32>) = (Vec::new(), Vec::new());
+        for r in runs.iter() {
+            slot.push(r.slot);
+            start.push(r.start_pos);
+            n_out.push(r.n_out);
+            match r.rows {
+                RunRows::Tokens(t) => {
+                    len.push(t.len() as u32);
+                    kind.push(0u32);
+                    tokens.extend_from_slice(t);
+                }
+                RunRows::Embeddings(e) => {
+                    assert!(dim > 0 && e.len() % dim == 0, "whole rows of dim floats");
+                    len.push((e.len() / dim) as u32);
+                    kind.push(1u32);
+                    embeddings.extend_from_slice(e);
+                }
+            }
+        }
+        let outs: usize = n_out.iter().map(|&n| n as usize).sum();
+        let mut argmax = vec![0u32; outs];
+        let tp = if tokens.is_empty() { ptr::null() } else { tokens.as_ptr() };
+        let ep = if embeddings.is_empty() { ptr::null() } else { embeddings.as_ptr() };
+        let ap = if outs > 0 { argmax.as_mut_ptr() } else { ptr::null_mut() };
+        check(unsafe {
+            lmrs_batch_forward_runs_embed(self.b, runs.len() as u32, slot.as_ptr(), start.as_ptr(), len.as_ptr(), n_out.as_ptr(), kind.as_ptr(), tp, ep, ap,
+                                          ptr::null_mut(), 0, ptr::null_mut(), ptr::null_mut())
+        });
+        argmax
     }
 
     /// K/V rows `[0, n_pos)` of `src` (`BATCH_CTX`: the transformer's own cache) into `dst`.
