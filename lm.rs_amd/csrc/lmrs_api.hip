@@ -78,11 +78,13 @@ struct lmrs_ctx {
     // pinned host
     unsigned long long* samp_keys = nullptr; float* samp_pairs = nullptr; void* h_pairs = nullptr; int samp_cap = 0;   // lmrs_forward_sample: the device sort of top-p candidates (allocated on first use)
     float* h_logits = nullptr; uint32_t* h_tok = nullptr; DevState* h_st = nullptr; unsigned h_st_next = 0;   // h_st: ring of kStateSlots pinned slots (an async copy may still be reading the previous one)
-    // the step graphs by form (StepForm: qkv + attention mode 0..2 | 3 + split-attention bucket 0..3) and steps per launch ([0] one, [1] multi_k):
+    // the step graphs by form (StepForm: qkv + attention mode 0..2 | 3 + split-attention bucket 0..3 | 7 + bucket: the split form with its scores in the
+    // qkv launch) and steps per launch ([0] one, [1] multi_k):
     // step_graph captures a missing one; the graph of position 0's form (primary_graph) is what says "this context replays graphs"
-    hipGraphExec_t g_steps[7][2] = {}, g_layers = nullptr;
+    hipGraphExec_t g_steps[11][2] = {}, g_layers = nullptr;
     // long contexts: from att_split_pos on a step's attention is the split pair (256-key chunks: 4, 8, 16, 32 by context bucket), scores in att_S
     float* att_S = nullptr; int att_split_pos = 0;
+    bool split_merged = false;                             // the split form's scores ride in the qkv launch (launch_qkv_scores): one GPU, quantised files, LMRS_ATT_SPLIT_MERGED
     // batched forward_layer (fill_kv_cache): device buffers for kPrefillTokens tokens, allocated on first use
     float *pf_x = nullptr, *pf_q = nullptr, *pf_k = nullptr, *pf_ao = nullptr, *pf_h = nullptr, *pf_xs = nullptr, *pf_t = nullptr; int8_t* pf_xq = nullptr; float* pf_att = nullptr; size_t pf_att_cap = 0;
     bool pf_ready = false;                                 // every prefill buffer above is allocated
@@ -171,8 +173,9 @@ bool prefill_tp_shapes_ok(const lmrs_ctx* c) {
 size_t prefill_tp_block(size_t n_l) { return pad256((size_t)kPrefillTokens * n_l + (size_t)kPrefillTokens * (n_l / 128) * 4); }
 
 // The form of one decode step: how it runs qkv + attention (qa_mode, see lmrs_ctx::qkv_att) and, when its attention is the split pair, over how many
-// 256-key chunks (then qa_mode is 0: the merged launch has no split form).  A value handed down to the enqueue functions, never context state.
-struct StepForm { int qa_mode = 0, split_chunks = 0; };
+// 256-key chunks (then qa_mode is 0) - as the plain qkv launch, the score launch and the value launch, or, split_merged, with the scores inside the
+// qkv launch (launch_qkv_scores).  A value handed down to the enqueue functions, never context state.
+struct StepForm { int qa_mode = 0, split_chunks = 0; bool split_merged = false; };
 // The form of one batched pass, a value in the same way: skinny = every GEMM of it, the layers' and the classifier's, in the weight-streaming forms (GemmArgs::skinny: up to 16 rows, a batch pass up to 64)
 // rows: the pass is lmrs_batch_forward's - row r is one token of its own sequence (the device row table, lmrs_kernels.h; max_T = the deepest row's
 // position + 1); null: m consecutive positions of one sequence, as always.  k_cache / v_cache: the caches the pass reads and writes - a batch's (with
@@ -189,6 +192,7 @@ StepForm step_form_for(const lmrs_ctx* c, uint32_t pos, bool merged = true) {
         int b = 0;
         while (b < 3 && pos >= (1024u << b)) ++b;
         f.split_chunks = 4 << b;
+        f.split_merged = merged && c->split_merged;
     } else if (merged && c->qkv_att) f.qa_mode = (int)pos < c->qa_wave_T ? 2 : ((int)pos < c->qa_max_T ? 1 : 0);
     return f;
 }
@@ -299,7 +303,15 @@ int enqueue_layer(lmrs_ctx* c, StepForm f, int l) {
     t.q = c->q; t.k_raw = c->k_raw; t.k_cache = c->k_cache; t.v_cache = c->v_cache; t.rope = c->rope; t.out = c->att_out;
     t.n_heads = a.n_heads; t.n_kv_heads = a.n_kv_heads; t.head_size = a.head_size; t.seq_len = a.seq_len; t.layer = l;
     t.gemma = gemma; t.st = c->st;
-    if (f.qa_mode && !f.split_chunks) {
+    if (f.split_chunks && f.split_merged) {
+        // 1 + the scores of 2 as ONE launch: the (head, key chunk) score items poll the granules the qkv workgroups write (launch_qkv_scores); then the values
+        g.gran = c->gran + (size_t)l * (c->att_dim + 2 * c->kv_dim); g.seq = c->seq;
+        HIP_OK(launch_qkv_scores(g, pending ? PRO_ADD_RMS_QUANT : PRO_RMS_QUANT, t, c->att_S, c->err, f.split_chunks, c->sw.att_split_score_wgs, c->stream));
+        g.gran = nullptr; g.seq = nullptr;
+        t.dbg = c->dbg ? c->dbg + 8 * (c->dbg_node++) : nullptr;
+        set_launch_tag(1);
+        HIP_OK(launch_attention_split_values(t, c->att_S, c->stream));
+    } else if (f.qa_mode && !f.split_chunks) {
         // 1 + 2 as ONE launch: the attention workgroups poll the granules the qkv workgroups write (launch_qkv_attn)
         g.gran = c->gran + (size_t)l * (c->att_dim + 2 * c->kv_dim); g.seq = c->seq;
         t.dbg = c->dbg ? c->dbg + 8 * (c->dbg_node++) : nullptr;
@@ -637,7 +649,7 @@ int capture(lmrs_ctx* c, StepForm f, bool full, hipGraphExec_t* out, int n_steps
 
 // ---- the table of step graphs (lmrs_ctx::g_steps): the graph of `k` steps of form `f`, captured when it is not there yet; null: the capture failed
 hipGraphExec_t step_graph(lmrs_ctx* c, StepForm f, int k = 1) {
-    hipGraphExec_t& g = c->g_steps[f.split_chunks ? __builtin_ctz(f.split_chunks) + 1 : f.qa_mode][k > 1];      // (chunks 4, 8, 16, 32 -> 3 .. 6)
+    hipGraphExec_t& g = c->g_steps[f.split_chunks ? __builtin_ctz(f.split_chunks) + (f.split_merged ? 5 : 1) : f.qa_mode][k > 1];      // (chunks 4, 8, 16, 32 -> 3 .. 6, scores in the qkv launch: 7 .. 10)
     if (!g && capture(c, f, true, &g, k)) g = nullptr;
     return g;
 }
@@ -1112,6 +1124,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
         // (the wave forms' prefetch reads whole 64-row blocks of the caches - 128 rows for the 64-wide heads; their form for positions 128 .. 255 clamps its rows to the sequence)
         if (c->qa_wave_T > (int)a.seq_len) c->qa_wave_T = a.head_size == 64 && a.seq_len >= 128 ? (int)a.seq_len : 0;
     }
+    c->split_merged = c->qkv_att && !sharded && sw.att_split_merged;      // (sharded contexts and f32 files: the split form stays six launches)
     if (!sharded) c->multi_k = sw.steps_per_graph;   // (measured: 4 steps per launch +1.5 % on a 20-step run, no effect on long runs)
     c->cls_tail = !sharded && !f32w && V < (1u << 20) - 1 && sw.cls_tail;
     if (!sharded) {
@@ -2921,7 +2934,9 @@ extern "C" int lmrs_step_info(const lmrs_ctx* c, uint32_t pos, int* n_launches, 
     double b = L * ((dim * att + 2 * dim * kv + att * dim + 3 * dim * hid) * (bpe + 4.0 / 128.0) + n_norm * dim * 4) + V * dim * (bpe + 4.0 / 128.0) +
                dim * 4 + L * 2 * kv * 4 * ((double)pos + 2);
     if (algo_bytes) *algo_bytes = b;
-    if (n_launches) *n_launches = (a.model_type == LMRS_GEMMA && !c->gemma_fused ? 7 : (step_form_for(c, pos).qa_mode ? 4 : 5)) * (int)a.n_layers + (c->cls_tail ? 1 : 2);
+    const StepForm f = step_form_for(c, pos);
+    const int att_launches = f.split_chunks ? (f.split_merged ? 2 : 3) : (f.qa_mode ? 1 : 2);      // qkv + attention: merged | separate | the split form with / without its scores in the qkv launch
+    if (n_launches) *n_launches = ((a.model_type == LMRS_GEMMA && !c->gemma_fused ? 5 : 3) + att_launches) * (int)a.n_layers + (c->cls_tail ? 1 : 2);
     return 0;
 }
 

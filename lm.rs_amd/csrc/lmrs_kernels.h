@@ -127,6 +127,12 @@ hipError_t launch_qkv_attn(const GemvArgs& g, int pro, const AttnArgs& t, int* e
 // long contexts: scores by (head, 256-key chunk), softmax + V by (head, quarter of the dims); S: attention_split_scratch_floats(..)
 size_t attention_split_scratch_floats(int n_heads, int seq_len);
 hipError_t launch_attention_split(const AttnArgs& a, float* S, int n_key_chunks, hipStream_t s);
+// the split form with its scores in the qkv launch (five launches per layer): the GEMV workgroups, first in the grid, publish {value, tag}
+// granules (g.gran, g.seq) and the (head, 256-key chunk) score items behind them poll q / the raw key - then the value launch alone.
+// n_key_chunks as above; max_score_wgs > 0: at most that many score workgroups (each then walks several items), 0: as many as are resident.
+// hipErrorNotSupported: no merged class for this shape (the classes of launch_qkv_attn).
+hipError_t launch_qkv_scores(const GemvArgs& g, int pro, const AttnArgs& t, float* S, int* err, int n_key_chunks, int max_score_wgs, hipStream_t s);
+hipError_t launch_attention_split_values(const AttnArgs& a, const float* S, hipStream_t s);
 hipError_t launch_embed(const EmbedArgs& a, hipStream_t s);
 hipError_t launch_addvec(float* x, const float* d, int n, hipStream_t st);
 hipError_t launch_addnorm(float* x, const float* delta, const float* w, int n, float eps, hipStream_t st);   // Gemma: x += rmsnorm(delta, 1 + w)

@@ -2487,16 +2487,17 @@ hipError_t launch_qkv_attn(const GemvArgs& g0, int pro, const AttnArgs& t0, int*
 // (max / exp / the sum chain / divide - the four copies run concurrently) and runs the V chains of its HS/4 dims, streaming
 // a quarter of the V bytes.  Same operations in the same order per value as attention_body: bit-identical.
 // ------------------------------------------------------------------------------------------------
-template <int HS, bool GEMMA>
-__global__ __launch_bounds__(kBlock) void attention_split_scores_kernel(const AttnArgs a, float* S) {
-    __shared__ __attribute__((aligned(16))) float q[HS];
-    __shared__ __attribute__((aligned(16))) float kn[HS];
+// The scores of one (head, 256-key chunk) item: q, kn = HS floats of LDS each; t0 = chunk * kBlock < T.
+// TAG (the merged qkv + scores launch, qkv_scores_kernel): q - and, in the chunk that holds `pos`, the raw key - come from the {value, tag}
+// granules the GEMV workgroups of the SAME launch publish (AttTag, poll_granules), polled after the chunk's K loads and the RoPE terms have
+// been issued; the pairs are then rotated in place in LDS.  Same operations in the same order per score as without TAG: bit-identical.
+template <int HS, bool GEMMA, bool TAG>
+__device__ __forceinline__ void split_scores_item(const AttnArgs& a, float* S, int h, int t0, int pos, float* q, float* kn, const AttTag& tg = AttTag()) {
+    static_assert(!TAG || HS <= kBlock, "granule polling: one value of each vector per lane");
     constexpr int half = HS / 2;
-    const int h = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int kv_mul = a.n_heads / a.n_kv_heads, kvh = h / kv_mul;
-    const int pos = a.st->pos, T = pos + 1;
-    const int t0 = blockIdx.y * kBlock;
-    if (t0 >= T) return;
+    const int T = pos + 1;
     const int SQ = a.seq_len;
     float* kT = att_k_head(a, kvh, HS);
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(kT, 0, HS * SQ * 4, 0x00020000);
@@ -2505,17 +2506,43 @@ __global__ __launch_bounds__(kBlock) void attention_split_scores_kernel(const At
     f32x4v kk[KG];
     att_kload<KG>(kk, krs, tc * 16, 0, SQ);
     const bool mine = pos >= t0 && pos < t0 + kBlock;       // this chunk holds the new key: rotate it, store it (every head of the kv head: same values)
+    float2 cs_tag = make_float2(0.f, 0.f);
+    if constexpr (TAG) {
+        cs_tag = *reinterpret_cast<const float2*>(a.rope + ((size_t)pos * half + (tid < half ? tid : 0)) * 2);   // ahead of the polls
+        if (tid < HS) {
+            const unsigned long long* gp3[3];
+            granules_of(tg, h, kvh, HS, tid, gp3);
+            if (mine) {                                     // workgroup-uniform
+                const unsigned long long* gp[2] = {gp3[0], gp3[1]};
+                unsigned long long xg[2];
+                poll_granules<2>(gp, tg, a.layer, xg);
+                q[tid] = __uint_as_float((unsigned)xg[0]); kn[tid] = __uint_as_float((unsigned)xg[1]);
+            } else {
+                const unsigned long long* gp[1] = {gp3[0]};
+                unsigned long long xg[1];
+                poll_granules<1>(gp, tg, a.layer, xg);
+                q[tid] = __uint_as_float((unsigned)xg[0]);
+            }
+        }
+        lds_barrier();
+    }
     for (int j = tid; j < half; j += kBlock) {              // RoPE (transformer.rs:480-491), as in attention_body
-        const float2 cs = *reinterpret_cast<const float2*>(a.rope + ((size_t)pos * half + j) * 2);
-        const float2 rq = rope_rotate(a.q[h * HS + j], a.q[h * HS + j + half], cs.x, cs.y);
+        float2 cs;
+        if constexpr (TAG) cs = cs_tag; else cs = *reinterpret_cast<const float2*>(a.rope + ((size_t)pos * half + j) * 2);
+        // the raw pair: TAG - in place in LDS (this thread owns both halves of pair j); else from memory
+        const float q0 = TAG ? q[j] : a.q[h * HS + j], q1 = TAG ? q[j + half] : a.q[h * HS + j + half];
+        const float2 rq = rope_rotate(q0, q1, cs.x, cs.y);
         q[j] = rq.x; q[j + half] = rq.y;
         if (mine) {
-            const float2 rk = rope_rotate(a.k_raw[kvh * HS + j], a.k_raw[kvh * HS + j + half], cs.x, cs.y);
+            const float k0 = TAG ? kn[j] : a.k_raw[kvh * HS + j], k1 = TAG ? kn[j + half] : a.k_raw[kvh * HS + j + half];
+            const float2 rk = rope_rotate(k0, k1, cs.x, cs.y);
             kn[j] = rk.x; kn[j + half] = rk.y;
             k_store_pair(kT, SQ, pos, j, half, rk.x, rk.y);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the key stores must have reached the cache hierarchy before a lane loads further batches of the key of `pos` from memory (heads wider
+    // than one batch); a key that fits one batch is patched whole from LDS below (TAG: the wait then only delayed the barrier)
+    if (!TAG || (mine && HS / 4 > KG)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     if (tc == pos) {                                        // batch 0 was loaded before the new key existed: patch it from LDS
 #pragma unroll
@@ -2528,6 +2555,85 @@ __global__ __launch_bounds__(kBlock) void attention_split_scores_kernel(const At
     score = score / sqrt_hs;
     if constexpr (GEMMA) score = gemma_cap_window(score, wpos, t);
     if (t < T) S[(size_t)h * SQ + t] = score;
+}
+
+template <int HS, bool GEMMA>
+__global__ __launch_bounds__(kBlock) void attention_split_scores_kernel(const AttnArgs a, float* S) {
+    __shared__ __attribute__((aligned(16))) float q[HS];
+    __shared__ __attribute__((aligned(16))) float kn[HS];
+    const int pos = a.st->pos;
+    const int t0 = blockIdx.y * kBlock;
+    if (t0 > pos) return;
+    split_scores_item<HS, GEMMA, false>(a, S, blockIdx.x, t0, pos, q, kn);
+}
+
+// ------------------------------------------------------------------------------------------------
+// qkv projection + the split form's SCORES of one layer in ONE launch (long contexts: five launches per layer instead of six).
+// The first n_gemv workgroups are the unchanged static GEMV body with the EPI_QKV_TAG epilogue (v goes to its cache row, q / raw k / v
+// leave as {value, tag} granules); the workgroups behind them take the (head, 256-key chunk) items of the score launch: they issue the
+// chunk's K loads - which land under the GEMV's weight stream - and then poll q (and, in the chunk of `pos`, the raw key) as the wave
+// forms of qkv_attn_kernel do.  No dependent launch boundary, no q / k_raw round trip through memory.
+// Why it cannot deadlock: score workgroups wait for GEMV workgroups, never the reverse, and a GEMV workgroup waits for nobody.  The GEMV
+// workgroups are FIRST in grid order and the grid is capped at what is resident at once (resident_grid_cap; a score workgroup then walks
+// several items), so every GEMV workgroup holds a slot before or together with the score workgroups; should a placement ever hold one
+// back all the same, every poll is bounded (kTagSpinMax, err): the pollers finish, free their slots and the host rejects the call.
+// ------------------------------------------------------------------------------------------------
+template <int N, int L, int PRO, bool Q4, int HS, bool GEMMA>
+__global__ __launch_bounds__(kBlock) void qkv_scores_kernel(LMRS_HOT_PARAMS, const QkvAttnArgs a0, float* S, const int n_gemv) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    QkvAttnArgs a = a0;                                              // (kernel-argument preload: see gemv_static_kernel)
+    a.g = with_hot(a0.g, h_xin, h_wq, h_ws, h_rms_w, h_st, h_seq, h_out); a.t.st = h_st;
+    if ((int)blockIdx.x < n_gemv) {
+        gemv_static_body<N, L, PRO, EPI_QKV_TAG, kBlock, Q4>(a.g, smem, (int)blockIdx.x, n_gemv);
+        return;
+    }
+    const int pos = a.t.st->pos;
+    const AttTag tg{a.g.gran, *a.g.seq + 1u, a.g.att_dim, a.g.kv_dim, a.err};
+    float* q = reinterpret_cast<float*>(smem);
+    float* kn = q + HS;
+    // item -> (chunk, head): the query heads that share a kv head sit n_kv_heads items apart (on one XCD with 8 or 32 kv heads: its L2 fetches
+    // their keys once, see qkv_attn_kernel); items past the context (the graph's bucket is wider) do not exist
+    const int nh = a.t.n_heads, nkv = a.t.n_kv_heads;
+    const int n_items = nh * (pos / kBlock + 1), n_score = (int)gridDim.x - n_gemv;
+    bool further = false;
+    for (int it = (int)blockIdx.x - n_gemv; it < n_items; it += n_score, further = true) {
+        const int chunk = it / nh, hq = it - chunk * nh, bq = hq / nkv, br = hq - bq * nkv;
+        if (further) lds_barrier();                                 // (a further item of this workgroup: the previous one's lanes are done with q / kn)
+        split_scores_item<HS, GEMMA, true>(a.t, S, br * (nh / nkv) + bq, chunk * kBlock, pos, q, kn, tg);
+    }
+}
+
+template <int N, int L, int PRO, bool Q4, int HS, bool GEMMA>
+static hipError_t launch_qkv_scores_class(const QkvAttnArgs& a, float* S, int n_gemv, int n_score, size_t smem, int max_score_wgs, hipStream_t s) {
+    const void* fn = reinterpret_cast<const void*>(qkv_scores_kernel<N, L, PRO, Q4, HS, GEMMA>);
+    if (smem > 64 * 1024) allow_big_lds(fn);
+    // one round of workgroups: the GEMV part keeps its grid where it can (surplus passes become second passes, as in launch_qkv_attn_class), the
+    // score part gets at least one workgroup per head and at most a quarter of the slots when the launch does not fit
+    const int cap = resident_grid_cap(fn, smem);
+    if (cap > a.t.n_heads + 64 && n_gemv + n_score > cap) {
+        const int floor_wgs = a.t.n_heads > cap / 4 ? a.t.n_heads : cap / 4;
+        if (n_score > floor_wgs) n_score = cap - n_gemv > floor_wgs ? cap - n_gemv : floor_wgs;
+        if (n_gemv + n_score > cap) n_gemv = cap - n_score;
+    }
+    if (max_score_wgs > 0 && n_score > max_score_wgs) n_score = max_score_wgs;
+    LMRS_LAUNCH_GRID((qkv_scores_kernel<N, L, PRO, Q4, HS, GEMMA>), dim3(n_gemv + n_score), kBlock, smem, s, LMRS_HOT_OF(a.g), a, S, n_gemv);
+    return hipGetLastError();
+}
+
+hipError_t launch_qkv_scores(const GemvArgs& g0, int pro, const AttnArgs& t0, float* S, int* err, int n_key_chunks, int max_score_wgs, hipStream_t s) {
+    if (!qkv_attn_supported(g0, pro, t0) || !g0.gran || !g0.seq || !err || !S || n_key_chunks <= 0) return hipErrorNotSupported;
+    QkvAttnArgs a{g0, t0, err};
+    a.g.order_barrier = a.g.chain_spread = 1;
+    const StaticClass sc = static_class(a.g, pro, EPI_QKV);
+    const int n_gemv = gemv_grid(a.g, pro, EPI_QKV);
+    size_t smem = gemv_smem(a.g, pro);
+    if (smem < (size_t)2 * t0.head_size * 4) smem = (size_t)2 * t0.head_size * 4;
+#define X(n_, l_, p_, q_, hs_, gm_)                                                                                      \
+    if (a.g.n == n_ && sc.L == l_ && pro == p_ && (a.g.q4 != 0) == q_ && t0.head_size == hs_ && (t0.gemma != 0) == gm_)  \
+        return launch_qkv_scores_class<n_, l_, p_, q_, hs_, gm_>(a, S, n_gemv, t0.n_heads * n_key_chunks, smem, max_score_wgs, s);
+    LMRS_QA_TABLE(X)
+#undef X
+    return hipErrorNotSupported;
 }
 
 // Round 6: the value phase as a PIPELINE with specialised waves.  Waves 1-3 load a chunk of 256 value rows (the workgroup's slice of the head
@@ -2672,19 +2778,31 @@ __global__ __launch_bounds__(kBlock) void attention_split_values_kernel(const At
 size_t attention_split_scratch_floats(int n_heads, int seq_len) { return (size_t)n_heads * seq_len; }
 
 template <int HS, bool GEMMA>
-static hipError_t launch_attention_split_hsg(const AttnArgs& a0, float* S, int n_key_chunks, hipStream_t s) {
+static hipError_t launch_split_values_hsg(const AttnArgs& a0, const float* S, hipStream_t s) {
     AttnArgs a = a0;
     using G = SplitGeom<HS>;
     a.chunk = G::CHK;
     const size_t smem = (size_t)(16 + 2 * G::HP * G::PITCH + ((a.seq_len + 3) & ~3) + 128) * 4;
     allow_big_lds(reinterpret_cast<const void*>(attention_split_values_kernel<HS, GEMMA>));
-    LMRS_LAUNCH_GRID((attention_split_scores_kernel<HS, GEMMA>), dim3(a.n_heads, n_key_chunks), kBlock, 0, s, a, S);
-    LMRS_LAUNCH_GRID((attention_split_values_kernel<HS, GEMMA>), dim3(a.n_heads, G::NSL), kBlock, smem, s, a, (const float*)S);
+    LMRS_LAUNCH_GRID((attention_split_values_kernel<HS, GEMMA>), dim3(a.n_heads, G::NSL), kBlock, smem, s, a, S);
     return hipGetLastError();
+}
+template <int HS, bool GEMMA>
+static hipError_t launch_attention_split_hsg(const AttnArgs& a0, float* S, int n_key_chunks, hipStream_t s) {
+    AttnArgs a = a0;
+    a.chunk = SplitGeom<HS>::CHK;
+    LMRS_LAUNCH_GRID((attention_split_scores_kernel<HS, GEMMA>), dim3(a.n_heads, n_key_chunks), kBlock, 0, s, a, S);
+    return launch_split_values_hsg<HS, GEMMA>(a0, S, s);
 }
 // n_key_chunks: 256-key chunks covering the longest context this launch (graph) will see
 hipError_t launch_attention_split(const AttnArgs& a, float* S, int n_key_chunks, hipStream_t s) {
 #define AS(HS_) return a.gemma ? launch_attention_split_hsg<HS_, true>(a, S, n_key_chunks, s) : launch_attention_split_hsg<HS_, false>(a, S, n_key_chunks, s);
+    switch (a.head_size) { case 64: AS(64) case 96: AS(96) case 128: AS(128) case 256: AS(256) default: return hipErrorInvalidValue; }
+#undef AS
+}
+// the value launch alone: the scores came with the qkv launch (launch_qkv_scores)
+hipError_t launch_attention_split_values(const AttnArgs& a, const float* S, hipStream_t s) {
+#define AS(HS_) return a.gemma ? launch_split_values_hsg<HS_, true>(a, S, s) : launch_split_values_hsg<HS_, false>(a, S, s);
     switch (a.head_size) { case 64: AS(64) case 96: AS(96) case 128: AS(128) case 256: AS(256) default: return hipErrorInvalidValue; }
 #undef AS
 }

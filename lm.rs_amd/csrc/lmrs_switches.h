@@ -23,6 +23,8 @@ struct Switches {
     int qkv_att = -1;                    // LMRS_QKV_ATT: -1 unset; 0 no merged qkv + attention launch; 1 its workgroup form only
     bool cls_tail = true;                // LMRS_CLS_TAIL=0: the final argmax as a launch of its own
     int att_split_pos = 384; bool att_split_pos_set = false;   // LMRS_ATT_SPLIT_POS: split attention from this position (0: never); set: used by stamped contexts too
+    bool att_split_merged = true;        // LMRS_ATT_SPLIT_MERGED=0: the split form as six launches per layer (plain qkv, scores, values) - the A/B switch of the merged qkv + scores launch
+    int att_split_score_wgs = 0;         // LMRS_ATT_SPLIT_SCORE_WGS: at most this many score workgroups in the merged qkv + scores launch (0: as many as are resident; tests lower it)
     int att_lds_keys = kAttLdsKeys;      // LMRS_ATT_LDS_KEYS (tests lower it)
     int steps_per_graph = 4;             // LMRS_STEPS_PER_GRAPH, clamped to 1 .. 64
     size_t topp_sort_min = 4096;         // LMRS_TOPP_DEVICE_SORT_MIN: device sort of top-p candidates from this count (host: 4096 in ~0.25 ms, device ~0.2 ms)
@@ -46,6 +48,8 @@ inline Switches read_switches() {
     if ((e = getenv("LMRS_QKV_ATT"))) s.qkv_att = atoi(e);
     if ((e = getenv("LMRS_CLS_TAIL"))) s.cls_tail = atoi(e) != 0;
     if ((e = getenv("LMRS_ATT_SPLIT_POS"))) { s.att_split_pos = atoi(e); s.att_split_pos_set = true; }
+    if ((e = getenv("LMRS_ATT_SPLIT_MERGED"))) s.att_split_merged = atoi(e) != 0;
+    if ((e = getenv("LMRS_ATT_SPLIT_SCORE_WGS"))) { const int k = atoi(e); s.att_split_score_wgs = k < 0 ? 0 : k; }
     if ((e = getenv("LMRS_ATT_LDS_KEYS"))) s.att_lds_keys = atoi(e);
     if ((e = getenv("LMRS_STEPS_PER_GRAPH"))) { const int k = atoi(e); s.steps_per_graph = k < 1 ? 1 : (k > 64 ? 64 : k); }
     if ((e = getenv("LMRS_TOPP_DEVICE_SORT_MIN"))) s.topp_sort_min = (size_t)atol(e);
