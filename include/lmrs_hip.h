@@ -255,6 +255,36 @@ void lmrs_batch_destroy(lmrs_batch* b);
 int  lmrs_batch_create_wide(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, lmrs_batch** out);
 /* 16 for lmrs_batch_create's batches, 64 for wide ones: the most rows (lmrs_batch_forward, _generate_greedy) and runs (_forward_runs) a call takes. */
 int  lmrs_batch_width(const lmrs_batch* b, uint32_t* width);
+/* ---- paged K/V (extensions, no reference counterpart): a WIDE batch (width 64) whose slots draw pages of page_len positions from ONE pool of n_pages
+ * pages instead of holding a whole cache each.  Same refusals as lmrs_batch_create (each message opens with this call's name); also refused: a
+ * page_len other than 64, 128, 256, 512, 1024, and n_pages == 0.  The allocation is (n_pages + 1) * 2 * n_layers * page_len * kv_dim * 4 bytes, all or
+ * nothing, the message gives the bytes.  The extra page is page 0, the ZERO PAGE: cleared at create, never written; every page-table entry of every
+ * slot starts there, so a position nobody wrote reads as zero, exactly as in a fresh contiguous slot.
+ * Every batch call works on a paged batch as documented for a wide batch, and - for any sequence of calls without lmrs_batch_release - returns what a
+ * lmrs_batch_create_wide batch returns, bit for bit: tokens, logits, top-k, sampled tokens, sampler state, lmrs_batch_debug_kv rows.  Paging changes
+ * addresses only, never the order of a floating-point operation.
+ * Page accounting, decided on the host and finished before any device work of a call.  A call that writes positions [p0, p1) of a slot (a prefill, a
+ * run, a decode row, all n_new steps of lmrs_batch_generate_greedy up front) takes, per page the range touches: a free page, cleared in stream order,
+ * where the entry is 0; a free page with the whole old page copied into it where the entry has more than one holder (copy on write; the old
+ * reference is dropped); nothing where the slot holds the page alone.  A call that needs more free pages than there are fails with a message of its
+ * own - the call's name, pages wanted, pages free - and has changed nothing: batch, context and samplers stay usable.
+ * lmrs_batch_fork(src, dst, n_pos): dst's entries of the pages wholly inside [0, n_pos) become references to src's pages (dst's former pages there are
+ * dropped); the rows of the partial last page are copied into a page dst holds alone; dst's later entries stay.  At most one page copy and a table
+ * edit.  From LMRS_BATCH_CTX (a contiguous cache) the rows are copied into dst's own pages.
+ * The cost: lmrs_batch_prefill and lmrs_batch_prefill_embeddings go through the table pass on a paged batch - one workgroup per (head, row), chunks of
+ * 512 rows - not through the block-attention launches, so a long prompt is slower than on a contiguous batch (512 tokens of Llama-3.2-1B: 5.88 ms
+ * against 2.69 ms); the values are the same bits.  A decode pass of 64 rows costs +2.9 % at 100 positions and +4.7 % at 1000 on Llama-3.2-1B Q8_0 and is
+ * 0.7 % / 5.7 % faster on Gemma-2-2B Q4_0 (profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt). */
+int lmrs_batch_create_paged(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
+                            uint32_t n_pages /* >= 1 */, lmrs_batch** out);
+/* the pool: its page length, its pages (the zero page not counted) and how many of them nobody holds.  Refused on a batch that is not paged. */
+int lmrs_batch_pages(const lmrs_batch* b, uint32_t* page_len, uint32_t* n_pages, uint32_t* n_free);
+/* the pages a slot holds, and how many of them have more than one holder.  Refused on a batch that is not paged, and for a slot >= n_slots. */
+int lmrs_batch_slot_pages(const lmrs_batch* b, uint32_t slot, uint32_t* n_held, uint32_t* n_shared);
+/* keep positions [0, n_pos) of a slot (0 empties it): the slot's references to the pages at index ceil(n_pos / page_len) and above are dropped, those
+ * entries return to the zero page, and a page nobody holds is free.  Refused, each with its own message: a batch that is not paged, a slot >=
+ * n_slots, n_pos > seq_len. */
+int lmrs_batch_release(lmrs_batch* b, uint32_t slot, uint32_t n_pos);
 
 /* == lmrs_prefill_tokens, into slot's cache: rows start_pos .. start_pos+n-1 as n forward calls leave them */
 int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n, uint32_t start_pos);

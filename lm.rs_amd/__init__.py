@@ -32,6 +32,7 @@ EXPORTS = [
     "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
     "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
+    "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -109,6 +110,10 @@ def lib():
         L.lmrs_batch_create.argtypes = [vp, u32, C.POINTER(vp)]
         L.lmrs_batch_create_wide.argtypes = [vp, u32, C.POINTER(vp)]
         L.lmrs_batch_width.argtypes = [vp, C.POINTER(u32)]
+        L.lmrs_batch_create_paged.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
+        L.lmrs_batch_pages.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+        L.lmrs_batch_slot_pages.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.lmrs_batch_release.argtypes = [vp, u32, u32]
         L.lmrs_batch_destroy.argtypes = [vp]; L.lmrs_batch_destroy.restype = None
         L.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
         L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
@@ -396,12 +401,36 @@ class Batch:
     DIFFERENT sequences, each at its own position (lmrs_batch_*).  Every result is bit for bit what forward / forward_argmax give on a model that
     holds only that sequence.  The model's own cache is untouched by every call here; close the batch before the model.
     wide=True: up to 64 slots, and forward / generate_greedy / forward_runs / forward_runs_sample take up to 64 rows or runs a call
-    (lmrs_batch_create_wide; forward_sample keeps 16 rows)."""
+    (lmrs_batch_create_wide; forward_sample keeps 16 rows).
+    page_len= and n_pages= (both or neither; wide= is then ignored): a PAGED batch, wide, whose slots draw pages of page_len positions (64, 128, 256,
+    512 or 1024) from one pool of n_pages pages instead of holding a whole cache each: fork shares whole pages, a write un-shares the page it
+    touches, release gives pages back.  Without release every result is bit for bit a wide batch's (lmrs_batch_create_paged)."""
 
-    def __init__(self, model: Transformer, n_slots: int, wide: bool = False):
+    def __init__(self, model: Transformer, n_slots: int, wide: bool = False, *, page_len=None, n_pages=None):
         h = C.c_void_p()
-        _chk((lib().lmrs_batch_create_wide if wide else lib().lmrs_batch_create)(model._h, n_slots, C.byref(h)))
+        if (page_len is None) != (n_pages is None):
+            raise LmrsError("page_len and n_pages must be given together")
+        if page_len is not None:
+            _chk(lib().lmrs_batch_create_paged(model._h, n_slots, page_len, n_pages, C.byref(h)))
+        else:
+            _chk((lib().lmrs_batch_create_wide if wide else lib().lmrs_batch_create)(model._h, n_slots, C.byref(h)))
         self._h, self.model, self.n_slots = h, model, n_slots
+
+    def pages(self):
+        """A paged batch's pool -> (page_len, n_pages, n_free) (lmrs_batch_pages)"""
+        a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _chk(lib().lmrs_batch_pages(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def slot_pages(self, slot: int):
+        """The pages `slot` holds and how many of them have more than one holder -> (held, shared) (lmrs_batch_slot_pages)"""
+        a, b = C.c_uint32(), C.c_uint32()
+        _chk(lib().lmrs_batch_slot_pages(self._h, slot, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def release(self, slot: int, n_pos: int = 0) -> None:
+        """Keep positions [0, n_pos) of `slot` (0 empties it): the pages behind them go back to the pool once nobody holds them (lmrs_batch_release)"""
+        _chk(lib().lmrs_batch_release(self._h, slot, n_pos))
 
     @property
     def width(self) -> int:

@@ -33,6 +33,7 @@
 #include "lmrs_device_math.h"
 #include "lmrs_format.h"
 #include "lmrs_kernels.h"
+#include "lmrs_pages.h"
 #include "lmrs_score.h"
 #include "lmrs_switches.h"
 
@@ -182,7 +183,7 @@ struct StepForm { int qa_mode = 0, split_chunks = 0; bool split_merged = false; 
 // rows: the base the table's offsets count from); null: the context's own
 // runs (runs.tok != null): the pass is lmrs_batch_forward_runs' - a table of up to kRunRowsMax rows, several of them consecutive positions of one slot; its
 // qkv block is wider than pf_q at that many rows, so the pass brings a buffer of its own (qkv; null: pf_q, as every other pass).
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; };
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1474,7 +1475,12 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
         t.q = qkv; t.k_raw = nullptr; t.k_cache = k_cache; t.v_cache = v_cache; t.rope = c->rope; t.out = c->pf_ao;
         t.n_heads = att / hs; t.n_kv_heads = kv / hs; t.head_size = hs; t.seq_len = (int)a.seq_len; t.layer = (int)l;
         t.gemma = gemma; t.st = c->st;
-        if (form.rows) {
+        if (form.pages.tab) {
+            // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
+            const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
+            HIP_OK(launch_paged_scatter(qkv, k_cache, v_cache, c->rope, rv, form.pages, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
+            HIP_OK(launch_paged_attention(t, rv, form.pages, m, form.max_T, c->stream));
+        } else if (form.rows) {
             // every row at its own position in its own slot: rotation, K / V rows into the slots, one attention workgroup per (head, row)
             HIP_OK(launch_rope_scatter_rows(c->pf_q, k_cache, v_cache, c->rope, form.rows, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
             HIP_OK(launch_attention_table(t, form.rows, m, form.max_T, c->stream));
@@ -2019,7 +2025,7 @@ extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, si
 // (no reference counterpart: per row Transformer::forward + sample_argmax on a cache of its own, value for value).  A batch is n_slots more K/V
 // caches of the context's layout; a step is run_tokens' batched arm, skinny, with a row table (PassForm::rows) - the qkv rows stay in scratch, one
 // launch rotates them and scatters K / V into the rows' slots, and attention_rows_kernel's workgroups take slot and position from the table.
-static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out);   // (with lmrs_debug_kv below)
+static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out, uint32_t page_len = 0);   // (with lmrs_debug_kv below)
 // the ragged pass's table (lmrs_batch_forward_runs): RowTable's columns for kRunRowsMax rows, and sel - the table rows whose outputs were asked for, in output order
 constexpr uint32_t kWideBatchMax = 64;         // a wide batch's slots, rows and runs
 struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
@@ -2041,7 +2047,20 @@ struct lmrs_batch {
     unsigned long long *rs_out = nullptr, *h_rs_heads = nullptr; size_t rs_rows = 0, rs_head_words = 0;
     unsigned long long *cs_keys = nullptr, *h_cs_pairs = nullptr; size_t cs_words = 0;
     float* embed_stage = nullptr;                       // the embedding rows of a ragged pass, [kRunRowsMax][dim] in caller order (allocated at the first call that has one)
+    // a paged batch (lmrs_batch_create_paged): kv is the pool - page p's K block at kv + p * 2 * page_floats, its V block page_floats behind, page 0 the zero
+    // page; the accounting (lmrs_pages.h), the device page table [n_slots][per_slot] and its pinned mirror
+    PagePool* pool = nullptr; uint32_t page_len = 0; size_t page_floats = 0;
+    uint32_t *ptab = nullptr, *h_ptab = nullptr;
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
+    // the `off` word of a row of `slot`: where its caches start, in floats - on a paged batch its row of the page table
+    unsigned long long off_of(uint32_t slot) const { return pool ? slot : (unsigned long long)slot * 2 * slot_floats; }
+    PageView page_view() const {
+        if (!pool) return PageView{};
+        int sh = 0; while ((1u << sh) < page_len) ++sh;
+        return PageView{ptab, (int)pool->per_slot(), sh, 2 * page_floats};
+    }
+    float* page_k(uint32_t page) const { return kv + (size_t)page * 2 * page_floats; }
+    float* page_v(uint32_t page) const { return kv + (size_t)page * 2 * page_floats + page_floats; }
     float* k_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->k_cache : kv + (size_t)slot * 2 * slot_floats; }
     float* v_of(uint32_t slot) const { return slot == LMRS_BATCH_CTX ? c->v_cache : kv + (size_t)slot * 2 * slot_floats + slot_floats; }
 };
@@ -2050,6 +2069,9 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->c->device);
     (void)hipStreamSynchronize(b->c->stream);
+    if (b->ptab) (void)hipFree(b->ptab);
+    if (b->h_ptab) (void)hipHostFree(b->h_ptab);
+    delete b->pool;
     for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x, (void*)b->samp_tab, (void*)b->samp_scratch, (void*)b->samp_out}) if (p) (void)hipFree(p);
     for (void* p : {(void*)b->rs_tab, (void*)b->rs_scratch, (void*)b->rs_out, (void*)b->cs_keys, (void*)b->embed_stage}) if (p) (void)hipFree(p);
     for (void* p : {(void*)b->h_rs_tab, (void*)b->h_rs_heads, (void*)b->h_cs_pairs}) if (p) (void)hipHostFree(p);
@@ -2062,7 +2084,8 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
 }
 
 // lmrs_batch_create / lmrs_batch_create_wide: `name` opens every message, width is the batch's row and slot limit
-static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width) {
+// page_len > 0 (lmrs_batch_create_paged): the slots draw pages of page_len positions from one pool of n_pages pages (+ the zero page) instead of a cache each
+static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width, uint32_t page_len = 0, uint32_t n_pages = 0) {
     if (!c || !out) return fail("NULL argument");
     *out = nullptr;
     if (n_slots < 1 || n_slots > width) return fail(name + ": n_slots = " + std::to_string(n_slots) + " is outside 1 .. " + std::to_string(width));
@@ -2080,9 +2103,22 @@ static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const s
     if (c->sc_rows < kRowTableMax) return fail(name + ": the logits block holds fewer than " + std::to_string(kRowTableMax) + " rows of this vocabulary");
     lmrs_batch* b = new lmrs_batch;
     b->c = c; b->n_slots = n_slots; b->width = width; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
-    const size_t bytes = (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
+    b->page_len = page_len; b->page_floats = (size_t)a.n_layers * page_len * c->kv_dim;
+    const size_t bytes = page_len ? ((size_t)n_pages + 1) * 2 * b->page_floats * 4 : (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
     bool ok = hipMalloc(reinterpret_cast<void**>(&b->kv), bytes) == hipSuccess;                         // all or nothing: one allocation
-    if (!ok) { (void)hipGetLastError(); b->kv = nullptr; lmrs_batch_destroy(b); return fail(name + ": " + std::to_string(bytes) + " bytes of K/V caches for " + std::to_string(n_slots) + " slots: out of memory"); }
+    if (!ok) {
+        (void)hipGetLastError(); b->kv = nullptr; lmrs_batch_destroy(b);
+        if (page_len) return fail(name + ": " + std::to_string(bytes) + " bytes of K/V pages for " + std::to_string(n_pages) + " pages (and the zero page): out of memory");
+        return fail(name + ": " + std::to_string(bytes) + " bytes of K/V caches for " + std::to_string(n_slots) + " slots: out of memory");
+    }
+    if (page_len) {
+        const uint32_t per_slot = (a.seq_len + page_len - 1) / page_len;
+        b->pool = new PagePool(n_slots, per_slot, page_len, n_pages);
+        ok = hipMalloc(reinterpret_cast<void**>(&b->ptab), (size_t)n_slots * per_slot * 4) == hipSuccess;
+        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_ptab), (size_t)n_slots * per_slot * 4, hipHostMallocDefault) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": page table: out of memory"); }
+        memset(b->h_ptab, 0, (size_t)n_slots * per_slot * 4);
+    }
     ok = hipMalloc(reinterpret_cast<void**>(&b->tab), sizeof(RowTable)) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->tokens), T * 4) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->out), T * width * 4) == hipSuccess;
@@ -2093,7 +2129,9 @@ static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const s
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_qkv), (size_t)kRunRowsMax * (c->att_dim + 2 * c->kv_dim) * 4) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_x), (size_t)kRunRowsMax * a.dim * 4) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": row table and result buffers: out of memory"); }
-    if (hipMemsetAsync(b->kv, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail(name + ": clearing the caches failed"); }
+    // (a paged batch: the zero page and the table - every entry names the zero page; a page is cleared when it is claimed)
+    if (page_len && hipMemsetAsync(b->ptab, 0, (size_t)n_slots * b->pool->per_slot() * 4, c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail(name + ": clearing the page table failed"); }
+    if (hipMemsetAsync(b->kv, 0, page_len ? 2 * b->page_floats * 4 : bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail(name + ": clearing the caches failed"); }
     *out = b;
     return 0;
 }
@@ -2112,11 +2150,91 @@ static int batch_failed(lmrs_ctx* c) { (void)hipStreamSynchronize(c->stream); c-
 // the one DevState of a batch call (only Gemma's kernels read it: every row tests the window against its own position)
 static int batch_state(lmrs_ctx* c) { return set_state(c, 0, 0, pass_win_base(c, 0, true)); }
 
+// ------------------------------------------------------------------ paged batches: the slots draw pages from one pool (extensions, no reference counterpart)
+// The accounting is lmrs_pages.cpp's, decided on the host and finished before any device work of the call; what it asks of the device - clear a
+// claimed page, copy a page that is being un-shared, the table rows that changed - is enqueued here, in stream order ahead of the pass.
+extern "C" int lmrs_batch_create_paged(lmrs_ctx* c, uint32_t n_slots, uint32_t page_len, uint32_t n_pages, lmrs_batch** out) {
+    const std::string name = "lmrs_batch_create_paged";
+    if (out) *out = nullptr;
+    if (page_len != 64 && page_len != 128 && page_len != 256 && page_len != 512 && page_len != 1024)
+        return fail(name + ": page_len = " + std::to_string(page_len) + " is none of 64, 128, 256, 512, 1024");
+    if (n_pages == 0) return fail(name + ": n_pages is 0");
+    return batch_create(c, n_slots, out, name, kWideBatchMax, page_len, n_pages);
+}
+extern "C" int lmrs_batch_pages(const lmrs_batch* b, uint32_t* page_len, uint32_t* n_pages, uint32_t* n_free) {
+    if (!b || !page_len || !n_pages || !n_free) return fail("lmrs_batch_pages: NULL argument");
+    if (!b->pool) return fail("lmrs_batch_pages: not a paged batch (lmrs_batch_create_paged)");
+    *page_len = b->page_len; *n_pages = b->pool->n_pages(); *n_free = b->pool->n_free();
+    return 0;
+}
+extern "C" int lmrs_batch_slot_pages(const lmrs_batch* b, uint32_t slot, uint32_t* n_held, uint32_t* n_shared) {
+    if (!b || !n_held || !n_shared) return fail("lmrs_batch_slot_pages: NULL argument");
+    if (!b->pool) return fail("lmrs_batch_slot_pages: not a paged batch (lmrs_batch_create_paged)");
+    if (slot >= b->n_slots) return fail("lmrs_batch_slot_pages: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    b->pool->slot_pages(slot, n_held, n_shared);
+    return 0;
+}
+// the table rows of `dirty` slots: pinned mirror, then the device table (stream order; every batch call drains the stream before it returns, so the
+// mirror is never rewritten under a copy in flight)
+static int pages_upload(lmrs_batch* b, const std::vector<uint32_t>& dirty) {
+    const size_t per = b->pool->per_slot();
+    for (uint32_t s : dirty) {
+        memcpy(b->h_ptab + s * per, b->pool->row(s), per * 4);
+        HIP_OK(hipMemcpyAsync(b->ptab + s * per, b->h_ptab + s * per, per * 4, hipMemcpyHostToDevice, b->c->stream));
+    }
+    return 0;
+}
+static int pages_enqueue(lmrs_batch* b, const std::vector<PageAction>& acts, const std::vector<uint32_t>& dirty) {
+    const size_t bytes = 2 * b->page_floats * 4;
+    for (const PageAction& a : acts) {
+        if (a.dst == 0 || a.dst > b->pool->n_pages() || a.src > b->pool->n_pages()) return fail("page accounting: an action outside the pool");
+        if (a.kind == PageAction::kClear) HIP_OK(hipMemsetAsync(b->page_k(a.dst), 0, bytes, b->c->stream));
+        else HIP_OK(hipMemcpyAsync(b->page_k(a.dst), b->page_k(a.src), bytes, hipMemcpyDeviceToDevice, b->c->stream));
+    }
+    return pages_upload(b, dirty);
+}
+// A call that writes the given ranges of a paged batch (no-op on any other): plan, commit, enqueue.  Short of pages the call fails here with nothing
+// changed: `what` opens the message ("name: "), which gives the pages wanted and the pages free.
+static int pages_claim(lmrs_batch* b, const std::string& what, const PageRange* ranges, size_t n) {
+    if (!b->pool) return 0;
+    std::vector<PageAction> acts; std::vector<uint32_t> dirty; uint32_t wanted = 0;
+    if (!b->pool->write(ranges, n, &acts, &dirty, &wanted))
+        return fail(what + std::to_string(wanted) + " pages wanted, " + std::to_string(b->pool->n_free()) + " free (the pool holds " + std::to_string(b->pool->n_pages()) + ")");
+    if (acts.empty() && dirty.empty()) return 0;
+    HIP_OK(hipSetDevice(b->c->device));
+    if (pages_enqueue(b, acts, dirty)) return batch_failed(b->c);
+    return 0;
+}
+// (the rows of a step: row i writes positions [pos[i], pos[i] + span) of slot[i]; the runs of a ragged pass)
+static int pages_claim_rows(lmrs_batch* b, const std::string& what, uint32_t n, const uint32_t* slot, const uint32_t* pos, const uint32_t* len, uint32_t span) {
+    if (!b->pool) return 0;
+    std::vector<PageRange> r(n);
+    for (uint32_t i = 0; i < n; ++i) r[i] = PageRange{slot[i], pos[i], pos[i] + (len ? len[i] : span)};
+    return pages_claim(b, what, r.data(), n);
+}
+extern "C" int lmrs_batch_release(lmrs_batch* b, uint32_t slot, uint32_t n_pos) {
+    if (!b) return fail("lmrs_batch_release: NULL argument");
+    if (!b->pool) return fail("lmrs_batch_release: not a paged batch (lmrs_batch_create_paged)");
+    if (slot >= b->n_slots) return fail("lmrs_batch_release: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if (n_pos > b->c->args.seq_len) return fail("lmrs_batch_release: n_pos = " + std::to_string(n_pos) + " exceeds seq_len");
+    std::vector<uint32_t> dirty;
+    b->pool->release(slot, n_pos, &dirty);
+    if (dirty.empty()) return 0;
+    HIP_OK(hipSetDevice(b->c->device));
+    if (pages_upload(b, dirty)) return batch_failed(b->c);
+    HIP_OK(hipStreamSynchronize(b->c->stream));
+    return 0;
+}
+// lmrs_batch_prefill and lmrs_batch_prefill_embeddings on a paged batch: the table pass, one run per chunk of at most kRunRowsMax rows (defined
+// with the ragged pass below)
+static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, const uint32_t* tokens, const float* embeddings, size_t n, uint32_t start_pos, float* residual);
+
 extern "C" int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n, uint32_t start_pos) {
     if (!b) return fail("NULL argument");
     lmrs_ctx* c = b->c;
     if (check_tokens(c, tokens, n, start_pos, n)) return -1;
     if (slot >= b->n_slots) return fail("lmrs_batch_prefill: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if (b->pool) return n ? paged_prefill("lmrs_batch_prefill: ", b, slot, tokens, nullptr, n, start_pos, nullptr) : 0;
     if (n == 1) {                                        // one token: lmrs_batch_forward's pass with nobody reading its result
         uint32_t am = 0;
         return lmrs_batch_forward(b, 1, &slot, tokens, &start_pos, &am, nullptr);
@@ -2144,6 +2262,32 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
     if (n_pos == 0) return 0;
     HIP_OK(hipSetDevice(c->device));
     const size_t S = a.seq_len, kv = (size_t)c->kv_dim;
+    if (b->pool) {
+        // a paged batch: the whole pages become references, at most one page is copied; rows [r0, r1) of a page's K / V blocks from `ks` / `vs`, whose rows
+        // lie ss positions apart (another page: page_len; the context's cache: seq_len)
+        const size_t PL = b->page_len;
+        auto copy_rows = [&](uint32_t page, size_t r0, size_t r1, const float* ks, const float* vs, size_t ss) -> int {
+            HIP_OK(hipMemcpy2DAsync(b->page_k(page) + r0 * 4, PL * 16, ks, ss * 16, (r1 - r0) * 16, (size_t)a.n_layers * kv / 4, hipMemcpyDeviceToDevice, c->stream));
+            HIP_OK(hipMemcpy2DAsync(b->page_v(page) + r0 * kv, PL * kv * 4, vs, ss * kv * 4, (r1 - r0) * kv * 4, a.n_layers, hipMemcpyDeviceToDevice, c->stream));
+            return 0;
+        };
+        if (src_slot == LMRS_BATCH_CTX) {                // a contiguous source: its rows are copied into pages dst holds alone
+            const PageRange all{dst_slot, 0, n_pos};
+            if (pages_claim(b, "lmrs_batch_fork: ", &all, 1)) return -1;
+            for (size_t p0 = 0; p0 < n_pos; p0 += PL) {
+                const size_t p1 = std::min<size_t>(n_pos, p0 + PL);
+                if (copy_rows(b->pool->row(dst_slot)[p0 / PL], 0, p1 - p0, c->k_cache + p0 * 4, c->v_cache + p0 * kv, S)) return batch_failed(c);
+            }
+        } else {
+            std::vector<PageAction> acts; std::vector<uint32_t> dirty; uint32_t wanted = 0, part_p0 = 0, part_src = 0, part_dst = 0;
+            if (!b->pool->fork(src_slot, dst_slot, n_pos, &acts, &dirty, &wanted, &part_p0, &part_src, &part_dst))
+                return fail("lmrs_batch_fork: " + std::to_string(wanted) + " pages wanted, " + std::to_string(b->pool->n_free()) + " free (the pool holds " + std::to_string(b->pool->n_pages()) + ")");
+            if (pages_enqueue(b, acts, dirty)) return batch_failed(c);
+            if (part_dst && copy_rows(part_dst, 0, n_pos - part_p0, b->page_k(part_src), b->page_v(part_src), PL)) return batch_failed(c);
+        }
+        HIP_OK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
     // K: [layer][kv head][head / 4] pieces of S x 4 floats, the first n_pos x 4 of each; V: [layer] pieces of S x kv floats, the first n_pos x kv
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpy2DAsync(b->k_of(dst_slot), S * 16, b->k_of(src_slot), S * 16, (size_t)n_pos * 16, (size_t)a.n_layers * kv / 4, hipMemcpyDeviceToDevice, c->stream));
@@ -2175,7 +2319,7 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
     RunTable* h = b->h_runs;
     for (size_t r = 0; r < R; ++r) {
         const int j = order[r];
-        h->off[r] = (unsigned long long)slot[rows[j].run] * 2 * b->slot_floats; h->pos[r] = (int)rows[j].pos; h->tok[r] = rows[j].word;
+        h->off[r] = b->off_of(slot[rows[j].run]); h->pos[r] = (int)rows[j].pos; h->tok[r] = rows[j].word;
         at[j] = (int)r;
     }
     size_t o = 0;
@@ -2223,7 +2367,7 @@ static int source_rows(lmrs_ctx* c, const uint32_t* src, const float* staged, in
 static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to, const float* staged = nullptr) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
-    form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
+    form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view();
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
@@ -2252,7 +2396,7 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
     std::stable_sort(order, order + n, [&](int x, int y) { return pos[x] > pos[y]; });
     for (uint32_t r = 0; r < n; ++r) {
         const int i = order[r];
-        b->h_tab->off[r] = (unsigned long long)slot[i] * 2 * b->slot_floats; b->h_tab->pos[r] = (int)pos[i]; b->h_tab->tok[r] = tokens[i];
+        b->h_tab->off[r] = b->off_of(slot[i]); b->h_tab->pos[r] = (int)pos[i]; b->h_tab->tok[r] = tokens[i];
     }
     return 0;
 }
@@ -2260,6 +2404,7 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
 static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logits) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
+    if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); }
     RowSink to{0, n, out_logits, 0}; to.targets = false;
     return run_tokens(c, to, form, /*batched=*/true);
 }
@@ -2269,6 +2414,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
     lmrs_ctx* c = b->c;
     int order[kRowTableMax];
     if (batch_rows(b, "lmrs_batch_forward", b->width, n, slot, tokens, pos, 1, order)) return -1;
+    if (pages_claim_rows(b, "lmrs_batch_forward: ", n, slot, pos, nullptr, 1)) return -1;
     HIP_OK(hipSetDevice(c->device));
     const size_t V = c->args.vocab_size;
     if (n > (uint32_t)kRowTableMax) {                    // a wide step: the long table, outputs in the caller's order straight to their places
@@ -2311,6 +2457,7 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     int order[kRowTableMax];
     if (batch_rows(b, "lmrs_batch_generate_greedy", b->width, n, slot, tokens, pos, n_new ? n_new : 1, order)) return -1;
     if (!n_new) return 0;
+    if (pages_claim_rows(b, "lmrs_batch_generate_greedy: ", n, slot, pos, nullptr, n_new)) return -1;     // all n_new steps up front: the device loop crosses page edges alone
     HIP_OK(hipSetDevice(c->device));
     const bool wide = n > (uint32_t)kRowTableMax;        // the long table: results in the caller's row order
     auto enqueue = [&]() -> int {
@@ -2394,6 +2541,7 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
     if (sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
     HIP_OK(hipSetDevice(c->device));
     if (sampled && batch_sample_alloc(b)) return -1;
+    if (pages_claim_rows(b, what, n, slot, pos, nullptr, 1)) return -1;
     for (uint32_t r = 0; r < n; ++r) { at[order[r]] = (int)r; if (sampled) b->h_samp_tab[r] = par[order[r]]; }
     const size_t head = b->head_words;
     auto enqueue = [&]() -> int {
@@ -2501,6 +2649,7 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     HIP_OK(hipSetDevice(c->device));
     if (k && O && topk_alloc(c, c->sc_rows, (int)k)) return -1;
     if (E && embed_stage_alloc(b, what)) return -1;
+    if (pages_claim_rows(b, what, n_runs, slot, start_pos, run_len, 0)) return -1;
     const HostScores hs = host_scores(c);
     const size_t nk = O * k;
     auto enqueue = [&]() -> int {
@@ -2521,6 +2670,36 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     if (finish_call(c)) return -1;
     if (O) memcpy(argmax, hs.idx, O * 4);
     if (O && k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
+    return 0;
+}
+static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, const uint32_t* tokens, const float* embeddings, size_t n, uint32_t start_pos, float* residual) {
+    lmrs_ctx* c = b->c;
+    const size_t dim = c->args.dim;
+    HIP_OK(hipSetDevice(c->device));
+    if (embeddings && embed_stage_alloc(b, what)) return -1;
+    const PageRange all{slot, start_pos, start_pos + (uint32_t)n};
+    if (pages_claim(b, what, &all, 1)) return -1;        // every chunk's pages up front: short of pages the call changes nothing
+    // Gemma-2's window, as the contiguous calls set it: per row for tokens (batch_state), the call's first position for every row of embeddings
+    const int win = embeddings ? pass_win_base(c, start_pos, false) : pass_win_base(c, 0, true);
+    const uint32_t kind = embeddings ? 1u : 0u;
+    for (size_t i0 = 0; i0 < n; i0 += kRunRowsMax) {
+        const uint32_t m = (uint32_t)std::min<size_t>(kRunRowsMax, n - i0), p0 = start_pos + (uint32_t)i0, n_out = residual ? m : 0u;
+        size_t R = 0, O = 0;
+        runs_table(b, 1, &slot, &p0, &m, &n_out, RunRows{&kind, tokens ? tokens + i0 : nullptr, embeddings}, &R, &O);
+        auto enqueue = [&]() -> int {
+            if (embeddings) HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+            if (set_state(c, embeddings ? start_pos : 0, 0, win)) return -1;
+            if (runs_pass(b, m, 0, 0, RowSink{0, 0, nullptr, 0}, embeddings ? b->embed_stage : nullptr)) return -1;
+            if (residual) {                              // the table's rows are deepest first: sel puts them back in position order
+                HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)dim, (int)m, c->stream));
+                HIP_OK(hipMemcpyAsync(residual + i0 * dim, b->runs_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));
+            }
+            return 0;
+        };
+        if (enqueue()) return batch_failed(c);
+        if (finish_call(c)) return -1;                   // (the pinned table is rewritten for the next chunk)
+    }
     return 0;
 }
 extern "C" int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* run_len,
@@ -2621,6 +2800,7 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
     HIP_OK(hipSetDevice(c->device));
     if (sampled && runs_sample_alloc(b, O)) return -1;
     if (E && embed_stage_alloc(b, what)) return -1;
+    if (pages_claim_rows(b, what, n_runs, slot, start_pos, run_len, 0)) return -1;
     for (uint32_t i = 0; i < n_runs; ++i) { next[i] = 0; if (sampled && out_of[i] >= 0) b->h_rs_tab[out_of[i]] = par[i]; }
     const size_t head = b->rs_head_words;
     const HostScores hs = host_scores(c);
@@ -2706,6 +2886,7 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
     if (!embeddings) return fail(what + "NULL argument (embeddings)");
     if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
     if ((size_t)start_pos + n > a.seq_len) return fail(what + "start_pos + n = " + std::to_string((size_t)start_pos + n) + " exceeds seq_len = " + std::to_string(a.seq_len));
+    if (b->pool) return paged_prefill(what, b, slot, nullptr, embeddings, n, start_pos, residual);
     HIP_OK(hipSetDevice(c->device));
     const size_t dim = a.dim;
     const int win = pass_win_base(c, start_pos, false);
@@ -2745,6 +2926,11 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
 extern "C" int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out) {
     if (!b || !out) return fail("NULL argument");
     if (slot >= b->n_slots) return fail("lmrs_batch_debug_kv: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if (b->pool) {                                       // the row's page (the zero page where nothing was claimed), at its in-page position
+        if (pos >= b->c->args.seq_len) return fail("bad layer / position");
+        const uint32_t page = b->pool->row(slot)[pos / b->page_len];
+        return debug_kv_row(b->c, b->page_k(page), b->page_v(page), which, layer, pos % b->page_len, out, b->page_len);
+    }
     return debug_kv_row(b->c, b->k_of(slot), b->v_of(slot), which, layer, pos, out);
 }
 
@@ -2880,11 +3066,12 @@ extern "C" int lmrs_debug_timeline(lmrs_ctx* c, unsigned long long* out, int max
 // Verification aid (no reference counterpart): one row of the KV cache in the reference's layout (transformer.rs:302-303, 413:
 // kv_dim floats of layer `layer`, position `pos`).  V is stored that way; K is stored blocked for the score lanes
 // ([kv head][head/4][seq_len][4], see attention_body) and is gathered back here.
-static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out) {
-    if (which < 0 || which > 1 || layer >= c->args.n_layers || pos >= c->args.seq_len) return fail("bad layer / position");
+// (page_len > 0: the caches are ONE page of a paged batch - the same layout with page_len in the place of seq_len, pos the in-page position)
+static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out, uint32_t page_len) {
+    if (which < 0 || which > 1 || layer >= c->args.n_layers || pos >= (page_len ? page_len : c->args.seq_len)) return fail("bad layer / position");
     HIP_OK(hipSetDevice(c->device));
     HIP_OK(hipStreamSynchronize(c->stream));
-    const size_t S = c->args.seq_len, hs = c->args.head_size, kv = (size_t)c->kv_dim, nkv = kv / hs;
+    const size_t S = page_len ? page_len : c->args.seq_len, hs = c->args.head_size, kv = (size_t)c->kv_dim, nkv = kv / hs;
     if (which == 1) { HIP_OK(hipMemcpy(out, v_cache + ((size_t)layer * S + pos) * kv, kv * 4, hipMemcpyDeviceToHost)); return 0; }
     const float* kl = k_cache + (size_t)layer * nkv * hs * S;
     for (size_t h = 0; h < nkv; ++h)

@@ -270,6 +270,14 @@ hipError_t launch_select_rows(const float* src, const uint32_t* sel, float* dst,
 // A ragged pass with embedding runs (source_rows_kernel, lmrs_api.hip): the `tok` column carries a source word per row - a token id (< 2^31: vocab_size is
 // far below), or kRowFromStage | s for row s of the staged block of embedding rows
 constexpr uint32_t kRowFromStage = 0x80000000u;
+// ---- the table passes over PAGED K/V (lmrs_batch_create_paged; lmrs_paged.inc).  tab: the device page table, [slot][per_slot] page numbers of a pool whose
+// pages lie page_stride floats apart (k_pool / v_pool: the K and the V block of page 0); a page has the slot layout with page_len = 1 << shift in the
+// place of seq_len.  The rows' `off` word carries the slot's table row, not a float offset.
+struct PageView { const uint32_t* tab; int per_slot; int shift; size_t page_stride; };
+// launch_rope_scatter_runs / launch_attention_runs with every K / V address looked up in the table: the same operations in the same order per value
+hipError_t launch_paged_scatter(float* qkv, float* k_pool, float* v_pool, const float* rope, RowView rows, PageView pv, int n_heads, int n_kv_heads, int hs,
+                                int layer, int n_rows, hipStream_t s);
+hipError_t launch_paged_attention(const AttnArgs& a, RowView rows, PageView pv, int n_rows, int max_T, hipStream_t s);
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

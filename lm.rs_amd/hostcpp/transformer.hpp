@@ -160,6 +160,17 @@ public:
     Batch(Transformer& t, std::uint32_t n_slots, bool wide = false) : vocab_size_(t.args.vocab_size) {
         check(wide ? lmrs_batch_create_wide(t.ctx_, n_slots, &b_) : lmrs_batch_create(t.ctx_, n_slots, &b_));
     }
+    // a PAGED batch (wide): the slots draw pages of page_len positions (64, 128, 256, 512 or 1024) from one pool of n_pages pages; fork shares whole pages,
+    // a write un-shares the page it touches, release gives pages back.  Without release every result is a wide batch's, bit for bit  (lmrs_batch_create_paged)
+    Batch(Transformer& t, std::uint32_t n_slots, std::uint32_t page_len, std::uint32_t n_pages) : vocab_size_(t.args.vocab_size) {
+        check(lmrs_batch_create_paged(t.ctx_, n_slots, page_len, n_pages, &b_));
+    }
+    struct Pages { std::uint32_t page_len, n_pages, n_free; };
+    Pages pages() const { Pages p{}; check(lmrs_batch_pages(b_, &p.page_len, &p.n_pages, &p.n_free)); return p; }                  // (lmrs_batch_pages)
+    struct SlotPages { std::uint32_t held, shared; };
+    SlotPages slot_pages(std::uint32_t slot) const { SlotPages p{}; check(lmrs_batch_slot_pages(b_, slot, &p.held, &p.shared)); return p; }   // (lmrs_batch_slot_pages)
+    // keep positions [0, n_pos) of a slot (0 empties it): the pages behind them return to the pool once nobody holds them  (lmrs_batch_release)
+    void release(std::uint32_t slot, std::uint32_t n_pos = 0) { check(lmrs_batch_release(b_, slot, n_pos)); }
     // the most rows (forward, generate_greedy) and runs (forward_runs) a call takes: 16, or 64 for a wide batch  (lmrs_batch_width)
     std::uint32_t width() const { std::uint32_t w = 0; check(lmrs_batch_width(b_, &w)); return w; }
     Batch(const Batch&) = delete;

@@ -27,6 +27,11 @@ extern "C" {
     pub fn lmrs_batch_forward_runs_embed_sample(b: *mut LmrsBatch, n_runs: u32, slot: *const u32, start_pos: *const u32, run_len: *const u32,
                                                 run_kind: *const u32, tokens: *const u32, embeddings: *const f32,
                                                 samplers: *const *mut LmrsSampler, next: *mut u32) -> c_int;
+    // paged K/V: declared here as the wide batch is (tests/test_batch_paged_host.py compares them with the header)
+    pub fn lmrs_batch_create_paged(ctx: *mut ffi::LmrsCtx, n_slots: u32, page_len: u32, n_pages: u32, out: *mut *mut LmrsBatch) -> c_int;
+    pub fn lmrs_batch_pages(b: *const LmrsBatch, page_len: *mut u32, n_pages: *mut u32, n_free: *mut u32) -> c_int;
+    pub fn lmrs_batch_slot_pages(b: *const LmrsBatch, slot: u32, n_held: *mut u32, n_shared: *mut u32) -> c_int;
+    pub fn lmrs_batch_release(b: *mut LmrsBatch, slot: u32, n_pos: u32) -> c_int;
 }
 
 /// What a run of `Batch::forward_runs_embed` feeds: token ids, or rows of `dim` floats taken as `Transformer::fill_kv_cache` takes them.
@@ -74,6 +79,34 @@ impl<'t, 'a> Batch<'t, 'a> {
         check(unsafe { lmrs_batch_create_wide(t.ctx(), n_slots, &mut b) });
         let vocab_size = t.args.vocab_size as usize;
         Batch { b, vocab_size, _t: t }
+    }
+
+    /// A wide batch whose slots draw pages of `page_len` positions (64, 128, 256, 512 or 1024) from one pool of `n_pages` pages: `fork` shares whole
+    /// pages, a write un-shares the page it touches, `release` gives pages back.  Without `release` every result is a wide batch's, bit for bit.
+    pub fn new_paged(t: &'t mut Transformer<'a>, n_slots: u32, page_len: u32, n_pages: u32) -> Batch<'t, 'a> {
+        let mut b: *mut LmrsBatch = ptr::null_mut();
+        check(unsafe { lmrs_batch_create_paged(t.ctx(), n_slots, page_len, n_pages, &mut b) });
+        let vocab_size = t.args.vocab_size as usize;
+        Batch { b, vocab_size, _t: t }
+    }
+
+    /// A paged batch's pool: (page_len, n_pages, n_free).
+    pub fn pages(&self) -> (u32, u32, u32) {
+        let (mut l, mut n, mut f) = (0u32, 0u32, 0u32);
+        check(unsafe { lmrs_batch_pages(self.b, &mut l, &mut n, &mut f) });
+        (l, n, f)
+    }
+
+    /// The pages `slot` holds and how many of them have more than one holder: (held, shared).
+    pub fn slot_pages(&self, slot: u32) -> (u32, u32) {
+        let (mut h, mut s) = (0u32, 0u32);
+        check(unsafe { lmrs_batch_slot_pages(self.b, slot, &mut h, &mut s) });
+        (h, s)
+    }
+
+    /// Keep positions `[0, n_pos)` of `slot` (0 empties it); the pages behind them return to the pool once nobody holds them.
+    pub fn release(&mut self, slot: u32, n_pos: u32) {
+        check(unsafe { lmrs_batch_release(self.b, slot, n_pos) });
     }
 
     /// The most rows a call takes: 16, or 64 for a wide batch.

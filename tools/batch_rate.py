@@ -9,7 +9,10 @@ usage: python tools/batch_rate.py [model] [q8_0|q4_0]
 --wide: the same protocol on a WIDE batch (lmrs_batch_create_wide) - n = 16, 17, 24, 32, 47, 48, 64 rows at about 100 positions and n = 64 at about 1030 -
 and, before it, the time of ONE ragged pass (lmrs_batch_forward_runs, 16 runs on 16 slots at 100 positions, every row's output asked for) of 16 .. 64 rows:
 host time of 64 synchronous calls / 64, median of 5 after 2 warm-ups.  That call exists without the wide batch too, so on a build that lacks
-lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: the two trees of an A/B run by turns.  BATCH_RATE_OUT names the file written."""
+lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: the two trees of an A/B run by turns.  BATCH_RATE_OUT names the file written.
+       python tools/batch_rate.py --paged [model] [q8_0|q4_0]
+--paged: a PAGED batch (lmrs_batch_create_paged) against the wide batch of the same build, the forms by turns (paged_main below)
+       (writes profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt, profiles/batch_paged_phi35.txt)"""
 import os
 import statistics
 import sys
@@ -96,9 +99,107 @@ def wide_main(argv):
             f.write("\n".join(lines) + "\n")
 
 
+PAGED_OUT = {("llama-3.2-1b", S.Q8_0): "batch_paged_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_paged_gemma2b_q4.txt", ("phi-3.5", S.Q8_0): "batch_paged_phi35.txt"}
+
+
+def paged_main(argv):
+    """--paged [model] [q8_0|q4_0]: a paged batch (lmrs_batch_create_paged, page_len 64 and 256) against the wide batch of the same build, in one process,
+    the forms by turns three times: us per pass of 16 and 64 decode rows at 100 and at 1000 positions (device time of 64 greedy steps a call, median of 3 a
+    turn), a fork of 1000 positions into 63 slots (wall time, bytes held), and a 512-token lmrs_batch_prefill (wall time).  --paged phi-3.5 q8_0: the
+    full-size case only - the wide batch of 64 slots against a pool for 64 x 1024 positions."""
+    model = argv[0] if argv else "llama-3.2-1b"
+    qname = argv[1] if len(argv) > 1 else "q8_0"
+    qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True); lines.append(s)
+
+    def finish():
+        name = PAGED_OUT.get((model, qt))
+        path = os.environ.get("BATCH_RATE_OUT") or (os.path.join(ROOT, "profiles", name) if name else None)
+        if path:
+            with open(path, "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+    img = S.build_image(model, qt, 1234)
+    m = lmrs_amd.Transformer(img)
+    a = m.args
+    say(f"python tools/batch_rate.py --paged {model} {qname}")
+    say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
+    pos_bytes = 2 * a.n_layers * a.n_kv_heads * a.head_size * 4                              # K and V of one position, all layers
+    if model == "phi-3.5":
+        try:
+            lmrs_amd.Batch(m, 64, wide=True)
+            say("lmrs_batch_create_wide(64): created")
+        except lmrs_amd.LmrsError as e:
+            say(f"lmrs_batch_create_wide(64): {e}")
+        b = lmrs_amd.Batch(m, 64, page_len=256, n_pages=64 * 4)
+        say(f"lmrs_batch_create_paged(64, page_len 256, 256 pages = 64 x 1024 positions): created, {257 * 256 * pos_bytes / 1e9:.2f} GB")
+        p = S.prompt_tokens(model, 101, 100)
+        for i in range(64):
+            b.prefill(i, p[:100], 0)
+        ids, us, lo, hi = timed(lambda: b.generate_greedy(list(range(64)), [int(p[100])] * 64, [100] * 64, STEPS, timing=True), reps=3, warm=1)
+        say(f"  lmrs_batch_generate_greedy n=64 at 100 positions, {STEPS} steps a call: {us / STEPS:8.1f} us per pass ({lo / STEPS:.1f} .. {hi / STEPS:.1f})   "
+            f"{64 * STEPS / us * 1e6:9.1f} tok/s aggregate; the 64 rows agree: {all(ids[i].tolist() == ids[0].tolist() for i in range(64))}; pages (page_len, n, free): {b.pages()}")
+        return finish()
+    forms = [("wide", None), ("paged 64", 64), ("paged 256", 256)]
+    say(f"us per pass of lmrs_batch_generate_greedy ({STEPS} greedy steps a call, device time of the steps): the three forms by turns, three turns, median of 3 "
+        f"calls after 1 warm-up a turn; per form the median of its turns (fastest .. slowest turn)")
+    prompt = S.prompt_tokens(model, 1001, 100)
+    for depth in (100, 1000):
+        batches = {}
+        for name, pl in forms:
+            b = lmrs_amd.Batch(m, 64, wide=True) if pl is None else lmrs_amd.Batch(m, 64, page_len=pl, n_pages=64 * (-(-(depth + STEPS + 1) // pl)))
+            for i in range(64):
+                b.prefill(i, prompt[:depth], 0)
+            batches[name] = b
+        for n in (16, 64):
+            turns, ids = {name: [] for name, _ in forms}, {}
+            for _ in range(3):
+                for name, _pl in forms:
+                    b = batches[name]
+                    ids[name], us, _lo, _hi = timed(lambda: b.generate_greedy(list(range(n)), [int(prompt[depth])] * n, [depth] * n, STEPS, timing=True), reps=3, warm=1)
+                    turns[name].append(us / STEPS)
+            same = all((ids[name] == ids["wide"]).all() for name, _ in forms)
+            w = statistics.median(turns["wide"])
+            for name, _pl in forms:
+                t = turns[name]
+                say(f"  {depth:4d} positions, n={n:2d}, {name:9s}  {statistics.median(t):8.1f} us per pass ({min(t):.1f} .. {max(t):.1f})   {statistics.median(t) / w - 1:+6.1%} against wide")
+            say(f"      the three forms give the same tokens: {same}")
+        if depth == 1000:
+            say("lmrs_batch_fork of 1000 positions from slot 0 into slots 1 .. 63 (host wall time of the 63 synchronous calls), and the K/V bytes the 64 slots then hold")
+            for name, pl in forms:
+                b = batches[name]
+                for s in range(1, 64):
+                    if pl is not None:
+                        b.release(s)
+                t0 = time.perf_counter()
+                for s in range(1, 64):
+                    b.fork(0, s, 1000)
+                ms = (time.perf_counter() - t0) * 1e3
+                held = 64 * 1000 * pos_bytes if pl is None else (b.pages()[1] - b.pages()[2]) * pl * pos_bytes
+                say(f"  {name:9s}  {ms:8.2f} ms   {held / 1e6:9.1f} MB of written or held K/V" + ("" if pl is None else f" ({b.pages()[1] - b.pages()[2]} pages)"))
+            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): the table pass of a paged batch "
+                "against the block attention of a contiguous one")
+            for name, pl in forms:
+                b = batches[name]
+
+                def call():
+                    t0 = time.perf_counter(); b.prefill(1, prompt[:512], 0)
+                    return None, time.perf_counter() - t0
+                _, us, lo, hi = timed(call, reps=5, warm=1)
+                say(f"  {name:9s}  {us / 1e3:8.2f} ms ({lo / 1e3:.2f} .. {hi / 1e3:.2f})")
+        for b in batches.values():
+            b.close()
+    finish()
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--wide":
         return wide_main(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--paged":
+        return paged_main(sys.argv[2:])
     model = sys.argv[1] if len(sys.argv) > 1 else "llama-3.2-1b"
     qname = sys.argv[2] if len(sys.argv) > 2 else "q8_0"
     qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
