@@ -627,6 +627,31 @@ int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_runs, const u
  * with n0 = 0, is not written.  Everything else is refused before the device is touched. */
 int lmrs_op_sort_candidates(int device, const void* pairs, size_t n_rows, size_t ld, const uint32_t* n0, void* sorted);
 
+/* ---- allowed-token masks: which tokens a slot's rows may produce (extensions, no reference counterpart) ----
+ * A mask is state of a batch slot, not an argument of a pass: W = (vocab_size + 31) / 32 words, bit (t & 31) of word (t >> 5) set = token t allowed;
+ * bits at and above vocab_size are ignored.  While slot s has a mask, every output row of s in any batch call - lmrs_batch_forward, _generate_greedy
+ * (every one of its steps, the mask constant over them), _forward_runs (all n_out rows of the run), _forward_sample, _forward_runs_sample and the two
+ * _embed forms, contiguous or paged - is computed from the row's logits with the disallowed entries equal to -inf: the logits the caller downloads
+ * show -inf exactly at the cleared bits and the unmasked bits everywhere else, argmax is sample_argmax (sampler.rs:29-41) of that row, the top-k
+ * the k first candidates of it, a sampled token Sampler::sample (sampler.rs:109-129) of it - temperature-0 samplers included.  No floating-point
+ * operation on an allowed logit changes.  One launch (mask_rows_kernel) behind the classifier and Gemma's soft-cap writes the -inf, for the slabs of
+ * logits rows that have a masked row; a batch on which no mask was set, or all were cleared, runs exactly the launches it ran without this call.
+ * A mask touches no K/V row, no other slot, no call of the context's own and no row without outputs.  It stays until it is replaced or cleared:
+ * lmrs_batch_fork and lmrs_batch_release neither copy nor clear it.
+ * lmrs_batch_set_masks: the masks of n slots (mask i = bits + i * W, for slot[i]), ordered before the next pass; the caller's arrays are free on return.
+ *   One copy uploads all n.  The device block (n_slots x W words) and a pinned block of the same size are allocated at the first call, all or nothing
+ *   (the message gives the bytes); lmrs_batch_destroy frees them.  n == 0 does nothing.
+ * lmrs_batch_clear_masks: the slots named lose their masks; n == 0 (slot may be NULL): every slot.  A slot without a mask is not an error.
+ * lmrs_batch_mask_info: *n_allowed = the tokens below vocab_size the slot's mask allows; 0: the slot has no mask.
+ * Errors, each with a message of its own that opens with the call's name, before any device work, batch, context and samplers left usable: a NULL
+ * batch; a NULL array with n > 0; n above lmrs_batch_width; a slot >= n_slots; the same slot twice in one call; a mask with no allowed token below
+ * vocab_size (the slot is named); a model whose classifier leaves a tail of the vocabulary unwritten (the sampled calls' condition).
+ * lmrs_batch_forward_runs and lmrs_batch_forward_runs_embed refuse k > n_allowed of a masked slot that has outputs in the call (the message gives
+ * the slot, k and n_allowed): such a row has only n_allowed candidates that are numbers. */
+int lmrs_batch_set_masks(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* bits /* n * W */);
+int lmrs_batch_clear_masks(lmrs_batch* b, uint32_t n, const uint32_t* slot);
+int lmrs_batch_mask_info(const lmrs_batch* b, uint32_t slot, uint32_t* n_allowed /* 0: no mask */);
+
 #ifdef __cplusplus
 }
 #endif

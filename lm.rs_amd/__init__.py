@@ -33,6 +33,7 @@ EXPORTS = [
     "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
     "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
     "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release",
+    "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -114,6 +115,9 @@ def lib():
         L.lmrs_batch_pages.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_slot_pages.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_release.argtypes = [vp, u32, u32]
+        L.lmrs_batch_set_masks.argtypes = [vp, u32, vp, vp]
+        L.lmrs_batch_clear_masks.argtypes = [vp, u32, vp]
+        L.lmrs_batch_mask_info.argtypes = [vp, u32, C.POINTER(u32)]
         L.lmrs_batch_destroy.argtypes = [vp]; L.lmrs_batch_destroy.restype = None
         L.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
         L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
@@ -393,6 +397,27 @@ def _is_embed_run(rows) -> bool:
     return isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.dtype == np.float32
 
 
+def pack_mask(allowed) -> np.ndarray:
+    """bool [..., vocab_size] (true = the token is allowed) -> uint32 [..., W], W = (vocab_size + 31) // 32: bit (t & 31) of word (t >> 5) is token t,
+    the bits at and above vocab_size zero (the layout lmrs_batch_set_masks takes)"""
+    a = np.asarray(allowed)
+    if a.dtype != np.bool_ or a.ndim < 1:
+        raise LmrsError("pack_mask takes a bool array whose last axis is the vocabulary")
+    V = a.shape[-1]
+    W = (V + 31) // 32
+    padded = np.zeros(a.shape[:-1] + (W * 32,), np.uint8)
+    padded[..., :V] = a
+    return np.ascontiguousarray(np.packbits(padded, axis=-1, bitorder="little")).view("<u4").astype(np.uint32, copy=False)
+
+
+def unpack_mask(words, vocab_size: int) -> np.ndarray:
+    """pack_mask's inverse: uint32 [..., W] -> bool [..., vocab_size]"""
+    w = np.ascontiguousarray(words, np.uint32)
+    if w.ndim < 1 or w.shape[-1] != (vocab_size + 31) // 32:
+        raise LmrsError(f"a mask of vocab_size = {vocab_size} holds {(vocab_size + 31) // 32} words")
+    return np.unpackbits(w.astype("<u4", copy=False).view(np.uint8), axis=-1, bitorder="little")[..., :vocab_size].astype(np.bool_)
+
+
 BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BATCH_CTX)
 
 
@@ -431,6 +456,37 @@ class Batch:
     def release(self, slot: int, n_pos: int = 0) -> None:
         """Keep positions [0, n_pos) of `slot` (0 empties it): the pages behind them go back to the pool once nobody holds them (lmrs_batch_release)"""
         _chk(lib().lmrs_batch_release(self._h, slot, n_pos))
+
+    def set_masks(self, slots, masks) -> None:
+        """Allowed-token masks for `slots`, one row of `masks` each: bool [n, vocab_size] (true = allowed) or packed uint32 [n, W] (pack_mask).  While a
+        slot has a mask, every output of its rows in any call here - logits, argmax, top-k, sampled token - comes from the row's logits with the
+        disallowed entries -inf; the mask stays until it is replaced or cleared (lmrs_batch_set_masks)"""
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+        V = self.model.args.vocab_size
+        m = np.asarray(masks)
+        if m.dtype == np.bool_:
+            if m.ndim != 2 or m.shape != (s.size, V):
+                raise LmrsError(f"bool masks must be [{s.size}, vocab_size = {V}]")
+            m = pack_mask(m)
+        m = np.ascontiguousarray(m, np.uint32)
+        if m.ndim != 2 or m.shape != (s.size, (V + 31) // 32):
+            raise LmrsError(f"packed masks must be [{s.size}, {(V + 31) // 32}] uint32 words")
+        _chk(lib().lmrs_batch_set_masks(self._h, s.size, _p(s) if s.size else None, _p(m) if s.size else None))
+
+    def clear_masks(self, slots=None) -> None:
+        """The named slots lose their masks; None: every slot (lmrs_batch_clear_masks)"""
+        if slots is None:
+            _chk(lib().lmrs_batch_clear_masks(self._h, 0, None))
+            return
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+        if s.size:                                              # (an empty list names no slot; n == 0 in the C call means all of them)
+            _chk(lib().lmrs_batch_clear_masks(self._h, s.size, _p(s)))
+
+    def mask_info(self, slot: int):
+        """The number of tokens `slot`'s mask allows, or None when the slot has no mask (lmrs_batch_mask_info)"""
+        n = C.c_uint32()
+        _chk(lib().lmrs_batch_mask_info(self._h, slot, C.byref(n)))
+        return n.value or None
 
     @property
     def width(self) -> int:

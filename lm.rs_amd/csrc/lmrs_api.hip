@@ -183,7 +183,10 @@ struct StepForm { int qa_mode = 0, split_chunks = 0; bool split_merged = false; 
 // rows: the base the table's offsets count from); null: the context's own
 // runs (runs.tok != null): the pass is lmrs_batch_forward_runs' - a table of up to kRunRowsMax rows, several of them consecutive positions of one slot; its
 // qkv block is wider than pf_q at that many rows, so the pass brings a buffer of its own (qkv; null: pf_q, as every other pass).
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows
+// masks (masks.bits != null): some output row of the pass belongs to a batch slot with an allowed-token mask (lmrs_batch_set_masks) - of[r] is the mask row of
+// output row r in the order the classifier sees the rows, -1 for none; h_of is its pinned source, which says on the host whether a slab has a masked row at all.
+struct MaskView { const uint32_t* bits = nullptr; int words = 0; const int* of = nullptr; const int* h_of = nullptr; };
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1814,6 +1817,9 @@ static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, float* x
         g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits; g.skinny = form.skinny;
         HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
         if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));
+        // a batch's masks (PassForm::masks): one launch a slab, and only for a slab that has a masked row
+        if (form.masks.bits && std::any_of(form.masks.h_of + i0 + j0, form.masks.h_of + i0 + j0 + mj, [](int m) { return m >= 0; }))
+            HIP_OK(launch_mask_rows(c->sc_logits, o, o, mj, form.masks.bits, form.masks.words, form.masks.of + i0 + j0, c->stream));
         if (to.out_logits && copy_out_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
         if ((!to.out_logits || to.reduce_too) && reduce_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
     }
@@ -2051,6 +2057,14 @@ struct lmrs_batch {
     // page; the accounting (lmrs_pages.h), the device page table [n_slots][per_slot] and its pinned mirror
     PagePool* pool = nullptr; uint32_t page_len = 0; size_t page_floats = 0;
     uint32_t *ptab = nullptr, *h_ptab = nullptr;
+    // allowed-token masks (lmrs_batch_set_masks; allocated at the first call, all or nothing): the device block [n_slots][mask_words] and its pinned mirror,
+    // which is also the upload's staging; n_allowed[s] = 0: slot s has no mask, n_masked = the slots that have one.  mask_of / h_mask_of: the per-call
+    // column of PassForm::masks, written with the tables (batch_rows, runs_table); mask_live: this call uploaded it - some output row of the call is masked
+    uint32_t *masks = nullptr, *h_masks = nullptr; size_t mask_words = 0;
+    uint32_t n_allowed[kWideBatchMax] = {}; uint32_t n_masked = 0;
+    int *mask_of = nullptr, *h_mask_of = nullptr; bool mask_live = false;
+    int mask_row_of(uint32_t slot) const { return n_allowed[slot] ? (int)slot : -1; }
+    MaskView mask_view() const { return mask_live ? MaskView{masks, (int)mask_words, mask_of, h_mask_of} : MaskView{}; }
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
     // the `off` word of a row of `slot`: where its caches start, in floats - on a paged batch its row of the page table
     unsigned long long off_of(uint32_t slot) const { return pool ? slot : (unsigned long long)slot * 2 * slot_floats; }
@@ -2071,6 +2085,10 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     (void)hipStreamSynchronize(b->c->stream);
     if (b->ptab) (void)hipFree(b->ptab);
     if (b->h_ptab) (void)hipHostFree(b->h_ptab);
+    if (b->masks) (void)hipFree(b->masks);
+    if (b->mask_of) (void)hipFree(b->mask_of);
+    if (b->h_masks) (void)hipHostFree(b->h_masks);
+    if (b->h_mask_of) (void)hipHostFree(b->h_mask_of);
     delete b->pool;
     for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x, (void*)b->samp_tab, (void*)b->samp_scratch, (void*)b->samp_out}) if (p) (void)hipFree(p);
     for (void* p : {(void*)b->rs_tab, (void*)b->rs_scratch, (void*)b->rs_out, (void*)b->cs_keys, (void*)b->embed_stage}) if (p) (void)hipFree(p);
@@ -2149,6 +2167,90 @@ extern "C" int lmrs_batch_width(const lmrs_batch* b, uint32_t* width) {
 static int batch_failed(lmrs_ctx* c) { (void)hipStreamSynchronize(c->stream); c->err_queued = false; return -1; }
 // the one DevState of a batch call (only Gemma's kernels read it: every row tests the window against its own position)
 static int batch_state(lmrs_ctx* c) { return set_state(c, 0, 0, pass_win_base(c, 0, true)); }
+
+// ------------------------------------------------------------------ allowed-token masks: state of a slot (extensions, no reference counterpart)
+// While slot s has a mask, every output row of s in any batch call is Sampler::sample / sample_argmax / the top-k definition over the row's logits with the
+// disallowed entries -inf: classify_rows' one launch (mask_rows_kernel) between the soft-cap and the sinks, for the slabs that have a masked row.  No
+// arithmetic on an allowed logit changes; a batch with no mask set runs exactly the launches it ran before.
+static int masks_alloc(lmrs_batch* b) {
+    if (b->masks) return 0;
+    const size_t W = ((size_t)b->c->args.vocab_size + 31) / 32, bytes = (size_t)b->n_slots * W * 4;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&b->masks), bytes) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_masks), bytes, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->mask_of), (size_t)kRunRowsMax * sizeof(int)) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_mask_of), (size_t)kRunRowsMax * sizeof(int), hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void** p : {(void**)&b->masks, (void**)&b->mask_of}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        for (void** p : {(void**)&b->h_masks, (void**)&b->h_mask_of}) if (*p) { (void)hipHostFree(*p); *p = nullptr; }
+        return fail("lmrs_batch_set_masks: " + std::to_string(bytes) + " bytes of masks for " + std::to_string(b->n_slots) + " slots (and as many pinned): out of memory");
+    }
+    memset(b->h_masks, 0, bytes);
+    b->mask_words = W;
+    return 0;
+}
+// the slots of a mask call, checked: `what` opens every message
+static int mask_slots_check(const lmrs_batch* b, const std::string& what, uint32_t n, const uint32_t* slot) {
+    if (n > b->width) return fail(what + "n = " + std::to_string(n) + " exceeds the batch's width of " + std::to_string(b->width));
+    uint64_t seen = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (slot[i] >= b->n_slots) return fail(what + "mask " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
+        if (seen >> slot[i] & 1u) return fail(what + "slot " + std::to_string(slot[i]) + " appears twice");
+        seen |= uint64_t(1) << slot[i];
+    }
+    return 0;
+}
+extern "C" int lmrs_batch_set_masks(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* bits) {
+    const std::string what = "lmrs_batch_set_masks: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && (!slot || !bits)) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot)) return -1;
+    lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, W = (V + 31) / 32;
+    if (cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no masks for this vocabulary");
+    const uint32_t last = V % 32 ? (1u << V % 32) - 1u : ~0u;                  // the bits of the last word that lie below vocab_size
+    uint32_t count[kWideBatchMax];
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t* w = bits + (size_t)i * W;
+        count[i] = (uint32_t)__builtin_popcount(w[W - 1] & last);
+        for (size_t j = 0; j + 1 < W; ++j) count[i] += (uint32_t)__builtin_popcount(w[j]);
+        if (!count[i]) return fail(what + "mask " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " would have no allowed token below vocab_size = " + std::to_string(V));
+    }
+    if (!n) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    if (masks_alloc(b)) return -1;
+    // the mirror's rows, then ONE copy: the span of rows from the lowest slot of the call to the highest (the rows between them go as they stand on the device)
+    uint32_t lo = slot[0], hi = slot[0];
+    for (uint32_t i = 0; i < n; ++i) {
+        memcpy(b->h_masks + (size_t)slot[i] * W, bits + (size_t)i * W, W * 4);
+        b->h_masks[(size_t)slot[i] * W + W - 1] &= last;
+        lo = std::min(lo, slot[i]); hi = std::max(hi, slot[i]);
+    }
+    if (hipMemcpyAsync(b->masks + (size_t)lo * W, b->h_masks + (size_t)lo * W, (size_t)(hi - lo + 1) * W * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        // (the slots of the call lose their masks: what the device holds for them is unknown)
+        for (uint32_t i = 0; i < n; ++i) if (b->n_allowed[slot[i]]) { b->n_allowed[slot[i]] = 0; --b->n_masked; }
+        return fail(what + std::string("uploading the masks failed: ") + hipGetErrorString(hipGetLastError()));
+    }
+    for (uint32_t i = 0; i < n; ++i) { if (!b->n_allowed[slot[i]]) ++b->n_masked; b->n_allowed[slot[i]] = count[i]; }
+    return 0;
+}
+extern "C" int lmrs_batch_clear_masks(lmrs_batch* b, uint32_t n, const uint32_t* slot) {
+    const std::string what = "lmrs_batch_clear_masks: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && !slot) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot)) return -1;
+    if (!n) { memset(b->n_allowed, 0, sizeof b->n_allowed); b->n_masked = 0; return 0; }
+    for (uint32_t i = 0; i < n; ++i) if (b->n_allowed[slot[i]]) { b->n_allowed[slot[i]] = 0; --b->n_masked; }
+    return 0;
+}
+extern "C" int lmrs_batch_mask_info(const lmrs_batch* b, uint32_t slot, uint32_t* n_allowed) {
+    const std::string what = "lmrs_batch_mask_info: ";
+    if (!b || !n_allowed) return fail(what + "NULL argument");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    *n_allowed = b->n_allowed[slot];
+    return 0;
+}
 
 // ------------------------------------------------------------------ paged batches: the slots draw pages from one pool (extensions, no reference counterpart)
 // The accounting is lmrs_pages.cpp's, decided on the host and finished before any device work of the call; what it asks of the device - clear a
@@ -2325,9 +2427,13 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
     size_t o = 0;
     for (size_t i = 0, j = 0; i < n_runs; ++i) {
         const uint32_t len = run_len ? run_len[i] : 1u, no = n_out ? n_out[i] : 1u;
-        for (uint32_t u = len - no; u < len; ++u) h->sel[o++] = (uint32_t)at[j + u];
+        for (uint32_t u = len - no; u < len; ++u) {
+            if (b->n_masked) b->h_mask_of[o] = b->mask_row_of(slot[i]);     // (the classifier sees the outputs in this order)
+            h->sel[o++] = (uint32_t)at[j + u];
+        }
         j += len;
     }
+    b->mask_live = false;
     *rows_out = R; *outs = o;
 }
 // One pass over the device's long table as it stands: R rows through the layers, then the O rows of sel through the final norm and the classifier to
@@ -2371,7 +2477,7 @@ static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink t
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
-    PassForm cls; cls.skinny = O <= kStreamPassMax;
+    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view();
     to.targets = false;
     return classify_rows(c, cls, to, b->runs_x, 0, (int)O);
 }
@@ -2397,7 +2503,17 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
     for (uint32_t r = 0; r < n; ++r) {
         const int i = order[r];
         b->h_tab->off[r] = b->off_of(slot[i]); b->h_tab->pos[r] = (int)pos[i]; b->h_tab->tok[r] = tokens[i];
+        if (b->n_masked) b->h_mask_of[r] = b->mask_row_of(slot[i]);
     }
+    b->mask_live = false;
+    return 0;
+}
+// The mask column of a call with n output rows, beside its table: uploaded - and the pass's forms carry it (lmrs_batch::mask_view) - only when one of the
+// rows is masked; a batch without masks enqueues nothing here
+static int masks_enqueue(lmrs_batch* b, size_t n) {
+    if (!b->n_masked || !std::any_of(b->h_mask_of, b->h_mask_of + n, [](int m) { return m >= 0; })) return 0;
+    HIP_OK(hipMemcpyAsync(b->mask_of, b->h_mask_of, n * sizeof(int), hipMemcpyHostToDevice, b->c->stream));
+    b->mask_live = true;
     return 0;
 }
 // one pass over the device table's rows as they stand; step: how far the rows have moved since batch_rows (sizes the attention's score vector)
@@ -2405,6 +2521,7 @@ static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logit
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
     if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); }
+    form.masks = b->mask_view();
     RowSink to{0, n, out_logits, 0}; to.targets = false;
     return run_tokens(c, to, form, /*batched=*/true);
 }
@@ -2421,7 +2538,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
         const HostScores hs = host_scores(c);
         auto enqueue = [&]() -> int {
             HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-            if (batch_state(c)) return -1;
+            if (masks_enqueue(b, n) || batch_state(c)) return -1;
             RowSink to{0, n, logits, 0}; to.reduce_too = true;
             if (runs_pass(b, n, n, 0, to)) return -1;
             HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2435,7 +2552,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
     std::vector<float> rows(logits ? n * V : 0);         // the pass's rows in table order
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (batch_state(c)) return -1;
+        if (masks_enqueue(b, n) || batch_state(c)) return -1;
         if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx
         if (logits && copy_out_rows(c, RowSink{0, n, rows.data(), 0}, c->sc_logits, cls_rows(c), (int)n, 0)) return -1;
         HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2463,7 +2580,7 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     auto enqueue = [&]() -> int {
         if (wide) HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
         else HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (batch_state(c)) return -1;
+        if (masks_enqueue(b, n) || batch_state(c)) return -1;       // (the column once: the rows keep their order over the n_new steps)
         HIP_OK(hipEventRecord(c->ev0, c->stream));
         for (uint32_t j = 0; j < n_new && wide; ++j) {
             if (runs_pass(b, n, n, j, RowSink{0, n, nullptr, 0})) return -1;
@@ -2546,7 +2663,7 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
     const size_t head = b->head_words;
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (batch_state(c)) return -1;
+        if (masks_enqueue(b, n) || batch_state(c)) return -1;
         if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx; the rows stay in sc_logits
         if (!sampled) { HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
         HIP_OK(hipMemcpyAsync(b->samp_tab, b->h_samp_tab, n * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
@@ -2645,6 +2762,9 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     if (k && topk_check_k(k, a.vocab_size)) return -1;
     if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
     if (O && !argmax) return fail(what + "argmax is NULL with " + std::to_string(O) + " output rows asked for");
+    for (uint32_t i = 0; i < n_runs && k; ++i)            // a masked row has n_allowed candidates that are numbers
+        if (n_out[i] && b->n_allowed[slot[i]] && k > b->n_allowed[slot[i]])
+            return fail(what + "run " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + ": k = " + std::to_string(k) + " exceeds the " + std::to_string(b->n_allowed[slot[i]]) + " tokens its mask allows (n_allowed)");
     runs_table(b, n_runs, slot, start_pos, run_len, n_out, src, &R, &O);
     HIP_OK(hipSetDevice(c->device));
     if (k && O && topk_alloc(c, c->sc_rows, (int)k)) return -1;
@@ -2655,7 +2775,7 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     auto enqueue = [&]() -> int {
         if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * a.dim * 4, hipMemcpyHostToDevice, c->stream));     // the call's embedding rows, in caller order
         HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-        if (batch_state(c)) return -1;
+        if (masks_enqueue(b, O) || batch_state(c)) return -1;
         RowSink to{0, O, logits, k}; to.reduce_too = true;
         if (runs_pass(b, R, O, 0, to, E ? b->embed_stage : nullptr)) return -1;
         if (!O) return 0;
@@ -2807,7 +2927,7 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
     auto enqueue = [&]() -> int {
         if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * c->args.dim * 4, hipMemcpyHostToDevice, c->stream));
         HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-        if (batch_state(c)) return -1;
+        if (masks_enqueue(b, O) || batch_state(c)) return -1;
         if (runs_pass(b, R, O, 0, RowSink{0, O, nullptr, 0}, E ? b->embed_stage : nullptr)) return -1;          // the reduction: sample_argmax of every output row -> sc_idx; the rows stay in sc_logits
         if (!O) return 0;
         if (!sampled) { HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }

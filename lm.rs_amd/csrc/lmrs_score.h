@@ -46,4 +46,9 @@ hipError_t launch_topk_rows(const TopkArgs& a, hipStream_t s);
 // `dim` logits (transformer.rs:375-381), the decode classifier epilogue's arithmetic over a block of rows
 hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStream_t s);
 
+// logits[r * ld + t] = -inf for r < rows with mask_of[r] >= 0 and every t < cols whose bit - bit (t & 31) of word (t >> 5) of mask row mask_of[r],
+// `words` words a row of `bits` - is clear; nothing else is written and nothing of the block is read.  cols % 4 == 0, ld % 4 == 0, cols <= 32 * words,
+// the block 16-byte aligned.  (lmrs_batch_set_masks: behind the soft-cap, in front of every sink)
+hipError_t launch_mask_rows(float* logits, int ld, int cols, int rows, const uint32_t* bits, int words, const int* mask_of, hipStream_t s);
+
 }  // namespace lmrs

@@ -13,6 +13,9 @@
 //
 // softcap_rows_kernel: Gemma-2's soft-cap of the first `dim` logits of every row of the block, between the batched classifier GEMM and the
 // reduction (the decode classifier applies it in its epilogue).
+//
+// mask_rows_kernel: a batch slot's allowed-token mask (lmrs_batch_set_masks) over the rows of the block, behind the soft-cap and in front of every
+// sink: -inf over the disallowed logits.  Stores only.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -295,11 +298,39 @@ __global__ __launch_bounds__(kLanes) void softcap_rows_kernel(float* logits, int
     *p = v;
 }
 
+// Row blockIdx.y of the block under mask row mask_of[blockIdx.y] of `bits` (`words` words a mask; < 0: the row has no mask and its workgroup leaves).
+// No logit is read.  A lane owns four consecutive columns - one aligned 16-byte store - and the four bits of them in the mask word it shares with
+// seven neighbours: all set, nothing; none set, one float4 of -inf; mixed, a dword store per cleared bit.  A wave covers 256 columns: eight mask
+// words, 1 KB of contiguous stores.  cols % 4 == 0, so no lane's four straddle the row's end.
+__global__ __launch_bounds__(kLanes) void mask_rows_kernel(float* logits, int ld, int cols, const uint32_t* bits, int words, const int* mask_of) {
+    const int m = mask_of[blockIdx.y];
+    if (m < 0) return;
+    const int g = blockIdx.x * kLanes + threadIdx.x;
+    if (4 * g >= cols) return;
+    const uint32_t allowed = bits[(size_t)m * words + (g >> 3)] >> ((g & 7) * 4) & 15u;
+    if (allowed == 15u) return;
+    float* p = logits + (size_t)blockIdx.y * ld + 4 * g;
+    const float ninf = -INFINITY;
+    if (allowed == 0u) { *reinterpret_cast<float4*>(p) = make_float4(ninf, ninf, ninf, ninf); return; }
+    if (!(allowed & 1u)) p[0] = ninf;
+    if (!(allowed & 2u)) p[1] = ninf;
+    if (!(allowed & 4u)) p[2] = ninf;
+    if (!(allowed & 8u)) p[3] = ninf;
+}
+
 }  // namespace
 
 hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStream_t s) {
     if (!logits || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld) return hipErrorInvalidValue;
     hipLaunchKernelGGL(softcap_rows_kernel, dim3((cols + kLanes - 1) / kLanes, rows), dim3(kLanes), 0, s, logits, ld, cols);
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_rows(float* logits, int ld, int cols, int rows, const uint32_t* bits, int words, const int* mask_of, hipStream_t s) {
+    if (!logits || !bits || !mask_of || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld || cols % 4 || ld % 4 || (size_t)words * 32 < (size_t)cols ||
+        (reinterpret_cast<uintptr_t>(logits) & 15) != 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_rows_kernel, dim3((cols / 4 + kLanes - 1) / kLanes, rows), dim3(kLanes), 0, s, logits, ld, cols, bits, words, mask_of);
     return hipGetLastError();
 }
 

@@ -171,6 +171,19 @@ public:
     SlotPages slot_pages(std::uint32_t slot) const { SlotPages p{}; check(lmrs_batch_slot_pages(b_, slot, &p.held, &p.shared)); return p; }   // (lmrs_batch_slot_pages)
     // keep positions [0, n_pos) of a slot (0 empties it): the pages behind them return to the pool once nobody holds them  (lmrs_batch_release)
     void release(std::uint32_t slot, std::uint32_t n_pos = 0) { check(lmrs_batch_release(b_, slot, n_pos)); }
+    // Allowed-token masks, state of a slot: bits = mask_words() words per slot, bit (t & 31) of word (t >> 5) set = token t allowed.  While a slot has a
+    // mask every output row of it in any call here - logits, argmax, top-k, sampled token - comes from the row's logits with the disallowed entries -inf;
+    // the mask stays until it is replaced or cleared  (lmrs_batch_set_masks / lmrs_batch_clear_masks / lmrs_batch_mask_info)
+    std::size_t mask_words() const { return (vocab_size_ + 31) / 32; }
+    void set_masks(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& bits) {
+        if (bits.size() != slot.size() * mask_words()) throw Panic("Batch::set_masks: bits must hold mask_words() words per slot");
+        check(lmrs_batch_set_masks(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), bits.data()));
+    }
+    void clear_masks() { check(lmrs_batch_clear_masks(b_, 0, nullptr)); }                                      // every slot
+    void clear_masks(const std::vector<std::uint32_t>& slot) {
+        if (!slot.empty()) check(lmrs_batch_clear_masks(b_, static_cast<std::uint32_t>(slot.size()), slot.data()));
+    }
+    std::uint32_t mask_info(std::uint32_t slot) const { std::uint32_t n = 0; check(lmrs_batch_mask_info(b_, slot, &n)); return n; }   // the tokens allowed; 0: no mask
     // the most rows (forward, generate_greedy) and runs (forward_runs) a call takes: 16, or 64 for a wide batch  (lmrs_batch_width)
     std::uint32_t width() const { std::uint32_t w = 0; check(lmrs_batch_width(b_, &w)); return w; }
     Batch(const Batch&) = delete;

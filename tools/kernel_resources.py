@@ -17,7 +17,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lm.rs_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
-OBJECTS = ["lmrs_kernels.o", "lmrs_api.o", "lmrs_vision_att.o"]
+# (lmrs_score.o - the reductions, the soft-cap, mask_rows_kernel - holds no hot class: its kernels live in an anonymous namespace, which HOT never matches)
+OBJECTS = ["lmrs_kernels.o", "lmrs_api.o", "lmrs_vision_att.o", "lmrs_score.o"]
 TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
 # the kernel classes of the decode step, the batched prefill and the image tower (everything a bench line or a profile quotes)
 HOT = re.compile(r"^(?:void )?lmrs::(gemv_static_kernel|qkv_attn_kernel|gemm_q8_dma_kernel|gemm_q4_pair_kernel|attention_split_values_kernel|attention_split_scores_kernel|"
@@ -51,6 +52,7 @@ def collect(hot_only=True):
         ks = _kernels_of(path)
         names = subprocess.run(["c++filt"], input="\n".join(n for n, _ in ks), capture_output=True, text=True, check=True).stdout.splitlines()
         for (_, k), name in zip(ks, names):
+            name = name.replace("(anonymous namespace)::", "anon::")        # (the first parenthesis of such a name is not the parameter list's)
             name = re.sub(r"\(.*$", "", name).replace("void ", "")          # template arguments identify the class; the parameter list does not
             if hot_only and not HOT.match(name):
                 continue
