@@ -1190,10 +1190,16 @@ hipError_t launch_rows_prologue(float* x, const float* rms_w, const float* delta
         else { if (q4) RPK(N_, NT_, 2, true); else RPK(N_, NT_, 2, false); }                              \
         return hipGetLastError();                                                                         \
     }
-    // (the hidden-size vectors are only ever quantised: no norm variants of their kernels)
-#define RP0(N_, NT_) if (n == N_) { if (mode != 0) return hipErrorInvalidValue; if (q4) RPK(N_, NT_, 0, true); else RPK(N_, NT_, 0, false); return hipGetLastError(); }
-    RP(2048, 256) RP(3072, 256) RP0(8192, 512) RP(2304, 256) RP0(9216, 512) RP(1024, 256) RP0(4096, 512)
-#undef RP0
+    // (4096, 8192 and 9216 are hidden sizes, quantised only, and model widths of Llama / Phi geometries, normed too; mode 2 is Gemma-2's, whose width is 2304)
+#define RP1(N_, NT_)                                                                                      \
+    if (n == N_) {                                                                                        \
+        if (mode == 0) { if (q4) RPK(N_, NT_, 0, true); else RPK(N_, NT_, 0, false); }                    \
+        else if (mode == 1) { if (q4) RPK(N_, NT_, 1, true); else RPK(N_, NT_, 1, false); }               \
+        else return hipErrorInvalidValue;                                                                 \
+        return hipGetLastError();                                                                         \
+    }
+    RP(2048, 256) RP(3072, 256) RP1(8192, 512) RP(2304, 256) RP1(9216, 512) RP(1024, 256) RP1(4096, 512)
+#undef RP1
 #undef RP
 #undef RPK
     return hipErrorInvalidValue;

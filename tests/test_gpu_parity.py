@@ -346,7 +346,9 @@ def test_mini_q4_and_gemma_logits_bit_exact(L, cfg, q):
 @pytest.mark.parametrize("i", range(18))
 def test_random_geometries_single_token_and_batched(L, i):
     """Geometries no kernel was tuned or instantiated for (random family, heads, kv heads, head size, hidden, depth and a vocabulary
-    that is not a multiple of 4), in each weight format: single-token steps, then a batched prefill and decode steps on its cache."""
+    that is not a multiple of 4), in each weight format: single-token steps, then one fill_kv_cache call of many tokens and decode steps on its
+    cache.  With widths of 128 and 256 these geometries lie outside what the batched pass admits: the call feeds its tokens one by one through the
+    layers' decode kernels - the batched kernels at other geometries than the four model families' are tests/test_lattice.py's."""
     rng = np.random.default_rng(2000 + i)
     cfg = S.random_cfg(rng, i, max_pos=128)
     q = [S.Q8_0, S.Q4_0, S.Q_NONE][i % 3]
@@ -792,6 +794,11 @@ def test_row_sharding_on_random_geometries(L, monkeypatch, i):
     grp.close()
 
 
+def _lattice_corner(corner, **changes):
+    import dataclasses
+    return dataclasses.replace({c.name: c for c in S.lattice_corners()}[corner], **changes)
+
+
 def _p2p_rank(rank, world, img_path, cfg, env, q_in, q_out, n_fill=6, n_prompt=3):
     """One process of the peer-to-peer test: its shard of the model on device 0, handles exchanged through the parent."""
     try:
@@ -829,7 +836,12 @@ def _p2p_rank(rank, world, img_path, cfg, env, q_in, q_out, n_fill=6, n_prompt=3
     ("mini-llama", 2, "tp-splitout", 70, 12, S.Q8_0), ("mini-llama3b", 4, "tp-splitout", 70, 12, S.Q8_0), ("mini-gemma", 2, "tp-splitout", 70, 12, S.Q4_0),    # ... and wo / w2 split too
     # 8 shards (a full node), 520 classifier rows each = 65 argmax partials per shard: an ODD count, whose 520-byte block the push transport (16 bytes per lane)
     # refused until round 6 - as it did Llama-3.2-1B's 501 partials on 8 shards (the block is padded to 16 bytes now: lmrs_ctx::part_stride)
-    (S.ModelCfg("mini-llama-v4160", 2048, 8192, 2, 32, 64, 8, 4160, 256, 1e-5, 500000.0, S.LLAMA), 8, "cls", 6, 3, S.Q8_0)])
+    (S.ModelCfg("mini-llama-v4160", 2048, 8192, 2, 32, 64, 8, 4160, 256, 1e-5, 500000.0, S.LLAMA), 8, "cls", 6, 3, S.Q8_0),
+    # corners of the geometry lattice prefill_tp_shapes_ok admits beside the four families' shapes (tools/synth_lmrs.py::lattice_corners), two shards, every
+    # per-shard slice whole 128-groups: attention wider than the model (32 x 96 with two kv heads: 1536 | 96 | 96 rows a shard), kv = heads at head
+    # size 64, Gemma-2 off its 8 / 4 heads (4 x 256 / 2, hidden 2304: 1152 a shard)
+    (_lattice_corner("w1024-att3072", name="w1024-att3072-kv2", n_kv_heads=2), 2, "tp", 70, 12, S.Q8_0),
+    (_lattice_corner("w2048-kv32"), 2, "tp", 70, 12, S.Q4_0), (_lattice_corner("gemma-h2304"), 2, "tp", 70, 12, S.Q8_0)])
 def test_peer_to_peer_shards_in_separate_processes(L, tmp_path, cfg, world, plan, n_fill, n_prompt, q):
     """The multi-GPU launch shape on a one-GPU box: `world` PROCESSES, one shard each (here all on device 0), exchange arenas opened
     through IPC handles, every exchange a push kernel that really waits for the other process's flag.  fill_kv_cache on the shards,

@@ -46,7 +46,7 @@ PREFILL_CASES = [
     ("mini-gemma", S.Q8_0, 60, 4), ("mini-gemma", S.Q4_0, 75, 0),
     ("mini-llama", S.Q_NONE, 12, 1),                 # unquantised: token path
     ("mini-gemma9b", S.Q8_0, 30, 0),                 # a Gemma geometry the batched pass refuses: token path
-    ("random", S.Q8_0, 40, 2),
+    ("random", S.Q8_0, 40, 2),                      # a 128- or 256-wide geometry: outside what the batched pass admits, token path (tests/test_lattice.py: the batched one)
 ]
 
 

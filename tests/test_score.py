@@ -38,7 +38,7 @@ FORWARD_CASES = [
     ("mini-llama-v4102", S.Q8_0, 40, 2),             # zero tail, classifier rows not a multiple of 16: token path
     ("mini-gemma", S.Q8_0, 30, 4), ("mini-gemma", S.Q4_0, 30, 0),     # token path
     ("mini-llama", S.Q_NONE, 12, 1),                 # unquantised
-    ("random", S.Q8_0, 40, 2),
+    ("random", S.Q8_0, 40, 2),                      # a 128- or 256-wide geometry: outside what the batched pass admits, token path (tests/test_lattice.py: the batched one)
 ]
 
 

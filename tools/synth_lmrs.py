@@ -260,6 +260,41 @@ def random_cfg(rng, i: int, max_pos: int = 32) -> ModelCfg:
                     [10000.0, 500000.0, 10000.0][mt], mt)
 
 
+def lattice_corners() -> list:
+    """Corners of the geometry lattice the batched pass admits (the library's prefill_batched_ok: dim, n_heads * head_size and hidden_dim each one of
+    1024 / 2048 / 2304 / 3072 / 4096 / 8192 / 9216; head size 64, 96 or 128, Gemma-2: dim 2304 with 256-wide heads; any n_kv_heads that divides
+    n_heads) that no entry of CONFIGS stands on.  Two layers and a small vocabulary each; 640 positions hold the longest run tests/test_lattice.py
+    feeds.  A fixed, named list - not part of CONFIGS, which documents and other tests enumerate.  tests/test_lattice_host.py proves on the host that the list, with the four mini shapes, reaches every GEMM instantiation the lattice can."""
+    def c(name, mt, dim, hidden, heads, hs, kv, vocab=4096):
+        return ModelCfg(name, dim, hidden, 2, heads, hs, kv, vocab, 640, [1e-6, 1e-5][mt != GEMMA],
+                        [10000.0, 500000.0, 10000.0][mt], mt)
+    return [
+        # width 1024, one kv head; a vocabulary below one 256-row tile plus a ragged remainder, and one that is a multiple of 16 but not of 64
+        c("w1024-h1024", LLAMA, 1024, 1024, 16, 64, 1, 272),
+        c("w1024-h2304", LLAMA, 1024, 2304, 16, 64, 1, 4112),
+        # attention wider than the model, one kv head: the last row tile of the qkv launch straddles the q | k | v boundaries part-filled
+        c("w1024-att3072", PHI, 1024, 1024, 32, 96, 1),
+        c("w1024-att9216", PHI, 1024, 2048, 96, 96, 1),
+        c("w1024-att8192", LLAMA, 1024, 8192, 128, 64, 1),
+        # as many kv heads as heads at head size 64
+        c("w2048-kv32", LLAMA, 2048, 2048, 32, 64, 32),
+        c("w1024-kv48", LLAMA, 1024, 1024, 48, 64, 48),
+        # wide models with a narrow MLP and narrow attention
+        c("w8192-h1024", LLAMA, 8192, 1024, 16, 64, 1),
+        c("w9216-h1024", PHI, 9216, 1024, 16, 64, 1),
+        # width 4096, 128-wide heads: kv = heads, and a ratio of 4
+        c("w4096-kv32", LLAMA, 4096, 2048, 32, 128, 32),
+        c("w4096-kv8", LLAMA, 4096, 4096, 32, 128, 8),
+        # odd GQA ratios: 12 and 3 (a Llama of Gemma's width: 96-row tiles that divide 2304)
+        c("w3072-gqa12", LLAMA, 3072, 2048, 24, 128, 2),
+        c("w2304-gqa3", LLAMA, 2304, 1024, 36, 64, 12),
+        # Gemma-2 off its 8 / 4 heads: attention narrower than the model, and as wide with a ratio of 3
+        c("gemma-att1024", GEMMA, 2304, 1024, 4, 256, 1),
+        c("gemma-att2304", GEMMA, 2304, 8192, 9, 256, 3),
+        c("gemma-h2304", GEMMA, 2304, 2304, 4, 256, 2),
+    ]
+
+
 def prompt_tokens(cfg: ModelCfg | str, n: int = 16, seed: int = 1234) -> np.ndarray:
     if isinstance(cfg, str):
         cfg = CONFIGS[cfg]
