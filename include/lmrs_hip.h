@@ -271,9 +271,11 @@ int  lmrs_batch_width(const lmrs_batch* b, uint32_t* width);
  * lmrs_batch_fork(src, dst, n_pos): dst's entries of the pages wholly inside [0, n_pos) become references to src's pages (dst's former pages there are
  * dropped); the rows of the partial last page are copied into a page dst holds alone; dst's later entries stay.  At most one page copy and a table
  * edit.  From LMRS_BATCH_CTX (a contiguous cache) the rows are copied into dst's own pages.
- * The cost: lmrs_batch_prefill and lmrs_batch_prefill_embeddings go through the table pass on a paged batch - one workgroup per (head, row), chunks of
- * 512 rows - not through the block-attention launches, so a long prompt is slower than on a contiguous batch (512 tokens of Llama-3.2-1B: 5.88 ms
- * against 2.69 ms); the values are the same bits.  A decode pass of 64 rows costs +2.9 % at 100 positions and +4.7 % at 1000 on Llama-3.2-1B Q8_0 and is
+ * Prompts: lmrs_batch_prefill and lmrs_batch_prefill_embeddings run chunks of at most 512 rows on a paged batch; a chunk of 112 rows or more takes block
+ * attention over the page table (64-query blocks, one table lookup per 64-key chunk or tile) under the contiguous rule - head sizes 64 / 96 / 128, Gemma's
+ * 256, at most 1 GiB of score slabs -, a shorter one the table pass, one workgroup per (head, row), which measures faster there; the values are the same
+ * bits either way (lmrs_batch_prefill_form tells how a call would run).  512 tokens of Llama-3.2-1B Q8_0: 2.73 ms against 2.59 ms on a wide batch (1.05x;
+ * the table pass took 5.91 ms), Gemma-2-2B Q4_0 7.85 against 7.57 ms (1.04x; 12.44) (profiles/batch_paged_prefill_*.txt).  A decode pass of 64 rows costs +2.9 % at 100 positions and +4.7 % at 1000 on Llama-3.2-1B Q8_0 and is
  * 0.7 % / 5.7 % faster on Gemma-2-2B Q4_0 (profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt). */
 int lmrs_batch_create_paged(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
                             uint32_t n_pages /* >= 1 */, lmrs_batch** out);
@@ -285,6 +287,16 @@ int lmrs_batch_slot_pages(const lmrs_batch* b, uint32_t slot, uint32_t* n_held, 
  * entries return to the zero page, and a page nobody holds is free.  Refused, each with its own message: a batch that is not paged, a slot >=
  * n_slots, n_pos > seq_len. */
 int lmrs_batch_release(lmrs_batch* b, uint32_t slot, uint32_t n_pos);
+/* (extension, no reference counterpart)
+ * How lmrs_batch_prefill / lmrs_batch_prefill_embeddings would run n rows at start_pos on this batch:
+ * *n_chunks = passes of at most 512 rows, *n_block = how many of them take block attention (64-query blocks);
+ * the others take one workgroup per (head, row).  Host arithmetic only; any batch, paged or not.  Refused: NULL arguments, start_pos + n > seq_len. */
+int lmrs_batch_prefill_form(const lmrs_batch* b, size_t n, uint32_t start_pos, uint32_t* n_chunks, uint32_t* n_block);
+/* (extension, no reference counterpart)
+ * Test / A-B aid in lmrs_debug_inject's manner (an explicit call; nothing is read from the environment): force != 0 -
+ * every prompt chunk of this PAGED batch takes the table pass from now on (the routing before block attention read the page table); 0 - the
+ * library's rule.  Refused on a batch that is not paged. */
+int lmrs_batch_debug_prefill_table(lmrs_batch* b, int force);
 
 /* == lmrs_prefill_tokens, into slot's cache: rows start_pos .. start_pos+n-1 as n forward calls leave them */
 int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n, uint32_t start_pos);

@@ -32,7 +32,7 @@ EXPORTS = [
     "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
     "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
-    "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release",
+    "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
@@ -115,6 +115,8 @@ def lib():
         L.lmrs_batch_pages.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_slot_pages.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_release.argtypes = [vp, u32, u32]
+        L.lmrs_batch_prefill_form.argtypes = [vp, sz, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.lmrs_batch_debug_prefill_table.argtypes = [vp, C.c_int]
         L.lmrs_batch_set_masks.argtypes = [vp, u32, vp, vp]
         L.lmrs_batch_clear_masks.argtypes = [vp, u32, vp]
         L.lmrs_batch_mask_info.argtypes = [vp, u32, C.POINTER(u32)]
@@ -456,6 +458,18 @@ class Batch:
     def release(self, slot: int, n_pos: int = 0) -> None:
         """Keep positions [0, n_pos) of `slot` (0 empties it): the pages behind them go back to the pool once nobody holds them (lmrs_batch_release)"""
         _chk(lib().lmrs_batch_release(self._h, slot, n_pos))
+
+    def prefill_form(self, n: int, start_pos: int = 0):
+        """How prefill / prefill_embeddings would run n rows at start_pos on this batch -> (n_chunks, n_block): passes of at most 512 rows, and how many
+        of them take block attention (64-query blocks); the others take one workgroup per (head, row).  Host arithmetic only (lmrs_batch_prefill_form)"""
+        a, b = C.c_uint32(), C.c_uint32()
+        _chk(lib().lmrs_batch_prefill_form(self._h, n, start_pos, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def debug_prefill_table(self, force: bool = True) -> None:
+        """Test / A-B aid: every prompt chunk of this PAGED batch takes the table pass from now on (force false: the library's rule again).  Refused
+        on a batch that is not paged (lmrs_batch_debug_prefill_table)"""
+        _chk(lib().lmrs_batch_debug_prefill_table(self._h, 1 if force else 0))
 
     def set_masks(self, slots, masks) -> None:
         """Allowed-token masks for `slots`, one row of `masks` each: bool [n, vocab_size] (true = allowed) or packed uint32 [n, W] (pack_mask).  While a

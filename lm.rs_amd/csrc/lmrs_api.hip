@@ -186,7 +186,7 @@ struct StepForm { int qa_mode = 0, split_chunks = 0; bool split_merged = false; 
 // masks (masks.bits != null): some output row of the pass belongs to a batch slot with an allowed-token mask (lmrs_batch_set_masks) - of[r] is the mask row of
 // output row r in the order the classifier sees the rows, -1 for none; h_of is its pinned source, which says on the host whether a slab has a masked row at all.
 struct MaskView { const uint32_t* bits = nullptr; int words = 0; const int* of = nullptr; const int* h_of = nullptr; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1394,18 +1394,25 @@ static int prefill_alloc(lmrs_ctx* c) {
 // RoPE + attention of a batch (transformer.rs:443-544 inside the sl loop) on the rows the qkv GEMM left in pf_q / pf_k / the V cache.  Block attention
 // (64-query blocks): the rotation rides in the score kernel's staging, which also writes the rotated keys to the cache (att_stage; round 6 - RoPE was a
 // launch of its own).  Otherwise (a few tokens, or score slabs beyond 1 GiB): the RoPE launch, then one workgroup per (token, head).
+// (the rule as a question of its own - lmrs_batch_prefill_form asks it without a pass: m rows of one sequence at p0 take block attention)
+static bool prefill_block_route(const lmrs_ctx* c, int m, int p0) {
+    AttnArgs t{};
+    t.head_size = (int)c->args.head_size; t.n_heads = c->att_dim / t.head_size; t.n_kv_heads = c->kv_dim / t.head_size; t.gemma = c->args.model_type == LMRS_GEMMA;
+    return attention_block_supported(t, m) && attention_block_scratch_floats(t.n_heads, m, p0 + m) <= ((size_t)1 << 28);    // <= 1 GiB of score slabs; longer contexts: per-token kernel
+}
+static int prefill_slabs(lmrs_ctx* c, size_t need) {                           // pf_att, grown to the pass's score slabs
+    if (need > c->pf_att_cap) {
+        if (c->pf_att) { HIP_OK(hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_att); c->pf_att = nullptr; c->pf_att_cap = 0; }
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->pf_att), need * 4)); c->pf_att_cap = need;
+    }
+    return 0;
+}
 static int prefill_attention(lmrs_ctx* c, AttnArgs& t, int m, int p0) {
-    if (attention_block_supported(t, m)) {
-        const size_t need = attention_block_scratch_floats(t.n_heads, m, p0 + m);
-        if (need <= ((size_t)1 << 28)) {                                       // <= 1 GiB of score slabs; longer contexts: per-token kernel
-            if (need > c->pf_att_cap) {
-                if (c->pf_att) { HIP_OK(hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_att); c->pf_att = nullptr; c->pf_att_cap = 0; }
-                HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->pf_att), need * 4)); c->pf_att_cap = need;
-            }
-            t.k_raw = c->pf_k;
-            HIP_OK(launch_attention_block(t, p0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
-            return 0;
-        }
+    if (prefill_block_route(c, m, p0)) {
+        if (prefill_slabs(c, attention_block_scratch_floats(t.n_heads, m, p0 + m))) return -1;
+        t.k_raw = c->pf_k;
+        HIP_OK(launch_attention_block(t, p0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
+        return 0;
     }
     HIP_OK(launch_rope_rows(c->pf_q, c->pf_k, t.k_cache, c->rope, t.n_heads, t.n_kv_heads, t.head_size, t.seq_len, t.layer, p0, m, c->stream));
     HIP_OK(launch_attention_rows(t, p0, m, c->stream));
@@ -1482,7 +1489,11 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
             // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
             const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
             HIP_OK(launch_paged_scatter(qkv, k_cache, v_cache, c->rope, rv, form.pages, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
-            HIP_OK(launch_paged_attention(t, rv, form.pages, m, form.max_T, c->stream));
+            if (form.block_pos0 >= 0) {
+                // one slot's consecutive rows, rotated and in its pages by now: 64-query blocks read every key and value row through the slot's page row
+                if (prefill_slabs(c, attention_block_scratch_floats(t.n_heads, m, form.block_pos0 + m))) return -1;
+                HIP_OK(launch_paged_attention_block(t, form.pages, form.block_row, form.block_pos0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
+            } else HIP_OK(launch_paged_attention(t, rv, form.pages, m, form.max_T, c->stream));
         } else if (form.rows) {
             // every row at its own position in its own slot: rotation, K / V rows into the slots, one attention workgroup per (head, row)
             HIP_OK(launch_rope_scatter_rows(c->pf_q, k_cache, v_cache, c->rope, form.rows, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
@@ -2034,6 +2045,11 @@ extern "C" int lmrs_generate_speculative(lmrs_ctx* c, const uint32_t* prompt, si
 static int debug_kv_row(lmrs_ctx* c, const float* k_cache, const float* v_cache, int which, uint32_t layer, uint32_t pos, float* out, uint32_t page_len = 0);   // (with lmrs_debug_kv below)
 // the ragged pass's table (lmrs_batch_forward_runs): RowTable's columns for kRunRowsMax rows, and sel - the table rows whose outputs were asked for, in output order
 constexpr uint32_t kWideBatchMax = 64;         // a wide batch's slots, rows and runs
+// fewest rows of a paged batch's prompt chunk that take block attention.  Measured by turns against the table pass (tools/batch_rate.py
+// --paged-prefill): at position 0, 16 / 32 / 64 rows by block attention take 1.9x / 1.45x / 1.02x the table pass's time on Llama-3.2-1B Q8_0 and 2.0x / 1.95x /
+// 1.06x on Gemma-2-2B Q4_0 (up to 47 rows the table pass also runs the weight-streaming GEMMs), 80 rows are within the turns' spread of it on both, 96 rows 0.93x
+// on Llama but 1.003x, just outside the spread, on Gemma; from 112 rows on both are faster outside the spread (0.90x / 0.96x)
+constexpr uint32_t kPagedBlockMin = 112;
 struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
 struct lmrs_batch {
     lmrs_ctx* c = nullptr; uint32_t n_slots = 0;
@@ -2057,6 +2073,7 @@ struct lmrs_batch {
     // page; the accounting (lmrs_pages.h), the device page table [n_slots][per_slot] and its pinned mirror
     PagePool* pool = nullptr; uint32_t page_len = 0; size_t page_floats = 0;
     uint32_t *ptab = nullptr, *h_ptab = nullptr;
+    bool pf_table = false;                              // lmrs_batch_debug_prefill_table: every prompt chunk takes the table pass
     // allowed-token masks (lmrs_batch_set_masks; allocated at the first call, all or nothing): the device block [n_slots][mask_words] and its pinned mirror,
     // which is also the upload's staging; n_allowed[s] = 0: slot s has no mask, n_masked = the slots that have one.  mask_of / h_mask_of: the per-call
     // column of PassForm::masks, written with the tables (batch_rows, runs_table); mask_live: this call uploaded it - some output row of the call is masked
@@ -2792,6 +2809,30 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     if (O && k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
     return 0;
 }
+// A prompt chunk of a paged batch - m rows of one slot from p0 on - takes block attention over the page table by prefill_attention's rule (and from
+// kPagedBlockMin rows on); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it
+static bool paged_block_route(const lmrs_batch* b, uint32_t m, uint32_t p0) {
+    return !b->pf_table && m >= kPagedBlockMin && prefill_block_route(b->c, (int)m, (int)p0);
+}
+extern "C" int lmrs_batch_prefill_form(const lmrs_batch* b, size_t n, uint32_t start_pos, uint32_t* n_chunks, uint32_t* n_block) {
+    const std::string what = "lmrs_batch_prefill_form: ";
+    if (!b || !n_chunks || !n_block) return fail(what + "NULL argument");
+    if ((size_t)start_pos + n > b->c->args.seq_len) return fail(what + "start_pos + n = " + std::to_string((size_t)start_pos + n) + " exceeds seq_len = " + std::to_string(b->c->args.seq_len));
+    uint32_t chunks = 0, block = 0;
+    for (size_t i0 = 0; i0 < n; i0 += kPrefillTokens, ++chunks) {
+        const uint32_t m = (uint32_t)std::min<size_t>(kPrefillTokens, n - i0), p0 = start_pos + (uint32_t)i0;
+        // (a contiguous batch sends a call of ONE row through the table pass; a longer call's last chunk of one row fails the rule by itself)
+        if (b->pool ? paged_block_route(b, m, p0) : n > 1 && prefill_block_route(b->c, (int)m, (int)p0)) ++block;
+    }
+    *n_chunks = chunks; *n_block = block;
+    return 0;
+}
+extern "C" int lmrs_batch_debug_prefill_table(lmrs_batch* b, int force) {
+    if (!b) return fail("lmrs_batch_debug_prefill_table: NULL argument");
+    if (!b->pool) return fail("lmrs_batch_debug_prefill_table: not a paged batch (lmrs_batch_create_paged)");
+    b->pf_table = force != 0;
+    return 0;
+}
 static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, const uint32_t* tokens, const float* embeddings, size_t n, uint32_t start_pos, float* residual) {
     lmrs_ctx* c = b->c;
     const size_t dim = c->args.dim;
@@ -2805,11 +2846,24 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
     for (size_t i0 = 0; i0 < n; i0 += kRunRowsMax) {
         const uint32_t m = (uint32_t)std::min<size_t>(kRunRowsMax, n - i0), p0 = start_pos + (uint32_t)i0, n_out = residual ? m : 0u;
         size_t R = 0, O = 0;
-        runs_table(b, 1, &slot, &p0, &m, &n_out, RunRows{&kind, tokens ? tokens + i0 : nullptr, embeddings}, &R, &O);
+        const bool block = paged_block_route(b, m, p0);
+        if (block) {                                     // block attention: the table's rows in POSITION order (row r = position p0 + r), no outputs
+            RunTable* h = b->h_runs;
+            for (uint32_t r = 0; r < m; ++r) { h->off[r] = b->off_of(slot); h->pos[r] = (int)(p0 + r); h->tok[r] = embeddings ? kRowFromStage | r : tokens[i0 + r]; }
+            b->mask_live = false;
+        } else runs_table(b, 1, &slot, &p0, &m, &n_out, RunRows{&kind, tokens ? tokens + i0 : nullptr, embeddings}, &R, &O);
         auto enqueue = [&]() -> int {
             if (embeddings) HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
             HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
             if (set_state(c, embeddings ? start_pos : 0, 0, win)) return -1;
+            if (block) {
+                // the GEMM forms of a contiguous batch's chunk (m >= 16: never the skinny ones), the qkv block and the scatter of the table pass
+                PassForm form; form.runs = b->runs_view(); form.qkv = b->runs_qkv; form.k_cache = b->kv; form.v_cache = b->kv + b->page_floats;
+                form.pages = b->page_view(); form.block_pos0 = (int)p0; form.block_row = slot;
+                if ((embeddings ? source_rows(c, form.runs.tok, b->embed_stage, (int)m) : token_rows(c, form.runs.tok, (int)m)) || prefill_pass(c, form, (int)m, (int)p0)) return -1;
+                if (residual) HIP_OK(hipMemcpyAsync(residual + i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));     // (position order already)
+                return 0;
+            }
             if (runs_pass(b, m, 0, 0, RowSink{0, 0, nullptr, 0}, embeddings ? b->embed_stage : nullptr)) return -1;
             if (residual) {                              // the table's rows are deepest first: sel puts them back in position order
                 HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)dim, (int)m, c->stream));

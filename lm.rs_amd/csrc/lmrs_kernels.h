@@ -278,6 +278,9 @@ struct PageView { const uint32_t* tab; int per_slot; int shift; size_t page_stri
 hipError_t launch_paged_scatter(float* qkv, float* k_pool, float* v_pool, const float* rope, RowView rows, PageView pv, int n_heads, int n_kv_heads, int hs,
                                 int layer, int n_rows, hipStream_t s);
 hipError_t launch_paged_attention(const AttnArgs& a, RowView rows, PageView pv, int n_rows, int max_T, hipStream_t s);
+// launch_attention_block over ONE slot's page row (table_row): n_tok consecutive rows from pos0 on, rotated and scattered already (launch_paged_scatter), so
+// every key is read from the pages.  a.q: the qkv block (row stride att + 2 kv); a.k_cache / a.v_cache: k_pool / v_pool; scratch, lds_keys, long_forms: as there
+hipError_t launch_paged_attention_block(const AttnArgs& a, PageView pv, unsigned table_row, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s);
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

@@ -185,3 +185,261 @@ hipError_t launch_paged_attention(const AttnArgs& a0, RowView rows, PageView pv,
     switch (a.head_size) { case 64: AP(64, false) case 96: AP(96, false) case 128: AP(128, false) default: return hipErrorInvalidValue; }
 #undef AP
 }
+
+// ------------------------------------------------------------------------------------------------
+// BLOCK attention over the page table: a prompt chunk of ONE slot - n_tok consecutive rows from pos0 on - through launch_attention_block's three launches
+// with the two readers of the K/V cache looked up.  q is rotated and every key and value row of the chunk is in the slot's pages already
+// (launch_paged_scatter over the chunk's rows), so the score launch is att_stage's `k_raw == nullptr` form and nothing here stores to a page.
+// Both readers walk the key axis in chunks of 64 keys (Gemma's short form: 32) that start at multiples of their length; page_len is a multiple of 64,
+// so a chunk or a tile lies in ONE page - one wave-uniform table lookup each.  Past-the-end keys are clamped to the block's last key, as in the
+// contiguous kernels, and the table index is formed from the CLAMPED key: the value phase prefetches up to four tiles past the end, whose tile number
+// may name an entry past the slot's row (or, for the last slot, past the table).  An entry of a position nobody wrote is page 0, the zero page.
+// The sums are att_scores_kernel's / att_scores_wide_kernel's / att_values_kernel's, built from the same helpers in the same order: the same bits.
+// qs: floats between query rows (the qkv block: att + 2 kv); tab: the slot's page row; k_pool / v_pool: the K and the V block of page 0.
+// ------------------------------------------------------------------------------------------------
+struct BlockPages { const uint32_t* tab; int shift; size_t page_stride; int layer; };
+template <int HS, int RS, int NK = 64, int NT = 256>
+__device__ __forceinline__ void block_paged_stage(float* qt, float* kt, const float* __restrict__ qrows, int qs, const float* __restrict__ k_pool, const BlockPages pg,
+                                                  int n_kv_heads, int h, int kvh, int qb, int cb, int bT, int n_tok) {
+    constexpr int HS4 = HS / 4;
+    const int tid = threadIdx.x, PL = 1 << pg.shift;
+    const int kc = cb < bT ? cb : bT - 1;                                     // the chunk's first key, clamped: its page holds every clamped key of the chunk
+    const float* kT = k_pool + (size_t)pg.tab[kc >> pg.shift] * pg.page_stride + ((size_t)pg.layer * n_kv_heads + kvh) * HS * (size_t)PL;   // [HS/4][page_len][4]
+    for (int f = tid; f < 64 * HS4; f += NT) {
+        const int r = f / HS4, c4 = f - r * HS4;
+        int qi = qb * kAttQB + r; qi = qi < n_tok ? qi : n_tok - 1;
+        *reinterpret_cast<float4*>(qt + r * RS + c4 * 4) = *reinterpret_cast<const float4*>(qrows + (size_t)qi * qs + h * HS + c4 * 4);
+        if (NK == 64 || f < NK * HS4) {
+            const int g = f / NK, kl = f % NK;
+            const int key = cb + kl < bT ? cb + kl : bT - 1;
+            *reinterpret_cast<float4*>(kt + kl * RS + g * 4) = *reinterpret_cast<const float4*>(kT + ((size_t)g * PL + (key & (PL - 1))) * 4);
+        }
+    }
+}
+template <int HS>
+__global__ __launch_bounds__(256) void block_paged_scores_kernel(const float* __restrict__ qrows, int qs, const float* __restrict__ k_pool, const BlockPages pg,
+                                                                 float* __restrict__ scratch, int n_heads, int n_kv_heads, int pos0, int n_tok, int Tmax) {
+    constexpr int RS = HS + 4, HS4 = HS / 4;
+    __shared__ __attribute__((aligned(16))) float qt[64 * RS];
+    __shared__ __attribute__((aligned(16))) float kt[64 * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), qb = gridDim.z - 1 - blockIdx.z, h = blockIdx.x;
+    const AttBlock b = att_block(qb, lane, pos0, n_tok);
+    const int cb = blockIdx.y * 64;
+    if (cb >= b.T) return;
+    const int kv_mul = n_heads / n_kv_heads, kvh = h / kv_mul;
+    float* S = scratch + ((size_t)h * gridDim.z + qb) * (size_t)Tmax * kAttQB + lane;
+    block_paged_stage<HS, RS>(qt, kt, qrows, qs, k_pool, pg, n_kv_heads, h, kvh, qb, cb, b.T, n_tok);
+    __syncthreads();
+    const int c0 = cb + wave * 16;
+    if (c0 >= b.T) return;
+    const int nk = b.T - c0 < 16 ? b.T - c0 : 16;
+    f32x4v q[HS4];
+#pragma unroll
+    for (int u = 0; u < HS4; ++u) q[u] = *reinterpret_cast<const f32x4v*>(qt + lane * RS + u * 4);
+    const float sqrt_hs = sqrtf((float)HS);
+    const float* kv = kt + wave * 16 * RS;
+    constexpr int UB = 2;
+    static_assert(HS4 % (2 * UB) == 0, "head size");
+#pragma unroll 1
+    for (int kk = 0; kk < nk; kk += 4) {
+        const float* kr = kv + kk * RS;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+        f32x4v ka[4][UB], kb[4][UB];
+        att_kread<UB, RS>(ka, kr, 0);
+#pragma unroll
+        for (int u0 = 0; u0 < HS4; u0 += 2 * UB) {
+            att_kread<UB, RS>(kb, kr, u0 + UB);
+            att_kdot<UB>(s0, s1, s2, s3, ka, q + u0);
+            asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+            if (u0 + 2 * UB < HS4) att_kread<UB, RS>(ka, kr, u0 + 2 * UB);
+            att_kdot<UB>(s0, s1, s2, s3, kb, q + u0 + UB);
+            asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+        }
+        const float sc[4] = {s0 / sqrt_hs, s1 / sqrt_hs, s2 / sqrt_hs, s3 / sqrt_hs};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (kk + j < nk) S[(size_t)(c0 + kk + j) * kAttQB] = sc[j];
+    }
+}
+// att_scores_wide_kernel (Gemma-2's 256-wide heads: two passes of 128 dims, the soft-cap, the window term) over the pages
+template <int HS, int NK, int NT>
+__global__ __launch_bounds__(NT) void block_paged_scores_wide_kernel(const float* __restrict__ qrows, int qs, const float* __restrict__ k_pool, const BlockPages pg,
+                                                                      float* __restrict__ scratch, const DevState* __restrict__ st, int n_heads, int n_kv_heads,
+                                                                      int pos0, int n_tok, int Tmax) {
+    constexpr int HP = HS / 2, RS = HS + 4, HP4 = HP / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* qt = reinterpret_cast<float*>(smem_raw);              // [64][RS]
+    float* kt = qt + 64 * RS;                                    // [NK][RS]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), qb = gridDim.z - 1 - blockIdx.z, h = blockIdx.x;
+    const AttBlock b = att_block(qb, lane, pos0, n_tok);
+    constexpr int KW = NK / (NT / 64);
+    static_assert(KW % 4 == 0 && KW >= 4 && 64 % NK == 0, "four score chains at a time; a chunk lies in one page");
+    const int cb = blockIdx.y * NK;
+    if (cb >= b.T) return;
+    const int kv_mul = n_heads / n_kv_heads, kvh = h / kv_mul;
+    float* S = scratch + ((size_t)h * gridDim.z + qb) * (size_t)Tmax * kAttQB + lane;
+    block_paged_stage<HS, RS, NK, NT>(qt, kt, qrows, qs, k_pool, pg, n_kv_heads, h, kvh, qb, cb, b.T, n_tok);
+    __syncthreads();
+    const int c0 = cb + wave * KW;
+    if (c0 >= b.T) return;
+    const int nk = b.T - c0 < KW ? b.T - c0 : KW;
+    const float* kv = kt + wave * KW * RS;
+    float part[KW];
+#pragma unroll
+    for (int i = 0; i < KW; ++i) part[i] = 0.0f;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        f32x4v q[HP4];
+#pragma unroll
+        for (int u = 0; u < HP4; ++u) q[u] = *reinterpret_cast<const f32x4v*>(qt + lane * RS + pass * HP + u * 4);
+#pragma unroll
+        for (int kq = 0; kq < KW / 4; ++kq) {
+            if (kq * 4 < nk) {
+                const float* kr = kv + kq * 4 * RS + pass * HP;
+                float s0 = part[kq * 4 + 0], s1 = part[kq * 4 + 1], s2 = part[kq * 4 + 2], s3 = part[kq * 4 + 3];
+                constexpr int UB = 2;
+                f32x4v ka[4][UB], kb[4][UB];
+                att_kread<UB, RS>(ka, kr, 0);
+#pragma unroll
+                for (int u0 = 0; u0 < HP4; u0 += 2 * UB) {
+                    att_kread<UB, RS>(kb, kr, u0 + UB);
+                    att_kdot<UB>(s0, s1, s2, s3, ka, q + u0);
+                    asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+                    if (u0 + 2 * UB < HP4) att_kread<UB, RS>(ka, kr, u0 + 2 * UB);
+                    att_kdot<UB>(s0, s1, s2, s3, kb, q + u0 + UB);
+                    asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+                }
+                part[kq * 4 + 0] = s0; part[kq * 4 + 1] = s1; part[kq * 4 + 2] = s2; part[kq * 4 + 3] = s3;
+            }
+        }
+    }
+    const float sqrt_hs = sqrtf((float)HS);
+    const int wb = st->win_base, wpos = wb >= 0 ? wb : (wb == kWinPerQuery ? b.p : pos0);
+#pragma unroll
+    for (int i = 0; i < KW; ++i) {
+        if (i < nk) {
+            const int t = c0 + i;
+            S[(size_t)t * kAttQB] = gemma_cap_window(part[i] / sqrt_hs, wpos, t);
+        }
+    }
+}
+
+// att_tile_load with the tile's value rows looked up: vh = v_pool + this layer's and kv head's offset inside a page (the slice's columns included)
+template <int NT, int SW, int NS, int NV>
+__device__ __forceinline__ void block_paged_tile_load(f32x4v (&rw)[NS], f32x4v (&rv)[NV], const float* Sb, const float* vh, const BlockPages pg, int kv_dim, int t, int T) {
+    constexpr int SW4 = SW / 4;
+    const int tid = threadIdx.x, k0 = t * 64, PL = 1 << pg.shift;
+    const int kc = k0 < T ? k0 : T - 1;                                       // the tile's first key, clamped (a prefetch past the end: the last key's page)
+    const float* vb = vh + (size_t)pg.tab[kc >> pg.shift] * pg.page_stride;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int f = tid + j * NT, kl = f >> 4, c4 = f & 15;
+        const int key = k0 + kl < T ? k0 + kl : T - 1;
+        const f32x4v w4 = *reinterpret_cast<const f32x4v*>(Sb + (size_t)key * kAttQB + c4 * 4);
+        rw[j] = k0 + kl < T ? w4 : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int f = tid + j * NT;
+        if (NV * NT == 64 * SW4 || f < 64 * SW4) {
+            const int kl = f / SW4, c4 = f - kl * SW4;
+            const int key = k0 + kl < T ? k0 + kl : T - 1;
+            rv[j] = *reinterpret_cast<const f32x4v*>(vb + (size_t)(key & (PL - 1)) * kv_dim + c4 * 4);
+        }
+    }
+}
+template <int HS, int NW, int DW>
+__global__ __launch_bounds__(NW * 64) void block_paged_values_kernel(const float* __restrict__ v_pool, const BlockPages pg, const float* __restrict__ scratch,
+                                                                     float* __restrict__ out, int n_heads, int n_kv_heads, int pos0, int n_tok, int Tmax) {
+    constexpr int NT = NW * 64, SW = NW * DW, NS = 64 * 16 / NT, NV = (16 * SW + NT - 1) / NT;
+    static_assert(HS % SW == 0 && DW % 4 == 0 && (64 * 16) % NT == 0, "slice geometry");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* sm = reinterpret_cast<float*>(smem_raw);
+    constexpr int TILE = 64 * 64 + 64 * SW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = blockIdx.x, sl = blockIdx.z;
+    const int qb = (sl & 1) ? (int)blockIdx.y : (int)(gridDim.y - 1 - blockIdx.y);
+    const AttBlock b = att_block(qb, lane, pos0, n_tok);
+    const int T = b.T, n_tiles = (T + 63) / 64;
+    const int kv_mul = n_heads / n_kv_heads, kvh = h / kv_mul, kv_dim = n_kv_heads * HS, att = n_heads * HS;
+    const float* Sb = scratch + ((size_t)h * gridDim.y + qb) * (size_t)Tmax * kAttQB;
+    const float* vh = v_pool + ((size_t)pg.layer << pg.shift) * kv_dim + kvh * HS + sl * SW;
+    f32x4v rwa[NS], rva[NV], rwb[NS], rvb[NV];
+    float acc[DW];
+#pragma unroll
+    for (int d = 0; d < DW; ++d) acc[d] = 0.0f;
+    block_paged_tile_load<NT, SW, NS, NV>(rwa, rva, Sb, vh, pg, kv_dim, 0, T);
+    att_tile_store<NT, SW, NS, NV>(rwa, rva, sm);
+    block_paged_tile_load<NT, SW, NS, NV>(rwa, rva, Sb, vh, pg, kv_dim, 1, T);
+    block_paged_tile_load<NT, SW, NS, NV>(rwb, rvb, Sb, vh, pg, kv_dim, 2, T);
+    lds_barrier();
+    for (int t = 0; t < n_tiles; t += 2) {
+        att_tile_compute<HS, DW, SW>(acc, sm, lane, wave, T - t * 64);
+        if (t + 1 < n_tiles) att_tile_store<NT, SW, NS, NV>(rwa, rva, sm + TILE);
+        block_paged_tile_load<NT, SW, NS, NV>(rwa, rva, Sb, vh, pg, kv_dim, t + 3, T);
+        lds_barrier();
+        if (t + 1 < n_tiles) {
+            att_tile_compute<HS, DW, SW>(acc, sm + TILE, lane, wave, T - (t + 1) * 64);
+            if (t + 2 < n_tiles) att_tile_store<NT, SW, NS, NV>(rwb, rvb, sm);
+            block_paged_tile_load<NT, SW, NS, NV>(rwb, rvb, Sb, vh, pg, kv_dim, t + 4, T);
+            lds_barrier();
+        }
+    }
+    if (b.live) {
+        float* ob = out + (size_t)b.i * att + h * HS + sl * SW + wave * DW;
+#pragma unroll
+        for (int g = 0; g < DW / 4; ++g) *reinterpret_cast<float4*>(ob + g * 4) = make_float4(acc[g * 4], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3]);
+    }
+}
+
+// launch_attention_block's choices - softmax in LDS or in memory, Gemma's forms by live64 and by slices - over one slot's page row.  a.q: the rotated qkv
+// block (row stride att + 2 kv), a.k_cache / a.v_cache: the pool's K and V block of page 0, a.out [n_tok][att]
+hipError_t launch_paged_attention_block(const AttnArgs& a, PageView pv, unsigned table_row, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s) {
+    const int T = pos0 + n_tok, nqb = (n_tok + kAttQB - 1) / kAttQB, nch = (T + 63) / 64;
+    if (!pv.tab || pv.shift < 6 || pv.per_slot < 1 || n_tok < 1 || pos0 < 0 || T > a.seq_len || ((T - 1) >> pv.shift) >= pv.per_slot) return hipErrorInvalidValue;
+    const int qs = (a.n_heads + 2 * a.n_kv_heads) * a.head_size;
+    const BlockPages pg{pv.tab + (size_t)table_row * pv.per_slot, pv.shift, pv.page_stride, a.layer};
+    const bool in_lds = T <= lds_keys;
+    const size_t sm = (kAttSW * 64 + kAttSQ + (in_lds ? (size_t)(T + 48) * kAttSQ : 0)) * sizeof(float);
+    allow_big_lds(reinterpret_cast<const void*>(att_softmax_kernel<true>));
+    auto softmax = [&]() {
+        if (in_lds) hipLaunchKernelGGL(att_softmax_kernel<true>, dim3(a.n_heads, nqb, kAttQB / kAttSQ), dim3(kAttSW * 64), sm, s, pos0, n_tok, scratch, T);
+        else hipLaunchKernelGGL(att_softmax_kernel<false>, dim3(a.n_heads, nqb, kAttQB / kAttSQ), dim3(kAttSW * 64), sm, s, pos0, n_tok, scratch, T);
+    };
+#define PV(HS_, NW_, DW_)                                                                                                             \
+    {                                                                                                                                 \
+        allow_big_lds(reinterpret_cast<const void*>(block_paged_values_kernel<HS_, NW_, DW_>));                                       \
+        hipLaunchKernelGGL((block_paged_values_kernel<HS_, NW_, DW_>), dim3(a.n_heads, nqb, HS_ / (NW_ * DW_)), dim3(NW_ * 64), 2 * (64 * 64 + 64 * NW_ * DW_) * sizeof(float), s, \
+                           (const float*)a.v_cache, pg, (const float*)scratch, a.out, a.n_heads, a.n_kv_heads, pos0, n_tok, T);       \
+        return hipGetLastError();                                                                                                     \
+    }
+#define PB(HS_, NW_, DW_)                                                                                                             \
+    {                                                                                                                                 \
+        hipLaunchKernelGGL((block_paged_scores_kernel<HS_>), dim3(a.n_heads, nch, nqb), dim3(256), 0, s, a.q, qs, (const float*)a.k_cache, pg, scratch,   \
+                           a.n_heads, a.n_kv_heads, pos0, n_tok, T);                                                                  \
+        softmax();                                                                                                                    \
+        PV(HS_, NW_, DW_)                                                                                                             \
+    }
+    if (a.gemma) {
+        if (a.head_size != 256) return hipErrorInvalidValue;
+        int live64 = 0;
+        for (int qb = 0; qb < nqb; ++qb) { const int last = qb * kAttQB + kAttQB - 1 < n_tok - 1 ? qb * kAttQB + kAttQB - 1 : n_tok - 1; live64 += (pos0 + last + 1 + 63) / 64; }
+        live64 *= a.n_heads;
+        if (live64 < 512 && !long_forms) {
+            constexpr size_t smem32 = (size_t)(64 + 32) * (256 + 4) * sizeof(float);
+            allow_big_lds(reinterpret_cast<const void*>(block_paged_scores_wide_kernel<256, 32, 512>));
+            hipLaunchKernelGGL((block_paged_scores_wide_kernel<256, 32, 512>), dim3(a.n_heads, (T + 31) / 32, nqb), dim3(512), smem32, s, a.q, qs, (const float*)a.k_cache, pg,
+                               scratch, a.st, a.n_heads, a.n_kv_heads, pos0, n_tok, T);
+        } else {
+            constexpr size_t wide_smem = (size_t)2 * 64 * (256 + 4) * sizeof(float);
+            allow_big_lds(reinterpret_cast<const void*>(block_paged_scores_wide_kernel<256, 64, 256>));
+            hipLaunchKernelGGL((block_paged_scores_wide_kernel<256, 64, 256>), dim3(a.n_heads, nch, nqb), dim3(256), wide_smem, s, a.q, qs, (const float*)a.k_cache, pg,
+                               scratch, a.st, a.n_heads, a.n_kv_heads, pos0, n_tok, T);
+        }
+        softmax();
+        if (a.n_heads * nqb * 4 < 256 && !long_forms) PV(256, 8, 4)
+        PV(256, 8, 8)
+    }
+    switch (a.head_size) { case 64: PB(64, 8, 4) case 96: PB(96, 4, 12) case 128: PB(128, 8, 8) default: return hipErrorInvalidValue; }
+#undef PB
+#undef PV
+}

@@ -62,7 +62,9 @@ int main(int argc, char** argv) {
         const std::vector<std::uint32_t> sys = tok.encode(system_text, true, false, false, mt);
         const std::uint32_t n_sys = static_cast<std::uint32_t>(sys.size());
         batch.prefill(0, sys, 0);                                          // once: every continuation refers to these pages
-        std::printf("system prompt: %u tokens in %u pages of %u positions; %u of %u pages free\n", n_sys, batch.slot_pages(0).held, PL, batch.pages().n_free, batch.pages().n_pages);
+        const auto form = batch.prefill_form(n_sys, 0);                    // how that call ran: chunks of at most 512 rows, and how many by block attention
+        std::printf("system prompt: %u tokens in %u pages of %u positions; %u of %u pages free; prefilled in %u chunk(s), %u by block attention\n", n_sys,
+                    batch.slot_pages(0).held, PL, batch.pages().n_free, batch.pages().n_pages, form.n_chunks, form.n_block);
         using Run = lmrs_host::Batch::Run;
         struct Live { std::size_t line; std::vector<std::uint32_t> feed; std::uint32_t pos, last; std::vector<std::uint32_t> out; };     // last: where the continuation ends
         std::vector<Live> slot(static_cast<std::size_t>(n_slots));         // slot[s].feed empty: the slot is free

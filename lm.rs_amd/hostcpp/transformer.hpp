@@ -171,6 +171,12 @@ public:
     SlotPages slot_pages(std::uint32_t slot) const { SlotPages p{}; check(lmrs_batch_slot_pages(b_, slot, &p.held, &p.shared)); return p; }   // (lmrs_batch_slot_pages)
     // keep positions [0, n_pos) of a slot (0 empties it): the pages behind them return to the pool once nobody holds them  (lmrs_batch_release)
     void release(std::uint32_t slot, std::uint32_t n_pos = 0) { check(lmrs_batch_release(b_, slot, n_pos)); }
+    // how prefill / prefill_embeddings would run n rows at start_pos: passes of at most 512 rows, and how many of them take block attention (64-query
+    // blocks; the others one workgroup per (head, row)).  Host arithmetic only, any batch  (lmrs_batch_prefill_form)
+    struct PrefillForm { std::uint32_t n_chunks, n_block; };
+    PrefillForm prefill_form(std::size_t n, std::uint32_t start_pos = 0) const { PrefillForm f{}; check(lmrs_batch_prefill_form(b_, n, start_pos, &f.n_chunks, &f.n_block)); return f; }
+    // test / A-B aid: every prompt chunk of this PAGED batch takes the table pass from now on (false: the library's rule)  (lmrs_batch_debug_prefill_table)
+    void debug_prefill_table(bool force = true) { check(lmrs_batch_debug_prefill_table(b_, force ? 1 : 0)); }
     // Allowed-token masks, state of a slot: bits = mask_words() words per slot, bit (t & 31) of word (t >> 5) set = token t allowed.  While a slot has a
     // mask every output row of it in any call here - logits, argmax, top-k, sampled token - comes from the row's logits with the disallowed entries -inf;
     // the mask stays until it is replaced or cleared  (lmrs_batch_set_masks / lmrs_batch_clear_masks / lmrs_batch_mask_info)

@@ -32,6 +32,8 @@ extern "C" {
     pub fn lmrs_batch_pages(b: *const LmrsBatch, page_len: *mut u32, n_pages: *mut u32, n_free: *mut u32) -> c_int;
     pub fn lmrs_batch_slot_pages(b: *const LmrsBatch, slot: u32, n_held: *mut u32, n_shared: *mut u32) -> c_int;
     pub fn lmrs_batch_release(b: *mut LmrsBatch, slot: u32, n_pos: u32) -> c_int;
+    pub fn lmrs_batch_prefill_form(b: *const LmrsBatch, n: usize, start_pos: u32, n_chunks: *mut u32, n_block: *mut u32) -> c_int;
+    pub fn lmrs_batch_debug_prefill_table(b: *mut LmrsBatch, force: c_int) -> c_int;
 }
 
 /// What a run of `Batch::forward_runs_embed` feeds: token ids, or rows of `dim` floats taken as `Transformer::fill_kv_cache` takes them.
@@ -107,6 +109,20 @@ impl<'t, 'a> Batch<'t, 'a> {
     /// Keep positions `[0, n_pos)` of `slot` (0 empties it); the pages behind them return to the pool once nobody holds them.
     pub fn release(&mut self, slot: u32, n_pos: u32) {
         check(unsafe { lmrs_batch_release(self.b, slot, n_pos) });
+    }
+
+    /// How `prefill` / `prefill_embeddings` would run `n` rows at `start_pos`: (passes of at most 512 rows, how many of them take block attention -
+    /// 64-query blocks; the others take one workgroup per (head, row)).  Host arithmetic only, on any batch.
+    pub fn prefill_form(&self, n: usize, start_pos: u32) -> (u32, u32) {
+        let (mut c, mut k) = (0u32, 0u32);
+        check(unsafe { lmrs_batch_prefill_form(self.b, n, start_pos, &mut c, &mut k) });
+        (c, k)
+    }
+
+    /// Test / A-B aid: every prompt chunk of this paged batch takes the table pass from now on (`false`: the library's rule).  Panics on a batch that
+    /// is not paged.
+    pub fn debug_prefill_table(&mut self, force: bool) {
+        check(unsafe { lmrs_batch_debug_prefill_table(self.b, force as c_int) });
     }
 
     /// The most rows a call takes: 16, or 64 for a wide batch.

@@ -12,7 +12,11 @@ host time of 64 synchronous calls / 64, median of 5 after 2 warm-ups.  That call
 lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: the two trees of an A/B run by turns.  BATCH_RATE_OUT names the file written.
        python tools/batch_rate.py --paged [model] [q8_0|q4_0]
 --paged: a PAGED batch (lmrs_batch_create_paged) against the wide batch of the same build, the forms by turns (paged_main below)
-       (writes profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt, profiles/batch_paged_phi35.txt)"""
+       (writes profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt, profiles/batch_paged_phi35.txt)
+       python tools/batch_rate.py --paged-prefill [model] [q8_0|q4_0]
+--paged-prefill: lmrs_batch_prefill of 16 .. 512 tokens on a wide batch, on paged batches (block attention over the page table from 16 rows on) and on the
+same paged batches with lmrs_batch_debug_prefill_table (every chunk through the table pass: the routing before), the forms by turns (paged_prefill_main below)
+       (writes profiles/batch_paged_prefill_llama1b.txt, profiles/batch_paged_prefill_gemma2b_q4.txt)"""
 import os
 import statistics
 import sys
@@ -180,8 +184,8 @@ def paged_main(argv):
                 ms = (time.perf_counter() - t0) * 1e3
                 held = 64 * 1000 * pos_bytes if pl is None else (b.pages()[1] - b.pages()[2]) * pl * pos_bytes
                 say(f"  {name:9s}  {ms:8.2f} ms   {held / 1e6:9.1f} MB of written or held K/V" + ("" if pl is None else f" ({b.pages()[1] - b.pages()[2]} pages)"))
-            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): the table pass of a paged batch "
-                "against the block attention of a contiguous one")
+            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): block attention on every form, "
+                "over the page table on a paged batch (--paged-prefill: every length by turns, and the table pass it replaced)")
             for name, pl in forms:
                 b = batches[name]
 
@@ -195,7 +199,76 @@ def paged_main(argv):
     finish()
 
 
+PREFILL_OUT = {("llama-3.2-1b", S.Q8_0): "batch_paged_prefill_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_paged_prefill_gemma2b_q4.txt"}
+PREFILL_CASES = [(16, 0), (32, 0), (64, 0), (80, 0), (96, 0), (112, 0), (128, 0), (256, 0), (512, 0), (512, 512)]   # (tokens, start position); 80 .. 112: around the crossover
+
+
+def paged_prefill_main(argv):
+    """--paged-prefill [model] [q8_0|q4_0]: host wall time of the synchronous lmrs_batch_prefill call into slot 0, in one process, five forms by turns,
+    three turns, median of 5 calls after 1 warm-up a turn: (a) the wide batch; (b) paged batches of page_len 64 and 256 under the library's routing; (c) the
+    same two with lmrs_batch_debug_prefill_table(1) - every chunk through the table pass, one workgroup per (head, row).  Per form and length the median of
+    its turns (fastest .. slowest turn), lmrs_batch_prefill_form's answer, and whether the forms leave the same last K row."""
+    model = argv[0] if argv else "llama-3.2-1b"
+    qname = argv[1] if len(argv) > 1 else "q8_0"
+    qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True); lines.append(s)
+
+    img = S.build_image(model, qt, 1234)
+    m = lmrs_amd.Transformer(img)
+    say(f"python tools/batch_rate.py --paged-prefill {model} {qname}")
+    say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
+    say("lmrs_batch_prefill into slot 0, host wall time of the synchronous call: five forms by turns, three turns, median of 5 calls after 1 warm-up a turn; "
+        "per form the median of its turns (fastest .. slowest turn); form = lmrs_batch_prefill_form's (chunks, of them block attention)")
+    forms = [("wide", None, False), ("paged 64", 64, False), ("paged 256", 256, False), ("paged 64 table", 64, True), ("paged 256 table", 256, True)]
+    prompt = S.prompt_tokens(model, 1024, 100)
+    batches = {}
+    for name, pl, table in forms:
+        b = lmrs_amd.Batch(m, 2, wide=True) if pl is None else lmrs_amd.Batch(m, 2, page_len=pl, n_pages=2 * (1024 // pl))
+        if table:
+            b.debug_prefill_table(True)
+        batches[name] = b
+    nl = m.args.n_layers
+    for n, start in PREFILL_CASES:
+        toks = prompt[start:start + n]
+        turns, last = {name: [] for name, _, _ in forms}, {}
+        for b in batches.values():
+            if start:
+                b.prefill(0, prompt[:start], 0)
+        for _ in range(3):
+            for name, _pl, _t in forms:
+                b = batches[name]
+
+                def call():
+                    t0 = time.perf_counter(); b.prefill(0, toks, start)
+                    return None, time.perf_counter() - t0
+                _, us, _lo, _hi = timed(call, reps=5, warm=1)
+                turns[name].append(us / 1e3)
+        for name, _pl, _t in forms:
+            last[name] = batches[name].kv_row(0, 0, nl - 1, start + n - 1).view(np.uint32).copy()
+        w = statistics.median(turns["wide"])
+        for name, pl, table in forms:
+            t = turns[name]
+            note = f"{statistics.median(t) / w:5.2f}x wide"
+            if pl is not None and not table:
+                old = turns[name + " table"]
+                note += f"   {statistics.median(t) / statistics.median(old):5.2f}x its table pass; slowest turn below the table pass's fastest: {max(t) < min(old)}"
+            say(f"  {n:3d} tokens at {start:3d}, {name:15s} form {batches[name].prefill_form(n, start)}  {statistics.median(t):8.3f} ms ({min(t):.3f} .. {max(t):.3f})   {note}")
+        say(f"      the five forms leave the same last K row: {all((last[name] == last['wide']).all() for name, _, _ in forms)}")
+    for b in batches.values():
+        b.close()
+    name = PREFILL_OUT.get((model, qt))
+    path = os.environ.get("BATCH_RATE_OUT") or (os.path.join(ROOT, "profiles", name) if name else None)
+    if path:
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--paged-prefill":
+        return paged_prefill_main(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--wide":
         return wide_main(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--paged":
