@@ -26,10 +26,12 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/lmrs_hip.h"
+#include "lmrs_buf.h"
 #include "lmrs_device_math.h"
 #include "lmrs_format.h"
 #include "lmrs_kernels.h"
@@ -48,6 +50,14 @@ static int fail(const std::string& m) { g_err = m; return -1; }
     } while (0)
 
 extern "C" const char* lmrs_last_error(void) { return g_err.c_str(); }
+// The owners of device and pinned memory (lmrs_buf.h): the only callers of the runtime's free functions in this file besides the arenas and pfx_*
+static thread_local hipError_t g_alloc_err = hipSuccess;                       // what the last obtain returned
+struct DevMem { static void* obtain(size_t bytes) { void* p = nullptr; return (g_alloc_err = hipMalloc(&p, bytes)) == hipSuccess ? p : nullptr; } static void release(void* p) { (void)hipFree(p); } };
+struct PinMem { static void* obtain(size_t bytes) { void* p = nullptr; return (g_alloc_err = hipHostMalloc(&p, bytes, hipHostMallocDefault)) == hipSuccess ? p : nullptr; } static void release(void* p) { (void)hipHostFree(p); } };
+template <class T> using DevBuf = Buf<T, DevMem>;
+template <class T> using PinBuf = Buf<T, PinMem>;
+// the message of an allocation that failed where the call reports the runtime's own error (the others say "out of memory" and clear it)
+static int alloc_failed(const char* what) { return fail(std::string(what) + ": " + hipGetErrorString(g_alloc_err)); }
 namespace lmrs { int text_fail(const char* msg) { return fail(msg); } }       // lmrs_text.cpp reports through the same message slot
 
 namespace {
@@ -77,17 +87,17 @@ struct lmrs_ctx {
     uint32_t* tokens = nullptr; DevState* st = nullptr;
     unsigned long long* dbg = nullptr; int dbg_node = 0;     // LMRS_DEBUG_TIMELINE=1: 8 stamps per kernel node
     // pinned host
-    unsigned long long* samp_keys = nullptr; float* samp_pairs = nullptr; void* h_pairs = nullptr; int samp_cap = 0;   // lmrs_forward_sample: the device sort of top-p candidates (allocated on first use)
-    float* h_logits = nullptr; uint32_t* h_tok = nullptr; DevState* h_st = nullptr; unsigned h_st_next = 0;   // h_st: ring of kStateSlots pinned slots (an async copy may still be reading the previous one)
+    DevBuf<unsigned long long> samp_keys; DevBuf<float> samp_pairs; PinBuf<char> h_pairs; int samp_cap = 0;   // lmrs_forward_sample: the device sort of top-p candidates (allocated on first use; samp_cap != 0: the set stands)
+    PinBuf<float> h_logits; PinBuf<uint32_t> h_tok; PinBuf<DevState> h_st; unsigned h_st_next = 0;   // h_st: ring of kStateSlots pinned slots (an async copy may still be reading the previous one)
     // the step graphs by form (StepForm: qkv + attention mode 0..2 | 3 + split-attention bucket 0..3 | 7 + bucket: the split form with its scores in the
     // qkv launch) and steps per launch ([0] one, [1] multi_k):
     // step_graph captures a missing one; the graph of position 0's form (primary_graph) is what says "this context replays graphs"
     hipGraphExec_t g_steps[11][2] = {}, g_layers = nullptr;
     // long contexts: from att_split_pos on a step's attention is the split pair (256-key chunks: 4, 8, 16, 32 by context bucket), scores in att_S
-    float* att_S = nullptr; int att_split_pos = 0;
+    DevBuf<float> att_S; int att_split_pos = 0;
     bool split_merged = false;                             // the split form's scores ride in the qkv launch (launch_qkv_scores): one GPU, quantised files, LMRS_ATT_SPLIT_MERGED
     // batched forward_layer (fill_kv_cache): device buffers for kPrefillTokens tokens, allocated on first use
-    float *pf_x = nullptr, *pf_q = nullptr, *pf_k = nullptr, *pf_ao = nullptr, *pf_h = nullptr, *pf_xs = nullptr, *pf_t = nullptr; int8_t* pf_xq = nullptr; float* pf_att = nullptr; size_t pf_att_cap = 0;
+    DevBuf<float> pf_x, pf_q, pf_k, pf_ao, pf_h, pf_xs, pf_t; DevBuf<int8_t> pf_xq; DevBuf<float> pf_att;     // (pf_att: grown to a pass's score slabs, count() floats)
     bool pf_ready = false;                                 // every prefill buffer above is allocated
     // batched prefill on row shards (plan "tp", Q8_0): the gathered blocks of a token batch - per shard [n_tok x slice int8 | n_tok x slice / 128 scales],
     // pfb_att / pfb_h bytes apart; inside the peer-to-peer arena when that is the transport (peers write them), ordinary memory for RCCL
@@ -96,7 +106,7 @@ struct lmrs_ctx {
     float* x2 = nullptr; bool gemma_fused = false;           // Gemma: second residual buffer; norm+add steps folded into the consuming GEMV prologues
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     Switches sw;                                   // the environment switches, read at create (lmrs_switches.h)
-    std::vector<float*> scales_t;                  // the layers' transposed scale copies (owned)
+    std::vector<DevBuf<float>> scales_t;           // the layers' transposed scale copies
     int att_dim = 0, kv_dim = 0, cls_grid = 0;     // att_dim / kv_dim: THIS shard's query / key-value widths
     int part_stride = 0;                           // floats between two shards' argmax partials: 2 * cls_grid rounded up to 16 bytes (the push transport copies 16 bytes per lane;
                                                    // Llama-3.2-1B on 8 shards has 501 partials per shard)
@@ -120,7 +130,7 @@ struct lmrs_ctx {
     unsigned *xflags = nullptr, *xseq = nullptr; int* xerr = nullptr; int ex_slot = 0; bool xarena_is_ipc[kMaxWorld] = {};
     double last_fill_ms = -1.0;                    // device time of the last batched fill_kv_cache between its upload and its download (lmrs_last_fill_ms)
     bool err_queued = false;                       // the error word's copy to h_err rides in front of the call's own synchronise (queue_err)
-    int* err = nullptr; int* h_err = nullptr;      // error word of the bounded in-launch waits (merged qkv + attention launch, classifier tail)
+    int* err = nullptr; PinBuf<int> h_err;         // error word of the bounded in-launch waits (merged qkv + attention launch, classifier tail)
     // ---- merged qkv + attention launch (launch_qkv_attn): per-layer {value, tag} granules, the step sequence number the tags are
     // made of (bumped by the last kernel of every step, never reset), and the graph of the separate kernels for the steps it does not cover
     // what enqueue_layer launches is StepForm::qa_mode: 0 the separate kernels, 1 merged with one workgroup per head (pos < qa_max_T), 2 merged with
@@ -134,11 +144,11 @@ struct lmrs_ctx {
     int inj_fail_connect = 0, inj_stall_seg = -1; long long inj_stall_ticks = 0;      // lmrs_debug_inject
     // lmrs_forward_tokens / lmrs_score_tokens (allocated on first use): the [sc_rows][vocab] logits block, the reduction's chunk summaries,
     // its per-position results on the device and their pinned host copy
-    float* sc_logits = nullptr; int sc_rows = 0; ScorePart* sc_part = nullptr; double* sc_lp = nullptr; uint32_t* sc_idx = nullptr; char* h_sc = nullptr;
+    DevBuf<float> sc_logits; int sc_rows = 0; DevBuf<ScorePart> sc_part; DevBuf<double> sc_lp; DevBuf<uint32_t> sc_idx; PinBuf<char> h_sc;
     // lmrs_score_tokens_topk / lmrs_forward_topk (allocated on first use, for tk_rows rows of tk_k candidates): the selection's keys and counts between
     // its two launches, the seq_len x tk_k results (index, value) and the seq_len target ranks, and their pinned host copy
-    unsigned long long* tk_cand = nullptr; uint32_t* tk_cnt = nullptr; uint32_t* tk_idx = nullptr; float* tk_val = nullptr; uint32_t* tk_rank = nullptr;
-    char* h_tk = nullptr; int tk_rows = 0, tk_k = 0;
+    DevBuf<unsigned long long> tk_cand; DevBuf<uint32_t> tk_cnt, tk_idx; DevBuf<float> tk_val; DevBuf<uint32_t> tk_rank;
+    PinBuf<char> h_tk; int tk_rows = 0, tk_k = 0;            // (tk_rows != 0: the set stands - alloc_all)
 
     template <class T> T* alloc(size_t count) {
         size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
@@ -203,8 +213,7 @@ StepForm step_form_for(const lmrs_ctx* c, uint32_t pos, bool merged = true) {
 // the score scratch of the split attention, allocated when the first split step is about to be enqueued
 int split_scratch(lmrs_ctx* c, StepForm f) {
     if (!f.split_chunks || c->att_S) return 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->att_S), attention_split_scratch_floats(c->att_dim / (int)c->args.head_size, (int)c->args.seq_len) * 4));
-    return 0;
+    return c->att_S.alloc(attention_split_scratch_floats(c->att_dim / (int)c->args.head_size, (int)c->args.seq_len)) ? 0 : alloc_failed("split attention scores: hipMalloc");
 }
 
 // RoPE terms, transformer.rs:446-482 (libm powf/cosf/sinf/logf exactly where the reference calls them).
@@ -1096,10 +1105,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
         HCK(hipMemcpyAsync(c->rope, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
         HCK(hipStreamSynchronize(c->stream));       // tab goes out of scope
     }
-    HCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_logits), V * 4, hipHostMallocDefault));
-    HCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_tok), ((size_t)a.seq_len + 8) * 4, hipHostMallocDefault));
-    HCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_st), kStateSlots * sizeof(DevState), hipHostMallocDefault));
-    HCK(hipHostMalloc(reinterpret_cast<void**>(&c->h_err), 4, hipHostMallocDefault));
+    if (!alloc_all({{c->h_logits, V}, {c->h_tok, (size_t)a.seq_len + 8}, {c->h_st, kStateSlots}, {c->h_err, 1}})) { alloc_failed("pinned host buffers: hipHostMalloc"); return cleanup(); }
     CK(set_state(c, 0, 0));
     HCK(hipStreamSynchronize(c->stream));
     if (a.model_type == LMRS_GEMMA && !sharded && !f32w) {
@@ -1164,33 +1170,15 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     return 0;
 }
 
-static void topk_free(lmrs_ctx* c) {
-    for (void** p : {(void**)&c->tk_cand, (void**)&c->tk_cnt, (void**)&c->tk_idx, (void**)&c->tk_val, (void**)&c->tk_rank}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (c->h_tk) { (void)hipHostFree(c->h_tk); c->h_tk = nullptr; }
-    c->tk_rows = c->tk_k = 0;
-}
-
+// What is not plain memory goes here, in this order; the context's owners (lmrs_buf.h) free theirs in `delete c`, on the context's device
 extern "C" void lmrs_destroy(lmrs_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     destroy_step_graphs(c);
-    if (c->att_S) (void)hipFree(c->att_S);
     if (c->g_layers) (void)hipGraphExecDestroy(c->g_layers);
-    for (void* q : {(void*)c->pf_x, (void*)c->pf_q, (void*)c->pf_k, (void*)c->pf_ao, (void*)c->pf_h, (void*)c->pf_xq, (void*)c->pf_xs, (void*)c->pf_t, (void*)c->pf_att}) if (q) (void)hipFree(q);
-    for (float* q : c->scales_t) if (q) (void)hipFree(q);
-    for (void* q : {(void*)c->sc_logits, (void*)c->sc_part, (void*)c->sc_lp, (void*)c->sc_idx}) if (q) (void)hipFree(q);
-    if (c->h_sc) (void)hipHostFree(c->h_sc);
-    topk_free(c);
     if (c->pfx_owned) { if (c->pfx_att) (void)hipFree(c->pfx_att); if (c->pfx_h) (void)hipFree(c->pfx_h); if (c->pfx_x) (void)hipFree(c->pfx_x); }
     if (c->comm) ncclCommDestroy(c->comm);
-    if (c->h_logits) (void)hipHostFree(c->h_logits);
-    if (c->samp_keys) (void)hipFree(c->samp_keys);
-    if (c->samp_pairs) (void)hipFree(c->samp_pairs);
-    if (c->h_pairs) (void)hipHostFree(c->h_pairs);
-    if (c->h_tok) (void)hipHostFree(c->h_tok);
-    if (c->h_st) (void)hipHostFree(c->h_st);
-    if (c->h_err) (void)hipHostFree(c->h_err);
     for (int w = 0; w < kMaxWorld; ++w) if (c->xarena_is_ipc[w] && c->peer_base[w]) (void)hipIpcCloseMemHandle(c->peer_base[w]);
     if (c->xarena) (void)hipFree(c->xarena);
     if (c->arena) (void)hipFree(c->arena);
@@ -1257,15 +1245,11 @@ extern "C" int lmrs_forward_argmax(lmrs_ctx* c, uint32_t token, uint32_t pos, ui
 // the device sort's buffers (launch_sample_topp_sort): keys, the count word behind them, the sorted pairs and their pinned copy - once, for the whole
 // vocabulary of n entries, at the first call that sorts N keys
 static int samp_sort_alloc(lmrs_ctx* c, int N, size_t n) {
-    if (c->samp_keys && c->samp_cap >= N) return 0;
-    if (c->samp_keys) { (void)hipFree(c->samp_keys); c->samp_keys = nullptr; }
-    if (c->samp_pairs) { (void)hipFree(c->samp_pairs); c->samp_pairs = nullptr; }
-    if (c->h_pairs) { (void)hipHostFree(c->h_pairs); c->h_pairs = nullptr; }
+    if (c->samp_cap >= N) return 0;
     int cap = sample_sort_min_n();
     while ((size_t)cap < n) cap <<= 1;                                               // once, for the whole vocabulary
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->samp_keys), (size_t)cap * 8 + 256));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->samp_pairs), (size_t)cap * 8));
-    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->h_pairs), (size_t)cap * 8 + 8, hipHostMallocDefault));
+    c->samp_cap = 0;
+    if (!alloc_all({{c->samp_keys, (size_t)cap + 32}, {c->samp_pairs, (size_t)cap * 2}, {c->h_pairs, (size_t)cap * 8 + 8}})) return alloc_failed("top-p sort buffers: hipMalloc");
     c->samp_cap = cap;
     return 0;
 }
@@ -1304,9 +1288,9 @@ extern "C" int lmrs_forward_sample(lmrs_ctx* c, uint32_t token, uint32_t pos, lm
     unsigned* count = reinterpret_cast<unsigned*>(c->samp_keys + c->samp_cap);           // (the word behind the keys)
     HIP_OK(launch_sample_topp_sort(c->logits, (int)n, sum, cutoff, N, c->samp_keys, count, c->samp_pairs, c->stream));
     HIP_OK(hipMemcpyAsync(c->h_pairs, c->samp_pairs, n0 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(c->h_pairs) + (size_t)c->samp_cap * 8, count, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(c->h_pairs + (size_t)c->samp_cap * 8, count, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
-    unsigned dev_n0 = 0; memcpy(&dev_n0, reinterpret_cast<char*>(c->h_pairs) + (size_t)c->samp_cap * 8, 4);
+    unsigned dev_n0 = 0; memcpy(&dev_n0, c->h_pairs + (size_t)c->samp_cap * 8, 4);
     if (dev_n0 != n0) return fail("lmrs_forward_sample: the device found " + std::to_string(dev_n0) + " top-p candidates, the host " + std::to_string(n0));
     return lmrs_sampler_exps_finish(sampler, c->h_logits, c->h_pairs, next);
 }
@@ -1350,20 +1334,16 @@ static int prefill_alloc(lmrs_ctx* c) {
     const size_t B = kPrefillTokens, wide = std::max<size_t>(std::max<size_t>(a.dim, a.hidden_dim), (size_t)std::max(c->att_dim, c->att_full));
     const bool own_blocks = c->tp_prefill && c->comm && !c->pfx_att;      // (peer-to-peer shards: the blocks are part of the exchange arena, laid out at create)
     if (own_blocks) { c->pfb_att = prefill_tp_block((size_t)c->att_dim); c->pfb_h = prefill_tp_block((size_t)c->hid_l); c->pfb_x = pad256((size_t)kPrefillTokens * c->dim_l * 4); c->pfx_owned = true; }
-    struct Want { void** p; size_t bytes; } want[] = {
-        {reinterpret_cast<void**>(&c->pf_x), B * a.dim * 4}, {reinterpret_cast<void**>(&c->pf_q), B * c->att_dim * 4},
-        {reinterpret_cast<void**>(&c->pf_k), B * c->kv_dim * 4}, {reinterpret_cast<void**>(&c->pf_ao), B * c->att_dim * 4},
-        {reinterpret_cast<void**>(&c->pf_h), B * a.hidden_dim * 4}, {reinterpret_cast<void**>(&c->pf_xq), B * wide},
-        {reinterpret_cast<void**>(&c->pf_xs), B * (wide / 128) * 4}, {reinterpret_cast<void**>(&c->pf_t), a.model_type == LMRS_GEMMA ? B * a.dim * 4 : 0},
-        {reinterpret_cast<void**>(&c->pfx_att), own_blocks ? c->world * c->pfb_att : 0}, {reinterpret_cast<void**>(&c->pfx_h), own_blocks ? c->world * c->pfb_h : 0},
-        {reinterpret_cast<void**>(&c->pfx_x), own_blocks && !c->rep_out ? c->world * c->pfb_x : 0}};
-    for (const Want& w : want) {
-        if (!w.bytes || *w.p) continue;
-        const hipError_t e = hipMalloc(w.p, w.bytes);
-        if (e != hipSuccess) {                       // all or nothing: a half-allocated set must never reach the kernels
-            for (const Want& u : want) if (u.bytes && *u.p) { (void)hipFree(*u.p); *u.p = nullptr; }      // (bytes == 0: not ours to free - Gemma's pf_t absent, blocks inside the exchange arena)
-            return fail(std::string("prefill buffers: hipMalloc: ") + hipGetErrorString(e));
-        }
+    // all or nothing (alloc_all), Gemma's pf_t and the shards' own blocks with the set: the blocks stay raw pointers - on peer-to-peer shards they are
+    // views into the exchange arena
+    struct Want { char** p; size_t bytes; } blocks[] = {{&c->pfx_att, c->world * c->pfb_att}, {&c->pfx_h, c->world * c->pfb_h}, {&c->pfx_x, c->rep_out ? 0 : c->world * c->pfb_x}};
+    bool ok = alloc_all({{c->pf_x, B * a.dim}, {c->pf_q, B * c->att_dim}, {c->pf_k, B * c->kv_dim}, {c->pf_ao, B * c->att_dim}, {c->pf_h, B * a.hidden_dim}, {c->pf_xq, B * wide},
+                         {c->pf_xs, B * (wide / 128)}}) && (a.model_type != LMRS_GEMMA || c->pf_t.alloc(B * a.dim));
+    for (const Want& w : blocks) if (ok && own_blocks && w.bytes) ok = (*w.p = static_cast<char*>(DevMem::obtain(w.bytes))) != nullptr;
+    if (!ok) {
+        c->pf_x.reset(); c->pf_q.reset(); c->pf_k.reset(); c->pf_ao.reset(); c->pf_h.reset(); c->pf_xq.reset(); c->pf_xs.reset(); c->pf_t.reset();
+        for (const Want& w : blocks) if (own_blocks && *w.p) { DevMem::release(*w.p); *w.p = nullptr; }
+        return alloc_failed("prefill buffers: hipMalloc");
     }
     // The layers' weight scales transposed, [group][row], once: a ring GEMM fetches a group's scales of 64 rows as 256 consecutive bytes instead of 4 bytes
     // from each of 64 lines (GemmArgs::ws_ld; +1/32 of the quantised weights' bytes).  A failed allocation only means the row-major scales stay in use.
@@ -1375,9 +1355,10 @@ static int prefill_alloc(lmrs_ctx* c) {
         bool ok = true;
         auto tr = [&](const float* src, int rows, int groups) -> const float* {
             if (!ok) return nullptr;
-            float* d = nullptr;
-            if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)rows * groups * 4) != hipSuccess) { (void)hipGetLastError(); ok = false; return nullptr; }
-            c->scales_t.push_back(d);
+            DevBuf<float> t;
+            if (!t.alloc((size_t)rows * groups)) { (void)hipGetLastError(); ok = false; return nullptr; }
+            float* d = t;
+            c->scales_t.push_back(std::move(t));
             if (launch_transpose_scales(src, rows, groups, d, c->stream) != hipSuccess) { ok = false; return nullptr; }
             return d;
         };
@@ -1401,11 +1382,9 @@ static bool prefill_block_route(const lmrs_ctx* c, int m, int p0) {
     return attention_block_supported(t, m) && attention_block_scratch_floats(t.n_heads, m, p0 + m) <= ((size_t)1 << 28);    // <= 1 GiB of score slabs; longer contexts: per-token kernel
 }
 static int prefill_slabs(lmrs_ctx* c, size_t need) {                           // pf_att, grown to the pass's score slabs
-    if (need > c->pf_att_cap) {
-        if (c->pf_att) { HIP_OK(hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_att); c->pf_att = nullptr; c->pf_att_cap = 0; }
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->pf_att), need * 4)); c->pf_att_cap = need;
-    }
-    return 0;
+    if (need <= c->pf_att.count()) return 0;
+    if (c->pf_att) HIP_OK(hipStreamSynchronize(c->stream));
+    return c->pf_att.alloc(need) ? 0 : alloc_failed("prefill score slabs: hipMalloc");
 }
 static int prefill_attention(lmrs_ctx* c, AttnArgs& t, int m, int p0) {
     if (prefill_block_route(c, m, p0)) {
@@ -1518,7 +1497,7 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
             if (all_gather(c->pf_h, hid_l, c->pfx_h, c->pfb_h)) return -1;
         } else if (gemm_q8_hq_fused(dim, 2 * hid, m, q4 != 0)) {
             // (the quantiser of h in w1/w3's epilogue: int8 rows + scales in the buffer the f32 rows would have taken)
-            g.hq = reinterpret_cast<int8_t*>(c->pf_h); g.hs = reinterpret_cast<float*>(reinterpret_cast<char*>(c->pf_h) + (size_t)kPrefillTokens * hid);
+            g.hq = reinterpret_cast<int8_t*>(c->pf_h.get()); g.hs = reinterpret_cast<float*>(reinterpret_cast<char*>(c->pf_h.get()) + (size_t)kPrefillTokens * hid);
             g.hs_ld = xld;
             HIP_OK(launch_gemm_q8(g, gemma ? EPI_GELU_Q : EPI_SWIGLU_Q, c->stream));
             g.xq = g.hq; g.xs = g.hs;
@@ -1723,25 +1702,17 @@ static bool score_batched_ok(const lmrs_ctx* c, size_t n) {
 // rows whose reductions one call can hold: a token run is at most seq_len long, a ragged batch pass (lmrs_batch_forward_runs) kPrefillTokens rows of any positions
 static size_t score_cap(const lmrs_ctx* c) { return std::max<size_t>(c->args.seq_len, kPrefillTokens); }
 
-// all or nothing, like prefill_alloc; `block`: the logits block too (forward_tokens and the batched path need it, token-by-token scoring does not)
+// one set of alloc_all's (whole or absent: any member speaks for it); `block`: the logits block too (forward_tokens and the batched path need it, token-by-token scoring does not)
 static int score_alloc(lmrs_ctx* c, bool block) {
     const size_t V = c->args.vocab_size, T = score_cap(c), S = (size_t)score_chunks((int)V);
     const size_t rows = std::min<size_t>(kPrefillTokens, std::max<size_t>(1, kScoreBlockBytes / (V * 4)));
-    if (!c->sc_part) {
-        bool ok = hipMalloc(reinterpret_cast<void**>(&c->sc_part), rows * S * sizeof(ScorePart)) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void**>(&c->sc_lp), T * 8) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void**>(&c->sc_idx), T * 4) == hipSuccess;
-        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_sc), T * 12, hipHostMallocDefault) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            for (void** p : {(void**)&c->sc_part, (void**)&c->sc_lp, (void**)&c->sc_idx}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-            if (c->h_sc) { (void)hipHostFree(c->h_sc); c->h_sc = nullptr; }
-            return fail("scoring buffers: out of memory");
-        }
+    if (!c->h_sc && !alloc_all({{c->sc_part, rows * S}, {c->sc_lp, T}, {c->sc_idx, T}, {c->h_sc, T * 12}})) {
+        (void)hipGetLastError();
+        return fail("scoring buffers: out of memory");
     }
     if (block && !c->sc_logits) {
-        if (hipMalloc(reinterpret_cast<void**>(&c->sc_logits), rows * V * 4) != hipSuccess) {
-            (void)hipGetLastError(); c->sc_logits = nullptr;
+        if (!c->sc_logits.alloc(rows * V)) {
+            (void)hipGetLastError();
             return fail("scoring logits block (" + std::to_string(rows * V * 4 >> 20) + " MiB): out of memory");
         }
         c->sc_rows = (int)rows;
@@ -1756,21 +1727,14 @@ static int topk_check_k(uint32_t k, uint32_t vocab) {
     return 0;
 }
 
-// all or nothing, like score_alloc; made anew when a call asks for more rows per launch or a larger k than the buffers hold
+// alloc_all's, like score_alloc's; made anew when a call asks for more rows per launch or a larger k than the buffers hold
 static int topk_alloc(lmrs_ctx* c, int rows, int k) {
-    if (c->tk_cand && rows <= c->tk_rows && k <= c->tk_k) return 0;
+    if (c->tk_rows && rows <= c->tk_rows && k <= c->tk_k) return 0;
     rows = std::max(rows, c->tk_rows); k = std::max(k, c->tk_k);
-    topk_free(c);
+    c->tk_rows = c->tk_k = 0;
     const size_t T = score_cap(c), S = (size_t)score_chunks((int)c->args.vocab_size);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&c->tk_cand), (size_t)rows * S * k * 8) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_cnt), (size_t)rows * S * 4) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_idx), T * k * 4) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_val), T * k * 4) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->tk_rank), T * 4) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_tk), T * k * 8 + T * 4, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
+    if (!alloc_all({{c->tk_cand, (size_t)rows * S * k}, {c->tk_cnt, (size_t)rows * S}, {c->tk_idx, T * k}, {c->tk_val, T * k}, {c->tk_rank, T}, {c->h_tk, T * k * 8 + T * 4}})) {
         (void)hipGetLastError();
-        topk_free(c);
         return fail("top-k buffers: out of memory");
     }
     c->tk_rows = rows; c->tk_k = k;
@@ -1782,7 +1746,7 @@ struct TopkOut { uint32_t k; uint32_t* idx; float* logprob; uint32_t* rank; };
 
 // The pinned h_sc in its two halves (score_alloc): score_cap doubles for the log-probabilities, then score_cap indices
 struct HostScores { double* lp; uint32_t* idx; };
-static HostScores host_scores(const lmrs_ctx* c) { return {reinterpret_cast<double*>(c->h_sc), reinterpret_cast<uint32_t*>(c->h_sc + score_cap(c) * 8)}; }
+static HostScores host_scores(const lmrs_ctx* c) { return {reinterpret_cast<double*>(c->h_sc.get()), reinterpret_cast<uint32_t*>(c->h_sc + score_cap(c) * 8)}; }
 
 // What becomes of the logits rows of a run of n tokens in c->tokens[start_pos ..).  out_logits != null: they go to the host as they are
 // (lmrs_forward_tokens); else the reduction of every row - the next token's log-probability to c->sc_lp, sample_argmax to c->sc_idx - and with k the
@@ -2051,35 +2015,38 @@ constexpr uint32_t kWideBatchMax = 64;         // a wide batch's slots, rows and
 // on Llama but 1.003x, just outside the spread, on Gemma; from 112 rows on both are faster outside the spread (0.90x / 0.96x)
 constexpr uint32_t kPagedBlockMin = 112;
 struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
+// The buffers of a sampled call (sample_set_alloc; rows != 0: the set stands, for that many rows): the rows' sampler table and its pinned source,
+// launch_sample_rows' scratch, the result blocks ([rows][vocab + 1] words: {token, n0}, then the candidates) and the pinned copy of their heads (head_words each)
+struct SampleSet {
+    DevBuf<SampleRow> tab; PinBuf<SampleRow> h_tab; DevBuf<float> scratch; DevBuf<unsigned long long> out; PinBuf<unsigned long long> h_heads;
+    size_t rows = 0, head_words = 0;
+};
 struct lmrs_batch {
     lmrs_ctx* c = nullptr; uint32_t n_slots = 0;
     uint32_t width = kRowTableMax;                      // the most rows / runs a call takes: 16, or kWideBatchMax for lmrs_batch_create_wide's batches
-    float* kv = nullptr; size_t slot_floats = 0;        // [n_slots][K cache | V cache], slot_floats floats each: one allocation
-    RowTable *tab = nullptr, *h_tab = nullptr;          // the pass's row table and its pinned source
-    uint32_t *tokens = nullptr;                         // a prefill's token run (seq_len)
-    uint32_t *out = nullptr, *h_out = nullptr;          // generate_greedy: [n_new][n] results of the passes, and their pinned copy (seq_len x 16)
-    RunTable *runs = nullptr, *h_runs = nullptr;        // forward_runs: the long table and its pinned source,
-    float *runs_qkv = nullptr, *runs_x = nullptr;       // its [kRunRowsMax][att + 2 kv] qkv block and the [kRunRowsMax][dim] rows picked for the classifier
-    // forward_sample (allocated at the first call with a sampled row, all or nothing): the rows' sampler table and its pinned source, launch_sample_rows'
-    // scratch, the result blocks ([kRowTableMax][vocab + 1] words: {token, n0}, then the candidates) and the pinned copy of their heads (head_words each)
-    SampleRow *samp_tab = nullptr, *h_samp_tab = nullptr; float* samp_scratch = nullptr;
-    unsigned long long *samp_out = nullptr, *h_samp_heads = nullptr; size_t head_words = 0;
-    // forward_runs_sample's own set of the same (rs_rows rows, grown on demand), and the flat rows' keys / sorted pairs with their pinned copy (cs_words words)
-    SampleRow *rs_tab = nullptr, *h_rs_tab = nullptr; float* rs_scratch = nullptr;
-    unsigned long long *rs_out = nullptr, *h_rs_heads = nullptr; size_t rs_rows = 0, rs_head_words = 0;
-    unsigned long long *cs_keys = nullptr, *h_cs_pairs = nullptr; size_t cs_words = 0;
-    float* embed_stage = nullptr;                       // the embedding rows of a ragged pass, [kRunRowsMax][dim] in caller order (allocated at the first call that has one)
+    // Every buffer is an owner (lmrs_buf.h): `delete b` frees them; the sets made after create are alloc_all's - whole or absent, their size word says which
+    DevBuf<float> kv; size_t slot_floats = 0;           // [n_slots][K cache | V cache], slot_floats floats each: one allocation
+    DevBuf<RowTable> tab; PinBuf<RowTable> h_tab;       // the pass's row table and its pinned source
+    DevBuf<uint32_t> tokens;                            // a prefill's token run (seq_len)
+    DevBuf<uint32_t> out; PinBuf<uint32_t> h_out;       // generate_greedy: [n_new][n] results of the passes, and their pinned copy (seq_len x 16)
+    DevBuf<RunTable> runs; PinBuf<RunTable> h_runs;     // forward_runs: the long table and its pinned source,
+    DevBuf<float> runs_qkv, runs_x;                     // its [kRunRowsMax][att + 2 kv] qkv block and the [kRunRowsMax][dim] rows picked for the classifier
+    // forward_sample's set (kRowTableMax rows, made at the first call with a sampled row) and forward_runs_sample's own (whole sixteens up to the batch's width,
+    // made anew when a call needs more), and the flat rows' keys / sorted pairs of the ragged call with their pinned copy (cs_words words)
+    SampleSet samp, rs;
+    DevBuf<unsigned long long> cs_keys; PinBuf<unsigned long long> h_cs_pairs; size_t cs_words = 0;
+    DevBuf<float> embed_stage;                          // the embedding rows of a ragged pass, [kRunRowsMax][dim] in caller order (allocated at the first call that has one)
     // a paged batch (lmrs_batch_create_paged): kv is the pool - page p's K block at kv + p * 2 * page_floats, its V block page_floats behind, page 0 the zero
     // page; the accounting (lmrs_pages.h), the device page table [n_slots][per_slot] and its pinned mirror
-    PagePool* pool = nullptr; uint32_t page_len = 0; size_t page_floats = 0;
-    uint32_t *ptab = nullptr, *h_ptab = nullptr;
+    std::unique_ptr<PagePool> pool; uint32_t page_len = 0; size_t page_floats = 0;
+    DevBuf<uint32_t> ptab; PinBuf<uint32_t> h_ptab;
     bool pf_table = false;                              // lmrs_batch_debug_prefill_table: every prompt chunk takes the table pass
-    // allowed-token masks (lmrs_batch_set_masks; allocated at the first call, all or nothing): the device block [n_slots][mask_words] and its pinned mirror,
+    // allowed-token masks (lmrs_batch_set_masks; made at the first call, mask_words != 0 from then on): the device block [n_slots][mask_words] and its pinned mirror,
     // which is also the upload's staging; n_allowed[s] = 0: slot s has no mask, n_masked = the slots that have one.  mask_of / h_mask_of: the per-call
     // column of PassForm::masks, written with the tables (batch_rows, runs_table); mask_live: this call uploaded it - some output row of the call is masked
-    uint32_t *masks = nullptr, *h_masks = nullptr; size_t mask_words = 0;
+    DevBuf<uint32_t> masks; PinBuf<uint32_t> h_masks; size_t mask_words = 0;
     uint32_t n_allowed[kWideBatchMax] = {}; uint32_t n_masked = 0;
-    int *mask_of = nullptr, *h_mask_of = nullptr; bool mask_live = false;
+    DevBuf<int> mask_of; PinBuf<int> h_mask_of; bool mask_live = false;
     int mask_row_of(uint32_t slot) const { return n_allowed[slot] ? (int)slot : -1; }
     MaskView mask_view() const { return mask_live ? MaskView{masks, (int)mask_words, mask_of, h_mask_of} : MaskView{}; }
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
@@ -2100,21 +2067,6 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->c->device);
     (void)hipStreamSynchronize(b->c->stream);
-    if (b->ptab) (void)hipFree(b->ptab);
-    if (b->h_ptab) (void)hipHostFree(b->h_ptab);
-    if (b->masks) (void)hipFree(b->masks);
-    if (b->mask_of) (void)hipFree(b->mask_of);
-    if (b->h_masks) (void)hipHostFree(b->h_masks);
-    if (b->h_mask_of) (void)hipHostFree(b->h_mask_of);
-    delete b->pool;
-    for (void* p : {(void*)b->kv, (void*)b->tab, (void*)b->tokens, (void*)b->out, (void*)b->runs, (void*)b->runs_qkv, (void*)b->runs_x, (void*)b->samp_tab, (void*)b->samp_scratch, (void*)b->samp_out}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->rs_tab, (void*)b->rs_scratch, (void*)b->rs_out, (void*)b->cs_keys, (void*)b->embed_stage}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->h_rs_tab, (void*)b->h_rs_heads, (void*)b->h_cs_pairs}) if (p) (void)hipHostFree(p);
-    if (b->h_samp_tab) (void)hipHostFree(b->h_samp_tab);
-    if (b->h_samp_heads) (void)hipHostFree(b->h_samp_heads);
-    if (b->h_tab) (void)hipHostFree(b->h_tab);
-    if (b->h_runs) (void)hipHostFree(b->h_runs);
-    if (b->h_out) (void)hipHostFree(b->h_out);
     delete b;
 }
 
@@ -2140,30 +2092,21 @@ static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const s
     b->c = c; b->n_slots = n_slots; b->width = width; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
     b->page_len = page_len; b->page_floats = (size_t)a.n_layers * page_len * c->kv_dim;
     const size_t bytes = page_len ? ((size_t)n_pages + 1) * 2 * b->page_floats * 4 : (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
-    bool ok = hipMalloc(reinterpret_cast<void**>(&b->kv), bytes) == hipSuccess;                         // all or nothing: one allocation
-    if (!ok) {
-        (void)hipGetLastError(); b->kv = nullptr; lmrs_batch_destroy(b);
+    if (!b->kv.alloc(bytes / 4)) {                                                                       // all or nothing: one allocation
+        (void)hipGetLastError(); lmrs_batch_destroy(b);
         if (page_len) return fail(name + ": " + std::to_string(bytes) + " bytes of K/V pages for " + std::to_string(n_pages) + " pages (and the zero page): out of memory");
         return fail(name + ": " + std::to_string(bytes) + " bytes of K/V caches for " + std::to_string(n_slots) + " slots: out of memory");
     }
     if (page_len) {
         const uint32_t per_slot = (a.seq_len + page_len - 1) / page_len;
-        b->pool = new PagePool(n_slots, per_slot, page_len, n_pages);
-        ok = hipMalloc(reinterpret_cast<void**>(&b->ptab), (size_t)n_slots * per_slot * 4) == hipSuccess;
-        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_ptab), (size_t)n_slots * per_slot * 4, hipHostMallocDefault) == hipSuccess;
-        if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": page table: out of memory"); }
+        b->pool.reset(new PagePool(n_slots, per_slot, page_len, n_pages));
+        if (!alloc_all({{b->ptab, (size_t)n_slots * per_slot}, {b->h_ptab, (size_t)n_slots * per_slot}})) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": page table: out of memory"); }
         memset(b->h_ptab, 0, (size_t)n_slots * per_slot * 4);
     }
-    ok = hipMalloc(reinterpret_cast<void**>(&b->tab), sizeof(RowTable)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->tokens), T * 4) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->out), T * width * 4) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_tab), sizeof(RowTable), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_out), T * width * 4, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs), sizeof(RunTable)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_runs), sizeof(RunTable), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_qkv), (size_t)kRunRowsMax * (c->att_dim + 2 * c->kv_dim) * 4) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->runs_x), (size_t)kRunRowsMax * a.dim * 4) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": row table and result buffers: out of memory"); }
+    if (!alloc_all({{b->tab, 1}, {b->tokens, T}, {b->out, T * width}, {b->h_tab, 1}, {b->h_out, T * width}, {b->runs, 1}, {b->h_runs, 1},
+                    {b->runs_qkv, (size_t)kRunRowsMax * (c->att_dim + 2 * c->kv_dim)}, {b->runs_x, (size_t)kRunRowsMax * a.dim}})) {
+        (void)hipGetLastError(); lmrs_batch_destroy(b); return fail(name + ": row table and result buffers: out of memory");
+    }
     // (a paged batch: the zero page and the table - every entry names the zero page; a page is cleared when it is claimed)
     if (page_len && hipMemsetAsync(b->ptab, 0, (size_t)n_slots * b->pool->per_slot() * 4, c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail(name + ": clearing the page table failed"); }
     if (hipMemsetAsync(b->kv, 0, page_len ? 2 * b->page_floats * 4 : bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { lmrs_batch_destroy(b); return fail(name + ": clearing the caches failed"); }
@@ -2182,6 +2125,8 @@ extern "C" int lmrs_batch_width(const lmrs_batch* b, uint32_t* width) {
 // A batch call that fails after it began to enqueue drains the stream before it returns: nothing queued may still read the pinned row table or the
 // state slot that the next call rewrites (ctx and batch stay usable); the failure's message stands
 static int batch_failed(lmrs_ctx* c) { (void)hipStreamSynchronize(c->stream); c->err_queued = false; return -1; }
+// the closing frame of a batch call: its enqueue, drained where that failed, then finish_call
+template <class F> static int batch_call(lmrs_ctx* c, F&& enqueue) { return enqueue() ? batch_failed(c) : finish_call(c); }
 // the one DevState of a batch call (only Gemma's kernels read it: every row tests the window against its own position)
 static int batch_state(lmrs_ctx* c) { return set_state(c, 0, 0, pass_win_base(c, 0, true)); }
 
@@ -2190,16 +2135,10 @@ static int batch_state(lmrs_ctx* c) { return set_state(c, 0, 0, pass_win_base(c,
 // disallowed entries -inf: classify_rows' one launch (mask_rows_kernel) between the soft-cap and the sinks, for the slabs that have a masked row.  No
 // arithmetic on an allowed logit changes; a batch with no mask set runs exactly the launches it ran before.
 static int masks_alloc(lmrs_batch* b) {
-    if (b->masks) return 0;
+    if (b->mask_words) return 0;
     const size_t W = ((size_t)b->c->args.vocab_size + 31) / 32, bytes = (size_t)b->n_slots * W * 4;
-    bool ok = hipMalloc(reinterpret_cast<void**>(&b->masks), bytes) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_masks), bytes, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->mask_of), (size_t)kRunRowsMax * sizeof(int)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_mask_of), (size_t)kRunRowsMax * sizeof(int), hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
+    if (!alloc_all({{b->masks, bytes / 4}, {b->h_masks, bytes / 4}, {b->mask_of, kRunRowsMax}, {b->h_mask_of, kRunRowsMax}})) {
         (void)hipGetLastError();
-        for (void** p : {(void**)&b->masks, (void**)&b->mask_of}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-        for (void** p : {(void**)&b->h_masks, (void**)&b->h_mask_of}) if (*p) { (void)hipHostFree(*p); *p = nullptr; }
         return fail("lmrs_batch_set_masks: " + std::to_string(bytes) + " bytes of masks for " + std::to_string(b->n_slots) + " slots (and as many pinned): out of memory");
     }
     memset(b->h_masks, 0, bytes);
@@ -2366,8 +2305,7 @@ extern "C" int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* 
         PassForm form; form.skinny = n < kShortPassMax; form.k_cache = b->k_of(slot); form.v_cache = b->v_of(slot);
         return prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, b->tokens + i0, m); }, [](size_t, int) { return 0; });
     };
-    if (enqueue()) return batch_failed(c);
-    return finish_call(c);
+    return batch_call(c, enqueue);
 }
 
 extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_slot, uint32_t n_pos) {
@@ -2528,7 +2466,7 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
 // The mask column of a call with n output rows, beside its table: uploaded - and the pass's forms carry it (lmrs_batch::mask_view) - only when one of the
 // rows is masked; a batch without masks enqueues nothing here
 static int masks_enqueue(lmrs_batch* b, size_t n) {
-    if (!b->n_masked || !std::any_of(b->h_mask_of, b->h_mask_of + n, [](int m) { return m >= 0; })) return 0;
+    if (!b->n_masked || !std::any_of(b->h_mask_of.get(), b->h_mask_of + n, [](int m) { return m >= 0; })) return 0;
     HIP_OK(hipMemcpyAsync(b->mask_of, b->h_mask_of, n * sizeof(int), hipMemcpyHostToDevice, b->c->stream));
     b->mask_live = true;
     return 0;
@@ -2561,8 +2499,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
             HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
             return 0;
         };
-        if (enqueue()) return batch_failed(c);
-        if (finish_call(c)) return -1;
+        if (batch_call(c, enqueue)) return -1;
         memcpy(argmax, hs.idx, n * 4);
         return 0;
     }
@@ -2575,8 +2512,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
         HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
         return 0;
     };
-    if (enqueue()) return batch_failed(c);
-    if (finish_call(c)) return -1;
+    if (batch_call(c, enqueue)) return -1;
     for (uint32_t r = 0; r < n; ++r) {
         argmax[order[r]] = b->h_out[r];
         if (logits) memcpy(logits + (size_t)order[r] * V, rows.data() + (size_t)r * V, V * 4);
@@ -2612,8 +2548,7 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
         HIP_OK(hipMemcpyAsync(b->h_out, b->out, (size_t)n_new * n * 4, hipMemcpyDeviceToHost, c->stream));
         return 0;
     };
-    if (enqueue()) return batch_failed(c);
-    if (finish_call(c)) return -1;
+    if (batch_call(c, enqueue)) return -1;
     for (uint32_t j = 0; j < n_new; ++j) for (uint32_t r = 0; r < n; ++r) out_tokens[(size_t)(wide ? r : (uint32_t)order[r]) * n_new + j] = b->h_out[(size_t)j * n + r];
     if (seconds) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *seconds = ms * 1e-3; }
     return 0;
@@ -2631,24 +2566,51 @@ static SampleRowsArgs sample_rows_args(float* rows, int n_rows, int ld, int n, c
     float* sum = scratch + (size_t)n_rows * (kSampleRowsGrid + 1);
     return SampleRowsArgs{rows, n_rows, ld, n, tab, argmax, scratch, sum, reinterpret_cast<unsigned*>(sum + n_rows), out};
 }
-static int batch_sample_alloc(lmrs_batch* b) {
-    if (b->samp_out) return 0;
-    const lmrs_ctx* c = b->c;
-    const size_t V = c->args.vocab_size, R = kRowTableMax, head = 1 + std::min<size_t>(V, c->sw.topp_sort_min);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&b->samp_tab), R * sizeof(SampleRow)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_samp_tab), R * sizeof(SampleRow), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->samp_scratch), sample_scratch_floats(R) * 4) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_samp_heads), R * head * 8, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->samp_out), R * (V + 1) * 8) == hipSuccess;      // (last: what every later call tests)
-    if (!ok) {
+// A sampling set for R rows (alloc_all: whole or absent, one that grows is made anew); oom: the call's out-of-memory message, from the result blocks' bytes and R
+static int sample_set_alloc(const lmrs_ctx* c, SampleSet& s, size_t R, std::string (*oom)(size_t bytes, size_t rows)) {
+    const size_t V = c->args.vocab_size, head = 1 + std::min<size_t>(V, c->sw.topp_sort_min);
+    s.rows = 0;
+    if (!alloc_all({{s.tab, R}, {s.h_tab, R}, {s.scratch, sample_scratch_floats(R)}, {s.h_heads, R * head}, {s.out, R * (V + 1)}})) {
         (void)hipGetLastError();
-        for (void** p : {(void**)&b->samp_tab, (void**)&b->samp_scratch, (void**)&b->samp_out}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-        for (void** p : {(void**)&b->h_samp_tab, (void**)&b->h_samp_heads}) if (*p) { (void)hipHostFree(*p); *p = nullptr; }
-        return fail("lmrs_batch_forward_sample: " + std::to_string(R * (V + 1) * 8) + " bytes of candidate buffers: out of memory");
+        return fail(oom(R * (V + 1) * 8, R));
     }
-    b->head_words = head;
+    s.rows = R; s.head_words = head;
     return 0;
 }
+// The samplers of a sampled call, checked before any device work (`what` opens every message, noun: "row" / "run"): i's parameters to par[i], topp[i] by
+// sampler.rs:117-126, *sampled: some row has a temperature.  A NULL sampler is refused (need_all) or skipped - that run has no output
+static int samplers_check(const lmrs_ctx* c, const std::string& what, const char* noun, bool need_all, uint32_t n, lmrs_sampler* const* samplers,
+                          SampleRow* par, bool* topp, bool* sampled) {
+    const size_t V = c->args.vocab_size;
+    *sampled = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        topp[i] = false;
+        const std::string at = what + noun + " " + std::to_string(i) + ": ";
+        if (!samplers[i]) { if (need_all) return fail(at + "the sampler is NULL"); continue; }
+        uint32_t vs = 0;
+        if (lmrs_sampler_info(samplers[i], &vs, &par[i].temperature, &par[i].top_p, &par[i].rnd)) return -1;
+        if (vs != V) return fail(at + "the sampler was made for another vocabulary size (" + std::to_string(vs) + ", the model has " + std::to_string(V) + ")");
+        topp[i] = par[i].temperature != 0.0f && !(par[i].top_p <= 0.0f || par[i].top_p >= 1.0f);         // sampler.rs:117-126
+        *sampled = *sampled || par[i].temperature != 0.0f;
+        // (a top-p sampler carries its candidate vector from call to call: two rows of one call cannot both be "the next call")
+        for (uint32_t j = 0; j < i && topp[i]; ++j)
+            if (samplers[j] == samplers[i]) return fail(at + "the top-p sampler of " + noun + " " + std::to_string(j) + " appears twice (it carries state from call to call)");
+    }
+    if (*sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
+    return 0;
+}
+// The sampled tail of a pass whose n output rows stand in sc_logits: the sampler table up, launch_sample_rows over the rows in place, and THE transfer -
+// every row's {token, n0} and the first head_words - 1 of its candidates
+static int sample_enqueue(lmrs_ctx* c, const SampleSet& s, size_t n, int max_rows = kSampleRowsMax) {
+    const size_t V = c->args.vocab_size, head = s.head_words;
+    HIP_OK(hipMemcpyAsync(s.tab, s.h_tab, n * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(launch_sample_rows(sample_rows_args(c->sc_logits, (int)n, (int)V, (int)V, s.tab, c->sc_idx, s.scratch, s.out), c->stream, max_rows));
+    HIP_OK(hipMemcpy2DAsync(s.h_heads, head * 8, s.out, (V + 1) * 8, head * 8, n, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+// a row's head in the pinned copy: its first word is {token in the low half, n0 in the high half}, the candidates follow
+struct SampleHead { const unsigned long long* cand; uint32_t tok, n0; };
+static SampleHead sample_head(const SampleSet& s, size_t row) { const unsigned long long* w = s.h_heads + row * s.head_words; return {w + 1, (uint32_t)w[0], (uint32_t)(w[0] >> 32)}; }
 
 extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
                                          lmrs_sampler* const* samplers, uint32_t* next) {
@@ -2660,46 +2622,29 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
     if (batch_rows(b, "lmrs_batch_forward_sample", kRowTableMax, n, slot, tokens, pos, 1, order)) return -1;
     const size_t V = c->args.vocab_size;
     SampleRow par[kRowTableMax]; bool topp[kRowTableMax]; bool sampled = false;
-    for (uint32_t i = 0; i < n; ++i) {
-        const std::string row = what + "row " + std::to_string(i) + ": ";
-        if (!samplers[i]) return fail(row + "the sampler is NULL");
-        uint32_t vs = 0;
-        if (lmrs_sampler_info(samplers[i], &vs, &par[i].temperature, &par[i].top_p, &par[i].rnd)) return -1;
-        if (vs != V) return fail(row + "the sampler was made for another vocabulary size (" + std::to_string(vs) + ", the model has " + std::to_string(V) + ")");
-        topp[i] = par[i].temperature != 0.0f && !(par[i].top_p <= 0.0f || par[i].top_p >= 1.0f);         // sampler.rs:117-126
-        sampled = sampled || par[i].temperature != 0.0f;
-        // (a top-p sampler carries its candidate vector from call to call: two rows of one call cannot both be "the next call")
-        for (uint32_t j = 0; j < i && topp[i]; ++j)
-            if (samplers[j] == samplers[i]) return fail(row + "the top-p sampler of row " + std::to_string(j) + " appears twice (it carries state from call to call)");
-    }
-    if (sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
+    if (samplers_check(c, what, "row", /*need_all=*/true, n, samplers, par, topp, &sampled)) return -1;
     HIP_OK(hipSetDevice(c->device));
-    if (sampled && batch_sample_alloc(b)) return -1;
+    if (sampled && !b->samp.rows && sample_set_alloc(c, b->samp, kRowTableMax, [](size_t bytes, size_t) {
+            return "lmrs_batch_forward_sample: " + std::to_string(bytes) + " bytes of candidate buffers: out of memory"; })) return -1;
     if (pages_claim_rows(b, what, n, slot, pos, nullptr, 1)) return -1;
-    for (uint32_t r = 0; r < n; ++r) { at[order[r]] = (int)r; if (sampled) b->h_samp_tab[r] = par[order[r]]; }
-    const size_t head = b->head_words;
+    for (uint32_t r = 0; r < n; ++r) { at[order[r]] = (int)r; if (sampled) b->samp.h_tab[r] = par[order[r]]; }
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
         if (masks_enqueue(b, n) || batch_state(c)) return -1;
         if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx; the rows stay in sc_logits
         if (!sampled) { HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
-        HIP_OK(hipMemcpyAsync(b->samp_tab, b->h_samp_tab, n * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(launch_sample_rows(sample_rows_args(c->sc_logits, (int)n, (int)V, (int)V, b->samp_tab, c->sc_idx, b->samp_scratch, b->samp_out), c->stream));
-        // THE transfer: every row's {token, n0} and the first head - 1 of its candidates
-        HIP_OK(hipMemcpy2DAsync(b->h_samp_heads, head * 8, b->samp_out, (V + 1) * 8, head * 8, n, hipMemcpyDeviceToHost, c->stream));
-        return 0;
+        return sample_enqueue(c, b->samp, n);
     };
-    if (enqueue()) return batch_failed(c);
-    if (finish_call(c)) return -1;
+    if (batch_call(c, enqueue)) return -1;
     if (!sampled) { for (uint32_t r = 0; r < n; ++r) next[order[r]] = b->h_out[r]; return 0; }
     for (uint32_t i = 0; i < n; ++i) {                   // in row order: the host samplers move as n calls of lmrs_forward_sample would move them
         const int r = at[i];
-        const unsigned long long* blk = b->h_samp_heads + (size_t)r * head;
-        const uint32_t tok = (uint32_t)blk[0], n0 = (uint32_t)(blk[0] >> 32);
-        if (!topp[i]) { next[i] = tok; continue; }
+        const SampleHead h = sample_head(b->samp, (size_t)r);
+        const uint32_t n0 = h.n0;
+        if (!topp[i]) { next[i] = h.tok; continue; }
         if (n0 > V) return fail(what + "row " + std::to_string(i) + ": the device reported " + std::to_string(n0) + " candidates");
         if (n0 < c->sw.topp_sort_min || n0 == 0) {
-            if (lmrs_sampler_topp_pairs(samplers[i], blk + 1, n0, &next[i])) return fail(what + "row " + std::to_string(i) + ": " + g_err);
+            if (lmrs_sampler_topp_pairs(samplers[i], h.cand, n0, &next[i])) return fail(what + "row " + std::to_string(i) + ": " + g_err);
             continue;
         }
         // a flat row: the candidates' sort (sampler.rs:81) on the device, over the row's probabilities as they stand in the logits block - p / 1.0f is p, so
@@ -2712,12 +2657,12 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
         auto sort = [&]() -> int {
             HIP_OK(launch_sample_topp_sort(c->sc_logits + (size_t)r * V, (int)V, 1.0f, cutoff, N, c->samp_keys, count, c->samp_pairs, c->stream));
             HIP_OK(hipMemcpyAsync(c->h_pairs, c->samp_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(c->h_pairs) + (size_t)c->samp_cap * 8, count, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(c->h_pairs + (size_t)c->samp_cap * 8, count, 4, hipMemcpyDeviceToHost, c->stream));
             return 0;
         };
         if (sort()) return batch_failed(c);
         HIP_OK(hipStreamSynchronize(c->stream));
-        unsigned dev_n0 = 0; memcpy(&dev_n0, reinterpret_cast<char*>(c->h_pairs) + (size_t)c->samp_cap * 8, 4);
+        unsigned dev_n0 = 0; memcpy(&dev_n0, c->h_pairs + (size_t)c->samp_cap * 8, 4);
         if (dev_n0 != n0) return fail(what + "row " + std::to_string(i) + ": the sort found " + std::to_string(dev_n0) + " top-p candidates, the filter " + std::to_string(n0));
         if (lmrs_sampler_topp_sorted_pairs(samplers[i], c->h_pairs, n0, &next[i])) return fail(what + "row " + std::to_string(i) + ": " + g_err);
     }
@@ -2759,12 +2704,12 @@ static int runs_check(const lmrs_batch* b, const std::string& what, uint32_t n_r
     if (embeds) *embeds = E;
     return 0;
 }
-// the staged block of a pass with embedding rows: all or nothing, at the first call that has one
+// the staged block of a pass with embedding rows, at the first call that has one
 static int embed_stage_alloc(lmrs_batch* b, const std::string& what) {
     if (b->embed_stage) return 0;
     const size_t bytes = (size_t)kRunRowsMax * b->c->args.dim * 4;
-    if (hipMalloc(reinterpret_cast<void**>(&b->embed_stage), bytes) != hipSuccess) {
-        (void)hipGetLastError(); b->embed_stage = nullptr;
+    if (!b->embed_stage.alloc(bytes / 4)) {
+        (void)hipGetLastError();
         return fail(what + std::to_string(bytes) + " bytes of staging for " + std::to_string(kRunRowsMax) + " embedding rows: out of memory");
     }
     return 0;
@@ -2803,8 +2748,7 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
         }
         return 0;
     };
-    if (enqueue()) return batch_failed(c);
-    if (finish_call(c)) return -1;
+    if (batch_call(c, enqueue)) return -1;
     if (O) memcpy(argmax, hs.idx, O * 4);
     if (O && k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
     return 0;
@@ -2871,8 +2815,7 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
             }
             return 0;
         };
-        if (enqueue()) return batch_failed(c);
-        if (finish_call(c)) return -1;                   // (the pinned table is rewritten for the next chunk)
+        if (batch_call(c, enqueue)) return -1;                   // (the pinned table is rewritten for the next chunk)
     }
     return 0;
 }
@@ -2900,44 +2843,18 @@ extern "C" int lmrs_batch_forward_runs_embed(lmrs_batch* b, uint32_t n_runs, con
 // launch_sample_rows takes them as lmrs_batch_forward_sample's rows, up to the batch's width of them; the flat top-p rows of the call - n0 known after the
 // first synchronise - are sorted together (launch_cand_sort) behind ONE second synchronise.  The buffers are this call's own: lmrs_batch_forward_sample's
 // stay as that call documents them.
-static void runs_sample_free(lmrs_batch* b) {
-    for (void** p : {(void**)&b->rs_tab, (void**)&b->rs_scratch, (void**)&b->rs_out}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    for (void** p : {(void**)&b->h_rs_tab, (void**)&b->h_rs_heads}) if (*p) { (void)hipHostFree(*p); *p = nullptr; }
-    b->rs_rows = 0;
-}
-static void cand_sort_free(lmrs_batch* b) {
-    if (b->cs_keys) { (void)hipFree(b->cs_keys); b->cs_keys = nullptr; }
-    if (b->h_cs_pairs) { (void)hipHostFree(b->h_cs_pairs); b->h_cs_pairs = nullptr; }
-    b->cs_words = 0;
-}
-// room for `rows` sampled rows (whole sixteens, the batch's width at the most): all or nothing, made anew when a call needs more rows than they hold
+// room for `rows` sampled rows (whole sixteens, the batch's width at the most): made anew when a call needs more rows than the set holds
 static int runs_sample_alloc(lmrs_batch* b, size_t rows) {
-    if (b->rs_rows >= rows) return 0;
-    runs_sample_free(b);
-    const lmrs_ctx* c = b->c;
-    const size_t V = c->args.vocab_size, R = std::min<size_t>(b->width, (rows + 15) / 16 * 16), head = 1 + std::min<size_t>(V, c->sw.topp_sort_min);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&b->rs_tab), R * sizeof(SampleRow)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_rs_tab), R * sizeof(SampleRow), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->rs_scratch), sample_scratch_floats(R) * 4) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_rs_heads), R * head * 8, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&b->rs_out), R * (V + 1) * 8) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        runs_sample_free(b);
-        return fail("lmrs_batch_forward_runs_sample: " + std::to_string(R * (V + 1) * 8) + " bytes of candidate buffers for " + std::to_string(R) + " rows: out of memory");
-    }
-    b->rs_rows = R; b->rs_head_words = head;
-    return 0;
+    if (b->rs.rows >= rows) return 0;
+    return sample_set_alloc(b->c, b->rs, std::min<size_t>(b->width, (rows + 15) / 16 * 16), [](size_t bytes, size_t R) {
+        return "lmrs_batch_forward_runs_sample: " + std::to_string(bytes) + " bytes of candidate buffers for " + std::to_string(R) + " rows: out of memory"; });
 }
-// F rows of N keys on the device and their pinned copy: all or nothing, made anew when a call sorts more
+// F rows of N keys on the device and their pinned copy (alloc_all), made anew when a call sorts more
 static int cand_sort_alloc(lmrs_batch* b, size_t F, size_t N) {
     if (b->cs_words >= F * N) return 0;
-    cand_sort_free(b);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&b->cs_keys), F * N * 8) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_cs_pairs), F * N * 8, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
+    b->cs_words = 0;
+    if (!alloc_all({{b->cs_keys, F * N}, {b->h_cs_pairs, F * N}})) {
         (void)hipGetLastError();
-        cand_sort_free(b);
         return fail("lmrs_batch_forward_runs_sample: " + std::to_string(F * N * 8) + " bytes of sort buffers for " + std::to_string(F) + " flat top-p rows: out of memory");
     }
     b->cs_words = F * N;
@@ -2955,28 +2872,14 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
     if (runs_check(b, what, n_runs, slot, start_pos, run_len, n_out, src, &R, &O, &E)) return -1;
     const size_t V = c->args.vocab_size;
     SampleRow par[kWideBatchMax]; bool topp[kWideBatchMax]; bool sampled = false;
-    for (uint32_t i = 0; i < n_runs; ++i) {
-        topp[i] = false;
-        if (!samplers[i]) continue;
-        const std::string run = what + "run " + std::to_string(i) + ": ";
-        uint32_t vs = 0;
-        if (lmrs_sampler_info(samplers[i], &vs, &par[i].temperature, &par[i].top_p, &par[i].rnd)) return -1;
-        if (vs != V) return fail(run + "the sampler was made for another vocabulary size (" + std::to_string(vs) + ", the model has " + std::to_string(V) + ")");
-        topp[i] = par[i].temperature != 0.0f && !(par[i].top_p <= 0.0f || par[i].top_p >= 1.0f);         // sampler.rs:117-126
-        sampled = sampled || par[i].temperature != 0.0f;
-        // (a top-p sampler carries its candidate vector from call to call: two runs of one call cannot both be "the next call")
-        for (uint32_t j = 0; j < i && topp[i]; ++j)
-            if (samplers[j] == samplers[i]) return fail(run + "the top-p sampler of run " + std::to_string(j) + " appears twice (it carries state from call to call)");
-    }
-    if (sampled && cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no sampled pass for this vocabulary");
+    if (samplers_check(c, what, "run", /*need_all=*/false, n_runs, samplers, par, topp, &sampled)) return -1;
     if (O > (size_t)c->sc_rows) return fail(what + "the logits block holds " + std::to_string(c->sc_rows) + " rows of this vocabulary, " + std::to_string(O) + " outputs were asked for");
     runs_table(b, n_runs, slot, start_pos, run_len, n_out, src, &R, &O);
     HIP_OK(hipSetDevice(c->device));
     if (sampled && runs_sample_alloc(b, O)) return -1;
     if (E && embed_stage_alloc(b, what)) return -1;
     if (pages_claim_rows(b, what, n_runs, slot, start_pos, run_len, 0)) return -1;
-    for (uint32_t i = 0; i < n_runs; ++i) { next[i] = 0; if (sampled && out_of[i] >= 0) b->h_rs_tab[out_of[i]] = par[i]; }
-    const size_t head = b->rs_head_words;
+    for (uint32_t i = 0; i < n_runs; ++i) { next[i] = 0; if (sampled && out_of[i] >= 0) b->rs.h_tab[out_of[i]] = par[i]; }
     const HostScores hs = host_scores(c);
     auto enqueue = [&]() -> int {
         if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * c->args.dim * 4, hipMemcpyHostToDevice, c->stream));
@@ -2985,14 +2888,9 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
         if (runs_pass(b, R, O, 0, RowSink{0, O, nullptr, 0}, E ? b->embed_stage : nullptr)) return -1;          // the reduction: sample_argmax of every output row -> sc_idx; the rows stay in sc_logits
         if (!O) return 0;
         if (!sampled) { HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
-        HIP_OK(hipMemcpyAsync(b->rs_tab, b->h_rs_tab, O * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(launch_sample_rows(sample_rows_args(c->sc_logits, (int)O, (int)V, (int)V, b->rs_tab, c->sc_idx, b->rs_scratch, b->rs_out), c->stream, (int)b->width));
-        // THE transfer: every row's {token, n0} and the first head - 1 of its candidates
-        HIP_OK(hipMemcpy2DAsync(b->h_rs_heads, head * 8, b->rs_out, (V + 1) * 8, head * 8, O, hipMemcpyDeviceToHost, c->stream));
-        return 0;
+        return sample_enqueue(c, b->rs, O, (int)b->width);
     };
-    if (enqueue()) return batch_failed(c);
-    if (finish_call(c)) return -1;
+    if (batch_call(c, enqueue)) return -1;
     if (!O) return 0;
     if (!sampled) { for (uint32_t i = 0; i < n_runs; ++i) if (out_of[i] >= 0) next[i] = hs.idx[out_of[i]]; return 0; }
     // the flat rows of the call (a top-p row with LMRS_TOPP_DEVICE_SORT_MIN candidates or more): one table, one sequence of launches, one synchronise
@@ -3000,7 +2898,7 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
     for (uint32_t i = 0; i < n_runs; ++i) {
         flat_of[i] = -1;
         if (!topp[i]) continue;
-        const uint32_t n0 = (uint32_t)(b->h_rs_heads[(size_t)out_of[i] * head] >> 32);
+        const uint32_t n0 = sample_head(b->rs, (size_t)out_of[i]).n0;
         if (n0 > V) return fail(what + "run " + std::to_string(i) + ": the device reported " + std::to_string(n0) + " candidates");
         if (n0 < c->sw.topp_sort_min || n0 == 0) continue;
         flat_of[i] = cs.n_rows; cs.t.row[cs.n_rows] = (unsigned)out_of[i]; cs.t.n0[cs.n_rows] = n0; ++cs.n_rows;
@@ -3010,7 +2908,7 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
         cs.N = sample_sort_min_n();
         while ((size_t)cs.N < n0_max) cs.N <<= 1;
         if (cand_sort_alloc(b, (size_t)cs.n_rows, (size_t)cs.N)) return -1;
-        cs.src = b->rs_out + 1; cs.ld = V + 1; cs.keys = b->cs_keys;
+        cs.src = b->rs.out + 1; cs.ld = V + 1; cs.keys = b->cs_keys;
         auto sort = [&]() -> int {
             HIP_OK(launch_cand_sort(cs, c->stream));
             for (int f = 0; f < cs.n_rows; ++f)
@@ -3022,11 +2920,10 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
     }
     for (uint32_t i = 0; i < n_runs; ++i) {              // in run order: the host samplers move as n_runs calls of lmrs_forward_sample would move them
         if (out_of[i] < 0) continue;
-        const unsigned long long* blk = b->h_rs_heads + (size_t)out_of[i] * head;
-        const uint32_t tok = (uint32_t)blk[0], n0 = (uint32_t)(blk[0] >> 32);
-        if (!topp[i]) { next[i] = tok; continue; }
-        const int rc = flat_of[i] < 0 ? lmrs_sampler_topp_pairs(samplers[i], blk + 1, n0, &next[i])
-                                      : lmrs_sampler_topp_sorted_pairs(samplers[i], b->h_cs_pairs + (size_t)flat_of[i] * cs.N, n0, &next[i]);
+        const SampleHead h = sample_head(b->rs, (size_t)out_of[i]);
+        if (!topp[i]) { next[i] = h.tok; continue; }
+        const int rc = flat_of[i] < 0 ? lmrs_sampler_topp_pairs(samplers[i], h.cand, h.n0, &next[i])
+                                      : lmrs_sampler_topp_sorted_pairs(samplers[i], b->h_cs_pairs + (size_t)flat_of[i] * cs.N, h.n0, &next[i]);
         if (rc) return fail(what + "run " + std::to_string(i) + ": " + g_err);
     }
     return 0;
@@ -3077,8 +2974,7 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
             if (residual) HIP_OK(hipMemcpyAsync(residual, c->pf_x, dim * 4, hipMemcpyDeviceToHost, c->stream));
             return 0;
         };
-        if (enqueue()) return batch_failed(c);
-        return finish_call(c);
+        return batch_call(c, enqueue);
     }
     auto enqueue = [&]() -> int {
         if (set_state(c, start_pos, 0, win)) return -1;
@@ -3093,8 +2989,7 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
         };
         return prefill_chunks(c, form, start_pos, n, upload_rows, download_rows);
     };
-    if (enqueue()) return batch_failed(c);
-    return finish_call(c);
+    return batch_call(c, enqueue);
 }
 
 extern "C" int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out) {
@@ -3304,9 +3199,8 @@ extern "C" int lmrs_step_info(const lmrs_ctx* c, uint32_t pos, int* n_launches, 
 // ------------------------------------------------------------------ L2 free functions (unit parity)
 namespace {
 struct Scratch {          // RAII device buffers for the op entry points
-    std::vector<void*> p;
-    ~Scratch() { for (void* q : p) (void)hipFree(q); }
-    void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 4) != hipSuccess) return nullptr; p.push_back(q); return q; }
+    std::vector<DevBuf<char>> p;
+    void* get(size_t bytes) { DevBuf<char> q; if (!q.alloc(bytes)) return nullptr; p.push_back(std::move(q)); return p.back().get(); }
 };
 int op_begin(int device) {
     int ndev = 0;
@@ -3669,17 +3563,18 @@ struct lmrs_vision {
     Switches sw;                                   // the environment switches, read at create (vis_no_stray)
     float *class_emb = nullptr, *patch_emb = nullptr, *pos_emb = nullptr, *pre_ln = nullptr, *pre_ln_b = nullptr;
     std::vector<VisLayer> layers;
-    std::vector<void*> owned;
-    // work buffers, grown on demand
+    std::vector<DevBuf<char>> owned;               // the weights' blocks (the pointers above and the layers' are views of them)
+    // work buffers, grown on demand (alloc_all; cap_tok != 0: the set stands)
     size_t cap_tok = 0;
-    float *pix = nullptr, *X = nullptr, *E = nullptr, *QKV = nullptr, *AO = nullptr, *H = nullptr, *scratch = nullptr, *xs = nullptr; int8_t* xq = nullptr;
+    DevBuf<float> pix, X, E, QKV, AO, H, scratch, xs; DevBuf<int8_t> xq;
 };
 
 namespace {
 template <class T> T* vis_dev(lmrs_vision* v, const void* src, size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    v->owned.push_back(p);
+    DevBuf<char> d;
+    if (!d.alloc(bytes)) return nullptr;
+    void* p = d.get();
+    v->owned.push_back(std::move(d));
     if (src && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return static_cast<T*>(p);
 }
@@ -3689,8 +3584,6 @@ uint32_t rd32(const uint8_t* p) { uint32_t x; memcpy(&x, p, 4); return x; }
 extern "C" void lmrs_vision_destroy(lmrs_vision* v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
-    for (void* p : v->owned) (void)hipFree(p);
-    for (void* p : {(void*)v->pix, (void*)v->X, (void*)v->E, (void*)v->QKV, (void*)v->AO, (void*)v->H, (void*)v->scratch, (void*)v->xs, (void*)v->xq}) if (p) (void)hipFree(p);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
 }
@@ -3769,19 +3662,11 @@ extern "C" int lmrs_vision_create(const uint8_t* sec, size_t len, int device, lm
 
 static int vis_reserve(lmrs_vision* v, size_t n_tok, uint32_t num_crops) {
     if (n_tok <= v->cap_tok) return 0;
-    for (void** p : {(void**)&v->pix, (void**)&v->X, (void**)&v->E, (void**)&v->QKV, (void**)&v->AO, (void**)&v->H, (void**)&v->scratch, (void**)&v->xs, (void**)&v->xq})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
     v->cap_tok = 0;
     const size_t dim = v->dim, hid = v->hidden;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->pix), (size_t)num_crops * 3 * v->image * v->image * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->X), n_tok * dim * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->E), n_tok * dim * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->QKV), n_tok * dim * 3 * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->AO), n_tok * dim * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->H), n_tok * hid * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->scratch), vis_attention_scratch_floats((int)num_crops, (int)v->n_heads, 577) * 4));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->xq), n_tok * hid));
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&v->xs), n_tok * (hid / 128) * 4));
+    if (!alloc_all({{v->pix, (size_t)num_crops * 3 * v->image * v->image}, {v->X, n_tok * dim}, {v->E, n_tok * dim}, {v->QKV, n_tok * dim * 3}, {v->AO, n_tok * dim}, {v->H, n_tok * hid},
+                    {v->scratch, vis_attention_scratch_floats((int)num_crops, (int)v->n_heads, 577)}, {v->xq, n_tok * hid}, {v->xs, n_tok * (hid / 128)}}))
+        return alloc_failed("vision work buffers: hipMalloc");
     v->cap_tok = n_tok;
     return 0;
 }
@@ -3808,9 +3693,8 @@ extern "C" int lmrs_vision_forward(lmrs_vision* v, const float* pixel_values, ui
     if (v->qt == LMRS_Q8_0 && !v->layers.empty() && !v->layers[0].sqkvT && !v->no_scales_t) {      // (Q4_0 sections run the direct kernels: row-major scales)
         bool ok = true;
         auto tr = [&](const float* src, int rows, int groups) -> float* {
-            float* d = nullptr;
-            if (!ok || hipMalloc(reinterpret_cast<void**>(&d), (size_t)rows * groups * 4) != hipSuccess) { (void)hipGetLastError(); ok = false; return nullptr; }
-            v->owned.push_back(d);
+            float* d = ok ? vis_dev<float>(v, nullptr, (size_t)rows * groups * 4) : nullptr;
+            if (!d) { (void)hipGetLastError(); ok = false; return nullptr; }
             if (launch_transpose_scales(src, rows, groups, d, s) != hipSuccess) ok = false;
             return d;
         };
@@ -3862,15 +3746,13 @@ struct lmrs_processor {
     int device = 0; hipStream_t stream = nullptr;
     uint32_t hidden = 0, text = 0; int qt = LMRS_Q8_0;       // q_type of the section: Q8_0, Q4_0 or None (f32)
     std::vector<float> glb_gn, sub_gn;
-    char *p0 = nullptr, *p1 = nullptr; float *s0 = nullptr, *s1 = nullptr, *b0 = nullptr, *b1 = nullptr;
-    size_t cap = 0; float *emb = nullptr, *hid = nullptr, *outd = nullptr, *xs = nullptr; int8_t* xq = nullptr;
+    DevBuf<char> p0, p1; DevBuf<float> s0, s1, b0, b1;
+    size_t cap = 0; DevBuf<float> emb, hid, outd, xs; DevBuf<int8_t> xq;        // work buffers for cap embeddings (alloc_all)
 };
 
 extern "C" void lmrs_processor_destroy(lmrs_processor* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    for (void* q : {(void*)p->p0, (void*)p->p1, (void*)p->s0, (void*)p->s1, (void*)p->b0, (void*)p->b1, (void*)p->emb, (void*)p->hid, (void*)p->outd, (void*)p->xs, (void*)p->xq})
-        if (q) (void)hipFree(q);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
@@ -3897,11 +3779,10 @@ extern "C" int lmrs_processor_create(const uint8_t* sec, size_t len, int device,
     size_t off = 128;
     p->glb_gn.assign(reinterpret_cast<const float*>(sec + off), reinterpret_cast<const float*>(sec + off) + H); off += H * 4;
     p->sub_gn.assign(reinterpret_cast<const float*>(sec + off), reinterpret_cast<const float*>(sec + off) + H); off += H * 4;
-    auto up = [&](void** dst, size_t bytes) {
-        if (hipMalloc(dst, bytes ? bytes : 4) != hipSuccess) return false;
-        const bool ok = !bytes || hipMemcpy(*dst, sec + off, bytes, hipMemcpyHostToDevice) == hipSuccess; off += bytes; return ok; };
-    if (!up(reinterpret_cast<void**>(&p->p0), qb(Tt * H)) || !up(reinterpret_cast<void**>(&p->s0), sb(Tt * H)) || !up(reinterpret_cast<void**>(&p->p1), qb(Tt * Tt)) ||
-        !up(reinterpret_cast<void**>(&p->s1), sb(Tt * Tt)) || !up(reinterpret_cast<void**>(&p->b0), Tt * 4) || !up(reinterpret_cast<void**>(&p->b1), Tt * 4))
+    auto up = [&](auto& dst, size_t bytes) {
+        if (!dst.alloc(bytes / sizeof(*dst.get()))) return false;
+        const bool ok = !bytes || hipMemcpy(dst, sec + off, bytes, hipMemcpyHostToDevice) == hipSuccess; off += bytes; return ok; };
+    if (!up(p->p0, qb(Tt * H)) || !up(p->s0, sb(Tt * H)) || !up(p->p1, qb(Tt * Tt)) || !up(p->s1, sb(Tt * Tt)) || !up(p->b0, Tt * 4) || !up(p->b1, Tt * 4))
         return bad("hipMalloc / upload failed");
     if (bytes_consumed) *bytes_consumed = off;
     *out = p;
@@ -3973,11 +3854,8 @@ extern "C" int lmrs_processor_forward(lmrs_processor* p, const float* out_patche
     const size_t ne = emb.size() / H;
     if (ne != (size_t)(h_crop * patch_side) * (w_crop * patch_side + 1) + (size_t)patch_side * (patch_side + 1) + 1) return fail("processor: embedding count");
     if (ne > p->cap) {
-        for (void** q : {(void**)&p->emb, (void**)&p->hid, (void**)&p->outd, (void**)&p->xs, (void**)&p->xq}) if (*q) { (void)hipFree(*q); *q = nullptr; }
         p->cap = 0;
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&p->emb), ne * H * 4)); HIP_OK(hipMalloc(reinterpret_cast<void**>(&p->hid), ne * Tt * 4));
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&p->outd), ne * Tt * 4)); HIP_OK(hipMalloc(reinterpret_cast<void**>(&p->xq), ne * H));
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&p->xs), ne * (H / 128) * 4));
+        if (!alloc_all({{p->emb, ne * H}, {p->hid, ne * Tt}, {p->outd, ne * Tt}, {p->xq, ne * H}, {p->xs, ne * (H / 128)}})) return alloc_failed("projector work buffers: hipMalloc");
         p->cap = ne;
     }
     hipStream_t s = p->stream;
