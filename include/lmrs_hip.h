@@ -664,6 +664,40 @@ int lmrs_batch_set_masks(lmrs_batch* b, uint32_t n, const uint32_t* slot, const 
 int lmrs_batch_clear_masks(lmrs_batch* b, uint32_t n, const uint32_t* slot);
 int lmrs_batch_mask_info(const lmrs_batch* b, uint32_t slot, uint32_t* n_allowed /* 0: no mask */);
 
+/* ---- repetition, presence and frequency penalties per slot, over a token record kept on the device (extensions, no reference counterpart) ----
+ * The record: hist[n_slots][seq_len] words on the device, hist[s][p] = the token whose K/V row stands at position p of slot s, LMRS_TOKEN_NONE where it
+ * is unknown or the row was an embedding.  It is made - all NONE - by the first lmrs_batch_set_history or lmrs_batch_set_penalties call (all or
+ * nothing, the message gives the bytes) and until then a batch enqueues exactly the launches and copies it enqueued without these calls.  From then
+ * on every batch call that writes K/V rows of a slot writes the record of the same positions: lmrs_batch_forward, _forward_sample, _forward_runs* and
+ * every step of lmrs_batch_generate_greedy (one launch over the pass's device table, so the loop's own tokens are recorded without crossing to the
+ * host), lmrs_batch_prefill (contiguous and paged); lmrs_batch_prefill_embeddings and embedding runs write NONE; lmrs_batch_fork copies the first
+ * n_pos entries of src to dst, NONE from LMRS_BATCH_CTX.  The record is a function of the position, not a counter: a position is rewritten before it
+ * is read again, so rewinds, rejected drafts and lmrs_batch_release need no bookkeeping.
+ * The rule.  Output row r of slot s at position p, logits l (f32) as the classifier and Gemma's soft-cap leave them; H = the entries hist[s][i],
+ * 0 <= i <= p, that are not NONE (the row's own input token is one of them); c_all[t] = occurrences of t in H, c_out[t] = those at i >= out_from[s]:
+ *   for every t with c_all[t] > 0 and repetition != 1:  l[t] = l[t] > 0 ? l[t] / repetition : l[t] * repetition
+ *   then for every t with c_out[t] > 0:                   l[t] = (l[t] - frequency * (float)c_out[t]) - presence
+ * each operation one correctly rounded f32 operation (the division IEEE), nothing contracted; no other logit changes; the counts are integers, so the
+ * result does not depend on scheduling.  The slot's mask is applied behind this and the sinks run unchanged: the logits a caller downloads, argmax,
+ * top-k, log-probabilities and sampled tokens of every batch call, contiguous, wide or paged, come from the penalised row.  repetition < 1 and
+ * negative presence / frequency are legal (they raise seen tokens); (1, 0, 0) is the same as clearing.  Penalties stay until replaced or cleared:
+ * lmrs_batch_fork and lmrs_batch_release neither copy nor clear them.  The context's own calls (lmrs_forward*, lmrs_generate_*) are not touched.
+ * lmrs_batch_set_history: hist[slot][start_pos .. start_pos + n) = tokens (what a caller knows of positions written before the record existed);
+ *   n may be 0: only switches the record on.  lmrs_batch_history: the same range read back; an error while the batch keeps no record.
+ * lmrs_batch_set_penalties: the parameters of n slots (arrays of n); lmrs_batch_clear_penalties: n == 0 (slot may be NULL): every slot;
+ * lmrs_batch_penalty_info: the slot's parameters as set ((1, 0, 0, 0) if never), *active = 1 while they change a logit.
+ * Errors, each with a message that opens with the call's name, before any state changes: a NULL batch; a NULL array with n > 0; n above
+ * lmrs_batch_width; a slot >= n_slots; the same slot twice in one call; a value that is not finite; repetition <= 0; out_from > seq_len; a token
+ * >= vocab_size that is not LMRS_TOKEN_NONE; start_pos + n > seq_len; a model whose classifier leaves a tail of the vocabulary unwritten. */
+#define LMRS_TOKEN_NONE 0xFFFFFFFFu
+int lmrs_batch_set_history(lmrs_batch* b, uint32_t slot, uint32_t start_pos, const uint32_t* tokens, size_t n);
+int lmrs_batch_history(lmrs_batch* b, uint32_t slot, uint32_t start_pos, size_t n, uint32_t* out);
+int lmrs_batch_set_penalties(lmrs_batch* b, uint32_t n, const uint32_t* slot, const float* repetition, const float* presence,
+                             const float* frequency, const uint32_t* out_from);
+int lmrs_batch_clear_penalties(lmrs_batch* b, uint32_t n, const uint32_t* slot);
+int lmrs_batch_penalty_info(const lmrs_batch* b, uint32_t slot, float* repetition, float* presence, float* frequency,
+                            uint32_t* out_from, int* active);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ EXPORTS = [
     "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
     "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
+    "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -120,6 +121,11 @@ def lib():
         L.lmrs_batch_set_masks.argtypes = [vp, u32, vp, vp]
         L.lmrs_batch_clear_masks.argtypes = [vp, u32, vp]
         L.lmrs_batch_mask_info.argtypes = [vp, u32, C.POINTER(u32)]
+        L.lmrs_batch_set_history.argtypes = [vp, u32, u32, vp, sz]
+        L.lmrs_batch_history.argtypes = [vp, u32, u32, sz, vp]
+        L.lmrs_batch_set_penalties.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.lmrs_batch_clear_penalties.argtypes = [vp, u32, vp]
+        L.lmrs_batch_penalty_info.argtypes = [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_int)]
         L.lmrs_batch_destroy.argtypes = [vp]; L.lmrs_batch_destroy.restype = None
         L.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
         L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
@@ -421,6 +427,7 @@ def unpack_mask(words, vocab_size: int) -> np.ndarray:
 
 
 BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BATCH_CTX)
+TOKEN_NONE = 0xFFFFFFFF       # Batch.history / set_history: a position whose token is unknown, or an embedding row (LMRS_TOKEN_NONE)
 
 
 class Batch:
@@ -501,6 +508,58 @@ class Batch:
         n = C.c_uint32()
         _chk(lib().lmrs_batch_mask_info(self._h, slot, C.byref(n)))
         return n.value or None
+
+    def set_penalties(self, slots, repetition=1.0, presence=0.0, frequency=0.0, out_from=0) -> None:
+        """Repetition / presence / frequency penalties for `slots`; a scalar serves every slot, an array gives one value each.  While a slot has
+        them, every output of its rows in any call here comes from the row's logits changed by the rule of include/lmrs_hip.h over the tokens the
+        slot has seen (history): tokens seen anywhere are divided / multiplied by `repetition`, tokens seen at positions >= out_from lose
+        frequency * count + presence.  The first call switches the batch's token record on (lmrs_batch_set_penalties)"""
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+
+        def per_slot(name, v, dtype):
+            a = np.asarray(v)
+            if a.ndim == 0:
+                a = np.full(s.size, v)
+            a = a.reshape(-1)
+            if a.size != s.size:
+                raise LmrsError(f"{name} must be a scalar or hold one value per slot ({s.size}), got {a.size}")
+            if dtype == np.uint32 and a.size and (np.any(a < 0) or np.any(a != np.floor(a))):
+                raise LmrsError(f"{name} must hold whole numbers >= 0")
+            return np.ascontiguousarray(a, dtype)
+        r, p, f = (per_slot(n, v, np.float32) for n, v in (("repetition", repetition), ("presence", presence), ("frequency", frequency)))
+        o = per_slot("out_from", out_from, np.uint32)
+        _chk(lib().lmrs_batch_set_penalties(self._h, s.size, *((_p(x) if s.size else None) for x in (s, r, p, f, o))))
+
+    def clear_penalties(self, slots=None) -> None:
+        """The named slots lose their penalties; None: every slot.  The token record stays (lmrs_batch_clear_penalties)"""
+        if slots is None:
+            _chk(lib().lmrs_batch_clear_penalties(self._h, 0, None))
+            return
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+        if s.size:                                              # (an empty list names no slot; n == 0 in the C call means all of them)
+            _chk(lib().lmrs_batch_clear_penalties(self._h, s.size, _p(s)))
+
+    def penalty_info(self, slot: int):
+        """`slot`'s penalties -> dict(repetition, presence, frequency, out_from, active); active is False while they change no logit
+        (lmrs_batch_penalty_info)"""
+        r, p, f, o, a = C.c_float(), C.c_float(), C.c_float(), C.c_uint32(), C.c_int()
+        _chk(lib().lmrs_batch_penalty_info(self._h, slot, C.byref(r), C.byref(p), C.byref(f), C.byref(o), C.byref(a)))
+        return dict(repetition=r.value, presence=p.value, frequency=f.value, out_from=o.value, active=bool(a.value))
+
+    def set_history(self, slot: int, tokens=(), start_pos: int = 0) -> None:
+        """The token record of `slot` from start_pos on = tokens (TOKEN_NONE: unknown) - what the caller knows of positions written before the record
+        existed.  With no tokens the call only switches the record on (lmrs_batch_set_history)"""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        _chk(lib().lmrs_batch_set_history(self._h, slot, start_pos, _p(t) if t.size else None, t.size))
+
+    def history(self, slot: int, n: int, start_pos: int = 0):
+        """The token record of `slot` at positions [start_pos, start_pos + n) -> uint32 [n], TOKEN_NONE where the token is unknown or the row was an
+        embedding; an error on a batch that keeps no record (lmrs_batch_history)"""
+        if n < 0:
+            raise LmrsError("n must not be negative")
+        out = np.empty(n, np.uint32)
+        _chk(lib().lmrs_batch_history(self._h, slot, start_pos, n, _p(out) if n else None))
+        return out
 
     @property
     def width(self) -> int:

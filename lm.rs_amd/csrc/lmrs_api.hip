@@ -196,7 +196,11 @@ struct StepForm { int qa_mode = 0, split_chunks = 0; bool split_merged = false; 
 // masks (masks.bits != null): some output row of the pass belongs to a batch slot with an allowed-token mask (lmrs_batch_set_masks) - of[r] is the mask row of
 // output row r in the order the classifier sees the rows, -1 for none; h_of is its pinned source, which says on the host whether a slab has a masked row at all.
 struct MaskView { const uint32_t* bits = nullptr; int words = 0; const int* of = nullptr; const int* h_of = nullptr; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+// penalties (penalties.hist != null): some output row of the pass belongs to a slot with penalties (lmrs_batch_set_penalties) - of[r] carries slot, parameters and the
+// table row whose position is row r's (pos: that column of the pass's device table, read on the device - right inside lmrs_batch_generate_greedy's loops); h_of is
+// its pinned source, as with the masks; max_n = the deepest row's position + 1 at this pass (the keys a workgroup sorts)
+struct PenaltyView { const uint32_t* hist = nullptr; int seq_len = 0; const int* pos = nullptr; const PenaltyRow* of = nullptr; const PenaltyRow* h_of = nullptr; int max_n = 0; };
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; PenaltyView penalties{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1792,6 +1796,9 @@ static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, float* x
         g.n = dim; g.o = o; g.n_tok = mj; g.q4 = c->q4; g.out = c->sc_logits; g.skinny = form.skinny;
         HIP_OK(launch_gemm_q8(g, EPI_STORE, c->stream));
         if (gemma) HIP_OK(launch_softcap_rows(c->sc_logits, o, std::min(dim, o), mj, c->stream));
+        // a batch's penalties (PassForm::penalties), in front of its masks: one launch a slab, and only for a slab that has a penalised row
+        if (form.penalties.hist && std::any_of(form.penalties.h_of + i0 + j0, form.penalties.h_of + i0 + j0 + mj, [](const PenaltyRow& r) { return r.slot >= 0; }))
+            HIP_OK(launch_penalty_rows(c->sc_logits, o, o, mj, form.penalties.hist, form.penalties.seq_len, form.penalties.pos, form.penalties.of + i0 + j0, form.penalties.max_n, c->stream));
         // a batch's masks (PassForm::masks): one launch a slab, and only for a slab that has a masked row
         if (form.masks.bits && std::any_of(form.masks.h_of + i0 + j0, form.masks.h_of + i0 + j0 + mj, [](int m) { return m >= 0; }))
             HIP_OK(launch_mask_rows(c->sc_logits, o, o, mj, form.masks.bits, form.masks.words, form.masks.of + i0 + j0, c->stream));
@@ -2049,6 +2056,23 @@ struct lmrs_batch {
     DevBuf<int> mask_of; PinBuf<int> h_mask_of; bool mask_live = false;
     int mask_row_of(uint32_t slot) const { return n_allowed[slot] ? (int)slot : -1; }
     MaskView mask_view() const { return mask_live ? MaskView{masks, (int)mask_words, mask_of, h_mask_of} : MaskView{}; }
+    // the token record and the penalties over it (lmrs_batch_set_history / lmrs_batch_set_penalties; made at the first call of either, `hist` non-null from then
+    // on): hist[n_slots][seq_len], LMRS_TOKEN_NONE where the token is unknown.  hist_slot / h_hist_slot: the slot of every row of the pass's table, beside the
+    // table (record_enqueue).  pen[s]: slot s's parameters, pen_on[s] - they are other than (1, 0, 0), n_pen the slots where they are.  pen_of / h_pen_of: the
+    // per-call column of PassForm::penalties, written with the tables; pen_live: this call uploaded it - some output row of the call is penalised
+    DevBuf<uint32_t> hist; DevBuf<int> hist_slot; PinBuf<int> h_hist_slot;
+    struct Penalty { float repetition = 1.0f, presence = 0.0f, frequency = 0.0f; uint32_t out_from = 0; };
+    Penalty pen[kWideBatchMax]; bool pen_on[kWideBatchMax] = {}; uint32_t n_pen = 0;
+    DevBuf<PenaltyRow> pen_of; PinBuf<PenaltyRow> h_pen_of; bool pen_live = false;
+    uint32_t* hist_of(uint32_t slot) const { return hist + (size_t)slot * c->args.seq_len; }
+    PenaltyRow penalty_row_of(uint32_t slot, int tab_row) const {
+        const Penalty& p = pen[slot];
+        return pen_on[slot] ? PenaltyRow{(int)slot, tab_row, p.repetition, p.presence, p.frequency, p.out_from} : PenaltyRow{-1, 0, 1.0f, 0.0f, 0.0f, 0};
+    }
+    // table: the position column the rows' tab_row counts in (the row table's, or the long table's); max_n: the deepest row's position + 1 at this pass
+    PenaltyView penalty_view(const int* table_pos, int max_n) const {
+        return pen_live ? PenaltyView{hist, (int)c->args.seq_len, table_pos, pen_of, h_pen_of, max_n} : PenaltyView{};
+    }
     RowView runs_view() const { return RowView{runs->off, runs->pos, runs->tok}; }      // (addresses inside the device table: nothing is read here)
     // the `off` word of a row of `slot`: where its caches start, in floats - on a paged batch its row of the page table
     unsigned long long off_of(uint32_t slot) const { return pool ? slot : (unsigned long long)slot * 2 * slot_floats; }
@@ -2146,11 +2170,11 @@ static int masks_alloc(lmrs_batch* b) {
     return 0;
 }
 // the slots of a mask call, checked: `what` opens every message
-static int mask_slots_check(const lmrs_batch* b, const std::string& what, uint32_t n, const uint32_t* slot) {
+static int mask_slots_check(const lmrs_batch* b, const std::string& what, uint32_t n, const uint32_t* slot, const char* noun = "mask ") {
     if (n > b->width) return fail(what + "n = " + std::to_string(n) + " exceeds the batch's width of " + std::to_string(b->width));
     uint64_t seen = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (slot[i] >= b->n_slots) return fail(what + "mask " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
+        if (slot[i] >= b->n_slots) return fail(what + noun + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
         if (seen >> slot[i] & 1u) return fail(what + "slot " + std::to_string(slot[i]) + " appears twice");
         seen |= uint64_t(1) << slot[i];
     }
@@ -2205,6 +2229,118 @@ extern "C" int lmrs_batch_mask_info(const lmrs_batch* b, uint32_t slot, uint32_t
     if (!b || !n_allowed) return fail(what + "NULL argument");
     if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
     *n_allowed = b->n_allowed[slot];
+    return 0;
+}
+
+// ------------------------------------------------------------------ the token record and the penalties over it: state of a slot (extensions, no reference counterpart)
+// hist[slot][pos] is the token whose K/V row stands at `pos` of `slot`: every batch call that writes K/V rows writes it too (record_rows_kernel over the pass's
+// table, a copy for a contiguous prefill and a fork), so it is a function of the position - rewinds, rejected drafts, forks and releases need no bookkeeping,
+// a row at position p reads hist[slot][0 .. p] only.  While slot s has penalties, every output row of s in any batch call is the row with
+// penalty_rows_kernel's changes (lmrs_score.h: the rule, operation by operation), behind the soft-cap and in front of the slot's mask and every sink.
+// A batch that made neither call enqueues exactly what it enqueued before: every hook below tests b->hist.
+static_assert(LMRS_TOKEN_NONE == kTokenNone, "the header's NONE is the kernels'");
+static int history_alloc(lmrs_batch* b, const std::string& what) {
+    if (b->hist) return 0;
+    const size_t words = (size_t)b->n_slots * b->c->args.seq_len;
+    if (!alloc_all({{b->hist, words}, {b->hist_slot, kRunRowsMax}, {b->h_hist_slot, kRunRowsMax}, {b->pen_of, kRunRowsMax}, {b->h_pen_of, kRunRowsMax}})) {
+        (void)hipGetLastError();
+        return fail(what + std::to_string(words * 4) + " bytes of token record for " + std::to_string(b->n_slots) + " slots: out of memory");
+    }
+    if (hipMemsetAsync(b->hist, 0xFF, words * 4, b->c->stream) != hipSuccess || hipStreamSynchronize(b->c->stream) != hipSuccess) {
+        b->hist.reset(); b->hist_slot.reset(); b->h_hist_slot.reset(); b->pen_of.reset(); b->h_pen_of.reset();
+        return fail(what + std::string("clearing the token record failed: ") + hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+}
+extern "C" int lmrs_batch_set_history(lmrs_batch* b, uint32_t slot, uint32_t start_pos, const uint32_t* tokens, size_t n) {
+    const std::string what = "lmrs_batch_set_history: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && !tokens) return fail(what + "NULL array");
+    lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, T = c->args.seq_len;
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if (start_pos > T || n > T - start_pos) return fail(what + "start_pos + n = " + std::to_string((size_t)start_pos + n) + " exceeds seq_len = " + std::to_string(T));
+    for (size_t i = 0; i < n; ++i)
+        if (tokens[i] >= V && tokens[i] != LMRS_TOKEN_NONE) return fail(what + "token " + std::to_string(i) + " out of range (neither below vocab_size = " + std::to_string(V) + " nor LMRS_TOKEN_NONE)");
+    HIP_OK(hipSetDevice(c->device));
+    if (history_alloc(b, what)) return -1;
+    if (!n) return 0;
+    if (hipMemcpyAsync(b->hist_of(slot) + start_pos, tokens, n * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(what + std::string("uploading the tokens failed: ") + hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+extern "C" int lmrs_batch_history(lmrs_batch* b, uint32_t slot, uint32_t start_pos, size_t n, uint32_t* out) {
+    const std::string what = "lmrs_batch_history: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && !out) return fail(what + "NULL array");
+    lmrs_ctx* c = b->c;
+    const size_t T = c->args.seq_len;
+    if (!b->hist) return fail(what + "the batch keeps no token record (lmrs_batch_set_history or lmrs_batch_set_penalties switches it on)");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    if (start_pos > T || n > T - start_pos) return fail(what + "start_pos + n = " + std::to_string((size_t)start_pos + n) + " exceeds seq_len = " + std::to_string(T));
+    if (!n) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    if (hipMemcpyAsync(out, b->hist_of(slot) + start_pos, n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(what + std::string("reading the record failed: ") + hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+extern "C" int lmrs_batch_set_penalties(lmrs_batch* b, uint32_t n, const uint32_t* slot, const float* repetition, const float* presence, const float* frequency,
+                                        const uint32_t* out_from) {
+    const std::string what = "lmrs_batch_set_penalties: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && (!slot || !repetition || !presence || !frequency || !out_from)) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot, "penalty ")) return -1;
+    lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, T = c->args.seq_len;
+    if (cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no penalties for this vocabulary");
+    if (T > (size_t)kPenaltyKeysMax) return fail(what + "seq_len = " + std::to_string(T) + " exceeds the " + std::to_string(kPenaltyKeysMax) + " positions a penalised row sorts");
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string at = what + "penalty " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + ": ";
+        if (!std::isfinite(repetition[i]) || !std::isfinite(presence[i]) || !std::isfinite(frequency[i])) return fail(at + "a value is not finite");
+        if (!(repetition[i] > 0.0f)) return fail(at + "repetition = " + std::to_string(repetition[i]) + " is not above 0");
+        if (out_from[i] > T) return fail(at + "out_from = " + std::to_string(out_from[i]) + " exceeds seq_len = " + std::to_string(T));
+    }
+    HIP_OK(hipSetDevice(c->device));
+    if (history_alloc(b, what)) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t s = slot[i];
+        const bool on = !(repetition[i] == 1.0f && presence[i] == 0.0f && frequency[i] == 0.0f);       // (1, 0, 0) changes no logit: the same as clearing
+        b->pen[s] = lmrs_batch::Penalty{repetition[i], presence[i], frequency[i], out_from[i]};
+        if (on && !b->pen_on[s]) ++b->n_pen;
+        if (!on && b->pen_on[s]) --b->n_pen;
+        b->pen_on[s] = on;
+    }
+    return 0;
+}
+extern "C" int lmrs_batch_clear_penalties(lmrs_batch* b, uint32_t n, const uint32_t* slot) {
+    const std::string what = "lmrs_batch_clear_penalties: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && !slot) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot, "penalty ")) return -1;
+    for (uint32_t s = 0; s < b->n_slots && !n; ++s) { b->pen[s] = lmrs_batch::Penalty{}; b->pen_on[s] = false; }
+    if (!n) b->n_pen = 0;
+    for (uint32_t i = 0; i < n; ++i) { if (b->pen_on[slot[i]]) --b->n_pen; b->pen[slot[i]] = lmrs_batch::Penalty{}; b->pen_on[slot[i]] = false; }
+    return 0;
+}
+extern "C" int lmrs_batch_penalty_info(const lmrs_batch* b, uint32_t slot, float* repetition, float* presence, float* frequency, uint32_t* out_from, int* active) {
+    const std::string what = "lmrs_batch_penalty_info: ";
+    if (!b || !repetition || !presence || !frequency || !out_from || !active) return fail(what + "NULL argument");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    const lmrs_batch::Penalty& p = b->pen[slot];
+    *repetition = p.repetition; *presence = p.presence; *frequency = p.frequency; *out_from = p.out_from; *active = b->pen_on[slot] ? 1 : 0;
+    return 0;
+}
+// A fork's record: dst's first n_pos positions are src's; the context's sequence (LMRS_BATCH_CTX) has no record - unknown tokens
+static int history_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_slot, uint32_t n_pos) {
+    if (!b->hist) return 0;
+    if (src_slot == LMRS_BATCH_CTX) HIP_OK(hipMemsetAsync(b->hist_of(dst_slot), 0xFF, (size_t)n_pos * 4, b->c->stream));
+    else HIP_OK(hipMemcpyAsync(b->hist_of(dst_slot), b->hist_of(src_slot), (size_t)n_pos * 4, hipMemcpyDeviceToDevice, b->c->stream));
+    return 0;
+}
+// The record of a pass over the device table as it stands (its pos / tok columns; the slot column went up with the table, record_enqueue): R rows, one launch
+static int record_rows(lmrs_batch* b, const int* pos, const uint32_t* tok, size_t R) {
+    if (!b->hist) return 0;
+    HIP_OK(launch_record_rows(b->hist, (int)b->c->args.seq_len, (int)b->n_slots, pos, tok, b->hist_slot, (int)R, b->c->stream));
     return 0;
 }
 
@@ -2301,6 +2437,7 @@ extern "C" int lmrs_batch_prefill(lmrs_batch* b, uint32_t slot, const uint32_t* 
     memcpy(c->h_tok, tokens, n * 4);
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tokens, c->h_tok, n * 4, hipMemcpyHostToDevice, c->stream));
+        if (b->hist) HIP_OK(hipMemcpyAsync(b->hist_of(slot) + start_pos, b->tokens, n * 4, hipMemcpyDeviceToDevice, c->stream));     // the record: the run as it stands on the device
         if (batch_state(c)) return -1;
         PassForm form; form.skinny = n < kShortPassMax; form.k_cache = b->k_of(slot); form.v_cache = b->v_of(slot);
         return prefill_chunks(c, form, start_pos, n, [&](size_t i0, int m) { return token_rows(c, b->tokens + i0, m); }, [](size_t, int) { return 0; });
@@ -2342,6 +2479,7 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
             if (pages_enqueue(b, acts, dirty)) return batch_failed(c);
             if (part_dst && copy_rows(part_dst, 0, n_pos - part_p0, b->page_k(part_src), b->page_v(part_src), PL)) return batch_failed(c);
         }
+        if (history_fork(b, src_slot, dst_slot, n_pos)) return batch_failed(c);
         HIP_OK(hipStreamSynchronize(c->stream));
         return 0;
     }
@@ -2349,7 +2487,7 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpy2DAsync(b->k_of(dst_slot), S * 16, b->k_of(src_slot), S * 16, (size_t)n_pos * 16, (size_t)a.n_layers * kv / 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_OK(hipMemcpy2DAsync(b->v_of(dst_slot), S * kv * 4, b->v_of(src_slot), S * kv * 4, (size_t)n_pos * kv * 4, a.n_layers, hipMemcpyDeviceToDevice, c->stream));
-        return 0;
+        return history_fork(b, src_slot, dst_slot, n_pos);
     };
     if (enqueue()) return batch_failed(c);
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -2377,6 +2515,7 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
     for (size_t r = 0; r < R; ++r) {
         const int j = order[r];
         h->off[r] = b->off_of(slot[rows[j].run]); h->pos[r] = (int)rows[j].pos; h->tok[r] = rows[j].word;
+        if (b->hist) b->h_hist_slot[r] = (int)slot[rows[j].run];
         at[j] = (int)r;
     }
     size_t o = 0;
@@ -2384,11 +2523,12 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
         const uint32_t len = run_len ? run_len[i] : 1u, no = n_out ? n_out[i] : 1u;
         for (uint32_t u = len - no; u < len; ++u) {
             if (b->n_masked) b->h_mask_of[o] = b->mask_row_of(slot[i]);     // (the classifier sees the outputs in this order)
+            if (b->n_pen) b->h_pen_of[o] = b->penalty_row_of(slot[i], at[j + u]);
             h->sel[o++] = (uint32_t)at[j + u];
         }
         j += len;
     }
-    b->mask_live = false;
+    b->mask_live = false; b->pen_live = false;
     *rows_out = R; *outs = o;
 }
 // One pass over the device's long table as it stands: R rows through the layers, then the O rows of sel through the final norm and the classifier to
@@ -2429,10 +2569,11 @@ static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink t
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
     form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view();
+    if (record_rows(b, form.runs.pos, form.runs.tok, R)) return -1;
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
-    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view();
+    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view(); cls.penalties = b->penalty_view(form.runs.pos, form.max_T);
     to.targets = false;
     return classify_rows(c, cls, to, b->runs_x, 0, (int)O);
 }
@@ -2459,8 +2600,20 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
         const int i = order[r];
         b->h_tab->off[r] = b->off_of(slot[i]); b->h_tab->pos[r] = (int)pos[i]; b->h_tab->tok[r] = tokens[i];
         if (b->n_masked) b->h_mask_of[r] = b->mask_row_of(slot[i]);
+        if (b->hist) b->h_hist_slot[r] = (int)slot[i];
+        if (b->n_pen) b->h_pen_of[r] = b->penalty_row_of(slot[i], (int)r);
     }
-    b->mask_live = false;
+    b->mask_live = false; b->pen_live = false;
+    return 0;
+}
+// The record's columns of a call beside its table (a batch without the record enqueues nothing here): the slot of every one of the table's R rows, and - only
+// when one of the O output rows is penalised - the penalty column, which the pass's forms then carry (lmrs_batch::penalty_view)
+static int record_enqueue(lmrs_batch* b, size_t R, size_t O) {
+    if (!b->hist) return 0;
+    HIP_OK(hipMemcpyAsync(b->hist_slot, b->h_hist_slot, R * sizeof(int), hipMemcpyHostToDevice, b->c->stream));
+    if (!b->n_pen || !std::any_of(b->h_pen_of.get(), b->h_pen_of + O, [](const PenaltyRow& r) { return r.slot >= 0; })) return 0;
+    HIP_OK(hipMemcpyAsync(b->pen_of, b->h_pen_of, O * sizeof(PenaltyRow), hipMemcpyHostToDevice, b->c->stream));
+    b->pen_live = true;
     return 0;
 }
 // The mask column of a call with n output rows, beside its table: uploaded - and the pass's forms carry it (lmrs_batch::mask_view) - only when one of the
@@ -2476,7 +2629,8 @@ static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logit
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
     if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); }
-    form.masks = b->mask_view();
+    form.masks = b->mask_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T);
+    if (record_rows(b, b->tab->pos, b->tab->tok, n)) return -1;
     RowSink to{0, n, out_logits, 0}; to.targets = false;
     return run_tokens(c, to, form, /*batched=*/true);
 }
@@ -2493,7 +2647,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
         const HostScores hs = host_scores(c);
         auto enqueue = [&]() -> int {
             HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-            if (masks_enqueue(b, n) || batch_state(c)) return -1;
+            if (masks_enqueue(b, n) || record_enqueue(b, n, n) || batch_state(c)) return -1;
             RowSink to{0, n, logits, 0}; to.reduce_too = true;
             if (runs_pass(b, n, n, 0, to)) return -1;
             HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2506,7 +2660,7 @@ extern "C" int lmrs_batch_forward(lmrs_batch* b, uint32_t n, const uint32_t* slo
     std::vector<float> rows(logits ? n * V : 0);         // the pass's rows in table order
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (masks_enqueue(b, n) || batch_state(c)) return -1;
+        if (masks_enqueue(b, n) || record_enqueue(b, n, n) || batch_state(c)) return -1;
         if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx
         if (logits && copy_out_rows(c, RowSink{0, n, rows.data(), 0}, c->sc_logits, cls_rows(c), (int)n, 0)) return -1;
         HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2533,7 +2687,7 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     auto enqueue = [&]() -> int {
         if (wide) HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
         else HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (masks_enqueue(b, n) || batch_state(c)) return -1;       // (the column once: the rows keep their order over the n_new steps)
+        if (masks_enqueue(b, n) || record_enqueue(b, n, n) || batch_state(c)) return -1;       // (the column once: the rows keep their order over the n_new steps)
         HIP_OK(hipEventRecord(c->ev0, c->stream));
         for (uint32_t j = 0; j < n_new && wide; ++j) {
             if (runs_pass(b, n, n, j, RowSink{0, n, nullptr, 0})) return -1;
@@ -2630,7 +2784,7 @@ extern "C" int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32
     for (uint32_t r = 0; r < n; ++r) { at[order[r]] = (int)r; if (sampled) b->samp.h_tab[r] = par[order[r]]; }
     auto enqueue = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (masks_enqueue(b, n) || batch_state(c)) return -1;
+        if (masks_enqueue(b, n) || record_enqueue(b, n, n) || batch_state(c)) return -1;
         if (batch_pass(b, n, 0, nullptr)) return -1;     // the reduction: sample_argmax of every row -> sc_idx; the rows stay in sc_logits
         if (!sampled) { HIP_OK(hipMemcpyAsync(b->h_out, c->sc_idx, n * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
         return sample_enqueue(c, b->samp, n);
@@ -2737,7 +2891,7 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     auto enqueue = [&]() -> int {
         if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * a.dim * 4, hipMemcpyHostToDevice, c->stream));     // the call's embedding rows, in caller order
         HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-        if (masks_enqueue(b, O) || batch_state(c)) return -1;
+        if (masks_enqueue(b, O) || record_enqueue(b, R, O) || batch_state(c)) return -1;
         RowSink to{0, O, logits, k}; to.reduce_too = true;
         if (runs_pass(b, R, O, 0, to, E ? b->embed_stage : nullptr)) return -1;
         if (!O) return 0;
@@ -2793,14 +2947,15 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
         const bool block = paged_block_route(b, m, p0);
         if (block) {                                     // block attention: the table's rows in POSITION order (row r = position p0 + r), no outputs
             RunTable* h = b->h_runs;
-            for (uint32_t r = 0; r < m; ++r) { h->off[r] = b->off_of(slot); h->pos[r] = (int)(p0 + r); h->tok[r] = embeddings ? kRowFromStage | r : tokens[i0 + r]; }
-            b->mask_live = false;
+            for (uint32_t r = 0; r < m; ++r) { h->off[r] = b->off_of(slot); h->pos[r] = (int)(p0 + r); h->tok[r] = embeddings ? kRowFromStage | r : tokens[i0 + r]; if (b->hist) b->h_hist_slot[r] = (int)slot; }
+            b->mask_live = false; b->pen_live = false;
         } else runs_table(b, 1, &slot, &p0, &m, &n_out, RunRows{&kind, tokens ? tokens + i0 : nullptr, embeddings}, &R, &O);
         auto enqueue = [&]() -> int {
             if (embeddings) HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
             HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-            if (set_state(c, embeddings ? start_pos : 0, 0, win)) return -1;
+            if (record_enqueue(b, m, 0) || set_state(c, embeddings ? start_pos : 0, 0, win)) return -1;
             if (block) {
+                if (record_rows(b, b->runs->pos, b->runs->tok, m)) return -1;                // (the table pass records in runs_pass)
                 // the GEMM forms of a contiguous batch's chunk (m >= 16: never the skinny ones), the qkv block and the scatter of the table pass
                 PassForm form; form.runs = b->runs_view(); form.qkv = b->runs_qkv; form.k_cache = b->kv; form.v_cache = b->kv + b->page_floats;
                 form.pages = b->page_view(); form.block_pos0 = (int)p0; form.block_row = slot;
@@ -2884,7 +3039,7 @@ static int forward_runs_sample_from(const std::string& what, lmrs_batch* b, uint
     auto enqueue = [&]() -> int {
         if (E) HIP_OK(hipMemcpyAsync(b->embed_stage, src.embeddings, E * c->args.dim * 4, hipMemcpyHostToDevice, c->stream));
         HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-        if (masks_enqueue(b, O) || batch_state(c)) return -1;
+        if (masks_enqueue(b, O) || record_enqueue(b, R, O) || batch_state(c)) return -1;
         if (runs_pass(b, R, O, 0, RowSink{0, O, nullptr, 0}, E ? b->embed_stage : nullptr)) return -1;          // the reduction: sample_argmax of every output row -> sc_idx; the rows stay in sc_logits
         if (!O) return 0;
         if (!sampled) { HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, O * 4, hipMemcpyDeviceToHost, c->stream)); return 0; }
@@ -2969,7 +3124,7 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
         auto enqueue = [&]() -> int {
             HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings, dim * 4, hipMemcpyHostToDevice, c->stream));
             HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
-            if (set_state(c, start_pos, 0, win)) return -1;
+            if (record_enqueue(b, 1, 0) || set_state(c, start_pos, 0, win)) return -1;
             if (runs_pass(b, 1, 0, 0, RowSink{0, 0, nullptr, 0}, b->embed_stage)) return -1;
             if (residual) HIP_OK(hipMemcpyAsync(residual, c->pf_x, dim * 4, hipMemcpyDeviceToHost, c->stream));
             return 0;
@@ -2978,6 +3133,7 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
     }
     auto enqueue = [&]() -> int {
         if (set_state(c, start_pos, 0, win)) return -1;
+        if (b->hist) HIP_OK(hipMemsetAsync(b->hist_of(slot) + start_pos, 0xFF, (size_t)n * 4, c->stream));       // the record: embedding rows have no token
         PassForm form; form.skinny = n < kShortPassMax; form.k_cache = b->k_of(slot); form.v_cache = b->v_of(slot);
         auto upload_rows = [&](size_t i0, int m) -> int {
             HIP_OK(hipMemcpyAsync(c->pf_x, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));

@@ -51,4 +51,19 @@ hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStr
 // the block 16-byte aligned.  (lmrs_batch_set_masks: behind the soft-cap, in front of every sink)
 hipError_t launch_mask_rows(float* logits, int ld, int cols, int rows, const uint32_t* bits, int words, const int* mask_of, hipStream_t s);
 
+// ---- a batch's token record and the penalties over it (lmrs_batch_set_history / lmrs_batch_set_penalties)
+constexpr uint32_t kTokenNone = 0xFFFFFFFFu;                // = LMRS_TOKEN_NONE: a position whose token is unknown, or an embedding row
+constexpr int kPenaltyKeysMax = 8192;                       // the keys one workgroup sorts in LDS (32 KB): the clamp of seq_len
+// hist[slot_of[r] * seq_len + pos[r]] = tok[r] for r < n_rows, kTokenNone where tok[r] has the stage bit of an embedding row (kRowFromStage); a row whose
+// slot or position lies outside [0, n_slots) x [0, seq_len) writes nothing.  pos / tok are the columns of the pass's device table as they stand.
+hipError_t launch_record_rows(uint32_t* hist, int seq_len, int n_slots, const int* pos, const uint32_t* tok, const int* slot_of, int n_rows, hipStream_t s);
+// One output row's penalties, in the order the classifier sees the rows: slot < 0 - none; tab_row - the row of the pass's device table whose position is the row's
+struct PenaltyRow { int slot; int tab_row; float repetition, presence, frequency; uint32_t out_from; };
+// Row r < rows of the block with of[r].slot >= 0, at position p = pos[of[r].tab_row] (read on the device): over H = the entries of hist[slot][0 .. p] that are not
+// kTokenNone, c_all[t] = occurrences of t, c_out[t] = those at positions >= out_from; for every t with c_all[t] > 0 and repetition != 1,
+// l[t] = l[t] > 0 ? l[t] / repetition : l[t] * repetition; then for every t with c_out[t] > 0, l[t] = (l[t] - frequency * (float)c_out[t]) - presence - each
+// operation one correctly rounded f32 operation, nothing contracted.  No other logit is read or written, each penalised one by exactly one thread, and the
+// counts are integers: the result does not depend on scheduling.  max_n >= every row's p + 1, at most min(seq_len, kPenaltyKeysMax): sizes the launch's LDS.
+hipError_t launch_penalty_rows(float* logits, int ld, int cols, int rows, const uint32_t* hist, int seq_len, const int* pos, const PenaltyRow* of, int max_n, hipStream_t s);
+
 }  // namespace lmrs

@@ -16,6 +16,10 @@
 //
 // mask_rows_kernel: a batch slot's allowed-token mask (lmrs_batch_set_masks) over the rows of the block, behind the soft-cap and in front of every
 // sink: -inf over the disallowed logits.  Stores only.
+//
+// record_rows_kernel / penalty_rows_kernel: a batch's token record per slot and the repetition / presence / frequency penalties over it
+// (lmrs_batch_set_penalties), between the soft-cap and the mask: one workgroup a penalised row sorts the row's record in LDS and changes one logit per
+// distinct token.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -318,7 +322,86 @@ __global__ __launch_bounds__(kLanes) void mask_rows_kernel(float* logits, int ld
     if (!(allowed & 8u)) p[3] = ninf;
 }
 
+// The token record of a batch (lmrs_batch_set_history): table row r wrote K/V at position pos[r] of slot slot_of[r], so hist[slot][pos] = its token -
+// kTokenNone for an embedding row (a source word with the stage bit, lmrs_kernels.h).  One lane a row; two rows of one launch never share a (slot, position).
+__global__ __launch_bounds__(kLanes) void record_rows_kernel(uint32_t* hist, int seq_len, int n_slots, const int* pos, const uint32_t* tok, const int* slot_of, int n_rows) {
+    const int r = blockIdx.x * kLanes + threadIdx.x;
+    if (r >= n_rows) return;
+    const int s = slot_of[r], p = pos[r];
+    if (s < 0 || s >= n_slots || p < 0 || p >= seq_len) return;
+    const uint32_t w = tok[r];
+    hist[(size_t)s * seq_len + p] = (w & 0x80000000u) ? kTokenNone : w;
+}
+
+// Row blockIdx.x of the block under the penalties of its slot (lmrs_batch_set_penalties; rows[blockIdx.x].slot < 0: none, the workgroup leaves).  p = the
+// position of the row as the device table has it NOW (pos[rows[..].tab_row]: inside lmrs_batch_generate_greedy's loop the host does not know it).
+// 1. the record hist[slot][0 .. p] into LDS as keys (token << 1) | (i >= out_from), kTokenNone as the all-ones key, padded with it to a power of two;
+// 2. a bitonic network over the keys, ascending: the occurrences of a token become one run, those in front of out_from first;
+// 3. the lane that holds the head of a run finds the run's end and the first key of it with the low bit by binary search - c_all and c_out are differences of
+//    indices, integers whatever the order the lanes arrive in - and is the ONE thread that reads, changes and writes that logit: an IEEE division or a
+//    product, then a product, a difference and a difference, each rounded once (the object is built with -ffp-contract=off).
+// cap: the power of two the launch's LDS holds, >= every row's p + 1.
+__global__ __launch_bounds__(kLanes) void penalty_rows_kernel(float* logits, int ld, int cols, const uint32_t* hist, int seq_len, const int* pos, const PenaltyRow* rows, int cap) {
+    extern __shared__ uint32_t keys[];
+    const PenaltyRow pr = rows[blockIdx.x];
+    if (pr.slot < 0) return;
+    const int p = pos[pr.tab_row];
+    if (p < 0 || p >= seq_len || p >= cap) return;
+    int N = 2;
+    while (N < p + 1) N <<= 1;
+    const uint32_t* h = hist + (size_t)pr.slot * seq_len;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < N; i += kLanes) {
+        const uint32_t t = i <= p ? h[i] : kTokenNone;
+        keys[i] = t == kTokenNone ? kTokenNone : (t << 1 | ((uint32_t)i >= pr.out_from ? 1u : 0u));
+    }
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < N / 2; t += kLanes) {
+                const int lo = 2 * t - (t & (j - 1)), hi = lo + j;                  // the t-th pair of the stage: lo has bit j clear
+                const uint32_t a = keys[lo], b = keys[hi];
+                if ((a > b) == ((lo & k) == 0)) { keys[lo] = b; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    float* row = logits + (size_t)blockIdx.x * ld;
+    for (int i = tid; i < N; i += kLanes) {
+        const uint32_t key = keys[i];
+        if (key == kTokenNone) continue;
+        const uint32_t t = key >> 1;
+        if ((i > 0 && keys[i - 1] >> 1 == t) || t >= (uint32_t)cols) continue;
+        // first index in (i, N] whose key is >= bound (the padding is above every token's keys)
+        auto first_at_least = [&](uint32_t bound) {
+            int a = i, b = N;
+            while (a < b) { const int mid = (a + b) >> 1; if (keys[mid] < bound) a = mid + 1; else b = mid; }
+            return a;
+        };
+        const int end = first_at_least((t + 1) << 1), out0 = first_at_least(t << 1 | 1u);
+        const int c_out = end - out0;                                               // (c_all = end - i >= 1: the head itself)
+        float l = row[t];
+        if (pr.repetition != 1.0f) l = l > 0.0f ? __fdiv_rn(l, pr.repetition) : __fmul_rn(l, pr.repetition);
+        if (c_out > 0) l = __fsub_rn(__fsub_rn(l, __fmul_rn(pr.frequency, (float)c_out)), pr.presence);
+        row[t] = l;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_record_rows(uint32_t* hist, int seq_len, int n_slots, const int* pos, const uint32_t* tok, const int* slot_of, int n_rows, hipStream_t s) {
+    if (!hist || !pos || !tok || !slot_of || seq_len <= 0 || n_slots <= 0 || n_rows <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(record_rows_kernel, dim3((n_rows + kLanes - 1) / kLanes), dim3(kLanes), 0, s, hist, seq_len, n_slots, pos, tok, slot_of, n_rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_penalty_rows(float* logits, int ld, int cols, int rows, const uint32_t* hist, int seq_len, const int* pos, const PenaltyRow* of, int max_n, hipStream_t s) {
+    if (!logits || !hist || !pos || !of || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld || seq_len <= 0 || max_n <= 0 || max_n > seq_len || max_n > kPenaltyKeysMax)
+        return hipErrorInvalidValue;
+    int cap = 2;
+    while (cap < max_n) cap <<= 1;
+    hipLaunchKernelGGL(penalty_rows_kernel, dim3(rows), dim3(kLanes), (size_t)cap * 4, s, logits, ld, cols, hist, seq_len, pos, of, cap);
+    return hipGetLastError();
+}
 
 hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStream_t s) {
     if (!logits || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld) return hipErrorInvalidValue;

@@ -190,6 +190,36 @@ public:
         if (!slot.empty()) check(lmrs_batch_clear_masks(b_, static_cast<std::uint32_t>(slot.size()), slot.data()));
     }
     std::uint32_t mask_info(std::uint32_t slot) const { std::uint32_t n = 0; check(lmrs_batch_mask_info(b_, slot, &n)); return n; }   // the tokens allowed; 0: no mask
+    // Repetition / presence / frequency penalties, state of a slot, over the token record the batch keeps on the device from the first of these calls on
+    // (include/lmrs_hip.h: the rule): tokens the slot has seen anywhere are divided / multiplied by `repetition`, tokens seen at positions >= out_from lose
+    // frequency * count + presence, in front of the slot's mask and of every sink  (lmrs_batch_set_penalties / _clear_penalties / _penalty_info)
+    struct Penalty { float repetition = 1.0f, presence = 0.0f, frequency = 0.0f; std::uint32_t out_from = 0; bool active = false; };
+    static constexpr std::uint32_t TOKEN_NONE = LMRS_TOKEN_NONE;   // the record's word for an unknown token or an embedding row
+    void set_penalties(const std::vector<std::uint32_t>& slot, const std::vector<Penalty>& p) {
+        if (p.size() != slot.size()) throw Panic("Batch::set_penalties: one Penalty per slot");
+        std::vector<float> rep, pres, freq; std::vector<std::uint32_t> from;
+        for (const Penalty& x : p) { rep.push_back(x.repetition); pres.push_back(x.presence); freq.push_back(x.frequency); from.push_back(x.out_from); }
+        check(lmrs_batch_set_penalties(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), rep.data(), pres.data(), freq.data(), from.data()));
+    }
+    void clear_penalties() { check(lmrs_batch_clear_penalties(b_, 0, nullptr)); }                              // every slot
+    void clear_penalties(const std::vector<std::uint32_t>& slot) {
+        if (!slot.empty()) check(lmrs_batch_clear_penalties(b_, static_cast<std::uint32_t>(slot.size()), slot.data()));
+    }
+    Penalty penalty_info(std::uint32_t slot) const {
+        Penalty p; int active = 0;
+        check(lmrs_batch_penalty_info(b_, slot, &p.repetition, &p.presence, &p.frequency, &p.out_from, &active));
+        p.active = active != 0;
+        return p;
+    }
+    // the record of `slot` from start_pos on: written by the caller (positions filled before the record existed; no tokens: only switches it on), read back
+    void set_history(std::uint32_t slot, const std::vector<std::uint32_t>& tokens = {}, std::uint32_t start_pos = 0) {
+        check(lmrs_batch_set_history(b_, slot, start_pos, tokens.empty() ? nullptr : tokens.data(), tokens.size()));
+    }
+    std::vector<std::uint32_t> history(std::uint32_t slot, std::size_t n, std::uint32_t start_pos = 0) {
+        std::vector<std::uint32_t> out(n);
+        check(lmrs_batch_history(b_, slot, start_pos, n, n ? out.data() : nullptr));
+        return out;
+    }
     // the most rows (forward, generate_greedy) and runs (forward_runs) a call takes: 16, or 64 for a wide batch  (lmrs_batch_width)
     std::uint32_t width() const { std::uint32_t w = 0; check(lmrs_batch_width(b_, &w)); return w; }
     Batch(const Batch&) = delete;

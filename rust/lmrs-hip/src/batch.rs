@@ -34,6 +34,28 @@ extern "C" {
     pub fn lmrs_batch_release(b: *mut LmrsBatch, slot: u32, n_pos: u32) -> c_int;
     pub fn lmrs_batch_prefill_form(b: *const LmrsBatch, n: usize, start_pos: u32, n_chunks: *mut u32, n_block: *mut u32) -> c_int;
     pub fn lmrs_batch_debug_prefill_table(b: *mut LmrsBatch, force: c_int) -> c_int;
+    // the token record per slot and the penalties over it: declared here as the paged calls are (tests/test_batch_penalty_host.py compares them with the
+    // header; the batch block of ffi.rs keeps its seven entry points, tests/test_batch.py)
+    pub fn lmrs_batch_set_history(b: *mut LmrsBatch, slot: u32, start_pos: u32, tokens: *const u32, n: usize) -> c_int;
+    pub fn lmrs_batch_history(b: *mut LmrsBatch, slot: u32, start_pos: u32, n: usize, out: *mut u32) -> c_int;
+    pub fn lmrs_batch_set_penalties(b: *mut LmrsBatch, n: u32, slot: *const u32, repetition: *const f32, presence: *const f32,
+                                    frequency: *const f32, out_from: *const u32) -> c_int;
+    pub fn lmrs_batch_clear_penalties(b: *mut LmrsBatch, n: u32, slot: *const u32) -> c_int;
+    pub fn lmrs_batch_penalty_info(b: *const LmrsBatch, slot: u32, repetition: *mut f32, presence: *mut f32, frequency: *mut f32,
+                                   out_from: *mut u32, active: *mut c_int) -> c_int;
+}
+
+/// The record's word for a position whose token is unknown, or an embedding row (`LMRS_TOKEN_NONE`).
+pub const TOKEN_NONE: u32 = 0xFFFF_FFFF;
+
+/// A slot's penalties (`Batch::set_penalties`): tokens the slot has seen anywhere are divided / multiplied by `repetition`, tokens seen at positions
+/// `>= out_from` lose `frequency * count + presence` (include/lmrs_hip.h: the rule).
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct Penalty {
+    pub repetition: f32,
+    pub presence: f32,
+    pub frequency: f32,
+    pub out_from: u32,
 }
 
 /// What a run of `Batch::forward_runs_embed` feeds: token ids, or rows of `dim` floats taken as `Transformer::fill_kv_cache` takes them.
@@ -130,6 +152,41 @@ impl<'t, 'a> Batch<'t, 'a> {
         let mut w = 0u32;
         check(unsafe { lmrs_batch_width(self.b, &mut w) });
         w
+    }
+
+    /// Penalties for `slot[i]`, state of the slots until replaced or cleared: every output of their rows in any call here comes from the row's logits
+    /// changed over the tokens the slot has seen.  The first call switches the batch's token record on.
+    pub fn set_penalties(&mut self, slot: &[u32], penalties: &[Penalty]) {
+        assert!(slot.len() == penalties.len(), "one Penalty per slot");
+        let rep: Vec<f32> = penalties.iter().map(|p| p.repetition).collect();
+        let pres: Vec<f32> = penalties.iter().map(|p| p.presence).collect();
+        let freq: Vec<f32> = penalties.iter().map(|p| p.frequency).collect();
+        let from: Vec<u32> = penalties.iter().map(|p| p.out_from).collect();
+        check(unsafe { lmrs_batch_set_penalties(self.b, slot.len() as u32, slot.as_ptr(), rep.as_ptr(), pres.as_ptr(), freq.as_ptr(), from.as_ptr()) });
+    }
+
+    /// The named slots lose their penalties; an empty list: every slot.
+    pub fn clear_penalties(&mut self, slot: &[u32]) {
+        check(unsafe { lmrs_batch_clear_penalties(self.b, slot.len() as u32, if slot.is_empty() { ptr::null() } else { slot.as_ptr() }) });
+    }
+
+    /// `slot`'s penalties as set, and whether they change a logit.
+    pub fn penalty_info(&self, slot: u32) -> (Penalty, bool) {
+        let (mut p, mut active) = (Penalty { repetition: 1.0, presence: 0.0, frequency: 0.0, out_from: 0 }, 0 as c_int);
+        check(unsafe { lmrs_batch_penalty_info(self.b, slot, &mut p.repetition, &mut p.presence, &mut p.frequency, &mut p.out_from, &mut active) });
+        (p, active != 0)
+    }
+
+    /// The token record of `slot` from `start_pos` on = `tokens` (`TOKEN_NONE`: unknown); no tokens: only switches the record on.
+    pub fn set_history(&mut self, slot: u32, tokens: &[u32], start_pos: u32) {
+        check(unsafe { lmrs_batch_set_history(self.b, slot, start_pos, if tokens.is_empty() { ptr::null() } else { tokens.as_ptr() }, tokens.len()) });
+    }
+
+    /// The token record of `slot` at positions `start_pos .. start_pos + n`; panics on a batch that keeps no record.
+    pub fn history(&mut self, slot: u32, n: usize, start_pos: u32) -> Vec<u32> {
+        let mut out = vec![0u32; n];
+        check(unsafe { lmrs_batch_history(self.b, slot, start_pos, n, if n == 0 { ptr::null_mut() } else { out.as_mut_ptr() }) });
+        out
     }
 
     /// `Transformer::prefill_tokens` into `slot`'s cache.
