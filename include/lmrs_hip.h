@@ -555,8 +555,8 @@ int lmrs_forward_sample(lmrs_ctx* ctx, uint32_t token, uint32_t pos, lmrs_sample
  * cost.  Top-p rows finish on the host in row order - lmrs_sampler_topp_pairs, each sampler's persistent vector updated exactly as that call
  * updates it; a row with 4096 candidates or more (a flat distribution) first has them sorted on the device (as lmrs_forward_sample does), one
  * such row at a time behind a second synchronise, and finishes through lmrs_sampler_topp_sorted_pairs.
- * There is no device-resident sampled loop: sample_topp's stale candidate vector lives in the host sampler, so a loop that includes the default
- * sampler cannot run a step without a host round trip.
+ * There is no device-resident sampled loop for top-p rows (lmrs_batch_generate is that loop for argmax and sample_mult rows): sample_topp's stale
+ * candidate vector lives in the host sampler, so a loop that includes the default sampler cannot run a step without a host round trip.
  * Errors, each with a message of its own, before any device work, batch, context and samplers left usable: everything lmrs_batch_forward checks;
  * a NULL array; a NULL sampler (the row is named); a sampler made for another vocabulary size; a top-p sampler that appears twice in one call (it
  * carries state; argmax and sample_mult samplers are stateless and may be shared); a vocabulary whose last vocab_size % 4 logits the classifier
@@ -576,7 +576,7 @@ int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, c
  * through lmrs_sampler_topp_pairs; the rows with 4096 candidates or more (flat distributions) are first sorted on the device ALL TOGETHER - keys
  * straight from the candidates the filter left, one bitonic network with the row in the grid's second dimension, the rows padded to the power of two
  * that holds the longest - behind ONE second synchronise however many they are, and finish through lmrs_sampler_topp_sorted_pairs.  The host
- * finishes do not overlap the copies.  There is no device-resident loop, for the reason given above.
+ * finishes do not overlap the copies.  The device-resident loop (lmrs_batch_generate) takes no top-p row, for the reason given above.
  * Errors, each with a message of its own that opens with this call's name, before any device work, batch, context and samplers left usable:
  * everything lmrs_batch_forward_runs checks for these arguments; a NULL array; a sampler made for another vocabulary size (the run is named); a
  * top-p sampler in two runs of one call; a sampled (temperature != 0) output on a vocabulary whose last vocab_size % 4 logits the classifier leaves
@@ -697,6 +697,49 @@ int lmrs_batch_set_penalties(lmrs_batch* b, uint32_t n, const uint32_t* slot, co
 int lmrs_batch_clear_penalties(lmrs_batch* b, uint32_t n, const uint32_t* slot);
 int lmrs_batch_penalty_info(const lmrs_batch* b, uint32_t slot, float* repetition, float* presence, float* frequency,
                             uint32_t* out_from, int* active);
+
+/* ---- the device loop whose rows end one by one: stop sets, budgets, samplers, log-probabilities (extension) ----
+ * lmrs_batch_generate_greedy with the loop's own control.  Row i starts with t_0 = tokens[i]; for j = 0, 1, ...:
+ *   1. Transformer::forward(t_j, pos[i] + j) runs on slot[i];
+ *   2. o_j is chosen from the row as the sinks see it - the slot's penalties, then its mask, exactly as in every other batch call - by
+ *      Sampler::sample (sampler.rs:109-129) with samplers[i], or Sampler::sample_argmax (:29-41) for a NULL entry (samplers NULL: every row);
+ *   3. out_tokens[i*M + j] = o_j, M = the largest max_new of the call;
+ *   4. o_j in row i's stop set: the row ends, finish[i] = LMRS_FINISH_STOP;
+ *   5. else j + 1 == max_new[i]: the row ends, finish[i] = LMRS_FINISH_BUDGET;
+ *   6. else t_{j+1} = o_j.
+ * n_out[i] = j + 1 at the end.  STOP wins when both hold; the stop token is reported and never fed (the loop of chat.rs:188-222 on EOS).
+ * Every token is, bit for bit, what the per-sequence calls give - lmrs_forward_argmax or lmrs_forward_sample on a context that holds only that
+ * sequence; with no stop sets, NULL samplers and equal budgets out_tokens is lmrs_batch_generate_greedy's.  Results do not depend on check_every.
+ * A finished row leaves its slot exactly as n_out[i] feeds leave it: K/V rows and record entries pos[i] .. pos[i] + n_out[i] - 1 are written, and
+ * no K/V row, record entry or page-table entry at or beyond pos[i] + n_out[i] changes through the row's own progress.  On a paged batch the pages
+ * of [pos[i], pos[i] + max_new[i]) are claimed up front, per row, all or nothing, under the accounting of every other call; the pages an early stop
+ * did not reach stay with the slot, cleared, until lmrs_batch_release(slot, pos[i] + n_out[i]) gives them back.
+ * Stop sets: n_stop[i] <= LMRS_STOP_MAX tokens of row i, packed in row order in stop_tokens (n_stop NULL: no row has one).
+ * Samplers: argmax (temperature 0) and sample_mult (top_p <= 0 or >= 1) samplers; being stateless they may be shared between rows (the reference never
+ * advances its seed, sampler.rs:119, so the loop carries no generator state).  A top-p sampler is refused, the row named: sample_topp's stale candidate
+ * vector lives in the host sampler (sampler.rs:81), so a step with such a row cannot do without a host round trip.  Sampled rows: up to the batch's width.
+ * out_logprobs (may be NULL: the loop then enqueues nothing for it), same layout as out_tokens: the log-softmax of that same row (penalised, masked,
+ * temperature 1) at o_j by lmrs_score_tokens' definition - the f32 maximum widened to double, the sum in double over all vocabulary entries, one
+ * rounding to float.  Entries beyond n_out[i] of both blocks are written as 0.
+ * The loop: check_every passes are enqueued, each followed by ONE launch that records the chosen tokens, tests them against the stop sets and budgets
+ * and moves the live rows on; then the host reads the rows' states and goes on with a table of the live rows alone (the pass forms follow the row
+ * count as in every call: 17 rows and more the long table, fewer the 16-row table).  A row that has ended inside a chunk computes its last row again -
+ * the same bits into the same places.  stats2 (may be NULL): [0] = passes run = the largest ceil(n_out[i] / check_every) * check_every, [1] = the sum
+ * over the passes of the rows in the pass = the sum over rows of that quantity.  *seconds (may be NULL): host wall time of the call.
+ * Errors, each with a message of its own that opens with the call's name, before any device work, batch, context and samplers left usable:
+ * everything lmrs_batch_generate_greedy checks, with pos[i] + max_new[i] against seq_len; a NULL required array; max_new[i] == 0; n_stop[i] >
+ * LMRS_STOP_MAX; n_stop given without stop_tokens; a stop token >= vocab_size; check_every == 0; a top-p sampler; a sampler for another vocabulary
+ * size; a sampled row, or out_logprobs, on a model whose classifier leaves a vocabulary tail unwritten (or with more rows than the logits block
+ * holds); too few free pages - the message gives the pages wanted and the pages free, and nothing has changed.
+ * Buffers of this call's own, allocated at first need, all or nothing: the rows' state blocks; n * M floats (and as many pinned) for
+ * out_logprobs, made anew when a call needs more; rows * (vocab_size + 1) * 8 bytes of result blocks for sampled rows in whole sixteens, and rows * vocab_size floats more when sampled
+ * rows and out_logprobs meet (the samplers then work on a copy of the logits).  The buffers of the other sampled calls are not touched. */
+#define LMRS_STOP_MAX 16
+enum { LMRS_FINISH_BUDGET = 0, LMRS_FINISH_STOP = 1 };
+int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
+                        const uint32_t* max_new, const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers,
+                        uint32_t check_every, uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish,
+                        uint64_t* stats2, double* seconds);
 
 #ifdef __cplusplus
 }

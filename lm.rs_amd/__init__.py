@@ -35,6 +35,7 @@ EXPORTS = [
     "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
+    "lmrs_batch_generate",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -131,6 +132,7 @@ def lib():
         L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
         L.lmrs_batch_forward.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.lmrs_batch_generate_greedy.argtypes = [vp, u32, vp, vp, vp, u32, vp, C.POINTER(C.c_double)]
+        L.lmrs_batch_generate.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
         L.lmrs_batch_debug_kv.argtypes = [vp, u32, C.c_int, u32, u32, vp]
         L.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
         L.lmrs_batch_forward_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp]
@@ -428,6 +430,8 @@ def unpack_mask(words, vocab_size: int) -> np.ndarray:
 
 BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BATCH_CTX)
 TOKEN_NONE = 0xFFFFFFFF       # Batch.history / set_history: a position whose token is unknown, or an embedding row (LMRS_TOKEN_NONE)
+STOP_MAX = 16                 # Batch.generate: the most stop tokens a row takes (LMRS_STOP_MAX)
+FINISH_BUDGET, FINISH_STOP = 0, 1     # Batch.generate's finish codes (LMRS_FINISH_BUDGET / LMRS_FINISH_STOP)
 
 
 class Batch:
@@ -706,6 +710,48 @@ class Batch:
         out = np.zeros((s.size, n_new), np.uint32); sec = C.c_double()
         _chk(lib().lmrs_batch_generate_greedy(self._h, s.size, _p(s), _p(t), _p(p), n_new, _p(out), C.byref(sec)))
         return (out, sec.value) if timing else out
+
+    def generate(self, slots, tokens, pos, max_new, stop=None, samplers=None, check_every: int = 4, logprobs: bool = False, timing: bool = False):
+        """The device loop whose rows end one by one: row i feeds tokens[i] at pos[i] of slots[i] and goes on with what it chose - Sampler.sample with
+        samplers[i], the argmax for None (samplers=None: every row) - until it chooses a token of its stop set (finish STOP; the token is reported, never
+        fed) or has produced max_new[i] tokens (BUDGET).  max_new: one budget per row, or a scalar for all.  stop: a list of token lists, one per row, or
+        one list of tokens for all rows; at most STOP_MAX tokens a row.  Samplers: argmax and sample_mult ones (top-p is refused); they may be shared.
+        check_every: passes between two looks at the rows' state - the results do not depend on it.
+        -> (tokens, finish[, logprobs], stats): tokens a list of uint32 arrays, row i cut to its n_out; finish uint32 [n] (FINISH_BUDGET /
+        FINISH_STOP); logprobs a list of float32 arrays of the same lengths - log softmax of the row each token was chosen from, at that token; stats a
+        dict: passes, row_passes (and seconds, host wall time, if timing)  (lmrs_batch_generate)"""
+        s, t, p = self._rows(slots, tokens, pos)
+        n = s.size
+        mx = np.asarray(max_new)
+        mx = np.ascontiguousarray(np.full(n, mx) if mx.ndim == 0 else mx.reshape(-1), np.uint32)
+        if mx.size != n:
+            raise LmrsError("max_new must be a scalar or hold one budget per row")
+        ns, st = None, None
+        if stop is not None:
+            sets = list(stop)
+            if not (len(sets) == n and all(hasattr(x, "__len__") for x in sets)):     # one list for all rows
+                if any(hasattr(x, "__len__") for x in sets):
+                    raise LmrsError("stop must be one list of tokens, or one list of tokens per row")
+                sets = [sets] * n
+            ns = np.array([len(x) for x in sets], np.uint32)
+            st = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint32).reshape(-1) for x in sets]) if n else [], np.uint32)
+        if samplers is not None and len(samplers) != n:
+            raise LmrsError("samplers must have one entry per row (None: the argmax)")
+        hs = None if samplers is None else (C.c_void_p * max(n, 1))(*[None if x is None else x._h for x in samplers])
+        M = int(mx.max()) if n else 0
+        out = np.zeros((n, max(M, 1)), np.uint32)
+        lp = np.zeros((n, max(M, 1)), np.float32) if logprobs else None
+        n_out, fin = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        stats2, sec = np.zeros(2, np.uint64), C.c_double()
+        _chk(lib().lmrs_batch_generate(self._h, n, _p(s), _p(t), _p(p), _p(mx), None if ns is None else _p(ns), _p(st) if st is not None and st.size else None,
+                                       None if hs is None else C.cast(hs, C.c_void_p), check_every, _p(out), _p(lp) if logprobs else None, _p(n_out), _p(fin),
+                                       _p(stats2), C.byref(sec)))
+        stats = dict(passes=int(stats2[0]), row_passes=int(stats2[1]))
+        if timing:
+            stats["seconds"] = sec.value
+        toks = [out[i, :n_out[i]].copy() for i in range(n)]
+        res = (toks, fin) + (([lp[i, :n_out[i]].copy() for i in range(n)],) if logprobs else ()) + (stats,)
+        return res
 
     def kv_row(self, slot: int, which: int, layer: int, pos: int) -> np.ndarray:
         """Transformer.kv_row of `slot`'s cache (lmrs_batch_debug_kv)"""

@@ -2064,6 +2064,13 @@ struct lmrs_batch {
     struct Penalty { float repetition = 1.0f, presence = 0.0f, frequency = 0.0f; uint32_t out_from = 0; };
     Penalty pen[kWideBatchMax]; bool pen_on[kWideBatchMax] = {}; uint32_t n_pen = 0;
     DevBuf<PenaltyRow> pen_of; PinBuf<PenaltyRow> h_pen_of; bool pen_live = false;
+    // lmrs_batch_generate (made at its first call; gen_st non-null: the set stands): the rows' state blocks beside the pass's table and their pinned mirror, the
+    // live-row count and its pinned copy; `out` / `h_out` take the tokens [n][M].  gen_lp / h_gen_lp: the log-probabilities' block of the same layout (made at
+    // the first call that asks for them, n * M words, made anew when a call needs more).  gen: the call's own sampling set (whole sixteens, as rs); gen_logits: the copy of the logits block the samplers
+    // work on when a call wants log-probabilities too (gen_logits_rows rows)
+    DevBuf<GenRow> gen_st; PinBuf<GenRow> h_gen_st; DevBuf<uint32_t> gen_live; PinBuf<uint32_t> h_gen_live;
+    DevBuf<float> gen_lp; PinBuf<float> h_gen_lp;
+    SampleSet gen; DevBuf<float> gen_logits; size_t gen_logits_rows = 0;
     uint32_t* hist_of(uint32_t slot) const { return hist + (size_t)slot * c->args.seq_len; }
     PenaltyRow penalty_row_of(uint32_t slot, int tab_row) const {
         const Penalty& p = pen[slot];
@@ -3097,6 +3104,158 @@ extern "C" int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_ru
     if (!b) return fail(what + "NULL argument (the batch)");
     if (!slot || !start_pos || !run_len || !run_kind || !samplers || !next) return fail(what + "NULL array");
     return forward_runs_sample_from(what, b, n_runs, slot, start_pos, run_len, RunRows{run_kind, tokens, embeddings}, samplers, next);
+}
+
+// ------------------------------------------------------------------ the device loop whose rows end one by one: lmrs_batch_generate
+// (per row the loop of chat.rs:188-222 over Transformer::forward + Sampler::sample with a stop set and a budget: bit for bit the per-sequence calls on a
+// context that holds only that sequence).  The passes are lmrs_batch_generate_greedy's; behind each stands ONE launch (launch_gen_advance) where that loop
+// has its advance: it records the chosen token, tests it against the row's stop set and budget, and either moves the table row on or leaves it where it is.
+// A row that has ended but is still in the table computes the row it computed last - same token, same position, same earlier K/V - so it writes the same
+// K/V bits, the same record entry and the same logits and chooses the same token again (sample_mult too: rnd is a constant of the sampler): harmless, and
+// nothing at or beyond its end is touched.  Every check_every passes the host looks at the rows' states and, where a row has ended, builds the table anew from
+// the live rows alone, through batch_rows (the mask, record and penalty columns with it): rows are independent of each other in every GEMM form, so compaction
+// changes no bit.
+static_assert(kGenRowsMax == (int)kWideBatchMax && kGenStopMax == LMRS_STOP_MAX, "a state block per row of a wide batch, the header's stop set");
+static int gen_alloc(lmrs_batch* b, size_t lp_words) {
+    if (!b->gen_st && !alloc_all({{b->gen_st, kWideBatchMax}, {b->h_gen_st, kWideBatchMax}, {b->gen_live, 1}, {b->h_gen_live, 1}})) {
+        (void)hipGetLastError();
+        return fail("lmrs_batch_generate: row state blocks: out of memory");
+    }
+    // the log-probabilities' block by need (n * M of this call; one that grows is made anew)
+    if (lp_words > b->gen_lp.count() && !alloc_all({{b->gen_lp, lp_words}, {b->h_gen_lp, lp_words}})) {
+        (void)hipGetLastError();
+        return fail("lmrs_batch_generate: " + std::to_string(lp_words * 4) + " bytes of log-probabilities (and as many pinned): out of memory");
+    }
+    return 0;
+}
+extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, const uint32_t* max_new,
+                                   const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers, uint32_t check_every,
+                                   uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish, uint64_t* stats2, double* seconds) {
+    const std::string what = "lmrs_batch_generate: ";
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (!slot || !tokens || !pos || !max_new || !out_tokens || !n_out || !finish) return fail(what + "NULL array");
+    lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, T = c->args.seq_len;
+    if (check_every == 0) return fail(what + "check_every is 0");
+    // the rows as every step checks them (batch_rows: n, slots, tokens, one position each; the table it leaves is built again below) and the samplers as the
+    // sampled calls check them (samplers_check: the ONE copy of those rules), then what only this call asks
+    int order0[kRowTableMax];
+    if (batch_rows(b, "lmrs_batch_generate", b->width, n, slot, tokens, pos, 1, order0)) return -1;
+    GenRow row[kWideBatchMax]; SampleRow par[kWideBatchMax]; bool topp[kWideBatchMax] = {};
+    for (uint32_t i = 0; i < n; ++i) par[i] = SampleRow{0.0f, 0.0f, 0.0f};               // a NULL entry: sample_argmax
+    uint32_t M = 0; size_t at_stop = 0; bool sampled = false;
+    if (samplers && samplers_check(c, what, "row", /*need_all=*/false, n, samplers, par, topp, &sampled)) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string at = what + "row " + std::to_string(i) + ": ";
+        if (max_new[i] == 0) return fail(at + "max_new is 0");
+        if ((size_t)pos[i] + max_new[i] > T) return fail(at + "pos + max_new = " + std::to_string((size_t)pos[i] + max_new[i]) + " exceeds seq_len = " + std::to_string(T));
+        GenRow& g = row[i];
+        g = GenRow{};
+        g.live = 1; g.budget = max_new[i]; g.last = tokens[i];
+        if (n_stop) {
+            if (n_stop[i] > (uint32_t)LMRS_STOP_MAX) return fail(at + "n_stop = " + std::to_string(n_stop[i]) + " exceeds LMRS_STOP_MAX = " + std::to_string(LMRS_STOP_MAX));
+            if (n_stop[i] && !stop_tokens) return fail(what + "n_stop given without stop_tokens");
+            for (uint32_t k = 0; k < n_stop[i]; ++k) {
+                g.stop[k] = stop_tokens[at_stop + k];
+                if (g.stop[k] >= V) return fail(at + "stop token " + std::to_string(k) + " = " + std::to_string(g.stop[k]) + " is not below vocab_size = " + std::to_string(V));
+            }
+            g.n_stop = n_stop[i]; at_stop += n_stop[i];
+        }
+        // (sample_topp's stale candidate vector lives in the host sampler, sampler.rs:81: a loop with a top-p row cannot run a step without a host round trip)
+        if (topp[i]) return fail(at + "a top-p sampler (top_p = " + std::to_string(par[i].top_p) + ") cannot run in the device loop: its candidate vector lives in the host sampler");
+        g.from_samp = par[i].temperature != 0.0f ? 1u : 0u;
+        M = std::max(M, max_new[i]);
+    }
+    for (uint32_t i = 0; i < n; ++i) row[i].out_at = i * M;
+    if ((sampled || out_logprobs) && cls_rows(c) != (int)V)
+        return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: neither sampled rows nor log-probabilities for this vocabulary");
+    if ((sampled || out_logprobs) && n > (uint32_t)c->sc_rows)
+        return fail(what + "the logits block holds " + std::to_string(c->sc_rows) + " rows of this vocabulary, " + std::to_string(n) + " rows were given");
+    HIP_OK(hipSetDevice(c->device));
+    if (gen_alloc(b, out_logprobs ? (size_t)n * M : 0)) return -1;
+    if (sampled && b->gen.rows < n && sample_set_alloc(c, b->gen, std::min<size_t>(b->width, ((size_t)n + 15) / 16 * 16), [](size_t bytes, size_t R) {
+            return "lmrs_batch_generate: " + std::to_string(bytes) + " bytes of candidate buffers for " + std::to_string(R) + " rows: out of memory"; })) return -1;
+    if (sampled && out_logprobs && b->gen_logits_rows < n) {
+        b->gen_logits_rows = 0;
+        if (!b->gen_logits.alloc((size_t)n * V)) { (void)hipGetLastError(); return fail(what + std::to_string((size_t)n * V * 4) + " bytes for the sampled rows' copy of the logits: out of memory"); }
+        b->gen_logits_rows = n;
+    }
+    if (pages_claim_rows(b, what, n, slot, pos, max_new, 0)) return -1;     // every row's whole budget up front: the device loop crosses page edges alone
+    std::vector<uint32_t> live(n);
+    for (uint32_t i = 0; i < n; ++i) live[i] = i;
+    uint64_t passes = 0, row_passes = 0;
+    // the table of the live rows alone, each where it stands now; output o of the pass is live row (wide ? o : order[o]).  It is built anew only behind a look
+    // that found a row ended: while every row is live the device's table and state blocks ARE the rows' state, and the next chunk is enqueued as it stands
+    uint32_t ls[kWideBatchMax], lt[kWideBatchMax], lp[kWideBatchMax]; int order[kRowTableMax];
+    bool rebuild = true, wide = false, samp = false; int top = 0;
+    while (!live.empty()) {
+        const uint32_t nl = (uint32_t)live.size();
+        for (uint32_t j = 0; j < nl; ++j) { const uint32_t i = live[j]; ls[j] = slot[i]; lt[j] = row[i].last; lp[j] = pos[i] + row[i].done; }
+        auto row_of = [&](uint32_t o) { return live[wide ? o : (uint32_t)order[o]]; };
+        if (rebuild) {
+            if (batch_rows(b, "lmrs_batch_generate", b->width, nl, ls, lt, lp, 1, order)) return -1;
+            wide = nl > (uint32_t)kRowTableMax; samp = false;
+            for (uint32_t o = 0; o < nl; ++o) { b->h_gen_st[o] = row[row_of(o)]; samp = samp || row[row_of(o)].from_samp; }
+            for (uint32_t o = 0; o < nl && samp; ++o) b->gen.h_tab[o] = par[row_of(o)];
+            top = wide ? b->h_runs->pos[0] : b->h_tab->pos[0];             // the deepest live row at the build (the tables are sorted by descending position)
+        }
+        auto enqueue = [&]() -> int {
+            if (rebuild) {
+                if (wide) HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+                else HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
+                if (masks_enqueue(b, nl) || record_enqueue(b, nl, nl) || (!passes && batch_state(c))) return -1;
+                HIP_OK(hipMemcpyAsync(b->gen_st, b->h_gen_st, nl * sizeof(GenRow), hipMemcpyHostToDevice, c->stream));
+                if (samp) HIP_OK(hipMemcpyAsync(b->gen.tab, b->gen.h_tab, nl * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+            }
+            const GenPick pick{c->sc_idx, samp ? b->gen.out.get() : nullptr, V + 1};
+            for (uint32_t k = 0; k < check_every; ++k) {
+                // max_T from the deepest position a live row can stand at in this pass: a row never moves beyond its budget's last position
+                uint32_t deepest = 0;
+                for (uint32_t j = 0; j < nl; ++j) deepest = std::max(deepest, std::min(lp[j] + k, pos[live[j]] + max_new[live[j]] - 1));
+                const uint32_t step = deepest - (uint32_t)top;
+                if (wide ? runs_pass(b, nl, nl, step, RowSink{0, nl, nullptr, 0}) : batch_pass(b, nl, step, nullptr)) return -1;
+                if (samp) {
+                    // the samplers overwrite their rows: with log-probabilities asked for they work on a copy and the block stays as the reduction saw it
+                    float* rows = c->sc_logits;
+                    if (out_logprobs) {
+                        HIP_OK(hipMemcpyAsync(b->gen_logits, c->sc_logits, (size_t)nl * V * 4, hipMemcpyDeviceToDevice, c->stream));
+                        rows = b->gen_logits;
+                    }
+                    HIP_OK(launch_sample_rows(sample_rows_args(rows, (int)nl, (int)V, (int)V, b->gen.tab, c->sc_idx, b->gen.scratch, b->gen.out), c->stream, (int)b->width));
+                }
+                if (out_logprobs) HIP_OK(launch_gen_logprobs(b->gen_st, pick, c->sc_logits, (int)V, (int)V, c->sc_part, b->gen_lp, (int)nl, c->stream));
+                HIP_OK(launch_gen_advance(b->gen_st, wide ? b->runs->pos : b->tab->pos, wide ? b->runs->tok : b->tab->tok, wide ? b->runs->sel : nullptr, pick, b->out,
+                                          b->gen_live, (int)nl, c->stream));
+            }
+            HIP_OK(hipMemcpyAsync(b->h_gen_st, b->gen_st, nl * sizeof(GenRow), hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(b->h_gen_live, b->gen_live, 4, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        if (batch_call(c, enqueue)) return -1;
+        passes += check_every; row_passes += (uint64_t)check_every * nl;
+        std::vector<uint32_t> next;
+        for (uint32_t o = 0; o < nl; ++o) { row[row_of(o)] = b->h_gen_st[o]; if (b->h_gen_st[o].live) next.push_back(row_of(o)); }
+        if (next.size() != *b->h_gen_live) return fail(what + "the device counted " + std::to_string(*b->h_gen_live) + " live rows, their states show " + std::to_string(next.size()));
+        rebuild = next.size() != nl;
+        if (rebuild) { std::sort(next.begin(), next.end()); live.swap(next); }
+    }
+    auto results = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->h_out, b->out, (size_t)n * M * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_logprobs) HIP_OK(hipMemcpyAsync(b->h_gen_lp, b->gen_lp, (size_t)n * M * 4, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    if (batch_call(c, results)) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        n_out[i] = row[i].done; finish[i] = row[i].finish ? LMRS_FINISH_STOP : LMRS_FINISH_BUDGET;
+        for (uint32_t j = 0; j < M; ++j) {
+            out_tokens[(size_t)i * M + j] = j < row[i].done ? b->h_out[(size_t)i * M + j] : 0u;
+            if (out_logprobs) out_logprobs[(size_t)i * M + j] = j < row[i].done ? b->h_gen_lp[(size_t)i * M + j] : 0.0f;
+        }
+    }
+    if (stats2) { stats2[0] = passes; stats2[1] = row_passes; }
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
 }
 
 // ------------------------------------------------------------------ embedding rows into a slot: ONE fill_kv_cache call (transformer.rs:672-684) on the slot's cache

@@ -66,4 +66,21 @@ struct PenaltyRow { int slot; int tab_row; float repetition, presence, frequency
 // counts are integers: the result does not depend on scheduling.  max_n >= every row's p + 1, at most min(seq_len, kPenaltyKeysMax): sizes the launch's LDS.
 hipError_t launch_penalty_rows(float* logits, int ld, int cols, int rows, const uint32_t* hist, int seq_len, const int* pos, const PenaltyRow* of, int max_n, hipStream_t s);
 
+// ---- the step boundary of lmrs_batch_generate's device loop: one block per output row of the pass's table, in the order the classifier sees the rows
+constexpr int kGenStopMax = 16;                             // = LMRS_STOP_MAX
+constexpr int kGenRowsMax = 64;                             // one lane per row: a wide batch's rows
+// live: the row still generates; done: tokens it has produced; budget: its max_new; finish: 0 budget / 1 stop (valid once live == 0); last: the token it
+// chose last; out_at: where its outputs start in the call's output blocks (words); from_samp: its token is word 0 of its sampling result block, else idx[o]
+struct GenRow { uint32_t live, done, budget, finish, last, out_at, from_samp, n_stop; uint32_t stop[kGenStopMax]; };
+// Where the chosen tokens stand behind a pass: idx[o] (the reduction's sample_argmax) or the low word of samp[o * samp_ld] (launch_sample_rows' result blocks)
+struct GenPick { const uint32_t* idx; const unsigned long long* samp; size_t samp_ld; };
+// Output o < n_rows, live: t = its chosen token -> out[out_at + done]; done += 1; t in its stop set: live = 0, finish = 1; else done == budget: live = 0,
+// finish = 0; else the table row behind it (sel[o]; sel null: row o) gets tok = t, pos += 1.  A row that is not live changes nothing: its table row stays, so
+// the next pass computes the same row again.  *n_live = the rows still live.  One lane per row, plain stores.
+hipError_t launch_gen_advance(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, GenPick pick, uint32_t* out, uint32_t* n_live, int n_rows, hipStream_t s);
+// In front of launch_gen_advance, for every live output o: lp_out[out_at + done] = (float)((double)l[t] - m - log(sum)) of row o of `logits` (ld floats a row,
+// all `vocab` written), t the token launch_gen_advance is about to record, m and sum from the chunk summaries launch_score_rows left for the SAME rows in
+// `part`: score_merge_kernel's arithmetic, one rounding to float.  One wave per row.
+hipError_t launch_gen_logprobs(const GenRow* st, GenPick pick, const float* logits, int ld, int vocab, const ScorePart* part, float* lp_out, int n_rows, hipStream_t s);
+
 }  // namespace lmrs

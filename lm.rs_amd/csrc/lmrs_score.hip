@@ -124,6 +124,9 @@ __device__ __forceinline__ void row_max_sum(const ScorePart* pp, int S, int lane
     s = wave_sum(s);
 }
 
+// the log-softmax of a row at a logit ly: md = the row's f32 maximum widened, s = row_max_sum's sum (score_merge_kernel and gen_logprobs_kernel: one copy)
+__device__ __forceinline__ double log_softmax_at(float ly, double md, double s) { return (double)ly - md - log(s); }
+
 // one wave per row (four rows per workgroup)
 __global__ __launch_bounds__(kLanes) void score_merge_kernel(const ScoreArgs a) {
     const int r = blockIdx.x * (kLanes / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(kLanes) void score_merge_kernel(const ScoreArgs a) 
         if (r < a.n_tgt) {
             const uint32_t y = a.tgt[r];
             const float ly = y < (uint32_t)a.written ? row[y] : 0.0f;
-            a.out_lp[r] = (double)ly - md - log(s);
+            a.out_lp[r] = log_softmax_at(ly, md, s);
         }
     }
 }
@@ -386,7 +389,65 @@ __global__ __launch_bounds__(kLanes) void penalty_rows_kernel(float* logits, int
     }
 }
 
+// ------------------------------------------------------------------ the step boundary of lmrs_batch_generate's device loop (launch_gen_advance / launch_gen_logprobs)
+__device__ __forceinline__ uint32_t gen_picked(const GenRow& g, const GenPick& pick, int o) {
+    return g.from_samp ? (uint32_t)pick.samp[(size_t)o * pick.samp_ld] : pick.idx[o];
+}
+// one lane per output row; sel null: the row table (output o is table row o), else the long table's sel column
+__global__ __launch_bounds__(kGenRowsMax) void gen_advance_kernel(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, const GenPick pick, uint32_t* out,
+                                                                  uint32_t* n_live, int n_rows) {
+    const int o = threadIdx.x;
+    bool live = false;
+    if (o < n_rows) {
+        // everything the lane may need is asked for at once, whether or not the row is live: the launch is one round trip to memory deep (two through sel),
+        // as table_advance_kernel / runs_advance_kernel are
+        const GenRow g = st[o];
+        const uint32_t ti = pick.idx[o], ts = pick.samp ? (uint32_t)pick.samp[(size_t)o * pick.samp_ld] : 0u;
+        const uint32_t r = sel ? sel[o] : (uint32_t)o;
+        const int p = pos[r];
+        if (g.live) {
+            const uint32_t t = g.from_samp ? ts : ti, done = g.done + 1;
+            out[g.out_at + g.done] = t;
+            bool stop = false;
+#pragma unroll
+            for (int k = 0; k < kGenStopMax; ++k) stop = stop || ((uint32_t)k < g.n_stop && g.stop[k] == t);
+            st[o].done = done; st[o].last = t;
+            if (stop) { st[o].live = 0; st[o].finish = 1; }
+            else if (done >= g.budget) { st[o].live = 0; st[o].finish = 0; }
+            else { tok[r] = t; pos[r] = p + 1; live = true; }
+        }
+    }
+    const unsigned long long m = __ballot(live);
+    if (o == 0) *n_live = (uint32_t)__popcll(m);
+}
+// one wave per output row (four rows per workgroup)
+__global__ __launch_bounds__(kLanes) void gen_logprobs_kernel(const GenRow* st, const GenPick pick, const float* logits, int ld, int vocab, const ScorePart* part,
+                                                             float* lp_out, int n_rows) {
+    const int o = blockIdx.x * (kLanes / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (o >= n_rows || !st[o].live) return;                                 // (wave-uniform)
+    const int S = score_chunks(vocab);
+    float m; int mi; double s;
+    row_max_sum(part + (size_t)o * S, S, lane, m, mi, s);
+    if (lane == 0) {
+        const GenRow g = st[o];
+        const uint32_t t = gen_picked(g, pick, o);
+        const float ly = t < (uint32_t)vocab ? logits[(size_t)o * ld + t] : 0.0f;
+        lp_out[g.out_at + g.done] = (float)log_softmax_at(ly, (double)m, s);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_gen_advance(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, GenPick pick, uint32_t* out, uint32_t* n_live, int n_rows, hipStream_t s) {
+    if (!st || !pos || !tok || !pick.idx || !out || !n_live || n_rows < 1 || n_rows > kGenRowsMax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gen_advance_kernel, dim3(1), dim3(kGenRowsMax), 0, s, st, pos, tok, sel, pick, out, n_live, n_rows);
+    return hipGetLastError();
+}
+hipError_t launch_gen_logprobs(const GenRow* st, GenPick pick, const float* logits, int ld, int vocab, const ScorePart* part, float* lp_out, int n_rows, hipStream_t s) {
+    if (!st || !pick.idx || !logits || !part || !lp_out || n_rows < 1 || n_rows > kGenRowsMax || vocab <= 0 || ld < vocab) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gen_logprobs_kernel, dim3((n_rows + kLanes / 64 - 1) / (kLanes / 64)), dim3(kLanes), 0, s, st, pick, logits, ld, vocab, part, lp_out, n_rows);
+    return hipGetLastError();
+}
 
 hipError_t launch_record_rows(uint32_t* hist, int seq_len, int n_slots, const int* pos, const uint32_t* tok, const int* slot_of, int n_rows, hipStream_t s) {
     if (!hist || !pos || !tok || !slot_of || seq_len <= 0 || n_slots <= 0 || n_rows <= 0) return hipErrorInvalidValue;

@@ -262,6 +262,42 @@ public:
         check(lmrs_batch_generate_greedy(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), tokens.data(), pos.data(), n_new, out.data(), seconds));
         return out;
     }
+    // The device loop whose rows end one by one: row i feeds tokens[i] at pos[i] of slot[i] and goes on with what it chose - Sampler::sample with samplers[i]
+    // (Sampler::handle(), text.hpp; argmax and sample_mult samplers, top-p is refused), the argmax for a null entry or an empty `samplers` - until it chooses a
+    // token of stop[i] (FINISH_STOP: the token is reported, never fed) or has produced max_new[i] tokens (FINISH_BUDGET).  stop: empty, or one set (at most
+    // STOP_MAX tokens) per row.  check_every: passes between two looks at the rows' state; no result depends on it  (lmrs_batch_generate)
+    static constexpr std::uint32_t STOP_MAX = LMRS_STOP_MAX, FINISH_BUDGET = LMRS_FINISH_BUDGET, FINISH_STOP = LMRS_FINISH_STOP;
+    struct Generated {
+        std::vector<std::vector<std::uint32_t>> tokens;      // row i's outputs, n_out[i] of them
+        std::vector<std::vector<float>> logprobs;            // with logprobs: log softmax of the row each token was chosen from, at that token
+        std::vector<std::uint32_t> finish;
+        std::uint64_t passes = 0, row_passes = 0; double seconds = 0.0;
+    };
+    Generated generate(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
+                       const std::vector<std::uint32_t>& max_new, const std::vector<std::vector<std::uint32_t>>& stop = {},
+                       const std::vector<lmrs_sampler*>& samplers = {}, std::uint32_t check_every = 4, bool logprobs = false) {
+        const std::size_t n = slot.size();
+        if (tokens.size() != n || pos.size() != n || max_new.size() != n) throw Panic("Batch::generate: one slot, token, position and budget per row");
+        if (!stop.empty() && stop.size() != n) throw Panic("Batch::generate: stop is empty or holds one set per row");
+        if (!samplers.empty() && samplers.size() != n) throw Panic("Batch::generate: samplers is empty or holds one entry per row");
+        std::vector<std::uint32_t> n_stop, packed;
+        for (const auto& s : stop) { n_stop.push_back(static_cast<std::uint32_t>(s.size())); packed.insert(packed.end(), s.begin(), s.end()); }
+        std::uint32_t M = 1;
+        for (std::uint32_t m : max_new) M = m > M ? m : M;
+        std::vector<std::uint32_t> out(n * M), n_out(n), fin(n);
+        std::vector<float> lp(logprobs ? n * M : 0);
+        std::uint64_t stats[2] = {0, 0};
+        Generated g;
+        check(lmrs_batch_generate(b_, static_cast<std::uint32_t>(n), slot.data(), tokens.data(), pos.data(), max_new.data(), stop.empty() ? nullptr : n_stop.data(),
+                                  packed.empty() ? nullptr : packed.data(), samplers.empty() ? nullptr : samplers.data(), check_every, out.data(),
+                                  logprobs ? lp.data() : nullptr, n_out.data(), fin.data(), stats, &g.seconds));
+        for (std::size_t i = 0; i < n; ++i) {
+            g.tokens.emplace_back(out.begin() + i * M, out.begin() + i * M + n_out[i]);
+            if (logprobs) g.logprobs.emplace_back(lp.begin() + i * M, lp.begin() + i * M + n_out[i]);
+        }
+        g.finish = fin; g.passes = stats[0]; g.row_passes = stats[1];
+        return g;
+    }
     // One pass over runs of consecutive tokens, one run per slot (a prompt chunk, a draft to verify, one decode row; at most 512 tokens in all): outputs for
     // the LAST n_out rows of every run, packed in run order - argmax always, logits (x vocab_size) and the k first candidates with their log-probabilities
     // (x k, as lmrs_score_tokens_topk defines them) when asked for  (lmrs_batch_forward_runs)

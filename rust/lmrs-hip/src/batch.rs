@@ -43,6 +43,30 @@ extern "C" {
     pub fn lmrs_batch_clear_penalties(b: *mut LmrsBatch, n: u32, slot: *const u32) -> c_int;
     pub fn lmrs_batch_penalty_info(b: *const LmrsBatch, slot: u32, repetition: *mut f32, presence: *mut f32, frequency: *mut f32,
                                    out_from: *mut u32, active: *mut c_int) -> c_int;
+    // the device loop whose rows end one by one: declared here as the penalty calls are (tests/test_batch_generate_host.py compares it with the header)
+    pub fn lmrs_batch_generate(b: *mut LmrsBatch, n: u32, slot: *const u32, tokens: *const u32, pos: *const u32, max_new: *const u32,
+                               n_stop: *const u32, stop_tokens: *const u32, samplers: *const *mut LmrsSampler, check_every: u32,
+                               out_tokens: *mut u32, out_logprobs: *mut f32, n_out: *mut u32, finish: *mut u32, stats2: *mut u64,
+                               seconds: *mut f64) -> c_int;
+}
+
+/// The most stop tokens a row of `Batch::generate` takes (`LMRS_STOP_MAX`).
+pub const STOP_MAX: usize = 16;
+/// `Batch::generate`'s finish codes (`LMRS_FINISH_BUDGET`, `LMRS_FINISH_STOP`).
+pub const FINISH_BUDGET: u32 = 0;
+pub const FINISH_STOP: u32 = 1;
+
+/// What `Batch::generate` returns: per row its tokens (cut to `n_out`), their log-probabilities when asked for, and its finish code; the passes the
+/// loop ran, the sum over them of the rows in the pass, and the call's host wall time.
+#[derive(Clone, Debug, Default)]
+pub struct Generated {
+    pub tokens: Vec<Vec<u32>>,
+    pub logprobs: Vec<Vec<f32>>,
+    pub finish: Vec<u32>,
+    pub passes: u64,
+    pub row_passes: u64,
+    /// Host wall time of the call, in seconds.
+    pub seconds: f64,
 }
 
 /// The record's word for a position whose token is unknown, or an embedding row (`LMRS_TOKEN_NONE`).
@@ -299,6 +323,42 @@ impl<'t, 'a> Batch<'t, 'a> {
             ffi::lmrs_batch_generate_greedy(self.b, slot.len() as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), n_new, out.as_mut_ptr(), ptr::null_mut())
         });
         out
+    }
+
+    /// The device loop whose rows end one by one (`lmrs_batch_generate`): row i feeds `tokens[i]` at `pos[i]` of `slot[i]` and goes on with what it
+    /// chose - `Sampler::sample` with `samplers[i]`, the argmax for `None` or an empty list - until it chooses a token of `stop[i]` (`FINISH_STOP`; the
+    /// token is reported, never fed) or has produced `max_new[i]` tokens (`FINISH_BUDGET`).  `stop`: empty, or one set of at most `STOP_MAX` tokens per
+    /// row.  Argmax and sample_mult samplers only (they are stateless and may be shared); a top-p sampler panics with the library's message.
+    /// `check_every`: passes between two looks at the rows' state; no result depends on it.
+    #[allow(clippy::too_many_arguments)]
+    pub fn generate(&mut self, slot: &[u32], tokens: &[u32], pos: &[u32], max_new: &[u32], stop: &[&[u32]], samplers: &[Option<&Sampler>],
+                    check_every: u32, logprobs: bool) -> Generated {
+        let n = slot.len();
+        assert!(tokens.len() == n && pos.len() == n && max_new.len() == n, "one slot, token, position and budget per row");
+        assert!(stop.is_empty() || stop.len() == n, "stop is empty or holds one set per row");
+        assert!(samplers.is_empty() || samplers.len() == n, "samplers is empty or holds one entry per row");
+        let n_stop: Vec<u32> = stop.iter().map(|s| s.len() as u32).collect();
+        let packed: Vec<u32> = stop.iter().flat_map(|s| s.iter().copied()).collect();
+        let handles: Vec<*mut LmrsSampler> = samplers.iter().map(|s| s.map_or(ptr::null_mut(), |s| s.handle)).collect();
+        let m = max_new.iter().copied().max().unwrap_or(0).max(1) as usize;
+        let (mut out, mut lp) = (vec![0u32; n * m], vec![0f32; if logprobs { n * m } else { 0 }]);
+        let (mut n_out, mut finish, mut stats, mut seconds) = (vec![0u32; n], vec![0u32; n], [0u64; 2], 0f64);
+        check(unsafe {
+            lmrs_batch_generate(self.b, n as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), max_new.as_ptr(),
+                                if stop.is_empty() { ptr::null() } else { n_stop.as_ptr() }, if packed.is_empty() { ptr::null() } else { packed.as_ptr() },
+                                if samplers.is_empty() { ptr::null() } else { handles.as_ptr() }, check_every, out.as_mut_ptr(),
+                                if logprobs { lp.as_mut_ptr() } else { ptr::null_mut() }, n_out.as_mut_ptr(), finish.as_mut_ptr(), stats.as_mut_ptr(),
+                                &mut seconds)
+        });
+        let cut = |i: usize| i * m..i * m + n_out[i] as usize;
+        Generated {
+            tokens: (0..n).map(|i| out[cut(i)].to_vec()).collect(),
+            logprobs: if logprobs { (0..n).map(|i| lp[cut(i)].to_vec()).collect() } else { Vec::new() },
+            finish,
+            passes: stats[0],
+            row_passes: stats[1],
+            seconds,
+        }
     }
 }
 
