@@ -381,6 +381,10 @@ int lmrs_op_sample_rows(int device, float* rows, size_t n_rows, size_t n, const 
  * on the dispatches, one warm-up run before them); *clock_mhz (optional) = the device's nominal shader clock.  tools/sample_rate.py turns launches 2
  * and 4 into cycles per term. */
 int lmrs_bench_sample_rows(int device, size_t n_rows, size_t n, int iters, double* us6, double* clock_mhz);
+/* Measurement: the launches behind lmrs_op_topp_rows on n_rows (1 .. 64) rows of n0 (1 .. n) candidates each, probabilities scattered, over vectors of n
+ * (2 .. 2^24) entries that carry the runs before: *us = device microseconds of all launches of one run (HIP events on the dispatches, summed), the
+ * mean of iters runs after one warm-up; *launches (optional): how many launches a run has - vocab_size alone decides. */
+int lmrs_bench_topp_rows(int device, size_t n_rows, size_t n, size_t n0, int iters, double* us, int* launches);
 /* The selection kernels of lmrs_score_tokens_topk / lmrs_forward_topk on one caller-supplied row of n logits of which the first `written` exist
  * (the rest count as 0.0 and are never read): idx[j], val[j] = the rank-j index and its raw value, j < k.  Unit parity for the ordering rule (NaNs,
  * signed zeros, equal values, k = n); extension, no reference counterpart.  k = 0, k > 256 and k > n are refused before the device is touched. */
@@ -521,6 +525,13 @@ int lmrs_sampler_topp_pairs(lmrs_sampler* s, const void* pairs, size_t n0, uint3
  * stable sort of :81 makes of the index-ordered candidates (lmrs_batch_forward_sample sorts a flat row's candidates on the device).  The merge
  * with the stale rest of the persistent vector, the cumulative cut and the draw run here. */
 int lmrs_sampler_topp_sorted_pairs(lmrs_sampler* s, const void* sorted_pairs, size_t n0, uint32_t* next);
+/* The persistent candidate vector of a sampler, out and in, as it stands (host code): vocab_size pairs {f32 prob, u32 index}, 8 bytes each.
+ * pairs may be NULL when only the flag is wanted.  *ordered (may be NULL): 1 when the vector is known to be in descending order of prob and free of NaNs - true from creation (all zeros) and after
+ * every call of this library.  lmrs_sampler_set_candidates scans what it is given and sets that flag from what it finds; a vector that is not
+ * ordered is sorted whole by every later call, as sampler.rs:81 writes it.  A sampler that takes another's vector continues exactly as the other
+ * would.  set_candidates is refused between lmrs_sampler_exps_prepare and lmrs_sampler_exps_finish (this call's candidates sit in the vector). */
+int lmrs_sampler_candidates(const lmrs_sampler* s, void* pairs, int* ordered);
+int lmrs_sampler_set_candidates(lmrs_sampler* s, const void* pairs);
 /* Sampler::sample from the softmax's exponentials on (functional.rs:134-139, then sampler.rs:119-128): exps[i] = exp(logits[i] / temperature - max)
  * were formed elsewhere (lmrs_forward_sample forms them on the device); the sequential sum, the division, and sample_mult / sample_topp run here.
  * exps become the probabilities in place.  Same token and probabilities as lmrs_sampler_sample on the logits. */
@@ -555,8 +566,9 @@ int lmrs_forward_sample(lmrs_ctx* ctx, uint32_t token, uint32_t pos, lmrs_sample
  * cost.  Top-p rows finish on the host in row order - lmrs_sampler_topp_pairs, each sampler's persistent vector updated exactly as that call
  * updates it; a row with 4096 candidates or more (a flat distribution) first has them sorted on the device (as lmrs_forward_sample does), one
  * such row at a time behind a second synchronise, and finishes through lmrs_sampler_topp_sorted_pairs.
- * There is no device-resident sampled loop for top-p rows (lmrs_batch_generate is that loop for argmax and sample_mult rows): sample_topp's stale
- * candidate vector lives in the host sampler, so a loop that includes the default sampler cannot run a step without a host round trip.
+ * lmrs_batch_generate, the device loop for argmax and sample_mult rows, is no device-resident sampled loop for top-p rows: sample_topp's stale
+ * candidate vector lives in the host sampler, so a step with such a row cannot do without a host round trip - unless the vector itself goes to
+ * the device, which is what lmrs_batch_generate_topp does for the length of a call.
  * Errors, each with a message of its own, before any device work, batch, context and samplers left usable: everything lmrs_batch_forward checks;
  * a NULL array; a NULL sampler (the row is named); a sampler made for another vocabulary size; a top-p sampler that appears twice in one call (it
  * carries state; argmax and sample_mult samplers are stateless and may be shared); a vocabulary whose last vocab_size % 4 logits the classifier
@@ -576,7 +588,7 @@ int lmrs_batch_forward_sample(lmrs_batch* b, uint32_t n, const uint32_t* slot, c
  * through lmrs_sampler_topp_pairs; the rows with 4096 candidates or more (flat distributions) are first sorted on the device ALL TOGETHER - keys
  * straight from the candidates the filter left, one bitonic network with the row in the grid's second dimension, the rows padded to the power of two
  * that holds the longest - behind ONE second synchronise however many they are, and finish through lmrs_sampler_topp_sorted_pairs.  The host
- * finishes do not overlap the copies.  The device-resident loop (lmrs_batch_generate) takes no top-p row, for the reason given above.
+ * finishes do not overlap the copies.  The device-resident loop that takes a top-p row is lmrs_batch_generate_topp (lmrs_batch_generate refuses one, for the reason given above).
  * Errors, each with a message of its own that opens with this call's name, before any device work, batch, context and samplers left usable:
  * everything lmrs_batch_forward_runs checks for these arguments; a NULL array; a sampler made for another vocabulary size (the run is named); a
  * top-p sampler in two runs of one call; a sampled (temperature != 0) output on a vocabulary whose last vocab_size % 4 logits the classifier leaves
@@ -638,6 +650,14 @@ int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_runs, const u
  * n0[r] entries by descending prob, ties by ascending index - what the stable sort of sampler.rs:81 makes of them; the rest of the row, and a row
  * with n0 = 0, is not written.  Everything else is refused before the device is touched. */
 int lmrs_op_sort_candidates(int device, const void* pairs, size_t n_rows, size_t ld, const uint32_t* n0, void* sorted);
+/* The launches that finish a top-p row on the device (lmrs_batch_generate_topp) on caller-supplied rows: unit parity against lmrs_sampler_topp_pairs.
+ * Row r < n_rows (1 .. 64) over n (2 .. 2^24) entries: cand + r * n pairs holds its n0[r] (<= n) candidates {f32 prob > 0, u32 index} in ascending index
+ * order, state + r * n pairs its persistent vector in descending order of prob, top_p[r] and rnd[r] its parameters.  Afterwards state holds the new
+ * vector - the candidates sorted by (prob descending, index ascending) and merged stably with entries [n0, n) of the old one, equal probabilities from
+ * the candidates first: what sampler.rs:81 leaves - token[r] the draw of sampler.rs:83-105 and status[r] = 0; n0[r] == 0: status[r] = 1, token[r] = 0,
+ * the state unchanged.  Everything else is refused before the device is touched. */
+int lmrs_op_topp_rows(int device, size_t n_rows, size_t n, const void* cand, const uint32_t* n0, const float* top_p, const float* rnd,
+                      void* state, uint32_t* token, uint32_t* status);
 
 /* ---- allowed-token masks: which tokens a slot's rows may produce (extensions, no reference counterpart) ----
  * A mask is state of a batch slot, not an argument of a pass: W = (vocab_size + 31) / 32 words, bit (t & 31) of word (t >> 5) set = token t allowed;
@@ -740,6 +760,44 @@ int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* slot, const u
                         const uint32_t* max_new, const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers,
                         uint32_t check_every, uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish,
                         uint64_t* stats2, double* seconds);
+
+/* ---- lmrs_batch_generate with top-p rows: the candidate vectors resident on the device for the length of the call (extension) ----
+ * lmrs_batch_generate's contract word for word - arguments, outputs, stop sets, budgets, log-probabilities, masks, penalties, contiguous, wide and
+ * paged batches, any check_every, stats2, errors (each message opens with this call's name) - with these differences:
+ *   - a top-p sampler (temperature != 0, 0 < top_p < 1: the reference's default, chat.rs:28-31) is accepted for a row; rows may mix argmax,
+ *     sample_mult and top-p samplers.  A top-p sampler carries state from call to call and may appear in one row only;
+ *   - every token is, bit for bit, what lmrs_forward_sample returns with that sampler on a context that holds only that sequence, stale entries of the
+ *     sampler's persistent vector included (sampler.rs:81 sorts the whole vector);
+ *   - when the call returns, every top-p sampler's host vector is, bit for bit, what n_out[i] such per-sequence calls leave in it: whatever the caller
+ *     does with the sampler next continues exactly;
+ *   - a row whose step finds no candidate above the cutoff (the reference underflows n0 - 1 and panics there, lmrs_sampler_topp_pairs fails the call)
+ *     ends with finish[i] = LMRS_FINISH_NO_CANDIDATE.  That step reports no token: n_out[i] counts the tokens before it and may be 0.  Its K/V row and
+ *     record entry are written - the forward ran - and the sampler's vector is as the steps before it left it (the sort of an unchanged ordered vector
+ *     changes nothing).  The call returns 0 and the other rows go on;
+ *   - a top-p sampler whose vector is not ordered (lmrs_sampler_candidates: an import through lmrs_sampler_set_candidates) is refused before any device
+ *     work, with a message of its own: the device merge rests on the order every call of this library leaves.
+ * The device side: the vectors travel to the device at the start of the call (one that is still all zero, as created, is cleared there instead) and
+ * back through lmrs_sampler_set_candidates at its end; they do not stay resident between calls.  Behind launch_sample_rows' six launches every pass with
+ * a live top-p row enqueues a fixed sequence - its length set by vocab_size alone, no n0 known to the host: the bitonic sort of each row's n0 candidates
+ * on the keys (~bits(prob) << 32) | index, sized per row on the device (a row of up to 8192 candidates is done after the first launch, the others
+ * return at once); the stable merge with the ordered rest of the vector by rank, one binary search per element, into the row's second block
+ * (ping-pong; only the prefix that changes is written: a few hundred bytes for a peaked row, up to 2 * vocab_size * 8 read and written for a flat
+ * one); the cumulative cut and the draw, one adding lane per row.  A row that has ended but still stands in the table reads its live word and leaves
+ * its vector alone.  The vectors are addressed by the row's number among the call's top-p rows, a column beside the pass's table: no vector moves
+ * when the table is rebuilt.
+ * Measured on Llama-3.2-1B Q8_0 (synthetic weights, rows at 100 positions, 128 tokens, upload and download included) against one
+ * lmrs_batch_forward_runs_sample per step: flat rows (0.7, 0.9) 4073 against 13047 us a step at 64 rows, 2895 against 4136 at 16; peaked rows
+ * (0.02, 0.9) 1780 against 1863 at 16 rows, but 2346 against 2294 at 64 - slower by 52 us a step there.  The new launches alone: 113 us a step for 64
+ * peaked rows, 2063 us for 64 rows of 112224 candidates (profiles/batch_generate_topp_llama1b.txt).
+ * Gemma-2-2B Q4_0: flat rows 9150 against 25602 us at 64 rows, 5866 against 9058 at 16; peaked rows slower at both sizes, 3744 against 3714 and 5632
+ * against 5454 (profiles/batch_generate_topp_gemma2b_q4.txt): five of the eight cases are no slower than the per-call route, three are slower.
+ * Buffers of this call's own beside lmrs_batch_generate's, at the first call that needs them, all or nothing, the bytes in the message: per top-p row
+ * 2 * vocab_size * 8 bytes of vector blocks, 8 bytes times the power of two that holds max(vocab_size, 8192) of sort keys, and vocab_size * 8 pinned. */
+#define LMRS_FINISH_NO_CANDIDATE 2
+int lmrs_batch_generate_topp(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
+                             const uint32_t* max_new, const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers,
+                             uint32_t check_every, uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish,
+                             uint64_t* stats2, double* seconds);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@ EXPORTS = [
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
     "lmrs_batch_generate",
+    "lmrs_batch_generate_topp", "lmrs_sampler_candidates", "lmrs_sampler_set_candidates", "lmrs_op_topp_rows", "lmrs_bench_topp_rows",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -141,6 +142,11 @@ def lib():
         L.lmrs_batch_forward_runs_embed.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
         L.lmrs_batch_forward_runs_embed_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.lmrs_op_sort_candidates.argtypes = [C.c_int, vp, sz, sz, vp, vp]
+        L.lmrs_batch_generate_topp.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
+        L.lmrs_sampler_candidates.argtypes = [vp, vp, C.POINTER(C.c_int)]
+        L.lmrs_sampler_set_candidates.argtypes = [vp, vp]
+        L.lmrs_op_topp_rows.argtypes = [C.c_int, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.lmrs_bench_topp_rows.argtypes = [C.c_int, sz, sz, sz, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.lmrs_op_sample_rows.argtypes = [C.c_int, vp, sz, sz, vp, vp, vp, vp, vp, vp]
         L.lmrs_sampler_topp_sorted_pairs.argtypes = [vp, vp, sz, C.POINTER(u32)]
         L.lmrs_bench_sample_rows.argtypes = [C.c_int, sz, sz, C.c_int, vp, C.POINTER(C.c_double)]
@@ -432,6 +438,7 @@ BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BA
 TOKEN_NONE = 0xFFFFFFFF       # Batch.history / set_history: a position whose token is unknown, or an embedding row (LMRS_TOKEN_NONE)
 STOP_MAX = 16                 # Batch.generate: the most stop tokens a row takes (LMRS_STOP_MAX)
 FINISH_BUDGET, FINISH_STOP = 0, 1     # Batch.generate's finish codes (LMRS_FINISH_BUDGET / LMRS_FINISH_STOP)
+FINISH_NO_CANDIDATE = 2               # Batch.generate_topp: a top-p row's step found no candidate above the cutoff (LMRS_FINISH_NO_CANDIDATE)
 
 
 class Batch:
@@ -711,7 +718,14 @@ class Batch:
         _chk(lib().lmrs_batch_generate_greedy(self._h, s.size, _p(s), _p(t), _p(p), n_new, _p(out), C.byref(sec)))
         return (out, sec.value) if timing else out
 
-    def generate(self, slots, tokens, pos, max_new, stop=None, samplers=None, check_every: int = 4, logprobs: bool = False, timing: bool = False):
+    def generate_topp(self, slots, tokens, pos, max_new, stop=None, samplers=None, check_every: int = 4, logprobs: bool = False, timing: bool = False):
+        """generate with top-p samplers admitted (each in one row only): their candidate vectors live on the device for the length of the call and are
+        back in the samplers when it returns, so whatever is done with a sampler next continues exactly.  A row whose step finds no candidate above the
+        cutoff ends with finish FINISH_NO_CANDIDATE and reports no token for that step.  Arguments and results as generate  (lmrs_batch_generate_topp)"""
+        return self.generate(slots, tokens, pos, max_new, stop, samplers, check_every, logprobs, timing, _call="lmrs_batch_generate_topp")
+
+    def generate(self, slots, tokens, pos, max_new, stop=None, samplers=None, check_every: int = 4, logprobs: bool = False, timing: bool = False, *,
+                 _call: str = "lmrs_batch_generate"):
         """The device loop whose rows end one by one: row i feeds tokens[i] at pos[i] of slots[i] and goes on with what it chose - Sampler.sample with
         samplers[i], the argmax for None (samplers=None: every row) - until it chooses a token of its stop set (finish STOP; the token is reported, never
         fed) or has produced max_new[i] tokens (BUDGET).  max_new: one budget per row, or a scalar for all.  stop: a list of token lists, one per row, or
@@ -743,9 +757,9 @@ class Batch:
         lp = np.zeros((n, max(M, 1)), np.float32) if logprobs else None
         n_out, fin = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         stats2, sec = np.zeros(2, np.uint64), C.c_double()
-        _chk(lib().lmrs_batch_generate(self._h, n, _p(s), _p(t), _p(p), _p(mx), None if ns is None else _p(ns), _p(st) if st is not None and st.size else None,
-                                       None if hs is None else C.cast(hs, C.c_void_p), check_every, _p(out), _p(lp) if logprobs else None, _p(n_out), _p(fin),
-                                       _p(stats2), C.byref(sec)))
+        _chk(getattr(lib(), _call)(self._h, n, _p(s), _p(t), _p(p), _p(mx), None if ns is None else _p(ns), _p(st) if st is not None and st.size else None,
+                                   None if hs is None else C.cast(hs, C.c_void_p), check_every, _p(out), _p(lp) if logprobs else None, _p(n_out), _p(fin),
+                                   _p(stats2), C.byref(sec)))
         stats = dict(passes=int(stats2[0]), row_passes=int(stats2[1]))
         if timing:
             stats["seconds"] = sec.value
@@ -920,6 +934,31 @@ def op_sort_candidates(pairs, n0, device=0):
     out = x.copy()
     _chk(lib().lmrs_op_sort_candidates(device, _p(x), x.shape[0], x.shape[1], _p(n), _p(out)))
     return out
+
+
+def op_topp_rows(cand, n0, top_p, rnd, state, device=0):
+    """The launches that finish generate_topp's top-p rows, on caller-supplied rows: cand [n_rows, n] of PAIR, the first n0[r] of row r the call's
+    candidates in ascending index order; state [n_rows, n] of PAIR, each row a persistent vector in descending order of prob; top_p, rnd per row
+    -> (token [n_rows], status [n_rows]: 0 a token, 1 no candidate, new state)  (lmrs_op_topp_rows)"""
+    x = np.ascontiguousarray(cand, PAIR)
+    st = np.array(state, PAIR, order="C")
+    if x.ndim != 2 or st.shape != x.shape:
+        raise LmrsError("op_topp_rows: cand and state must both be [n_rows, n]")
+    n = np.ascontiguousarray(n0, np.uint32).reshape(-1)
+    tp = np.ascontiguousarray(top_p, np.float32).reshape(-1); rn = np.ascontiguousarray(rnd, np.float32).reshape(-1)
+    if not n.size == tp.size == rn.size == x.shape[0]:
+        raise LmrsError("op_topp_rows: one n0, top_p and rnd per row")
+    tok = np.zeros(x.shape[0], np.uint32); status = np.zeros(x.shape[0], np.uint32)
+    _chk(lib().lmrs_op_topp_rows(device, x.shape[0], x.shape[1], _p(x), _p(n), _p(tp), _p(rn), _p(st), _p(tok), _p(status)))
+    return tok, status, st
+
+
+def bench_topp_rows(n_rows: int, n: int, n0: int, iters: int = 5, device=0):
+    """(device microseconds of the launches behind op_topp_rows on n_rows rows of n0 candidates over vectors of n entries, mean of iters runs; how many
+    launches a run has)  (lmrs_bench_topp_rows)"""
+    us = C.c_double(); k = C.c_int()
+    _chk(lib().lmrs_bench_topp_rows(device, n_rows, n, n0, iters, C.byref(us), C.byref(k)))
+    return us.value, k.value
 
 
 def bench_sample_rows(n_rows: int, n: int, iters: int = 5, device=0):
@@ -1115,6 +1154,20 @@ class Sampler:
         nxt = C.c_uint32()
         _chk(lib().lmrs_sampler_topp_sorted_pairs(self._h, _p(pairs) if prob.size else None, prob.size, C.byref(nxt)))
         return nxt.value
+
+    def candidates(self):
+        """(the persistent candidate vector as it stands, a PAIR array of vocab_size entries; whether it is known to be in descending order of prob)
+        (lmrs_sampler_candidates)"""
+        pairs = np.zeros(self.vocab_size, PAIR); ordered = C.c_int()
+        _chk(lib().lmrs_sampler_candidates(self._h, _p(pairs), C.byref(ordered)))
+        return pairs, bool(ordered.value)
+
+    def set_candidates(self, pairs) -> None:
+        """replace the persistent vector (vocab_size PAIR entries); the order flag follows from what is given  (lmrs_sampler_set_candidates)"""
+        x = np.ascontiguousarray(pairs, PAIR).reshape(-1)
+        if x.size != self.vocab_size:
+            raise LmrsError("set_candidates: the vector has vocab_size = %d entries, %d were given" % (self.vocab_size, x.size))
+        _chk(lib().lmrs_sampler_set_candidates(self._h, _p(x)))
 
     def info(self):
         """(vocab_size, temperature, top_p, the random number every call draws: random_f32(seed), sampler.rs:119)"""

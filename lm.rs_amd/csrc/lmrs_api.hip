@@ -2071,6 +2071,12 @@ struct lmrs_batch {
     DevBuf<GenRow> gen_st; PinBuf<GenRow> h_gen_st; DevBuf<uint32_t> gen_live; PinBuf<uint32_t> h_gen_live;
     DevBuf<float> gen_lp; PinBuf<float> h_gen_lp;
     SampleSet gen; DevBuf<float> gen_logits; size_t gen_logits_rows = 0;
+    // lmrs_batch_generate_topp (made at the first call with a top-p row, topp_vecs vectors; a call with more makes the set anew): per vector two blocks of
+    // vocab_size pairs (ping-pong) and the sort's keys, the word that says which block holds it now (and its pinned copy), and topp_of / h_topp_of - the
+    // column beside the pass's table that names every output row's vector by its number among the call's top-p rows, so no vector moves at a rebuild
+    // topp_ext: per vector {from where its two blocks agree, how far the call has changed it}; h_topp: the vectors' pinned copies, upload source and download target
+    DevBuf<unsigned long long> topp_state, topp_keys; DevBuf<uint32_t> topp_which, topp_ext, topp_of; PinBuf<uint32_t> h_topp_which, h_topp_ext, h_topp_of;
+    PinBuf<unsigned long long> h_topp; size_t topp_vecs = 0;
     uint32_t* hist_of(uint32_t slot) const { return hist + (size_t)slot * c->args.seq_len; }
     PenaltyRow penalty_row_of(uint32_t slot, int tab_row) const {
         const Penalty& p = pen[slot];
@@ -3116,22 +3122,39 @@ extern "C" int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_ru
 // the live rows alone, through batch_rows (the mask, record and penalty columns with it): rows are independent of each other in every GEMM form, so compaction
 // changes no bit.
 static_assert(kGenRowsMax == (int)kWideBatchMax && kGenStopMax == LMRS_STOP_MAX, "a state block per row of a wide batch, the header's stop set");
-static int gen_alloc(lmrs_batch* b, size_t lp_words) {
+static int gen_alloc(lmrs_batch* b, const std::string& what, size_t lp_words) {
     if (!b->gen_st && !alloc_all({{b->gen_st, kWideBatchMax}, {b->h_gen_st, kWideBatchMax}, {b->gen_live, 1}, {b->h_gen_live, 1}})) {
         (void)hipGetLastError();
-        return fail("lmrs_batch_generate: row state blocks: out of memory");
+        return fail(what + "row state blocks: out of memory");
     }
     // the log-probabilities' block by need (n * M of this call; one that grows is made anew)
     if (lp_words > b->gen_lp.count() && !alloc_all({{b->gen_lp, lp_words}, {b->h_gen_lp, lp_words}})) {
         (void)hipGetLastError();
-        return fail("lmrs_batch_generate: " + std::to_string(lp_words * 4) + " bytes of log-probabilities (and as many pinned): out of memory");
+        return fail(what + std::to_string(lp_words * 4) + " bytes of log-probabilities (and as many pinned): out of memory");
     }
     return 0;
 }
-extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, const uint32_t* max_new,
-                                   const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers, uint32_t check_every,
-                                   uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish, uint64_t* stats2, double* seconds) {
-    const std::string what = "lmrs_batch_generate: ";
+extern "C" int lmrs_sampler_candidates(const lmrs_sampler* s, void* pairs, int* ordered);
+extern "C" int lmrs_sampler_set_candidates(lmrs_sampler* s, const void* pairs);
+// The vectors of a call's nt top-p rows on the device (alloc_all: whole or absent, a call with more rows makes the set anew)
+static int topp_alloc(lmrs_batch* b, const std::string& what, size_t nt) {
+    const size_t V = b->c->args.vocab_size, N = (size_t)topp_sort_n(V), bytes = nt * (2 * V + N) * 8;       // (and nt * V * 8 pinned)
+    if (nt <= b->topp_vecs) return 0;
+    b->topp_vecs = 0;
+    if (!alloc_all({{b->topp_state, nt * 2 * V}, {b->topp_keys, nt * N}, {b->h_topp, nt * V}, {b->topp_which, kWideBatchMax}, {b->h_topp_which, kWideBatchMax},
+                    {b->topp_ext, 2 * kWideBatchMax}, {b->h_topp_ext, 2 * kWideBatchMax}, {b->topp_of, kWideBatchMax}, {b->h_topp_of, kWideBatchMax}})) {
+        (void)hipGetLastError();
+        return fail(what + std::to_string(bytes) + " bytes of candidate vectors and sort keys (and " + std::to_string(nt * V * 8) + " pinned) for " + std::to_string(nt) + " top-p rows: out of memory");
+    }
+    b->topp_vecs = nt;
+    return 0;
+}
+// lmrs_batch_generate and lmrs_batch_generate_topp: one loop.  allow_topp: a top-p row's candidate vector travels to the device at the start, launch_topp_rows
+// follows launch_sample_rows in every pass, and the vector goes back into the host sampler at the end
+static int batch_generate_run(const char* name, bool allow_topp, lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos,
+                              const uint32_t* max_new, const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers, uint32_t check_every,
+                              uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish, uint64_t* stats2, double* seconds) {
+    const std::string what = std::string(name) + ": ";
     const auto t0 = std::chrono::steady_clock::now();
     if (!b) return fail(what + "NULL argument (the batch)");
     if (!slot || !tokens || !pos || !max_new || !out_tokens || !n_out || !finish) return fail(what + "NULL array");
@@ -3141,7 +3164,7 @@ extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* sl
     // the rows as every step checks them (batch_rows: n, slots, tokens, one position each; the table it leaves is built again below) and the samplers as the
     // sampled calls check them (samplers_check: the ONE copy of those rules), then what only this call asks
     int order0[kRowTableMax];
-    if (batch_rows(b, "lmrs_batch_generate", b->width, n, slot, tokens, pos, 1, order0)) return -1;
+    if (batch_rows(b, name, b->width, n, slot, tokens, pos, 1, order0)) return -1;
     GenRow row[kWideBatchMax]; SampleRow par[kWideBatchMax]; bool topp[kWideBatchMax] = {};
     for (uint32_t i = 0; i < n; ++i) par[i] = SampleRow{0.0f, 0.0f, 0.0f};               // a NULL entry: sample_argmax
     uint32_t M = 0; size_t at_stop = 0; bool sampled = false;
@@ -3163,40 +3186,67 @@ extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* sl
             g.n_stop = n_stop[i]; at_stop += n_stop[i];
         }
         // (sample_topp's stale candidate vector lives in the host sampler, sampler.rs:81: a loop with a top-p row cannot run a step without a host round trip)
-        if (topp[i]) return fail(at + "a top-p sampler (top_p = " + std::to_string(par[i].top_p) + ") cannot run in the device loop: its candidate vector lives in the host sampler");
+        if (topp[i] && !allow_topp) return fail(at + "a top-p sampler (top_p = " + std::to_string(par[i].top_p) + ") cannot run in the device loop: its candidate vector lives in the host sampler");
         g.from_samp = par[i].temperature != 0.0f ? 1u : 0u;
         M = std::max(M, max_new[i]);
     }
     for (uint32_t i = 0; i < n; ++i) row[i].out_at = i * M;
+    // the top-p rows' vectors, numbered in row order (tv[i]; hvec: their host copies, the upload's source and the download's target); one that is not
+    // ordered would break the merge's rank argument - no call of this library leaves one (a NaN never passes p >= cutoff), an import can
+    uint32_t tv[kWideBatchMax], nt = 0;
+    for (uint32_t i = 0; i < n; ++i) tv[i] = topp[i] ? nt++ : kToppNoVec;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!topp[i]) continue;
+        int ordered = 0;
+        if (lmrs_sampler_candidates(samplers[i], nullptr, &ordered)) return -1;
+        if (!ordered) return fail(what + "row " + std::to_string(i) + ": the top-p sampler's candidate vector is not in descending order (an import through lmrs_sampler_set_candidates, or a NaN): the device merge needs an ordered vector");
+    }
     if ((sampled || out_logprobs) && cls_rows(c) != (int)V)
         return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: neither sampled rows nor log-probabilities for this vocabulary");
     if ((sampled || out_logprobs) && n > (uint32_t)c->sc_rows)
         return fail(what + "the logits block holds " + std::to_string(c->sc_rows) + " rows of this vocabulary, " + std::to_string(n) + " rows were given");
     HIP_OK(hipSetDevice(c->device));
-    if (gen_alloc(b, out_logprobs ? (size_t)n * M : 0)) return -1;
-    if (sampled && b->gen.rows < n && sample_set_alloc(c, b->gen, std::min<size_t>(b->width, ((size_t)n + 15) / 16 * 16), [](size_t bytes, size_t R) {
+    if (gen_alloc(b, what, out_logprobs ? (size_t)n * M : 0)) return -1;
+    if (sampled && b->gen.rows < n && sample_set_alloc(c, b->gen, std::min<size_t>(b->width, ((size_t)n + 15) / 16 * 16), allow_topp ? +[](size_t bytes, size_t R) {
+            return "lmrs_batch_generate_topp: " + std::to_string(bytes) + " bytes of candidate buffers for " + std::to_string(R) + " rows: out of memory"; } : +[](size_t bytes, size_t R) {
             return "lmrs_batch_generate: " + std::to_string(bytes) + " bytes of candidate buffers for " + std::to_string(R) + " rows: out of memory"; })) return -1;
+    if (nt && topp_alloc(b, what, nt)) return -1;
     if (sampled && out_logprobs && b->gen_logits_rows < n) {
         b->gen_logits_rows = 0;
         if (!b->gen_logits.alloc((size_t)n * V)) { (void)hipGetLastError(); return fail(what + std::to_string((size_t)n * V * 4) + " bytes for the sampled rows' copy of the logits: out of memory"); }
         b->gen_logits_rows = n;
     }
     if (pages_claim_rows(b, what, n, slot, pos, max_new, 0)) return -1;     // every row's whole budget up front: the device loop crosses page edges alone
+    // the vectors up: a vector that is all zero, as created, is cleared in place; every vector starts in its block 0
+    // (both blocks of a vector hold it at the start: a step rewrites a prefix of the other block and relies on the rest)
+    if (nt) { HIP_OK(hipMemsetAsync(b->topp_which, 0, kWideBatchMax * 4, c->stream)); HIP_OK(hipMemsetAsync(b->topp_ext, 0, 2 * kWideBatchMax * 4, c->stream)); }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!topp[i]) continue;
+        unsigned long long* h = b->h_topp + (size_t)tv[i] * V;
+        unsigned long long* d = b->topp_state + (size_t)tv[i] * 2 * V;
+        if (lmrs_sampler_candidates(samplers[i], h, nullptr)) return batch_failed(c);
+        if (std::all_of(h, h + V, [](unsigned long long w) { return w == 0; })) HIP_OK(hipMemsetAsync(d, 0, 2 * V * 8, c->stream));
+        else {
+            HIP_OK(hipMemcpyAsync(d, h, V * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(d + V, d, V * 8, hipMemcpyDeviceToDevice, c->stream));
+        }
+    }
     std::vector<uint32_t> live(n);
     for (uint32_t i = 0; i < n; ++i) live[i] = i;
     uint64_t passes = 0, row_passes = 0;
     // the table of the live rows alone, each where it stands now; output o of the pass is live row (wide ? o : order[o]).  It is built anew only behind a look
     // that found a row ended: while every row is live the device's table and state blocks ARE the rows' state, and the next chunk is enqueued as it stands
     uint32_t ls[kWideBatchMax], lt[kWideBatchMax], lp[kWideBatchMax]; int order[kRowTableMax];
-    bool rebuild = true, wide = false, samp = false; int top = 0;
+    bool rebuild = true, wide = false, samp = false, tp = false; int top = 0;
     while (!live.empty()) {
         const uint32_t nl = (uint32_t)live.size();
         for (uint32_t j = 0; j < nl; ++j) { const uint32_t i = live[j]; ls[j] = slot[i]; lt[j] = row[i].last; lp[j] = pos[i] + row[i].done; }
         auto row_of = [&](uint32_t o) { return live[wide ? o : (uint32_t)order[o]]; };
         if (rebuild) {
-            if (batch_rows(b, "lmrs_batch_generate", b->width, nl, ls, lt, lp, 1, order)) return -1;
-            wide = nl > (uint32_t)kRowTableMax; samp = false;
-            for (uint32_t o = 0; o < nl; ++o) { b->h_gen_st[o] = row[row_of(o)]; samp = samp || row[row_of(o)].from_samp; }
+            if (batch_rows(b, name, b->width, nl, ls, lt, lp, 1, order)) return -1;
+            wide = nl > (uint32_t)kRowTableMax; samp = false; tp = false;
+            for (uint32_t o = 0; o < nl; ++o) { b->h_gen_st[o] = row[row_of(o)]; samp = samp || row[row_of(o)].from_samp; tp = tp || topp[row_of(o)]; }
+            for (uint32_t o = 0; o < nl && tp; ++o) b->h_topp_of[o] = tv[row_of(o)];
             for (uint32_t o = 0; o < nl && samp; ++o) b->gen.h_tab[o] = par[row_of(o)];
             top = wide ? b->h_runs->pos[0] : b->h_tab->pos[0];             // the deepest live row at the build (the tables are sorted by descending position)
         }
@@ -3207,6 +3257,7 @@ extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* sl
                 if (masks_enqueue(b, nl) || record_enqueue(b, nl, nl) || (!passes && batch_state(c))) return -1;
                 HIP_OK(hipMemcpyAsync(b->gen_st, b->h_gen_st, nl * sizeof(GenRow), hipMemcpyHostToDevice, c->stream));
                 if (samp) HIP_OK(hipMemcpyAsync(b->gen.tab, b->gen.h_tab, nl * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+                if (tp) HIP_OK(hipMemcpyAsync(b->topp_of, b->h_topp_of, nl * 4, hipMemcpyHostToDevice, c->stream));
             }
             const GenPick pick{c->sc_idx, samp ? b->gen.out.get() : nullptr, V + 1};
             for (uint32_t k = 0; k < check_every; ++k) {
@@ -3223,6 +3274,12 @@ extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* sl
                         rows = b->gen_logits;
                     }
                     HIP_OK(launch_sample_rows(sample_rows_args(rows, (int)nl, (int)V, (int)V, b->gen.tab, c->sc_idx, b->gen.scratch, b->gen.out), c->stream, (int)b->width));
+                    // the top-p rows' sort, merge and draw behind it; a row that has ended reads its live word and stands still, one without a
+                    // candidate is marked ended (finish 2) before the advance sees it
+                    uint32_t* st_words = reinterpret_cast<uint32_t*>(b->gen_st.get());
+                    if (tp) HIP_OK(launch_topp_rows(ToppRowsArgs{b->gen.out, V + 1, b->gen.tab, b->topp_of, (int)nl, (int)V, b->topp_state, b->topp_which, b->topp_ext, b->topp_keys,
+                                                                 topp_sort_n(V), st_words + offsetof(GenRow, live) / 4, st_words + offsetof(GenRow, finish) / 4,
+                                                                 sizeof(GenRow) / 4, nullptr}, c->stream));
                 }
                 if (out_logprobs) HIP_OK(launch_gen_logprobs(b->gen_st, pick, c->sc_logits, (int)V, (int)V, c->sc_part, b->gen_lp, (int)nl, c->stream));
                 HIP_OK(launch_gen_advance(b->gen_st, wide ? b->runs->pos : b->tab->pos, wide ? b->runs->tok : b->tab->tok, wide ? b->runs->sel : nullptr, pick, b->out,
@@ -3243,11 +3300,27 @@ extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* sl
     auto results = [&]() -> int {
         HIP_OK(hipMemcpyAsync(b->h_out, b->out, (size_t)n * M * 4, hipMemcpyDeviceToHost, c->stream));
         if (out_logprobs) HIP_OK(hipMemcpyAsync(b->h_gen_lp, b->gen_lp, (size_t)n * M * 4, hipMemcpyDeviceToHost, c->stream));
+        if (nt) {
+            HIP_OK(hipMemcpyAsync(b->h_topp_which, b->topp_which, nt * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(b->h_topp_ext, b->topp_ext, nt * 2 * 4, hipMemcpyDeviceToHost, c->stream));
+        }
         return 0;
     };
     if (batch_call(c, results)) return -1;
+    // the vectors back into their samplers: the pinned copies still hold them as they came, and a vector has changed only below its extent - that prefix
+    // comes down.  Whatever the caller does with a sampler next continues exactly
+    auto vectors = [&]() -> int {
+        for (uint32_t v = 0; v < nt; ++v) {
+            const size_t changed = std::min<size_t>(b->h_topp_ext[2 * v + 1], V);
+            if (changed) HIP_OK(hipMemcpyAsync(b->h_topp + (size_t)v * V, b->topp_state + ((size_t)v * 2 + (b->h_topp_which[v] & 1u)) * V, changed * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
+    };
+    if (nt && batch_call(c, vectors)) return -1;
+    for (uint32_t i = 0; i < n; ++i)
+        if (topp[i] && lmrs_sampler_set_candidates(samplers[i], b->h_topp + (size_t)tv[i] * V)) return -1;
     for (uint32_t i = 0; i < n; ++i) {
-        n_out[i] = row[i].done; finish[i] = row[i].finish ? LMRS_FINISH_STOP : LMRS_FINISH_BUDGET;
+        n_out[i] = row[i].done; finish[i] = row[i].finish == 2 ? (uint32_t)LMRS_FINISH_NO_CANDIDATE : row[i].finish ? LMRS_FINISH_STOP : LMRS_FINISH_BUDGET;
         for (uint32_t j = 0; j < M; ++j) {
             out_tokens[(size_t)i * M + j] = j < row[i].done ? b->h_out[(size_t)i * M + j] : 0u;
             if (out_logprobs) out_logprobs[(size_t)i * M + j] = j < row[i].done ? b->h_gen_lp[(size_t)i * M + j] : 0.0f;
@@ -3256,6 +3329,19 @@ extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* sl
     if (stats2) { stats2[0] = passes; stats2[1] = row_passes; }
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
+}
+extern "C" int lmrs_batch_generate(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, const uint32_t* max_new,
+                                   const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers, uint32_t check_every,
+                                   uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish, uint64_t* stats2, double* seconds) {
+    return batch_generate_run("lmrs_batch_generate", false, b, n, slot, tokens, pos, max_new, n_stop, stop_tokens, samplers, check_every, out_tokens, out_logprobs,
+                              n_out, finish, stats2, seconds);
+}
+// The same loop with top-p rows admitted: their candidate vectors resident on the device for the length of the call (launch_topp_rows)
+extern "C" int lmrs_batch_generate_topp(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* tokens, const uint32_t* pos, const uint32_t* max_new,
+                                        const uint32_t* n_stop, const uint32_t* stop_tokens, lmrs_sampler* const* samplers, uint32_t check_every,
+                                        uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish, uint64_t* stats2, double* seconds) {
+    return batch_generate_run("lmrs_batch_generate_topp", true, b, n, slot, tokens, pos, max_new, n_stop, stop_tokens, samplers, check_every, out_tokens, out_logprobs,
+                              n_out, finish, stats2, seconds);
 }
 
 // ------------------------------------------------------------------ embedding rows into a slot: ONE fill_kv_cache call (transformer.rs:672-684) on the slot's cache
@@ -3784,6 +3870,100 @@ extern "C" int lmrs_op_sort_candidates(int device, const void* pairs, size_t n_r
     HIP_OK(hipDeviceSynchronize());
     for (int f = 0; f < cs.n_rows; ++f)
         HIP_OK(hipMemcpy(static_cast<char*>(sorted) + (size_t)cs.t.row[f] * ld * 8, cs.keys + (size_t)f * cs.N, (size_t)cs.t.n0[f] * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_topp_rows on caller-supplied rows (unit parity against lmrs_sampler_topp_pairs): result blocks as launch_sample_rows leaves them - {0, n0}, then
+// the candidates - every row its own vector, in block 0 of its pair
+static_assert(kToppRowsMax == (int)kWideBatchMax, "a vector per row of a wide batch");
+extern "C" int lmrs_op_topp_rows(int device, size_t n_rows, size_t n, const void* cand, const uint32_t* n0, const float* top_p, const float* rnd,
+                                 void* state, uint32_t* token, uint32_t* status) {
+    const std::string what = "lmrs_op_topp_rows: ";
+    if (!cand || !n0 || !top_p || !rnd || !state || !token || !status) return fail(what + "NULL argument");
+    if (n_rows < 1 || n_rows > (size_t)kToppRowsMax) return fail(what + "n_rows = " + std::to_string(n_rows) + " is outside 1 .. " + std::to_string(kToppRowsMax));
+    if (n < 2 || n > ((size_t)1 << 24)) return fail(what + "need 2 <= n <= 2^24");
+    for (size_t r = 0; r < n_rows; ++r)
+        if (n0[r] > n) return fail(what + "row " + std::to_string(r) + ": n0 = " + std::to_string(n0[r]) + " exceeds n = " + std::to_string(n));
+    if (op_begin(device)) return -1;
+    const size_t N = (size_t)topp_sort_n(n);
+    Scratch S;
+    void *dres = S.get(n_rows * (n + 1) * 8), *dtab = S.get(n_rows * sizeof(SampleRow)), *dof = S.get(n_rows * 4), *dst = S.get(n_rows * 2 * n * 8),
+         *dwhich = S.get(n_rows * 4), *dext = S.get(n_rows * 8), *dkeys = S.get(n_rows * N * 8), *dstatus = S.get(n_rows * 4);
+    if (!dres || !dtab || !dof || !dst || !dwhich || !dext || !dkeys || !dstatus) return fail("hipMalloc failed");
+    std::vector<SampleRow> tab(n_rows); std::vector<uint32_t> of(n_rows), which(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) {
+        tab[r] = SampleRow{1.0f, top_p[r], rnd[r]}; of[r] = (uint32_t)r;
+        const unsigned long long head = (unsigned long long)n0[r] << 32;
+        char* blk = static_cast<char*>(dres) + r * (n + 1) * 8;
+        HIP_OK(hipMemcpy(blk, &head, 8, hipMemcpyHostToDevice));
+        if (n0[r]) HIP_OK(hipMemcpy(blk + 8, static_cast<const char*>(cand) + r * n * 8, (size_t)n0[r] * 8, hipMemcpyHostToDevice));
+        for (int blk2 = 0; blk2 < 2; ++blk2)
+            HIP_OK(hipMemcpy(static_cast<char*>(dst) + (r * 2 + blk2) * n * 8, static_cast<const char*>(state) + r * n * 8, n * 8, hipMemcpyHostToDevice));
+    }
+    HIP_OK(hipMemset(dext, 0, n_rows * 8));
+    HIP_OK(hipMemcpy(dtab, tab.data(), n_rows * sizeof(SampleRow), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dof, of.data(), n_rows * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dwhich, 0, n_rows * 4));
+    HIP_OK(hipMemset(dstatus, 0xFF, n_rows * 4));
+    HIP_OK(launch_topp_rows(ToppRowsArgs{static_cast<unsigned long long*>(dres), n + 1, static_cast<const SampleRow*>(dtab), static_cast<const uint32_t*>(dof),
+                                         (int)n_rows, (int)n, static_cast<unsigned long long*>(dst), static_cast<uint32_t*>(dwhich), static_cast<uint32_t*>(dext),
+                                         static_cast<unsigned long long*>(dkeys), (int)N, nullptr, nullptr, 0, static_cast<uint32_t*>(dstatus)}, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(which.data(), dwhich, n_rows * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(status, dstatus, n_rows * 4, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < n_rows; ++r) {
+        if (status[r] > 1u || (which[r] & 1u) != (status[r] ^ 1u)) return fail(what + "row " + std::to_string(r) + ": the device left no result");
+        unsigned long long head = 0;
+        HIP_OK(hipMemcpy(&head, static_cast<const char*>(dres) + r * (n + 1) * 8, 8, hipMemcpyDeviceToHost));
+        token[r] = status[r] ? 0u : (uint32_t)head;
+        HIP_OK(hipMemcpy(static_cast<char*>(state) + r * n * 8, static_cast<const char*>(dst) + (r * 2 + (which[r] & 1u)) * n * 8, n * 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// measurement: launch_topp_rows on n_rows rows of n0 candidates each (scattered probabilities, index order) over vectors that carry the steps before;
+// *us = the device time of all its launches (HIP events on each dispatch, summed) per run, the mean of iters runs after one warm-up; *launches: how many
+extern "C" int lmrs_bench_topp_rows(int device, size_t n_rows, size_t n, size_t n0, int iters, double* us, int* launches) {
+    if (!us || iters < 1 || n_rows < 1 || n_rows > (size_t)kToppRowsMax || n < 2 || n > ((size_t)1 << 24) || n0 < 1 || n0 > n) return fail("lmrs_bench_topp_rows: bad argument");
+    if (op_begin(device)) return -1;
+    const size_t N = (size_t)topp_sort_n(n);
+    const int K = topp_launches((int)N);
+    Scratch S;
+    void *dres = S.get(n_rows * (n + 1) * 8), *dtab = S.get(n_rows * sizeof(SampleRow)), *dof = S.get(n_rows * 4), *dst = S.get(n_rows * 2 * n * 8),
+         *dwhich = S.get(n_rows * 4), *dext = S.get(n_rows * 8), *dkeys = S.get(n_rows * N * 8);
+    if (!dres || !dtab || !dof || !dst || !dwhich || !dext || !dkeys) return fail("hipMalloc failed");
+    std::vector<unsigned long long> blk(n0 + 1);
+    blk[0] = (unsigned long long)n0 << 32;
+    for (size_t i = 0; i < n0; ++i) {
+        const float p = (float)(1 + (i * 2654435761ull) % 4093) / (4096.0f * (float)n0);
+        uint32_t bits; memcpy(&bits, &p, 4);
+        blk[1 + i] = ((unsigned long long)(uint32_t)(i * (n / n0)) << 32) | bits;
+    }
+    std::vector<SampleRow> tab(n_rows, SampleRow{1.0f, 0.9f, 0.5f}); std::vector<uint32_t> of(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) { of[r] = (uint32_t)r; HIP_OK(hipMemcpy(static_cast<char*>(dres) + r * (n + 1) * 8, blk.data(), (n0 + 1) * 8, hipMemcpyHostToDevice)); }
+    HIP_OK(hipMemcpy(dtab, tab.data(), n_rows * sizeof(SampleRow), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dof, of.data(), n_rows * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dwhich, 0, n_rows * 4));
+    HIP_OK(hipMemset(dst, 0, n_rows * 2 * n * 8));
+    HIP_OK(hipMemset(dext, 0, n_rows * 8));
+    const ToppRowsArgs a{static_cast<unsigned long long*>(dres), n + 1, static_cast<const SampleRow*>(dtab), static_cast<const uint32_t*>(dof), (int)n_rows, (int)n,
+                         static_cast<unsigned long long*>(dst), static_cast<uint32_t*>(dwhich), static_cast<uint32_t*>(dext), static_cast<unsigned long long*>(dkeys), (int)N, nullptr,
+                         nullptr, 0, nullptr};
+    std::vector<hipEvent_t> ev(2 * (size_t)K);
+    for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+    *us = 0.0;
+    int rc = 0;
+    for (int it = -1; it < iters && !rc; ++it) {
+        set_launch_event_pool(ev.data(), K);
+        const hipError_t le = launch_topp_rows(a, nullptr);
+        const int used = launch_event_pool_used();
+        set_launch_event_pool(nullptr, 0);
+        if (le != hipSuccess || hipDeviceSynchronize() != hipSuccess || used != K) { rc = fail("lmrs_bench_topp_rows: the launches failed"); break; }
+        for (int k = 0; k < K && it >= 0; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess) { rc = fail("hipEventElapsedTime failed"); break; } *us += (double)ms * 1e3 / iters; }
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    if (rc) return -1;
+    if (launches) *launches = K;
     return 0;
 }
 

@@ -174,6 +174,27 @@ struct CandSortRows { unsigned row[kCandSortRowsMax]; unsigned n0[kCandSortRowsM
 struct CandSortArgs { const unsigned long long* src; size_t ld; unsigned long long* keys; int N, n_rows; CandSortRows t; };
 hipError_t launch_cand_sort(const CandSortArgs& a, hipStream_t s);
 
+// ---- sample_topp from its sort on (sampler.rs:81-105) for the top-p rows behind launch_sample_rows, their persistent candidate vectors resident on the device
+// (lmrs_batch_generate_topp; see lmrs_kernels.hip).  Output o < n_rows with vec_of[o] != kToppNoVec: res + o * res_ld is its result block ({token, n0}, then
+// the n0 candidates in index order), tab[o] its top_p and rnd; its vector v = vec_of[o] stands in block which[v] of the two blocks of n pairs at
+// state + v * 2 * n, ordered by descending prob.  The new vector - the stable merge of the sorted candidates with entries [n0, n) of the old one - goes to the
+// other block, the token to the low word of the result block's head, and which[v] flips.  Only a prefix is written: entries at and beyond
+// P = n0 + #{rest entries above the smallest candidate} keep place and value, and the two blocks agree from ext[2 v] on (0 at the start: the caller makes
+// them equal), so a step writes [0, max(P, ext[2 v])) and leaves ext[2 v] = P; ext[2 v + 1] = the largest P so far: beyond it the vector is as it
+// came.  n0 == 0: nothing moves; live[o * st_ld] = 0 and
+// finish[o * st_ld] = 2 (live non-null), status[o] = 1 (status non-null; 0 for a token).  A row whose live word is 0 is left alone by every launch.
+// keys: N words per vector, N = topp_sort_n(n).  The launch count depends on n alone; all asynchronous on `s`.
+constexpr uint32_t kToppNoVec = 0xFFFFFFFFu;
+constexpr int kToppRowsMax = 64;                 // = kWideBatchMax
+struct ToppRowsArgs {
+    unsigned long long* res; size_t res_ld; const SampleRow* tab; const uint32_t* vec_of; int n_rows, n;
+    unsigned long long* state; uint32_t* which; uint32_t* ext; unsigned long long* keys; int N;
+    uint32_t* live; uint32_t* finish; size_t st_ld; uint32_t* status;
+};
+int topp_sort_n(size_t n);
+int topp_launches(int N);
+hipError_t launch_topp_rows(const ToppRowsArgs& a, hipStream_t s);
+
 // thin kernels over the same device functions, for the lmrs_op_* unit-parity entry points
 hipError_t launch_quantize(const float* x, void* q, float* s, int n, int q4, hipStream_t st);
 // batched prefill on row shards (Q8_0): this shard's slices of n_tok tokens quantised into its exchange block; the gathered blocks as a GEMM operand

@@ -3251,6 +3251,211 @@ hipError_t launch_cand_sort(const CandSortArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// sample_topp from its sort on (sampler.rs:81-105) with the persistent candidate vectors resident on the device (launch_topp_rows: lmrs_batch_generate_topp).
+// batch_sample_pairs_kernel has left every top-p row's n0 candidates in index order behind the row's head word; per such row, with no host step and no n0
+// known to the host:
+//   1. the candidates sorted by (prob descending, index ascending): the network above on the keys (~bits(prob) << 32) | index, sized per row - N_r = the
+//      power of two >= max(n0, kSortBlock), read from the head word.  The first launch forms the keys as it loads them; workgroups beyond N_r and whole
+//      launches of stages beyond it return at once, so the launch count is fixed by n alone and a row of n0 <= kSortBlock is done after one launch.
+//   2. the stable merge with the ordered rest, by rank: the host's topp_tail merges the sorted candidates with entries [n0, n) of the old vector, equal
+//      probabilities from the candidates first (std::inplace_merge).  Candidate i therefore lands at i + #{rest entries > it}, rest entry j at
+//      (j - n0) + #{candidates >= it} - both counts one binary search in a descending run, every target written once, no atomics.  The new vector goes to
+//      the row's other block (ping-pong): the old one is read while the new one is written.  Rest entries not above the smallest candidate keep their
+//      place, so only [0, P) is formed, P = n0 + #{rest entries above the smallest candidate}; the other block is two steps old, but it agrees with
+//      this one from the P of the step before on (ext), so copying [P, that) completes it: a peaked row moves a few hundred bytes a step, not 2 x n pairs.
+//   3. the cumulative chain over the new vector's first n0 entries until it exceeds top_p, r = rnd * cumulative, the cdf chain up to last_idx
+//      (sampler.rs:83-105): one adding lane per row, the rows side by side, the terms through LDS; the chains of non-negative terms never fall, so the lane
+//      tests once per 16 terms and walks the group that passed again.
+// A row that is not live (it has ended but still stands in the pass's table) returns from every launch: a second merge of the same candidates would not
+// leave the same bits.  n0 == 0: the reference panics (n0 - 1 underflows); here the draw marks the row ended (finish 2) and nothing else of it moves.
+// ------------------------------------------------------------------------------------------------
+constexpr int kToppChunk = 2048, kToppGroup = 16;                 // the chains: terms per LDS fill, terms per test
+struct ToppRow { int v, n0, Nr; };                                 // v < 0: nothing to do for this output row
+__device__ __forceinline__ ToppRow topp_row(const ToppRowsArgs& a, int o) {
+    const uint32_t v = a.vec_of[o];
+    if (v == kToppNoVec || (a.live && !a.live[(size_t)o * a.st_ld])) return ToppRow{-1, 0, 0};
+    const int n0 = (int)(a.res[(size_t)o * a.res_ld] >> 32);
+    int Nr = kSortBlock;
+    while (Nr < n0) Nr <<= 1;
+    return ToppRow{(int)v, n0 < a.n ? n0 : a.n, Nr};
+}
+__device__ __forceinline__ float topp_pair_prob(unsigned long long w) { return __uint_as_float((unsigned)w); }       // {prob, index}: prob in the low word
+__device__ __forceinline__ float topp_key_prob(unsigned long long k) { return __uint_as_float(~(unsigned)(k >> 32)); }
+template <bool TAIL>
+__global__ __launch_bounds__(kSortThreads) void topp_sort_local_kernel(const ToppRowsArgs a, int k_outer) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long* t = reinterpret_cast<unsigned long long*>(smem);
+    const int o = blockIdx.y, base = blockIdx.x * kSortBlock;
+    const ToppRow tr = topp_row(a, o);
+    if (tr.v < 0 || tr.n0 == 0 || base >= tr.Nr || (TAIL && k_outer > tr.Nr)) return;          // (uniform over the workgroup)
+    // a row that fits this one block sorts the power of two that holds its n0, not the whole block: a peaked row's network is a few steps long
+    int m = kSortBlock;
+    if (!TAIL && tr.Nr == kSortBlock) { m = 2; while (m < tr.n0) m <<= 1; }
+    unsigned long long* keys = a.keys + (size_t)tr.v * a.N + base;
+    const unsigned long long* cand = a.res + (size_t)o * a.res_ld + 1 + base;
+    for (int i = threadIdx.x; i < m; i += kSortThreads) {
+        unsigned long long key;
+        if (TAIL) key = keys[i];
+        else {
+            key = ~0ull;
+            if (base + i < tr.n0) { const unsigned long long w = cand[i]; key = ((unsigned long long)(~(unsigned)w) << 32) | (w >> 32); }
+        }
+        t[i] = key;
+    }
+    __syncthreads();
+    for (int k = TAIL ? k_outer : 2; k <= (TAIL ? k_outer : m); k <<= 1) {
+        for (int j = (TAIL ? kSortBlock : k) >> 1; j > 0; j >>= 1) {
+            for (int q = threadIdx.x; q < m / 2; q += kSortThreads) {
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;        // the pair (i, i + j)
+                const bool up = ((base + i) & k) == 0;
+                const unsigned long long x = t[i], y = t[l];
+                if ((x > y) == up) { t[i] = y; t[l] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = threadIdx.x; i < m; i += kSortThreads) keys[i] = t[i];
+}
+__global__ __launch_bounds__(kBlock) void topp_sort_global_kernel(const ToppRowsArgs a, int j, int k) {
+    const ToppRow tr = topp_row(a, blockIdx.y);
+    if (tr.v < 0 || tr.n0 == 0 || k > tr.Nr) return;
+    unsigned long long* keys = a.keys + (size_t)tr.v * a.N;
+    for (int q = blockIdx.x * kBlock + threadIdx.x; q < tr.Nr / 2; q += gridDim.x * kBlock) {
+        const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
+        const bool up = (i & k) == 0;
+        const unsigned long long x = keys[i], y = keys[l];
+        if ((x > y) == up) { keys[i] = y; keys[l] = x; }
+    }
+}
+// P: the first rest entry (in the old vector's own numbering, >= n0) that is not above the smallest candidate - from there on nothing moves
+__device__ __forceinline__ int topp_moved(const unsigned long long* keys, const unsigned long long* old, int n0, int n) {
+    const float least = topp_key_prob(keys[n0 - 1]);
+    int lo = n0, hi = n;
+    while (lo < hi) { const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1); if (topp_pair_prob(old[mid]) > least) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__global__ __launch_bounds__(kBlock) void topp_rank_kernel(const ToppRowsArgs a) {
+    __shared__ int moved;
+    const ToppRow tr = topp_row(a, blockIdx.y);
+    if (tr.v < 0 || tr.n0 == 0) return;
+    const int n = a.n, n0 = tr.n0;
+    const unsigned long long* keys = a.keys + (size_t)tr.v * a.N;
+    const unsigned long long* old = a.state + ((size_t)tr.v * 2 + a.which[tr.v]) * (size_t)n;
+    unsigned long long* neu = a.state + ((size_t)tr.v * 2 + (a.which[tr.v] ^ 1u)) * (size_t)n;
+    if (threadIdx.x == 0) moved = topp_moved(keys, old, n0, n);
+    __syncthreads();
+    const int P = moved, agree = (int)a.ext[2 * tr.v], W = P > agree ? P : (agree < n ? agree : n);
+    for (int e = blockIdx.x * kBlock + threadIdx.x; e < W; e += gridDim.x * kBlock) {
+        if (e >= P) neu[e] = old[e];                              // (in place already; the other block missed the step before)
+        else if (e < n0) {                                             // a candidate: the rest entries that go before it are those strictly above it
+            const unsigned long long key = keys[e];
+            const float p = topp_key_prob(key);
+            int lo = n0, hi = n;
+            while (lo < hi) { const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1); if (topp_pair_prob(old[mid]) > p) lo = mid + 1; else hi = mid; }
+            neu[e + (lo - n0)] = (key << 32) | (unsigned long long)(~(unsigned)(key >> 32));
+        } else {                                                  // a rest entry: the candidates that go before it are those at or above it
+            const unsigned long long w = old[e];
+            const float p = topp_pair_prob(w);
+            int lo = 0, hi = n0;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (topp_key_prob(keys[mid]) >= p) lo = mid + 1; else hi = mid; }
+            neu[(e - n0) + lo] = w;
+        }
+    }
+}
+// one chain: acc over vec[0 .. limit) in order until `acc > bound`; -> the index where it passed (acc there), or -1 (acc: the whole sum).  Every thread of the
+// workgroup calls it; thread 0 adds, and the answer is the same in all
+__device__ __forceinline__ int topp_chain(const unsigned long long* vec, int limit, float bound, float& acc_out, float* buf, int* sh) {
+    const int tid = threadIdx.x;
+    float acc = 0.0f; int hit = -1;
+    if (tid == 0) sh[0] = -1;
+    for (int c0 = 0; c0 < limit; c0 += kToppChunk) {
+        for (int i = tid; i < kToppChunk; i += kBlock) buf[i] = c0 + i < limit ? topp_pair_prob(vec[c0 + i]) : 0.0f;         // (beyond the limit: +0.0, which moves no chain)
+        __syncthreads();
+        if (tid == 0) {
+            for (int g = 0; g < kToppChunk && c0 + g < limit && hit < 0; g += kToppGroup) {
+                const float start = acc;
+#pragma unroll
+                for (int u = 0; u < kToppGroup; ++u) acc = acc + buf[g + u];
+                if (acc > bound) {
+                    float cu = start;                            // (once per chain: rolled, no branches)
+#pragma unroll 1
+                    for (int u = 0; u < kToppGroup; ++u) {
+                        cu = cu + buf[g + u];
+                        const bool first = hit < 0 && cu > bound;
+                        hit = first ? c0 + g + u : hit; acc = first ? cu : acc;
+                    }
+                }
+            }
+            if (hit >= 0) sh[0] = hit;
+        }
+        __syncthreads();
+        if (sh[0] >= 0) break;
+    }
+    if (tid == 0) reinterpret_cast<float*>(sh)[1] = acc;
+    __syncthreads();
+    acc_out = reinterpret_cast<float*>(sh)[1];
+    const int r = sh[0];
+    __syncthreads();
+    return r;
+}
+__global__ __launch_bounds__(kBlock) void topp_draw_kernel(const ToppRowsArgs a) {
+    __shared__ float buf[kToppChunk];
+    __shared__ int sh[2];
+    const int o = blockIdx.x, tid = threadIdx.x;
+    const ToppRow tr = topp_row(a, o);
+    if (tr.v < 0) return;
+    if (tr.n0 == 0) {
+        if (tid == 0) {
+            if (a.live) { a.live[(size_t)o * a.st_ld] = 0; a.finish[(size_t)o * a.st_ld] = 2; }
+            if (a.status) a.status[o] = 1;
+        }
+        return;
+    }
+    const SampleRow sr = a.tab[o];
+    const unsigned long long* vec = a.state + ((size_t)tr.v * 2 + (a.which[tr.v] ^ 1u)) * (size_t)a.n;
+    // the cumulative chain up to top_p (sampler.rs:86-93), then the cdf chain up to r = rnd * cumulative (:96-104, r < cdf): one copy of the chain's code
+    float bound = sr.top_p, acc;
+    int limit = tr.n0, last_idx = 0, drawn = -1;
+#pragma unroll 1
+    for (int phase = 0; phase < 2; ++phase) {
+        const int hit = topp_chain(vec, limit, bound, acc, buf, sh);
+        if (phase == 0) { last_idx = hit >= 0 ? hit : tr.n0 - 1; limit = last_idx + 1; bound = sr.rnd * acc; }
+        else drawn = hit;
+    }
+    if (tid == 0) {
+        reinterpret_cast<uint32_t*>(a.res + (size_t)o * a.res_ld)[0] = (uint32_t)(vec[drawn >= 0 ? drawn : last_idx] >> 32);
+        const uint32_t P = (uint32_t)topp_moved(a.keys + (size_t)tr.v * a.N, a.state + ((size_t)tr.v * 2 + a.which[tr.v]) * (size_t)a.n, tr.n0, a.n);
+        a.ext[2 * tr.v] = P;
+        if (P > a.ext[2 * tr.v + 1]) a.ext[2 * tr.v + 1] = P;
+        a.which[tr.v] ^= 1u;
+        if (a.status) a.status[o] = 0;
+    }
+}
+int topp_sort_n(size_t n) { size_t N = kSortBlock; while (N < n) N <<= 1; return (int)N; }
+int topp_launches(int N) {
+    int c = 3;                                                     // the first sort launch, the merge, the draw
+    for (int k = 2 * kSortBlock; k <= N; k <<= 1) { for (int j = k >> 1; j >= kSortBlock; j >>= 1) ++c; ++c; }
+    return c;
+}
+hipError_t launch_topp_rows(const ToppRowsArgs& a, hipStream_t s) {
+    if (a.n_rows < 1 || a.n_rows > kToppRowsMax || a.n < 2 || a.N != topp_sort_n((size_t)a.n) || a.res_ld < (size_t)a.n + 1 || !a.res || !a.tab || !a.vec_of || !a.state ||
+        !a.which || !a.ext || !a.keys || (a.live && !a.finish)) return hipErrorInvalidValue;
+    const unsigned R = (unsigned)a.n_rows;
+    const int half = a.N / 2 / kBlock < 256 ? a.N / 2 / kBlock : 256, all = (a.n + kBlock - 1) / kBlock < 256 ? (a.n + kBlock - 1) / kBlock : 256;
+    allow_big_lds(reinterpret_cast<const void*>(topp_sort_local_kernel<false>));
+    allow_big_lds(reinterpret_cast<const void*>(topp_sort_local_kernel<true>));
+    const size_t smem = (size_t)kSortBlock * 8;
+    LMRS_LAUNCH_GRID(topp_sort_local_kernel<false>, dim3(a.N / kSortBlock, R), kSortThreads, smem, s, a, 0);
+    for (int k = 2 * kSortBlock; k <= a.N; k <<= 1) {
+        for (int j = k >> 1; j >= kSortBlock; j >>= 1) LMRS_LAUNCH_GRID(topp_sort_global_kernel, dim3(half, R), kBlock, 0, s, a, j, k);
+        LMRS_LAUNCH_GRID(topp_sort_local_kernel<true>, dim3(a.N / kSortBlock, R), kSortThreads, smem, s, a, k);
+    }
+    LMRS_LAUNCH_GRID(topp_rank_kernel, dim3(all, R), kBlock, 0, s, a);
+    LMRS_LAUNCH_GRID(topp_draw_kernel, dim3(R), kBlock, 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Thin kernels for the lmrs_op_* entry points: the same device functions as the fused path.
 // ------------------------------------------------------------------------------------------------
 template <bool Q4>

@@ -257,6 +257,28 @@ extern "C" int lmrs_sampler_info(const lmrs_sampler* s, uint32_t* vocab_size, fl
     return 0;
 }
 
+// The persistent vector out and in, as it stands: vocab_size pairs {f32 prob, u32 index} (lmrs_batch_generate_topp carries it to the device and back).
+// *ordered: rest_ordered (pairs NULL: the flag alone).  An import scans what it is given: descending and free of NaNs, or every later call sorts the whole vector (topp_tail)
+extern "C" int lmrs_sampler_candidates(const lmrs_sampler* s, void* pairs, int* ordered) {
+    if (!s || (!pairs && !ordered)) return text_fail("lmrs_sampler_candidates: NULL argument");
+    static_assert(sizeof(lmrs_sampler::ProbIndex) == 8, "pair layout");
+    if (pairs) memcpy(pairs, s->probindex.data(), s->probindex.size() * sizeof(lmrs_sampler::ProbIndex));
+    if (ordered) *ordered = s->rest_ordered ? 1 : 0;
+    return 0;
+}
+extern "C" int lmrs_sampler_set_candidates(lmrs_sampler* s, const void* pairs) {
+    if (!s || !pairs) return text_fail("lmrs_sampler_set_candidates: NULL argument");
+    if (s->pending_n0 != (size_t)-1) return text_fail("lmrs_sampler_set_candidates: between lmrs_sampler_exps_prepare and lmrs_sampler_exps_finish (this call's candidates sit in the vector)");
+    memcpy(s->probindex.data(), pairs, s->probindex.size() * sizeof(lmrs_sampler::ProbIndex));
+    bool ok = true;
+    for (size_t i = 0; i < s->probindex.size() && ok; ++i) {
+        const float p = s->probindex[i].prob;
+        ok = p == p && (i == 0 || !(p > s->probindex[i - 1].prob));
+    }
+    s->rest_ordered = ok;
+    return 0;
+}
+
 // sample_topp from its sort on (sampler.rs:81-105): probindex[0 .. n0) holds this call's candidates in index order
 static int topp_tail(lmrs_sampler* s, size_t n0, float rnd, uint32_t* next, bool presorted = false) {
     // :81 sorts the WHOLE vector (stable, descending by prob), stale entries of earlier calls included.  The vector left that sort fully

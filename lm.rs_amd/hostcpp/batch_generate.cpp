@@ -3,9 +3,11 @@
 // tokens are admitted in ONE call of Batch::forward_runs (lmrs_batch_forward_runs, K/V rows only); then ONE call of Batch::generate (lmrs_batch_generate)
 // feeds every prompt's last token and runs every row to the tokenizer's EOS - every row's stop set - or to --n tokens: the stop test, the budget and the
 // rows' advance stand on the device, the host looks at the rows' state every --check-every passes and goes on with the live rows alone.  With
-// --temperature T > 0 row i samples with Sampler::new(vocab_size, T, 1.0, --seed + i) (sample_mult; the loop takes no top-p sampler), else it takes the argmax.
+// --temperature T > 0 row i samples with Sampler::new(vocab_size, T, 1.0, --seed + i) (sample_mult), else it takes the argmax.  With --top-p P in (0, 1) beside
+// it the samplers are the reference's default kind, Sampler::new(vocab_size, T, P, --seed + i), and the call is Batch::generate_topp
+// (lmrs_batch_generate_topp: the samplers' candidate vectors live on the device for the length of the call).
 // Prints per prompt "[i] (stop|budget, logprob S) text": the finish reason and the sum of the log-probabilities of the tokens it chose.
-//   usage: batch_generate --model m.lmrs --tokenizer tokenizer.bin --prompts file.txt [--n N (default 64)] [--check-every K (4)] [--temperature T (0)] [--seed S (0)]
+//   usage: batch_generate --model m.lmrs --tokenizer tokenizer.bin --prompts file.txt [--n N (default 64)] [--check-every K (4)] [--temperature T (0)] [--top-p P (1)] [--seed S (0)]
 //   g++ -O2 -std=c++17 batch_generate.cpp -I../../include -L.. -llmrs_hip -Wl,-rpath,'$ORIGIN/..' -o batch_generate
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -23,7 +25,7 @@
 int main(int argc, char** argv) {
     std::string model_path, tok_path, prompts_path;
     long n_new = 64, check_every = 4;
-    float temperature = 0.0f;
+    float temperature = 0.0f, top_p = 1.0f;
     unsigned long long seed = 0;
     for (int i = 1; i < argc; i += 2) {
         const std::string k = argv[i];
@@ -34,11 +36,12 @@ int main(int argc, char** argv) {
         else if (k == "--n") n_new = std::atol(argv[i + 1]);
         else if (k == "--check-every") check_every = std::atol(argv[i + 1]);
         else if (k == "--temperature") temperature = std::strtof(argv[i + 1], nullptr);
+        else if (k == "--top-p") top_p = std::strtof(argv[i + 1], nullptr);
         else if (k == "--seed") seed = std::strtoull(argv[i + 1], nullptr, 10);
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (model_path.empty() || tok_path.empty() || prompts_path.empty() || n_new < 1 || check_every < 1) {
-        std::fprintf(stderr, "usage: %s --model m.lmrs --tokenizer tokenizer.bin --prompts file.txt [--n N] [--check-every K] [--temperature T] [--seed S]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s --model m.lmrs --tokenizer tokenizer.bin --prompts file.txt [--n N] [--check-every K] [--temperature T] [--top-p P] [--seed S]\n", argv[0]);
         return 2;
     }
     std::ifstream pf(prompts_path);
@@ -70,21 +73,23 @@ int main(int argc, char** argv) {
             if (ids.size() + static_cast<std::size_t>(n_new) - 1 > model.args.seq_len) { std::fprintf(stderr, "prompt %u and %ld tokens exceed seq_len\n", i, n_new); return 1; }
             slots.push_back(i); last.push_back(ids.back()); pos.push_back(static_cast<std::uint32_t>(ids.size() - 1)); budget.push_back(static_cast<std::uint32_t>(n_new));
             stop.push_back({tok.eos});
-            if (temperature > 0.0f) { owners.push_back(std::make_unique<lmrs_host::Sampler>(V, temperature, 1.0f, seed + i)); samplers.push_back(owners.back()->handle()); }
+            if (temperature > 0.0f) { owners.push_back(std::make_unique<lmrs_host::Sampler>(V, temperature, top_p, seed + i)); samplers.push_back(owners.back()->handle()); }
             ids.pop_back();
             total += ids.size();
             if (!ids.empty()) admit.push_back(lmrs_host::Batch::Run{i, 0, std::move(ids), 0});
         }
         if (total > 512) { std::fprintf(stderr, "the prompts hold %zu tokens, more than the 512 rows of one pass\n", total); return 1; }
         if (!admit.empty()) batch.forward_runs(admit);
-        const lmrs_host::Batch::Generated g = batch.generate(slots, last, pos, budget, stop, samplers, static_cast<std::uint32_t>(check_every), /*logprobs=*/true);
+        const bool topp = temperature > 0.0f && top_p > 0.0f && top_p < 1.0f;
+        const lmrs_host::Batch::Generated g = topp ? batch.generate_topp(slots, last, pos, budget, stop, samplers, static_cast<std::uint32_t>(check_every), /*logprobs=*/true)
+                                                   : batch.generate(slots, last, pos, budget, stop, samplers, static_cast<std::uint32_t>(check_every), /*logprobs=*/true);
         for (std::uint32_t i = 0; i < n; ++i) {
             std::string text; double sum = 0.0;
             for (std::size_t j = 0; j < g.tokens[i].size(); ++j) {
                 sum += g.logprobs[i][j];
                 if (g.tokens[i][j] != tok.eos) text += tok.decode(g.tokens[i][j]);
             }
-            std::printf("[%u] (%s, logprob %.4f) %s\n", i, g.finish[i] == lmrs_host::Batch::FINISH_STOP ? "stop" : "budget", sum, text.c_str());
+            std::printf("[%u] (%s, logprob %.4f) %s\n", i, g.finish[i] == lmrs_host::Batch::FINISH_STOP ? "stop" : g.finish[i] == lmrs_host::Batch::FINISH_NO_CANDIDATE ? "no candidate" : "budget", sum, text.c_str());
         }
         std::fprintf(stderr, "%llu passes, %llu row passes, %.3f s\n", static_cast<unsigned long long>(g.passes), static_cast<unsigned long long>(g.row_passes), g.seconds);
     } catch (const lmrs_host::Panic& e) { std::fprintf(stderr, "panic: %s\n", e.what()); return 101; }

@@ -266,7 +266,8 @@ public:
     // (Sampler::handle(), text.hpp; argmax and sample_mult samplers, top-p is refused), the argmax for a null entry or an empty `samplers` - until it chooses a
     // token of stop[i] (FINISH_STOP: the token is reported, never fed) or has produced max_new[i] tokens (FINISH_BUDGET).  stop: empty, or one set (at most
     // STOP_MAX tokens) per row.  check_every: passes between two looks at the rows' state; no result depends on it  (lmrs_batch_generate)
-    static constexpr std::uint32_t STOP_MAX = LMRS_STOP_MAX, FINISH_BUDGET = LMRS_FINISH_BUDGET, FINISH_STOP = LMRS_FINISH_STOP;
+    static constexpr std::uint32_t STOP_MAX = LMRS_STOP_MAX, FINISH_BUDGET = LMRS_FINISH_BUDGET, FINISH_STOP = LMRS_FINISH_STOP,
+                                   FINISH_NO_CANDIDATE = LMRS_FINISH_NO_CANDIDATE;
     struct Generated {
         std::vector<std::vector<std::uint32_t>> tokens;      // row i's outputs, n_out[i] of them
         std::vector<std::vector<float>> logprobs;            // with logprobs: log softmax of the row each token was chosen from, at that token
@@ -276,6 +277,19 @@ public:
     Generated generate(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
                        const std::vector<std::uint32_t>& max_new, const std::vector<std::vector<std::uint32_t>>& stop = {},
                        const std::vector<lmrs_sampler*>& samplers = {}, std::uint32_t check_every = 4, bool logprobs = false) {
+        return generate_by(false, slot, tokens, pos, max_new, stop, samplers, check_every, logprobs);
+    }
+    // generate with top-p samplers admitted, each in one row only: their candidate vectors live on the device for the length of the call and are back in
+    // the samplers when it returns.  A row whose step finds no candidate above the cutoff ends with FINISH_NO_CANDIDATE and reports no token for that
+    // step  (lmrs_batch_generate_topp)
+    Generated generate_topp(const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
+                            const std::vector<std::uint32_t>& max_new, const std::vector<std::vector<std::uint32_t>>& stop = {},
+                            const std::vector<lmrs_sampler*>& samplers = {}, std::uint32_t check_every = 4, bool logprobs = false) {
+        return generate_by(true, slot, tokens, pos, max_new, stop, samplers, check_every, logprobs);
+    }
+    Generated generate_by(bool topp, const std::vector<std::uint32_t>& slot, const std::vector<std::uint32_t>& tokens, const std::vector<std::uint32_t>& pos,
+                          const std::vector<std::uint32_t>& max_new, const std::vector<std::vector<std::uint32_t>>& stop,
+                          const std::vector<lmrs_sampler*>& samplers, std::uint32_t check_every, bool logprobs) {
         const std::size_t n = slot.size();
         if (tokens.size() != n || pos.size() != n || max_new.size() != n) throw Panic("Batch::generate: one slot, token, position and budget per row");
         if (!stop.empty() && stop.size() != n) throw Panic("Batch::generate: stop is empty or holds one set per row");
@@ -288,9 +302,13 @@ public:
         std::vector<float> lp(logprobs ? n * M : 0);
         std::uint64_t stats[2] = {0, 0};
         Generated g;
-        check(lmrs_batch_generate(b_, static_cast<std::uint32_t>(n), slot.data(), tokens.data(), pos.data(), max_new.data(), stop.empty() ? nullptr : n_stop.data(),
-                                  packed.empty() ? nullptr : packed.data(), samplers.empty() ? nullptr : samplers.data(), check_every, out.data(),
-                                  logprobs ? lp.data() : nullptr, n_out.data(), fin.data(), stats, &g.seconds));
+        const std::uint32_t* ns = stop.empty() ? nullptr : n_stop.data(); const std::uint32_t* st = packed.empty() ? nullptr : packed.data();
+        lmrs_sampler* const* sm = samplers.empty() ? nullptr : samplers.data(); float* lps = logprobs ? lp.data() : nullptr;
+        const std::uint32_t rows = static_cast<std::uint32_t>(n);
+        check(topp ? lmrs_batch_generate_topp(b_, rows, slot.data(), tokens.data(), pos.data(), max_new.data(), ns, st, sm, check_every, out.data(), lps, n_out.data(),
+                                              fin.data(), stats, &g.seconds)
+                   : lmrs_batch_generate(b_, rows, slot.data(), tokens.data(), pos.data(), max_new.data(), ns, st, sm, check_every, out.data(), lps, n_out.data(),
+                                         fin.data(), stats, &g.seconds));
         for (std::size_t i = 0; i < n; ++i) {
             g.tokens.emplace_back(out.begin() + i * M, out.begin() + i * M + n_out[i]);
             if (logprobs) g.logprobs.emplace_back(lp.begin() + i * M, lp.begin() + i * M + n_out[i]);

@@ -48,6 +48,10 @@ extern "C" {
                                n_stop: *const u32, stop_tokens: *const u32, samplers: *const *mut LmrsSampler, check_every: u32,
                                out_tokens: *mut u32, out_logprobs: *mut f32, n_out: *mut u32, finish: *mut u32, stats2: *mut u64,
                                seconds: *mut f64) -> c_int;
+    pub fn lmrs_batch_generate_topp(b: *mut LmrsBatch, n: u32, slot: *const u32, tokens: *const u32, pos: *const u32, max_new: *const u32,
+                                    n_stop: *const u32, stop_tokens: *const u32, samplers: *const *mut LmrsSampler, check_every: u32,
+                                    out_tokens: *mut u32, out_logprobs: *mut f32, n_out: *mut u32, finish: *mut u32, stats2: *mut u64,
+                                    seconds: *mut f64) -> c_int;
 }
 
 /// The most stop tokens a row of `Batch::generate` takes (`LMRS_STOP_MAX`).
@@ -55,6 +59,8 @@ pub const STOP_MAX: usize = 16;
 /// `Batch::generate`'s finish codes (`LMRS_FINISH_BUDGET`, `LMRS_FINISH_STOP`).
 pub const FINISH_BUDGET: u32 = 0;
 pub const FINISH_STOP: u32 = 1;
+/// `Batch::generate_topp`: a top-p row's step found no candidate above the cutoff (`LMRS_FINISH_NO_CANDIDATE`).
+pub const FINISH_NO_CANDIDATE: u32 = 2;
 
 /// What `Batch::generate` returns: per row its tokens (cut to `n_out`), their log-probabilities when asked for, and its finish code; the passes the
 /// loop ran, the sum over them of the rows in the pass, and the call's host wall time.
@@ -333,6 +339,21 @@ impl<'t, 'a> Batch<'t, 'a> {
     #[allow(clippy::too_many_arguments)]
     pub fn generate(&mut self, slot: &[u32], tokens: &[u32], pos: &[u32], max_new: &[u32], stop: &[&[u32]], samplers: &[Option<&Sampler>],
                     check_every: u32, logprobs: bool) -> Generated {
+        self.generate_by(false, slot, tokens, pos, max_new, stop, samplers, check_every, logprobs)
+    }
+
+    /// `generate` with top-p samplers admitted, each in one row only (`lmrs_batch_generate_topp`): their candidate vectors live on the device for the
+    /// length of the call and are back in the samplers when it returns, so whatever is done with a sampler next continues exactly.  A row whose step
+    /// finds no candidate above the cutoff ends with `FINISH_NO_CANDIDATE` and reports no token for that step.
+    #[allow(clippy::too_many_arguments)]
+    pub fn generate_topp(&mut self, slot: &[u32], tokens: &[u32], pos: &[u32], max_new: &[u32], stop: &[&[u32]], samplers: &[Option<&Sampler>],
+                         check_every: u32, logprobs: bool) -> Generated {
+        self.generate_by(true, slot, tokens, pos, max_new, stop, samplers, check_every, logprobs)
+    }
+
+    #[allow(clippy::too_many_arguments)]
+    fn generate_by(&mut self, topp: bool, slot: &[u32], tokens: &[u32], pos: &[u32], max_new: &[u32], stop: &[&[u32]], samplers: &[Option<&Sampler>],
+                   check_every: u32, logprobs: bool) -> Generated {
         let n = slot.len();
         assert!(tokens.len() == n && pos.len() == n && max_new.len() == n, "one slot, token, position and budget per row");
         assert!(stop.is_empty() || stop.len() == n, "stop is empty or holds one set per row");
@@ -343,12 +364,13 @@ impl<'t, 'a> Batch<'t, 'a> {
         let m = max_new.iter().copied().max().unwrap_or(0).max(1) as usize;
         let (mut out, mut lp) = (vec![0u32; n * m], vec![0f32; if logprobs { n * m } else { 0 }]);
         let (mut n_out, mut finish, mut stats, mut seconds) = (vec![0u32; n], vec![0u32; n], [0u64; 2], 0f64);
+        let call = if topp { lmrs_batch_generate_topp } else { lmrs_batch_generate };
         check(unsafe {
-            lmrs_batch_generate(self.b, n as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), max_new.as_ptr(),
-                                if stop.is_empty() { ptr::null() } else { n_stop.as_ptr() }, if packed.is_empty() { ptr::null() } else { packed.as_ptr() },
-                                if samplers.is_empty() { ptr::null() } else { handles.as_ptr() }, check_every, out.as_mut_ptr(),
-                                if logprobs { lp.as_mut_ptr() } else { ptr::null_mut() }, n_out.as_mut_ptr(), finish.as_mut_ptr(), stats.as_mut_ptr(),
-                                &mut seconds)
+            call(self.b, n as u32, slot.as_ptr(), tokens.as_ptr(), pos.as_ptr(), max_new.as_ptr(),
+                 if stop.is_empty() { ptr::null() } else { n_stop.as_ptr() }, if packed.is_empty() { ptr::null() } else { packed.as_ptr() },
+                 if samplers.is_empty() { ptr::null() } else { handles.as_ptr() }, check_every, out.as_mut_ptr(),
+                 if logprobs { lp.as_mut_ptr() } else { ptr::null_mut() }, n_out.as_mut_ptr(), finish.as_mut_ptr(), stats.as_mut_ptr(),
+                 &mut seconds)
         });
         let cut = |i: usize| i * m..i * m + n_out[i] as usize;
         Generated {
