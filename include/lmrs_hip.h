@@ -799,6 +799,69 @@ int lmrs_batch_generate_topp(lmrs_batch* b, uint32_t n, const uint32_t* slot, co
                              uint32_t check_every, uint32_t* out_tokens, float* out_logprobs, uint32_t* n_out, uint32_t* finish,
                              uint64_t* stats2, double* seconds);
 
+/* ---- token automata on batch slots: a mask that follows the chosen token, inside the device loops (extensions, no reference counterpart) ----
+ * A grammar needs another mask after every token; lmrs_batch_set_masks' mask is constant over a call.  An automaton is a DFA over tokens in the usual
+ * compressed form: class_of[vocab_size] (uint16_t, each below n_classes), next[n_states * n_classes] (each a state or LMRS_STATE_DEAD), and an optional
+ * final flag per state (final NULL: no state is final).  Token t is allowed in state q iff next[q][class_of[t]] != DEAD, and choosing t moves the slot to
+ * that state.  Every state that is not final must allow at least one token below vocab_size; a final state may allow none.
+ * Host only, plain arithmetic, no device touched:
+ * lmrs_automaton_check: the tables' rules - n_states in 1 .. 2^31 - 1, n_classes in 1 .. 65536, every class below n_classes (the token and the class are
+ *   named), every next entry a state or DEAD (the state and the class are named), every non-final state with an allowed token (the state is named; where
+ *   its live classes are all empty, the first of them too); n_allowed_out (n_states words, may be NULL): the allowed tokens of every state.
+ * lmrs_automaton_walk: tokens[0 .. n) from `state`; 0, *out_state = the state behind them, *n_walked = n.  At the first token its state does not allow the
+ *   call fails (the message names the token and the state) with *n_walked = the tokens consumed and *out_state = the state in front of that token.
+ * Automata of a batch, at most LMRS_AUTOMATA_MAX (16) at a time:
+ * lmrs_batch_automaton_create: runs the check (under this call's name), uploads class_of and next - the final flag folded into bit 31 of the next entries,
+ *   so the step boundary needs no third dependent load - and BUILDS THE PER-STATE MASKS ON THE DEVICE (automaton_masks_kernel): n_states * W words in
+ *   lmrs_batch_set_masks' bit layout, bits at and above vocab_size clear.  2 * vocab_size + 4 * n_states * (n_classes + W) bytes on the device, all or
+ *   nothing, the message gives the bytes; the caller's arrays are free on return.  Refused on a model whose classifier leaves a vocabulary tail unwritten.
+ * lmrs_batch_automaton_destroy: refused while a slot is attached to it; lmrs_batch_destroy frees every automaton of the batch.
+ * lmrs_batch_attach_automaton: slot[i] is attached to a[i] in state[i] (a[i] NULL: detached, state[i] ignored; detaching a slot without one is no error).
+ * lmrs_batch_automaton_state: the slot's state, that state's allowed tokens and its final flag; *state = LMRS_STATE_DEAD (the others 0): no automaton.
+ * lmrs_batch_automaton_advance: lmrs_automaton_walk applied to the slot's state; a disallowed token fails the call and changes nothing.
+ * lmrs_op_automaton_masks: the mask builder alone on caller-supplied tables (bits_out: n_states * W words); the tables' ranges are checked, the rule
+ *   about non-final states is not.
+ * Semantics, in the masks' own words: a slot with an automaton has, at every moment, the mask of its current state.  Every output row of the slot in any
+ * batch call - lmrs_batch_forward, _forward_runs* (all n_out rows under the slot's current state: a draft is verified under it), _forward_sample,
+ * _forward_runs_sample, the _embed forms and both device loops, contiguous, wide and paged - is computed under that mask, behind the slot's penalties and
+ * in front of every sink, bit for bit as lmrs_batch_set_masks defines it.  The launch (auto_rows_mask_kernel) is mask_rows_kernel with the row's mask
+ * address resolved on the device through the slot's state word: masks + state * W.  ONLY the explicit calls above and the two device loops move a state.
+ * lmrs_batch_mask_info reports the current state's count, lmrs_batch_forward_runs refuses k above it; lmrs_batch_fork and lmrs_batch_release neither copy
+ * nor clear an attachment.  A batch that never attaches an automaton enqueues exactly what it enqueued without these calls.
+ * The device loops (lmrs_batch_generate, lmrs_batch_generate_topp; signatures unchanged).  Steps 1 to 6 run as documented; the boundary launch also forms
+ * q' = next[q][class_of[o_j]] for every live row whose slot has an automaton, and between STOP and BUDGET stands a new ending: q' final - the row ends
+ * with finish[i] = LMRS_FINISH_FINAL, the token reported and never fed.  A row that stays live has q' stored in the slot's state word on the device, and
+ * the next pass is masked under it with no host involvement (nor does a rebuilt table need anything new: it names slots, not states).  A row that ends
+ * leaves its state word alone, so its recomputed last row is the same bits into the same places; the host completes the walk when it collects the row:
+ * when the call returns, lmrs_batch_automaton_state of every row's slot is the walk of its n_out reported tokens from the start state (a STOP or BUDGET
+ * token included; a LMRS_FINISH_NO_CANDIDATE step reports no token and moves nothing).  Results do not depend on check_every; out_logprobs come from the
+ * masked row; stats2, the paged claims and "no write beyond pos + n_out" are unchanged.  A row whose allowed logits hold no number can choose a token
+ * its state does not allow: the device leaves such a state alone and the call fails at the end with the walk's message.
+ * Not measured yet: the loop against one set_masks + one-token lmrs_batch_generate per step, and the automaton's cost per pass (DESIGN.md 4.4.15;
+ * hostcpp/batch_grammar.cpp prints both).
+ * Errors, each with a message of its own that opens with the call's name, before any device work, the states unchanged, batch and context usable:
+ * a NULL batch or array; a handle that is not an automaton of this batch; a seventeenth automaton; slot >= n_slots, the same slot twice, n above
+ * lmrs_batch_width; attaching to a slot that has a mask, and lmrs_batch_set_masks on a slot that has an automaton (one mask source per slot: a ban-list
+ * belongs in the automaton's classes); a start state out of range; a start state that is final and allows no token; any pass whose output rows include
+ * a slot standing in a final state that allows no token; lmrs_batch_generate_greedy with a row whose slot has an automaton (lmrs_batch_generate without
+ * stop sets is its superset). */
+#define LMRS_STATE_DEAD 0xFFFFFFFFu
+#define LMRS_AUTOMATA_MAX 16
+#define LMRS_FINISH_FINAL 3
+typedef struct lmrs_automaton lmrs_automaton;
+int lmrs_automaton_check(uint32_t vocab_size, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next,
+                         const uint8_t* final /* n_states, may be NULL */, uint32_t* n_allowed_out /* n_states, may be NULL */);
+int lmrs_automaton_walk(uint32_t vocab_size, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next,
+                        const uint8_t* final, uint32_t state, const uint32_t* tokens, size_t n, uint32_t* out_state, size_t* n_walked);
+int lmrs_batch_automaton_create(lmrs_batch* b, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next,
+                                const uint8_t* final, lmrs_automaton** a);
+int lmrs_batch_automaton_destroy(lmrs_batch* b, lmrs_automaton* a);
+int lmrs_batch_attach_automaton(lmrs_batch* b, uint32_t n, const uint32_t* slot, lmrs_automaton* const* a /* a[i] NULL: detach */, const uint32_t* state);
+int lmrs_batch_automaton_state(const lmrs_batch* b, uint32_t slot, uint32_t* state /* LMRS_STATE_DEAD: no automaton */, uint32_t* n_allowed, int* is_final);
+int lmrs_batch_automaton_advance(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n);
+int lmrs_op_automaton_masks(int device, uint32_t vocab_size, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next,
+                            uint32_t* bits_out /* n_states * W */);
+
 #ifdef __cplusplus
 }
 #endif

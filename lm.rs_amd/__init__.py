@@ -37,6 +37,8 @@ EXPORTS = [
     "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
     "lmrs_batch_generate",
     "lmrs_batch_generate_topp", "lmrs_sampler_candidates", "lmrs_sampler_set_candidates", "lmrs_op_topp_rows", "lmrs_bench_topp_rows",
+    "lmrs_automaton_check", "lmrs_automaton_walk", "lmrs_batch_automaton_create", "lmrs_batch_automaton_destroy", "lmrs_batch_attach_automaton",
+    "lmrs_batch_automaton_state", "lmrs_batch_automaton_advance", "lmrs_op_automaton_masks",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -123,6 +125,14 @@ def lib():
         L.lmrs_batch_set_masks.argtypes = [vp, u32, vp, vp]
         L.lmrs_batch_clear_masks.argtypes = [vp, u32, vp]
         L.lmrs_batch_mask_info.argtypes = [vp, u32, C.POINTER(u32)]
+        L.lmrs_automaton_check.argtypes = [u32, u32, u32, vp, vp, vp, vp]
+        L.lmrs_automaton_walk.argtypes = [u32, u32, u32, vp, vp, vp, u32, vp, sz, C.POINTER(u32), C.POINTER(sz)]
+        L.lmrs_batch_automaton_create.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(vp)]
+        L.lmrs_batch_automaton_destroy.argtypes = [vp, vp]
+        L.lmrs_batch_attach_automaton.argtypes = [vp, u32, vp, vp, vp]
+        L.lmrs_batch_automaton_state.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
+        L.lmrs_batch_automaton_advance.argtypes = [vp, u32, vp, sz]
+        L.lmrs_op_automaton_masks.argtypes = [C.c_int, u32, u32, u32, vp, vp, vp]
         L.lmrs_batch_set_history.argtypes = [vp, u32, u32, vp, sz]
         L.lmrs_batch_history.argtypes = [vp, u32, u32, sz, vp]
         L.lmrs_batch_set_penalties.argtypes = [vp, u32, vp, vp, vp, vp, vp]
@@ -439,6 +449,92 @@ TOKEN_NONE = 0xFFFFFFFF       # Batch.history / set_history: a position whose to
 STOP_MAX = 16                 # Batch.generate: the most stop tokens a row takes (LMRS_STOP_MAX)
 FINISH_BUDGET, FINISH_STOP = 0, 1     # Batch.generate's finish codes (LMRS_FINISH_BUDGET / LMRS_FINISH_STOP)
 FINISH_NO_CANDIDATE = 2               # Batch.generate_topp: a top-p row's step found no candidate above the cutoff (LMRS_FINISH_NO_CANDIDATE)
+FINISH_FINAL = 3                      # Batch.generate / generate_topp: the row's automaton reached a final state (LMRS_FINISH_FINAL)
+STATE_DEAD = 0xFFFFFFFF               # TokenAutomaton.next: no transition - the class's tokens are not allowed in that state (LMRS_STATE_DEAD)
+AUTOMATA_MAX = 16                     # the automata a batch holds at a time (LMRS_AUTOMATA_MAX)
+
+
+class TokenAutomaton:
+    """A DFA over tokens in compressed form (include/lmrs_hip.h): class_of uint16 [vocab_size], next uint32 [n_states, n_classes] - a state or
+    STATE_DEAD - and final bool [n_states].  Token t is allowed in state q iff next[q, class_of[t]] != STATE_DEAD, and choosing it moves there.
+    Every state that is not final must allow a token; a final state may allow none.  Host arithmetic only: no GPU is touched here."""
+
+    def __init__(self, class_of, next, final=None):
+        self.class_of = np.ascontiguousarray(class_of, np.uint16).reshape(-1)
+        nx = np.ascontiguousarray(next, np.uint32)
+        if nx.ndim != 2:
+            raise LmrsError("next must be [n_states, n_classes]")
+        self.next = nx
+        self.final = np.zeros(nx.shape[0], np.uint8) if final is None else np.ascontiguousarray(np.asarray(final).astype(bool), np.uint8).reshape(-1)
+        if self.final.size != nx.shape[0]:
+            raise LmrsError("final must hold one flag per state")
+
+    vocab_size = property(lambda self: int(self.class_of.size))
+    n_states = property(lambda self: int(self.next.shape[0]))
+    n_classes = property(lambda self: int(self.next.shape[1]))
+
+    def check(self) -> np.ndarray:
+        """The tables' rules -> the allowed tokens of every state, uint32 [n_states]; a broken rule raises with the state, class or token named
+        (lmrs_automaton_check)"""
+        n = np.zeros(self.n_states, np.uint32)
+        _chk(lib().lmrs_automaton_check(self.vocab_size, self.n_states, self.n_classes, _p(self.class_of), _p(self.next), _p(self.final), _p(n)))
+        return n
+
+    def walk(self, state: int, tokens):
+        """tokens from `state` -> (state behind them, tokens walked, ok): ok false - the walk stopped in front of a token its state does not allow,
+        and the state is the one in front of that token (lmrs_automaton_walk)"""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        q, k = C.c_uint32(), C.c_size_t()
+        rc = lib().lmrs_automaton_walk(self.vocab_size, self.n_states, self.n_classes, _p(self.class_of), _p(self.next), _p(self.final), state,
+                                       _p(t) if t.size else None, t.size, C.byref(q), C.byref(k))
+        if rc and not (k.value < t.size and " is not allowed in state " in lib().lmrs_last_error().decode()):
+            _chk(rc)                                             # (an argument out of range, not a disallowed token)
+        return q.value, k.value, rc == 0
+
+    def allowed(self, state: int) -> np.ndarray:
+        """bool [vocab_size]: the tokens `state` allows"""
+        return self.next[state][self.class_of] != STATE_DEAD
+
+    @classmethod
+    def from_transitions(cls, vocab_size: int, table, final=None) -> "TokenAutomaton":
+        """table: dense uint32 [n_states, vocab_size] (a state or STATE_DEAD per token), or a list of dicts {token: state}, one per state.  Tokens whose
+        columns are identical share a class (at most 65536 classes)"""
+        if isinstance(table, np.ndarray):
+            dense = np.ascontiguousarray(table, np.uint32)
+        else:
+            dense = np.full((len(table), vocab_size), STATE_DEAD, np.uint32)
+            for q, row in enumerate(table):
+                for t, to in row.items():
+                    dense[q, t] = to
+        if dense.ndim != 2 or dense.shape[1] != vocab_size:
+            raise LmrsError(f"a dense table must be [n_states, vocab_size = {vocab_size}]")
+        cols, inverse = np.unique(dense.T, axis=0, return_inverse=True)
+        if cols.shape[0] > 65536:
+            raise LmrsError(f"{cols.shape[0]} distinct token columns: more than 65536 classes")
+        return cls(inverse.reshape(-1).astype(np.uint16), np.ascontiguousarray(cols.T), final)
+
+    @classmethod
+    def from_sequences(cls, vocab_size: int, seqs) -> "TokenAutomaton":
+        """"Choose one of these multi-token labels": a trie over the token sequences, state 0 its root, every leaf final.  No sequence may be empty
+        or a proper prefix of another (its end would be an inner state)"""
+        rows, final = [{}], [False]
+        for seq in seqs:
+            seq = [int(t) for t in seq]
+            if not seq:
+                raise LmrsError("from_sequences: an empty sequence")
+            q = 0
+            for t in seq:
+                if not 0 <= t < vocab_size:
+                    raise LmrsError(f"from_sequences: token {t} is not below vocab_size = {vocab_size}")
+                if final[q]:
+                    raise LmrsError("from_sequences: a sequence is a proper prefix of another")
+                if t not in rows[q]:
+                    rows[q][t] = len(rows); rows.append({}); final.append(False)
+                q = rows[q][t]
+            if rows[q]:
+                raise LmrsError("from_sequences: a sequence is a proper prefix of another")
+            final[q] = True
+        return cls.from_transitions(vocab_size, rows, final)
 
 
 class Batch:
@@ -519,6 +615,43 @@ class Batch:
         n = C.c_uint32()
         _chk(lib().lmrs_batch_mask_info(self._h, slot, C.byref(n)))
         return n.value or None
+
+    def automaton(self, ta: TokenAutomaton):
+        """`ta` on the device for this batch -> a handle for attach: its tables uploaded, the per-state masks built there; at most AUTOMATA_MAX at a
+        time (lmrs_batch_automaton_create).  drop_automaton frees one that no slot is attached to; closing the batch frees all"""
+        if ta.vocab_size != self.model.args.vocab_size:
+            raise LmrsError(f"the automaton is over {ta.vocab_size} tokens, the model's vocab_size is {self.model.args.vocab_size}")
+        h = C.c_void_p()
+        _chk(lib().lmrs_batch_automaton_create(self._h, ta.n_states, ta.n_classes, _p(ta.class_of), _p(ta.next), _p(ta.final), C.byref(h)))
+        return h
+
+    def drop_automaton(self, handle) -> None:
+        """lmrs_batch_automaton_destroy: refused while a slot is attached to it"""
+        _chk(lib().lmrs_batch_automaton_destroy(self._h, handle))
+
+    def attach(self, slots, automata, states=0) -> None:
+        """Slot slots[i] gets automaton automata[i] (a handle of automaton(); None detaches) in start state states[i]; one handle / one state serves
+        every slot.  From then on every output of the slot's rows is computed under the mask of its current state; generate / generate_topp move the
+        state with every token they choose, advance moves it by hand (lmrs_batch_attach_automaton)"""
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+        hs = list(automata) if isinstance(automata, (list, tuple)) else [automata] * s.size
+        q = np.asarray(states)
+        q = np.ascontiguousarray(np.full(s.size, q) if q.ndim == 0 else q.reshape(-1), np.uint32)
+        if len(hs) != s.size or q.size != s.size:
+            raise LmrsError("attach takes one automaton and one state per slot")
+        arr = (C.c_void_p * max(s.size, 1))(*[None if h is None else h for h in hs])
+        _chk(lib().lmrs_batch_attach_automaton(self._h, s.size, _p(s) if s.size else None, C.cast(arr, C.c_void_p), _p(q) if s.size else None))
+
+    def automaton_state(self, slot: int):
+        """-> (state, n_allowed, is_final) of `slot`'s automaton, or None when the slot has none (lmrs_batch_automaton_state)"""
+        q, n, f = C.c_uint32(), C.c_uint32(), C.c_int()
+        _chk(lib().lmrs_batch_automaton_state(self._h, slot, C.byref(q), C.byref(n), C.byref(f)))
+        return None if q.value == STATE_DEAD else (q.value, n.value, bool(f.value))
+
+    def advance(self, slot: int, tokens) -> None:
+        """The slot's state moves over `tokens`; a token its state does not allow raises and changes nothing (lmrs_batch_automaton_advance)"""
+        t = np.ascontiguousarray(tokens, np.uint32).reshape(-1)
+        _chk(lib().lmrs_batch_automaton_advance(self._h, slot, _p(t) if t.size else None, t.size))
 
     def set_penalties(self, slots, repetition=1.0, presence=0.0, frequency=0.0, out_from=0) -> None:
         """Repetition / presence / frequency penalties for `slots`; a scalar serves every slot, an array gives one value each.  While a slot has
@@ -732,7 +865,7 @@ class Batch:
         one list of tokens for all rows; at most STOP_MAX tokens a row.  Samplers: argmax and sample_mult ones (top-p is refused); they may be shared.
         check_every: passes between two looks at the rows' state - the results do not depend on it.
         -> (tokens, finish[, logprobs], stats): tokens a list of uint32 arrays, row i cut to its n_out; finish uint32 [n] (FINISH_BUDGET /
-        FINISH_STOP); logprobs a list of float32 arrays of the same lengths - log softmax of the row each token was chosen from, at that token; stats a
+        FINISH_STOP, FINISH_FINAL where the row's slot has an automaton that reached a final state); logprobs a list of float32 arrays of the same lengths - log softmax of the row each token was chosen from, at that token; stats a
         dict: passes, row_passes (and seconds, host wall time, if timing)  (lmrs_batch_generate)"""
         s, t, p = self._rows(slots, tokens, pos)
         n = s.size
@@ -1180,3 +1313,10 @@ class Sampler:
             lib().lmrs_sampler_destroy(self._h); self._h = None
 
     __del__ = close
+
+
+def automaton_masks(ta: TokenAutomaton, device: int = 0) -> np.ndarray:
+    """The per-state masks of `ta` as the device builds them -> uint32 [n_states, W] in pack_mask's layout (lmrs_op_automaton_masks)"""
+    out = np.zeros((ta.n_states, (ta.vocab_size + 31) // 32), np.uint32)
+    _chk(lib().lmrs_op_automaton_masks(device, ta.vocab_size, ta.n_states, ta.n_classes, _p(ta.class_of), _p(ta.next), _p(out)))
+    return out

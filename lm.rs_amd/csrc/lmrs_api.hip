@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/lmrs_hip.h"
+#include "lmrs_automaton.h"
 #include "lmrs_buf.h"
 #include "lmrs_device_math.h"
 #include "lmrs_format.h"
@@ -196,11 +197,14 @@ struct StepForm { int qa_mode = 0, split_chunks = 0; bool split_merged = false; 
 // masks (masks.bits != null): some output row of the pass belongs to a batch slot with an allowed-token mask (lmrs_batch_set_masks) - of[r] is the mask row of
 // output row r in the order the classifier sees the rows, -1 for none; h_of is its pinned source, which says on the host whether a slab has a masked row at all.
 struct MaskView { const uint32_t* bits = nullptr; int words = 0; const int* of = nullptr; const int* h_of = nullptr; };
+// autos (autos.of != null): some output row of the pass belongs to a slot with a token automaton (lmrs_batch_attach_automaton) - of[r] carries the automaton's
+// tables and the slot, whose state word (state[slot]) the launch reads on the device; h_of is its pinned source, as with the masks
+struct AutoView { const AutoRow* of = nullptr; const AutoRow* h_of = nullptr; const uint32_t* state = nullptr; int words = 0; };
 // penalties (penalties.hist != null): some output row of the pass belongs to a slot with penalties (lmrs_batch_set_penalties) - of[r] carries slot, parameters and the
 // table row whose position is row r's (pos: that column of the pass's device table, read on the device - right inside lmrs_batch_generate_greedy's loops); h_of is
 // its pinned source, as with the masks; max_n = the deepest row's position + 1 at this pass (the keys a workgroup sorts)
 struct PenaltyView { const uint32_t* hist = nullptr; int seq_len = 0; const int* pos = nullptr; const PenaltyRow* of = nullptr; const PenaltyRow* h_of = nullptr; int max_n = 0; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; PenaltyView penalties{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1802,6 +1806,9 @@ static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, float* x
         // a batch's masks (PassForm::masks): one launch a slab, and only for a slab that has a masked row
         if (form.masks.bits && std::any_of(form.masks.h_of + i0 + j0, form.masks.h_of + i0 + j0 + mj, [](int m) { return m >= 0; }))
             HIP_OK(launch_mask_rows(c->sc_logits, o, o, mj, form.masks.bits, form.masks.words, form.masks.of + i0 + j0, c->stream));
+        // a batch's token automata (PassForm::autos): the same stores under the mask of the state each row's slot stands in, found on the device
+        if (form.autos.of && std::any_of(form.autos.h_of + i0 + j0, form.autos.h_of + i0 + j0 + mj, [](const AutoRow& r) { return r.slot >= 0; }))
+            HIP_OK(launch_auto_mask_rows(c->sc_logits, o, o, mj, form.autos.of + i0 + j0, form.autos.state, form.autos.words, c->stream));
         if (to.out_logits && copy_out_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
         if ((!to.out_logits || to.reduce_too) && reduce_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
     }
@@ -2056,6 +2063,33 @@ struct lmrs_batch {
     DevBuf<int> mask_of; PinBuf<int> h_mask_of; bool mask_live = false;
     int mask_row_of(uint32_t slot) const { return n_allowed[slot] ? (int)slot : -1; }
     MaskView mask_view() const { return mask_live ? MaskView{masks, (int)mask_words, mask_of, h_mask_of} : MaskView{}; }
+    // token automata (lmrs_batch_automaton_create / lmrs_batch_attach_automaton): the batch's automata, each with its tables on the host (the walks) and on
+    // the device (class_of, next with the final flag in bit 31, the per-state masks the device built).  aut_of[s]: the automaton of slot s (-1: none), aut_q[s]
+    // its state as the host knows it, n_aut the slots that have one.  aut_state: the state words on the device (made at the first attach, with the columns);
+    // aut_dirty: the host moved a state since the last upload - the next call with such an output row uploads the words first; inside the device loops
+    // gen_advance_kernel moves them and the host catches up by walking the reported tokens.  aut_rows / h_aut_rows: the per-call column of PassForm::autos,
+    // written with the tables; aut_live: this call uploaded it
+    struct Automaton {
+        uint32_t n_states = 0, n_classes = 0, attached = 0;
+        std::vector<uint16_t> class_of; std::vector<uint32_t> next, n_allowed; std::vector<uint8_t> final;
+        DevBuf<uint16_t> d_class_of; DevBuf<uint32_t> d_next, d_masks;
+        AutomatonTables tables(uint32_t V) const { return AutomatonTables{V, n_states, n_classes, class_of.data(), next.data(), final.data()}; }
+    };
+    std::unique_ptr<Automaton> automata[LMRS_AUTOMATA_MAX];
+    int aut_of[kWideBatchMax]; uint32_t aut_q[kWideBatchMax] = {}; uint32_t n_aut = 0;
+    DevBuf<uint32_t> aut_state; PinBuf<uint32_t> h_aut_state; bool aut_dirty = false;
+    DevBuf<AutoRow> aut_rows; PinBuf<AutoRow> h_aut_rows; bool aut_live = false;
+    lmrs_batch() { std::fill(aut_of, aut_of + kWideBatchMax, -1); }
+    const Automaton* automaton_of(uint32_t slot) const { return aut_of[slot] >= 0 ? automata[aut_of[slot]].get() : nullptr; }
+    AutoRow auto_row_of(uint32_t slot) const {
+        const Automaton* a = automaton_of(slot);
+        return a ? AutoRow{a->d_masks, a->d_class_of, a->d_next, a->n_classes, a->n_states, c->args.vocab_size, (int)slot} : AutoRow{nullptr, nullptr, nullptr, 0, 0, 0, -1};
+    }
+    AutoView auto_view() const { return aut_live ? AutoView{aut_rows, h_aut_rows, aut_state, (int)((c->args.vocab_size + 31) / 32)} : AutoView{}; }
+    // the tokens slot's rows may produce now: its mask's count, or its automaton's current state's; 0: neither
+    uint32_t allowed_now(uint32_t slot) const { const Automaton* a = automaton_of(slot); return a ? a->n_allowed[aut_q[slot]] : n_allowed[slot]; }
+    // a slot standing in a final state that allows no token: no pass may ask for an output row of it
+    bool auto_exhausted(uint32_t slot) const { const Automaton* a = automaton_of(slot); return a && !a->n_allowed[aut_q[slot]]; }
     // the token record and the penalties over it (lmrs_batch_set_history / lmrs_batch_set_penalties; made at the first call of either, `hist` non-null from then
     // on): hist[n_slots][seq_len], LMRS_TOKEN_NONE where the token is unknown.  hist_slot / h_hist_slot: the slot of every row of the pass's table, beside the
     // table (record_enqueue).  pen[s]: slot s's parameters, pen_on[s] - they are other than (1, 0, 0), n_pen the slots where they are.  pen_of / h_pen_of: the
@@ -2201,6 +2235,8 @@ extern "C" int lmrs_batch_set_masks(lmrs_batch* b, uint32_t n, const uint32_t* s
     lmrs_ctx* c = b->c;
     const size_t V = c->args.vocab_size, W = (V + 31) / 32;
     if (cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no masks for this vocabulary");
+    for (uint32_t i = 0; i < n; ++i)
+        if (b->aut_of[slot[i]] >= 0) return fail(what + "mask " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " has an automaton: one mask source per slot (a ban-list belongs in the automaton's classes)");
     const uint32_t last = V % 32 ? (1u << V % 32) - 1u : ~0u;                  // the bits of the last word that lie below vocab_size
     uint32_t count[kWideBatchMax];
     for (uint32_t i = 0; i < n; ++i) {
@@ -2241,7 +2277,124 @@ extern "C" int lmrs_batch_mask_info(const lmrs_batch* b, uint32_t slot, uint32_t
     const std::string what = "lmrs_batch_mask_info: ";
     if (!b || !n_allowed) return fail(what + "NULL argument");
     if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
-    *n_allowed = b->n_allowed[slot];
+    *n_allowed = b->allowed_now(slot);      // (a slot with an automaton: its current state's count)
+    return 0;
+}
+
+// ------------------------------------------------------------------ token automata: a slot's mask follows the token it chose (extensions, no reference counterpart)
+// A slot with an automaton has the mask of its current state: classify_rows' launch (auto_rows_mask_kernel) finds it through the slot's state word on the
+// device, masks + state * W, so the device loops move a row's mask without the host (gen_advance_kernel stores the successor at the step boundary).  A batch
+// that never attaches one enqueues exactly what it enqueued before: every hook tests b->n_aut.
+static int automaton_index(const lmrs_batch* b, const lmrs_automaton* a) {
+    for (int i = 0; i < LMRS_AUTOMATA_MAX; ++i) if (a && reinterpret_cast<const lmrs_automaton*>(b->automata[i].get()) == a) return i;
+    return -1;
+}
+extern "C" int lmrs_batch_automaton_create(lmrs_batch* b, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next, const uint8_t* final,
+                                           lmrs_automaton** out) {
+    const char* name = "lmrs_batch_automaton_create";
+    const std::string what = std::string(name) + ": ";
+    if (!b || !out) return fail(what + "NULL argument");
+    *out = nullptr;
+    lmrs_ctx* c = b->c;
+    const size_t V = c->args.vocab_size, W = (V + 31) / 32;
+    if (cls_rows(c) != (int)V) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no masks for this vocabulary");
+    int at = 0;
+    while (at < LMRS_AUTOMATA_MAX && b->automata[at]) ++at;
+    if (at == LMRS_AUTOMATA_MAX) return fail(what + "the batch holds LMRS_AUTOMATA_MAX = " + std::to_string(LMRS_AUTOMATA_MAX) + " automata already");
+    std::unique_ptr<lmrs_batch::Automaton> a;
+    std::vector<uint32_t> coded;                         // next as the device holds it: the successor's final flag in bit 31
+    try {
+        a.reset(new lmrs_batch::Automaton);
+        a->n_allowed.resize(n_states < kStateFinalBit ? n_states : 0u);             // (out of range: the check says so before it writes a count)
+        if (automaton_check(name, AutomatonTables{(uint32_t)V, n_states, n_classes, class_of, next, final}, a->n_allowed.data(), false)) return -1;
+        const size_t cells = (size_t)n_states * n_classes;
+        a->n_states = n_states; a->n_classes = n_classes;
+        a->class_of.assign(class_of, class_of + V); a->next.assign(next, next + cells);
+        a->final.assign(n_states, 0);
+        if (final) for (uint32_t q = 0; q < n_states; ++q) a->final[q] = final[q] ? 1 : 0;
+        coded = a->next;
+        for (uint32_t& e : coded) if (e != kAutoDead && a->final[e]) e |= kAutoFinalBit;
+    } catch (...) { return fail(what + "out of memory on the host"); }                                  // nothing may unwind through the C ABI
+    HIP_OK(hipSetDevice(c->device));
+    const size_t cells = coded.size(), bytes = V * 2 + (cells + (size_t)n_states * W) * 4;
+    if (!alloc_all({{a->d_class_of, V}, {a->d_next, cells}, {a->d_masks, (size_t)n_states * W}})) {
+        (void)hipGetLastError();
+        return fail(what + std::to_string(bytes) + " bytes of tables and masks for " + std::to_string(n_states) + " states: out of memory");
+    }
+    if (hipMemcpyAsync(a->d_class_of, a->class_of.data(), V * 2, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(a->d_next, coded.data(), cells * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        launch_automaton_masks(a->d_class_of, a->d_next, (int)V, n_states, n_classes, a->d_masks, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(what + std::string("uploading the tables or building the masks failed: ") + hipGetErrorString(hipGetLastError()));
+    b->automata[at] = std::move(a);
+    *out = reinterpret_cast<lmrs_automaton*>(b->automata[at].get());
+    return 0;
+}
+extern "C" int lmrs_batch_automaton_destroy(lmrs_batch* b, lmrs_automaton* a) {
+    const std::string what = "lmrs_batch_automaton_destroy: ";
+    if (!b || !a) return fail(what + "NULL argument");
+    const int at = automaton_index(b, a);
+    if (at < 0) return fail(what + "not an automaton of this batch");
+    if (b->automata[at]->attached) return fail(what + std::to_string(b->automata[at]->attached) + " slots are attached to the automaton: detach them first");
+    HIP_OK(hipSetDevice(b->c->device));
+    HIP_OK(hipStreamSynchronize(b->c->stream));
+    b->automata[at].reset();
+    return 0;
+}
+extern "C" int lmrs_batch_attach_automaton(lmrs_batch* b, uint32_t n, const uint32_t* slot, lmrs_automaton* const* a, const uint32_t* state) {
+    const std::string what = "lmrs_batch_attach_automaton: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && (!slot || !a)) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot, "row ")) return -1;
+    int idx[kWideBatchMax];
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string at = what + "row " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + ": ";
+        idx[i] = -1;
+        if (!a[i]) continue;
+        if (!state) return fail(what + "NULL array (state)");
+        if ((idx[i] = automaton_index(b, a[i])) < 0) return fail(at + "not an automaton of this batch");
+        const lmrs_batch::Automaton& A = *b->automata[idx[i]];
+        if (b->n_allowed[slot[i]]) return fail(at + "the slot has a mask: one mask source per slot (clear it first; a ban-list belongs in the automaton's classes)");
+        if (state[i] >= A.n_states) return fail(at + "start state " + std::to_string(state[i]) + " of " + std::to_string(A.n_states));
+        if (!A.n_allowed[state[i]]) return fail(at + "start state " + std::to_string(state[i]) + " is final and allows no token");
+    }
+    if (!n) return 0;
+    if (!b->aut_state) {
+        HIP_OK(hipSetDevice(b->c->device));
+        if (!alloc_all({{b->aut_state, kWideBatchMax}, {b->h_aut_state, kWideBatchMax}, {b->aut_rows, kRunRowsMax}, {b->h_aut_rows, kRunRowsMax}})) {
+            (void)hipGetLastError();
+            return fail(what + "state words and the passes' column: out of memory");
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t s = slot[i];
+        if (b->aut_of[s] >= 0) { --b->automata[b->aut_of[s]]->attached; --b->n_aut; }
+        b->aut_of[s] = idx[i]; b->aut_q[s] = idx[i] >= 0 ? state[i] : 0u;
+        if (idx[i] >= 0) { ++b->automata[idx[i]]->attached; ++b->n_aut; }
+    }
+    b->aut_dirty = true;
+    return 0;
+}
+extern "C" int lmrs_batch_automaton_state(const lmrs_batch* b, uint32_t slot, uint32_t* state, uint32_t* n_allowed, int* is_final) {
+    const std::string what = "lmrs_batch_automaton_state: ";
+    if (!b || !state) return fail(what + "NULL argument");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    const lmrs_batch::Automaton* a = b->automaton_of(slot);
+    *state = a ? b->aut_q[slot] : LMRS_STATE_DEAD;
+    if (n_allowed) *n_allowed = a ? a->n_allowed[b->aut_q[slot]] : 0u;
+    if (is_final) *is_final = a ? (int)a->final[b->aut_q[slot]] : 0;
+    return 0;
+}
+extern "C" int lmrs_batch_automaton_advance(lmrs_batch* b, uint32_t slot, const uint32_t* tokens, size_t n) {
+    const char* name = "lmrs_batch_automaton_advance";
+    const std::string what = std::string(name) + ": ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    const lmrs_batch::Automaton* a = b->automaton_of(slot);
+    if (!a) return fail(what + "slot " + std::to_string(slot) + " has no automaton");
+    uint32_t q = b->aut_q[slot]; size_t walked = 0;
+    if (automaton_walk(name, a->tables(b->c->args.vocab_size), q, tokens, n, &q, &walked)) return -1;
+    if (q != b->aut_q[slot]) { b->aut_q[slot] = q; b->aut_dirty = true; }
     return 0;
 }
 
@@ -2536,12 +2689,13 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
         const uint32_t len = run_len ? run_len[i] : 1u, no = n_out ? n_out[i] : 1u;
         for (uint32_t u = len - no; u < len; ++u) {
             if (b->n_masked) b->h_mask_of[o] = b->mask_row_of(slot[i]);     // (the classifier sees the outputs in this order)
+            if (b->n_aut) b->h_aut_rows[o] = b->auto_row_of(slot[i]);
             if (b->n_pen) b->h_pen_of[o] = b->penalty_row_of(slot[i], at[j + u]);
             h->sel[o++] = (uint32_t)at[j + u];
         }
         j += len;
     }
-    b->mask_live = false; b->pen_live = false;
+    b->mask_live = false; b->pen_live = false; b->aut_live = false;
     *rows_out = R; *outs = o;
 }
 // One pass over the device's long table as it stands: R rows through the layers, then the O rows of sel through the final norm and the classifier to
@@ -2586,7 +2740,7 @@ static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink t
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
-    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view(); cls.penalties = b->penalty_view(form.runs.pos, form.max_T);
+    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view(); cls.autos = b->auto_view(); cls.penalties = b->penalty_view(form.runs.pos, form.max_T);
     to.targets = false;
     return classify_rows(c, cls, to, b->runs_x, 0, (int)O);
 }
@@ -2605,6 +2759,8 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
         seen |= uint64_t(1) << slot[i];
         if (tokens[i] >= c->args.vocab_size) return fail(std::string(what) + ": token " + std::to_string(i) + " out of range");
         if ((size_t)pos[i] + span > c->args.seq_len) return fail(std::string(what) + ": row " + std::to_string(i) + ": pos + " + std::to_string(span) + " positions exceeds seq_len");
+        if (b->auto_exhausted(slot[i]))
+            return fail(std::string(what) + ": row " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " stands in final state " + std::to_string(b->aut_q[slot[i]]) + " of its automaton, which allows no token");
     }
     if (n > (uint32_t)kRowTableMax) { size_t R, O; runs_table(b, n, slot, pos, nullptr, nullptr, RunRows{nullptr, tokens, nullptr}, &R, &O); return 0; }
     for (uint32_t i = 0; i < n; ++i) order[i] = (int)i;
@@ -2613,10 +2769,11 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
         const int i = order[r];
         b->h_tab->off[r] = b->off_of(slot[i]); b->h_tab->pos[r] = (int)pos[i]; b->h_tab->tok[r] = tokens[i];
         if (b->n_masked) b->h_mask_of[r] = b->mask_row_of(slot[i]);
+        if (b->n_aut) b->h_aut_rows[r] = b->auto_row_of(slot[i]);
         if (b->hist) b->h_hist_slot[r] = (int)slot[i];
         if (b->n_pen) b->h_pen_of[r] = b->penalty_row_of(slot[i], (int)r);
     }
-    b->mask_live = false; b->pen_live = false;
+    b->mask_live = false; b->pen_live = false; b->aut_live = false;
     return 0;
 }
 // The record's columns of a call beside its table (a batch without the record enqueues nothing here): the slot of every one of the table's R rows, and - only
@@ -2632,6 +2789,16 @@ static int record_enqueue(lmrs_batch* b, size_t R, size_t O) {
 // The mask column of a call with n output rows, beside its table: uploaded - and the pass's forms carry it (lmrs_batch::mask_view) - only when one of the
 // rows is masked; a batch without masks enqueues nothing here
 static int masks_enqueue(lmrs_batch* b, size_t n) {
+    // the automata's column in the same way, and in front of it the state words where the host has moved one since they last went up
+    if (b->n_aut && std::any_of(b->h_aut_rows.get(), b->h_aut_rows + n, [](const AutoRow& r) { return r.slot >= 0; })) {
+        if (b->aut_dirty) {
+            memcpy(b->h_aut_state, b->aut_q, b->n_slots * 4);
+            HIP_OK(hipMemcpyAsync(b->aut_state, b->h_aut_state, b->n_slots * 4, hipMemcpyHostToDevice, b->c->stream));
+            b->aut_dirty = false;
+        }
+        HIP_OK(hipMemcpyAsync(b->aut_rows, b->h_aut_rows, n * sizeof(AutoRow), hipMemcpyHostToDevice, b->c->stream));
+        b->aut_live = true;
+    }
     if (!b->n_masked || !std::any_of(b->h_mask_of.get(), b->h_mask_of + n, [](int m) { return m >= 0; })) return 0;
     HIP_OK(hipMemcpyAsync(b->mask_of, b->h_mask_of, n * sizeof(int), hipMemcpyHostToDevice, b->c->stream));
     b->mask_live = true;
@@ -2642,7 +2809,7 @@ static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logit
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
     if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); }
-    form.masks = b->mask_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T);
+    form.masks = b->mask_view(); form.autos = b->auto_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T);
     if (record_rows(b, b->tab->pos, b->tab->tok, n)) return -1;
     RowSink to{0, n, out_logits, 0}; to.targets = false;
     return run_tokens(c, to, form, /*batched=*/true);
@@ -2693,6 +2860,8 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     lmrs_ctx* c = b->c;
     int order[kRowTableMax];
     if (batch_rows(b, "lmrs_batch_generate_greedy", b->width, n, slot, tokens, pos, n_new ? n_new : 1, order)) return -1;
+    for (uint32_t i = 0; i < n; ++i)
+        if (b->aut_of[slot[i]] >= 0) return fail("lmrs_batch_generate_greedy: row " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + " has an automaton: its state moves in lmrs_batch_generate's loop only");
     if (!n_new) return 0;
     if (pages_claim_rows(b, "lmrs_batch_generate_greedy: ", n, slot, pos, nullptr, n_new)) return -1;     // all n_new steps up front: the device loop crosses page edges alone
     HIP_OK(hipSetDevice(c->device));
@@ -2862,6 +3031,8 @@ static int runs_check(const lmrs_batch* b, const std::string& what, uint32_t n_r
         seen |= uint64_t(1) << slot[i];
         if (n_out[i] > run_len[i]) return fail(run + "n_out = " + std::to_string(n_out[i]) + " exceeds run_len = " + std::to_string(run_len[i]));
         if ((size_t)start_pos[i] + run_len[i] > a.seq_len) return fail(run + "start_pos + run_len exceeds seq_len");
+        if (n_out[i] && b->auto_exhausted(slot[i]))
+            return fail(run + "slot " + std::to_string(slot[i]) + " stands in final state " + std::to_string(b->aut_q[slot[i]]) + " of its automaton, which allows no token");
         O += n_out[i];
     }
     if (R > E && !src.tokens) return fail(what + "tokens is NULL with a token run present");
@@ -2892,8 +3063,9 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
     if (O && !argmax) return fail(what + "argmax is NULL with " + std::to_string(O) + " output rows asked for");
     for (uint32_t i = 0; i < n_runs && k; ++i)            // a masked row has n_allowed candidates that are numbers
-        if (n_out[i] && b->n_allowed[slot[i]] && k > b->n_allowed[slot[i]])
-            return fail(what + "run " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + ": k = " + std::to_string(k) + " exceeds the " + std::to_string(b->n_allowed[slot[i]]) + " tokens its mask allows (n_allowed)");
+        if (n_out[i] && b->allowed_now(slot[i]) && k > b->allowed_now(slot[i]))
+            return fail(what + "run " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + ": k = " + std::to_string(k) + " exceeds the " + std::to_string(b->allowed_now(slot[i])) +
+                        (b->automaton_of(slot[i]) ? " tokens its automaton's state allows (n_allowed)" : " tokens its mask allows (n_allowed)"));
     runs_table(b, n_runs, slot, start_pos, run_len, n_out, src, &R, &O);
     HIP_OK(hipSetDevice(c->device));
     if (k && O && topk_alloc(c, c->sc_rows, (int)k)) return -1;
@@ -2961,7 +3133,7 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
         if (block) {                                     // block attention: the table's rows in POSITION order (row r = position p0 + r), no outputs
             RunTable* h = b->h_runs;
             for (uint32_t r = 0; r < m; ++r) { h->off[r] = b->off_of(slot); h->pos[r] = (int)(p0 + r); h->tok[r] = embeddings ? kRowFromStage | r : tokens[i0 + r]; if (b->hist) b->h_hist_slot[r] = (int)slot; }
-            b->mask_live = false; b->pen_live = false;
+            b->mask_live = false; b->pen_live = false; b->aut_live = false;
         } else runs_table(b, 1, &slot, &p0, &m, &n_out, RunRows{&kind, tokens ? tokens + i0 : nullptr, embeddings}, &R, &O);
         auto enqueue = [&]() -> int {
             if (embeddings) HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
@@ -3122,6 +3294,7 @@ extern "C" int lmrs_batch_forward_runs_embed_sample(lmrs_batch* b, uint32_t n_ru
 // the live rows alone, through batch_rows (the mask, record and penalty columns with it): rows are independent of each other in every GEMM form, so compaction
 // changes no bit.
 static_assert(kGenRowsMax == (int)kWideBatchMax && kGenStopMax == LMRS_STOP_MAX, "a state block per row of a wide batch, the header's stop set");
+static_assert(kGenFinishFinal == LMRS_FINISH_FINAL && kAutoDead == LMRS_STATE_DEAD && kAutoFinalBit == kStateFinalBit, "the boundary launch's codes are the header's");
 static int gen_alloc(lmrs_batch* b, const std::string& what, size_t lp_words) {
     if (!b->gen_st && !alloc_all({{b->gen_st, kWideBatchMax}, {b->h_gen_st, kWideBatchMax}, {b->gen_live, 1}, {b->h_gen_live, 1}})) {
         (void)hipGetLastError();
@@ -3233,6 +3406,10 @@ static int batch_generate_run(const char* name, bool allow_topp, lmrs_batch* b, 
     }
     std::vector<uint32_t> live(n);
     for (uint32_t i = 0; i < n; ++i) live[i] = i;
+    // rows whose slots have automata: the boundary launch moves their state words on the device, so however the call ends the host's states go up again
+    // before the next pass that needs them (the walk below makes them the reported tokens' states; a call that fails leaves the start states)
+    struct StatesMoved { lmrs_batch* b; bool on; ~StatesMoved() { if (on) b->aut_dirty = true; } } states_moved{b, false};
+    for (uint32_t i = 0; i < n; ++i) states_moved.on = states_moved.on || b->aut_of[slot[i]] >= 0;
     uint64_t passes = 0, row_passes = 0;
     // the table of the live rows alone, each where it stands now; output o of the pass is live row (wide ? o : order[o]).  It is built anew only behind a look
     // that found a row ended: while every row is live the device's table and state blocks ARE the rows' state, and the next chunk is enqueued as it stands
@@ -3282,8 +3459,9 @@ static int batch_generate_run(const char* name, bool allow_topp, lmrs_batch* b, 
                                                                  sizeof(GenRow) / 4, nullptr}, c->stream));
                 }
                 if (out_logprobs) HIP_OK(launch_gen_logprobs(b->gen_st, pick, c->sc_logits, (int)V, (int)V, c->sc_part, b->gen_lp, (int)nl, c->stream));
+                // (aut_live: the table's build found a row with an automaton - the launch then also moves the slots' state words)
                 HIP_OK(launch_gen_advance(b->gen_st, wide ? b->runs->pos : b->tab->pos, wide ? b->runs->tok : b->tab->tok, wide ? b->runs->sel : nullptr, pick, b->out,
-                                          b->gen_live, (int)nl, c->stream));
+                                          b->gen_live, (int)nl, c->stream, b->aut_live ? b->aut_rows.get() : nullptr, b->aut_live ? b->aut_state.get() : nullptr));
             }
             HIP_OK(hipMemcpyAsync(b->h_gen_st, b->gen_st, nl * sizeof(GenRow), hipMemcpyDeviceToHost, c->stream));
             HIP_OK(hipMemcpyAsync(b->h_gen_live, b->gen_live, 4, hipMemcpyDeviceToHost, c->stream));
@@ -3320,11 +3498,21 @@ static int batch_generate_run(const char* name, bool allow_topp, lmrs_batch* b, 
     for (uint32_t i = 0; i < n; ++i)
         if (topp[i] && lmrs_sampler_set_candidates(samplers[i], b->h_topp + (size_t)tv[i] * V)) return -1;
     for (uint32_t i = 0; i < n; ++i) {
-        n_out[i] = row[i].done; finish[i] = row[i].finish == 2 ? (uint32_t)LMRS_FINISH_NO_CANDIDATE : row[i].finish ? LMRS_FINISH_STOP : LMRS_FINISH_BUDGET;
+        n_out[i] = row[i].done;
+        finish[i] = row[i].finish == 2 ? (uint32_t)LMRS_FINISH_NO_CANDIDATE : row[i].finish == kGenFinishFinal ? (uint32_t)LMRS_FINISH_FINAL : row[i].finish ? LMRS_FINISH_STOP : LMRS_FINISH_BUDGET;
         for (uint32_t j = 0; j < M; ++j) {
             out_tokens[(size_t)i * M + j] = j < row[i].done ? b->h_out[(size_t)i * M + j] : 0u;
             if (out_logprobs) out_logprobs[(size_t)i * M + j] = j < row[i].done ? b->h_gen_lp[(size_t)i * M + j] : 0.0f;
         }
+    }
+    // the automata's states: the walk of every row's reported tokens from its start state (the device moved the words of the rows that stayed live only)
+    for (uint32_t i = 0; i < n; ++i) {
+        const lmrs_batch::Automaton* a = b->automaton_of(slot[i]);
+        if (!a) continue;
+        uint32_t q = b->aut_q[slot[i]]; size_t walked = 0;
+        const int rc = automaton_walk(name, a->tables((uint32_t)V), q, out_tokens + (size_t)i * M, row[i].done, &q, &walked);
+        b->aut_q[slot[i]] = q;
+        if (rc) return fail(what + "row " + std::to_string(i) + ": " + g_err + " (a row without a number among its allowed logits)");
     }
     if (stats2) { stats2[0] = passes; stats2[1] = row_passes; }
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -3870,6 +4058,28 @@ extern "C" int lmrs_op_sort_candidates(int device, const void* pairs, size_t n_r
     HIP_OK(hipDeviceSynchronize());
     for (int f = 0; f < cs.n_rows; ++f)
         HIP_OK(hipMemcpy(static_cast<char*>(sorted) + (size_t)cs.t.row[f] * ld * 8, cs.keys + (size_t)f * cs.N, (size_t)cs.t.n0[f] * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_automaton_masks on caller-supplied tables (unit parity against a host count): the tables' ranges are checked - the kernel indexes by them - the
+// rule about non-final states is not
+extern "C" int lmrs_op_automaton_masks(int device, uint32_t vocab_size, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next,
+                                       uint32_t* bits_out) {
+    const std::string what = "lmrs_op_automaton_masks: ";
+    if (!bits_out) return fail(what + "NULL argument (bits_out)");
+    if (automaton_check("lmrs_op_automaton_masks", AutomatonTables{vocab_size, n_states, n_classes, class_of, next, nullptr}, nullptr, true)) return -1;
+    if (vocab_size > (1u << 24)) return fail(what + "vocab_size exceeds 2^24");
+    if (op_begin(device)) return -1;
+    const size_t V = vocab_size, W = (V + 31) / 32, cells = (size_t)n_states * n_classes;
+    Scratch S;
+    void *dc = S.get(V * 2), *dn = S.get(cells * 4), *db = S.get((size_t)n_states * W * 4);
+    if (!dc || !dn || !db) return fail(what + "hipMalloc failed");
+    HIP_OK(hipMemcpy(dc, class_of, V * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dn, next, cells * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(db, 0xA5, (size_t)n_states * W * 4));                    // (a word the kernel failed to write shows)
+    HIP_OK(launch_automaton_masks(static_cast<const uint16_t*>(dc), static_cast<const uint32_t*>(dn), (int)V, n_states, n_classes, static_cast<uint32_t*>(db), nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(bits_out, db, (size_t)n_states * W * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -51,6 +51,21 @@ hipError_t launch_softcap_rows(float* logits, int ld, int cols, int rows, hipStr
 // the block 16-byte aligned.  (lmrs_batch_set_masks: behind the soft-cap, in front of every sink)
 hipError_t launch_mask_rows(float* logits, int ld, int cols, int rows, const uint32_t* bits, int words, const int* mask_of, hipStream_t s);
 
+// ---- token automata on batch slots (lmrs_batch_automaton_create / lmrs_batch_attach_automaton): the mask of a slot follows the token it chose
+// The tables on the device: class_of[vocab] (uint16_t), next[n_states][n_classes] - a state with kAutoFinalBit where that state is final, or kAutoDead -
+// and masks[n_states][words] in lmrs_batch_set_masks' bit layout.
+constexpr uint32_t kAutoDead = 0xFFFFFFFFu;                 // = LMRS_STATE_DEAD
+constexpr uint32_t kAutoFinalBit = 0x80000000u;
+// bits[q * words + w] for q < n_states, w < words = (vocab + 31) / 32: bit (t & 31) of word (t >> 5) set iff next[q * n_classes + class_of[t]] != kAutoDead;
+// bits at and above vocab clear.  Every class_of entry is below n_classes (the caller checked).  Stores only, every word by one lane, no atomics.
+hipError_t launch_automaton_masks(const uint16_t* class_of, const uint32_t* next, int vocab, uint32_t n_states, uint32_t n_classes, uint32_t* bits, hipStream_t s);
+// One output row's automaton, in the order the classifier sees the rows: slot < 0 - none; else the tables of the automaton the slot is attached to.
+// The slot's state is NOT in here: it is read on the device from the batch's state words (state[slot]), where launch_gen_advance leaves it.
+struct AutoRow { const uint32_t* masks; const uint16_t* class_of; const uint32_t* next; uint32_t n_classes, n_states, vocab; int slot; };
+// launch_mask_rows with the mask resolved on the device: row r < rows with of[r].slot >= 0 is masked under of[r].masks + state[of[r].slot] * words (a state
+// word that is not below n_states: the row is left alone).  Same stores, one more dependent load per workgroup; same conditions on cols, ld and the block.
+hipError_t launch_auto_mask_rows(float* logits, int ld, int cols, int rows, const AutoRow* of, const uint32_t* state, int words, hipStream_t s);
+
 // ---- a batch's token record and the penalties over it (lmrs_batch_set_history / lmrs_batch_set_penalties)
 constexpr uint32_t kTokenNone = 0xFFFFFFFFu;                // = LMRS_TOKEN_NONE: a position whose token is unknown, or an embedding row
 constexpr int kPenaltyKeysMax = 8192;                       // the keys one workgroup sorts in LDS (32 KB): the clamp of seq_len
@@ -77,7 +92,12 @@ struct GenPick { const uint32_t* idx; const unsigned long long* samp; size_t sam
 // Output o < n_rows, live: t = its chosen token -> out[out_at + done]; done += 1; t in its stop set: live = 0, finish = 1; else done == budget: live = 0,
 // finish = 0; else the table row behind it (sel[o]; sel null: row o) gets tok = t, pos += 1.  A row that is not live changes nothing: its table row stays, so
 // the next pass computes the same row again.  *n_live = the rows still live.  One lane per row, plain stores.
-hipError_t launch_gen_advance(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, GenPick pick, uint32_t* out, uint32_t* n_live, int n_rows, hipStream_t s);
+// aut (null: no row of the pass has an automaton - the launch is the kernel it was without them): output o's automaton, state the batch's state words.  For a
+// live row with one, q' = next[state[slot]][class_of[t]]; behind the stop test and in front of the budget's: q' final - live = 0, finish = 3 (kGenFinishFinal); a row
+// that stays live stores q' in state[slot]; a row that ends leaves its state word alone (its recomputed last row is masked as it was; the host completes the walk).
+constexpr uint32_t kGenFinishFinal = 3;                     // = LMRS_FINISH_FINAL (2 is launch_topp_rows' row without a candidate)
+hipError_t launch_gen_advance(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, GenPick pick, uint32_t* out, uint32_t* n_live, int n_rows, hipStream_t s,
+                              const AutoRow* aut = nullptr, uint32_t* state = nullptr);
 // In front of launch_gen_advance, for every live output o: lp_out[out_at + done] = (float)((double)l[t] - m - log(sum)) of row o of `logits` (ld floats a row,
 // all `vocab` written), t the token launch_gen_advance is about to record, m and sum from the chunk summaries launch_score_rows left for the SAME rows in
 // `part`: score_merge_kernel's arithmetic, one rounding to float.  One wave per row.

@@ -17,6 +17,9 @@
 // mask_rows_kernel: a batch slot's allowed-token mask (lmrs_batch_set_masks) over the rows of the block, behind the soft-cap and in front of every
 // sink: -inf over the disallowed logits.  Stores only.
 //
+// automaton_masks_kernel / auto_rows_mask_kernel: a token automaton's per-state masks built from its tables (lmrs_batch_automaton_create), and
+// mask_rows_kernel with the row's mask found through the slot's state word on the device; gen_advance_kernel moves that word at the step boundary.
+//
 // record_rows_kernel / penalty_rows_kernel: a batch's token record per slot and the repetition / presence / frequency penalties over it
 // (lmrs_batch_set_penalties), between the soft-cap and the mask: one workgroup a penalised row sorts the row's record in LDS and changes one logit per
 // distinct token.
@@ -325,6 +328,49 @@ __global__ __launch_bounds__(kLanes) void mask_rows_kernel(float* logits, int ld
     if (!(allowed & 8u)) p[3] = ninf;
 }
 
+// mask_rows_kernel with the mask found on the device (a slot with a token automaton): the row's mask is the one of the state its slot stands in NOW,
+// masks + state[slot] * words - one more dependent load per workgroup, then the same bits, the same four columns a lane and the same stores.  Inside the
+// device loop the state word is what gen_advance_kernel left behind the pass before: the host names the slot once and never the state.
+__global__ __launch_bounds__(kLanes) void auto_rows_mask_kernel(float* logits, int ld, int cols, const AutoRow* of, const uint32_t* state, int words) {
+    const AutoRow a = of[blockIdx.y];
+    if (a.slot < 0) return;
+    const uint32_t q = state[a.slot];
+    if (q >= a.n_states) return;
+    const int g = blockIdx.x * kLanes + threadIdx.x;
+    if (4 * g >= cols) return;
+    const uint32_t allowed = a.masks[(size_t)q * words + (g >> 3)] >> ((g & 7) * 4) & 15u;
+    if (allowed == 15u) return;
+    float* p = logits + (size_t)blockIdx.y * ld + 4 * g;
+    const float ninf = -INFINITY;
+    if (allowed == 0u) { *reinterpret_cast<float4*>(p) = make_float4(ninf, ninf, ninf, ninf); return; }
+    if (!(allowed & 1u)) p[0] = ninf;
+    if (!(allowed & 2u)) p[1] = ninf;
+    if (!(allowed & 4u)) p[2] = ninf;
+    if (!(allowed & 8u)) p[3] = ninf;
+}
+
+// The masks of an automaton's states from its tables (lmrs_batch_automaton_create): one token per lane, a wave's 64 tokens two mask words by a ballot.
+// A lane reads its token's class ONCE and keeps it; the workgroup then walks the states of its grid row (q = blockIdx.y, + gridDim.y, ...), one load from the
+// state's `next` row per lane and state - rows of a few classes sit in one or two cache lines.  Lane 0 of a wave stores the wave's two words; a token at or
+// above `vocab` votes 0, so the bits at and above vocab_size are clear, and a word at or above `words` is not written.  grid (ceil(vocab / 256), states)
+__global__ __launch_bounds__(kLanes) void automaton_masks_kernel(const uint16_t* class_of, const uint32_t* next, int vocab, uint32_t n_states, uint32_t n_classes,
+                                                                 uint32_t* bits, int words) {
+    const int t = blockIdx.x * kLanes + threadIdx.x;
+    const int w0 = (t >> 6) * 2;                                            // the wave's first word (wave-uniform: kLanes % 64 == 0)
+    if (w0 >= words) return;
+    const bool in = t < vocab;
+    const uint32_t c = in ? class_of[t] : 0u;
+    for (uint32_t q = blockIdx.y; q < n_states; q += gridDim.y) {
+        const bool live = in && next[(size_t)q * n_classes + c] != kAutoDead;
+        const unsigned long long m = __ballot(live);
+        if ((threadIdx.x & 63) == 0) {
+            uint32_t* p = bits + (size_t)q * words + w0;
+            p[0] = (uint32_t)m;
+            if (w0 + 1 < words) p[1] = (uint32_t)(m >> 32);
+        }
+    }
+}
+
 // The token record of a batch (lmrs_batch_set_history): table row r wrote K/V at position pos[r] of slot slot_of[r], so hist[slot][pos] = its token -
 // kTokenNone for an embedding row (a source word with the stage bit, lmrs_kernels.h).  One lane a row; two rows of one launch never share a (slot, position).
 __global__ __launch_bounds__(kLanes) void record_rows_kernel(uint32_t* hist, int seq_len, int n_slots, const int* pos, const uint32_t* tok, const int* slot_of, int n_rows) {
@@ -394,8 +440,13 @@ __device__ __forceinline__ uint32_t gen_picked(const GenRow& g, const GenPick& p
     return g.from_samp ? (uint32_t)pick.samp[(size_t)o * pick.samp_ld] : pick.idx[o];
 }
 // one lane per output row; sel null: the row table (output o is table row o), else the long table's sel column
-__global__ __launch_bounds__(kGenRowsMax) void gen_advance_kernel(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, const GenPick pick, uint32_t* out,
-                                                                  uint32_t* n_live, int n_rows) {
+// AUTO: some row of the pass has a token automaton (aut[o].slot >= 0: output o's; state: the batch's state words).  Such a live row takes two dependent loads
+// more - class_of[t], then next[q][class] - and nobody else does; without AUTO the kernel is, instruction for instruction, the one it was before automata.
+// q' dead (the row chose a token its mask had cleared: a row without a number among the allowed) moves nothing: the host's walk reports it.
+// (one body, two kernels under names of their own: gen_advance_kernel is the AUTO = false instance and takes the arguments it always took)
+template <bool AUTO>
+__device__ __forceinline__ void gen_advance_rows(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, const GenPick& pick, uint32_t* out,
+                                                 uint32_t* n_live, int n_rows, const AutoRow* aut, uint32_t* state) {
     const int o = threadIdx.x;
     bool live = false;
     if (o < n_rows) {
@@ -405,20 +456,42 @@ __global__ __launch_bounds__(kGenRowsMax) void gen_advance_kernel(GenRow* st, in
         const uint32_t ti = pick.idx[o], ts = pick.samp ? (uint32_t)pick.samp[(size_t)o * pick.samp_ld] : 0u;
         const uint32_t r = sel ? sel[o] : (uint32_t)o;
         const int p = pos[r];
+        AutoRow a{}; a.slot = -1;
+        if (AUTO) a = aut[o];
         if (g.live) {
             const uint32_t t = g.from_samp ? ts : ti, done = g.done + 1;
             out[g.out_at + g.done] = t;
             bool stop = false;
 #pragma unroll
             for (int k = 0; k < kGenStopMax; ++k) stop = stop || ((uint32_t)k < g.n_stop && g.stop[k] == t);
+            uint32_t nx = kAutoDead;
+            if (AUTO && a.slot >= 0) {
+                const uint32_t q = state[a.slot];
+                if (q < a.n_states && t < a.vocab) {
+                    const uint32_t c = a.class_of[t];
+                    if (c < a.n_classes) nx = a.next[(size_t)q * a.n_classes + c];
+                }
+            }
             st[o].done = done; st[o].last = t;
             if (stop) { st[o].live = 0; st[o].finish = 1; }
+            else if (AUTO && nx != kAutoDead && (nx & kAutoFinalBit)) { st[o].live = 0; st[o].finish = kGenFinishFinal; }
             else if (done >= g.budget) { st[o].live = 0; st[o].finish = 0; }
-            else { tok[r] = t; pos[r] = p + 1; live = true; }
+            else {
+                tok[r] = t; pos[r] = p + 1; live = true;
+                if (AUTO && nx != kAutoDead) state[a.slot] = nx & ~kAutoFinalBit;
+            }
         }
     }
     const unsigned long long m = __ballot(live);
     if (o == 0) *n_live = (uint32_t)__popcll(m);
+}
+__global__ __launch_bounds__(kGenRowsMax) void gen_advance_kernel(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, const GenPick pick, uint32_t* out,
+                                                                  uint32_t* n_live, int n_rows) {
+    gen_advance_rows<false>(st, pos, tok, sel, pick, out, n_live, n_rows, nullptr, nullptr);
+}
+__global__ __launch_bounds__(kGenRowsMax) void gen_advance_auto_kernel(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, const GenPick pick, uint32_t* out,
+                                                                       uint32_t* n_live, int n_rows, const AutoRow* aut, uint32_t* state) {
+    gen_advance_rows<true>(st, pos, tok, sel, pick, out, n_live, n_rows, aut, state);
 }
 // one wave per output row (four rows per workgroup)
 __global__ __launch_bounds__(kLanes) void gen_logprobs_kernel(const GenRow* st, const GenPick pick, const float* logits, int ld, int vocab, const ScorePart* part,
@@ -438,9 +511,25 @@ __global__ __launch_bounds__(kLanes) void gen_logprobs_kernel(const GenRow* st, 
 
 }  // namespace
 
-hipError_t launch_gen_advance(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, GenPick pick, uint32_t* out, uint32_t* n_live, int n_rows, hipStream_t s) {
-    if (!st || !pos || !tok || !pick.idx || !out || !n_live || n_rows < 1 || n_rows > kGenRowsMax) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gen_advance_kernel, dim3(1), dim3(kGenRowsMax), 0, s, st, pos, tok, sel, pick, out, n_live, n_rows);
+hipError_t launch_gen_advance(GenRow* st, int* pos, uint32_t* tok, const uint32_t* sel, GenPick pick, uint32_t* out, uint32_t* n_live, int n_rows, hipStream_t s,
+                              const AutoRow* aut, uint32_t* state) {
+    if (!st || !pos || !tok || !pick.idx || !out || !n_live || n_rows < 1 || n_rows > kGenRowsMax || (aut && !state)) return hipErrorInvalidValue;
+    if (aut) hipLaunchKernelGGL(gen_advance_auto_kernel, dim3(1), dim3(kGenRowsMax), 0, s, st, pos, tok, sel, pick, out, n_live, n_rows, aut, state);
+    else hipLaunchKernelGGL(gen_advance_kernel, dim3(1), dim3(kGenRowsMax), 0, s, st, pos, tok, sel, pick, out, n_live, n_rows);
+    return hipGetLastError();
+}
+hipError_t launch_automaton_masks(const uint16_t* class_of, const uint32_t* next, int vocab, uint32_t n_states, uint32_t n_classes, uint32_t* bits, hipStream_t s) {
+    if (!class_of || !next || !bits || vocab <= 0 || n_states < 1 || n_states >= kAutoFinalBit || n_classes < 1 || n_classes > 65536u) return hipErrorInvalidValue;
+    const int words = (vocab + 31) / 32;
+    hipLaunchKernelGGL(automaton_masks_kernel, dim3((vocab + kLanes - 1) / kLanes, n_states < 4096u ? n_states : 4096u), dim3(kLanes), 0, s, class_of, next, vocab,
+                       n_states, n_classes, bits, words);
+    return hipGetLastError();
+}
+hipError_t launch_auto_mask_rows(float* logits, int ld, int cols, int rows, const AutoRow* of, const uint32_t* state, int words, hipStream_t s) {
+    if (!logits || !of || !state || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld || cols % 4 || ld % 4 || (size_t)words * 32 < (size_t)cols ||
+        (reinterpret_cast<uintptr_t>(logits) & 15) != 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(auto_rows_mask_kernel, dim3((cols / 4 + kLanes - 1) / kLanes, rows), dim3(kLanes), 0, s, logits, ld, cols, of, state, words);
     return hipGetLastError();
 }
 hipError_t launch_gen_logprobs(const GenRow* st, GenPick pick, const float* logits, int ld, int vocab, const ScorePart* part, float* lp_out, int n_rows, hipStream_t s) {

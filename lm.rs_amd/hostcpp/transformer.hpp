@@ -190,6 +190,31 @@ public:
         if (!slot.empty()) check(lmrs_batch_clear_masks(b_, static_cast<std::uint32_t>(slot.size()), slot.data()));
     }
     std::uint32_t mask_info(std::uint32_t slot) const { std::uint32_t n = 0; check(lmrs_batch_mask_info(b_, slot, &n)); return n; }   // the tokens allowed; 0: no mask
+    // Token automata: a DFA over tokens - class_of[vocab_size] below n_classes, next[n_states * n_classes] a state or STATE_DEAD, a final flag per state (empty:
+    // none) - whose tables and per-state masks stay on the device.  A slot attached to one has the mask of its current state in every call here; generate /
+    // generate_topp move the state with every token they choose and end a row that reaches a final state with FINISH_FINAL; advance moves it by hand
+    // (lmrs_batch_automaton_create / _destroy, lmrs_batch_attach_automaton, lmrs_batch_automaton_state / _advance)
+    static constexpr std::uint32_t STATE_DEAD = LMRS_STATE_DEAD, FINISH_FINAL = LMRS_FINISH_FINAL;
+    lmrs_automaton* automaton(std::uint32_t n_states, std::uint32_t n_classes, const std::vector<std::uint16_t>& class_of, const std::vector<std::uint32_t>& next,
+                              const std::vector<std::uint8_t>& final_states = {}) {
+        if (class_of.size() != vocab_size_ || next.size() != static_cast<std::size_t>(n_states) * n_classes || (!final_states.empty() && final_states.size() != n_states))
+            throw Panic("Batch::automaton: class_of holds vocab_size entries, next n_states * n_classes, final_states none or n_states");
+        lmrs_automaton* a = nullptr;
+        check(lmrs_batch_automaton_create(b_, n_states, n_classes, class_of.data(), next.data(), final_states.empty() ? nullptr : final_states.data(), &a));
+        return a;
+    }
+    void drop_automaton(lmrs_automaton* a) { check(lmrs_batch_automaton_destroy(b_, a)); }                     // refused while a slot is attached to it
+    void attach(const std::vector<std::uint32_t>& slot, const std::vector<lmrs_automaton*>& a, const std::vector<std::uint32_t>& state) {   // a[i] null: detach
+        if (a.size() != slot.size() || state.size() != slot.size()) throw Panic("Batch::attach: one automaton and one state per slot");
+        check(lmrs_batch_attach_automaton(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), a.data(), state.data()));
+    }
+    struct AutomatonState { bool attached; std::uint32_t state, n_allowed; bool is_final; };
+    AutomatonState automaton_state(std::uint32_t slot) const {
+        std::uint32_t q = 0, n = 0; int f = 0;
+        check(lmrs_batch_automaton_state(b_, slot, &q, &n, &f));
+        return AutomatonState{q != STATE_DEAD, q, n, f != 0};
+    }
+    void advance(std::uint32_t slot, const std::vector<std::uint32_t>& tokens) { check(lmrs_batch_automaton_advance(b_, slot, tokens.data(), tokens.size())); }
     // Repetition / presence / frequency penalties, state of a slot, over the token record the batch keeps on the device from the first of these calls on
     // (include/lmrs_hip.h: the rule): tokens the slot has seen anywhere are divided / multiplied by `repetition`, tokens seen at positions >= out_from lose
     // frequency * count + presence, in front of the slot's mask and of every sink  (lmrs_batch_set_penalties / _clear_penalties / _penalty_info)
