@@ -862,6 +862,37 @@ int lmrs_batch_automaton_advance(lmrs_batch* b, uint32_t slot, const uint32_t* t
 int lmrs_op_automaton_masks(int device, uint32_t vocab_size, uint32_t n_states, uint32_t n_classes, const uint16_t* class_of, const uint32_t* next,
                             uint32_t* bits_out /* n_states * W */);
 
+/* ---- candidate filters per slot: top_k and min_gap (min_p in logit space), applied on the device (extensions, no reference counterpart) ----
+ * The rule.  Output row r of slot s, logits l[0 .. vocab_size) (f32) as they stand BEHIND Gemma's soft-cap, the slot's penalties and its mask or its
+ * automaton's mask; the slot's parameters top_k (0: off) and min_gap (+inf: off):
+ *   1. the candidate order is lmrs_score_tokens_topk's: the larger value first, -0.0 equal to +0.0, equal values by ascending index, a NaN behind every
+ *      number (NaNs by ascending index) but a NaN at index 0 first of all.  m = the value of the first candidate.
+ *   2. if top_k != 0 and top_k < vocab_size: every entry that is not among the first top_k candidates becomes -inf.
+ *   3. if min_gap is finite: thr = m - min_gap, one correctly rounded f32 subtraction; every entry with !(l[t] >= thr) becomes -inf (a NaN entry too).  If m
+ *      is a NaN this step clears nothing.  Every value tied at thr stays: this step never looks at indices.
+ *   4. no kept logit is changed by any floating-point operation; entries that are -inf already stay; the first candidate is always kept.
+ * The k-th candidate is found exactly for any top_k, by integer counts: the result does not depend on scheduling.  The sinks run unchanged on the filtered
+ * row: downloaded logits show -inf exactly at the cut entries; argmax is unchanged; top-k outputs and ranks are those of the filtered row (candidates beyond
+ * the kept set are its -inf entries in index order, log-probability -inf); sampled tokens (sample_mult, top-p) and every log-probability - lmrs_batch_forward_runs'
+ * and lmrs_batch_generate's out_logprobs - are the filtered row's: the chosen token's log-probability is RENORMALISED over the kept set, as under a mask.
+ * A caller turns min_p into min_gap = -temperature * ln(min_p) (a token stays while its probability is at least min_p times the largest): the library never
+ * sees min_p, so the result is defined in logit space and is bit-exact.
+ * Filters are state of a slot: they stay until replaced or cleared; lmrs_batch_fork and lmrs_batch_release neither copy nor clear them; they touch no K/V
+ * row, no other slot and no call of the context's own (lmrs_forward*, lmrs_generate_*), and they are constant over a device-loop call.
+ * lmrs_batch_generate_greedy SKIPS the launch: no filter moves an argmax.  A batch on which no filter was ever switched on enqueues exactly the launches
+ * and copies it enqueued without these calls.
+ * lmrs_batch_set_filters: the parameters of n slots (arrays of n); (0, +inf) is the same as clearing; top_k >= vocab_size is legal and inactive.
+ * lmrs_batch_clear_filters: n == 0 (slot may be NULL): every slot.
+ * lmrs_batch_filter_info: the slot's parameters as set ((0, +inf) if never), *active = 1 while they can clear a logit.
+ * lmrs_op_filter_rows: the kernel alone on n_rows caller rows of n logits at stride ld, in place (host memory; the floats between rows come back as they
+ *   went); a row with top_k 0 or >= n and min_gap +inf is left alone.  1 <= n_rows <= 65535, 1 <= n <= ld <= 2^24.
+ * Errors, each with a message that opens with the call's name, before any state changes: a NULL batch; a NULL array with n > 0; n above lmrs_batch_width;
+ * a slot >= n_slots; the same slot twice in one call; a min_gap that is NaN or negative; a model whose classifier leaves a tail of the vocabulary unwritten. */
+int lmrs_batch_set_filters(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* top_k /* n */, const float* min_gap /* n */);
+int lmrs_batch_clear_filters(lmrs_batch* b, uint32_t n, const uint32_t* slot);
+int lmrs_batch_filter_info(const lmrs_batch* b, uint32_t slot, uint32_t* top_k, float* min_gap, int* active);
+int lmrs_op_filter_rows(int device, float* rows, size_t n_rows, size_t n, size_t ld, const uint32_t* top_k /* n_rows */, const float* min_gap /* n_rows */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ EXPORTS = [
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
     "lmrs_batch_generate",
+    "lmrs_batch_set_filters", "lmrs_batch_clear_filters", "lmrs_batch_filter_info", "lmrs_op_filter_rows",
     "lmrs_batch_generate_topp", "lmrs_sampler_candidates", "lmrs_sampler_set_candidates", "lmrs_op_topp_rows", "lmrs_bench_topp_rows",
     "lmrs_automaton_check", "lmrs_automaton_walk", "lmrs_batch_automaton_create", "lmrs_batch_automaton_destroy", "lmrs_batch_attach_automaton",
     "lmrs_batch_automaton_state", "lmrs_batch_automaton_advance", "lmrs_op_automaton_masks",
@@ -138,6 +139,10 @@ def lib():
         L.lmrs_batch_set_penalties.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.lmrs_batch_clear_penalties.argtypes = [vp, u32, vp]
         L.lmrs_batch_penalty_info.argtypes = [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_int)]
+        L.lmrs_batch_set_filters.argtypes = [vp, u32, vp, vp, vp]
+        L.lmrs_batch_clear_filters.argtypes = [vp, u32, vp]
+        L.lmrs_batch_filter_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        L.lmrs_op_filter_rows.argtypes = [C.c_int, vp, sz, sz, sz, vp, vp]
         L.lmrs_batch_destroy.argtypes = [vp]; L.lmrs_batch_destroy.restype = None
         L.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
         L.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
@@ -689,6 +694,41 @@ class Batch:
         r, p, f, o, a = C.c_float(), C.c_float(), C.c_float(), C.c_uint32(), C.c_int()
         _chk(lib().lmrs_batch_penalty_info(self._h, slot, C.byref(r), C.byref(p), C.byref(f), C.byref(o), C.byref(a)))
         return dict(repetition=r.value, presence=p.value, frequency=f.value, out_from=o.value, active=bool(a.value))
+
+    def set_filters(self, slots, top_k=0, min_gap=float("inf")) -> None:
+        """Candidate filters for `slots`; a scalar serves every slot, an array gives one value each.  While a slot has them, every output of its rows in
+        any call here but generate_greedy comes from the row with every logit outside the first top_k candidates (0: off) and every logit more than
+        min_gap below the largest (inf: off; min_p_gap turns a min_p into it) set to -inf, behind the penalties and the mask (include/lmrs_hip.h: the
+        rule).  (0, inf) is the same as clearing (lmrs_batch_set_filters)"""
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+
+        def per_slot(name, v, dtype):
+            a = np.asarray(v)
+            if a.ndim == 0:
+                a = np.full(s.size, v)
+            a = a.reshape(-1)
+            if a.size != s.size:
+                raise LmrsError(f"{name} must be a scalar or hold one value per slot ({s.size}), got {a.size}")
+            if dtype == np.uint32 and a.size and (np.any(a < 0) or np.any(a != np.floor(a)) or np.any(a > 0xFFFFFFFF)):
+                raise LmrsError(f"{name} must hold whole numbers >= 0 and below 2^32")
+            return np.ascontiguousarray(a, dtype)
+        k, g = per_slot("top_k", top_k, np.uint32), per_slot("min_gap", min_gap, np.float32)
+        _chk(lib().lmrs_batch_set_filters(self._h, s.size, *((_p(x) if s.size else None) for x in (s, k, g))))
+
+    def clear_filters(self, slots=None) -> None:
+        """The named slots lose their filters; None: every slot (lmrs_batch_clear_filters)"""
+        if slots is None:
+            _chk(lib().lmrs_batch_clear_filters(self._h, 0, None))
+            return
+        s = np.ascontiguousarray(slots, np.uint32).reshape(-1)
+        if s.size:                                              # (an empty list names no slot; n == 0 in the C call means all of them)
+            _chk(lib().lmrs_batch_clear_filters(self._h, s.size, _p(s)))
+
+    def filter_info(self, slot: int):
+        """`slot`'s filters -> dict(top_k, min_gap, active); active is False while they can clear no logit (lmrs_batch_filter_info)"""
+        k, g, a = C.c_uint32(), C.c_float(), C.c_int()
+        _chk(lib().lmrs_batch_filter_info(self._h, slot, C.byref(k), C.byref(g), C.byref(a)))
+        return dict(top_k=k.value, min_gap=g.value, active=bool(a.value))
 
     def set_history(self, slot: int, tokens=(), start_pos: int = 0) -> None:
         """The token record of `slot` from start_pos on = tokens (TOKEN_NONE: unknown) - what the caller knows of positions written before the record
@@ -1313,6 +1353,26 @@ class Sampler:
             lib().lmrs_sampler_destroy(self._h); self._h = None
 
     __del__ = close
+
+
+def min_p_gap(min_p: float, temperature: float = 1.0) -> np.float32:
+    """The min_gap of Batch.set_filters that keeps the tokens whose probability at `temperature` is at least min_p times the largest:
+    -temperature * ln(min_p), formed in float64 and rounded once to float32.  min_p <= 0: inf (off); temperature 0 (argmax rows): 0"""
+    if not (min_p <= 1.0) or not (temperature >= 0.0):
+        raise LmrsError("min_p must lie in [0, 1] and temperature must not be negative")
+    if min_p <= 0.0:
+        return np.float32(np.inf)
+    return np.float32(-np.float64(temperature) * np.log(np.float64(min_p)) + 0.0)
+
+
+def filter_rows(rows, top_k=0, min_gap=float("inf"), n=None, device: int = 0) -> np.ndarray:
+    """The filter kernel alone over rows (float32 [n_rows, ld]; n: the logits a row holds, default ld): a copy with top_k / min_gap (a scalar, or one value
+    per row; (0, inf): the row is left alone) applied by the rule of include/lmrs_hip.h; columns from n on come back as they went (lmrs_op_filter_rows)"""
+    x = np.array(rows, np.float32, ndmin=2, order="C")
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, np.uint32), (x.shape[0],)))
+    g = np.ascontiguousarray(np.broadcast_to(np.asarray(min_gap, np.float32), (x.shape[0],)))
+    _chk(lib().lmrs_op_filter_rows(device, _p(x), x.shape[0], x.shape[1] if n is None else n, x.shape[1], _p(k), _p(g)))
+    return x
 
 
 def automaton_masks(ta: TokenAutomaton, device: int = 0) -> np.ndarray:

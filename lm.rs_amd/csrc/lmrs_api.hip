@@ -203,8 +203,11 @@ struct AutoView { const AutoRow* of = nullptr; const AutoRow* h_of = nullptr; co
 // penalties (penalties.hist != null): some output row of the pass belongs to a slot with penalties (lmrs_batch_set_penalties) - of[r] carries slot, parameters and the
 // table row whose position is row r's (pos: that column of the pass's device table, read on the device - right inside lmrs_batch_generate_greedy's loops); h_of is
 // its pinned source, as with the masks; max_n = the deepest row's position + 1 at this pass (the keys a workgroup sorts)
+// filters (filters.of != null): some output row of the pass belongs to a slot with candidate filters (lmrs_batch_set_filters) - of[r] carries the slot and its
+// top_k / min_gap in the order the classifier sees the rows, slot -1 for none; h_of is its pinned source, as with the masks
+struct FilterView { const FilterRow* of = nullptr; const FilterRow* h_of = nullptr; };
 struct PenaltyView { const uint32_t* hist = nullptr; int seq_len = 0; const int* pos = nullptr; const PenaltyRow* of = nullptr; const PenaltyRow* h_of = nullptr; int max_n = 0; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1809,6 +1812,9 @@ static int classify_rows(lmrs_ctx* c, PassForm form, const RowSink& to, float* x
         // a batch's token automata (PassForm::autos): the same stores under the mask of the state each row's slot stands in, found on the device
         if (form.autos.of && std::any_of(form.autos.h_of + i0 + j0, form.autos.h_of + i0 + j0 + mj, [](const AutoRow& r) { return r.slot >= 0; }))
             HIP_OK(launch_auto_mask_rows(c->sc_logits, o, o, mj, form.autos.of + i0 + j0, form.autos.state, form.autos.words, c->stream));
+        // a batch's candidate filters (PassForm::filters), behind everything that changes or clears a logit: one launch a slab, and only for a slab that has a filtered row
+        if (form.filters.of && std::any_of(form.filters.h_of + i0 + j0, form.filters.h_of + i0 + j0 + mj, [](const FilterRow& r) { return r.slot >= 0; }))
+            HIP_OK(launch_filter_rows(c->sc_logits, o, o, mj, form.filters.of + i0 + j0, c->stream));
         if (to.out_logits && copy_out_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
         if ((!to.out_logits || to.reduce_too) && reduce_rows(c, to, c->sc_logits, o, mj, i0 + j0)) return -1;
     }
@@ -2098,6 +2104,14 @@ struct lmrs_batch {
     struct Penalty { float repetition = 1.0f, presence = 0.0f, frequency = 0.0f; uint32_t out_from = 0; };
     Penalty pen[kWideBatchMax]; bool pen_on[kWideBatchMax] = {}; uint32_t n_pen = 0;
     DevBuf<PenaltyRow> pen_of; PinBuf<PenaltyRow> h_pen_of; bool pen_live = false;
+    // candidate filters (lmrs_batch_set_filters; flt_of made at the first call that switches one on): flt[s] slot s's parameters as set, flt_on[s] - they can clear
+    // a logit (0 < top_k < vocab_size, or a finite min_gap), n_flt the slots where they can.  flt_of / h_flt_of: the per-call column of PassForm::filters, written
+    // with the tables; flt_live: this call uploaded it - some output row of the call is filtered
+    struct Filter { uint32_t top_k = 0; float min_gap = INFINITY; };
+    Filter flt[kWideBatchMax]; bool flt_on[kWideBatchMax] = {}; uint32_t n_flt = 0;
+    DevBuf<FilterRow> flt_of; PinBuf<FilterRow> h_flt_of; bool flt_live = false;
+    FilterRow filter_row_of(uint32_t slot) const { return flt_on[slot] ? FilterRow{(int)slot, flt[slot].top_k, flt[slot].min_gap} : FilterRow{-1, 0u, INFINITY}; }
+    FilterView filter_view() const { return flt_live ? FilterView{flt_of, h_flt_of} : FilterView{}; }
     // lmrs_batch_generate (made at its first call; gen_st non-null: the set stands): the rows' state blocks beside the pass's table and their pinned mirror, the
     // live-row count and its pinned copy; `out` / `h_out` take the tokens [n][M].  gen_lp / h_gen_lp: the log-probabilities' block of the same layout (made at
     // the first call that asks for them, n * M words, made anew when a call needs more).  gen: the call's own sampling set (whole sixteens, as rs); gen_logits: the copy of the logits block the samplers
@@ -2496,6 +2510,60 @@ extern "C" int lmrs_batch_penalty_info(const lmrs_batch* b, uint32_t slot, float
     *repetition = p.repetition; *presence = p.presence; *frequency = p.frequency; *out_from = p.out_from; *active = b->pen_on[slot] ? 1 : 0;
     return 0;
 }
+// ------------------------------------------------------------------ candidate filters: top_k and min_gap, state of a slot (extensions, no reference counterpart)
+// While slot s has a filter, every output row of s in any batch call but lmrs_batch_generate_greedy is the row with filter_rows_kernel's -inf stores
+// (lmrs_score.h: the rule), behind the soft-cap, the penalties and the masks and in front of every sink.  A batch on which none was ever switched on has no
+// column and enqueues exactly what it enqueued before: every hook tests b->n_flt.
+static bool filter_active(const lmrs_batch* b, uint32_t top_k, float min_gap) { return (top_k != 0u && top_k < b->c->args.vocab_size) || min_gap < INFINITY; }
+extern "C" int lmrs_batch_set_filters(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* top_k, const float* min_gap) {
+    const std::string what = "lmrs_batch_set_filters: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && (!slot || !top_k || !min_gap)) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot, "filter ")) return -1;
+    lmrs_ctx* c = b->c;
+    if (cls_rows(c) != (int)c->args.vocab_size) return fail(what + "the classifier leaves the last vocab_size % 4 logits unwritten: no filters for this vocabulary");
+    bool any = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string at = what + "filter " + std::to_string(i) + ": slot " + std::to_string(slot[i]) + ": ";
+        if (min_gap[i] != min_gap[i]) return fail(at + "min_gap is NaN");
+        if (min_gap[i] < 0.0f) return fail(at + "min_gap = " + std::to_string(min_gap[i]) + " is negative");
+        any = any || filter_active(b, top_k[i], min_gap[i]);
+    }
+    if (any && !b->flt_of) {
+        HIP_OK(hipSetDevice(c->device));
+        if (!alloc_all({{b->flt_of, kRunRowsMax}, {b->h_flt_of, kRunRowsMax}})) {
+            (void)hipGetLastError();
+            return fail(what + "the filters' column: out of memory");
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t s = slot[i];
+        const bool on = filter_active(b, top_k[i], min_gap[i]);            // (0, +inf) and top_k >= vocab_size clear no logit: the same as clearing
+        b->flt[s] = lmrs_batch::Filter{top_k[i], min_gap[i]};
+        if (on && !b->flt_on[s]) ++b->n_flt;
+        if (!on && b->flt_on[s]) --b->n_flt;
+        b->flt_on[s] = on;
+    }
+    return 0;
+}
+extern "C" int lmrs_batch_clear_filters(lmrs_batch* b, uint32_t n, const uint32_t* slot) {
+    const std::string what = "lmrs_batch_clear_filters: ";
+    if (!b) return fail(what + "NULL argument (the batch)");
+    if (n && !slot) return fail(what + "NULL array");
+    if (mask_slots_check(b, what, n, slot, "filter ")) return -1;
+    for (uint32_t s = 0; s < b->n_slots && !n; ++s) { b->flt[s] = lmrs_batch::Filter{}; b->flt_on[s] = false; }
+    if (!n) b->n_flt = 0;
+    for (uint32_t i = 0; i < n; ++i) { if (b->flt_on[slot[i]]) --b->n_flt; b->flt[slot[i]] = lmrs_batch::Filter{}; b->flt_on[slot[i]] = false; }
+    return 0;
+}
+extern "C" int lmrs_batch_filter_info(const lmrs_batch* b, uint32_t slot, uint32_t* top_k, float* min_gap, int* active) {
+    const std::string what = "lmrs_batch_filter_info: ";
+    if (!b || !top_k || !min_gap || !active) return fail(what + "NULL argument");
+    if (slot >= b->n_slots) return fail(what + "slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
+    *top_k = b->flt[slot].top_k; *min_gap = b->flt[slot].min_gap; *active = b->flt_on[slot] ? 1 : 0;
+    return 0;
+}
+
 // A fork's record: dst's first n_pos positions are src's; the context's sequence (LMRS_BATCH_CTX) has no record - unknown tokens
 static int history_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_slot, uint32_t n_pos) {
     if (!b->hist) return 0;
@@ -2691,11 +2759,12 @@ static void runs_table(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot, con
             if (b->n_masked) b->h_mask_of[o] = b->mask_row_of(slot[i]);     // (the classifier sees the outputs in this order)
             if (b->n_aut) b->h_aut_rows[o] = b->auto_row_of(slot[i]);
             if (b->n_pen) b->h_pen_of[o] = b->penalty_row_of(slot[i], at[j + u]);
+            if (b->n_flt) b->h_flt_of[o] = b->filter_row_of(slot[i]);
             h->sel[o++] = (uint32_t)at[j + u];
         }
         j += len;
     }
-    b->mask_live = false; b->pen_live = false; b->aut_live = false;
+    b->mask_live = false; b->pen_live = false; b->aut_live = false; b->flt_live = false;
     *rows_out = R; *outs = o;
 }
 // One pass over the device's long table as it stands: R rows through the layers, then the O rows of sel through the final norm and the classifier to
@@ -2740,7 +2809,7 @@ static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink t
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
-    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view(); cls.autos = b->auto_view(); cls.penalties = b->penalty_view(form.runs.pos, form.max_T);
+    PassForm cls; cls.skinny = O <= kStreamPassMax; cls.masks = b->mask_view(); cls.autos = b->auto_view(); cls.penalties = b->penalty_view(form.runs.pos, form.max_T); cls.filters = b->filter_view();
     to.targets = false;
     return classify_rows(c, cls, to, b->runs_x, 0, (int)O);
 }
@@ -2772,8 +2841,9 @@ static int batch_rows(lmrs_batch* b, const char* what, uint32_t cap, uint32_t n,
         if (b->n_aut) b->h_aut_rows[r] = b->auto_row_of(slot[i]);
         if (b->hist) b->h_hist_slot[r] = (int)slot[i];
         if (b->n_pen) b->h_pen_of[r] = b->penalty_row_of(slot[i], (int)r);
+        if (b->n_flt) b->h_flt_of[r] = b->filter_row_of(slot[i]);
     }
-    b->mask_live = false; b->pen_live = false; b->aut_live = false;
+    b->mask_live = false; b->pen_live = false; b->aut_live = false; b->flt_live = false;
     return 0;
 }
 // The record's columns of a call beside its table (a batch without the record enqueues nothing here): the slot of every one of the table's R rows, and - only
@@ -2788,7 +2858,12 @@ static int record_enqueue(lmrs_batch* b, size_t R, size_t O) {
 }
 // The mask column of a call with n output rows, beside its table: uploaded - and the pass's forms carry it (lmrs_batch::mask_view) - only when one of the
 // rows is masked; a batch without masks enqueues nothing here
-static int masks_enqueue(lmrs_batch* b, size_t n) {
+// filters: the filters' column too, in the same way (lmrs_batch_generate_greedy passes false: no filter moves an argmax, so its passes skip the launch)
+static int masks_enqueue(lmrs_batch* b, size_t n, bool filters = true) {
+    if (filters && b->n_flt && std::any_of(b->h_flt_of.get(), b->h_flt_of + n, [](const FilterRow& r) { return r.slot >= 0; })) {
+        HIP_OK(hipMemcpyAsync(b->flt_of, b->h_flt_of, n * sizeof(FilterRow), hipMemcpyHostToDevice, b->c->stream));
+        b->flt_live = true;
+    }
     // the automata's column in the same way, and in front of it the state words where the host has moved one since they last went up
     if (b->n_aut && std::any_of(b->h_aut_rows.get(), b->h_aut_rows + n, [](const AutoRow& r) { return r.slot >= 0; })) {
         if (b->aut_dirty) {
@@ -2809,7 +2884,7 @@ static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logit
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
     if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); }
-    form.masks = b->mask_view(); form.autos = b->auto_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T);
+    form.masks = b->mask_view(); form.autos = b->auto_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T); form.filters = b->filter_view();
     if (record_rows(b, b->tab->pos, b->tab->tok, n)) return -1;
     RowSink to{0, n, out_logits, 0}; to.targets = false;
     return run_tokens(c, to, form, /*batched=*/true);
@@ -2869,7 +2944,7 @@ extern "C" int lmrs_batch_generate_greedy(lmrs_batch* b, uint32_t n, const uint3
     auto enqueue = [&]() -> int {
         if (wide) HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
         else HIP_OK(hipMemcpyAsync(b->tab, b->h_tab, sizeof(RowTable), hipMemcpyHostToDevice, c->stream));
-        if (masks_enqueue(b, n) || record_enqueue(b, n, n) || batch_state(c)) return -1;       // (the column once: the rows keep their order over the n_new steps)
+        if (masks_enqueue(b, n, /*filters=*/false) || record_enqueue(b, n, n) || batch_state(c)) return -1;       // (the column once: the rows keep their order over the n_new steps)
         HIP_OK(hipEventRecord(c->ev0, c->stream));
         for (uint32_t j = 0; j < n_new && wide; ++j) {
             if (runs_pass(b, n, n, j, RowSink{0, n, nullptr, 0})) return -1;
@@ -3133,7 +3208,7 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
         if (block) {                                     // block attention: the table's rows in POSITION order (row r = position p0 + r), no outputs
             RunTable* h = b->h_runs;
             for (uint32_t r = 0; r < m; ++r) { h->off[r] = b->off_of(slot); h->pos[r] = (int)(p0 + r); h->tok[r] = embeddings ? kRowFromStage | r : tokens[i0 + r]; if (b->hist) b->h_hist_slot[r] = (int)slot; }
-            b->mask_live = false; b->pen_live = false; b->aut_live = false;
+            b->mask_live = false; b->pen_live = false; b->aut_live = false; b->flt_live = false;
         } else runs_table(b, 1, &slot, &p0, &m, &n_out, RunRows{&kind, tokens ? tokens + i0 : nullptr, embeddings}, &R, &O);
         auto enqueue = [&]() -> int {
             if (embeddings) HIP_OK(hipMemcpyAsync(b->embed_stage, embeddings + i0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, c->stream));
@@ -4080,6 +4155,32 @@ extern "C" int lmrs_op_automaton_masks(int device, uint32_t vocab_size, uint32_t
     HIP_OK(launch_automaton_masks(static_cast<const uint16_t*>(dc), static_cast<const uint32_t*>(dn), (int)V, n_states, n_classes, static_cast<uint32_t*>(db), nullptr));
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(bits_out, db, (size_t)n_states * W * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_filter_rows on caller-supplied rows, in place (unit parity against the rule in numpy): row r is rows[r * ld .. r * ld + n), the floats between rows
+// travel with them and come back as they went; a row with (0 or >= n, +inf) is handed to the launch as an unfiltered one (slot -1)
+extern "C" int lmrs_op_filter_rows(int device, float* rows, size_t n_rows, size_t n, size_t ld, const uint32_t* top_k, const float* min_gap) {
+    const std::string what = "lmrs_op_filter_rows: ";
+    if (!rows || !top_k || !min_gap) return fail(what + "NULL argument");
+    if (n_rows < 1 || n_rows > 65535) return fail(what + "n_rows = " + std::to_string(n_rows) + " is outside 1 .. 65535");
+    if (n < 1 || n > ((size_t)1 << 24) || ld < n || ld > ((size_t)1 << 24)) return fail(what + "need 1 <= n <= ld <= 2^24");
+    std::vector<FilterRow> of(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) {
+        if (min_gap[r] != min_gap[r] || min_gap[r] < 0.0f) return fail(what + "row " + std::to_string(r) + ": min_gap is NaN or negative");
+        const bool on = (top_k[r] != 0u && top_k[r] < n) || min_gap[r] < INFINITY;
+        of[r] = FilterRow{on ? (int)r : -1, top_k[r], min_gap[r]};
+    }
+    if (op_begin(device)) return -1;
+    Scratch S;
+    const size_t bytes = n_rows * ld * 4;
+    void *dl = S.get(bytes), *dof = S.get(n_rows * sizeof(FilterRow));
+    if (!dl || !dof) return fail(what + "hipMalloc failed");
+    HIP_OK(hipMemcpy(dl, rows, bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dof, of.data(), n_rows * sizeof(FilterRow), hipMemcpyHostToDevice));
+    HIP_OK(launch_filter_rows(static_cast<float*>(dl), (int)ld, (int)n, (int)n_rows, static_cast<const FilterRow*>(dof), nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(rows, dl, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

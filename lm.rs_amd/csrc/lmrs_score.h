@@ -81,6 +81,17 @@ struct PenaltyRow { int slot; int tab_row; float repetition, presence, frequency
 // counts are integers: the result does not depend on scheduling.  max_n >= every row's p + 1, at most min(seq_len, kPenaltyKeysMax): sizes the launch's LDS.
 hipError_t launch_penalty_rows(float* logits, int ld, int cols, int rows, const uint32_t* hist, int seq_len, const int* pos, const PenaltyRow* of, int max_n, hipStream_t s);
 
+// ---- a batch slot's candidate filters (lmrs_batch_set_filters): top_k and min_gap over a row, behind the masks and in front of every sink
+// One output row's filter, in the order the classifier sees the rows: slot < 0 - none; top_k 0 or >= cols - off; min_gap +inf - off
+struct FilterRow { int slot; uint32_t top_k; float min_gap; };
+// Row r < rows of the block with of[r].slot >= 0, over its first `cols` entries in the candidate order above (launch_topk_rows: the 64-bit keys of topk_key),
+// m = the value of the first candidate:
+//   1 <= top_k < cols: every entry that is not among the first top_k candidates becomes -inf (the k-th key is found exactly, ties at its value by index);
+//   min_gap finite and m a number: thr = m - min_gap, one correctly rounded f32 subtraction; every entry with !(l >= thr) becomes -inf.
+// Only -inf is stored, and never over a kept entry; the first candidate is always kept.  The counts are integer sums in LDS, nothing global is written but
+// the row, and what is written depends on key values alone: a row gives the same bits in any launch.  One workgroup a row; rows <= 65535, cols <= ld.
+hipError_t launch_filter_rows(float* logits, int ld, int cols, int rows, const FilterRow* of, hipStream_t s);
+
 // ---- the step boundary of lmrs_batch_generate's device loop: one block per output row of the pass's table, in the order the classifier sees the rows
 constexpr int kGenStopMax = 16;                             // = LMRS_STOP_MAX
 constexpr int kGenRowsMax = 64;                             // one lane per row: a wide batch's rows

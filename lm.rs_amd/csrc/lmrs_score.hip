@@ -23,6 +23,9 @@
 // record_rows_kernel / penalty_rows_kernel: a batch's token record per slot and the repetition / presence / frequency penalties over it
 // (lmrs_batch_set_penalties), between the soft-cap and the mask: one workgroup a penalised row sorts the row's record in LDS and changes one logit per
 // distinct token.
+//
+// filter_rows_kernel: a batch slot's candidate filters (lmrs_batch_set_filters) - top_k by an exact radix select over the row's 64-bit keys, min_gap below the
+// row's first candidate - behind the masks and in front of every sink: one workgroup a filtered row, -inf stores only.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -435,6 +438,150 @@ __global__ __launch_bounds__(kLanes) void penalty_rows_kernel(float* logits, int
     }
 }
 
+// ------------------------------------------------------------------ a slot's candidate filters over its rows (launch_filter_rows)
+// One workgroup of 1024 lanes a filtered row (sixteen waves keep a CU's loads in flight; a row of 128 256 logits is 32 trips of float4 a lane), the row read
+// from L2 behind its first pass.  top_k: block_kth_key's radix select, eight bits a round from the top of topk_key's 64-bit keys, but over the row itself -
+// the keys are formed again from the logits at every round, so there is no vocabulary-sized scratch and no limit on k; the rounds stop at the first bin that
+// is wanted whole (three or four rounds on ordinary logits: the value's 32 bits, rarely a tie at the threshold), and a round over index bits that are the
+// same in every key of the row (~i above the row's width) is not run.  Rows of equal values take every round - the worst case - so a wave first adds the
+// bins most of its lanes share by one atomic each (two peels), then the rest lane by lane: LDS atomics on one address serialise.  min_gap: the largest value
+// word, taken along in the first round (a pass of its own for a row without top_k), then m - min_gap.  Then one pass of stores, -inf only.
+constexpr int kFilterLanes = 1024;
+struct FilterLds { unsigned hist[256]; unsigned wtot[4]; unsigned pick[3]; unsigned red[kFilterLanes / 64]; };
+
+// every entry of the row once, in trips that all lanes of the workgroup make together (the ballots of wave_bin_add see whole waves): f(value, index, valid).
+// vec: the row starts 16-byte aligned - float4 loads over its whole fours
+template <class F>
+__device__ __forceinline__ void filter_each(const float* row, int n, bool vec, F&& f) {
+    const int tid = threadIdx.x;
+    int done = 0;
+    if (vec) {
+        const int n4 = n >> 2;
+        for (int base = 0; base < n4; base += kFilterLanes) {
+            const int j = base + tid;
+            const bool ok = j < n4;
+            const float4 v = ok ? reinterpret_cast<const float4*>(row)[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            f(v.x, 4 * j, ok); f(v.y, 4 * j + 1, ok); f(v.z, 4 * j + 2, ok); f(v.w, 4 * j + 3, ok);
+        }
+        done = n4 * 4;
+    }
+    for (int base = done; base < n; base += kFilterLanes) {
+        const int i = base + tid;
+        const bool ok = i < n;
+        f(ok ? row[i] : 0.0f, i, ok);
+    }
+}
+
+// hist[bin] += 1 for every lane of the wave that wants it (bin < 256 in every lane): the first wanting lane's bin by one atomic for all lanes that share it,
+// twice, then an atomic a lane - integer sums, the same totals in any order
+__device__ __forceinline__ void wave_bin_add(unsigned* hist, unsigned bin, bool want) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(want);
+    for (int it = 0; it < 2 && todo; ++it) {
+        const int lead = __ffsll((unsigned long long)todo) - 1;
+        const unsigned lb = __shfl(bin, lead);
+        const unsigned long long same = __ballot(want && bin == lb);
+        if (lane == lead) atomicAdd(&hist[lb], (unsigned)__popcll(same));
+        if (bin == lb) want = false;
+        todo &= ~same;
+    }
+    if (want) atomicAdd(&hist[bin], 1u);
+}
+
+__global__ __launch_bounds__(kFilterLanes) void filter_rows_kernel(float* logits, int ld, int cols, const FilterRow* rows) {
+    __shared__ FilterLds L;
+    const FilterRow fr = rows[blockIdx.x];
+    if (fr.slot < 0) return;
+    const bool tk = fr.top_k != 0u && fr.top_k < (unsigned)cols;
+    const bool gap = fr.min_gap < INFINITY;                                 // (a NaN: off)
+    if (!tk && !gap) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* row = logits + (size_t)blockIdx.x * ld;
+    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    unsigned mx = 0;                                                        // the largest value word the lane has seen (never 0 over a whole row)
+    unsigned long long kth = 0;                                             // key >= kth: among the first top_k candidates
+    if (tk) {
+        unsigned long long pfx = 0, known = 0;
+        unsigned r = fr.top_k;                                              // 1 <= r <= the keys that share the bits decided so far, throughout
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            if (shift < 32 && ((unsigned)(cols - 1) >> shift) == 0u) {      // ~i has this byte all ones in every key of the row
+                pfx |= 0xFFull << shift; known |= 0xFFull << shift;
+                continue;
+            }
+            if (tid < 256) L.hist[tid] = 0;
+            __syncthreads();
+            filter_each(row, cols, vec, [&](float v, int i, bool ok) {
+                const unsigned long long key = topk_key(v, i);
+                if (shift == 56 && ok) mx = max(mx, (unsigned)(key >> 32));
+                wave_bin_add(L.hist, (unsigned)(key >> shift) & 255u, ok && (key & known) == pfx);
+            });
+            __syncthreads();
+            // lane = bin (the first four waves): the keys in higher bins, by a suffix sum over the wave and the waves' totals - block_kth_key's
+            unsigned h = 0, x = 0;
+            if (tid < 256) {
+                h = L.hist[tid]; x = h;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_down(x, off); if (lane + off < 64) x += y; }
+                if (lane == 0) L.wtot[wave] = x;
+            }
+            __syncthreads();
+            if (tid < 256) {
+                unsigned above = x - h;
+                for (int w = wave + 1; w < 4; ++w) above += L.wtot[w];
+                if (above < r && r <= above + h) { L.pick[0] = (unsigned)tid; L.pick[1] = r - above; L.pick[2] = h; }   // (one bin)
+            }
+            __syncthreads();
+            pfx |= (unsigned long long)L.pick[0] << shift; known |= 0xFFull << shift;
+            r = L.pick[1];
+            if (r == L.pick[2]) break;                                      // the whole bin is wanted (at shift 0: the one key)
+        }
+        kth = pfx;
+    }
+    bool use_gap = false;
+    float thr = 0.0f;
+    if (gap) {
+        if (!tk) filter_each(row, cols, vec, [&](float v, int i, bool ok) { if (ok) mx = max(mx, (unsigned)(topk_key(v, i) >> 32)); });
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor(mx, off));
+        if (lane == 0) L.red[wave] = mx;
+        __syncthreads();
+        mx = L.red[0];
+#pragma unroll
+        for (int w = 1; w < kFilterLanes / 64; ++w) mx = max(mx, L.red[w]);
+        // the first candidate's value from its word; all ones: a NaN at index 0 - nothing is cleared by the gap
+        use_gap = mx != 0xFFFFFFFFu && mx != 0u;
+        const unsigned mb = (mx & 0x80000000u) ? (mx & 0x7FFFFFFFu) : ~mx;
+        thr = __fsub_rn(__uint_as_float(mb), fr.min_gap);
+    }
+    auto cut = [&](float v, int i) { return (tk && topk_key(v, i) < kth) || (use_gap && !(v >= thr)); };
+    const unsigned kNinfBits = 0xFF800000u;
+    const float ninf = -INFINITY;
+    int done = 0;
+    if (vec) {
+        const int n4 = cols >> 2;
+        for (int j = tid; j < n4; j += kFilterLanes) {
+            float* p = row + 4 * j;
+            const float4 v = *reinterpret_cast<const float4*>(p);
+            const bool c0 = cut(v.x, 4 * j), c1 = cut(v.y, 4 * j + 1), c2 = cut(v.z, 4 * j + 2), c3 = cut(v.w, 4 * j + 3);
+            const bool w0 = c0 && __float_as_uint(v.x) != kNinfBits, w1 = c1 && __float_as_uint(v.y) != kNinfBits,
+                       w2 = c2 && __float_as_uint(v.z) != kNinfBits, w3 = c3 && __float_as_uint(v.w) != kNinfBits;
+            if (c0 && c1 && c2 && c3) {
+                if (w0 || w1 || w2 || w3) *reinterpret_cast<float4*>(p) = make_float4(ninf, ninf, ninf, ninf);
+                continue;
+            }
+            if (w0) p[0] = ninf;
+            if (w1) p[1] = ninf;
+            if (w2) p[2] = ninf;
+            if (w3) p[3] = ninf;
+        }
+        done = n4 * 4;
+    }
+    for (int i = done + tid; i < cols; i += kFilterLanes) {
+        const float v = row[i];
+        if (cut(v, i) && __float_as_uint(v) != kNinfBits) row[i] = ninf;
+    }
+}
+
 // ------------------------------------------------------------------ the step boundary of lmrs_batch_generate's device loop (launch_gen_advance / launch_gen_logprobs)
 __device__ __forceinline__ uint32_t gen_picked(const GenRow& g, const GenPick& pick, int o) {
     return g.from_samp ? (uint32_t)pick.samp[(size_t)o * pick.samp_ld] : pick.idx[o];
@@ -550,6 +697,12 @@ hipError_t launch_penalty_rows(float* logits, int ld, int cols, int rows, const 
     int cap = 2;
     while (cap < max_n) cap <<= 1;
     hipLaunchKernelGGL(penalty_rows_kernel, dim3(rows), dim3(kLanes), (size_t)cap * 4, s, logits, ld, cols, hist, seq_len, pos, of, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_rows(float* logits, int ld, int cols, int rows, const FilterRow* of, hipStream_t s) {
+    if (!logits || !of || rows <= 0 || rows > 65535 || cols <= 0 || cols > ld || cols > (1 << 30) || (reinterpret_cast<uintptr_t>(logits) & 3) != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_rows_kernel, dim3(rows), dim3(kFilterLanes), 0, s, logits, ld, cols, of);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 // behaviour (reference src/transformer.rs:127-131 struct, :134 new, :316 forward, :659 get_embeddings,
 // :672 fill_kv_cache; errors there are panics -> here exceptions).  Header-only; link liblmrs_hip.so.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -244,6 +245,33 @@ public:
         std::vector<std::uint32_t> out(n);
         check(lmrs_batch_history(b_, slot, start_pos, n, n ? out.data() : nullptr));
         return out;
+    }
+    // Candidate filters, state of a slot (include/lmrs_hip.h: the rule): every logit outside the row's first top_k candidates (0: off) and every logit more
+    // than min_gap below the largest (+inf: off; min_p_gap turns a min_p into it) reads -inf, behind the penalties and the mask and in front of every sink
+    // but generate_greedy's  (lmrs_batch_set_filters / _clear_filters / _filter_info; filter_rows: the kernel alone, lmrs_op_filter_rows)
+    struct Filter { std::uint32_t top_k = 0; float min_gap = HUGE_VALF; bool active = false; };
+    static float min_p_gap(double min_p, double temperature) { return min_p > 0.0 ? static_cast<float>(-temperature * std::log(min_p) + 0.0) : HUGE_VALF; }
+    void set_filters(const std::vector<std::uint32_t>& slot, const std::vector<Filter>& f) {
+        if (f.size() != slot.size()) throw Panic("Batch::set_filters: one Filter per slot");
+        std::vector<std::uint32_t> k; std::vector<float> gap;
+        for (const Filter& x : f) { k.push_back(x.top_k); gap.push_back(x.min_gap); }
+        check(lmrs_batch_set_filters(b_, static_cast<std::uint32_t>(slot.size()), slot.data(), k.data(), gap.data()));
+    }
+    void clear_filters() { check(lmrs_batch_clear_filters(b_, 0, nullptr)); }                                  // every slot
+    void clear_filters(const std::vector<std::uint32_t>& slot) {
+        if (!slot.empty()) check(lmrs_batch_clear_filters(b_, static_cast<std::uint32_t>(slot.size()), slot.data()));
+    }
+    Filter filter_info(std::uint32_t slot) const {
+        Filter f; int active = 0;
+        check(lmrs_batch_filter_info(b_, slot, &f.top_k, &f.min_gap, &active));
+        f.active = active != 0;
+        return f;
+    }
+    static void filter_rows(int device, float* rows, std::size_t n_rows, std::size_t n, std::size_t ld, const std::vector<Filter>& f) {
+        if (f.size() != n_rows) throw Panic("Batch::filter_rows: one Filter per row");
+        std::vector<std::uint32_t> k; std::vector<float> gap;
+        for (const Filter& x : f) { k.push_back(x.top_k); gap.push_back(x.min_gap); }
+        check(lmrs_op_filter_rows(device, rows, n_rows, n, ld, k.data(), gap.data()));
     }
     // the most rows (forward, generate_greedy) and runs (forward_runs) a call takes: 16, or 64 for a wide batch  (lmrs_batch_width)
     std::uint32_t width() const { std::uint32_t w = 0; check(lmrs_batch_width(b_, &w)); return w; }

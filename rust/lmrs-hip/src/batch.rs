@@ -52,6 +52,34 @@ extern "C" {
                                     n_stop: *const u32, stop_tokens: *const u32, samplers: *const *mut LmrsSampler, check_every: u32,
                                     out_tokens: *mut u32, out_logprobs: *mut f32, n_out: *mut u32, finish: *mut u32, stats2: *mut u64,
                                     seconds: *mut f64) -> c_int;
+    // candidate filters per slot, and the kernel alone on caller rows: declared here as the penalty calls are (tests/test_batch_filter_host.py compares them
+    // with the header)
+    pub fn lmrs_batch_set_filters(b: *mut LmrsBatch, n: u32, slot: *const u32, top_k: *const u32, min_gap: *const f32) -> c_int;
+    pub fn lmrs_batch_clear_filters(b: *mut LmrsBatch, n: u32, slot: *const u32) -> c_int;
+    pub fn lmrs_batch_filter_info(b: *const LmrsBatch, slot: u32, top_k: *mut u32, min_gap: *mut f32, active: *mut c_int) -> c_int;
+    pub fn lmrs_op_filter_rows(device: c_int, rows: *mut f32, n_rows: usize, n: usize, ld: usize, top_k: *const u32, min_gap: *const f32) -> c_int;
+}
+
+/// A slot's candidate filters (`Batch::set_filters`): every logit outside the row's first `top_k` candidates (0: off) and every logit more than `min_gap`
+/// below the largest (`f32::INFINITY`: off) reads `-inf` in front of every sink (include/lmrs_hip.h: the rule).
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct Filter {
+    pub top_k: u32,
+    pub min_gap: f32,
+}
+
+/// The `min_gap` that keeps the tokens whose probability at `temperature` is at least `min_p` times the largest: `-temperature * ln(min_p)`, formed in
+/// f64 and rounded once.
+pub fn min_p_gap(min_p: f64, temperature: f64) -> f32 {
+    if min_p > 0.0 { (-temperature * min_p.ln() + 0.0) as f32 } else { f32::INFINITY }
+}
+
+/// The filter kernel alone over `n_rows` rows of `n` logits at stride `ld`, in place (`lmrs_op_filter_rows`).
+pub fn filter_rows(device: i32, rows: &mut [f32], n_rows: usize, n: usize, ld: usize, filters: &[Filter]) {
+    assert!(filters.len() == n_rows && rows.len() >= n_rows * ld, "one Filter per row, n_rows * ld floats");
+    let k: Vec<u32> = filters.iter().map(|f| f.top_k).collect();
+    let gap: Vec<f32> = filters.iter().map(|f| f.min_gap).collect();
+    check(unsafe { lmrs_op_filter_rows(device as c_int, rows.as_mut_ptr(), n_rows, n, ld, k.as_ptr(), gap.as_ptr()) });
 }
 
 /// The most stop tokens a row of `Batch::generate` takes (`LMRS_STOP_MAX`).
@@ -205,6 +233,26 @@ impl<'t, 'a> Batch<'t, 'a> {
         let (mut p, mut active) = (Penalty { repetition: 1.0, presence: 0.0, frequency: 0.0, out_from: 0 }, 0 as c_int);
         check(unsafe { lmrs_batch_penalty_info(self.b, slot, &mut p.repetition, &mut p.presence, &mut p.frequency, &mut p.out_from, &mut active) });
         (p, active != 0)
+    }
+
+    /// Filters for `slot[i]`, state of the slots until replaced or cleared; `(0, INFINITY)` is the same as clearing.
+    pub fn set_filters(&mut self, slot: &[u32], filters: &[Filter]) {
+        assert!(slot.len() == filters.len(), "one Filter per slot");
+        let k: Vec<u32> = filters.iter().map(|f| f.top_k).collect();
+        let gap: Vec<f32> = filters.iter().map(|f| f.min_gap).collect();
+        check(unsafe { lmrs_batch_set_filters(self.b, slot.len() as u32, slot.as_ptr(), k.as_ptr(), gap.as_ptr()) });
+    }
+
+    /// The named slots lose their filters; an empty list: every slot.
+    pub fn clear_filters(&mut self, slot: &[u32]) {
+        check(unsafe { lmrs_batch_clear_filters(self.b, slot.len() as u32, if slot.is_empty() { ptr::null() } else { slot.as_ptr() }) });
+    }
+
+    /// `slot`'s filters as set, and whether they can clear a logit.
+    pub fn filter_info(&self, slot: u32) -> (Filter, bool) {
+        let (mut f, mut active) = (Filter { top_k: 0, min_gap: f32::INFINITY }, 0 as c_int);
+        check(unsafe { lmrs_batch_filter_info(self.b, slot, &mut f.top_k, &mut f.min_gap, &mut active) });
+        (f, active != 0)
     }
 
     /// The token record of `slot` from `start_pos` on = `tokens` (`TOKEN_NONE`: unknown); no tokens: only switches the record on.
