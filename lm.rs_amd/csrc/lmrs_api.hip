@@ -693,14 +693,60 @@ void destroy_step_graphs(lmrs_ctx* c) {
     for (auto& forms : c->g_steps) for (hipGraphExec_t& g : forms) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
 }
 
-// host->device copy of one tensor payload, optionally row-interleaved (dst row = 2*r + phase)
-int upload(lmrs_ctx* c, void* dst, const uint8_t* src, size_t bytes) {
-    HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+// The model file reaches the device through two pinned slabs.  Handed a pageable source the runtime pins the caller's pages for a large copy, and
+// where the host refuses to register memory (virtual machines) that copy crawls: 210 ms for a 16 MiB tensor, 5 - 90 ms for a strided one, 0.6 s
+// for a context of the smallest test model.  From a slab every copy is a plain DMA, and filling one slab overlaps the other's copy.
+struct Stager {
+    static constexpr size_t kSlab = (size_t)4 << 20;
+    hipStream_t stream; PinBuf<char> slab[2]; hipEvent_t sent[2] = {}; int turn = 0;
+    explicit Stager(hipStream_t s) : stream(s) {}
+    Stager(const Stager&) = delete;
+    Stager& operator=(const Stager&) = delete;
+    ~Stager() { for (hipEvent_t e : sent) if (e) (void)hipEventDestroy(e); }
+    // the slab whose turn it is, once the copy that last read it is done; null: the error is reported
+    char* take() {
+        const int i = turn;
+        if (!slab[i]) {
+            if (!slab[i].alloc(kSlab)) { alloc_failed("upload slab: hipHostMalloc"); return nullptr; }
+            const hipError_t e = hipEventCreateWithFlags(&sent[i], hipEventDisableTiming);
+            if (e != hipSuccess) { fail(std::string("upload slab: hipEventCreateWithFlags: ") + hipGetErrorString(e)); return nullptr; }
+        }
+        const hipError_t e = hipEventSynchronize(sent[i]);
+        if (e != hipSuccess) { fail(std::string("upload slab: hipEventSynchronize: ") + hipGetErrorString(e)); return nullptr; }
+        return slab[i];
+    }
+    // the first n bytes of the slab just taken -> dst; the turn passes to the other slab
+    int send(void* dst, size_t n) {
+        const int i = turn; turn ^= 1;
+        HIP_OK(hipMemcpyAsync(dst, slab[i].get(), n, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipEventRecord(sent[i], stream));
+        return 0;
+    }
+};
+// host->device copy of one tensor payload
+int upload(Stager& up, void* dst, const void* src, size_t bytes) {
+    for (size_t off = 0; off < bytes; off += Stager::kSlab) {
+        const size_t n = std::min(bytes - off, Stager::kSlab);
+        char* s = up.take();
+        if (!s) return -1;
+        memcpy(s, static_cast<const char*>(src) + off, n);
+        if (up.send(static_cast<char*>(dst) + off, n)) return -1;
+    }
     return 0;
 }
-int upload_interleaved(lmrs_ctx* c, void* dst, const uint8_t* src, size_t row_bytes, size_t rows, int phase) {
-    HIP_OK(hipMemcpy2DAsync(static_cast<char*>(dst) + phase * row_bytes, 2 * row_bytes, src, row_bytes, row_bytes, rows,
-                            hipMemcpyHostToDevice, c->stream));
+// ... of two payloads with their rows interleaved: dst row 2r = a's row r, row 2r + 1 = b's (row_bytes <= 40 KiB: a slab holds many pairs)
+int upload_interleaved(Stager& up, void* dst, const uint8_t* a, const uint8_t* b, size_t row_bytes, size_t rows) {
+    const size_t per = Stager::kSlab / (2 * row_bytes);
+    for (size_t r0 = 0; r0 < rows; r0 += per) {
+        const size_t nr = std::min(rows - r0, per);
+        char* s = up.take();
+        if (!s) return -1;
+        for (size_t r = 0; r < nr; ++r) {
+            memcpy(s + 2 * r * row_bytes, a + (r0 + r) * row_bytes, row_bytes);
+            memcpy(s + (2 * r + 1) * row_bytes, b + (r0 + r) * row_bytes, row_bytes);
+        }
+        if (up.send(static_cast<char*>(dst) + 2 * r0 * row_bytes, 2 * nr * row_bytes)) return -1;
+    }
     return 0;
 }
 
@@ -1012,10 +1058,11 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     c->arena_bytes = total;
 
     // ---- weights: this shard's rows only (the embedding / classifier table stays whole: any row may be looked up)
+    Stager up(c->stream);
     auto upload_rows = [&](void* dst, const TensorView& tv, size_t row0, size_t nrows, size_t cols, bool scales) -> int {
         if (scales && f32w) return 0;
         const size_t rb = scales ? cols / G * 4 : qbytes(1, cols);
-        return upload(c, dst, file + (scales ? tv.s_off : tv.q_off) + row0 * rb, nrows * rb);
+        return upload(up, dst, file + (scales ? tv.s_off : tv.q_off) + row0 * rb, nrows * rb);
     };
     c->layers.resize(nl);
     for (size_t l = 0; l < nl; ++l) {
@@ -1036,16 +1083,15 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
         CK(upload_rows(reinterpret_cast<char*>(sqkv) + (att_l + kv_l) * srb, tv, k0, kv_l, dim, true));
         CK(upload_rows(wo, lay.wo[l], d0, dim_l, att, false));
         CK(upload_rows(so, lay.wo[l], d0, dim_l, att, true));
-        CK(upload_interleaved(c, w13, file + lay.w1[l].q_off + h0 * rb, rb, hid_l, 0));
-        CK(upload_interleaved(c, w13, file + lay.w3[l].q_off + h0 * rb, rb, hid_l, 1));
-        if (!f32w) { CK(upload_interleaved(c, s13, file + lay.w1[l].s_off + h0 * srb, srb, hid_l, 0)); CK(upload_interleaved(c, s13, file + lay.w3[l].s_off + h0 * srb, srb, hid_l, 1)); }
+        CK(upload_interleaved(up, w13, file + lay.w1[l].q_off + h0 * rb, file + lay.w3[l].q_off + h0 * rb, rb, hid_l));
+        if (!f32w) CK(upload_interleaved(up, s13, file + lay.w1[l].s_off + h0 * srb, file + lay.w3[l].s_off + h0 * srb, srb, hid_l));
         CK(upload_rows(w2, lay.w2[l], d0, dim_l, hid, false));
         CK(upload_rows(s2, lay.w2[l], d0, dim_l, hid, true));
-        CK(upload(c, r0, file + lay.rms_att[l].q_off, dim * 4));
-        CK(upload(c, r1, file + lay.rms_post_att[l].q_off, dim * 4));
+        CK(upload(up, r0, file + lay.rms_att[l].q_off, dim * 4));
+        CK(upload(up, r1, file + lay.rms_post_att[l].q_off, dim * 4));
         if (a.model_type == LMRS_GEMMA) {
-            CK(upload(c, r2, file + lay.rms_pre_ffn[l].q_off, dim * 4));
-            CK(upload(c, r3, file + lay.rms_post_ffn[l].q_off, dim * 4));
+            CK(upload(up, r2, file + lay.rms_pre_ffn[l].q_off, dim * 4));
+            CK(upload(up, r3, file + lay.rms_post_ffn[l].q_off, dim * 4));
         }
         D.wqkv = wqkv; D.sqkv = sqkv; D.wo = wo; D.so = so; D.w13 = w13; D.s13 = s13; D.w2 = w2; D.s2 = s2;
         D.rms_att = r0; D.rms_post_att = r1; D.rms_pre_ffn = r2; D.rms_post_ffn = r3;
@@ -1053,16 +1099,16 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
     {
         char* eq = c->alloc<char>(lay.emb.q_bytes); float* es = c->alloc<float>(lay.emb.s_bytes / 4);
         if (!eq || !es) { fail("arena overflow"); return cleanup(); }
-        CK(upload(c, eq, file + lay.emb.q_off, lay.emb.q_bytes)); if (!f32w) CK(upload(c, es, file + lay.emb.s_off, lay.emb.s_bytes));
+        CK(upload(up, eq, file + lay.emb.q_off, lay.emb.q_bytes)); if (!f32w) CK(upload(up, es, file + lay.emb.s_off, lay.emb.s_bytes));
         c->emb_q = eq; c->emb_s = es; c->cls_q = eq; c->cls_s = es;        // tied classifier = the QUANTISED table
         if (a.model_type == LMRS_PHI) {
             char* hq = c->alloc<char>(lay.lm_head.q_bytes); float* hsx = c->alloc<float>(lay.lm_head.s_bytes / 4);
             if (!hq || !hsx) { fail("arena overflow"); return cleanup(); }
-            CK(upload(c, hq, file + lay.lm_head.q_off, lay.lm_head.q_bytes)); if (!f32w) CK(upload(c, hsx, file + lay.lm_head.s_off, lay.lm_head.s_bytes));
+            CK(upload(up, hq, file + lay.lm_head.q_off, lay.lm_head.q_bytes)); if (!f32w) CK(upload(up, hsx, file + lay.lm_head.s_off, lay.lm_head.s_bytes));
             c->cls_q = hq; c->cls_s = hsx;
         }
         float* rf = c->alloc<float>(dim);
-        CK(upload(c, rf, file + lay.rms_final.q_off, dim * 4));
+        CK(upload(up, rf, file + lay.rms_final.q_off, dim * 4));
         c->rms_final = rf;
     }
     // ---- state
@@ -1113,8 +1159,7 @@ static int create_impl(const uint8_t* file, size_t len, int device, int rank, in
         std::vector<float> tab((size_t)a.seq_len * a.head_size);
         for (uint32_t p = 0; p < a.seq_len; ++p)
             for (uint32_t j = 0; j < half; ++j) rope_terms(a, p, j, &tab[((size_t)p * half + j) * 2], &tab[((size_t)p * half + j) * 2 + 1]);
-        HCK(hipMemcpyAsync(c->rope, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HCK(hipStreamSynchronize(c->stream));       // tab goes out of scope
+        CK(upload(up, c->rope, tab.data(), tab.size() * 4));
     }
     if (!alloc_all({{c->h_logits, V}, {c->h_tok, (size_t)a.seq_len + 8}, {c->h_st, kStateSlots}, {c->h_err, 1}})) { alloc_failed("pinned host buffers: hipHostMalloc"); return cleanup(); }
     CK(set_state(c, 0, 0));
