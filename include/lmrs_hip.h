@@ -279,6 +279,26 @@ int  lmrs_batch_width(const lmrs_batch* b, uint32_t* width);
  * 0.7 % / 5.7 % faster on Gemma-2-2B Q4_0 (profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt). */
 int lmrs_batch_create_paged(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
                             uint32_t n_pages /* >= 1 */, lmrs_batch** out);
+/* ---- paged K/V in 8 bits (extensions, no reference counterpart): lmrs_batch_create_paged's pool with every K row (after RoPE) and every V row stored in
+ * groups of 32 consecutive elements of the kv_dim row, each group by the reference's Q8_0 rule (quantization.rs:44-67 at a group of 32): scale = max|x| /
+ * 127 in f32, q = round-half-away(x / scale) as int8, an all-zero group q = 0 and scale = 0.  A cached value reads back as (float)q * scale.  A row at
+ * position p of a slot attends to keys and values 0 .. p-1 as read back and to its OWN key and value in f32, as the pass computed them; rows of one run
+ * see the earlier rows of their run read back.  Everything else is the table pass, operation for operation.  So every output - logits, argmax, top-k,
+ * sampled tokens, the device loops' tokens - is bit for bit what the sequential forward gives when, after each forward(token, pos), the K and V rows of
+ * pos in every layer are replaced by their quantise -> dequantise round trip.  lmrs_batch_debug_kv returns the row as read back; a position nobody wrote
+ * reads as zero (the zero page: all-zero int8, all-zero scales).
+ * Same arguments and refusals as lmrs_batch_create_paged, each message opening with this call's name.  The allocation is (n_pages + 1) * 2 * n_layers *
+ * page_len * kv_dim * 9 / 8 bytes, all or nothing, the message gives the bytes: 1.125 bytes a cached value instead of 4.  Every batch call works as
+ * documented for a paged batch.  lmrs_batch_fork between slots copies pages and rows as bytes; from LMRS_BATCH_CTX the context's f32 rows are quantised.
+ * Out of scope: block attention over Q8 pages - every prompt chunk takes the table pass, lmrs_batch_prefill_form reports n_block = 0 and
+ * lmrs_batch_debug_prefill_table is accepted and changes nothing; Q8 for contiguous and wide batches; Q8 for the context's own cache; Q4 pages.
+ * Measured against the f32 pool on the parent commit's library, 64 rows a pass: Llama-3.2-1B Q8_0 -16 % at 100 positions and -38 % at 1000, Gemma-2-2B
+ * Q4_0 -4 % / -14 %; a 512-token prefill is about 1.5x / 1.6x slower (profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt). */
+int lmrs_batch_create_paged_q8(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
+                               uint32_t n_pages /* >= 1 */, lmrs_batch** out);
+/* how a batch keeps its K/V: *format 0 f32 / 1 Q8, *group 0 / 32, *page_bytes a page's size - K and V blocks of every layer (0 on a batch that is not
+ * paged); a paged batch's pool is page_bytes * (n_pages + 1).  Any batch. */
+int lmrs_batch_kv_format(const lmrs_batch* b, int* format /* 0 f32, 1 Q8 */, uint32_t* group /* 0 or 32 */, size_t* page_bytes);
 /* the pool: its page length, its pages (the zero page not counted) and how many of them nobody holds.  Refused on a batch that is not paged. */
 int lmrs_batch_pages(const lmrs_batch* b, uint32_t* page_len, uint32_t* n_pages, uint32_t* n_free);
 /* the pages a slot holds, and how many of them have more than one holder.  Refused on a batch that is not paged, and for a slot >= n_slots. */

@@ -32,7 +32,7 @@ EXPORTS = [
     "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
     "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
-    "lmrs_batch_create_paged", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
+    "lmrs_batch_create_paged", "lmrs_batch_create_paged_q8", "lmrs_batch_kv_format", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
     "lmrs_batch_generate",
@@ -119,6 +119,8 @@ def lib():
         L.lmrs_batch_width.argtypes = [vp, C.POINTER(u32)]
         L.lmrs_batch_create_paged.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
         L.lmrs_batch_pages.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+        L.lmrs_batch_create_paged_q8.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
+        L.lmrs_batch_kv_format.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u32), C.POINTER(C.c_size_t)]
         L.lmrs_batch_slot_pages.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_release.argtypes = [vp, u32, u32]
         L.lmrs_batch_prefill_form.argtypes = [vp, sz, u32, C.POINTER(u32), C.POINTER(u32)]
@@ -550,17 +552,31 @@ class Batch:
     (lmrs_batch_create_wide; forward_sample keeps 16 rows).
     page_len= and n_pages= (both or neither; wide= is then ignored): a PAGED batch, wide, whose slots draw pages of page_len positions (64, 128, 256,
     512 or 1024) from one pool of n_pages pages instead of holding a whole cache each: fork shares whole pages, a write un-shares the page it
-    touches, release gives pages back.  Without release every result is bit for bit a wide batch's (lmrs_batch_create_paged)."""
+    touches, release gives pages back.  Without release every result is bit for bit a wide batch's (lmrs_batch_create_paged).
+    kv="q8" (a paged batch only): the pages hold every K and V row in 8 bits, groups of 32 with an f32 scale each - 1.125 bytes a value instead of 4; a
+    row attends to the earlier positions as read back, (float)q * scale, and to its own key and value in f32 (lmrs_batch_create_paged_q8)."""
 
-    def __init__(self, model: Transformer, n_slots: int, wide: bool = False, *, page_len=None, n_pages=None):
+    def __init__(self, model: Transformer, n_slots: int, wide: bool = False, *, page_len=None, n_pages=None, kv: str = "f32"):
         h = C.c_void_p()
         if (page_len is None) != (n_pages is None):
             raise LmrsError("page_len and n_pages must be given together")
+        if kv not in ("f32", "q8"):
+            raise LmrsError(f"kv = {kv!r} is neither 'f32' nor 'q8'")
+        if kv == "q8" and page_len is None:
+            raise LmrsError("kv='q8' needs a paged batch: give page_len and n_pages")
         if page_len is not None:
-            _chk(lib().lmrs_batch_create_paged(model._h, n_slots, page_len, n_pages, C.byref(h)))
+            create = lib().lmrs_batch_create_paged_q8 if kv == "q8" else lib().lmrs_batch_create_paged
+            _chk(create(model._h, n_slots, page_len, n_pages, C.byref(h)))
         else:
             _chk((lib().lmrs_batch_create_wide if wide else lib().lmrs_batch_create)(model._h, n_slots, C.byref(h)))
         self._h, self.model, self.n_slots = h, model, n_slots
+
+    def kv_format(self):
+        """How the batch keeps K/V -> (name, group, page_bytes): ("f32", 0, ..) or ("q8", 32, ..); page_bytes is a page's size, K and V blocks of every
+        layer together (0 on a batch that is not paged) - the pool is page_bytes * (n_pages + 1) (lmrs_batch_kv_format)"""
+        f, g, n = C.c_int(), C.c_uint32(), C.c_size_t()
+        _chk(lib().lmrs_batch_kv_format(self._h, C.byref(f), C.byref(g), C.byref(n)))
+        return ("q8" if f.value else "f32"), g.value, n.value
 
     def pages(self):
         """A paged batch's pool -> (page_len, n_pages, n_free) (lmrs_batch_pages)"""

@@ -207,7 +207,7 @@ struct AutoView { const AutoRow* of = nullptr; const AutoRow* h_of = nullptr; co
 // top_k / min_gap in the order the classifier sees the rows, slot -1 for none; h_of is its pinned source, as with the masks
 struct FilterView { const FilterRow* of = nullptr; const FilterRow* h_of = nullptr; };
 struct PenaltyView { const uint32_t* hist = nullptr; int seq_len = 0; const int* pos = nullptr; const PenaltyRow* of = nullptr; const PenaltyRow* h_of = nullptr; int max_n = 0; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; };   // pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; size_t kvq_bytes = 0; };   // kvq_bytes != 0: the pool holds Q8 pages (lmrs_kvq.inc), that many int8 bytes a K / V block; pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1523,12 +1523,20 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
         if (form.pages.tab) {
             // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
             const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
+            if (form.kvq_bytes) {
+                // Q8 pages: the scatter quantises (and leaves the rotated k in the qkv row), the table pass reads the pages back; no block form
+                const KvqView qv{form.pages.tab, form.pages.per_slot, form.pages.shift, form.pages.page_stride * 4, form.kvq_bytes};
+                if (form.block_pos0 >= 0) return fail("block attention over Q8 pages is not built");
+                HIP_OK(launch_kvq_scatter(qkv, k_cache, v_cache, c->rope, rv, qv, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
+                HIP_OK(launch_kvq_attention(t, rv, qv, m, form.max_T, c->stream));
+            } else {
             HIP_OK(launch_paged_scatter(qkv, k_cache, v_cache, c->rope, rv, form.pages, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
             if (form.block_pos0 >= 0) {
                 // one slot's consecutive rows, rotated and in its pages by now: 64-query blocks read every key and value row through the slot's page row
                 if (prefill_slabs(c, attention_block_scratch_floats(t.n_heads, m, form.block_pos0 + m))) return -1;
                 HIP_OK(launch_paged_attention_block(t, form.pages, form.block_row, form.block_pos0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
             } else HIP_OK(launch_paged_attention(t, rv, form.pages, m, form.max_T, c->stream));
+            }
         } else if (form.rows) {
             // every row at its own position in its own slot: rotation, K / V rows into the slots, one attention workgroup per (head, row)
             HIP_OK(launch_rope_scatter_rows(c->pf_q, k_cache, v_cache, c->rope, form.rows, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
@@ -2104,6 +2112,9 @@ struct lmrs_batch {
     // a paged batch (lmrs_batch_create_paged): kv is the pool - page p's K block at kv + p * 2 * page_floats, its V block page_floats behind, page 0 the zero
     // page; the accounting (lmrs_pages.h), the device page table [n_slots][per_slot] and its pinned mirror
     std::unique_ptr<PagePool> pool; uint32_t page_len = 0; size_t page_floats = 0;
+    // Q8 pages (lmrs_batch_create_paged_q8; lmrs_kvq.inc): kvq_bytes = n_layers * page_len * kv_dim, the int8 bytes of a page's K (or V) block, its f32 scales
+    // behind them - page_floats is then that block's size in floats, 9 / 32 of the f32 one, and every page address and size below follows from it
+    size_t kvq_bytes = 0;
     DevBuf<uint32_t> ptab; PinBuf<uint32_t> h_ptab;
     bool pf_table = false;                              // lmrs_batch_debug_prefill_table: every prompt chunk takes the table pass
     // allowed-token masks (lmrs_batch_set_masks; made at the first call, mask_words != 0 from then on): the device block [n_slots][mask_words] and its pinned mirror,
@@ -2202,7 +2213,8 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
 
 // lmrs_batch_create / lmrs_batch_create_wide: `name` opens every message, width is the batch's row and slot limit
 // page_len > 0 (lmrs_batch_create_paged): the slots draw pages of page_len positions from one pool of n_pages pages (+ the zero page) instead of a cache each
-static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width, uint32_t page_len = 0, uint32_t n_pages = 0) {
+// q8: the pool's pages hold int8 values and f32 scales per 32 (lmrs_batch_create_paged_q8)
+static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width, uint32_t page_len = 0, uint32_t n_pages = 0, bool q8 = false) {
     if (!c || !out) return fail("NULL argument");
     *out = nullptr;
     if (n_slots < 1 || n_slots > width) return fail(name + ": n_slots = " + std::to_string(n_slots) + " is outside 1 .. " + std::to_string(width));
@@ -2221,6 +2233,7 @@ static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const s
     lmrs_batch* b = new lmrs_batch;
     b->c = c; b->n_slots = n_slots; b->width = width; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
     b->page_len = page_len; b->page_floats = (size_t)a.n_layers * page_len * c->kv_dim;
+    if (q8) { b->kvq_bytes = b->page_floats; b->page_floats = b->kvq_bytes * 9 / 32; }          // (page_len * kv_dim is a multiple of 64 * 32)
     const size_t bytes = page_len ? ((size_t)n_pages + 1) * 2 * b->page_floats * 4 : (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
     if (!b->kv.alloc(bytes / 4)) {                                                                       // all or nothing: one allocation
         (void)hipGetLastError(); lmrs_batch_destroy(b);
@@ -2634,6 +2647,22 @@ extern "C" int lmrs_batch_create_paged(lmrs_ctx* c, uint32_t n_slots, uint32_t p
     if (n_pages == 0) return fail(name + ": n_pages is 0");
     return batch_create(c, n_slots, out, name, kWideBatchMax, page_len, n_pages);
 }
+// the same pool with its pages in 8 bits (lmrs_kvq.inc: the rule, the layout): same arguments, same refusals, 9 / 32 of the bytes
+extern "C" int lmrs_batch_create_paged_q8(lmrs_ctx* c, uint32_t n_slots, uint32_t page_len, uint32_t n_pages, lmrs_batch** out) {
+    const std::string name = "lmrs_batch_create_paged_q8";
+    if (out) *out = nullptr;
+    if (page_len != 64 && page_len != 128 && page_len != 256 && page_len != 512 && page_len != 1024)
+        return fail(name + ": page_len = " + std::to_string(page_len) + " is none of 64, 128, 256, 512, 1024");
+    if (n_pages == 0) return fail(name + ": n_pages is 0");
+    if (c && c->args.head_size % 32) return fail(name + ": head_size = " + std::to_string(c->args.head_size) + " is not a multiple of the group of 32");
+    return batch_create(c, n_slots, out, name, kWideBatchMax, page_len, n_pages, true);
+}
+extern "C" int lmrs_batch_kv_format(const lmrs_batch* b, int* format, uint32_t* group, size_t* page_bytes) {
+    if (!b || !format || !group || !page_bytes) return fail("lmrs_batch_kv_format: NULL argument");
+    *format = b->kvq_bytes ? 1 : 0; *group = b->kvq_bytes ? 32u : 0u;
+    *page_bytes = b->pool ? 2 * b->page_floats * 4 : 0;
+    return 0;
+}
 extern "C" int lmrs_batch_pages(const lmrs_batch* b, uint32_t* page_len, uint32_t* n_pages, uint32_t* n_free) {
     if (!b || !page_len || !n_pages || !n_free) return fail("lmrs_batch_pages: NULL argument");
     if (!b->pool) return fail("lmrs_batch_pages: not a paged batch (lmrs_batch_create_paged)");
@@ -2740,6 +2769,17 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
         // lie ss positions apart (another page: page_len; the context's cache: seq_len)
         const size_t PL = b->page_len;
         auto copy_rows = [&](uint32_t page, size_t r0, size_t r1, const float* ks, const float* vs, size_t ss) -> int {
+            if (b->kvq_bytes) {
+                // Q8 pages, as bytes: K words [n_layers kv / 16][PL][16] and scales [n_layers kv / 32][PL], V rows [n_layers][PL][kv] and scales [..][kv / 32]
+                const char *kq = reinterpret_cast<const char*>(ks), *vq = reinterpret_cast<const char*>(vs);
+                char *dk = reinterpret_cast<char*>(b->page_k(page)), *dv = reinterpret_cast<char*>(b->page_v(page));
+                const size_t Q = b->kvq_bytes, n = r1 - r0, L = a.n_layers;
+                HIP_OK(hipMemcpy2DAsync(dk + r0 * 16, PL * 16, kq, ss * 16, n * 16, L * kv / 16, hipMemcpyDeviceToDevice, c->stream));
+                HIP_OK(hipMemcpy2DAsync(dk + Q + r0 * 4, PL * 4, kq + Q, ss * 4, n * 4, L * kv / 32, hipMemcpyDeviceToDevice, c->stream));
+                HIP_OK(hipMemcpy2DAsync(dv + r0 * kv, PL * kv, vq, ss * kv, n * kv, L, hipMemcpyDeviceToDevice, c->stream));
+                HIP_OK(hipMemcpy2DAsync(dv + Q + r0 * kv / 8, PL * kv / 8, vq + Q, ss * kv / 8, n * kv / 8, L, hipMemcpyDeviceToDevice, c->stream));
+                return 0;
+            }
             HIP_OK(hipMemcpy2DAsync(b->page_k(page) + r0 * 4, PL * 16, ks, ss * 16, (r1 - r0) * 16, (size_t)a.n_layers * kv / 4, hipMemcpyDeviceToDevice, c->stream));
             HIP_OK(hipMemcpy2DAsync(b->page_v(page) + r0 * kv, PL * kv * 4, vs, ss * kv * 4, (r1 - r0) * kv * 4, a.n_layers, hipMemcpyDeviceToDevice, c->stream));
             return 0;
@@ -2749,7 +2789,12 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
             if (pages_claim(b, "lmrs_batch_fork: ", &all, 1)) return -1;
             for (size_t p0 = 0; p0 < n_pos; p0 += PL) {
                 const size_t p1 = std::min<size_t>(n_pos, p0 + PL);
-                if (copy_rows(b->pool->row(dst_slot)[p0 / PL], 0, p1 - p0, c->k_cache + p0 * 4, c->v_cache + p0 * kv, S)) return batch_failed(c);
+                const uint32_t page = b->pool->row(dst_slot)[p0 / PL];
+                if (b->kvq_bytes) {                          // the context's f32 rows through the scatter's quantiser
+                    if (launch_kvq_import(c->k_cache, c->v_cache, (int)S, (int)p0, b->page_k(page), b->page_v(page), b->kvq_bytes, (int)a.n_layers, (int)kv, (int)PL, 0,
+                                          (int)(p1 - p0), c->stream) != hipSuccess) { fail("lmrs_batch_fork: the quantising copy failed to launch"); return batch_failed(c); }
+                } else
+                if (copy_rows(page, 0, p1 - p0, c->k_cache + p0 * 4, c->v_cache + p0 * kv, S)) return batch_failed(c);
             }
         } else {
             std::vector<PageAction> acts; std::vector<uint32_t> dirty; uint32_t wanted = 0, part_p0 = 0, part_src = 0, part_dst = 0;
@@ -2849,7 +2894,7 @@ static int source_rows(lmrs_ctx* c, const uint32_t* src, const float* staged, in
 static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to, const float* staged = nullptr) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
-    form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view();
+    form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes;
     if (record_rows(b, form.runs.pos, form.runs.tok, R)) return -1;
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
@@ -2928,7 +2973,7 @@ static int masks_enqueue(lmrs_batch* b, size_t n, bool filters = true) {
 static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logits) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
-    if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); }
+    if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; }
     form.masks = b->mask_view(); form.autos = b->auto_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T); form.filters = b->filter_view();
     if (record_rows(b, b->tab->pos, b->tab->tok, n)) return -1;
     RowSink to{0, n, out_logits, 0}; to.targets = false;
@@ -3215,7 +3260,7 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
 // A prompt chunk of a paged batch - m rows of one slot from p0 on - takes block attention over the page table by prefill_attention's rule (and from
 // kPagedBlockMin rows on); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it
 static bool paged_block_route(const lmrs_batch* b, uint32_t m, uint32_t p0) {
-    return !b->pf_table && m >= kPagedBlockMin && prefill_block_route(b->c, (int)m, (int)p0);
+    return !b->kvq_bytes && !b->pf_table && m >= kPagedBlockMin && prefill_block_route(b->c, (int)m, (int)p0);     // (Q8 pages: the table pass only)
 }
 extern "C" int lmrs_batch_prefill_form(const lmrs_batch* b, size_t n, uint32_t start_pos, uint32_t* n_chunks, uint32_t* n_block) {
     const std::string what = "lmrs_batch_prefill_form: ";
@@ -3701,12 +3746,33 @@ extern "C" int lmrs_batch_prefill_embeddings(lmrs_batch* b, uint32_t slot, const
     return batch_call(c, enqueue);
 }
 
+// a row of a Q8 page read back: (float)q * scale, the one multiply of the rule (lmrs_kvq.inc), formed here on the host
+static int debug_kvq_row(lmrs_batch* b, uint32_t page, int which, uint32_t layer, uint32_t pin, float* out) {
+    lmrs_ctx* c = b->c;
+    if (which < 0 || which > 1 || layer >= c->args.n_layers) return fail("bad layer / position");
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const size_t kv = (size_t)c->kv_dim, PL = b->page_len, Q = b->kvq_bytes;
+    std::vector<int8_t> q(kv); std::vector<float> s(kv / 32);
+    if (which == 1) {
+        const char* v = reinterpret_cast<const char*>(b->page_v(page));
+        HIP_OK(hipMemcpy(q.data(), v + ((size_t)layer * PL + pin) * kv, kv, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(s.data(), v + Q + ((size_t)layer * PL + pin) * (kv / 32) * 4, kv / 8, hipMemcpyDeviceToHost));
+    } else {
+        const char* k = reinterpret_cast<const char*>(b->page_k(page));
+        HIP_OK(hipMemcpy2D(q.data(), 16, k + ((size_t)layer * (kv / 16) * PL + pin) * 16, PL * 16, 16, kv / 16, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy2D(s.data(), 4, k + Q + ((size_t)layer * (kv / 32) * PL + pin) * 4, PL * 4, 4, kv / 32, hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < kv; ++i) out[i] = (float)q[i] * s[i / 32];
+    return 0;
+}
 extern "C" int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out) {
     if (!b || !out) return fail("NULL argument");
     if (slot >= b->n_slots) return fail("lmrs_batch_debug_kv: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
     if (b->pool) {                                       // the row's page (the zero page where nothing was claimed), at its in-page position
         if (pos >= b->c->args.seq_len) return fail("bad layer / position");
         const uint32_t page = b->pool->row(slot)[pos / b->page_len];
+        if (b->kvq_bytes) return debug_kvq_row(b, page, which, layer, pos % b->page_len, out);
         return debug_kv_row(b->c, b->page_k(page), b->page_v(page), which, layer, pos % b->page_len, out, b->page_len);
     }
     return debug_kv_row(b->c, b->k_of(slot), b->v_of(slot), which, layer, pos, out);

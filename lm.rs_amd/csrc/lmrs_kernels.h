@@ -302,6 +302,16 @@ hipError_t launch_paged_attention(const AttnArgs& a, RowView rows, PageView pv, 
 // launch_attention_block over ONE slot's page row (table_row): n_tok consecutive rows from pos0 on, rotated and scattered already (launch_paged_scatter), so
 // every key is read from the pages.  a.q: the qkv block (row stride att + 2 kv); a.k_cache / a.v_cache: k_pool / v_pool; scratch, lds_keys, long_forms: as there
 hipError_t launch_paged_attention_block(const AttnArgs& a, PageView pv, unsigned table_row, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s);
+// ---- the table pass over paged K/V kept in 8 bits (lmrs_batch_create_paged_q8; lmrs_kvq.inc: the rule and the page layout).  The PageView's table over pages
+// page_bytes apart; q_bytes = n_layers * page_len * kv_dim, the int8 part of a page's K (or V) block, its f32 scales behind it.  k_pool / v_pool: the K and
+// the V block of page 0.  The scatter leaves the ROTATED k in the qkv row; the attention reads the row's own key and value from there, in f32.
+struct KvqView { const uint32_t* tab; int per_slot; int shift; size_t page_bytes; size_t q_bytes; };
+hipError_t launch_kvq_scatter(float* qkv, float* k_pool, float* v_pool, const float* rope, RowView rows, KvqView pv, int n_heads, int n_kv_heads, int hs,
+                              int layer, int n_rows, hipStream_t s);
+hipError_t launch_kvq_attention(const AttnArgs& a, RowView rows, KvqView pv, int n_rows, int max_T, hipStream_t s);
+// rows p0 .. p0 + n_rows - 1 of a contiguous f32 cache (the context's layout, seq_len positions) quantised into in-page positions pin0 .. of ONE page
+hipError_t launch_kvq_import(const float* k_src, const float* v_src, int seq_len, int p0, float* k_page, float* v_page, size_t q_bytes, int n_layers, int kv, int page_len,
+                             int pin0, int n_rows, hipStream_t s);
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

@@ -166,6 +166,14 @@ public:
     Batch(Transformer& t, std::uint32_t n_slots, std::uint32_t page_len, std::uint32_t n_pages) : vocab_size_(t.args.vocab_size) {
         check(lmrs_batch_create_paged(t.ctx_, n_slots, page_len, n_pages, &b_));
     }
+    // ... with its pages in 8 bits (Q8{}): groups of 32 values with an f32 scale each, 1.125 bytes a value; a row attends to the earlier positions as read
+    // back and to its own key and value in f32  (lmrs_batch_create_paged_q8)
+    struct Q8 {};
+    Batch(Transformer& t, std::uint32_t n_slots, std::uint32_t page_len, std::uint32_t n_pages, Q8) : vocab_size_(t.args.vocab_size) {
+        check(lmrs_batch_create_paged_q8(t.ctx_, n_slots, page_len, n_pages, &b_));
+    }
+    struct KvFormat { int format; std::uint32_t group; std::size_t page_bytes; };                                                   // 0 f32 / 1 Q8, 0 / 32, a page's bytes
+    KvFormat kv_format() const { KvFormat f{}; check(lmrs_batch_kv_format(b_, &f.format, &f.group, &f.page_bytes)); return f; }      // (lmrs_batch_kv_format)
     struct Pages { std::uint32_t page_len, n_pages, n_free; };
     Pages pages() const { Pages p{}; check(lmrs_batch_pages(b_, &p.page_len, &p.n_pages, &p.n_free)); return p; }                  // (lmrs_batch_pages)
     struct SlotPages { std::uint32_t held, shared; };

@@ -30,6 +30,9 @@ extern "C" {
     // paged K/V: declared here as the wide batch is (tests/test_batch_paged_host.py compares them with the header)
     pub fn lmrs_batch_create_paged(ctx: *mut ffi::LmrsCtx, n_slots: u32, page_len: u32, n_pages: u32, out: *mut *mut LmrsBatch) -> c_int;
     pub fn lmrs_batch_pages(b: *const LmrsBatch, page_len: *mut u32, n_pages: *mut u32, n_free: *mut u32) -> c_int;
+    // the pool in 8 bits, and how a batch keeps its K/V: declared here as the paged calls are
+    pub fn lmrs_batch_create_paged_q8(ctx: *mut ffi::LmrsCtx, n_slots: u32, page_len: u32, n_pages: u32, out: *mut *mut LmrsBatch) -> c_int;
+    pub fn lmrs_batch_kv_format(b: *const LmrsBatch, format: *mut c_int, group: *mut u32, page_bytes: *mut usize) -> c_int;
     pub fn lmrs_batch_slot_pages(b: *const LmrsBatch, slot: u32, n_held: *mut u32, n_shared: *mut u32) -> c_int;
     pub fn lmrs_batch_release(b: *mut LmrsBatch, slot: u32, n_pos: u32) -> c_int;
     pub fn lmrs_batch_prefill_form(b: *const LmrsBatch, n: usize, start_pos: u32, n_chunks: *mut u32, n_block: *mut u32) -> c_int;
@@ -170,6 +173,22 @@ impl<'t, 'a> Batch<'t, 'a> {
         check(unsafe { lmrs_batch_create_paged(t.ctx(), n_slots, page_len, n_pages, &mut b) });
         let vocab_size = t.args.vocab_size as usize;
         Batch { b, vocab_size, _t: t }
+    }
+
+    /// `new_paged` with the pages in 8 bits: groups of 32 values with an f32 scale each, 1.125 bytes a value.  A row attends to the earlier positions as
+    /// read back and to its own key and value in f32.
+    pub fn new_paged_q8(t: &'t mut Transformer<'a>, n_slots: u32, page_len: u32, n_pages: u32) -> Batch<'t, 'a> {
+        let mut b: *mut LmrsBatch = ptr::null_mut();
+        check(unsafe { lmrs_batch_create_paged_q8(t.ctx(), n_slots, page_len, n_pages, &mut b) });
+        let vocab_size = t.args.vocab_size as usize;
+        Batch { b, vocab_size, _t: t }
+    }
+
+    /// How the batch keeps K/V: (0 f32 / 1 Q8, the group - 0 or 32, a page's bytes - 0 on a batch that is not paged).
+    pub fn kv_format(&self) -> (i32, u32, usize) {
+        let (mut f, mut g, mut n) = (0 as c_int, 0u32, 0usize);
+        check(unsafe { lmrs_batch_kv_format(self.b, &mut f, &mut g, &mut n) });
+        (f as i32, g, n)
     }
 
     /// A paged batch's pool: (page_len, n_pages, n_free).

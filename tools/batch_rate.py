@@ -13,6 +13,9 @@ lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: 
        python tools/batch_rate.py --paged [model] [q8_0|q4_0]
 --paged: a PAGED batch (lmrs_batch_create_paged) against the wide batch of the same build, the forms by turns (paged_main below)
        (writes profiles/batch_paged_llama1b.txt, profiles/batch_paged_gemma2b_q4.txt, profiles/batch_paged_phi35.txt)
+       python tools/batch_rate.py --kvq [--parent-lib PATH] [model] [q8_0|q4_0]
+--kvq: a Q8 paged batch (lmrs_batch_create_paged_q8) against the f32 paged batch of the same build, by turns (kvq_main below)
+       (writes profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt)
        python tools/batch_rate.py --paged-prefill [model] [q8_0|q4_0]
 --paged-prefill: lmrs_batch_prefill of 16 .. 512 tokens on a wide batch, on paged batches (block attention over the page table from 16 rows on) and on the
 same paged batches with lmrs_batch_debug_prefill_table (every chunk through the table pass: the routing before), the forms by turns (paged_prefill_main below)
@@ -266,11 +269,213 @@ def paged_prefill_main(argv):
             f.write("\n".join(lines) + "\n")
 
 
+def kvq_child(image_path, kv, traced):
+    """--kvq's child, over a binding of its own (the parent commit's library has no Q8 entry points) on the library LMRS_LIB names: 64 slots of a paged pool
+    (kv: f32 | q8, page_len 64).  Timed: each slot prefilled, then us per pass of 64 rows at 100 positions, 64 and 16 rows at 1000 (device time of 64 greedy
+    steps a call, median of 3 after 1 warm-up) and a 512-token prefill (wall time, median of 5 after 1).  traced (under rocprofv3): slot 0 prefilled to 1000 and
+    forked into the others, then one call of 2 steps and one of 8 - the last 8 x n_layers launches of a kernel are its decode launches at 1000 positions."""
+    import ctypes as C
+    lib = C.CDLL(os.environ.get("LMRS_LIB", lmrs_amd.LIB_PATH))
+    vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
+    lib.lmrs_last_error.restype = C.c_char_p
+    lib.lmrs_create.argtypes = [vp, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    create = lib.lmrs_batch_create_paged_q8 if kv == "q8" else lib.lmrs_batch_create_paged
+    create.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
+    lib.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
+    lib.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
+    lib.lmrs_batch_generate_greedy.argtypes = [vp, u32, vp, vp, vp, u32, vp, C.POINTER(C.c_double)]
+    lib.lmrs_batch_destroy.argtypes = [vp]; lib.lmrs_batch_destroy.restype = None
+    lib.lmrs_destroy.argtypes = [vp]; lib.lmrs_destroy.restype = None
+
+    def chk(rc):
+        if rc:
+            raise RuntimeError(lib.lmrs_last_error().decode())
+
+    img = np.fromfile(image_path, np.uint8)
+    prompt = np.ascontiguousarray(np.fromfile(image_path + ".prompt", np.uint32))
+    h, used = vp(), sz()
+    chk(lib.lmrs_create(img.ctypes.data, img.size, 0, C.byref(h), C.byref(used)))
+
+    def greedy(b, n, depth, steps):
+        slot = np.arange(n, dtype=np.uint32); pos = np.full(n, depth, np.uint32); tok = np.full(n, prompt[depth], np.uint32)
+        ids = np.zeros((n, steps), np.uint32); sec = C.c_double()
+        chk(lib.lmrs_batch_generate_greedy(b, n, slot.ctypes.data, tok.ctypes.data, pos.ctypes.data, steps, ids.ctypes.data, C.byref(sec)))
+        return sec.value * 1e6 / steps, int(ids.astype(np.uint64).sum())
+
+    out = []
+    for depth, ns in ((1000, (64,)),) if traced else ((100, (64,)), (1000, (64, 16))):
+        b = vp()
+        chk(create(h, 64, 64, 64 * (-(-(depth + STEPS + 1) // 64)) + 64, C.byref(b)))
+        for i in range(64):
+            if traced and i:
+                chk(lib.lmrs_batch_fork(b, 0, i, depth))
+            else:
+                chk(lib.lmrs_batch_prefill(b, i, prompt.ctypes.data, depth, 0))
+        if traced:
+            greedy(b, 64, depth, 2); greedy(b, 64, depth, 8)
+        for n in () if traced else ns:
+            runs = [greedy(b, n, depth, STEPS) for _ in range(4)][1:]
+            out += [statistics.median(u for u, _ in runs), runs[-1][1]]
+        if depth == 1000 and not traced:
+            ms = []
+            for _ in range(6):
+                t0 = time.perf_counter(); chk(lib.lmrs_batch_prefill(b, 1, prompt.ctypes.data, 512, 0)); ms.append((time.perf_counter() - t0) * 1e3)
+            out.append(statistics.median(ms[1:]))
+        lib.lmrs_batch_destroy(b)
+    lib.lmrs_destroy(h)
+    print("KVQ " + " ".join(f"{x:.2f}" if isinstance(x, float) else str(x) for x in out), flush=True)
+
+
+def kvq_processes(say, img, model, prompt, parent):
+    """--kvq's two sections that need processes of their own: the parent commit's library, and the launches alone under a kernel trace"""
+    import csv, glob, shutil, subprocess, tempfile  # noqa: E401
+    me, L = os.path.abspath(__file__), S.CONFIGS[model].n_layers
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "model.lmrs")
+        img.tofile(path); np.ascontiguousarray(prompt, np.uint32).tofile(path + ".prompt")
+        say("the f32 pool on the PARENT commit's library against this build's two pools, a process per library, pool and turn, two turns (us per pass as above, "
+            "median of 3 calls after 1 warm-up; the 512-token prefill in ms)")
+        if not parent or not os.path.exists(parent):
+            say("  not run: no parent library given (--parent-lib PATH)")
+        else:
+            runs = (("parent f32", os.path.abspath(parent), "f32"), ("this f32", lmrs_amd.LIB_PATH, "f32"), ("this q8", lmrs_amd.LIB_PATH, "q8"))
+            res = {k: [] for k, _, _ in runs}
+            for turn in range(2):
+                for who, lib, kv in runs:
+                    r = subprocess.run([sys.executable, me, "--kvq-child", path, kv], env=dict(os.environ, LMRS_LIB=lib), capture_output=True, text=True, timeout=900)
+                    got = [l for l in r.stdout.splitlines() if l.startswith("KVQ ")]
+                    if r.returncode or not got:
+                        say(f"  {who}, turn {turn}: failed: {r.stderr.strip()[-300:]}")
+                        continue
+                    v = got[0].split()[1:]
+                    res[who].append(v)
+                    say(f"  turn {turn}  {who:10s}  64 x 100: {v[0]:>8s}   64 x 1000: {v[2]:>8s}   16 x 1000: {v[4]:>8s} us per pass   prefill 512: {v[6]:>6s} ms   token checksums {v[1]} {v[3]} {v[5]}")
+            if all(res.values()):
+                mean = lambda who, k: statistics.mean(float(v[k]) for v in res[who])
+                for k, what in ((0, "64 x 100"), (2, "64 x 1000"), (4, "16 x 1000"), (6, "prefill 512")):
+                    p = mean("parent f32", k)
+                    spread = max(float(v[k]) for v in res["parent f32"]) - min(float(v[k]) for v in res["parent f32"])
+                    say(f"  {what:11s}  parent f32 {p:8.2f} (its turns {spread:.2f} apart)   this f32 {mean('this f32', k):8.2f} ({mean('this f32', k) / p - 1:+.2%})   "
+                        f"this q8 {mean('this q8', k):8.2f} ({mean('this q8', k) / p - 1:+.2%}{'  ** A MISS **' if mean('this q8', k) > p + spread else ''})")
+                say(f"  f32 tokens equal between the libraries: {[res['parent f32'][0][k] for k in (1, 3, 5)] == [res['this f32'][0][k] for k in (1, 3, 5)]}")
+        say(f"the launches alone, 64 rows at 1000 - 1007 positions: rocprofv3 --kernel-trace over a process per pool (slot 0 prefilled and forked into 63 slots, a call "
+            f"of 2 steps, then one of 8); per kernel the last 8 x {L} launches: median (fastest .. slowest) us")
+        if not shutil.which("rocprofv3"):
+            say("  not run: rocprofv3 is not on the PATH")
+            return
+        for kv, kernels in (("f32", ("paged_scatter_kernel", "paged_attn_kernel")), ("q8", ("kvq_scatter_kernel", "kvq_attn_kernel"))):
+            with tempfile.TemporaryDirectory() as tt:
+                r = subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tt, "--", sys.executable, me, "--kvq-child", path, kv, "traced"],
+                                   capture_output=True, text=True, timeout=900)
+                traces = glob.glob(os.path.join(tt, "**", "*kernel_trace.csv"), recursive=True)
+                if r.returncode or not traces:
+                    say(f"  {kv}: failed: {r.stderr.strip()[-300:]}")
+                    continue
+                rows = sorted(csv.DictReader(open(traces[0])), key=lambda x: int(x["Start_Timestamp"]))
+                for kern in kernels:
+                    us = [(int(x["End_Timestamp"]) - int(x["Start_Timestamp"])) / 1e3 for x in rows if kern in x["Kernel_Name"]][-8 * L:]
+                    say(f"  {kern:22s} {len(us):4d} launches  {statistics.median(us):8.2f} ({min(us):.2f} .. {max(us):.2f}) us" if us else f"  {kern}: no launch in the trace")
+
+
+KVQ_OUT = {("llama-3.2-1b", S.Q8_0): "batch_kvq_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_kvq_gemma2b_q4.txt"}
+KVQ_MINIS = [("mini-llama", S.Q8_0), ("mini-phi", S.Q8_0), ("mini-llama3b", S.Q8_0), ("mini-gemma", S.Q4_0)]
+
+
+def kvq_main(argv):
+    """--kvq [--parent-lib PATH] [model] [q8_0|q4_0]: first, in processes of their own (kvq_processes), the f32 pool on the parent commit's library against this
+    build's two pools, and the scatter and attention launches alone under a kernel trace.  Then a Q8 paged batch (lmrs_batch_create_paged_q8) against the f32 paged batch of the same build, page_len 64, in one process, the
+    two pools by turns three times: us per pass of 64 decode rows at 100 and at 1000 positions and of 16 rows at 1000 (device time of 64 greedy steps a call,
+    median of 3 a turn), a 512-token lmrs_batch_prefill (wall time; the Q8 pool takes the table pass), the pools' bytes for 64 x 1024 positions (also for
+    the Phi-3.5 geometry, from its shapes), and - on the four mini models - the logits of the Q8 batch against the f32 paged batch after 130 positions."""
+    parent = os.environ.get("BATCH_RATE_PARENT_LIB")
+    if argv and argv[0] == "--parent-lib":
+        parent, argv = argv[1], argv[2:]
+    model = argv[0] if argv else "llama-3.2-1b"
+    qname = argv[1] if len(argv) > 1 else "q8_0"
+    qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True); lines.append(s)
+
+    img = S.build_image(model, qt, 1234)
+    say(f"python tools/batch_rate.py --kvq --parent-lib <the parent commit's liblmrs_hip.so> {model} {qname}")
+    say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
+    kvq_processes(say, img, model, S.prompt_tokens(model, 1001, 100), parent)
+    m = lmrs_amd.Transformer(img)
+    say("in one process, both pools this build's:")
+    forms = [("f32 pages", "f32"), ("q8 pages", "q8")]
+    prompt = S.prompt_tokens(model, 1001, 100)
+    say(f"us per pass of lmrs_batch_generate_greedy ({STEPS} greedy steps a call, device time of the steps): the two pools by turns, three turns, median of 3 calls "
+        f"after 1 warm-up a turn; per pool the median of its turns (fastest .. slowest turn)")
+    for depth, ns in ((100, (64,)), (1000, (64, 16))):
+        batches = {}
+        for name, kv in forms:
+            b = lmrs_amd.Batch(m, 64, page_len=64, n_pages=64 * (-(-(depth + STEPS + 1) // 64)), kv=kv)
+            for i in range(64):
+                b.prefill(i, prompt[:depth], 0)
+            batches[name] = b
+        for n in ns:
+            turns, ids = {name: [] for name, _ in forms}, {}
+            for _ in range(3):
+                for name, _kv in forms:
+                    b = batches[name]
+                    ids[name], us, _lo, _hi = timed(lambda: b.generate_greedy(list(range(n)), [int(prompt[depth])] * n, [depth] * n, STEPS, timing=True), reps=3, warm=1)
+                    turns[name].append(us / STEPS)
+            w = statistics.median(turns["f32 pages"])
+            for name, _kv in forms:
+                t = turns[name]
+                say(f"  {depth:4d} positions, n={n:2d}, {name:9s}  {statistics.median(t):8.1f} us per pass ({min(t):.1f} .. {max(t):.1f})   {statistics.median(t) / w - 1:+6.1%} against f32 pages")
+            say(f"      tokens equal between the pools (not expected: Q8 is another rule): {bool((ids['f32 pages'] == ids['q8 pages']).all())}")
+        if depth == 1000:
+            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): block attention on f32 pages, the table pass on Q8 pages")
+            for name, _kv in forms:
+                b = batches[name]
+
+                def call():
+                    t0 = time.perf_counter(); b.prefill(1, prompt[:512], 0)
+                    return None, time.perf_counter() - t0
+                _, us, lo, hi = timed(call, reps=5, warm=1)
+                say(f"  {name:9s}  {us / 1e3:8.2f} ms ({lo / 1e3:.2f} .. {hi / 1e3:.2f}); lmrs_batch_prefill_form(512): {b.prefill_form(512)}")
+        for b in batches.values():
+            b.close()
+    say("pool bytes for 64 x 1024 positions (1024 pages of 64 and the zero page): kv_format's page_bytes x 1025")
+    for name, kv in forms:
+        b = lmrs_amd.Batch(m, 64, page_len=64, n_pages=1024, kv=kv)
+        say(f"  {name:9s}  {b.kv_format()[2] * 1025 / 1e9:8.3f} GB  ({b.kv_format()[2]} bytes a page)")
+        b.close()
+    c = S.CONFIGS["phi-3.5"]
+    per = 2 * c.n_layers * 64 * c.n_kv_heads * (c.dim // c.n_heads)
+    say(f"  phi-3.5 geometry, from its shapes (not created here): f32 {per * 4 * 1025 / 1e9:.3f} GB, q8 {per * 9 // 8 * 1025 / 1e9:.3f} GB")
+    say("accuracy (reported, not a gate; synthetic weights): Q8 pages against f32 pages on the mini models, 6 slots prefilled to 130 positions, then one step: "
+        "largest |logit difference| over the 6 rows, rows whose argmax agrees")
+    for cfg, q in KVQ_MINIS:
+        mm = lmrs_amd.Transformer(S.build_image(cfg, q, 1234))
+        out = {}
+        for name, kv in forms:
+            b = lmrs_amd.Batch(mm, 6, page_len=64, n_pages=18, kv=kv)
+            for i in range(6):
+                b.prefill(i, S.prompt_tokens(cfg, 130, 700 + i), 0)
+            out[name] = b.forward(list(range(6)), [7 + i for i in range(6)], [130] * 6, logits=True)
+            b.close()
+        (a0, l0), (a1, l1) = out["f32 pages"], out["q8 pages"]
+        say(f"  {cfg:13s} max |dlogit| {float(np.abs(l0 - l1).max()):.5f} (largest |logit| {float(np.abs(l0).max()):.3f}); argmax agrees in {int((a0 == a1).sum())} of 6 rows")
+    name = KVQ_OUT.get((model, qt))
+    path = os.environ.get("BATCH_RATE_OUT") or (os.path.join(ROOT, "profiles", name) if name else None)
+    if path:
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--paged-prefill":
         return paged_prefill_main(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--wide":
         return wide_main(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--kvq-child":
+        return kvq_child(sys.argv[2], sys.argv[3], len(sys.argv) > 4)
+    if len(sys.argv) > 1 and sys.argv[1] == "--kvq":
+        return kvq_main(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--paged":
         return paged_main(sys.argv[2:])
     model = sys.argv[1] if len(sys.argv) > 1 else "llama-3.2-1b"
