@@ -290,10 +290,15 @@ int lmrs_batch_create_paged(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint3
  * Same arguments and refusals as lmrs_batch_create_paged, each message opening with this call's name.  The allocation is (n_pages + 1) * 2 * n_layers *
  * page_len * kv_dim * 9 / 8 bytes, all or nothing, the message gives the bytes: 1.125 bytes a cached value instead of 4.  Every batch call works as
  * documented for a paged batch.  lmrs_batch_fork between slots copies pages and rows as bytes; from LMRS_BATCH_CTX the context's f32 rows are quantised.
- * Out of scope: block attention over Q8 pages - every prompt chunk takes the table pass, lmrs_batch_prefill_form reports n_block = 0 and
- * lmrs_batch_debug_prefill_table is accepted and changes nothing; Q8 for contiguous and wide batches; Q8 for the context's own cache; Q4 pages.
+ * Prompts: a chunk of 256 rows or more of lmrs_batch_prefill / lmrs_batch_prefill_embeddings takes block attention over the int8 pages (64-query blocks;
+ * the key chunks and value tiles are read back on the way into LDS, each query's own key and value come from its f32 qkv row) under the f32 pool's other
+ * conditions - head sizes 64 / 96 / 128, Gemma's 256, at most 1 GiB of score slabs; a shorter chunk, ragged runs and decode rows take the table pass.  The
+ * bits are the same either way.  256 is a floor (four whole query blocks), not a measured crossover: 112 .. 255 rows are not measured.
+ * lmrs_batch_prefill_form reports these chunks in n_block; lmrs_batch_debug_prefill_table(b, 1) forces the table pass on a Q8 batch too, 0 restores the rule.
+ * Out of scope: Q8 for contiguous and wide batches; Q8 for the context's own cache; Q4 pages.
  * Measured against the f32 pool on the parent commit's library, 64 rows a pass: Llama-3.2-1B Q8_0 -16 % at 100 positions and -38 % at 1000, Gemma-2-2B
- * Q4_0 -4 % / -14 %; a 512-token prefill is about 1.5x / 1.6x slower (profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt). */
+ * Q4_0 -4 % / -14 % (profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt); prefill by block attention against the table pass and against the
+ * f32 pool: profiles/batch_kvq_prefill_*.txt, DESIGN.md 4.4.17. */
 int lmrs_batch_create_paged_q8(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
                                uint32_t n_pages /* >= 1 */, lmrs_batch** out);
 /* how a batch keeps its K/V: *format 0 f32 / 1 Q8, *group 0 / 32, *page_bytes a page's size - K and V blocks of every layer (0 on a batch that is not

@@ -554,7 +554,8 @@ class Batch:
     512 or 1024) from one pool of n_pages pages instead of holding a whole cache each: fork shares whole pages, a write un-shares the page it
     touches, release gives pages back.  Without release every result is bit for bit a wide batch's (lmrs_batch_create_paged).
     kv="q8" (a paged batch only): the pages hold every K and V row in 8 bits, groups of 32 with an f32 scale each - 1.125 bytes a value instead of 4; a
-    row attends to the earlier positions as read back, (float)q * scale, and to its own key and value in f32 (lmrs_batch_create_paged_q8)."""
+    row attends to the earlier positions as read back, (float)q * scale, and to its own key and value in f32 (lmrs_batch_create_paged_q8).  A prompt chunk of 256 rows or more takes block attention over the int8 pages,
+    a shorter one the table pass - the same bits either way; prefill_form tells which, debug_prefill_table(True) forces the table pass."""
 
     def __init__(self, model: Transformer, n_slots: int, wide: bool = False, *, page_len=None, n_pages=None, kv: str = "f32"):
         h = C.c_void_p()

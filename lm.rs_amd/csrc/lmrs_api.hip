@@ -1524,11 +1524,14 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
             // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
             const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
             if (form.kvq_bytes) {
-                // Q8 pages: the scatter quantises (and leaves the rotated k in the qkv row), the table pass reads the pages back; no block form
+                // Q8 pages: the scatter quantises (and leaves the rotated k in the qkv row), the attention reads the pages back - one slot's consecutive
+                // rows in 64-query blocks, anything else by the table pass; either takes a row's own key and value from its qkv row
                 const KvqView qv{form.pages.tab, form.pages.per_slot, form.pages.shift, form.pages.page_stride * 4, form.kvq_bytes};
-                if (form.block_pos0 >= 0) return fail("block attention over Q8 pages is not built");
                 HIP_OK(launch_kvq_scatter(qkv, k_cache, v_cache, c->rope, rv, qv, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
-                HIP_OK(launch_kvq_attention(t, rv, qv, m, form.max_T, c->stream));
+                if (form.block_pos0 >= 0) {
+                    if (prefill_slabs(c, attention_block_scratch_floats(t.n_heads, m, form.block_pos0 + m))) return -1;
+                    HIP_OK(launch_kvq_attention_block(t, qv, form.block_row, form.block_pos0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
+                } else HIP_OK(launch_kvq_attention(t, rv, qv, m, form.max_T, c->stream));
             } else {
             HIP_OK(launch_paged_scatter(qkv, k_cache, v_cache, c->rope, rv, form.pages, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
             if (form.block_pos0 >= 0) {
@@ -2087,6 +2090,10 @@ constexpr uint32_t kWideBatchMax = 64;         // a wide batch's slots, rows and
 // 1.06x on Gemma-2-2B Q4_0 (up to 47 rows the table pass also runs the weight-streaming GEMMs), 80 rows are within the turns' spread of it on both, 96 rows 0.93x
 // on Llama but 1.003x, just outside the spread, on Gemma; from 112 rows on both are faster outside the spread (0.90x / 0.96x)
 constexpr uint32_t kPagedBlockMin = 112;
+// ... and of a Q8 paged batch's (block_kvq_*_kernel, lmrs_kvq.inc).  A FLOOR, not a measured crossover: tests/test_batch_kvq.py pins a 200-row chunk of a Q8
+// batch to the table pass, so the rule starts at the next whole number of 64-query blocks.  The Q8 table pass is faster than the f32 one, so the crossover
+// lies above 112 anyway; whether block attention would win between 112 and 255 rows is not measured
+constexpr uint32_t kKvqBlockMin = 256;
 struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
 // The buffers of a sampled call (sample_set_alloc; rows != 0: the set stands, for that many rows): the rows' sampler table and its pinned source,
 // launch_sample_rows' scratch, the result blocks ([rows][vocab + 1] words: {token, n0}, then the candidates) and the pinned copy of their heads (head_words each)
@@ -3258,9 +3265,9 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     return 0;
 }
 // A prompt chunk of a paged batch - m rows of one slot from p0 on - takes block attention over the page table by prefill_attention's rule (and from
-// kPagedBlockMin rows on); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it
+// kPagedBlockMin rows on; Q8 pages: kKvqBlockMin, 4.4.17); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it
 static bool paged_block_route(const lmrs_batch* b, uint32_t m, uint32_t p0) {
-    return !b->kvq_bytes && !b->pf_table && m >= kPagedBlockMin && prefill_block_route(b->c, (int)m, (int)p0);     // (Q8 pages: the table pass only)
+    return !b->pf_table && m >= (b->kvq_bytes ? kKvqBlockMin : kPagedBlockMin) && prefill_block_route(b->c, (int)m, (int)p0);
 }
 extern "C" int lmrs_batch_prefill_form(const lmrs_batch* b, size_t n, uint32_t start_pos, uint32_t* n_chunks, uint32_t* n_block) {
     const std::string what = "lmrs_batch_prefill_form: ";
@@ -3308,7 +3315,7 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
                 if (record_rows(b, b->runs->pos, b->runs->tok, m)) return -1;                // (the table pass records in runs_pass)
                 // the GEMM forms of a contiguous batch's chunk (m >= 16: never the skinny ones), the qkv block and the scatter of the table pass
                 PassForm form; form.runs = b->runs_view(); form.qkv = b->runs_qkv; form.k_cache = b->kv; form.v_cache = b->kv + b->page_floats;
-                form.pages = b->page_view(); form.block_pos0 = (int)p0; form.block_row = slot;
+                form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; form.block_pos0 = (int)p0; form.block_row = slot;
                 if ((embeddings ? source_rows(c, form.runs.tok, b->embed_stage, (int)m) : token_rows(c, form.runs.tok, (int)m)) || prefill_pass(c, form, (int)m, (int)p0)) return -1;
                 if (residual) HIP_OK(hipMemcpyAsync(residual + i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));     // (position order already)
                 return 0;

@@ -309,6 +309,9 @@ struct KvqView { const uint32_t* tab; int per_slot; int shift; size_t page_bytes
 hipError_t launch_kvq_scatter(float* qkv, float* k_pool, float* v_pool, const float* rope, RowView rows, KvqView pv, int n_heads, int n_kv_heads, int hs,
                               int layer, int n_rows, hipStream_t s);
 hipError_t launch_kvq_attention(const AttnArgs& a, RowView rows, KvqView pv, int n_rows, int max_T, hipStream_t s);
+// launch_paged_attention_block over Q8 pages: n_tok consecutive rows of ONE slot (page row table_row) from pos0 on, behind launch_kvq_scatter over the same rows
+// in position order.  a.q: the qkv block - the launches also read each row's own key and value from it; the output is launch_kvq_attention's, bit for bit
+hipError_t launch_kvq_attention_block(const AttnArgs& a, KvqView pv, unsigned table_row, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s);
 // rows p0 .. p0 + n_rows - 1 of a contiguous f32 cache (the context's layout, seq_len positions) quantised into in-page positions pin0 .. of ONE page
 hipError_t launch_kvq_import(const float* k_src, const float* v_src, int seq_len, int p0, float* k_page, float* v_page, size_t q_bytes, int n_layers, int kv, int page_len,
                              int pin0, int n_rows, hipStream_t s);

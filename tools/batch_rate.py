@@ -18,8 +18,10 @@ lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: 
        (writes profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt)
        python tools/batch_rate.py --paged-prefill [model] [q8_0|q4_0]
 --paged-prefill: lmrs_batch_prefill of 16 .. 512 tokens on a wide batch, on paged batches (block attention over the page table from 16 rows on) and on the
-same paged batches with lmrs_batch_debug_prefill_table (every chunk through the table pass: the routing before), the forms by turns (paged_prefill_main below)
-       (writes profiles/batch_paged_prefill_llama1b.txt, profiles/batch_paged_prefill_gemma2b_q4.txt)"""
+same paged batches with lmrs_batch_debug_prefill_table (every chunk through the table pass: the routing before), and on a Q8 paged batch under the library's
+rule and forced to the table pass, the forms by turns (paged_prefill_main below)
+       (writes profiles/batch_kvq_prefill_llama1b.txt, profiles/batch_kvq_prefill_gemma2b_q4.txt; the five f32 forms alone were recorded in
+       profiles/batch_paged_prefill_*.txt)"""
 import os
 import statistics
 import sys
@@ -202,15 +204,16 @@ def paged_main(argv):
     finish()
 
 
-PREFILL_OUT = {("llama-3.2-1b", S.Q8_0): "batch_paged_prefill_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_paged_prefill_gemma2b_q4.txt"}
+PREFILL_OUT = {("llama-3.2-1b", S.Q8_0): "batch_kvq_prefill_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_kvq_prefill_gemma2b_q4.txt"}
 PREFILL_CASES = [(16, 0), (32, 0), (64, 0), (80, 0), (96, 0), (112, 0), (128, 0), (256, 0), (512, 0), (512, 512)]   # (tokens, start position); 80 .. 112: around the crossover
 
 
 def paged_prefill_main(argv):
-    """--paged-prefill [model] [q8_0|q4_0]: host wall time of the synchronous lmrs_batch_prefill call into slot 0, in one process, five forms by turns,
+    """--paged-prefill [model] [q8_0|q4_0]: host wall time of the synchronous lmrs_batch_prefill call into slot 0, in one process, seven forms by turns,
     three turns, median of 5 calls after 1 warm-up a turn: (a) the wide batch; (b) paged batches of page_len 64 and 256 under the library's routing; (c) the
-    same two with lmrs_batch_debug_prefill_table(1) - every chunk through the table pass, one workgroup per (head, row).  Per form and length the median of
-    its turns (fastest .. slowest turn), lmrs_batch_prefill_form's answer, and whether the forms leave the same last K row."""
+    same two with lmrs_batch_debug_prefill_table(1) - every chunk through the table pass, one workgroup per (head, row); (d) a Q8 paged batch of page_len 64
+    under the library's rule (block attention over int8 pages from 256 rows on) and (e) the same forced to the table pass.  Per form and length the median
+    of its turns (fastest .. slowest turn), lmrs_batch_prefill_form's answer, and whether the forms of one K/V format leave the same last K row."""
     model = argv[0] if argv else "llama-3.2-1b"
     qname = argv[1] if len(argv) > 1 else "q8_0"
     qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
@@ -223,13 +226,14 @@ def paged_prefill_main(argv):
     m = lmrs_amd.Transformer(img)
     say(f"python tools/batch_rate.py --paged-prefill {model} {qname}")
     say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
-    say("lmrs_batch_prefill into slot 0, host wall time of the synchronous call: five forms by turns, three turns, median of 5 calls after 1 warm-up a turn; "
+    say("lmrs_batch_prefill into slot 0, host wall time of the synchronous call: seven forms by turns, three turns, median of 5 calls after 1 warm-up a turn; "
         "per form the median of its turns (fastest .. slowest turn); form = lmrs_batch_prefill_form's (chunks, of them block attention)")
-    forms = [("wide", None, False), ("paged 64", 64, False), ("paged 256", 256, False), ("paged 64 table", 64, True), ("paged 256 table", 256, True)]
+    forms = [("wide", None, False), ("paged 64", 64, False), ("paged 256", 256, False), ("paged 64 table", 64, True), ("paged 256 table", 256, True),
+             ("q8 64", 64, False), ("q8 64 table", 64, True)]
     prompt = S.prompt_tokens(model, 1024, 100)
     batches = {}
     for name, pl, table in forms:
-        b = lmrs_amd.Batch(m, 2, wide=True) if pl is None else lmrs_amd.Batch(m, 2, page_len=pl, n_pages=2 * (1024 // pl))
+        b = lmrs_amd.Batch(m, 2, wide=True) if pl is None else lmrs_amd.Batch(m, 2, page_len=pl, n_pages=2 * (1024 // pl), kv="q8" if name.startswith("q8") else "f32")
         if table:
             b.debug_prefill_table(True)
         batches[name] = b
@@ -258,8 +262,15 @@ def paged_prefill_main(argv):
             if pl is not None and not table:
                 old = turns[name + " table"]
                 note += f"   {statistics.median(t) / statistics.median(old):5.2f}x its table pass; slowest turn below the table pass's fastest: {max(t) < min(old)}"
+                if name.startswith("q8"):
+                    note += f"; {statistics.median(t) / statistics.median(turns['paged 64']):5.2f}x the f32 pages"
+                if name.startswith("q8") and batches[name].prefill_form(n, start)[1]:
+                    # the condition of DESIGN.md 4.4.17: faster than the table pass by more than the larger turn-to-turn spread of the two forms
+                    gap, spread = statistics.median(old) - statistics.median(t), max(max(t) - min(t), max(old) - min(old))
+                    note += f"; gap {gap:.3f} ms against spread {spread:.3f} ms: {'wins' if gap > spread else 'NO WIN'}"
             say(f"  {n:3d} tokens at {start:3d}, {name:15s} form {batches[name].prefill_form(n, start)}  {statistics.median(t):8.3f} ms ({min(t):.3f} .. {max(t):.3f})   {note}")
-        say(f"      the five forms leave the same last K row: {all((last[name] == last['wide']).all() for name, _, _ in forms)}")
+        same = all((last[name] == last["q8 64" if name.startswith("q8") else "wide"]).all() for name, _, _ in forms)
+        say(f"      the f32 forms leave the same last K row, and so do the Q8 forms: {same}")
     for b in batches.values():
         b.close()
     name = PREFILL_OUT.get((model, qt))
