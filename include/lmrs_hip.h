@@ -295,15 +295,38 @@ int lmrs_batch_create_paged(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint3
  * conditions - head sizes 64 / 96 / 128, Gemma's 256, at most 1 GiB of score slabs; a shorter chunk, ragged runs and decode rows take the table pass.  The
  * bits are the same either way.  256 is a floor (four whole query blocks), not a measured crossover: 112 .. 255 rows are not measured.
  * lmrs_batch_prefill_form reports these chunks in n_block; lmrs_batch_debug_prefill_table(b, 1) forces the table pass on a Q8 batch too, 0 restores the rule.
- * Out of scope: Q8 for contiguous and wide batches; Q8 for the context's own cache; Q4 pages.
+ * Out of scope: Q8 for contiguous and wide batches; Q8 for the context's own cache.  (Q4 pages: lmrs_batch_create_paged_q4 below.)
  * Measured against the f32 pool on the parent commit's library, 64 rows a pass: Llama-3.2-1B Q8_0 -16 % at 100 positions and -38 % at 1000, Gemma-2-2B
  * Q4_0 -4 % / -14 % (profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt); prefill by block attention against the table pass and against the
  * f32 pool: profiles/batch_kvq_prefill_*.txt, DESIGN.md 4.4.17. */
 int lmrs_batch_create_paged_q8(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
                                uint32_t n_pages /* >= 1 */, lmrs_batch** out);
-/* how a batch keeps its K/V: *format 0 f32 / 1 Q8, *group 0 / 32, *page_bytes a page's size - K and V blocks of every layer (0 on a batch that is not
- * paged); a paged batch's pool is page_bytes * (n_pages + 1).  Any batch. */
-int lmrs_batch_kv_format(const lmrs_batch* b, int* format /* 0 f32, 1 Q8 */, uint32_t* group /* 0 or 32 */, size_t* page_bytes);
+/* ---- paged K/V in 4 bits (extensions, no reference counterpart): the same pool with every K row (after RoPE) and every V row stored in groups of 32
+ * consecutive elements of the kv_dim row, each group by the reference's Q4_0 rule (quantization.rs:69-95 at a group of 32), operation for operation:
+ * scale = max|x| / -8.0f in f32 - NEGATIVE, as the reference has it; per element x / scale (a division), + 8.0f (its own rounding), round half away from
+ * zero, then Rust's saturating `as u8` (below 0 -> 0, NaN -> 0) and clamp(0, 15); elements 2i and 2i + 1 share a byte, low nibble first.  A cached value
+ * reads back as (float)(nibble - 8) * scale, one rounding.  What follows: an all-zero group has scale -0.0, every nibble 0, and reads back as +0.0; a
+ * zero inside a non-zero group is nibble 8 and reads back as -0.0; +max reads back exactly, -max as -7/8 max; a group whose maximum is denormal has scale
+ * -0.0 and reads back as +-0.0; maxima of 3e38 stay finite.  The attention contract is the Q8 pool's: a row at position p attends to keys and values
+ * 0 .. p-1 as read back and to its OWN key and value in f32; rows of one run see the earlier rows of their run read back; everything else is the table
+ * pass, operation for operation - so every output is bit for bit the sequential forward's with the K and V rows of pos in every layer replaced by their Q4
+ * round trip after each forward(token, pos).  lmrs_batch_debug_kv returns the row as read back.  A position nobody wrote reads as zero as a NUMERIC
+ * statement: a page of all-zero bytes (the zero page, a page cleared at its claim) is nibble 0 and scale +0.0, which reads back as -0.0 - equal to zero,
+ * not the bits of +0.0.
+ * Same arguments and refusals as lmrs_batch_create_paged_q8, each message opening with this call's name.  The allocation is (n_pages + 1) * 2 * n_layers *
+ * page_len * kv_dim * 5 / 8 bytes, all or nothing: 20 bytes a group of 32, 0.625 bytes a cached value (Llama-3.2-1B, 1024 pages of 64: 671 744 000 bytes
+ * where Q8 takes 1 209 139 200).  Every batch call works as documented for a paged batch; forks as for the Q8 pool.
+ * Prompts: EVERY chunk takes the table pass - there is no block attention over Q4 pages; lmrs_batch_prefill_form reports n_block = 0 for any length.
+ * Out of scope: block attention over Q4 pages; Q4 for contiguous and wide batches or the context's own cache; mixed K / V formats.
+ * Measured: profiles/batch_kv4_*.txt, DESIGN.md 4.4.18.
+ * lmrs_op_kv4_round_trip: n caller values (host memory, n a multiple of 32 in 32 .. 2^24, every aligned 32 a group) through the scatter kernel's quantiser
+ * and the attention kernel's read-back - the device functions those kernels call - into out[n]. */
+int lmrs_batch_create_paged_q4(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,
+                               uint32_t n_pages /* >= 1 */, lmrs_batch** out);
+int lmrs_op_kv4_round_trip(int device, const float* x, size_t n, float* out);
+/* how a batch keeps its K/V: *format 0 f32 / 1 Q8 / 2 Q4, *group 0 / 32, *page_bytes a page's size - K and V blocks of every layer (0 on a batch that
+ * is not paged); a paged batch's pool is page_bytes * (n_pages + 1).  Any batch. */
+int lmrs_batch_kv_format(const lmrs_batch* b, int* format /* 0 f32, 1 Q8, 2 Q4 */, uint32_t* group /* 0 or 32 */, size_t* page_bytes);
 /* the pool: its page length, its pages (the zero page not counted) and how many of them nobody holds.  Refused on a batch that is not paged. */
 int lmrs_batch_pages(const lmrs_batch* b, uint32_t* page_len, uint32_t* n_pages, uint32_t* n_free);
 /* the pages a slot holds, and how many of them have more than one holder.  Refused on a batch that is not paged, and for a slot >= n_slots. */

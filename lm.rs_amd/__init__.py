@@ -32,7 +32,7 @@ EXPORTS = [
     "lmrs_batch_debug_kv", "lmrs_batch_forward_runs", "lmrs_batch_forward_sample", "lmrs_batch_create_wide", "lmrs_batch_width", "lmrs_debug_gemm_wide", "lmrs_op_sample_rows", "lmrs_sampler_topp_sorted_pairs", "lmrs_bench_sample_rows",
     "lmrs_batch_forward_runs_sample", "lmrs_op_sort_candidates",
     "lmrs_batch_prefill_embeddings", "lmrs_batch_forward_runs_embed", "lmrs_batch_forward_runs_embed_sample",
-    "lmrs_batch_create_paged", "lmrs_batch_create_paged_q8", "lmrs_batch_kv_format", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
+    "lmrs_batch_create_paged", "lmrs_batch_create_paged_q8", "lmrs_batch_create_paged_q4", "lmrs_op_kv4_round_trip", "lmrs_batch_kv_format", "lmrs_batch_pages", "lmrs_batch_slot_pages", "lmrs_batch_release", "lmrs_batch_prefill_form", "lmrs_batch_debug_prefill_table",
     "lmrs_batch_set_masks", "lmrs_batch_clear_masks", "lmrs_batch_mask_info",
     "lmrs_batch_set_history", "lmrs_batch_history", "lmrs_batch_set_penalties", "lmrs_batch_clear_penalties", "lmrs_batch_penalty_info",
     "lmrs_batch_generate",
@@ -120,6 +120,8 @@ def lib():
         L.lmrs_batch_create_paged.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
         L.lmrs_batch_pages.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_create_paged_q8.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
+        L.lmrs_batch_create_paged_q4.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
+        L.lmrs_op_kv4_round_trip.argtypes = [C.c_int, vp, sz, vp]
         L.lmrs_batch_kv_format.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u32), C.POINTER(C.c_size_t)]
         L.lmrs_batch_slot_pages.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_release.argtypes = [vp, u32, u32]
@@ -555,29 +557,32 @@ class Batch:
     touches, release gives pages back.  Without release every result is bit for bit a wide batch's (lmrs_batch_create_paged).
     kv="q8" (a paged batch only): the pages hold every K and V row in 8 bits, groups of 32 with an f32 scale each - 1.125 bytes a value instead of 4; a
     row attends to the earlier positions as read back, (float)q * scale, and to its own key and value in f32 (lmrs_batch_create_paged_q8).  A prompt chunk of 256 rows or more takes block attention over the int8 pages,
-    a shorter one the table pass - the same bits either way; prefill_form tells which, debug_prefill_table(True) forces the table pass."""
+    a shorter one the table pass - the same bits either way; prefill_form tells which, debug_prefill_table(True) forces the table pass.
+    kv="q4" (a paged batch only): the pages hold every K and V row in 4 bits by the reference's Q4_0 rule at a group of 32 - 0.625 bytes a value; a row attends
+    to the earlier positions as read back, (float)(nibble - 8) * scale with the rule's negative scale, and to its own key and value in f32
+    (lmrs_batch_create_paged_q4).  Every prompt chunk takes the table pass; a position nobody wrote reads as -0.0."""
 
     def __init__(self, model: Transformer, n_slots: int, wide: bool = False, *, page_len=None, n_pages=None, kv: str = "f32"):
         h = C.c_void_p()
         if (page_len is None) != (n_pages is None):
             raise LmrsError("page_len and n_pages must be given together")
-        if kv not in ("f32", "q8"):
-            raise LmrsError(f"kv = {kv!r} is neither 'f32' nor 'q8'")
-        if kv == "q8" and page_len is None:
-            raise LmrsError("kv='q8' needs a paged batch: give page_len and n_pages")
+        if kv not in ("f32", "q8", "q4"):
+            raise LmrsError(f"kv = {kv!r} is none of 'f32', 'q8', 'q4'")
+        if kv != "f32" and page_len is None:
+            raise LmrsError(f"kv={kv!r} needs a paged batch: give page_len and n_pages")
         if page_len is not None:
-            create = lib().lmrs_batch_create_paged_q8 if kv == "q8" else lib().lmrs_batch_create_paged
+            create = {"f32": lib().lmrs_batch_create_paged, "q8": lib().lmrs_batch_create_paged_q8, "q4": lib().lmrs_batch_create_paged_q4}[kv]
             _chk(create(model._h, n_slots, page_len, n_pages, C.byref(h)))
         else:
             _chk((lib().lmrs_batch_create_wide if wide else lib().lmrs_batch_create)(model._h, n_slots, C.byref(h)))
         self._h, self.model, self.n_slots = h, model, n_slots
 
     def kv_format(self):
-        """How the batch keeps K/V -> (name, group, page_bytes): ("f32", 0, ..) or ("q8", 32, ..); page_bytes is a page's size, K and V blocks of every
+        """How the batch keeps K/V -> (name, group, page_bytes): ("f32", 0, ..), ("q8", 32, ..) or ("q4", 32, ..); page_bytes is a page's size, K and V blocks of every
         layer together (0 on a batch that is not paged) - the pool is page_bytes * (n_pages + 1) (lmrs_batch_kv_format)"""
         f, g, n = C.c_int(), C.c_uint32(), C.c_size_t()
         _chk(lib().lmrs_batch_kv_format(self._h, C.byref(f), C.byref(g), C.byref(n)))
-        return ("q8" if f.value else "f32"), g.value, n.value
+        return ("f32", "q8", "q4")[f.value], g.value, n.value
 
     def pages(self):
         """A paged batch's pool -> (page_len, n_pages, n_free) (lmrs_batch_pages)"""
@@ -1380,6 +1385,15 @@ def min_p_gap(min_p: float, temperature: float = 1.0) -> np.float32:
     if min_p <= 0.0:
         return np.float32(np.inf)
     return np.float32(-np.float64(temperature) * np.log(np.float64(min_p)) + 0.0)
+
+
+def kv4_round_trip(x, device: int = 0) -> np.ndarray:
+    """x (a multiple of 32 values, every aligned 32 a group) through the Q4 K/V format's quantiser and read-back, the device functions the scatter and the
+    attention kernel call (lmrs_op_kv4_round_trip)"""
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    out = np.empty_like(x)
+    _chk(lib().lmrs_op_kv4_round_trip(device, _p(x), x.size, _p(out)))
+    return out
 
 
 def filter_rows(rows, top_k=0, min_gap=float("inf"), n=None, device: int = 0) -> np.ndarray:

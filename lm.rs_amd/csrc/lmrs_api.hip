@@ -207,7 +207,7 @@ struct AutoView { const AutoRow* of = nullptr; const AutoRow* h_of = nullptr; co
 // top_k / min_gap in the order the classifier sees the rows, slot -1 for none; h_of is its pinned source, as with the masks
 struct FilterView { const FilterRow* of = nullptr; const FilterRow* h_of = nullptr; };
 struct PenaltyView { const uint32_t* hist = nullptr; int seq_len = 0; const int* pos = nullptr; const PenaltyRow* of = nullptr; const PenaltyRow* h_of = nullptr; int max_n = 0; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; size_t kvq_bytes = 0; };   // kvq_bytes != 0: the pool holds Q8 pages (lmrs_kvq.inc), that many int8 bytes a K / V block; pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; size_t kvq_bytes = 0; bool kv4 = false; };   // kv4: the pool holds Q4 pages (lmrs_kv4.inc), kvq_bytes values a K / V block, no block attention; else kvq_bytes != 0: the pool holds Q8 pages (lmrs_kvq.inc), that many int8 bytes a K / V block; pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1523,7 +1523,13 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
         if (form.pages.tab) {
             // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
             const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
-            if (form.kvq_bytes) {
+            if (form.kv4) {
+                // Q4 pages: the quantising scatter and the table pass that reads the nibbles back, for every row of every pass
+                if (form.block_pos0 >= 0) return fail("prefill_layers: no block attention over Q4 pages");
+                const KvqView qv{form.pages.tab, form.pages.per_slot, form.pages.shift, form.pages.page_stride * 4, form.kvq_bytes / 2};
+                HIP_OK(launch_kv4_scatter(qkv, k_cache, v_cache, c->rope, rv, qv, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
+                HIP_OK(launch_kv4_attention(t, rv, qv, m, form.max_T, c->stream));
+            } else if (form.kvq_bytes) {
                 // Q8 pages: the scatter quantises (and leaves the rotated k in the qkv row), the attention reads the pages back - one slot's consecutive
                 // rows in 64-query blocks, anything else by the table pass; either takes a row's own key and value from its qkv row
                 const KvqView qv{form.pages.tab, form.pages.per_slot, form.pages.shift, form.pages.page_stride * 4, form.kvq_bytes};
@@ -2121,7 +2127,9 @@ struct lmrs_batch {
     std::unique_ptr<PagePool> pool; uint32_t page_len = 0; size_t page_floats = 0;
     // Q8 pages (lmrs_batch_create_paged_q8; lmrs_kvq.inc): kvq_bytes = n_layers * page_len * kv_dim, the int8 bytes of a page's K (or V) block, its f32 scales
     // behind them - page_floats is then that block's size in floats, 9 / 32 of the f32 one, and every page address and size below follows from it
-    size_t kvq_bytes = 0;
+    // Q4 pages (lmrs_batch_create_paged_q4; lmrs_kv4.inc): kv4 is set, kvq_bytes the same count - the VALUES of a block: kvq_bytes / 2 bytes of nibbles, the
+    // f32 scales behind them - and page_floats 5 / 32 of the f32 one
+    size_t kvq_bytes = 0; bool kv4 = false;
     DevBuf<uint32_t> ptab; PinBuf<uint32_t> h_ptab;
     bool pf_table = false;                              // lmrs_batch_debug_prefill_table: every prompt chunk takes the table pass
     // allowed-token masks (lmrs_batch_set_masks; made at the first call, mask_words != 0 from then on): the device block [n_slots][mask_words] and its pinned mirror,
@@ -2220,8 +2228,8 @@ extern "C" void lmrs_batch_destroy(lmrs_batch* b) {
 
 // lmrs_batch_create / lmrs_batch_create_wide: `name` opens every message, width is the batch's row and slot limit
 // page_len > 0 (lmrs_batch_create_paged): the slots draw pages of page_len positions from one pool of n_pages pages (+ the zero page) instead of a cache each
-// q8: the pool's pages hold int8 values and f32 scales per 32 (lmrs_batch_create_paged_q8)
-static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width, uint32_t page_len = 0, uint32_t n_pages = 0, bool q8 = false) {
+// kv_format 1: the pool's pages hold int8 values and f32 scales per 32 (lmrs_batch_create_paged_q8); 2: nibbles and f32 scales per 32 (lmrs_batch_create_paged_q4)
+static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const std::string& name, uint32_t width, uint32_t page_len = 0, uint32_t n_pages = 0, int kv_format = 0) {
     if (!c || !out) return fail("NULL argument");
     *out = nullptr;
     if (n_slots < 1 || n_slots > width) return fail(name + ": n_slots = " + std::to_string(n_slots) + " is outside 1 .. " + std::to_string(width));
@@ -2240,7 +2248,7 @@ static int batch_create(lmrs_ctx* c, uint32_t n_slots, lmrs_batch** out, const s
     lmrs_batch* b = new lmrs_batch;
     b->c = c; b->n_slots = n_slots; b->width = width; b->slot_floats = (size_t)a.n_layers * a.seq_len * c->kv_dim;
     b->page_len = page_len; b->page_floats = (size_t)a.n_layers * page_len * c->kv_dim;
-    if (q8) { b->kvq_bytes = b->page_floats; b->page_floats = b->kvq_bytes * 9 / 32; }          // (page_len * kv_dim is a multiple of 64 * 32)
+    if (kv_format) { b->kvq_bytes = b->page_floats; b->kv4 = kv_format == 2; b->page_floats = b->kvq_bytes * (b->kv4 ? 5 : 9) / 32; }          // (page_len * kv_dim is a multiple of 64 * 32)
     const size_t bytes = page_len ? ((size_t)n_pages + 1) * 2 * b->page_floats * 4 : (size_t)n_slots * 2 * b->slot_floats * 4, T = a.seq_len;
     if (!b->kv.alloc(bytes / 4)) {                                                                       // all or nothing: one allocation
         (void)hipGetLastError(); lmrs_batch_destroy(b);
@@ -2662,11 +2670,21 @@ extern "C" int lmrs_batch_create_paged_q8(lmrs_ctx* c, uint32_t n_slots, uint32_
         return fail(name + ": page_len = " + std::to_string(page_len) + " is none of 64, 128, 256, 512, 1024");
     if (n_pages == 0) return fail(name + ": n_pages is 0");
     if (c && c->args.head_size % 32) return fail(name + ": head_size = " + std::to_string(c->args.head_size) + " is not a multiple of the group of 32");
-    return batch_create(c, n_slots, out, name, kWideBatchMax, page_len, n_pages, true);
+    return batch_create(c, n_slots, out, name, kWideBatchMax, page_len, n_pages, 1);
+}
+// ... and in 4 bits (lmrs_kv4.inc: the rule, the layout): same arguments, same refusals, 5 / 32 of the bytes
+extern "C" int lmrs_batch_create_paged_q4(lmrs_ctx* c, uint32_t n_slots, uint32_t page_len, uint32_t n_pages, lmrs_batch** out) {
+    const std::string name = "lmrs_batch_create_paged_q4";
+    if (out) *out = nullptr;
+    if (page_len != 64 && page_len != 128 && page_len != 256 && page_len != 512 && page_len != 1024)
+        return fail(name + ": page_len = " + std::to_string(page_len) + " is none of 64, 128, 256, 512, 1024");
+    if (n_pages == 0) return fail(name + ": n_pages is 0");
+    if (c && c->args.head_size % 32) return fail(name + ": head_size = " + std::to_string(c->args.head_size) + " is not a multiple of the group of 32");
+    return batch_create(c, n_slots, out, name, kWideBatchMax, page_len, n_pages, 2);
 }
 extern "C" int lmrs_batch_kv_format(const lmrs_batch* b, int* format, uint32_t* group, size_t* page_bytes) {
     if (!b || !format || !group || !page_bytes) return fail("lmrs_batch_kv_format: NULL argument");
-    *format = b->kvq_bytes ? 1 : 0; *group = b->kvq_bytes ? 32u : 0u;
+    *format = b->kv4 ? 2 : b->kvq_bytes ? 1 : 0; *group = b->kvq_bytes ? 32u : 0u;
     *page_bytes = b->pool ? 2 * b->page_floats * 4 : 0;
     return 0;
 }
@@ -2776,6 +2794,17 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
         // lie ss positions apart (another page: page_len; the context's cache: seq_len)
         const size_t PL = b->page_len;
         auto copy_rows = [&](uint32_t page, size_t r0, size_t r1, const float* ks, const float* vs, size_t ss) -> int {
+            if (b->kv4) {
+                // Q4 pages, as bytes: K words [n_layers kv / 32][PL][16] and scales [n_layers kv / 32][PL], V rows [n_layers kv heads][PL][hs / 2] and scales [..][hs / 32]
+                const char *kq = reinterpret_cast<const char*>(ks), *vq = reinterpret_cast<const char*>(vs);
+                char *dk = reinterpret_cast<char*>(b->page_k(page)), *dv = reinterpret_cast<char*>(b->page_v(page));
+                const size_t Q = b->kvq_bytes / 2, n = r1 - r0, G = (size_t)a.n_layers * kv / 32, H = (size_t)a.n_layers * a.n_kv_heads, hs = a.head_size;
+                HIP_OK(hipMemcpy2DAsync(dk + r0 * 16, PL * 16, kq, ss * 16, n * 16, G, hipMemcpyDeviceToDevice, c->stream));
+                HIP_OK(hipMemcpy2DAsync(dk + Q + r0 * 4, PL * 4, kq + Q, ss * 4, n * 4, G, hipMemcpyDeviceToDevice, c->stream));
+                HIP_OK(hipMemcpy2DAsync(dv + r0 * hs / 2, PL * hs / 2, vq, ss * hs / 2, n * hs / 2, H, hipMemcpyDeviceToDevice, c->stream));
+                HIP_OK(hipMemcpy2DAsync(dv + Q + r0 * hs / 8, PL * hs / 8, vq + Q, ss * hs / 8, n * hs / 8, H, hipMemcpyDeviceToDevice, c->stream));
+                return 0;
+            }
             if (b->kvq_bytes) {
                 // Q8 pages, as bytes: K words [n_layers kv / 16][PL][16] and scales [n_layers kv / 32][PL], V rows [n_layers][PL][kv] and scales [..][kv / 32]
                 const char *kq = reinterpret_cast<const char*>(ks), *vq = reinterpret_cast<const char*>(vs);
@@ -2797,6 +2826,10 @@ extern "C" int lmrs_batch_fork(lmrs_batch* b, uint32_t src_slot, uint32_t dst_sl
             for (size_t p0 = 0; p0 < n_pos; p0 += PL) {
                 const size_t p1 = std::min<size_t>(n_pos, p0 + PL);
                 const uint32_t page = b->pool->row(dst_slot)[p0 / PL];
+                if (b->kv4) {                                // the context's f32 rows through the Q4 scatter's quantiser
+                    if (launch_kv4_import(c->k_cache, c->v_cache, (int)S, (int)p0, b->page_k(page), b->page_v(page), b->kvq_bytes / 2, (int)a.n_layers, (int)kv, (int)a.head_size,
+                                          (int)PL, 0, (int)(p1 - p0), c->stream) != hipSuccess) { fail("lmrs_batch_fork: the quantising copy failed to launch"); return batch_failed(c); }
+                } else
                 if (b->kvq_bytes) {                          // the context's f32 rows through the scatter's quantiser
                     if (launch_kvq_import(c->k_cache, c->v_cache, (int)S, (int)p0, b->page_k(page), b->page_v(page), b->kvq_bytes, (int)a.n_layers, (int)kv, (int)PL, 0,
                                           (int)(p1 - p0), c->stream) != hipSuccess) { fail("lmrs_batch_fork: the quantising copy failed to launch"); return batch_failed(c); }
@@ -2901,7 +2934,7 @@ static int source_rows(lmrs_ctx* c, const uint32_t* src, const float* staged, in
 static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to, const float* staged = nullptr) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
-    form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes;
+    form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; form.kv4 = b->kv4;
     if (record_rows(b, form.runs.pos, form.runs.tok, R)) return -1;
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
@@ -2980,7 +3013,7 @@ static int masks_enqueue(lmrs_batch* b, size_t n, bool filters = true) {
 static int batch_pass(lmrs_batch* b, uint32_t n, uint32_t step, float* out_logits) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = true; form.rows = b->tab; form.max_T = b->h_tab->pos[0] + (int)step + 1; form.k_cache = b->kv; form.v_cache = b->kv + b->slot_floats;
-    if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; }
+    if (b->pool) { form.v_cache = b->kv + b->page_floats; form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; form.kv4 = b->kv4; }
     form.masks = b->mask_view(); form.autos = b->auto_view(); form.penalties = b->penalty_view(b->tab->pos, form.max_T); form.filters = b->filter_view();
     if (record_rows(b, b->tab->pos, b->tab->tok, n)) return -1;
     RowSink to{0, n, out_logits, 0}; to.targets = false;
@@ -3265,9 +3298,10 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     return 0;
 }
 // A prompt chunk of a paged batch - m rows of one slot from p0 on - takes block attention over the page table by prefill_attention's rule (and from
-// kPagedBlockMin rows on; Q8 pages: kKvqBlockMin, 4.4.17); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it
+// kPagedBlockMin rows on; Q8 pages: kKvqBlockMin, 4.4.17); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it.
+// Q4 pages have no block attention (4.4.18): every chunk takes the table pass
 static bool paged_block_route(const lmrs_batch* b, uint32_t m, uint32_t p0) {
-    return !b->pf_table && m >= (b->kvq_bytes ? kKvqBlockMin : kPagedBlockMin) && prefill_block_route(b->c, (int)m, (int)p0);
+    return !b->kv4 && !b->pf_table && m >= (b->kvq_bytes ? kKvqBlockMin : kPagedBlockMin) && prefill_block_route(b->c, (int)m, (int)p0);
 }
 extern "C" int lmrs_batch_prefill_form(const lmrs_batch* b, size_t n, uint32_t start_pos, uint32_t* n_chunks, uint32_t* n_block) {
     const std::string what = "lmrs_batch_prefill_form: ";
@@ -3315,7 +3349,7 @@ static int paged_prefill(const std::string& what, lmrs_batch* b, uint32_t slot, 
                 if (record_rows(b, b->runs->pos, b->runs->tok, m)) return -1;                // (the table pass records in runs_pass)
                 // the GEMM forms of a contiguous batch's chunk (m >= 16: never the skinny ones), the qkv block and the scatter of the table pass
                 PassForm form; form.runs = b->runs_view(); form.qkv = b->runs_qkv; form.k_cache = b->kv; form.v_cache = b->kv + b->page_floats;
-                form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; form.block_pos0 = (int)p0; form.block_row = slot;
+                form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; form.kv4 = b->kv4; form.block_pos0 = (int)p0; form.block_row = slot;
                 if ((embeddings ? source_rows(c, form.runs.tok, b->embed_stage, (int)m) : token_rows(c, form.runs.tok, (int)m)) || prefill_pass(c, form, (int)m, (int)p0)) return -1;
                 if (residual) HIP_OK(hipMemcpyAsync(residual + i0 * dim, c->pf_x, (size_t)m * dim * 4, hipMemcpyDeviceToHost, c->stream));     // (position order already)
                 return 0;
@@ -3773,12 +3807,33 @@ static int debug_kvq_row(lmrs_batch* b, uint32_t page, int which, uint32_t layer
     for (size_t i = 0; i < kv; ++i) out[i] = (float)q[i] * s[i / 32];
     return 0;
 }
+// a row of a Q4 page read back: (float)(nibble - 8) * scale, the rule's read-back (lmrs_kv4.inc), formed here on the host
+static int debug_kv4_row(lmrs_batch* b, uint32_t page, int which, uint32_t layer, uint32_t pin, float* out) {
+    lmrs_ctx* c = b->c;
+    if (which < 0 || which > 1 || layer >= c->args.n_layers) return fail("bad layer / position");
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const size_t kv = (size_t)c->kv_dim, PL = b->page_len, Q = b->kvq_bytes / 2, hs = c->args.head_size, nh = kv / hs;
+    std::vector<uint8_t> q(kv / 2); std::vector<float> s(kv / 32);
+    if (which == 1) {                                    // a kv head's piece of the row: hs / 2 bytes and hs / 32 scales, a head's rows apart
+        const char* v = reinterpret_cast<const char*>(b->page_v(page));
+        HIP_OK(hipMemcpy2D(q.data(), hs / 2, v + ((size_t)layer * nh * PL + pin) * (hs / 2), PL * hs / 2, hs / 2, nh, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy2D(s.data(), hs / 8, v + Q + ((size_t)layer * nh * PL + pin) * (hs / 8), PL * hs / 8, hs / 8, nh, hipMemcpyDeviceToHost));
+    } else {
+        const char* k = reinterpret_cast<const char*>(b->page_k(page));
+        HIP_OK(hipMemcpy2D(q.data(), 16, k + ((size_t)layer * (kv / 32) * PL + pin) * 16, PL * 16, 16, kv / 32, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy2D(s.data(), 4, k + Q + ((size_t)layer * (kv / 32) * PL + pin) * 4, PL * 4, 4, kv / 32, hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < kv; ++i) out[i] = (float)((int)((q[i / 2] >> (4 * (i & 1))) & 15) - 8) * s[i / 32];
+    return 0;
+}
 extern "C" int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out) {
     if (!b || !out) return fail("NULL argument");
     if (slot >= b->n_slots) return fail("lmrs_batch_debug_kv: slot " + std::to_string(slot) + " of " + std::to_string(b->n_slots));
     if (b->pool) {                                       // the row's page (the zero page where nothing was claimed), at its in-page position
         if (pos >= b->c->args.seq_len) return fail("bad layer / position");
         const uint32_t page = b->pool->row(slot)[pos / b->page_len];
+        if (b->kv4) return debug_kv4_row(b, page, which, layer, pos % b->page_len, out);
         if (b->kvq_bytes) return debug_kvq_row(b, page, which, layer, pos % b->page_len, out);
         return debug_kv_row(b->c, b->page_k(page), b->page_v(page), which, layer, pos % b->page_len, out, b->page_len);
     }
@@ -4299,6 +4354,23 @@ extern "C" int lmrs_op_filter_rows(int device, float* rows, size_t n_rows, size_
     HIP_OK(launch_filter_rows(static_cast<float*>(dl), (int)ld, (int)n, (int)n_rows, static_cast<const FilterRow*>(dof), nullptr));
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(rows, dl, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The two device functions of the Q4 K/V format on caller values (unit parity against the rule on the CPU): kv4_quant8, the quantiser of kv4_scatter_kernel and
+// kv4_import_kernel, then kv4_deq8, the read-back of kv4_attn_kernel - the functions themselves (lmrs_kv4.inc), every aligned 32 of x a group.  Host memory in and out
+extern "C" int lmrs_op_kv4_round_trip(int device, const float* x, size_t n, float* out) {
+    const std::string what = "lmrs_op_kv4_round_trip: ";
+    if (!x || !out) return fail(what + "NULL argument");
+    if (n < 32 || n % 32 || n > ((size_t)1 << 24)) return fail(what + "n = " + std::to_string(n) + " is not a multiple of 32 in 32 .. 2^24");
+    if (op_begin(device)) return -1;
+    Scratch S;
+    void *dx = S.get(n * 4), *dy = S.get(n * 4);
+    if (!dx || !dy) return fail(what + "hipMalloc failed");
+    HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
+    HIP_OK(launch_kv4_round_trip(static_cast<const float*>(dx), static_cast<float*>(dy), n, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out, dy, n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

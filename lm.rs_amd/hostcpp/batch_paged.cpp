@@ -7,7 +7,7 @@
 // batch_greedy on "<system><line>".
 //   usage: batch_paged --model m.lmrs --tokenizer tokenizer.bin --system "text" --prompts file.txt [--n N (default 64)] [--slots K (default 8)]
 //                      [--page-len L (default 64)] [--pages P (default: what K full sequences would need, halved)]
-//                      [--kv f32|q8 (default f32; q8: the pages hold K/V in 8 bits, lmrs_batch_create_paged_q8 - the ids are then those of that rule)]
+//                      [--kv f32|q8|q4 (default f32; q8 / q4: the pages hold K/V in 8 / 4 bits, lmrs_batch_create_paged_q8 / _q4 - the ids are then those of that rule)]
 //   g++ -O2 -std=c++17 batch_paged.cpp -I../../include -L.. -llmrs_hip -Wl,-rpath,'$ORIGIN/..' -o batch_paged
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -39,8 +39,8 @@ int main(int argc, char** argv) {
         else if (k == "--kv") kv = argv[i + 1];
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (model_path.empty() || tok_path.empty() || prompts_path.empty() || system_text.empty() || n_new < 1 || n_slots < 2 || n_slots > 64 || n_pages < 0 || (kv != "f32" && kv != "q8")) {
-        std::fprintf(stderr, "usage: %s --model m.lmrs --tokenizer tokenizer.bin --system \"text\" --prompts file.txt [--n N] [--slots 2..64] [--page-len L] [--pages P] [--kv f32|q8]\n", argv[0]);
+    if (model_path.empty() || tok_path.empty() || prompts_path.empty() || system_text.empty() || n_new < 1 || n_slots < 2 || n_slots > 64 || n_pages < 0 || (kv != "f32" && kv != "q8" && kv != "q4")) {
+        std::fprintf(stderr, "usage: %s --model m.lmrs --tokenizer tokenizer.bin --system \"text\" --prompts file.txt [--n N] [--slots 2..64] [--page-len L] [--pages P] [--kv f32|q8|q4]\n", argv[0]);
         return 2;
     }
     std::ifstream pf(prompts_path);
@@ -62,8 +62,10 @@ int main(int argc, char** argv) {
         const std::uint32_t PL = static_cast<std::uint32_t>(page_len), per_seq = (model.args.seq_len + PL - 1) / PL;
         if (n_pages == 0) n_pages = std::max<long>(per_seq, n_slots * per_seq / 2);
         const std::uint32_t NS = static_cast<std::uint32_t>(n_slots), NP = static_cast<std::uint32_t>(n_pages);
-        std::unique_ptr<lmrs_host::Batch> held(kv == "q8" ? new lmrs_host::Batch(model, NS, PL, NP, lmrs_host::Batch::Q8{}) : new lmrs_host::Batch(model, NS, PL, NP));
+        std::unique_ptr<lmrs_host::Batch> held(kv == "q8" ? new lmrs_host::Batch(model, NS, PL, NP, lmrs_host::Batch::Q8{})
+                                               : kv == "q4" ? new lmrs_host::Batch(model, NS, PL, NP, lmrs_host::Batch::Q4{}) : new lmrs_host::Batch(model, NS, PL, NP));
         lmrs_host::Batch& batch = *held;
+        if (kv == "q4") std::printf("K/V in 4 bits: %zu bytes a page, %zu in the pool\n", batch.kv_format().page_bytes, batch.kv_format().page_bytes * (NP + 1));
         if (kv == "q8") std::printf("K/V in 8 bits: %zu bytes a page, %zu in the pool\n", batch.kv_format().page_bytes, batch.kv_format().page_bytes * (NP + 1));
         const std::vector<std::uint32_t> sys = tok.encode(system_text, true, false, false, mt);
         const std::uint32_t n_sys = static_cast<std::uint32_t>(sys.size());

@@ -172,7 +172,13 @@ public:
     Batch(Transformer& t, std::uint32_t n_slots, std::uint32_t page_len, std::uint32_t n_pages, Q8) : vocab_size_(t.args.vocab_size) {
         check(lmrs_batch_create_paged_q8(t.ctx_, n_slots, page_len, n_pages, &b_));
     }
-    struct KvFormat { int format; std::uint32_t group; std::size_t page_bytes; };                                                   // 0 f32 / 1 Q8, 0 / 32, a page's bytes
+    // ... or in 4 bits (Q4{}): the reference's Q4_0 rule at a group of 32, 0.625 bytes a value; read back as (float)(nibble - 8) * scale, the row's own key and
+    // value in f32; every prompt chunk takes the table pass  (lmrs_batch_create_paged_q4)
+    struct Q4 {};
+    Batch(Transformer& t, std::uint32_t n_slots, std::uint32_t page_len, std::uint32_t n_pages, Q4) : vocab_size_(t.args.vocab_size) {
+        check(lmrs_batch_create_paged_q4(t.ctx_, n_slots, page_len, n_pages, &b_));
+    }
+    struct KvFormat { int format; std::uint32_t group; std::size_t page_bytes; };                                                   // 0 f32 / 1 Q8 / 2 Q4, 0 / 32, a page's bytes
     KvFormat kv_format() const { KvFormat f{}; check(lmrs_batch_kv_format(b_, &f.format, &f.group, &f.page_bytes)); return f; }      // (lmrs_batch_kv_format)
     struct Pages { std::uint32_t page_len, n_pages, n_free; };
     Pages pages() const { Pages p{}; check(lmrs_batch_pages(b_, &p.page_len, &p.n_pages, &p.n_free)); return p; }                  // (lmrs_batch_pages)

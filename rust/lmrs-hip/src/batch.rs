@@ -32,6 +32,7 @@ extern "C" {
     pub fn lmrs_batch_pages(b: *const LmrsBatch, page_len: *mut u32, n_pages: *mut u32, n_free: *mut u32) -> c_int;
     // the pool in 8 bits, and how a batch keeps its K/V: declared here as the paged calls are
     pub fn lmrs_batch_create_paged_q8(ctx: *mut ffi::LmrsCtx, n_slots: u32, page_len: u32, n_pages: u32, out: *mut *mut LmrsBatch) -> c_int;
+    pub fn lmrs_batch_create_paged_q4(ctx: *mut ffi::LmrsCtx, n_slots: u32, page_len: u32, n_pages: u32, out: *mut *mut LmrsBatch) -> c_int;
     pub fn lmrs_batch_kv_format(b: *const LmrsBatch, format: *mut c_int, group: *mut u32, page_bytes: *mut usize) -> c_int;
     pub fn lmrs_batch_slot_pages(b: *const LmrsBatch, slot: u32, n_held: *mut u32, n_shared: *mut u32) -> c_int;
     pub fn lmrs_batch_release(b: *mut LmrsBatch, slot: u32, n_pos: u32) -> c_int;
@@ -184,7 +185,16 @@ impl<'t, 'a> Batch<'t, 'a> {
         Batch { b, vocab_size, _t: t }
     }
 
-    /// How the batch keeps K/V: (0 f32 / 1 Q8, the group - 0 or 32, a page's bytes - 0 on a batch that is not paged).
+    /// `new_paged` with the pages in 4 bits: the reference's Q4_0 rule at a group of 32, 0.625 bytes a value.  A row attends to the earlier positions as
+    /// read back, (nibble - 8) * scale, and to its own key and value in f32; every prompt chunk takes the table pass.
+    pub fn new_paged_q4(t: &'t mut Transformer<'a>, n_slots: u32, page_len: u32, n_pages: u32) -> Batch<'t, 'a> {
+        let mut b: *mut LmrsBatch = ptr::null_mut();
+        check(unsafe { lmrs_batch_create_paged_q4(t.ctx(), n_slots, page_len, n_pages, &mut b) });
+        let vocab_size = t.args.vocab_size as usize;
+        Batch { b, vocab_size, _t: t }
+    }
+
+    /// How the batch keeps K/V: (0 f32 / 1 Q8 / 2 Q4, the group - 0 or 32, a page's bytes - 0 on a batch that is not paged).
     pub fn kv_format(&self) -> (i32, u32, usize) {
         let (mut f, mut g, mut n) = (0 as c_int, 0u32, 0usize);
         check(unsafe { lmrs_batch_kv_format(self.b, &mut f, &mut g, &mut n) });

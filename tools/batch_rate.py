@@ -16,6 +16,10 @@ lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: 
        python tools/batch_rate.py --kvq [--parent-lib PATH] [model] [q8_0|q4_0]
 --kvq: a Q8 paged batch (lmrs_batch_create_paged_q8) against the f32 paged batch of the same build, by turns (kvq_main below)
        (writes profiles/batch_kvq_llama1b.txt, profiles/batch_kvq_gemma2b_q4.txt)
+       python tools/batch_rate.py --kvq --kv q4 [--parent-lib PATH] [model] [q8_0|q4_0]
+--kv q4: the same protocol with a Q4 paged batch (lmrs_batch_create_paged_q4) as a third pool beside the f32 and the Q8 one; a Q4 line is a MISS where it is
+       slower than the Q8 pool's by more than the larger of the two pools' turn spreads
+       (writes profiles/batch_kv4_llama1b.txt, profiles/batch_kv4_gemma2b_q4.txt)
        python tools/batch_rate.py --paged-prefill [model] [q8_0|q4_0]
 --paged-prefill: lmrs_batch_prefill of 16 .. 512 tokens on a wide batch, on paged batches (block attention over the page table from 16 rows on) and on the
 same paged batches with lmrs_batch_debug_prefill_table (every chunk through the table pass: the routing before), and on a Q8 paged batch under the library's
@@ -290,7 +294,8 @@ def kvq_child(image_path, kv, traced):
     vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
     lib.lmrs_last_error.restype = C.c_char_p
     lib.lmrs_create.argtypes = [vp, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
-    create = lib.lmrs_batch_create_paged_q8 if kv == "q8" else lib.lmrs_batch_create_paged
+    create = {"f32": "lmrs_batch_create_paged", "q8": "lmrs_batch_create_paged_q8", "q4": "lmrs_batch_create_paged_q4"}[kv]
+    create = getattr(lib, create)
     create.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
     lib.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
     lib.lmrs_batch_fork.argtypes = [vp, u32, u32, u32]
@@ -337,7 +342,7 @@ def kvq_child(image_path, kv, traced):
     print("KVQ " + " ".join(f"{x:.2f}" if isinstance(x, float) else str(x) for x in out), flush=True)
 
 
-def kvq_processes(say, img, model, prompt, parent):
+def kvq_processes(say, img, model, prompt, parent, q4=False):
     """--kvq's two sections that need processes of their own: the parent commit's library, and the launches alone under a kernel trace"""
     import csv, glob, shutil, subprocess, tempfile  # noqa: E401
     me, L = os.path.abspath(__file__), S.CONFIGS[model].n_layers
@@ -350,6 +355,7 @@ def kvq_processes(say, img, model, prompt, parent):
             say("  not run: no parent library given (--parent-lib PATH)")
         else:
             runs = (("parent f32", os.path.abspath(parent), "f32"), ("this f32", lmrs_amd.LIB_PATH, "f32"), ("this q8", lmrs_amd.LIB_PATH, "q8"))
+            runs += (("this q4", lmrs_amd.LIB_PATH, "q4"),) if q4 else ()
             res = {k: [] for k, _, _ in runs}
             for turn in range(2):
                 for who, lib, kv in runs:
@@ -368,13 +374,19 @@ def kvq_processes(say, img, model, prompt, parent):
                     spread = max(float(v[k]) for v in res["parent f32"]) - min(float(v[k]) for v in res["parent f32"])
                     say(f"  {what:11s}  parent f32 {p:8.2f} (its turns {spread:.2f} apart)   this f32 {mean('this f32', k):8.2f} ({mean('this f32', k) / p - 1:+.2%})   "
                         f"this q8 {mean('this q8', k):8.2f} ({mean('this q8', k) / p - 1:+.2%}{'  ** A MISS **' if mean('this q8', k) > p + spread else ''})")
+                    if q4:                                # against this build's Q8 pool: slower by more than the larger of the two pools' turn spreads is a MISS
+                        gap = lambda who: max(float(v[k]) for v in res[who]) - min(float(v[k]) for v in res[who])
+                        a8, a4, allow = mean("this q8", k), mean("this q4", k), max(gap("this q8"), gap("this q4"))
+                        say(f"  {'':11s}  this q4 {a4:8.2f} ({a4 / p - 1:+.2%} against parent f32, {a4 / a8 - 1:+.2%} against this q8; turns q8 {gap('this q8'):.2f} / q4 {gap('this q4'):.2f} apart)"
+                            f"{f'  ** MISS: q4 {a4:.2f} against q8 {a8:.2f} **' if a4 > a8 + allow else ''}")
                 say(f"  f32 tokens equal between the libraries: {[res['parent f32'][0][k] for k in (1, 3, 5)] == [res['this f32'][0][k] for k in (1, 3, 5)]}")
         say(f"the launches alone, 64 rows at 1000 - 1007 positions: rocprofv3 --kernel-trace over a process per pool (slot 0 prefilled and forked into 63 slots, a call "
             f"of 2 steps, then one of 8); per kernel the last 8 x {L} launches: median (fastest .. slowest) us")
         if not shutil.which("rocprofv3"):
             say("  not run: rocprofv3 is not on the PATH")
             return
-        for kv, kernels in (("f32", ("paged_scatter_kernel", "paged_attn_kernel")), ("q8", ("kvq_scatter_kernel", "kvq_attn_kernel"))):
+        traced = (("f32", ("paged_scatter_kernel", "paged_attn_kernel")), ("q8", ("kvq_scatter_kernel", "kvq_attn_kernel")))
+        for kv, kernels in traced[1:] + (("q4", ("kv4_scatter_kernel", "kv4_attn_kernel")),) if q4 else traced:
             with tempfile.TemporaryDirectory() as tt:
                 r = subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tt, "--", sys.executable, me, "--kvq-child", path, kv, "traced"],
                                    capture_output=True, text=True, timeout=900)
@@ -389,6 +401,7 @@ def kvq_processes(say, img, model, prompt, parent):
 
 
 KVQ_OUT = {("llama-3.2-1b", S.Q8_0): "batch_kvq_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_kvq_gemma2b_q4.txt"}
+KV4_OUT = {("llama-3.2-1b", S.Q8_0): "batch_kv4_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_kv4_gemma2b_q4.txt"}
 KVQ_MINIS = [("mini-llama", S.Q8_0), ("mini-phi", S.Q8_0), ("mini-llama3b", S.Q8_0), ("mini-gemma", S.Q4_0)]
 
 
@@ -398,7 +411,9 @@ def kvq_main(argv):
     two pools by turns three times: us per pass of 64 decode rows at 100 and at 1000 positions and of 16 rows at 1000 (device time of 64 greedy steps a call,
     median of 3 a turn), a 512-token lmrs_batch_prefill (wall time; the Q8 pool takes the table pass), the pools' bytes for 64 x 1024 positions (also for
     the Phi-3.5 geometry, from its shapes), and - on the four mini models - the logits of the Q8 batch against the f32 paged batch after 130 positions."""
-    parent = os.environ.get("BATCH_RATE_PARENT_LIB")
+    parent, q4 = os.environ.get("BATCH_RATE_PARENT_LIB"), False
+    if argv[:2] == ["--kv", "q4"]:
+        q4, argv = True, argv[2:]
     if argv and argv[0] == "--parent-lib":
         parent, argv = argv[1], argv[2:]
     model = argv[0] if argv else "llama-3.2-1b"
@@ -410,12 +425,12 @@ def kvq_main(argv):
         print(s, flush=True); lines.append(s)
 
     img = S.build_image(model, qt, 1234)
-    say(f"python tools/batch_rate.py --kvq --parent-lib <the parent commit's liblmrs_hip.so> {model} {qname}")
+    say(f"python tools/batch_rate.py --kvq {'--kv q4 ' if q4 else ''}--parent-lib <the parent commit's liblmrs_hip.so> {model} {qname}")
     say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
-    kvq_processes(say, img, model, S.prompt_tokens(model, 1001, 100), parent)
+    kvq_processes(say, img, model, S.prompt_tokens(model, 1001, 100), parent, q4)
     m = lmrs_amd.Transformer(img)
     say("in one process, both pools this build's:")
-    forms = [("f32 pages", "f32"), ("q8 pages", "q8")]
+    forms = [("f32 pages", "f32"), ("q8 pages", "q8")] + ([("q4 pages", "q4")] if q4 else [])
     prompt = S.prompt_tokens(model, 1001, 100)
     say(f"us per pass of lmrs_batch_generate_greedy ({STEPS} greedy steps a call, device time of the steps): the two pools by turns, three turns, median of 3 calls "
         f"after 1 warm-up a turn; per pool the median of its turns (fastest .. slowest turn)")
@@ -439,7 +454,7 @@ def kvq_main(argv):
                 say(f"  {depth:4d} positions, n={n:2d}, {name:9s}  {statistics.median(t):8.1f} us per pass ({min(t):.1f} .. {max(t):.1f})   {statistics.median(t) / w - 1:+6.1%} against f32 pages")
             say(f"      tokens equal between the pools (not expected: Q8 is another rule): {bool((ids['f32 pages'] == ids['q8 pages']).all())}")
         if depth == 1000:
-            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): block attention on f32 pages, the table pass on Q8 pages")
+            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): block attention on f32 and on Q8 pages (see prefill_form), the table pass on Q4 pages")
             for name, _kv in forms:
                 b = batches[name]
 
@@ -457,8 +472,8 @@ def kvq_main(argv):
         b.close()
     c = S.CONFIGS["phi-3.5"]
     per = 2 * c.n_layers * 64 * c.n_kv_heads * (c.dim // c.n_heads)
-    say(f"  phi-3.5 geometry, from its shapes (not created here): f32 {per * 4 * 1025 / 1e9:.3f} GB, q8 {per * 9 // 8 * 1025 / 1e9:.3f} GB")
-    say("accuracy (reported, not a gate; synthetic weights): Q8 pages against f32 pages on the mini models, 6 slots prefilled to 130 positions, then one step: "
+    say(f"  phi-3.5 geometry, from its shapes (not created here): f32 {per * 4 * 1025 / 1e9:.3f} GB, q8 {per * 9 // 8 * 1025 / 1e9:.3f} GB, q4 {per * 5 // 8 * 1025 / 1e9:.3f} GB")
+    say(f"accuracy (reported, not a gate; synthetic weights): {'Q4' if q4 else 'Q8'} pages against f32 pages on the mini models, 6 slots prefilled to 130 positions, then one step: "
         "largest |logit difference| over the 6 rows, rows whose argmax agrees")
     for cfg, q in KVQ_MINIS:
         mm = lmrs_amd.Transformer(S.build_image(cfg, q, 1234))
@@ -469,9 +484,9 @@ def kvq_main(argv):
                 b.prefill(i, S.prompt_tokens(cfg, 130, 700 + i), 0)
             out[name] = b.forward(list(range(6)), [7 + i for i in range(6)], [130] * 6, logits=True)
             b.close()
-        (a0, l0), (a1, l1) = out["f32 pages"], out["q8 pages"]
-        say(f"  {cfg:13s} max |dlogit| {float(np.abs(l0 - l1).max()):.5f} (largest |logit| {float(np.abs(l0).max()):.3f}); argmax agrees in {int((a0 == a1).sum())} of 6 rows")
-    name = KVQ_OUT.get((model, qt))
+        (a0, l0), (a1, l1) = out["f32 pages"], out["q4 pages" if q4 else "q8 pages"]
+        say(f"  {cfg:13s} {'Q4 ' if q4 else ''}max |dlogit| {float(np.abs(l0 - l1).max()):.5f} (largest |logit| {float(np.abs(l0).max()):.3f}); argmax agrees in {int((a0 == a1).sum())} of 6 rows")
+    name = (KV4_OUT if q4 else KVQ_OUT).get((model, qt))
     path = os.environ.get("BATCH_RATE_OUT") or (os.path.join(ROOT, "profiles", name) if name else None)
     if path:
         with open(path, "w") as f:
