@@ -316,9 +316,14 @@ int lmrs_batch_create_paged_q8(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, ui
  * Same arguments and refusals as lmrs_batch_create_paged_q8, each message opening with this call's name.  The allocation is (n_pages + 1) * 2 * n_layers *
  * page_len * kv_dim * 5 / 8 bytes, all or nothing: 20 bytes a group of 32, 0.625 bytes a cached value (Llama-3.2-1B, 1024 pages of 64: 671 744 000 bytes
  * where Q8 takes 1 209 139 200).  Every batch call works as documented for a paged batch; forks as for the Q8 pool.
- * Prompts: EVERY chunk takes the table pass - there is no block attention over Q4 pages; lmrs_batch_prefill_form reports n_block = 0 for any length.
- * Out of scope: block attention over Q4 pages; Q4 for contiguous and wide batches or the context's own cache; mixed K / V formats.
- * Measured: profiles/batch_kv4_*.txt, DESIGN.md 4.4.18.
+ * Prompts: a chunk of 320 rows or more of lmrs_batch_prefill / lmrs_batch_prefill_embeddings takes block attention over the Q4 pages (64-query blocks; the
+ * key chunks and value tiles are read back on the way into LDS, each query's own key and value come from its f32 qkv row) under the f32 pool's other
+ * conditions; a shorter chunk, ragged runs and decode rows take the table pass.  The bits are the same either way.  320 is a floor (five whole query
+ * blocks, the first count above the 300-row chunks that tests pin to the table pass), not a measured crossover: nothing below 320 rows is measured.
+ * lmrs_batch_prefill_form reports these chunks in n_block; lmrs_batch_debug_prefill_table(b, 1) forces the table pass on a Q4 batch too, 0 restores the rule.
+ * Out of scope: Q4 for contiguous and wide batches or the context's own cache; mixed K / V formats.
+ * Measured: profiles/batch_kv4_*.txt; prefill by block attention against the table pass and against the Q8 and f32 pools:
+ * profiles/batch_kv4_prefill_*.txt, DESIGN.md 4.4.19.
  * lmrs_op_kv4_round_trip: n caller values (host memory, n a multiple of 32 in 32 .. 2^24, every aligned 32 a group) through the scatter kernel's quantiser
  * and the attention kernel's read-back - the device functions those kernels call - into out[n]. */
 int lmrs_batch_create_paged_q4(lmrs_ctx* ctx, uint32_t n_slots /* 1 .. 64 */, uint32_t page_len /* 64, 128, 256, 512 or 1024 */,

@@ -560,7 +560,8 @@ class Batch:
     a shorter one the table pass - the same bits either way; prefill_form tells which, debug_prefill_table(True) forces the table pass.
     kv="q4" (a paged batch only): the pages hold every K and V row in 4 bits by the reference's Q4_0 rule at a group of 32 - 0.625 bytes a value; a row attends
     to the earlier positions as read back, (float)(nibble - 8) * scale with the rule's negative scale, and to its own key and value in f32
-    (lmrs_batch_create_paged_q4).  Every prompt chunk takes the table pass; a position nobody wrote reads as -0.0."""
+    (lmrs_batch_create_paged_q4).  A prompt chunk of 320 rows or more takes block attention over the Q4 pages, a shorter one the table pass - the same bits
+    either way; a position nobody wrote reads as -0.0."""
 
     def __init__(self, model: Transformer, n_slots: int, wide: bool = False, *, page_len=None, n_pages=None, kv: str = "f32"):
         h = C.c_void_p()

@@ -1524,11 +1524,13 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
             // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
             const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
             if (form.kv4) {
-                // Q4 pages: the quantising scatter and the table pass that reads the nibbles back, for every row of every pass
-                if (form.block_pos0 >= 0) return fail("prefill_layers: no block attention over Q4 pages");
+                // Q4 pages: the quantising scatter, then the attention that reads the nibbles back - in 64-query blocks or by the table pass, as over Q8 pages
                 const KvqView qv{form.pages.tab, form.pages.per_slot, form.pages.shift, form.pages.page_stride * 4, form.kvq_bytes / 2};
                 HIP_OK(launch_kv4_scatter(qkv, k_cache, v_cache, c->rope, rv, qv, t.n_heads, t.n_kv_heads, hs, t.layer, m, c->stream));
-                HIP_OK(launch_kv4_attention(t, rv, qv, m, form.max_T, c->stream));
+                if (form.block_pos0 >= 0) {
+                    if (prefill_slabs(c, attention_block_scratch_floats(t.n_heads, m, form.block_pos0 + m))) return -1;
+                    HIP_OK(launch_kv4_attention_block(t, qv, form.block_row, form.block_pos0, m, c->pf_att, c->sw.att_lds_keys, c->sw.att_long_batch_forms, c->stream));
+                } else HIP_OK(launch_kv4_attention(t, rv, qv, m, form.max_T, c->stream));
             } else if (form.kvq_bytes) {
                 // Q8 pages: the scatter quantises (and leaves the rotated k in the qkv row), the attention reads the pages back - one slot's consecutive
                 // rows in 64-query blocks, anything else by the table pass; either takes a row's own key and value from its qkv row
@@ -2100,6 +2102,10 @@ constexpr uint32_t kPagedBlockMin = 112;
 // batch to the table pass, so the rule starts at the next whole number of 64-query blocks.  The Q8 table pass is faster than the f32 one, so the crossover
 // lies above 112 anyway; whether block attention would win between 112 and 255 rows is not measured
 constexpr uint32_t kKvqBlockMin = 256;
+// ... and of a Q4 paged batch's (block_kv4_*_kernel, lmrs_kv4.inc).  A FLOOR too, derived from tests that stand and not measured: tests/test_batch_kv4.py pins
+// 256-row chunks of the 256-position mini classes and a 300-row chunk of mini-llama-long to the table pass, so the rule starts at the next whole number of
+// 64-query blocks above 300.  Whether block attention would win anywhere below 320 rows is not measured
+constexpr uint32_t kKv4BlockMin = 320;
 struct RunTable { unsigned long long off[kRunRowsMax]; int pos[kRunRowsMax]; uint32_t tok[kRunRowsMax]; uint32_t sel[kRunRowsMax]; };
 // The buffers of a sampled call (sample_set_alloc; rows != 0: the set stands, for that many rows): the rows' sampler table and its pinned source,
 // launch_sample_rows' scratch, the result blocks ([rows][vocab + 1] words: {token, n0}, then the candidates) and the pinned copy of their heads (head_words each)
@@ -3298,10 +3304,10 @@ static int forward_runs_from(const std::string& what, lmrs_batch* b, uint32_t n_
     return 0;
 }
 // A prompt chunk of a paged batch - m rows of one slot from p0 on - takes block attention over the page table by prefill_attention's rule (and from
-// kPagedBlockMin rows on; Q8 pages: kKvqBlockMin, 4.4.17); the table pass otherwise, or when lmrs_batch_debug_prefill_table forced it.
-// Q4 pages have no block attention (4.4.18): every chunk takes the table pass
+// kPagedBlockMin rows on; Q8 pages: kKvqBlockMin, 4.4.17; Q4 pages: kKv4BlockMin, 4.4.19); the table pass otherwise, or when
+// lmrs_batch_debug_prefill_table forced it
 static bool paged_block_route(const lmrs_batch* b, uint32_t m, uint32_t p0) {
-    return !b->kv4 && !b->pf_table && m >= (b->kvq_bytes ? kKvqBlockMin : kPagedBlockMin) && prefill_block_route(b->c, (int)m, (int)p0);
+    return !b->pf_table && m >= (b->kv4 ? kKv4BlockMin : b->kvq_bytes ? kKvqBlockMin : kPagedBlockMin) && prefill_block_route(b->c, (int)m, (int)p0);
 }
 extern "C" int lmrs_batch_prefill_form(const lmrs_batch* b, size_t n, uint32_t start_pos, uint32_t* n_chunks, uint32_t* n_block) {
     const std::string what = "lmrs_batch_prefill_form: ";

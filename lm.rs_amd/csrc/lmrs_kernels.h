@@ -316,10 +316,13 @@ hipError_t launch_kvq_attention_block(const AttnArgs& a, KvqView pv, unsigned ta
 hipError_t launch_kvq_import(const float* k_src, const float* v_src, int seq_len, int p0, float* k_page, float* v_page, size_t q_bytes, int n_layers, int kv, int page_len,
                              int pin0, int n_rows, hipStream_t s);
 // ---- ... and kept in 4 bits (lmrs_batch_create_paged_q4; lmrs_kv4.inc: the rule and the page layout).  The same view, with q_bytes = n_layers * page_len *
-// kv_dim / 2, the nibbles of a page's K (or V) block, its f32 scales behind them.  No block attention: every row of every pass goes through launch_kv4_attention
+// kv_dim / 2, the nibbles of a page's K (or V) block, its f32 scales behind them
 hipError_t launch_kv4_scatter(float* qkv, float* k_pool, float* v_pool, const float* rope, RowView rows, KvqView pv, int n_heads, int n_kv_heads, int hs,
                               int layer, int n_rows, hipStream_t s);
 hipError_t launch_kv4_attention(const AttnArgs& a, RowView rows, KvqView pv, int n_rows, int max_T, hipStream_t s);
+// launch_kvq_attention_block over Q4 pages: n_tok consecutive rows of ONE slot (page row table_row) from pos0 on, behind launch_kv4_scatter over the same rows
+// in position order.  a.q: the qkv block - the launches also read each row's own key and value from it; the output is launch_kv4_attention's, bit for bit
+hipError_t launch_kv4_attention_block(const AttnArgs& a, KvqView pv, unsigned table_row, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s);
 hipError_t launch_kv4_import(const float* k_src, const float* v_src, int seq_len, int p0, float* k_page, float* v_page, size_t nib_bytes, int n_layers, int kv, int hs,
                              int page_len, int pin0, int n_rows, hipStream_t s);
 // n device floats (a multiple of 32) through the scatter's quantiser and the attention's read-back, the device functions themselves (lmrs_op_kv4_round_trip)

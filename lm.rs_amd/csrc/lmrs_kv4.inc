@@ -25,9 +25,10 @@
 //                                                       lane after lane 8 bytes on
 // 0.625 bytes a cached value: 20 bytes a group of 32.
 // What was built: ONE WORKGROUP PER (HEAD, ROW), as kvq_attn_kernel and paged_attn_kernel.  The (kv head, row) split - a key unpacked once for its
-// kv_mul query heads - was not built or measured.
-// Out of scope: block attention over Q4 pages (every prompt chunk takes this table pass), Q4 for contiguous and wide batches or the context's own
-// cache, mixed K / V formats.
+// kv_mul query heads - was not built or measured.  A prompt chunk of ONE slot of kKv4BlockMin rows or more (lmrs_api.hip) takes BLOCK attention over
+// the same pages (the second half of this file: block_kv4_scores_kernel, block_kv4_scores_wide_kernel, block_kv4_values_kernel); shorter chunks,
+// ragged runs and decode rows take the table pass.
+// Out of scope: a block floor below 320 rows, Q4 for contiguous and wide batches or the context's own cache, mixed K / V formats.
 // ------------------------------------------------------------------------------------------------
 typedef int i32x2v __attribute__((ext_vector_type(2)));
 // built without the packed f32 instructions, as the Q8 kernels are and for their reason (lmrs_kvq.inc): every value is compared bit for bit
@@ -378,5 +379,343 @@ hipError_t launch_kv4_attention(const AttnArgs& a0, RowView rows, KvqView pv, in
     if (a.gemma) { if (a.head_size == 256) A4(256, true) return hipErrorInvalidValue; }
     switch (a.head_size) { case 64: A4(64, false) case 96: A4(96, false) case 128: A4(128, false) default: return hipErrorInvalidValue; }
 #undef A4
+}
+
+// ------------------------------------------------------------------------------------------------
+// BLOCK attention over Q4 pages: launch_kvq_attention_block's three launches (lmrs_kvq.inc) with the two readers of the cache reading nibbles.  The
+// scatter (launch_kv4_scatter over the chunk's rows) has ended: q and k of every qkv row are rotated, every key and value row of the chunk is in the slot's
+// pages, quantised.  The contract is the table pass's at the top of this file: a query at position p takes keys and values 0 .. p-1 as kv4_deq8 reads
+// them back and its OWN key and value in f32 from its qkv row; keys behind p inside the 64-query block are read back and meet weight 0.0.  The diagonal
+// is the Q8 block kernels' (block_kvq_own_dot over S[p] in the wave that owns key p, block_kvq_tile_compute_own in the tiles that hold positions of the
+// query block), and everything behind the two loaders - the four score chains, the division by sqrtf(HS), the cap and window term, the softmax launch,
+// the tiles two ahead - is the f32 block kernels', so the output carries kv4_attn_kernel's bits whatever the chunking.
+// The loaders are this layout's own:
+//   keys    a chunk of NK keys is NK * HS / 32 words of 16 bytes, fewer than the workgroup has threads at HS 64 and in Gemma's 32-key form.  A thread's
+//           share of the chunk is NK * HS / 2 / NT bytes - 8 / 12 / 16 at HS 64 / 96 / 128, 8 and 32 in Gemma's two forms - and its PIECE the largest of
+//           16, 8 or 4 bytes that divides the share: one half word, three quarter words, one word, one half word, two words.  Pieces are numbered within a
+//           word first, then key by key, then group by group, so consecutive lanes read consecutive bytes of a group's NK * 16 - every thread loads and
+//           converts, every line is read whole.  A piece and the scale of its group wait in registers under the query rows' staging (at most ten a
+//           thread) and go through kv4_deq8 into the f32 tile att_kread consumes.
+//   values  V is head-major: a tile row's slice of SW dims is SW / 2 consecutive bytes, HS / 2 from the next row's.  One 16-dim piece a thread - two words
+//           and the scale of ITS group of 32 (a 48-dim slice of a 96-wide head starts in the middle of a group), three registers where Q8 holds five -
+//           kept two tiles ahead as raw words (Kv4Val) and read back on the way into LDS.  The weight half of the tile is the f32 kernels'.
+// ------------------------------------------------------------------------------------------------
+template <int PB> struct Kv4Piece { uint32_t w[PB / 4]; float s; };
+template <int HS, int RS, int NK, int NT>
+__device__ __forceinline__ void block_kv4_stage(float* qt, float* kt, const float* __restrict__ qrows, int qs, const uint8_t* __restrict__ k_pool, const KvqPages pg,
+                                                int n_kv_heads, int h, int kvh, int qb, int cb, int bT, int n_tok) {
+    constexpr int HS4 = HS / 4, SHARE = NK * HS / 2 / NT, PB = SHARE % 16 == 0 ? 16 : SHARE % 8 == 0 ? 8 : 4, NP = SHARE / PB, SUB = 16 / PB;
+    static_assert(HS % 32 == 0 && NP >= 1 && NP * NT * PB == NK * HS / 2 && (NK & (NK - 1)) == 0, "every thread the same number of whole pieces");
+    const int tid = threadIdx.x, PL = 1 << pg.shift;
+    const int kc = cb < bT ? cb : bT - 1;                                     // the chunk's first key, clamped: its page holds every clamped key of the chunk
+    const uint8_t* page = k_pool + (size_t)pg.tab[kc >> pg.shift] * pg.page_bytes;
+    const size_t head = ((size_t)pg.layer * n_kv_heads + kvh) * (HS / 32) * (size_t)PL;
+    const uint8_t* kq = page + head * 16;                                     // [HS/32][page_len][16]
+    const float* ks = reinterpret_cast<const float*>(page + pg.q_bytes) + head;          // [HS/32][page_len]
+    Kv4Piece<PB> raw[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int f = tid + i * NT, sub = f % SUB, kl = (f / SUB) % NK, g = f / (SUB * NK);
+        const int pin = (cb + kl < bT ? cb + kl : bT - 1) & (PL - 1);
+        const uint8_t* src = kq + ((size_t)g * PL + pin) * 16 + sub * PB;
+        if constexpr (PB == 16) {
+            const i32x4v w = *reinterpret_cast<const i32x4v*>(src);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) raw[i].w[u] = (uint32_t)w[u];
+        } else if constexpr (PB == 8) {
+            const i32x2v w = *reinterpret_cast<const i32x2v*>(src);
+            raw[i].w[0] = (uint32_t)w[0]; raw[i].w[1] = (uint32_t)w[1];
+        } else raw[i].w[0] = *reinterpret_cast<const uint32_t*>(src);
+        raw[i].s = ks[(size_t)g * PL + pin];
+    }
+    for (int f = tid; f < 64 * HS4; f += NT) {
+        const int r = f / HS4, c4 = f - r * HS4;
+        int qi = qb * kAttQB + r; qi = qi < n_tok ? qi : n_tok - 1;
+        *reinterpret_cast<float4*>(qt + r * RS + c4 * 4) = *reinterpret_cast<const float4*>(qrows + (size_t)qi * qs + h * HS + c4 * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int f = tid + i * NT, sub = f % SUB, kl = (f / SUB) % NK, g = f / (SUB * NK);
+        float* dst = kt + kl * RS + g * 32 + sub * (2 * PB);                  // a byte is two dims
+#pragma unroll
+        for (int u = 0; u < PB / 4; ++u) {
+            f32x4v a, b;
+            kv4_deq8(a, b, raw[i].w[u], raw[i].s);
+            *reinterpret_cast<f32x4v*>(dst + u * 8) = a;
+            *reinterpret_cast<f32x4v*>(dst + u * 8 + 4) = b;
+        }
+    }
+}
+template <int HS>
+KV4_KERNEL __launch_bounds__(256) void block_kv4_scores_kernel(const float* __restrict__ qrows, int qs, const uint8_t* __restrict__ k_pool, const KvqPages pg,
+                                                                float* __restrict__ scratch, int n_heads, int n_kv_heads, int pos0, int n_tok, int Tmax) {
+    constexpr int RS = HS + 4, HS4 = HS / 4;
+    __shared__ __attribute__((aligned(16))) float qt[64 * RS];
+    __shared__ __attribute__((aligned(16))) float kt[64 * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), qb = gridDim.z - 1 - blockIdx.z, h = blockIdx.x;
+    const AttBlock b = att_block(qb, lane, pos0, n_tok);
+    const int cb = blockIdx.y * 64;
+    if (cb >= b.T) return;
+    const int kv_mul = n_heads / n_kv_heads, kvh = h / kv_mul;
+    float* S = scratch + ((size_t)h * gridDim.z + qb) * (size_t)Tmax * kAttQB + lane;
+    block_kv4_stage<HS, RS, 64, 256>(qt, kt, qrows, qs, k_pool, pg, n_kv_heads, h, kvh, qb, cb, b.T, n_tok);
+    __syncthreads();
+    const int c0 = cb + wave * 16;
+    if (c0 >= b.T) return;
+    const int nk = b.T - c0 < 16 ? b.T - c0 : 16;
+    f32x4v q[HS4];
+#pragma unroll
+    for (int u = 0; u < HS4; ++u) q[u] = *reinterpret_cast<const f32x4v*>(qt + lane * RS + u * 4);
+    const float sqrt_hs = sqrtf((float)HS);
+    const float* kv = kt + wave * 16 * RS;
+    constexpr int UB = 2;
+    static_assert(HS4 % (2 * UB) == 0, "head size");
+#pragma unroll 1
+    for (int kk = 0; kk < nk; kk += 4) {
+        const float* kr = kv + kk * RS;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+        f32x4v ka[4][UB], kb[4][UB];
+        att_kread<UB, RS>(ka, kr, 0);
+#pragma unroll
+        for (int u0 = 0; u0 < HS4; u0 += 2 * UB) {
+            att_kread<UB, RS>(kb, kr, u0 + UB);
+            att_kdot<UB>(s0, s1, s2, s3, ka, q + u0);
+            asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+            if (u0 + 2 * UB < HS4) att_kread<UB, RS>(ka, kr, u0 + 2 * UB);
+            att_kdot<UB>(s0, s1, s2, s3, kb, q + u0 + UB);
+            asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+        }
+        const float sc[4] = {s0 / sqrt_hs, s1 / sqrt_hs, s2 / sqrt_hs, s3 / sqrt_hs};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (kk + j < nk) S[(size_t)(c0 + kk + j) * kAttQB] = sc[j];
+    }
+    // the diagonal: this wave owns the lane's own position (p <= T - 1, so p < c0 + 16 is p < c0 + nk) - the f32 key of its qkv row, over S[p]
+    if (b.p >= c0 && b.p < c0 + 16) {
+        const float* kown = qrows + (size_t)b.i * qs + n_heads * HS + kvh * HS;
+        S[(size_t)b.p * kAttQB] = block_kvq_own_dot<HS4>(0.0f, q, kown) / sqrt_hs;
+    }
+}
+// Gemma-2's 256-wide heads: NK keys a workgroup of NT threads, two passes of 128 dims over one chain; the diagonal's key comes from memory
+template <int HS, int NK, int NT>
+KV4_KERNEL __launch_bounds__(NT) void block_kv4_scores_wide_kernel(const float* __restrict__ qrows, int qs, const uint8_t* __restrict__ k_pool, const KvqPages pg,
+                                                                    float* __restrict__ scratch, const DevState* __restrict__ st, int n_heads, int n_kv_heads,
+                                                                    int pos0, int n_tok, int Tmax) {
+    constexpr int HP = HS / 2, RS = HS + 4, HP4 = HP / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* qt = reinterpret_cast<float*>(smem_raw);              // [64][RS]
+    float* kt = qt + 64 * RS;                                    // [NK][RS]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), qb = gridDim.z - 1 - blockIdx.z, h = blockIdx.x;
+    const AttBlock b = att_block(qb, lane, pos0, n_tok);
+    constexpr int KW = NK / (NT / 64);
+    static_assert(KW % 4 == 0 && KW >= 4 && 64 % NK == 0, "four score chains at a time; a chunk lies in one page");
+    const int cb = blockIdx.y * NK;
+    if (cb >= b.T) return;
+    const int kv_mul = n_heads / n_kv_heads, kvh = h / kv_mul;
+    float* S = scratch + ((size_t)h * gridDim.z + qb) * (size_t)Tmax * kAttQB + lane;
+    block_kv4_stage<HS, RS, NK, NT>(qt, kt, qrows, qs, k_pool, pg, n_kv_heads, h, kvh, qb, cb, b.T, n_tok);
+    __syncthreads();
+    const int c0 = cb + wave * KW;
+    if (c0 >= b.T) return;
+    const int nk = b.T - c0 < KW ? b.T - c0 : KW;
+    const float* kv = kt + wave * KW * RS;
+    const bool mine = b.p >= c0 && b.p < c0 + KW;                // this wave owns the lane's own position
+    const float* kown = qrows + (size_t)b.i * qs + n_heads * HS + kvh * HS;
+    float own = 0.0f;
+    float part[KW];
+#pragma unroll
+    for (int i = 0; i < KW; ++i) part[i] = 0.0f;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        f32x4v q[HP4];
+#pragma unroll
+        for (int u = 0; u < HP4; ++u) q[u] = *reinterpret_cast<const f32x4v*>(qt + lane * RS + pass * HP + u * 4);
+#pragma unroll
+        for (int kq = 0; kq < KW / 4; ++kq) {
+            if (kq * 4 < nk) {
+                const float* kr = kv + kq * 4 * RS + pass * HP;
+                float s0 = part[kq * 4 + 0], s1 = part[kq * 4 + 1], s2 = part[kq * 4 + 2], s3 = part[kq * 4 + 3];
+                constexpr int UB = 2;
+                f32x4v ka[4][UB], kb[4][UB];
+                att_kread<UB, RS>(ka, kr, 0);
+#pragma unroll
+                for (int u0 = 0; u0 < HP4; u0 += 2 * UB) {
+                    att_kread<UB, RS>(kb, kr, u0 + UB);
+                    att_kdot<UB>(s0, s1, s2, s3, ka, q + u0);
+                    asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+                    if (u0 + 2 * UB < HP4) att_kread<UB, RS>(ka, kr, u0 + 2 * UB);
+                    att_kdot<UB>(s0, s1, s2, s3, kb, q + u0 + UB);
+                    asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3) : : "memory");
+                }
+                part[kq * 4 + 0] = s0; part[kq * 4 + 1] = s1; part[kq * 4 + 2] = s2; part[kq * 4 + 3] = s3;
+            }
+        }
+        if (mine) own = block_kvq_own_dot<HP4>(own, q, kown + pass * HP);       // the pass's 128 dims of the one chain
+    }
+    const float sqrt_hs = sqrtf((float)HS);
+    const int wb = st->win_base, wpos = wb >= 0 ? wb : (wb == kWinPerQuery ? b.p : pos0);
+#pragma unroll
+    for (int i = 0; i < KW; ++i) {
+        if (i < nk) {
+            const int t = c0 + i;
+            S[(size_t)t * kAttQB] = gemma_cap_window(part[i] / sqrt_hs, wpos, t);
+        }
+    }
+    if (mine) S[(size_t)b.p * kAttQB] = gemma_cap_window(own / sqrt_hs, wpos, b.p);
+}
+
+// A tile's loads: the weights as in the f32 kernels; of the value tile one 16-dim piece a thread (64 * SW / 16 <= NT) - its two raw words and the scale of its
+// group of 32.  vq: bytes into a page's V block of this head's rows at the slice's first dim d0 (of the head); vs: floats into its scales of this head's rows.
+// Threads past the tile repeat its last piece (no load under a branch) and store nothing.
+template <int HS, int NT, int SW, int NS>
+__device__ __forceinline__ void block_kv4_tile_load(f32x4v (&rw)[NS], Kv4Val& rv, const float* Sb, const uint8_t* v_pool, size_t vq, size_t vs, int d0, const KvqPages pg,
+                                                    int t, int T) {
+    constexpr int S16 = SW / 16, NPC = 64 * S16;
+    static_assert(SW % 16 == 0 && NPC <= NT, "a piece a thread");
+    const int tid = threadIdx.x, k0 = t * 64, PL = 1 << pg.shift;
+    const int kc = k0 < T ? k0 : T - 1;                                       // the tile's first key, clamped (a prefetch past the end: the last key's page)
+    const uint8_t* vb = v_pool + (size_t)pg.tab[kc >> pg.shift] * pg.page_bytes;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int f = tid + j * NT, kl = f >> 4, c4 = f & 15;
+        const int key = k0 + kl < T ? k0 + kl : T - 1;
+        const f32x4v w4 = *reinterpret_cast<const f32x4v*>(Sb + (size_t)key * kAttQB + c4 * 4);
+        rw[j] = k0 + kl < T ? w4 : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    const int f = tid < NPC ? tid : NPC - 1, kl = f / S16, c16 = f - kl * S16;
+    const int pin = (k0 + kl < T ? k0 + kl : T - 1) & (PL - 1);
+    rv.w = *reinterpret_cast<const i32x2v*>(vb + vq + (size_t)pin * (HS / 2) + c16 * 8);
+    rv.s = reinterpret_cast<const float*>(vb + pg.q_bytes)[vs + (size_t)pin * (HS / 32) + ((d0 + c16 * 16) >> 5)];
+}
+// att_tile_store with the read-back in it, on the way into the [64][SW] f32 tile att_tile_compute reads
+template <int NT, int SW, int NS>
+__device__ __forceinline__ void block_kv4_tile_store(const f32x4v (&rw)[NS], const Kv4Val& rv, float* dst) {
+    constexpr int S16 = SW / 16;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) { const int f = tid + j * NT; *reinterpret_cast<f32x4v*>(dst + f * 4) = rw[j]; }
+    if (tid < 64 * S16) {
+        f32x4v v[4];
+        kv4_deq8(v[0], v[1], (uint32_t)rv.w[0], rv.s);
+        kv4_deq8(v[2], v[3], (uint32_t)rv.w[1], rv.s);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<f32x4v*>(dst + 64 * 64 + tid * 16 + u * 4) = v[u];           // piece tid: row tid / S16, dims (tid % S16) * 16 ..
+    }
+}
+template <int HS, int NW, int DW>
+KV4_KERNEL __launch_bounds__(NW * 64) void block_kv4_values_kernel(const float* __restrict__ qrows, int qs, const uint8_t* __restrict__ v_pool, const KvqPages pg,
+                                                                    const float* __restrict__ scratch, float* __restrict__ out, int n_heads, int n_kv_heads,
+                                                                    int pos0, int n_tok, int Tmax) {
+    constexpr int NT = NW * 64, SW = NW * DW, NS = 64 * 16 / NT;
+    static_assert(HS % SW == 0 && HS % 32 == 0 && DW % 4 == 0 && (64 * 16) % NT == 0, "slice geometry");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* sm = reinterpret_cast<float*>(smem_raw);
+    constexpr int TILE = 64 * 64 + 64 * SW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = blockIdx.x, sl = blockIdx.z;
+    const int qb = (sl & 1) ? (int)blockIdx.y : (int)(gridDim.y - 1 - blockIdx.y);
+    const AttBlock b = att_block(qb, lane, pos0, n_tok);
+    const int T = b.T, n_tiles = (T + 63) / 64;
+    const int kv_mul = n_heads / n_kv_heads, kvh = h / kv_mul, kv_dim = n_kv_heads * HS, att = n_heads * HS;
+    const float* Sb = scratch + ((size_t)h * gridDim.y + qb) * (size_t)Tmax * kAttQB;
+    const int d0 = sl * SW;                                                   // the slice's first dim of the head
+    const size_t rows = ((size_t)pg.layer * n_kv_heads + kvh) << pg.shift;    // head-major: this head's page_len rows
+    const size_t vq = rows * (HS / 2) + d0 / 2, vs = rows * (HS / 32);
+    const int t_own = (pos0 + qb * kAttQB) >> 6;                              // the first tile with a position of this query block: it and the next are the last two
+    float own[DW];
+    {
+        const float* vown = qrows + (size_t)b.i * qs + att + kv_dim + kvh * HS + d0 + wave * DW;
+#pragma unroll
+        for (int g = 0; g < DW / 4; ++g) {
+            const float4 v4 = *reinterpret_cast<const float4*>(vown + g * 4);
+            own[g * 4] = v4.x; own[g * 4 + 1] = v4.y; own[g * 4 + 2] = v4.z; own[g * 4 + 3] = v4.w;
+        }
+    }
+    f32x4v rwa[NS], rwb[NS];
+    Kv4Val rva, rvb;
+    float acc[DW];
+#pragma unroll
+    for (int d = 0; d < DW; ++d) acc[d] = 0.0f;
+    auto compute = [&](const float* cur, int t) __attribute__((always_inline)) {
+        if (t >= t_own) block_kvq_tile_compute_own<DW, SW>(acc, cur, lane, wave, T - t * 64, b.p - t * 64, own);
+        else att_tile_compute<HS, DW, SW>(acc, cur, lane, wave, T - t * 64);
+    };
+    block_kv4_tile_load<HS, NT, SW, NS>(rwa, rva, Sb, v_pool, vq, vs, d0, pg, 0, T);
+    block_kv4_tile_store<NT, SW, NS>(rwa, rva, sm);
+    block_kv4_tile_load<HS, NT, SW, NS>(rwa, rva, Sb, v_pool, vq, vs, d0, pg, 1, T);
+    block_kv4_tile_load<HS, NT, SW, NS>(rwb, rvb, Sb, v_pool, vq, vs, d0, pg, 2, T);
+    lds_barrier();
+    for (int t = 0; t < n_tiles; t += 2) {
+        compute(sm, t);
+        if (t + 1 < n_tiles) block_kv4_tile_store<NT, SW, NS>(rwa, rva, sm + TILE);
+        block_kv4_tile_load<HS, NT, SW, NS>(rwa, rva, Sb, v_pool, vq, vs, d0, pg, t + 3, T);
+        lds_barrier();
+        if (t + 1 < n_tiles) {
+            compute(sm + TILE, t + 1);
+            if (t + 2 < n_tiles) block_kv4_tile_store<NT, SW, NS>(rwb, rvb, sm);
+            block_kv4_tile_load<HS, NT, SW, NS>(rwb, rvb, Sb, v_pool, vq, vs, d0, pg, t + 4, T);
+            lds_barrier();
+        }
+    }
+    if (b.live) {
+        float* ob = out + (size_t)b.i * att + h * HS + d0 + wave * DW;
+#pragma unroll
+        for (int g = 0; g < DW / 4; ++g) *reinterpret_cast<float4*>(ob + g * 4) = make_float4(acc[g * 4], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3]);
+    }
+}
+
+// launch_kvq_attention_block's choices and refusals over Q4 pages.  a.q: the qkv block as launch_kv4_scatter left it (q and k rotated; row stride
+// att + 2 kv) - the score and the value launch read the rows' own keys and values from it; a.k_cache / a.v_cache: the pool's K and V block of page 0;
+// pv.q_bytes: nib_bytes
+hipError_t launch_kv4_attention_block(const AttnArgs& a, KvqView pv, unsigned table_row, int pos0, int n_tok, float* scratch, int lds_keys, bool long_forms, hipStream_t s) {
+    const int T = pos0 + n_tok, nqb = (n_tok + kAttQB - 1) / kAttQB, nch = (T + 63) / 64;
+    if (!pv.tab || pv.shift < 6 || pv.per_slot < 1 || !pv.q_bytes || n_tok < 1 || pos0 < 0 || T > a.seq_len || ((T - 1) >> pv.shift) >= pv.per_slot) return hipErrorInvalidValue;
+    const int qs = (a.n_heads + 2 * a.n_kv_heads) * a.head_size;
+    const KvqPages pg{pv.tab + (size_t)table_row * pv.per_slot, pv.shift, pv.page_bytes, pv.q_bytes, a.layer};
+    const uint8_t* k_pool = reinterpret_cast<const uint8_t*>(a.k_cache);
+    const uint8_t* v_pool = reinterpret_cast<const uint8_t*>(a.v_cache);
+    const bool in_lds = T <= lds_keys;
+    const size_t sm = (kAttSW * 64 + kAttSQ + (in_lds ? (size_t)(T + 48) * kAttSQ : 0)) * sizeof(float);
+    allow_big_lds(reinterpret_cast<const void*>(att_softmax_kernel<true>));
+    auto softmax = [&]() {
+        if (in_lds) hipLaunchKernelGGL(att_softmax_kernel<true>, dim3(a.n_heads, nqb, kAttQB / kAttSQ), dim3(kAttSW * 64), sm, s, pos0, n_tok, scratch, T);
+        else hipLaunchKernelGGL(att_softmax_kernel<false>, dim3(a.n_heads, nqb, kAttQB / kAttSQ), dim3(kAttSW * 64), sm, s, pos0, n_tok, scratch, T);
+    };
+#define V4(HS_, NW_, DW_)                                                                                                             \
+    {                                                                                                                                 \
+        allow_big_lds(reinterpret_cast<const void*>(block_kv4_values_kernel<HS_, NW_, DW_>));                                         \
+        hipLaunchKernelGGL((block_kv4_values_kernel<HS_, NW_, DW_>), dim3(a.n_heads, nqb, HS_ / (NW_ * DW_)), dim3(NW_ * 64), 2 * (64 * 64 + 64 * NW_ * DW_) * sizeof(float), s, \
+                           (const float*)a.q, qs, v_pool, pg, (const float*)scratch, a.out, a.n_heads, a.n_kv_heads, pos0, n_tok, T); \
+        return hipGetLastError();                                                                                                     \
+    }
+#define B4(HS_, NW_, DW_)                                                                                                             \
+    {                                                                                                                                 \
+        hipLaunchKernelGGL((block_kv4_scores_kernel<HS_>), dim3(a.n_heads, nch, nqb), dim3(256), 0, s, (const float*)a.q, qs, k_pool, pg, scratch,        \
+                           a.n_heads, a.n_kv_heads, pos0, n_tok, T);                                                                  \
+        softmax();                                                                                                                    \
+        V4(HS_, NW_, DW_)                                                                                                             \
+    }
+    if (a.gemma) {
+        if (a.head_size != 256) return hipErrorInvalidValue;
+        int live64 = 0;
+        for (int qb = 0; qb < nqb; ++qb) { const int last = qb * kAttQB + kAttQB - 1 < n_tok - 1 ? qb * kAttQB + kAttQB - 1 : n_tok - 1; live64 += (pos0 + last + 1 + 63) / 64; }
+        live64 *= a.n_heads;
+        if (live64 < 512 && !long_forms) {
+            constexpr size_t smem32 = (size_t)(64 + 32) * (256 + 4) * sizeof(float);
+            allow_big_lds(reinterpret_cast<const void*>(block_kv4_scores_wide_kernel<256, 32, 512>));
+            hipLaunchKernelGGL((block_kv4_scores_wide_kernel<256, 32, 512>), dim3(a.n_heads, (T + 31) / 32, nqb), dim3(512), smem32, s, (const float*)a.q, qs, k_pool, pg,
+                               scratch, a.st, a.n_heads, a.n_kv_heads, pos0, n_tok, T);
+        } else {
+            constexpr size_t wide_smem = (size_t)2 * 64 * (256 + 4) * sizeof(float);
+            allow_big_lds(reinterpret_cast<const void*>(block_kv4_scores_wide_kernel<256, 64, 256>));
+            hipLaunchKernelGGL((block_kv4_scores_wide_kernel<256, 64, 256>), dim3(a.n_heads, nch, nqb), dim3(256), wide_smem, s, (const float*)a.q, qs, k_pool, pg,
+                               scratch, a.st, a.n_heads, a.n_kv_heads, pos0, n_tok, T);
+        }
+        softmax();
+        if (a.n_heads * nqb * 4 < 256 && !long_forms) V4(256, 8, 4)
+        V4(256, 8, 8)
+    }
+    switch (a.head_size) { case 64: B4(64, 8, 4) case 96: B4(96, 4, 12) case 128: B4(128, 8, 8) default: return hipErrorInvalidValue; }
+#undef B4
+#undef V4
 }
 #undef KV4_KERNEL

@@ -173,7 +173,7 @@ public:
         check(lmrs_batch_create_paged_q8(t.ctx_, n_slots, page_len, n_pages, &b_));
     }
     // ... or in 4 bits (Q4{}): the reference's Q4_0 rule at a group of 32, 0.625 bytes a value; read back as (float)(nibble - 8) * scale, the row's own key and
-    // value in f32; every prompt chunk takes the table pass  (lmrs_batch_create_paged_q4)
+    // value in f32; a prompt chunk of 320 rows or more takes block attention over the Q4 pages, a shorter one the table pass  (lmrs_batch_create_paged_q4)
     struct Q4 {};
     Batch(Transformer& t, std::uint32_t n_slots, std::uint32_t page_len, std::uint32_t n_pages, Q4) : vocab_size_(t.args.vocab_size) {
         check(lmrs_batch_create_paged_q4(t.ctx_, n_slots, page_len, n_pages, &b_));

@@ -25,7 +25,11 @@ lmrs_batch_create_wide the mode prints the pass times and the n = 16 line only: 
 same paged batches with lmrs_batch_debug_prefill_table (every chunk through the table pass: the routing before), and on a Q8 paged batch under the library's
 rule and forced to the table pass, the forms by turns (paged_prefill_main below)
        (writes profiles/batch_kvq_prefill_llama1b.txt, profiles/batch_kvq_prefill_gemma2b_q4.txt; the five f32 forms alone were recorded in
-       profiles/batch_paged_prefill_*.txt)"""
+       profiles/batch_paged_prefill_*.txt)
+       python tools/batch_rate.py --paged-prefill --kv q4 [model] [q8_0|q4_0]
+--paged-prefill --kv q4: 320 .. 512 tokens on a Q4 paged batch under the library's rule (block attention over Q4 pages) and forced to the table pass, by turns
+beside the f32 and the Q8 paged batch's block attention
+       (writes profiles/batch_kv4_prefill_llama1b.txt, profiles/batch_kv4_prefill_gemma2b_q4.txt)"""
 import os
 import statistics
 import sys
@@ -211,13 +215,22 @@ def paged_main(argv):
 PREFILL_OUT = {("llama-3.2-1b", S.Q8_0): "batch_kvq_prefill_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_kvq_prefill_gemma2b_q4.txt"}
 PREFILL_CASES = [(16, 0), (32, 0), (64, 0), (80, 0), (96, 0), (112, 0), (128, 0), (256, 0), (512, 0), (512, 512)]   # (tokens, start position); 80 .. 112: around the crossover
 
+# --kv q4: from kKv4BlockMin rows on, a 64-query block at a time
+KV4_PREFILL_OUT = {("llama-3.2-1b", S.Q8_0): "batch_kv4_prefill_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_kv4_prefill_gemma2b_q4.txt"}
+KV4_PREFILL_CASES = [(320, 0), (384, 0), (448, 0), (512, 0)]
+
 
 def paged_prefill_main(argv):
     """--paged-prefill [model] [q8_0|q4_0]: host wall time of the synchronous lmrs_batch_prefill call into slot 0, in one process, seven forms by turns,
     three turns, median of 5 calls after 1 warm-up a turn: (a) the wide batch; (b) paged batches of page_len 64 and 256 under the library's routing; (c) the
     same two with lmrs_batch_debug_prefill_table(1) - every chunk through the table pass, one workgroup per (head, row); (d) a Q8 paged batch of page_len 64
     under the library's rule (block attention over int8 pages from 256 rows on) and (e) the same forced to the table pass.  Per form and length the median
-    of its turns (fastest .. slowest turn), lmrs_batch_prefill_form's answer, and whether the forms of one K/V format leave the same last K row."""
+    of its turns (fastest .. slowest turn), lmrs_batch_prefill_form's answer, and whether the forms of one K/V format leave the same last K row.
+    --kv q4 in front of the model: four forms at 320 .. 512 rows - f32, Q8 and Q4 pages of page_len 64 under the library's rule (block attention on all three)
+    and the Q4 pages forced to the table pass; a length at which Q4 block attention is not faster than its table pass outside the turns' spread is a MISS."""
+    q4 = argv[:2] == ["--kv", "q4"]
+    if q4:
+        argv = argv[2:]
     model = argv[0] if argv else "llama-3.2-1b"
     qname = argv[1] if len(argv) > 1 else "q8_0"
     qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
@@ -228,21 +241,25 @@ def paged_prefill_main(argv):
 
     img = S.build_image(model, qt, 1234)
     m = lmrs_amd.Transformer(img)
-    say(f"python tools/batch_rate.py --paged-prefill {model} {qname}")
+    say(f"python tools/batch_rate.py --paged-prefill {'--kv q4 ' if q4 else ''}{model} {qname}")
     say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
-    say("lmrs_batch_prefill into slot 0, host wall time of the synchronous call: seven forms by turns, three turns, median of 5 calls after 1 warm-up a turn; "
-        "per form the median of its turns (fastest .. slowest turn); form = lmrs_batch_prefill_form's (chunks, of them block attention)")
     forms = [("wide", None, False), ("paged 64", 64, False), ("paged 256", 256, False), ("paged 64 table", 64, True), ("paged 256 table", 256, True),
              ("q8 64", 64, False), ("q8 64 table", 64, True)]
+    if q4:
+        forms = [("paged 64", 64, False), ("q8 64", 64, False), ("q4 64", 64, False), ("q4 64 table", 64, True)]
+    say(f"lmrs_batch_prefill into slot 0, host wall time of the synchronous call: {len(forms)} forms by turns, three turns, median of 5 calls after 1 warm-up a turn; "
+        "per form the median of its turns (fastest .. slowest turn); form = lmrs_batch_prefill_form's (chunks, of them block attention)")
     prompt = S.prompt_tokens(model, 1024, 100)
     batches = {}
     for name, pl, table in forms:
-        b = lmrs_amd.Batch(m, 2, wide=True) if pl is None else lmrs_amd.Batch(m, 2, page_len=pl, n_pages=2 * (1024 // pl), kv="q8" if name.startswith("q8") else "f32")
+        kv = name.split()[0] if name[0] == "q" else "f32"
+        b = lmrs_amd.Batch(m, 2, wide=True) if pl is None else lmrs_amd.Batch(m, 2, page_len=pl, n_pages=2 * (1024 // pl), kv=kv)
         if table:
             b.debug_prefill_table(True)
         batches[name] = b
     nl = m.args.n_layers
-    for n, start in PREFILL_CASES:
+    first = forms[0][0]                                     # the form the others' times are quoted against
+    for n, start in (KV4_PREFILL_CASES if q4 else PREFILL_CASES):
         toks = prompt[start:start + n]
         turns, last = {name: [] for name, _, _ in forms}, {}
         for b in batches.values():
@@ -259,25 +276,29 @@ def paged_prefill_main(argv):
                 turns[name].append(us / 1e3)
         for name, _pl, _t in forms:
             last[name] = batches[name].kv_row(0, 0, nl - 1, start + n - 1).view(np.uint32).copy()
-        w = statistics.median(turns["wide"])
+        w = statistics.median(turns[first])
         for name, pl, table in forms:
             t = turns[name]
-            note = f"{statistics.median(t) / w:5.2f}x wide"
-            if pl is not None and not table:
+            note = f"{statistics.median(t) / w:5.2f}x {first}"
+            if pl is not None and not table and name + " table" in turns:
                 old = turns[name + " table"]
                 note += f"   {statistics.median(t) / statistics.median(old):5.2f}x its table pass; slowest turn below the table pass's fastest: {max(t) < min(old)}"
-                if name.startswith("q8"):
+                if name[0] == "q":
                     note += f"; {statistics.median(t) / statistics.median(turns['paged 64']):5.2f}x the f32 pages"
-                if name.startswith("q8") and batches[name].prefill_form(n, start)[1]:
-                    # the condition of DESIGN.md 4.4.17: faster than the table pass by more than the larger turn-to-turn spread of the two forms
+                if name.startswith("q4"):
+                    note += f", {statistics.median(t) / statistics.median(turns['q8 64']):5.2f}x the Q8 pages"
+                if name[0] == "q" and batches[name].prefill_form(n, start)[1]:
+                    # the condition of DESIGN.md 4.4.17 / 4.4.19: faster than the table pass by more than the larger turn-to-turn spread of the two forms
                     gap, spread = statistics.median(old) - statistics.median(t), max(max(t) - min(t), max(old) - min(old))
-                    note += f"; gap {gap:.3f} ms against spread {spread:.3f} ms: {'wins' if gap > spread else 'NO WIN'}"
+                    note += f"; gap {gap:.3f} ms against spread {spread:.3f} ms: {'wins' if gap > spread else '** MISS **' if q4 else 'NO WIN'}"
             say(f"  {n:3d} tokens at {start:3d}, {name:15s} form {batches[name].prefill_form(n, start)}  {statistics.median(t):8.3f} ms ({min(t):.3f} .. {max(t):.3f})   {note}")
-        same = all((last[name] == last["q8 64" if name.startswith("q8") else "wide"]).all() for name, _, _ in forms)
-        say(f"      the f32 forms leave the same last K row, and so do the Q8 forms: {same}")
+        # per K/V format the forms' last K row against the format's first form
+        head = {}
+        same = all((last[name] == last[head.setdefault(name.split()[0] if name[0] == "q" else "f32", name)]).all() for name, _, _ in forms)
+        say(f"      the forms of one K/V format leave the same last K row: {same}")
     for b in batches.values():
         b.close()
-    name = PREFILL_OUT.get((model, qt))
+    name = (KV4_PREFILL_OUT if q4 else PREFILL_OUT).get((model, qt))
     path = os.environ.get("BATCH_RATE_OUT") or (os.path.join(ROOT, "profiles", name) if name else None)
     if path:
         with open(path, "w") as f:
@@ -454,7 +475,7 @@ def kvq_main(argv):
                 say(f"  {depth:4d} positions, n={n:2d}, {name:9s}  {statistics.median(t):8.1f} us per pass ({min(t):.1f} .. {max(t):.1f})   {statistics.median(t) / w - 1:+6.1%} against f32 pages")
             say(f"      tokens equal between the pools (not expected: Q8 is another rule): {bool((ids['f32 pages'] == ids['q8 pages']).all())}")
         if depth == 1000:
-            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): block attention on f32 and on Q8 pages (see prefill_form), the table pass on Q4 pages")
+            say("lmrs_batch_prefill of 512 tokens into slot 1 (host wall time of the synchronous call, median of 5 after 1 warm-up): block attention on f32, on Q8 and on Q4 pages (lmrs_batch_prefill_form's answer beside each)")
             for name, _kv in forms:
                 b = batches[name]
 
