@@ -386,6 +386,44 @@ int lmrs_batch_forward_runs(lmrs_batch* b, uint32_t n_runs, const uint32_t* slot
                             const uint32_t* n_out, const uint32_t* tokens, uint32_t* argmax, float* logits,
                             uint32_t k, uint32_t* topk_idx, float* topk_logprob);
 
+/* ---- token trees in ONE weight pass (tree speculation: Medusa / EAGLE / SpecInfer style drafts, or a drafter's top-2 at every step).
+ * A call carries n_trees trees (1 .. the batch's width), one per slot, slots distinct.  Tree i has n_nodes[i] nodes (1 .. 64), numbered so
+ * that a parent precedes its children: parent[j] is LMRS_TREE_ROOT or an index < j of the same tree; several nodes may hang off the root.
+ * depth(j) = 0 under the root, else depth(parent[j]) + 1.  parent / tokens hold the trees one after another (sum of n_nodes entries).
+ * Node j = Transformer::forward(tokens[j], start_pos[i] + depth(j)) (src/transformer.rs:316-384) on a context that holds positions
+ * 0 .. start_pos[i] - 1 of the slot as they stand, then the tokens of j's ancestors, root-most first - and nothing of its siblings.  Every
+ * node is an output row, in node order, tree after tree; argmax, logits and top-k are defined as in lmrs_batch_forward_runs, and every
+ * output carries the bits the per-sequence calls give when they are fed that path token by token.
+ * STORAGE: node j's K row (rotated for its LOGICAL position start_pos + depth(j)) and its V row are kept at cache position start_pos + j;
+ * the call writes positions [start_pos, start_pos + n_nodes) of the slot.  On a paged batch the page accounting is that of a run of
+ * n_nodes rows at start_pos (claim, clear, copy on write, the "pages wanted / pages free" refusal that changes nothing).  A tree with
+ * parent[j] == j - 1 is a run: the call then returns lmrs_batch_forward_runs' bits, K/V rows included.
+ * Masks and filters are constants of a slot and apply to every node's row.  The call does NOT write the token record: a caller that keeps
+ * the record calls lmrs_batch_set_history for the tokens it accepted.
+ * Errors, each with a message of its own and before any device work: lmrs_batch_forward_runs' list, and n_nodes outside 1 .. 64, more
+ * than 512 nodes in all, a parent that is neither LMRS_TREE_ROOT nor below its own index, start_pos + n_nodes > seq_len, a slot with
+ * penalties set (the record has no notion of a path) or with an automaton attached (its state is per slot, not per node), a Q8 or Q4
+ * page pool (not built yet). */
+#define LMRS_TREE_ROOT 0xFFFFFFFFu
+int lmrs_batch_forward_tree(lmrs_batch* b, uint32_t n_trees, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* n_nodes,
+                            const uint32_t* parent, const uint32_t* tokens, uint32_t* argmax, float* logits,
+                            uint32_t k, uint32_t* topk_idx, float* topk_logprob);
+/* Make an accepted path the slot's next positions.  Stateless: entry i (slots distinct) moves the K and V rows of every layer from storage
+ * position start_pos[i] + path[j] to start_pos[i] + j, j = 0 .. path_len[i] - 1 (path: the entries' node indexes one after another, root-most
+ * first).  An entry with path[j] == j everywhere moves nothing; a call where nothing moves launches nothing.  path must be strictly ascending
+ * (so path[j] >= j; the ancestors of a node always are) and start_pos + path[last] must lie inside seq_len.  That the indexes form a
+ * root-to-node path of the tree just run is the caller's business, as stale draft rows already are.  On a paged batch the destination
+ * range [start_pos, start_pos + path_len) of an entry that moves a row goes through the write accounting of any write.  Positions behind
+ * the path stay stale; lmrs_batch_release gives their pages back. */
+int lmrs_batch_accept_path(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* path_len,
+                           const uint32_t* path);
+/* Greedy acceptance, host arithmetic (no context): `expected` is the argmax of the row in front of the tree; from the root follow the child
+ * of the current node whose token equals the expected token (the lowest index among several), then expected = argmax[that node], until no
+ * child matches.  path (room for n_nodes) / *path_len: the accepted nodes, root-most first; *next: the final expected token - the one
+ * greedy decoding feeds next.  n_nodes 0 .. 64, parents as in lmrs_batch_forward_tree. */
+int lmrs_tree_accept(uint32_t n_nodes, const uint32_t* parent, const uint32_t* tokens, const uint32_t* argmax, uint32_t expected,
+                     uint32_t* path, uint32_t* path_len, uint32_t* next);
+
 /* verification aid, as lmrs_debug_kv */
 int lmrs_batch_debug_kv(lmrs_batch* b, uint32_t slot, int which, uint32_t layer, uint32_t pos, float* out);
 

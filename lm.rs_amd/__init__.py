@@ -40,6 +40,7 @@ EXPORTS = [
     "lmrs_batch_generate_topp", "lmrs_sampler_candidates", "lmrs_sampler_set_candidates", "lmrs_op_topp_rows", "lmrs_bench_topp_rows",
     "lmrs_automaton_check", "lmrs_automaton_walk", "lmrs_batch_automaton_create", "lmrs_batch_automaton_destroy", "lmrs_batch_attach_automaton",
     "lmrs_batch_automaton_state", "lmrs_batch_automaton_advance", "lmrs_op_automaton_masks",
+    "lmrs_batch_forward_tree", "lmrs_batch_accept_path", "lmrs_tree_accept",
     "lmrs_last_error",
     "lmrs_op_matmul_q8", "lmrs_op_matmul_q4", "lmrs_op_quantize", "lmrs_op_quantize_q4", "lmrs_op_rmsnorm",
     "lmrs_op_softmax", "lmrs_op_expf", "lmrs_op_tanh_cast", "lmrs_forward_sample", "lmrs_sampler_info", "lmrs_op_sample_mult", "lmrs_op_classifier_argmax", "lmrs_bench_gemv", "lmrs_bench_step", "lmrs_step_info", "lmrs_debug_timeline", "lmrs_debug_kv", "lmrs_debug_inject", "lmrs_last_fill_ms", "lmrs_debug_gemm_tile", "lmrs_debug_w13_quant",
@@ -155,6 +156,9 @@ def lib():
         L.lmrs_batch_generate.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
         L.lmrs_batch_debug_kv.argtypes = [vp, u32, C.c_int, u32, u32, vp]
         L.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.lmrs_batch_forward_tree.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.lmrs_batch_accept_path.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.lmrs_tree_accept.argtypes = [u32, vp, vp, vp, u32, vp, C.POINTER(u32), C.POINTER(u32)]
         L.lmrs_batch_forward_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.lmrs_batch_forward_runs_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.lmrs_batch_prefill_embeddings.argtypes = [vp, u32, vp, u32, u32, vp]
@@ -454,6 +458,7 @@ def unpack_mask(words, vocab_size: int) -> np.ndarray:
 
 
 BATCH_CTX = 0xFFFFFFFF        # Batch.fork's src: the model's own cache (LMRS_BATCH_CTX)
+TREE_ROOT = 0xFFFFFFFF        # a node under the root in lmrs_batch_forward_tree's parent array (LMRS_TREE_ROOT); Batch.forward_tree takes None
 TOKEN_NONE = 0xFFFFFFFF       # Batch.history / set_history: a position whose token is unknown, or an embedding row (LMRS_TOKEN_NONE)
 STOP_MAX = 16                 # Batch.generate: the most stop tokens a row takes (LMRS_STOP_MAX)
 FINISH_BUDGET, FINISH_STOP = 0, 1     # Batch.generate's finish codes (LMRS_FINISH_BUDGET / LMRS_FINISH_STOP)
@@ -882,6 +887,34 @@ class Batch:
         out = (am,) + ((lg,) if logits else ()) + ((ti, tl) if k else ())
         return out if len(out) > 1 else am
 
+    def forward_tree(self, trees, k: int = 0, logits: bool = False):
+        """One pass over token trees = [(slot, start_pos, parents, tokens), ...]: tree i hangs off position start_pos of its slot; parents[j] is None
+        (under the root) or the index < j of node j's parent.  Node j is fed at start_pos + depth(j) on the slot's positions below start_pos followed by
+        its ancestors' tokens; its K/V rows are stored at start_pos + j.  Up to `width` trees, 64 nodes each, 512 in all; every node is an output, in node
+        order, tree after tree -> argmax uint32 [N], or the tuple (argmax[, logits][, topk_idx, topk_logprob]) as forward_runs  (lmrs_batch_forward_tree)"""
+        s, p = (np.array([t[i] for t in trees], np.uint32) for i in (0, 1))
+        n = np.array([len(t[2]) for t in trees], np.uint32)
+        par = np.array([TREE_ROOT if q is None else q for t in trees for q in t[2]], np.uint32)
+        tok = np.concatenate([np.ascontiguousarray(t[3], np.uint32).reshape(-1) for t in trees]) if trees else np.empty(0, np.uint32)
+        if tok.size != par.size:
+            raise ValueError("forward_tree: a tree's parents and tokens differ in length")
+        N, V = int(par.size), self.model.args.vocab_size
+        am = np.empty(N, np.uint32)
+        lg = np.empty((N, V), np.float32) if logits else None
+        ti, tl = (np.empty((N, k), np.uint32), np.empty((N, k), np.float32)) if k else (None, None)
+        _chk(lib().lmrs_batch_forward_tree(self._h, len(trees), _p(s), _p(p), _p(n), _p(par), _p(tok), _p(am), _p(lg) if logits else None,
+                                           k, _p(ti) if k else None, _p(tl) if k else None))
+        out = (am,) + ((lg,) if logits else ()) + ((ti, tl) if k else ())
+        return out if len(out) > 1 else am
+
+    def accept_path(self, paths):
+        """Make accepted paths the slots' next positions: paths = [(slot, start_pos, [node, ...]), ...], the nodes root-most first.  The K/V rows stored
+        at start_pos + node move to start_pos + 0, 1, ..; positions behind a path stay stale  (lmrs_batch_accept_path)"""
+        s, p = (np.array([t[i] for t in paths], np.uint32) for i in (0, 1))
+        n = np.array([len(t[2]) for t in paths], np.uint32)
+        path = np.array([q for t in paths for q in t[2]], np.uint32)
+        _chk(lib().lmrs_batch_accept_path(self._h, len(paths), _p(s), _p(p), _p(n), _p(path) if path.size else _p(np.zeros(1, np.uint32))))
+
     def forward_runs_sample(self, runs):
         """forward_runs' pass over runs = [(slot, start_pos, tokens, sampler_or_None), ...] with the LAST row of every run that has a Sampler sampled
         ON THE DEVICE with it; None: the run leaves its K/V rows only (a prompt chunk that is not the last).  Up to `width` runs, 512 tokens in all; runs
@@ -1217,6 +1250,19 @@ def draft_lookup(hist, ngram_max: int, max_draft: int) -> np.ndarray:
     d = np.zeros(max(int(max_draft), 1), np.uint32); n = C.c_uint32()
     _chk(lib().lmrs_draft_lookup(_p(h), h.size, ngram_max, max_draft, _p(d), C.byref(n)))
     return d[:n.value].copy()
+
+
+def tree_accept(parents, tokens, argmax, expected: int):
+    """Greedy acceptance over a verified tree, host only: from `expected` (the argmax of the row in front of the tree) follow the child whose token is
+    the expected one (the lowest index among several), expected becoming that node's argmax, until no child matches -> (path, next): the accepted node
+    indexes root-most first, and the token greedy decoding feeds next (lmrs_tree_accept)."""
+    par = np.array([TREE_ROOT if q is None else q for q in parents], np.uint32)
+    tok, am = (np.ascontiguousarray(x, np.uint32).reshape(-1) for x in (tokens, argmax))
+    if not par.size == tok.size == am.size:
+        raise ValueError("tree_accept: parents, tokens and argmax differ in length")
+    path = np.zeros(max(par.size, 1), np.uint32); n, nxt = C.c_uint32(), C.c_uint32()
+    _chk(lib().lmrs_tree_accept(par.size, _p(par), _p(tok), _p(am), expected, _p(path), C.byref(n), C.byref(nxt)))
+    return [int(x) for x in path[:n.value]], int(nxt.value)
 
 
 def debug_gemm_wide(xq, xs, wq, ws, n: int, o: int, n_tok: int, q4: bool = False, device: int = 0) -> np.ndarray:

@@ -207,7 +207,9 @@ struct AutoView { const AutoRow* of = nullptr; const AutoRow* h_of = nullptr; co
 // top_k / min_gap in the order the classifier sees the rows, slot -1 for none; h_of is its pinned source, as with the masks
 struct FilterView { const FilterRow* of = nullptr; const FilterRow* h_of = nullptr; };
 struct PenaltyView { const uint32_t* hist = nullptr; int seq_len = 0; const int* pos = nullptr; const PenaltyRow* of = nullptr; const PenaltyRow* h_of = nullptr; int max_n = 0; };
-struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; size_t kvq_bytes = 0; bool kv4 = false; };   // kv4: the pool holds Q4 pages (lmrs_kv4.inc), kvq_bytes values a K / V block, no block attention; else kvq_bytes != 0: the pool holds Q8 pages (lmrs_kvq.inc), that many int8 bytes a K / V block; pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+struct PassForm { bool skinny = false; const RowTable* rows = nullptr; int max_T = 0; float *k_cache = nullptr, *v_cache = nullptr; RowView runs{}; TreeView tree{}; float* qkv = nullptr; PageView pages{}; MaskView masks{}; AutoView autos{}; PenaltyView penalties{}; FilterView filters{}; int block_pos0 = -1; uint32_t block_row = 0; size_t kvq_bytes = 0; bool kv4 = false; };   // kv4: the pool holds Q4 pages (lmrs_kv4.inc), kvq_bytes values a K / V block, no block attention; else kvq_bytes != 0: the pool holds Q8 pages (lmrs_kvq.inc), that many int8 bytes a K / V block; pages.tab != null: the table pass of a paged batch - k_cache / v_cache are the pool's, the rows' off words table rows; block_pos0 >= 0: its rows are the consecutive positions of ONE slot (page row block_row) from there on, in position order - block attention over the pages
+// tree (tree.rows != null): the runs' table is lmrs_batch_forward_tree's - its pos column the nodes' LOGICAL positions, tree.rows their storage positions and ancestor
+// lists (lmrs_tree.inc); the scatter and the attention are the tree's, over contiguous slots or f32 pages; everything else is the ragged pass
 // The whole rule, by position: split attention from att_split_pos on, bucket b covering positions below 1024 << b; below it the merged launch where
 // it reaches.  merged = false: the separate kernels whatever the position (steps enqueued because the runtime refused to capture them, the layer
 // passes of fill_kv_cache).
@@ -1520,7 +1522,11 @@ static int prefill_layers(lmrs_ctx* c, PassForm form, int m, int p0) {
         t.q = qkv; t.k_raw = nullptr; t.k_cache = k_cache; t.v_cache = v_cache; t.rope = c->rope; t.out = c->pf_ao;
         t.n_heads = att / hs; t.n_kv_heads = kv / hs; t.head_size = hs; t.seq_len = (int)a.seq_len; t.layer = (int)l;
         t.gemma = gemma; t.st = c->st;
-        if (form.pages.tab) {
+        if (form.tree.rows) {
+            // a pass over token trees: rotation by the logical position, K / V rows to the storage position, attention over each node's own path
+            HIP_OK(launch_tree_scatter(qkv, k_cache, v_cache, c->rope, form.runs, form.tree, form.pages, t.n_heads, t.n_kv_heads, hs, t.seq_len, t.layer, m, c->stream));
+            HIP_OK(launch_tree_attention(t, form.runs, form.tree, form.pages, m, form.max_T, c->stream));
+        } else if (form.pages.tab) {
             // a paged batch: the table pass (either table, as a RowView) with every K / V address looked up in the slot's page row
             const RowView rv = form.rows ? RowView{form.rows->off, form.rows->pos, form.rows->tok} : form.runs;
             if (form.kv4) {
@@ -2128,6 +2134,9 @@ struct lmrs_batch {
     SampleSet samp, rs;
     DevBuf<unsigned long long> cs_keys; PinBuf<unsigned long long> h_cs_pairs; size_t cs_words = 0;
     DevBuf<float> embed_stage;                          // the embedding rows of a ragged pass, [kRunRowsMax][dim] in caller order (allocated at the first call that has one)
+    // lmrs_batch_forward_tree / lmrs_batch_accept_path (made at the first call of either, all or nothing): a TreeRow beside every row of the long table, the
+    // moves of an accept call, and their pinned sources
+    DevBuf<TreeRow> tree_rows; PinBuf<TreeRow> h_tree_rows; DevBuf<TreeMove> tree_moves; PinBuf<TreeMove> h_tree_moves;
     // a paged batch (lmrs_batch_create_paged): kv is the pool - page p's K block at kv + p * 2 * page_floats, its V block page_floats behind, page 0 the zero
     // page; the accounting (lmrs_pages.h), the device page table [n_slots][per_slot] and its pinned mirror
     std::unique_ptr<PagePool> pool; uint32_t page_len = 0; size_t page_floats = 0;
@@ -2937,11 +2946,13 @@ static int source_rows(lmrs_ctx* c, const uint32_t* src, const float* staged, in
     HIP_OK(launch_source_rows(c->emb_q, c->emb_s, c->q4, src, staged, m, (int)c->args.dim, c->pf_x, c->stream, scale));
     return 0;
 }
-static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to, const float* staged = nullptr) {
+// tree: the table is tree_table's (lmrs_batch_forward_tree) - the tree's scatter and attention, and no token record (a position of it is a path's, not a node's)
+static int runs_pass(lmrs_batch* b, size_t R, size_t O, uint32_t step, RowSink to, const float* staged = nullptr, TreeView tree = TreeView{nullptr}) {
     lmrs_ctx* c = b->c;
     PassForm form; form.skinny = R <= kStreamPassMax; form.runs = b->runs_view(); form.max_T = b->h_runs->pos[0] + (int)step + 1; form.qkv = b->runs_qkv;
     form.k_cache = b->kv; form.v_cache = b->kv + (b->pool ? b->page_floats : b->slot_floats); form.pages = b->page_view(); form.kvq_bytes = b->kvq_bytes; form.kv4 = b->kv4;
-    if (record_rows(b, form.runs.pos, form.runs.tok, R)) return -1;
+    form.tree = tree;
+    if (!tree.rows && record_rows(b, form.runs.pos, form.runs.tok, R)) return -1;
     if ((staged ? source_rows(c, form.runs.tok, staged, (int)R) : token_rows(c, form.runs.tok, (int)R)) || prefill_pass(c, form, (int)R, 0)) return -1;
     if (!O) return 0;                                    // K/V rows only: neither the final norm nor the classifier runs
     HIP_OK(launch_select_rows(c->pf_x, b->runs->sel, b->runs_x, (int)c->args.dim, (int)O, c->stream));
@@ -3387,6 +3398,156 @@ extern "C" int lmrs_batch_forward_runs_embed(lmrs_batch* b, uint32_t n_runs, con
     if (!b) return fail(what + "NULL argument (the batch)");
     if (!slot || !start_pos || !run_len || !n_out || !run_kind) return fail(what + "NULL array");
     return forward_runs_from(what, b, n_runs, slot, start_pos, run_len, n_out, RunRows{run_kind, tokens, embeddings}, argmax, logits, k, topk_idx, topk_logprob);
+}
+
+// ------------------------------------------------------------------ token trees in a pass (lmrs_batch_forward_tree, lmrs_batch_accept_path; no reference counterpart:
+// per node Transformer::forward over the node's root-to-node path on a context that holds only the slot's prefix).  The kernels and the two positions of a
+// node: lmrs_tree.inc.  Everything behind the attention is the ragged pass.
+static int tree_alloc(lmrs_batch* b, const std::string& what) {
+    if (b->tree_rows) return 0;
+    if (!alloc_all({{b->tree_rows, (size_t)kRunRowsMax}, {b->h_tree_rows, (size_t)kRunRowsMax}, {b->tree_moves, (size_t)kTreeMovesMax}, {b->h_tree_moves, (size_t)kTreeMovesMax}})) {
+        (void)hipGetLastError();
+        return fail(what + "the trees' row and move tables: out of memory");
+    }
+    return 0;
+}
+// runs_table for trees (the arguments checked by the caller): the long table with the nodes' LOGICAL positions, deepest first, and beside every row its
+// TreeRow - the tree's base, the node's storage position, its ancestors root-most first and itself.  Every node is an output, in node order, tree after tree.
+static void tree_table(lmrs_batch* b, uint32_t n_trees, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* n_nodes, const uint32_t* parent,
+                       const uint32_t* tokens, size_t* rows_out) {
+    struct Row { uint32_t tree, node, depth; };
+    std::vector<Row> rows;
+    std::vector<uint32_t> first(n_trees);
+    for (uint32_t i = 0, j0 = 0; i < n_trees; j0 += n_nodes[i++]) {
+        first[i] = j0;
+        for (uint32_t j = 0; j < n_nodes[i]; ++j) rows.push_back(Row{i, j, parent[j0 + j] == LMRS_TREE_ROOT ? 0u : rows[j0 + parent[j0 + j]].depth + 1});
+    }
+    const size_t R = rows.size();
+    std::vector<int> order(R);
+    for (size_t j = 0; j < R; ++j) order[j] = (int)j;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return start_pos[rows[x].tree] + rows[x].depth > start_pos[rows[y].tree] + rows[y].depth; });
+    RunTable* h = b->h_runs;
+    for (size_t r = 0; r < R; ++r) {
+        const int j = order[r];
+        const Row& n = rows[j];
+        const uint32_t j0 = first[n.tree];
+        h->off[r] = b->off_of(slot[n.tree]); h->pos[r] = (int)(start_pos[n.tree] + n.depth); h->tok[r] = tokens[j];
+        h->sel[j] = (uint32_t)r;
+        TreeRow& t = b->h_tree_rows[r];
+        t.base = (int)start_pos[n.tree]; t.spos = (int)(start_pos[n.tree] + n.node);
+        uint32_t a = n.node;
+        for (uint32_t d = n.depth + 1; d-- > 0; a = parent[j0 + a]) t.anc[d] = (uint8_t)a;
+        if (b->n_masked) b->h_mask_of[j] = b->mask_row_of(slot[n.tree]);     // (the classifier sees the outputs in node order)
+        if (b->n_aut) b->h_aut_rows[j] = b->auto_row_of(slot[n.tree]);       // (no slot of the call has an automaton or penalties: the columns say "none")
+        if (b->n_pen) b->h_pen_of[j] = b->penalty_row_of(slot[n.tree], (int)r);
+        if (b->n_flt) b->h_flt_of[j] = b->filter_row_of(slot[n.tree]);
+    }
+    b->mask_live = false; b->pen_live = false; b->aut_live = false; b->flt_live = false;
+    *rows_out = R;
+}
+extern "C" int lmrs_batch_forward_tree(lmrs_batch* b, uint32_t n_trees, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* n_nodes, const uint32_t* parent,
+                                       const uint32_t* tokens, uint32_t* argmax, float* logits, uint32_t k, uint32_t* topk_idx, float* topk_logprob) {
+    const std::string what = "lmrs_batch_forward_tree: ";
+    if (!b || !slot || !start_pos || !n_nodes || !parent || !tokens || !argmax) return fail(what + "NULL argument");
+    lmrs_ctx* c = b->c;
+    const lmrs_args& a = c->args;
+    if (b->kvq_bytes) return fail(what + "token trees over a " + (b->kv4 ? "Q4" : "Q8") + " page pool are not built yet");
+    if (n_trees < 1 || n_trees > b->width) return fail(what + "n_trees = " + std::to_string(n_trees) + " is outside 1 .. " + std::to_string(b->width));
+    size_t R = 0;
+    for (uint32_t i = 0; i < n_trees; ++i) {
+        if (n_nodes[i] < 1 || n_nodes[i] > (uint32_t)kTreeNodesMax)
+            return fail(what + "tree " + std::to_string(i) + ": n_nodes = " + std::to_string(n_nodes[i]) + " is outside 1 .. " + std::to_string(kTreeNodesMax));
+        if ((R += n_nodes[i]) > (size_t)kRunRowsMax) return fail(what + "the trees hold more than " + std::to_string(kRunRowsMax) + " nodes");
+    }
+    uint64_t seen = 0;
+    for (uint32_t i = 0, j0 = 0; i < n_trees; j0 += n_nodes[i++]) {
+        const std::string tree = what + "tree " + std::to_string(i) + ": ";
+        if (slot[i] >= b->n_slots) return fail(tree + "slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
+        if (seen >> slot[i] & 1u) return fail(what + "slot " + std::to_string(slot[i]) + " appears in more than one tree");
+        seen |= uint64_t(1) << slot[i];
+        if ((size_t)start_pos[i] + n_nodes[i] > a.seq_len) return fail(tree + "start_pos + n_nodes exceeds seq_len");
+        for (uint32_t j = 0; j < n_nodes[i]; ++j)
+            if (parent[j0 + j] != LMRS_TREE_ROOT && parent[j0 + j] >= j)
+                return fail(tree + "parent[" + std::to_string(j) + "] = " + std::to_string(parent[j0 + j]) + " is neither LMRS_TREE_ROOT nor below its own index");
+        if (b->pen_on[slot[i]]) return fail(tree + "slot " + std::to_string(slot[i]) + " has penalties set: the token record has no notion of a path");
+        if (b->automaton_of(slot[i])) return fail(tree + "slot " + std::to_string(slot[i]) + " has an automaton attached: its state is per slot, not per node");
+        if (k && b->allowed_now(slot[i]) && k > b->allowed_now(slot[i]))
+            return fail(tree + "slot " + std::to_string(slot[i]) + ": k = " + std::to_string(k) + " exceeds the " + std::to_string(b->allowed_now(slot[i])) + " tokens its mask allows (n_allowed)");
+    }
+    for (size_t j = 0; j < R; ++j) if (tokens[j] >= a.vocab_size) return fail(what + "token " + std::to_string(j) + " out of range");
+    if (k && topk_check_k(k, a.vocab_size)) return -1;
+    if (k && (!topk_idx || !topk_logprob)) return fail(what + "k > 0 needs topk_idx and topk_logprob");
+    HIP_OK(hipSetDevice(c->device));
+    if (tree_alloc(b, what)) return -1;
+    if (k && topk_alloc(c, c->sc_rows, (int)k)) return -1;
+    tree_table(b, n_trees, slot, start_pos, n_nodes, parent, tokens, &R);
+    if (pages_claim_rows(b, what, n_trees, slot, start_pos, n_nodes, 0)) return -1;         // the storage positions: a run of n_nodes rows at start_pos
+    const HostScores hs = host_scores(c);
+    const size_t nk = R * k;
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->runs, b->h_runs, sizeof(RunTable), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(b->tree_rows, b->h_tree_rows, R * sizeof(TreeRow), hipMemcpyHostToDevice, c->stream));
+        if (masks_enqueue(b, R) || batch_state(c)) return -1;
+        RowSink to{0, R, logits, k}; to.reduce_too = true;
+        if (runs_pass(b, R, R, 0, to, nullptr, TreeView{b->tree_rows})) return -1;
+        HIP_OK(hipMemcpyAsync(hs.idx, c->sc_idx, R * 4, hipMemcpyDeviceToHost, c->stream));
+        if (k) {
+            HIP_OK(hipMemcpyAsync(c->h_tk, c->tk_idx, nk * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(c->h_tk + nk * 4, c->tk_val, nk * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
+    };
+    if (batch_call(c, enqueue)) return -1;
+    memcpy(argmax, hs.idx, R * 4);
+    if (k) { memcpy(topk_idx, c->h_tk, nk * 4); memcpy(topk_logprob, c->h_tk + nk * 4, nk * 4); }
+    return 0;
+}
+extern "C" int lmrs_batch_accept_path(lmrs_batch* b, uint32_t n, const uint32_t* slot, const uint32_t* start_pos, const uint32_t* path_len, const uint32_t* path) {
+    const std::string what = "lmrs_batch_accept_path: ";
+    if (!b || !slot || !start_pos || !path_len || !path) return fail(what + "NULL argument");
+    lmrs_ctx* c = b->c;
+    const lmrs_args& a = c->args;
+    if (b->kvq_bytes) return fail(what + "token trees over a " + (b->kv4 ? "Q4" : "Q8") + " page pool are not built yet");
+    if (n < 1 || n > b->width) return fail(what + "n = " + std::to_string(n) + " is outside 1 .. " + std::to_string(b->width));
+    uint64_t seen = 0;
+    std::vector<uint32_t> moved;                         // the entries that move a row
+    for (uint32_t i = 0, j0 = 0; i < n; j0 += path_len[i++]) {
+        const std::string entry = what + "entry " + std::to_string(i) + ": ";
+        if (slot[i] >= b->n_slots) return fail(entry + "slot " + std::to_string(slot[i]) + " of " + std::to_string(b->n_slots));
+        if (seen >> slot[i] & 1u) return fail(what + "slot " + std::to_string(slot[i]) + " appears in more than one entry");
+        seen |= uint64_t(1) << slot[i];
+        if (path_len[i] > (uint32_t)kTreeNodesMax) return fail(entry + "path_len = " + std::to_string(path_len[i]) + " exceeds " + std::to_string(kTreeNodesMax));
+        bool moves = false;
+        for (uint32_t j = 0; j < path_len[i]; ++j) {
+            const uint32_t p = path[j0 + j];
+            if (p >= (uint32_t)kTreeNodesMax) return fail(entry + "path[" + std::to_string(j) + "] = " + std::to_string(p) + " is no node index (0 .. " + std::to_string(kTreeNodesMax - 1) + ")");
+            if (j && p <= path[j0 + j - 1]) return fail(entry + "path is not strictly ascending at " + std::to_string(j));
+            moves = moves || p != j;
+        }
+        if (path_len[i] && (size_t)start_pos[i] + path[j0 + path_len[i] - 1] >= a.seq_len) return fail(entry + "start_pos + the path's last node lies outside seq_len");
+        if (moves) moved.push_back(i);
+    }
+    if (moved.empty()) return 0;                         // every path lies where it was stored: nothing to launch
+    HIP_OK(hipSetDevice(c->device));
+    if (tree_alloc(b, what)) return -1;
+    std::vector<PageRange> ranges;
+    std::vector<uint32_t> first(n);
+    for (uint32_t i = 0, j0 = 0; i < n; j0 += path_len[i++]) first[i] = j0;
+    for (size_t e = 0; e < moved.size(); ++e) {
+        const uint32_t i = moved[e];
+        TreeMove& m = b->h_tree_moves[e];
+        m.off = b->off_of(slot[i]); m.start = (int)start_pos[i]; m.len = (int)path_len[i];
+        for (uint32_t j = 0; j < path_len[i]; ++j) m.path[j] = (uint8_t)path[first[i] + j];
+        ranges.push_back(PageRange{slot[i], start_pos[i], start_pos[i] + path_len[i]});
+    }
+    if (pages_claim(b, what, ranges.data(), ranges.size())) return -1;                      // the destinations are written: claim, un-share
+    auto enqueue = [&]() -> int {
+        HIP_OK(hipMemcpyAsync(b->tree_moves, b->h_tree_moves, moved.size() * sizeof(TreeMove), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(launch_tree_commit(b->kv, b->kv + (b->pool ? b->page_floats : b->slot_floats), b->tree_moves, b->page_view(), (int)a.n_layers, c->kv_dim, (int)a.seq_len,
+                                  (int)moved.size(), c->stream));
+        return 0;
+    };
+    return batch_call(c, enqueue);
 }
 
 // ------------------------------------------------------------------ the sampled ragged pass: lmrs_batch_forward_runs' pass, then Sampler::sample on the last row of every run

@@ -327,6 +327,20 @@ hipError_t launch_kv4_import(const float* k_src, const float* v_src, int seq_len
                              int page_len, int pin0, int n_rows, hipStream_t s);
 // n device floats (a multiple of 32) through the scatter's quantiser and the attention's read-back, the device functions themselves (lmrs_op_kv4_round_trip)
 hipError_t launch_kv4_round_trip(const float* x, float* out, size_t n, hipStream_t s);
+// ---- the table pass over token trees (lmrs_batch_forward_tree; lmrs_tree.inc: the contract).  Beside the RowView - whose `pos` column carries the rows'
+// LOGICAL positions, base + depth - one TreeRow per table row: base = the tree's start_pos, spos = the STORAGE position base + node index, anc = the node
+// indexes of the row's ancestors root-most first and itself last (depth + 1 of them).  pv.tab null: contiguous slots (the rows' off words float offsets),
+// else an f32 page pool (table rows), as launch_paged_scatter / launch_paged_attention
+constexpr int kTreeNodesMax = 64;
+struct TreeRow { int base, spos; uint8_t anc[kTreeNodesMax]; };
+struct TreeView { const TreeRow* rows; };
+hipError_t launch_tree_scatter(float* qkv, float* k_cache, float* v_cache, const float* rope, RowView rows, TreeView tv, PageView pv, int n_heads, int n_kv_heads,
+                               int hs, int seq_len, int layer, int n_rows, hipStream_t s);
+hipError_t launch_tree_attention(const AttnArgs& a, RowView rows, TreeView tv, PageView pv, int n_rows, int max_T, hipStream_t s);
+// lmrs_batch_accept_path: entry e moves the K and V rows of every layer of the slot at `off` from storage position start + path[j] to start + j, j < len
+constexpr int kTreeMovesMax = 64;                                               // = a wide batch's slots
+struct TreeMove { unsigned long long off; int start, len; uint8_t path[kTreeNodesMax]; };
+hipError_t launch_tree_commit(float* k_cache, float* v_cache, const TreeMove* moves, PageView pv, int n_layers, int kv_dim, int seq_len, int n_moves, hipStream_t s);
 
 // ---- CLIP vision tower (lmrs_vision.inc; reference src/vision.rs:244-577), dim 1024 / 16 heads x 64 / 577 tokens per crop
 struct VisPatchArgs { const float* pixels; const float* kernel; const float* class_emb; const float* pos_emb; float* out; int dim, n_patches, kdim; };

@@ -3769,6 +3769,7 @@ hipError_t launch_exchange_push(const ExchangeArgs& a, hipStream_t s) {
 #include "lmrs_paged.inc"      // (the table passes over paged K/V: kernels of their own beside the ones above)
 #include "lmrs_kvq.inc"        // (... and over paged K/V kept in 8 bits)
 #include "lmrs_kv4.inc"        // (... and in 4 bits)
+#include "lmrs_tree.inc"       // (the table pass over token trees: contiguous slots and f32 pages)
 #include "lmrs_f32.inc"        // (its batched kernel uses the epilogues of lmrs_prefill.inc)
 #include "lmrs_vision_att.h"
 #include "lmrs_vision.inc"

@@ -425,3 +425,18 @@ extern "C" int lmrs_draft_lookup(const uint32_t* hist, size_t n_hist, uint32_t n
     }
     return 0;
 }
+
+// ------------------------------------------------------------------ greedy acceptance over a verified token tree (lmrs_batch_forward_tree; no reference counterpart)
+extern "C" int lmrs_tree_accept(uint32_t n_nodes, const uint32_t* parent, const uint32_t* tokens, const uint32_t* argmax, uint32_t expected,
+                                uint32_t* path, uint32_t* path_len, uint32_t* next) {
+    if (!path_len || !next || (n_nodes && (!parent || !tokens || !argmax || !path))) return lmrs::text_fail("lmrs_tree_accept: NULL argument");
+    if (n_nodes > 64) return lmrs::text_fail(("lmrs_tree_accept: n_nodes = " + std::to_string(n_nodes) + " exceeds 64").c_str());
+    for (uint32_t j = 0; j < n_nodes; ++j)
+        if (parent[j] != LMRS_TREE_ROOT && parent[j] >= j)
+            return lmrs::text_fail(("lmrs_tree_accept: parent[" + std::to_string(j) + "] = " + std::to_string(parent[j]) + " is neither LMRS_TREE_ROOT nor below its own index").c_str());
+    uint32_t at = LMRS_TREE_ROOT, len = 0;
+    for (uint32_t j = 0; j < n_nodes; ++j)                                             // a child lies behind its parent: one walk finds the whole path
+        if (parent[j] == at && tokens[j] == expected) { path[len++] = j; expected = argmax[j]; at = j; }
+    *path_len = len; *next = expected;
+    return 0;
+}

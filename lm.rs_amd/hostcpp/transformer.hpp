@@ -419,6 +419,49 @@ public:
                                       k ? o.topk_logprob.data() : nullptr));
         return o;
     }
+    // Token trees in one weight pass, one tree per slot: parents[j] is TREE_ROOT or the index < j of node j's parent; node j is fed at start_pos + depth(j)
+    // behind the slot's prefix and its own ancestors, and its K/V rows are kept at start_pos + j.  Every node is an output row, in node order, tree after
+    // tree: RunsOut as forward_runs fills it  (lmrs_batch_forward_tree)
+    static constexpr std::uint32_t TREE_ROOT = LMRS_TREE_ROOT;
+    struct Tree { std::uint32_t slot, start_pos; std::vector<std::uint32_t> parents, tokens; };
+    RunsOut forward_tree(const std::vector<Tree>& trees, std::uint32_t k = 0, bool logits = false) {
+        std::vector<std::uint32_t> slot, start, n_nodes, parents, tokens;
+        for (const Tree& t : trees) {
+            if (t.parents.size() != t.tokens.size()) throw Panic("Batch::forward_tree: a tree's parents and tokens differ in length");
+            slot.push_back(t.slot); start.push_back(t.start_pos); n_nodes.push_back(static_cast<std::uint32_t>(t.parents.size()));
+            parents.insert(parents.end(), t.parents.begin(), t.parents.end());
+            tokens.insert(tokens.end(), t.tokens.begin(), t.tokens.end());
+        }
+        const std::size_t rows = tokens.size();
+        RunsOut o;
+        o.argmax.resize(rows + 1); o.topk_idx.resize(rows * k); o.topk_logprob.resize(rows * k);
+        if (logits) o.logits.resize(rows * vocab_size_);
+        check(lmrs_batch_forward_tree(b_, static_cast<std::uint32_t>(trees.size()), slot.data(), start.data(), n_nodes.data(), parents.data(), tokens.data(),
+                                      o.argmax.data(), logits ? o.logits.data() : nullptr, k, k ? o.topk_idx.data() : nullptr, k ? o.topk_logprob.data() : nullptr));
+        o.argmax.resize(rows);
+        return o;
+    }
+    // Make accepted paths the slots' next positions: the K/V rows kept at start_pos + path[j] move to start_pos + j  (lmrs_batch_accept_path)
+    struct Path { std::uint32_t slot, start_pos; std::vector<std::uint32_t> nodes; };
+    void accept_path(const std::vector<Path>& paths) {
+        std::vector<std::uint32_t> slot, start, len, nodes;
+        for (const Path& p : paths) {
+            slot.push_back(p.slot); start.push_back(p.start_pos); len.push_back(static_cast<std::uint32_t>(p.nodes.size()));
+            nodes.insert(nodes.end(), p.nodes.begin(), p.nodes.end());
+        }
+        nodes.push_back(0);                                            // (never read: a non-null pointer for a call whose paths are all empty)
+        check(lmrs_batch_accept_path(b_, static_cast<std::uint32_t>(paths.size()), slot.data(), start.data(), len.data(), nodes.data()));
+    }
+    // Greedy acceptance over a verified tree, host only: the accepted nodes root-most first, and the token greedy decoding feeds next  (lmrs_tree_accept)
+    static std::pair<std::vector<std::uint32_t>, std::uint32_t> tree_accept(const std::vector<std::uint32_t>& parents, const std::vector<std::uint32_t>& tokens,
+                                                                           const std::vector<std::uint32_t>& argmax, std::uint32_t expected) {
+        if (parents.size() != tokens.size() || parents.size() != argmax.size()) throw Panic("Batch::tree_accept: one parent, token and argmax per node");
+        std::vector<std::uint32_t> path(parents.size() + 1);
+        std::uint32_t n = 0, next = 0;
+        check(lmrs_tree_accept(static_cast<std::uint32_t>(parents.size()), parents.data(), tokens.data(), argmax.data(), expected, path.data(), &n, &next));
+        path.resize(n);
+        return {path, next};
+    }
     // forward_runs with a sampler per run, sampled on the device: the LAST row of every run whose sampler (Sampler::handle(), text.hpp) is not null goes
     // through Sampler::sample with it -> next[i], bit for bit Transformer::forward_sample's token after the run's tokens on a transformer that holds only
     // that sequence; a null sampler leaves the run's K/V rows only and next[i] = 0.  Up to width() runs; runs may mix samplers, a top-p sampler in at most

@@ -62,6 +62,34 @@ extern "C" {
     pub fn lmrs_batch_clear_filters(b: *mut LmrsBatch, n: u32, slot: *const u32) -> c_int;
     pub fn lmrs_batch_filter_info(b: *const LmrsBatch, slot: u32, top_k: *mut u32, min_gap: *mut f32, active: *mut c_int) -> c_int;
     pub fn lmrs_op_filter_rows(device: c_int, rows: *mut f32, n_rows: usize, n: usize, ld: usize, top_k: *const u32, min_gap: *const f32) -> c_int;
+    // token trees in a pass, accept-a-path and greedy acceptance: declared here as the filter calls are (tests/test_batch_tree_host.py looks for them)
+    pub fn lmrs_batch_forward_tree(b: *mut LmrsBatch, n_trees: u32, slot: *const u32, start_pos: *const u32, n_nodes: *const u32, parent: *const u32,
+                                   tokens: *const u32, argmax: *mut u32, logits: *mut f32, k: u32, topk_idx: *mut u32, topk_logprob: *mut f32) -> c_int;
+    pub fn lmrs_batch_accept_path(b: *mut LmrsBatch, n: u32, slot: *const u32, start_pos: *const u32, path_len: *const u32, path: *const u32) -> c_int;
+    pub fn lmrs_tree_accept(n_nodes: u32, parent: *const u32, tokens: *const u32, argmax: *const u32, expected: u32, path: *mut u32,
+                            path_len: *mut u32, next: *mut u32) -> c_int;
+}
+
+/// A node under the root in a tree's `parents` (`LMRS_TREE_ROOT`).
+pub const TREE_ROOT: u32 = 0xFFFF_FFFF;
+
+/// One tree of `Batch::forward_tree`: it hangs off position `start_pos` of `slot`; `parents[j]` is `TREE_ROOT` or the index `< j` of node `j`'s parent.
+pub struct Tree<'r> {
+    pub slot: u32,
+    pub start_pos: u32,
+    pub parents: &'r [u32],
+    pub tokens: &'r [u32],
+}
+
+/// Greedy acceptance over a verified tree, host only (`lmrs_tree_accept`): the accepted node indexes root-most first, and the token greedy decoding
+/// feeds next.  `expected` is the argmax of the row in front of the tree.
+pub fn tree_accept(parents: &[u32], tokens: &[u32], argmax: &[u32], expected: u32) -> (Vec<u32>, u32) {
+    assert!(parents.len() == tokens.len() && parents.len() == argmax.len(), "one parent, token and argmax per node");
+    let mut path = vec![0u32; parents.len().max(1)];
+    let (mut n, mut next) = (0u32, 0u32);
+    check(unsafe { lmrs_tree_accept(parents.len() as u32, parents.as_ptr(), tokens.as_ptr(), argmax.as_ptr(), expected, path.as_mut_ptr(), &mut n, &mut next) });
+    path.truncate(n as usize);
+    (path, next)
 }
 
 /// A slot's candidate filters (`Batch::set_filters`): every logit outside the row's first `top_k` candidates (0: off) and every logit more than `min_gap`
@@ -299,6 +327,42 @@ impl<'t, 'a> Batch<'t, 'a> {
     /// `Transformer::prefill_tokens` into `slot`'s cache.
     pub fn prefill(&mut self, slot: u32, tokens: &[u32], start_pos: u32) {
         check(unsafe { ffi::lmrs_batch_prefill(self.b, slot, tokens.as_ptr(), tokens.len(), start_pos) });
+    }
+
+    /// One weight pass over token trees, one per slot: node `j` is fed at `start_pos + depth(j)` behind the slot's prefix and its own ancestors, its K/V
+    /// rows kept at `start_pos + j`.  The argmax of every node, in node order, tree after tree (`lmrs_batch_forward_tree`).  The call's logits and top-k
+    /// outputs are not bound here (the Python and C++ bindings carry them); the extern above takes them.
+    pub fn forward_tree(&mut self, trees: &[Tree]) -> Vec<u32> {
+        let (mut slot, mut start, mut n_nodes, mut parents, mut tokens) = (Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new());
+        for t in trees.iter() {
+            assert!(t.parents.len() == t.tokens.len(), "one parent and one token per node");
+            slot.push(t.slot);
+            start.push(t.start_pos);
+            n_nodes.push(t.parents.len() as u32);
+            parents.extend_from_slice(t.parents);
+            tokens.extend_from_slice(t.tokens);
+        }
+        let mut argmax = vec![0u32; tokens.len().max(1)];
+        check(unsafe {
+            lmrs_batch_forward_tree(self.b, trees.len() as u32, slot.as_ptr(), start.as_ptr(), n_nodes.as_ptr(), parents.as_ptr(), tokens.as_ptr(),
+                                    argmax.as_mut_ptr(), ptr::null_mut(), 0, ptr::null_mut(), ptr::null_mut())
+        });
+        argmax.truncate(tokens.len());
+        argmax
+    }
+
+    /// Make accepted paths the slots' next positions: per `(slot, start_pos, path)` the K/V rows kept at `start_pos + path[j]` move to `start_pos + j`
+    /// (`lmrs_batch_accept_path`).
+    pub fn accept_path(&mut self, paths: &[(u32, u32, &[u32])]) {
+        let (mut slot, mut start, mut len, mut path) = (Vec::new(), Vec::new(), Vec::new(), vec![]);
+        for (s, p, nodes) in paths.iter() {
+            slot.push(*s);
+            start.push(*p);
+            len.push(nodes.len() as u32);
+            path.extend_from_slice(nodes);
+        }
+        path.push(0);                                    // (never read: a non-null pointer for a call whose paths are all empty)
+        check(unsafe { lmrs_batch_accept_path(self.b, paths.len() as u32, slot.as_ptr(), start.as_ptr(), len.as_ptr(), path.as_ptr()) });
     }
 
     /// ONE `Transformer::fill_kv_cache` call into `slot`'s cache: `embeddings.len() / dim` rows, taken as given, from `start_pos` on.  With

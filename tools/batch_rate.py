@@ -29,7 +29,11 @@ rule and forced to the table pass, the forms by turns (paged_prefill_main below)
        python tools/batch_rate.py --paged-prefill --kv q4 [model] [q8_0|q4_0]
 --paged-prefill --kv q4: 320 .. 512 tokens on a Q4 paged batch under the library's rule (block attention over Q4 pages) and forced to the table pass, by turns
 beside the f32 and the Q8 paged batch's block attention
-       (writes profiles/batch_kv4_prefill_llama1b.txt, profiles/batch_kv4_prefill_gemma2b_q4.txt)"""
+       (writes profiles/batch_kv4_prefill_llama1b.txt, profiles/batch_kv4_prefill_gemma2b_q4.txt)
+       python tools/batch_rate.py --tree [--parent-lib PATH] [model] [q8_0|q4_0]
+--tree: a pass over token trees (lmrs_batch_forward_tree) against lmrs_batch_forward_runs of equal rows, this build's by turns and the parent commit's in
+processes of their own, the existing calls against the parent, lmrs_batch_accept_path and the launch lists (tree_main below)
+       (writes profiles/batch_tree_llama1b.txt, profiles/batch_tree_gemma2b_q4.txt)"""
 import os
 import statistics
 import sys
@@ -514,7 +518,209 @@ def kvq_main(argv):
             f.write("\n".join(lines) + "\n")
 
 
+TREE_OUT = {("llama-3.2-1b", S.Q8_0): "batch_tree_llama1b.txt", ("gemma-2-2b", S.Q4_0): "batch_tree_gemma2b_q4.txt"}
+# (slots, rows a slot): 16- and 64-node binary trees on 1 and 16 slots - a call takes 512 rows, so the 64-node trees stand on 8 slots - and one node a slot
+TREE_SHAPES = ((1, 16), (16, 16), (1, 64), (8, 64), (1, 1), (16, 1))
+TREE_PASSES = 8
+
+
+def tree_child(image_path, mode):
+    """--tree's child, over a binding of its own (the parent commit's library has no tree entry points) on the library LMRS_LIB names.  Per batch kind (wide,
+    f32 paged with pages of 64), depth (100, 1000) and shape of TREE_SHAPES: us per pass of lmrs_batch_forward_runs with every row's output asked for and,
+    where the library has it, of lmrs_batch_forward_tree over binary trees of as many rows at the same prefix - the two forms by turns, three turns, a turn
+    the median of 3 calls of TREE_PASSES passes after 1 warm-up (host time of the synchronous calls).  Then lmrs_batch_forward at 16 and 64 rows, the decode
+    step (lmrs_generate_greedy, bench.py's workload; device time) and lmrs_batch_accept_path of a 4-of-16 path on 16 slots.  One line a figure: TREE key
+    median min max.  mode "traced" (under rocprofv3): one forward_runs call at 16 slots x 16 rows and 100 positions and one forward of 16 and of 64 rows, wide
+    and paged - the calls both libraries have; "traced-tree": one tree pass there instead, and one accept."""
+    import ctypes as C
+    lib = C.CDLL(os.environ.get("LMRS_LIB", lmrs_amd.LIB_PATH))
+    vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
+    lib.lmrs_last_error.restype = C.c_char_p
+    lib.lmrs_create.argtypes = [vp, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    lib.lmrs_batch_create_wide.argtypes = [vp, u32, C.POINTER(vp)]
+    lib.lmrs_batch_create_paged.argtypes = [vp, u32, u32, u32, C.POINTER(vp)]
+    lib.lmrs_batch_prefill.argtypes = [vp, u32, vp, sz, u32]
+    lib.lmrs_batch_forward.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+    lib.lmrs_batch_forward_runs.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+    lib.lmrs_generate_greedy.argtypes = [vp, vp, sz, u32, u32, vp, C.POINTER(C.c_double)]
+    lib.lmrs_batch_destroy.argtypes = [vp]; lib.lmrs_batch_destroy.restype = None
+    traced, tree_only = mode != "", mode == "traced-tree"
+    has_tree = hasattr(lib, "lmrs_batch_forward_tree")
+    if has_tree:
+        lib.lmrs_batch_forward_tree.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        lib.lmrs_batch_accept_path.argtypes = [vp, u32, vp, vp, vp, vp]
+
+    def chk(rc):
+        if rc:
+            raise RuntimeError(lib.lmrs_last_error().decode())
+
+    def p(a):
+        return a.ctypes.data
+
+    img = np.fromfile(image_path, np.uint8)
+    prompt = np.ascontiguousarray(np.fromfile(image_path + ".prompt", np.uint32))
+    h, used = vp(), sz()
+    chk(lib.lmrs_create(p(img), img.size, 0, C.byref(h), C.byref(used)))
+    u = lambda x: np.ascontiguousarray(x, np.uint32)
+
+    def turns(forms, passes=TREE_PASSES, n_turns=3):
+        """forms: {name: call}; by turns -> {name: (median, min, max) of the turns' medians, us per pass}"""
+        got = {k: [] for k in forms}
+        for _ in range(1 if traced else n_turns):
+            for k, call in forms.items():
+                us = []
+                for _ in range(1 if traced else 4):
+                    t0 = time.perf_counter()
+                    for _ in range(1 if traced else passes):
+                        call()
+                    us.append((time.perf_counter() - t0) * 1e6 / (1 if traced else passes))
+                got[k].append(statistics.median(us[0 if traced else 1:]))
+        return {k: (statistics.median(v), min(v), max(v)) for k, v in got.items()}
+
+    def say(key, r):
+        print(f"TREE {key} {r[0]:.1f} {r[1]:.1f} {r[2]:.1f}", flush=True)
+
+    for kind in ("wide", "paged"):
+        for depth in (100,) if traced else (100, 1000):
+            b = vp()
+            if kind == "wide":
+                chk(lib.lmrs_batch_create_wide(h, 64, C.byref(b)))
+            else:
+                chk(lib.lmrs_batch_create_paged(h, 64, 64, 64 * (-(-(depth + 65) // 64)), C.byref(b)))
+            for i in range(64 if kind == "wide" and depth == 100 else 16):
+                chk(lib.lmrs_batch_prefill(b, i, p(prompt), depth, 0))
+            for slots, rows in ((16, 16),) if traced else TREE_SHAPES:
+                sl, st, n = u(range(slots)), u([depth] * slots), u([rows] * slots)
+                tok = u(np.tile(prompt[depth:depth + rows], slots))
+                par = u(np.tile([0xFFFFFFFF] + [(j - 1) // 2 for j in range(1, rows)], slots))
+                am = np.zeros(slots * rows, np.uint32)
+                forms = {} if tree_only else {"runs": lambda: chk(lib.lmrs_batch_forward_runs(b, slots, p(sl), p(st), p(n), p(n), p(tok), p(am), None, 0, None, None))}
+                if has_tree and (tree_only or not traced):
+                    forms["tree"] = lambda: chk(lib.lmrs_batch_forward_tree(b, slots, p(sl), p(st), p(n), p(par), p(tok), p(am), None, 0, None, None))
+                for k, r in turns(forms).items():
+                    say(f"{kind}:{slots}x{rows}@{depth}:{k}", r)
+            if kind == "wide" and depth == 100:
+                for rows in () if tree_only else (16, 64):
+                    sl, tok, pos, am = u(range(rows)), u([prompt[depth]] * rows), u([depth] * rows), np.zeros(rows, np.uint32)
+                    say(f"forward:{rows}@{depth}", turns({"f": lambda: chk(lib.lmrs_batch_forward(b, rows, p(sl), p(tok), p(pos), p(am), None))})["f"])
+                if has_tree and (tree_only or not traced):   # a 16-node tree a slot, then the path 0, 1, 3, 7 -> .. accepted: 4 of 16, rows 3 and 7 move
+                    sl, st, n = u(range(16)), u([depth] * 16), u([16] * 16)
+                    tok, par = u(np.tile(prompt[depth:depth + 16], 16)), u(np.tile([0xFFFFFFFF] + [(j - 1) // 2 for j in range(1, 16)], 16))
+                    am, plen, path = np.zeros(256, np.uint32), u([4] * 16), u([0, 1, 3, 7] * 16)
+                    chk(lib.lmrs_batch_forward_tree(b, 16, p(sl), p(st), p(n), p(par), p(tok), p(am), None, 0, None, None))
+                    say("accept:16x4of16", turns({"a": lambda: chk(lib.lmrs_batch_accept_path(b, 16, p(sl), p(st), p(plen), p(path)))}, passes=1)["a"])
+            lib.lmrs_batch_destroy(b)
+    if not traced:
+        ids, sec, us = np.zeros(STEPS, np.uint32), C.c_double(), []
+        for _ in range(4):
+            chk(lib.lmrs_generate_greedy(h, p(prompt), 10, STEPS, 0, p(ids), C.byref(sec)))
+            us.append(sec.value * 1e6 / STEPS)
+        say("decode:1@10", (statistics.median(us[1:]), min(us[1:]), max(us[1:])))
+
+
+def tree_main(argv):
+    """--tree [--parent-lib PATH] [model] [q8_0|q4_0]: tree_child a process per library by turns (the parent commit's, this build's; two turns), then the
+    conditions: (1) a tree pass is no slower than the PARENT's lmrs_batch_forward_runs pass of equal rows by more than the parent's spread over its turns plus
+    the cost of the one extra upload (tree against runs at one node a slot, this build); (2) this build's forward_runs, forward at 16 and 64 rows and the
+    decode step stay within the parent's spread.  A MISS is printed as a MISS with its size.  Last, under rocprofv3 --kernel-trace in processes of their own: the
+    launch lists of the calls both libraries have, compared, and the tree kernels' times (tree_commit_kernel: a 4-of-16 path on 16 slots)."""
+    import csv, glob, shutil, subprocess, tempfile  # noqa: E401
+    parent = os.environ.get("BATCH_RATE_PARENT_LIB")
+    if argv and argv[0] == "--parent-lib":
+        parent, argv = argv[1], argv[2:]
+    model = argv[0] if argv else "llama-3.2-1b"
+    qname = argv[1] if len(argv) > 1 else "q8_0"
+    qt = S.Q4_0 if qname == "q4_0" else S.Q8_0
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True); lines.append(s)
+
+    say(f"python tools/batch_rate.py --tree --parent-lib <the parent commit's liblmrs_hip.so> {model} {qname}")
+    say(f"{model} {qname.upper()}, synthetic weights (tools/synth_lmrs.py seed 1234); kernel_source_hash {bench.kernel_source_hash()}")
+    say(f"us per pass, host time of synchronous calls ({TREE_PASSES} passes a call); in a process the forms by turns, three turns of 3 calls after 1 warm-up; "
+        "a process per library by turns, two turns; per figure the mean of the processes' medians (their distance apart)")
+    libs = [("this", lmrs_amd.LIB_PATH)] + ([("parent", os.path.abspath(parent))] if parent and os.path.exists(parent) else [])
+    if len(libs) == 1:
+        say("no parent library given (--parent-lib PATH): the conditions against the parent are not judged")
+    me, res = os.path.abspath(__file__), {}
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "model.lmrs")
+        S.build_image(model, qt, 1234).tofile(path); np.ascontiguousarray(S.prompt_tokens(model, 1100, 100), np.uint32).tofile(path + ".prompt")
+        for turn in range(2):
+            for who, lib in libs:
+                r = subprocess.run([sys.executable, me, "--tree-child", path], env=dict(os.environ, LMRS_LIB=lib), capture_output=True, text=True, timeout=900)
+                if r.returncode:
+                    say(f"  {who}, turn {turn}: failed: {r.stderr.strip()[-300:]}")
+                for l in r.stdout.splitlines():
+                    if l.startswith("TREE "):
+                        res.setdefault((who, l.split()[1]), []).append(float(l.split()[2]))
+        mean = lambda who, k: statistics.mean(res[(who, k)])
+        gap = lambda who, k: max(res[(who, k)]) - min(res[(who, k)])
+        misses = 0
+        say("condition 1 - the tree pass against the parent's forward_runs pass of equal rows (binary trees; kind:slots x rows@prefix):")
+        for kind in ("wide", "paged"):
+            for depth in (100, 1000):
+                for slots, rows in TREE_SHAPES:
+                    k = f"{kind}:{slots}x{rows}@{depth}"
+                    t, own = mean("this", k + ":tree"), mean("this", k + ":runs")
+                    line = f"  {k:18s} tree {t:8.1f} ({gap('this', k + ':tree'):.1f})   this build's runs {own:8.1f} ({t / own - 1:+.1%})"
+                    if len(libs) > 1:
+                        one = f"{kind}:{1 if slots == 1 else 16}x1@{depth}"          # (the 8-slot shape: the 16-slot upload, the larger table)
+                        up = max(0.0, mean("this", one + ":tree") - mean("this", one + ":runs"))
+                        pr, allow = mean("parent", k + ":runs"), gap("parent", k + ":runs") + up
+                        miss = t > pr + allow
+                        misses += miss
+                        line += f"   parent's runs {pr:8.1f} ({t / pr - 1:+.1%}; allowed {allow:.1f} = its turns {gap('parent', k + ':runs'):.1f} + upload {up:.1f})"
+                        line += f"   ** MISS by {t - pr - allow:.1f} us **" if miss else ""
+                    say(line)
+        if len(libs) > 1:
+            say("condition 2 - existing calls against the parent (a MISS: slower by more than the parent's turns are apart):")
+            keys = [f"{kind}:{s}x{r}@{d}:runs" for kind in ("wide", "paged") for d in (100, 1000) for s, r in TREE_SHAPES] + ["forward:16@100", "forward:64@100", "decode:1@10"]
+            for k in keys:
+                a, pr, g = mean("this", k), mean("parent", k), gap("parent", k)
+                misses += a > pr + g
+                say(f"  {k:24s} this {a:8.1f}   parent {pr:8.1f} ({a / pr - 1:+.1%}; parent's turns {g:.1f} apart)" + (f"   ** MISS by {a - pr - g:.1f} us **" if a > pr + g else ""))
+            say(f"  MISSES in all: {misses}")
+        r = res.get(("this", "accept:16x4of16"))
+        say(f"lmrs_batch_accept_path, a 4-of-16 path on 16 slots (two rows a slot move), host time of the synchronous call: {statistics.mean(r):.1f} us" if r else "accept: not run")
+        say("launch lists under rocprofv3 --kernel-trace, a process each: forward_runs 16 x 16 and forward at 16 and 64 rows on a wide and a paged batch, per library; "
+            "then this build's tree pass and accept alone")
+        counts = {}
+        for who, lib, mode in [(w, l, "traced") for w, l in libs] + [("this, tree", lmrs_amd.LIB_PATH, "traced-tree")] if shutil.which("rocprofv3") else ():
+            with tempfile.TemporaryDirectory() as tt:
+                r = subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tt, "--", sys.executable, me, "--tree-child", path, mode],
+                                   env=dict(os.environ, LMRS_LIB=lib), capture_output=True, text=True, timeout=900)
+                traces = glob.glob(os.path.join(tt, "**", "*kernel_trace.csv"), recursive=True)
+                if r.returncode or not traces:
+                    say(f"  {who}: failed: {r.stderr.strip()[-300:]}")
+                    continue
+                rows = list(csv.DictReader(open(traces[0])))
+                counts[who] = {}
+                for x in rows:
+                    name = x["Kernel_Name"].split("(")[0]
+                    counts[who][name] = counts[who].get(name, 0) + 1
+                say(f"  {who}: {sum(counts[who].values())} launches of {len(counts[who])} kernels")
+                for kern in ("tree_scatter_kernel", "tree_attn_kernel", "tree_commit_kernel") if mode == "traced-tree" else ():
+                    us = [(int(x["End_Timestamp"]) - int(x["Start_Timestamp"])) / 1e3 for x in rows if kern in x["Kernel_Name"]]
+                    say(f"    {kern:20s} {len(us):3d} launches  median {statistics.median(us):8.2f} us ({min(us):.2f} .. {max(us):.2f})" if us else f"    {kern}: no launch")
+        if not shutil.which("rocprofv3"):
+            say("  not run: rocprofv3 is not on the PATH")
+        if "this" in counts and "parent" in counts:
+            diff = {k: (counts["this"].get(k, 0), counts["parent"].get(k, 0)) for k in set(counts["this"]) | set(counts["parent"]) if counts["this"].get(k, 0) != counts["parent"].get(k, 0)}
+            say(f"  launch lists of the existing calls identical between the libraries: {not diff}" + (f"   (this, parent): {diff}" if diff else ""))
+    name = TREE_OUT.get((model, qt))
+    out = os.environ.get("BATCH_RATE_OUT") or (os.path.join(ROOT, "profiles", name) if name else None)
+    if out:
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--tree-child":
+        return tree_child(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "")
+    if len(sys.argv) > 1 and sys.argv[1] == "--tree":
+        return tree_main(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--paged-prefill":
         return paged_prefill_main(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--wide":
