@@ -2,7 +2,7 @@
 subnormal softmax terms, saturated soft-caps, all-zero quantisation groups, outlier channels, SiLU / GELU at their extremes, exactly tied logits -
 through the single-sequence paths; every lmrs_batch_* call has its own copies of that arithmetic (the skinny and stream GEMMs' epilogues, the row
 quantisers, attention over a row table, the paged softmax, block attention over a page table, the batch's soft-cap, argmax, top-k, sampler, mask and
-penalty kernels) and had only ever seen narrow Gaussian weights.  Here those calls run on the recipes.
+penalty kernels; the tree pass's scatter, attention and commit kernels) and had only ever seen narrow Gaussian weights.  Here those calls run on the recipes.
 
 The reference is ONE sequential oracle decode per (model, format, recipe) of N positions of one token sequence (oracle_run): every slot of a test holds a
 prefix of that sequence, so a slot at depth d fed toks[d] must give the run's logits row d and write the run's K/V row d - a slot's state is a function
@@ -25,6 +25,7 @@ from test_batch import Seq, check_slot_rows, snapshot, step
 from test_batch_mask import ban, masked
 from test_batch_runs import run_pass
 from test_batch_sample import KINDS
+from test_batch_tree import feed_tree
 from test_stress_regimes import CASES, SEED, check_witness, h_quantiser_fused, image_of, oracle_decode, recipes_for
 from test_topk import rank_row
 from tools import synth_lmrs as S
@@ -589,6 +590,71 @@ def test_verify_tokens_under_stress(L, cfg, q, recipe):
             assert_bit_equal(m.kv_row(0, layer, p), ref.K[layer, p], f"{what}: key row, layer {layer}, pos {p}")
             assert_bit_equal(m.kv_row(1, layer, p), ref.V[layer, p], f"{what}: value row, layer {layer}, pos {p}")
     m.close()
+
+
+# ---------------------------------------------------------------------------------------------- 9. token trees
+
+TREE_DEPTH = 32                     # spine nodes a tree; a leaf sibling in front of each: 64 nodes
+
+
+def tree_of(ref, start):
+    """-> (parents, tokens, the spine's node indices): spine node d carries toks[start + d] and hangs under spine node d - 1; in front of it in index
+    order sits a leaf sibling with the next token id, so spine node d is stored at start + 2 d + 1 and fed at start + d"""
+    V, par, tok = ref.cfg.vocab_size, [], []
+    for d in range(TREE_DEPTH):
+        t = int(ref.toks[start + d])
+        par += [None if d == 0 else 2 * d - 1] * 2
+        tok += [(t + 1) % V, t]
+    return par, tok, list(range(1, 2 * TREE_DEPTH, 2))
+
+
+def tree_positions(cfg, q, recipe, kind):
+    return [d + k for d in STARTS for k in range(TREE_DEPTH + 1)]
+
+
+TREE = cases("tree", [(c, q, r, ("contiguous", "paged")[i % 2]) for i, (c, q, r) in enumerate(
+    by_recipe([("mini-llama", S.Q8_0), ("mini-phi", S.Q8_0), ("mini-gemma", S.Q4_0)], ("peaked", "dead_groups", "outliers", "glu_extremes", "combined"),
+              gemma=("softcap",)))], tree_positions)
+
+
+@gpu
+@pytest.mark.parametrize("cfg,q,recipe,kind", TREE, ids=ident)
+def test_token_trees(L, cfg, q, recipe, kind):
+    """forward_tree over five slots at STARTS, a 64-node tree each (tree_scatter_kernel, tree_attn_kernel: their own copies of the score, softmax and
+    value phases): the spines replay the shared run, so their logits and K/V rows are the run's; the leaves of the slot at 5 against a Seq oracle on
+    the recipe's image.  Then accept_path of the spines (tree_commit_kernel) and one step behind them"""
+    ref = witness(cfg, q, recipe, tree_positions(cfg, q, recipe, kind))
+    what = f"{ref.cfg.name} q{q} {recipe} trees, {kind}"
+    n = len(STARTS)
+    m = L.Transformer(ref.img); b = paged_batch(L, m, n + 1) if kind == "paged" else L.Batch(m, n + 1)
+    seqs = populate(b, ref, STARTS + [0], n, what)[:n]
+    trees = [(s.slot, s.n) + tree_of(ref, s.n)[:2] for s in seqs]
+    spine = tree_of(ref, 0)[2]
+    am, lg = b.forward_tree(trees, logits=True)
+    nl = ref.cfg.n_layers
+    for i, s in enumerate(seqs):
+        for d, j in enumerate(spine):
+            r, p = 2 * TREE_DEPTH * i + j, s.n + d
+            assert_bit_equal(lg[r], ref.rows[p], f"{what}: slot {s.slot}, spine node {d} (position {p}): logits")
+            assert int(am[r]) == ref_argmax(ref.rows[p]), f"{what}: slot {s.slot}, spine node {d}: argmax"
+            for layer in range(nl):
+                assert_bit_equal(b.kv_row(s.slot, 0, layer, s.n + j), ref.K[layer, p], f"{what}: slot {s.slot}, spine node {d}: k row of layer {layer} at storage {s.n + j}")
+                assert_bit_equal(b.kv_row(s.slot, 1, layer, s.n + j), ref.V[layer, p], f"{what}: slot {s.slot}, spine node {d}: v row of layer {layer} at storage {s.n + j}")
+    i = STARTS.index(5)
+    o = Seq(ref.img, i)
+    o.feed(ref.toks[:5])
+    for j, (want, rows) in enumerate(feed_tree(o, trees[i][2], trees[i][3])):
+        r = 2 * TREE_DEPTH * i + j
+        assert_bit_equal(lg[r], want, f"{what}: the slot at 5, node {j}: logits")
+        assert int(am[r]) == ref_argmax(want), f"{what}: the slot at 5, node {j}: argmax"
+        for x, (layer, w) in zip(rows, [(layer, w) for layer in range(nl) for w in (0, 1)]):
+            assert_bit_equal(b.kv_row(i, w, layer, 5 + j), x, f"{what}: the slot at 5, node {j}: {'kv'[w]} row of layer {layer}")
+    b.accept_path([(s.slot, s.n, spine) for s in seqs])
+    for s in seqs:
+        s.feed(s.next(TREE_DEPTH))
+        check_slot_rows(b, s, range(s.n - TREE_DEPTH, s.n), f"{what}: after accept_path")
+    steps(b, seqs, 1, f"{what}: behind the accepted spines")
+    b.close(); m.close()
 
 
 # ---------------------------------------------------------------------------------------------- CPU tier

@@ -8,7 +8,7 @@ import pytest
 
 import filter_rules as F
 from parity_rules import assert_bit_equal, ref_argmax
-from test_batch import CFGS, Seq, check_slot_rows, step
+from test_batch import CFGS, DEPTHS16, Seq, check_slot_rows, step
 from test_batch_mask import masked
 from test_topk import rank_row, topk_rule
 from tools import synth_lmrs as S
@@ -17,7 +17,8 @@ gpu = pytest.mark.gpu
 KINDS = ["contiguous", "wide", "paged"]
 SHAPES = {"chain7": [None] + list(range(6)), "star8": [None] * 8, "binary15": [None] + [(j - 1) // 2 for j in range(1, 15)],
           "comb20": [None if j == 0 else j - 2 + j % 2 for j in range(20)],          # spine 0, 2, 4, .. with the leaf 2i + 1 under spine node 2i
-          "comb64": [None if j == 0 else j - 2 + j % 2 for j in range(64)], "one": [None]}
+          "comb64": [None if j == 0 else j - 2 + j % 2 for j in range(64)], "one": [None], "star64": [None] * 64,
+          "chain7+1": [None] + list(range(6)) + [None]}                              # a chain and a second root behind it
 
 
 @pytest.fixture(scope="module")
@@ -158,6 +159,83 @@ def test_accept_path(L, kind):
         for slot in range(5):
             b.release(slot)
         assert b.pages()[2] == b.pages()[1], "pages lost"
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["contiguous", "paged"])
+@pytest.mark.parametrize("cfg,q", CFGS)
+def test_accept_a_path_of_20_nodes_on_every_geometry(L, cfg, q, kind):
+    """every head size and kv width of the [layer][kv head][hs / 4][positions][4] K layout through tree_commit_kernel: the first 20 spine nodes of a
+    comb at 50 - sources 50 .. 88, destinations 50 .. 69, both across the page edge at 64 - then a step that reads every moved row"""
+    img = S.build_image(cfg, q, seed=361)
+    m = L.Transformer(img); b = batch_of(L, m, kind, 1); s = Seq(img, 0)
+    base, path = 50, list(range(0, 40, 2))
+    prefix, toks = S.prompt_tokens(cfg, base, 362), node_tokens(64, 363, m.args.vocab_size)
+    b.prefill(0, prefix, 0); s.feed(prefix)
+    b.forward_tree([(0, base, SHAPES["comb64"], toks)])
+    b.accept_path([(0, base, path)])
+    s.feed([toks[j] for j in path])
+    check_slot_rows(b, s, range(base, base + 20), f"{cfg} q{q} {kind}: after accept_path of 20 nodes")
+    check_slot_rows(b, s, [0, base - 1], f"{cfg} q{q} {kind}: below the base")
+    step(b, [s], [5], f"{cfg} q{q} {kind}: forward after accept_path of 20 nodes")
+
+
+def check_nodes(b, slot, base, nodes, am, lg, r, what):
+    """rows r .. of a forward_tree call against feed_tree's nodes: argmax, logits and the K/V rows of every layer at base + node -> the next row"""
+    for j, (want, rows) in enumerate(nodes):
+        assert int(am[r]) == ref_argmax(want), f"{what}, node {j}: argmax"
+        assert_bit_equal(lg[r], want, f"{what}, node {j}: logits")
+        for n, x in enumerate(rows):
+            assert_bit_equal(b.kv_row(slot, n % 2, n // 2, base + j), x, f"{what}, node {j}: {'kv'[n % 2]} row of layer {n // 2} at storage position {base + j}")
+        r += 1
+    return r
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["contiguous", "paged"])
+def test_drafting_again_at_the_same_base(L, kind):
+    """star64 at 70, then - no accept between - a chain7 of other tokens at 70, then a binary15: the smaller trees' gathered V chunk (64 .. 127) still
+    holds the star's rows 77 .. 133 behind its last key, where tree_gload's clamp reads; nothing of them may reach a node"""
+    cfg, q, base = "mini-llama", S.Q8_0, 70
+    img = S.build_image(cfg, q, seed=371)
+    m = L.Transformer(img); b = batch_of(L, m, kind, 1); s = Seq(img, 0)
+    prefix = S.prompt_tokens(cfg, base, 372)
+    b.prefill(0, prefix, 0); s.feed(prefix)
+    for n, shape in enumerate(("star64", "chain7", "binary15")):
+        toks = node_tokens(len(SHAPES[shape]), 373 + n, m.args.vocab_size)
+        am, lg = b.forward_tree([(0, base, SHAPES[shape], toks)], logits=True)
+        assert check_nodes(b, 0, base, feed_tree(s, SHAPES[shape], toks), am, lg, 0, f"{kind}: {shape} at {base}, pass {n}") == len(toks)
+    check_slot_rows(b, s, [0, base - 1], f"{kind}: below the base")
+
+
+WIDE_DEPTHS = [DEPTHS16[i] for i in (0, 3, 4, 8, 9)] + [248]                          # 0, 63, 64, 129, 200; 248: the last node at the last position
+
+
+@gpu
+def test_64_trees_fill_a_wide_batch(L):
+    """a wide batch at its width and the call at kRunRowsMax: 64 trees of 8 nodes (star8 and chain7 + 1 by turns), slots in shuffled order, 512 rows.
+    The slots of a depth are forks of one prompt, so one oracle a depth serves them: feed_tree feeds every tree from the base again"""
+    cfg, q = "mini-llama", S.Q8_0
+    img = S.build_image(cfg, q, seed=381)
+    m = L.Transformer(img); b = L.Batch(m, 64, wide=True)
+    V, first, orcs = m.args.vocab_size, {}, {}
+    for slot in range(64):
+        d = WIDE_DEPTHS[slot % len(WIDE_DEPTHS)]
+        if d not in first:
+            first[d], orcs[d] = slot, Seq(img, slot)
+            if d:
+                prefix = S.prompt_tokens(cfg, d, 382 + d)
+                b.prefill(slot, prefix, 0); orcs[d].feed(prefix)
+        elif d:
+            b.fork(first[d], slot, d)
+    order = [int(x) for x in np.random.default_rng(383).permutation(64)]
+    trees = [(slot, WIDE_DEPTHS[slot % len(WIDE_DEPTHS)], SHAPES[("star8", "chain7+1")[(slot // len(WIDE_DEPTHS) + slot) % 2]], node_tokens(8, 384 + slot, V)) for slot in order]
+    am, lg = b.forward_tree(trees, logits=True)
+    assert am.shape == (512,)
+    r = 0
+    for slot, d, par, toks in trees:
+        r = check_nodes(b, slot, d, feed_tree(orcs[d], par, toks), am, lg, r, f"wide: slot {slot} at {d}")
+    assert r == 512
 
 
 @gpu

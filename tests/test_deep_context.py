@@ -12,6 +12,9 @@ Oracle cost, one layer, sequential steps - each reference() prints its wall time
 mini-phi 2320 steps 13.7 s / 2.6 s: 115 s / 36 s together, against 3 x the window recipe's 4100 two-layer Gemma steps (about as many layer passes as
 mini-gemma's run here, so about 3 x 46 s / 3 x 21 s).  The whole module beside the GPU: 47 tests in 47 s, 36 s of it these four runs (charged to the
 four tests that call reference() first); every test is below 0.15 s otherwise."""
+import functools
+import types
+
 import numpy as np
 import pytest
 
@@ -19,6 +22,7 @@ import deep_rules as D
 from deep_rules import reference
 from parity_rules import assert_bit_equal, ref_argmax
 from penalty_rules import params, penalised
+from test_batch_tree import SHAPES, feed_tree, node_tokens, path_of
 
 pytestmark = pytest.mark.gpu
 
@@ -291,6 +295,89 @@ def test_penalties_over_a_full_record(L, monkeypatch):
     b.close()
 
 
+# ---------------------------------------------------------------------------------------------- i. token trees at depth
+
+TREE_KINDS = [(n, k) for n in D.NAMES for k in (("16", "wide", 64, 1024) if n in ("mini-llama", "mini-gemma") else ("16", 64))]
+CHAIN64 = [None] + list(range(63))
+SPINE = list(range(0, 64, 2))                             # comb64's spine: node 2 d at depth d
+WINDOW_COMB = 4090                                        # mini-gemma: a comb whose logical T crosses 4097 while node index and depth differ by up to 31
+
+
+def deep_trees(name):
+    """(base, shape) of the trees of slots 0, 2, 3, deepest first: a comb whose last node is stored at the geometry's last position; a chain whose T
+    crosses the 32-chunk bucket's edge (Phi: the 16-chunk one); Gemma: the comb across the window's edge"""
+    d = D.depth_of(name)
+    return [(d - 64, "comb64"), (4060 if d > 4160 else 2020, "chain64")] + ([(WINDOW_COMB, "comb64")] if D.is_gemma(name) else [])
+
+
+@functools.lru_cache(maxsize=None)
+def tree_reference(name):
+    """the trees' paths through the geometry's ONE standing oracle, fed at base + depth; the rows are put back after every tree (one layer: a row is
+    its token and position) -> per tree (slot, base, parents, tokens, feed_tree's nodes); the last entry is slot 1's star8 behind 3 positions.  A comb's
+    spine node d carries toks[base + d], its leaves the next token id; the chain carries tokens of its own."""
+    ref = reference(name)
+    V, out = ref.cfg.vocab_size, []
+    plan = [(slot, base, shape) for slot, (base, shape) in zip((0, 2, 3), deep_trees(name))] + [(1, 3, "star8")]
+    for n, (slot, base, shape) in enumerate(plan):
+        par = CHAIN64 if shape == "chain64" else SHAPES[shape]
+        tok = node_tokens(len(par), 581 + n, V)
+        if shape == "comb64":
+            tok = [int(ref.toks[base + j // 2]) if j % 2 == 0 else int(ref.toks[base + j // 2] + 1) % V for j in range(64)]
+        deepest = max(len(path_of(par, j)) for j in range(len(par)))
+        try:
+            nodes = feed_tree(types.SimpleNamespace(orc=ref.orc, n=base), par, tok)
+        finally:
+            D.restore(ref, ref.toks, range(base, base + deepest), ref.logits)
+        out.append((slot, base, par, tok, nodes))
+    return out
+
+
+@pytest.mark.parametrize("name,kind", TREE_KINDS)
+def test_token_trees_at_depth(L, monkeypatch, name, kind):
+    """forward_tree with slots 0, 2 and 3 forked from the filled context at their trees' bases beside a star8 behind 3 positions: every node's logits,
+    argmax and K/V rows at base + node against the standing oracle fed the node's path; the combs' spines replay toks, so they equal the kept logits
+    too.  Then accept_path of the combs' spines and one forward at base + 32."""
+    ref = reference(name)
+    toks, what = ref.toks, f"{name}, trees on batch {kind}"
+    trees = tree_reference(name)
+    m = filled(L, monkeypatch, ref)
+    if kind in ("16", "wide"):
+        b = L.Batch(m, 20, wide=True) if kind == "wide" else L.Batch(m, 4)
+    else:
+        b = L.Batch(m, 4, page_len=kind, n_pages=sum(pages_of(base + 64, kind) for _, base, _, _, _ in trees) + 2)
+    for slot, base, _, _, _ in trees[:-1]:
+        b.fork(L.BATCH_CTX, slot, base)
+    assert b.prefill(1, toks[:3], 0) == 3
+    am, lg = b.forward_tree([(slot, base, par, tok) for slot, base, par, tok, _ in trees], logits=True)
+    r, crossed = 0, 0
+    for slot, base, par, tok, nodes in trees:
+        comb = len(par) == 64 and par[2] == 0
+        for j, (want, rows) in enumerate(nodes):
+            w = f"{what}: the tree at {base}, node {j}"
+            assert_bit_equal(lg[r], want, f"{w}: logits")
+            assert int(am[r]) == ref_argmax(want), f"{w}: argmax"
+            assert_bit_equal(b.kv_row(slot, 0, 0, base + j), rows[0], f"{w}: key row at storage position {base + j}")
+            assert_bit_equal(b.kv_row(slot, 1, 0, base + j), rows[1], f"{w}: value row at storage position {base + j}")
+            if comb and j % 2 == 0 and base + j // 2 in ref.logits:
+                assert_bit_equal(want, ref.logits[base + j // 2], f"{w}: the fed reference against the kept logits at {base + j // 2}")
+                crossed += 1
+            r += 1
+    assert crossed >= 32, "the comb at the end lies wholly in kept positions"
+    combs = [(slot, base) for slot, base, par, _, _ in trees if len(par) == 64 and par[2] == 0]
+    b.accept_path([(slot, base, SPINE) for slot, base in combs])
+    for slot, base in combs:
+        check_rows(lambda w, l, p: b.kv_row(slot, w, l, p), ref, [p for p in range(base, base + 32) if p in ref.K], f"{what}: after accept_path at {base}")
+    at = [base + 32 for _, base in combs]
+    am, lg = b.forward([slot for slot, _ in combs], [int(toks[p]) for p in at], at, logits=True)
+    for i, p in enumerate(at):
+        want = ref.orc.forward(int(toks[p]), p).copy()         # (the oracle stands on toks: the step rewrites the row it holds)
+        if p in ref.logits:
+            assert_bit_equal(want, ref.logits[p], f"oracle: logits at {p}")
+        assert_bit_equal(lg[i], want, f"{what}: the step at {p} behind the accepted spine")
+        assert int(am[i]) == ref_argmax(want)
+    b.close()
+
+
 # ---------------------------------------------------------------------------------------------- teeth: on the oracle alone
 
 def test_teeth_llama_deep_keys_are_read():
@@ -309,3 +396,13 @@ def test_teeth_gemma_window_edges():
     assert D.moved_by(ref, 4095, 8191) > 0, "oracle: key 4095 does not move the logits at 8191"
     assert D.moved_by(ref, 255, 4352) == 0, "oracle: key 255 moves the logits at 4352 - it lies behind the window"
     assert D.moved_by(ref, 256, 4352) > 0, "oracle: key 256 does not move the logits at 4352"
+
+
+def test_teeth_gemma_window_edge_inside_the_comb():
+    """Spine node 15 of the comb at 4090 is fed at 4105 and stored at 4120: with the logical position the window's first live key is 9 (4105 - 4096),
+    with the storage position it would be 24.  Key 8 moves nothing at 4105, key 9 does - so the comb's rows tell the two apart."""
+    ref = reference("mini-gemma")
+    q = WINDOW_COMB + 15
+    assert q in ref.logits
+    assert D.moved_by(ref, q - 4097, q) == 0, f"oracle: key {q - 4097} moves the logits at {q} - it lies behind the window"
+    assert D.moved_by(ref, q - 4096, q) > 0, f"oracle: key {q - 4096} does not move the logits at {q}"
